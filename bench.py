@@ -1,6 +1,6 @@
 """bench.py — audio samples/s of the FastPitch -> HiFi-GAN hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--tokens 64]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--tokens 64] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1]): FastPitch+HiFi-GAN, synthetic 64-phoneme x batch 32
 per GPU, fp32, synthetic weights (ttsamd.synth, seed 0), forced durations dur_tgt in [2,12]
@@ -12,6 +12,8 @@ HBM.  N>1: one process per GPU — under torch.distributed.run, or started by th
 PER RANK (weak scaling), every rank's lengths all-gathered in the step's one host sync and the packed
 audio fanned in to rank 0 every step.  Prints ONE JSON line on rank 0; at N=1 the line also carries
 `configs`: the batch-1 and batch-8 sub-results of the same step function.
+--dump-outputs DIR: what the last timed step returned (mel, dec_lens, wave of rank 0) as DIR/<name>.npy, so that two
+builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -447,6 +449,44 @@ def _median(xs):
     return None if n == 0 else (xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2]))
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def step_outputs(mel, dec_lens, wave, hop):
+    """What a caller of the timed step receives, on the host and independent of the engines' row padding: mel [B, 80, T] and
+    wave [B, T * hop] cut to T = max(dec_lens) and zeroed past each utterance's end, dec_lens [B]."""
+    lens = dec_lens.cpu().numpy().astype(np.int64)
+    t = int(lens.max()) if lens.size else 0
+    mel_h = mel[:, :, :t].float().cpu().numpy().copy()
+    wave_h = wave[:, :t * hop].float().cpu().numpy().copy()
+    for b, n in enumerate(lens):
+        mel_h[b, :, n:] = 0.0
+        wave_h[b, n * hop:] = 0.0
+    return {'mel': mel_h, 'dec_lens': lens, 'wave': wave_h}
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """Write `arrays` (name -> array, first axis = utterance) as out_dir/<name>.npy: integers as float64, the rest as float32.
+    Above `cap` bytes in all, the same seeded sample of utterances from every array, their indices in rows.npy.  Returns the
+    file names."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(a, dtype=np.float64 if np.issubdtype(a.dtype, np.integer) else np.float32)
+            for k, a in arrays.items()}
+    n = min(a.shape[0] for a in arrs.values())
+    per_row = sum(a.nbytes // max(1, a.shape[0]) for a in arrs.values())
+    keep = min(n, (cap - 8 * n) // max(1, per_row))
+    rows_path = os.path.join(out_dir, 'rows.npy')
+    if keep < n:
+        rows = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs['rows'] = rows.astype(np.float64)
+    elif os.path.exists(rows_path):
+        os.remove(rows_path)                               # a sample list of an earlier, larger dump would not fit these files
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return sorted(k + '.npy' for k in arrs)
+
+
 BF16_RIDGE_FLOP_PER_BYTE = 2500.0e12 / 8000.0e9      # 312.5: above it a bf16 launch sequence is bound by the matrix pipe, below by HBM
 
 
@@ -495,7 +535,12 @@ def main():
     ap.add_argument('--precision', default='f32', choices=['f32', 'bf16', 'bf16x3'],
                     help='MFMA operand precision of the conv/linear GEMMs (f32 = BASELINE config 2; bf16 = config 3; '
                          'bf16x3 = split bf16, fp32-class accuracy)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (mel, dec_lens, wave; rank 0) as DIR/<name>.npy, '
+                         f'float32 / float64, at most {DUMP_CAP_BYTES >> 20} MB in all (a seeded sample of utterances beyond that)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -621,13 +666,13 @@ def main():
         if world == 1:
             if pipe is not None:
                 def step():
-                    _, dec_lens, wave = pipe.submit(ids_, dur_tgt=dur_)
-                    return wave, dec_lens
+                    mel, dec_lens, wave = pipe.submit(ids_, dur_tgt=dur_)
+                    return wave, dec_lens, mel
                 return step
 
             def step():
                 mel, dec_lens, *_ = fp.infer(ids_, dur_tgt=dur_)
-                return hg.forward(mel, dec_lens), dec_lens
+                return hg.forward(mel, dec_lens), dec_lens, mel
             return step
         state = {}
 
@@ -648,10 +693,10 @@ def main():
 
         def step():
             if pipe is not None:
-                _, dec_lens, wave = pipe.submit(ids_, vocode=vocode, dur_tgt=dur_, lens_hook=hook)
-                return wave, dec_lens
+                mel, dec_lens, wave = pipe.submit(ids_, vocode=vocode, dur_tgt=dur_, lens_hook=hook)
+                return wave, dec_lens, mel
             mel, dec_lens, *_ = fp.infer(ids_, dur_tgt=dur_, lens_hook=hook)
-            return vocode(mel, dec_lens), dec_lens
+            return vocode(mel, dec_lens), dec_lens, mel
         return step
 
     step = make_step(ids, dur)
@@ -676,10 +721,13 @@ def main():
     lib = L.load()
     import ctypes
     lib.ttsamd_profile_enable(0 if os.environ.get("TTSAMD_BENCH_NO_EVENTS") else 1)
-    elapsed, (wave, dec_lens), per_step = _time_steps(step, args.steps, sync, barrier, tick=step.tick)
+    elapsed, (wave, dec_lens, mel), per_step = _time_steps(step, args.steps, sync, barrier, tick=step.tick)
     prof = (ctypes.c_double * 3)()
     L.check(lib.ttsamd_profile_read(prof), 'profile_read')
     lib.ttsamd_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        # right after the timed steps: the sub-results below reuse the engines' workspaces
+        dump_outputs(args.dump_outputs, step_outputs(mel, dec_lens, wave, hop))
 
     frames = int(dec_lens.sum().item())
     samples = frames * hop * args.steps
@@ -739,7 +787,7 @@ def main():
                 st()
             sync()
             n = max(args.steps, 20)
-            el, (_, dl), ps = _time_steps(st, n, sync, tick=st.tick)
+            el, (_, dl, _), ps = _time_steps(st, n, sync, tick=st.tick)
         finally:
             set_precision(args.precision)
         fr = int(dl.sum().item())

@@ -52,3 +52,44 @@ def test_median_and_gpu_count_helpers(tmp_path, monkeypatch):
     assert b._count_gpus() == 2
     monkeypatch.setenv('HIP_VISIBLE_DEVICES', '')
     assert b._count_gpus() == 0
+
+
+def test_dump_outputs_cut_zeroed_and_capped(tmp_path):
+    """--dump-outputs: the step's outputs cut to max(dec_lens) and zeroed past each utterance's end (independent of the engines'
+    row padding), float32 / float64 files; above the cap the same seeded utterances of every array, listed in rows.npy."""
+    import numpy as np
+    import torch
+    b = _bench()
+    hop = 4
+    lens = torch.tensor([3, 5, 2], dtype=torch.int64)
+    mel = torch.randn(3, 2, 8)
+    wave = torch.randn(3, 8 * hop)
+    got = b.step_outputs(mel, lens, wave, hop)
+    assert got['mel'].shape == (3, 2, 5) and got['wave'].shape == (3, 5 * hop)
+    for i, n in enumerate(lens.tolist()):
+        assert np.array_equal(got['mel'][i, :, :n], mel[i, :, :n].numpy()) and not got['mel'][i, :, n:].any()
+        assert np.array_equal(got['wave'][i, :n * hop], wave[i, :n * hop].numpy()) and not got['wave'][i, n * hop:].any()
+    files = b.dump_outputs(str(tmp_path / 'all'), got)
+    assert files == ['dec_lens.npy', 'mel.npy', 'wave.npy']
+    lo = np.load(tmp_path / 'all' / 'dec_lens.npy')
+    assert lo.dtype == np.float64 and lo.tolist() == [3.0, 5.0, 2.0]
+    assert np.load(tmp_path / 'all' / 'wave.npy').dtype == np.float32
+    big = {'wave': np.arange(100 * 1000, dtype=np.float32).reshape(100, 1000), 'dec_lens': np.arange(100)}
+    cap = 30 * (4000 + 8) + 800
+    files = b.dump_outputs(str(tmp_path / 'cap'), big, cap=cap)
+    assert 'rows.npy' in files and sum(os.path.getsize(tmp_path / 'cap' / f) for f in files) <= cap + 128 * len(files)
+    rows = np.load(tmp_path / 'cap' / 'rows.npy').astype(np.int64)
+    assert len(rows) == 30 and np.array_equal(rows, np.sort(rows))
+    assert np.array_equal(np.load(tmp_path / 'cap' / 'dec_lens.npy'), rows.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / 'cap' / 'wave.npy'), big['wave'][rows])
+    assert b.dump_outputs(str(tmp_path / 'cap2'), big, cap=cap) == files
+    assert np.array_equal(np.load(tmp_path / 'cap2' / 'rows.npy'), np.load(tmp_path / 'cap' / 'rows.npy'))   # seeded
+    b.dump_outputs(str(tmp_path / 'cap'), {'dec_lens': np.arange(3)}, cap=cap)
+    assert not os.path.exists(tmp_path / 'cap' / 'rows.npy')            # no stale sample list beside a full dump
+
+
+def test_bench_rejects_zero_steps():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '0'], capture_output=True, text=True)
+    assert r.returncode == 2 and '--steps' in r.stderr
