@@ -526,6 +526,7 @@ int64_t ttsamd_resblock_pair_packed_floats(int32_t channels, int32_t k, int32_t 
     if (channels < 1 || k < 1) return 0;
     const int64_t n = 2 * (int64_t)channels * k * channels;
     const int nwino = (variant == 4 ? 1 : (variant == 5 ? 2 : 0));
+    if (variant == 6) return n + ((k == 3 || k == 7 || k == 11) ? 2 * (int64_t)channels * wino4_groups(k) * channels : 0);   // both convs as F(4,3) groups
     return n + ((k == 3 || k == 7 || k == 11) ? nwino * (int64_t)channels * wino2_groups(k) * channels : 0);
 }
 
@@ -566,10 +567,21 @@ int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const fl
         }
         rc = launch_fused_pair2(channels, x, y, packed, b1, packed + n, b2, k, dil, lens, len_mul, L, batch, mode, div, slope,
                                 variant == 3 ? 1 : 2, s, w2w, w1w);
+    } else if (variant == 6) {
+        // C = 32, both convs on Winograd F(4,3) (resblock_pair4.hip): the group filters behind the direct packings
+        TTS_REQUIRE(channels == 32 && (k == 3 || k == 7 || k == 11), "resblock_pair: variant 6 is built for C = 32, k = 3 / 7 / 11");
+        const int64_t nw4 = (int64_t)channels * wino4_groups(k) * channels;
+        for (int i = 0; i < 2; ++i) {
+            hipLaunchKernelGGL(pack_wino4_weight_kernel, dim3((unsigned)((nw4 + 255) / 256)), dim3(256), 0, s, i == 0 ? w1 : w2, channels,
+                               channels, k, channels, packed + 2 * n + i * nw4);
+            TTS_CHECK_HIP(hipGetLastError());
+        }
+        rc = launch_fused_pair4(channels, x, y, packed + 2 * n, b1, packed + 2 * n + nw4, b2, k, dil, lens, len_mul, L, batch, mode, div,
+                                slope, s);
     } else if (variant == -1) {
         rc = 0;                                    // the two weight re-layout launches only (tools/fused_pair_bench.py subtracts them)
     } else {
-        set_error("resblock_pair: variant %d (1: first generation, 2 / 3: second generation with 256- / 128-column blocks, 4 / 5: 256 columns + Winograd phase B / both phases)", variant);
+        set_error("resblock_pair: variant %d (1: first generation, 2 / 3: second generation with 256- / 128-column blocks, 4 / 5: 256 columns + Winograd phase B / both phases, 6: C = 32 with both phases on Winograd F(4,3))", variant);
         rc = TTSAMD_EINVAL;
     }
     prof_end(s);

@@ -81,6 +81,7 @@ inline hipError_t lds_opt_in(const void* fn, int bytes, std::atomic<uint64_t>& d
     X(FUSED2_MASK, 1, 0, 0x1ff)   /* which (C, k) pairs it takes: bit 3 ci + ki (default 00f) */            \
     X(FUSED2_MASK_N1, 1, 0, 0x1ff) /* ... with 128-column direct-arithmetic blocks (default 000) */         \
     X(FUSED2_WB, 0, 0, 2)         /* its Winograd phases: 0 none, 1 phase B, 2 both (default) */            \
+    X(PAIR4, 0, 0, 1)             /* C = 32 fused pairs with both convs on Winograd F(4,3) (resblock_pair4) off / on */ \
     X(CONVT, 0, 0, 1)             /* all-phase transposed conv (convt_mfma.hip) off / on */                 \
     X(BFO, 0, 0, 1)               /* bf16 modes: 0 = the round-2 bf16 conv engine instead of the octet engine */ \
     X(BFO_CHAIN, 0, 0, 1)         /* whole k = 3 ResBlock in one launch (octet engines) */                  \
@@ -199,6 +200,12 @@ int32_t launch_fused_pair2(int32_t channels, const float* x, float* y, const flo
                            const float* w1_wino = nullptr);
 // (w2_wino: conv 2 as Winograd F(2,3) groups -- pack_wino2_weight; C = 32 / 64, ntw = 2: phase B of the pair runs on them; w1_wino:
 // conv 1 likewise -> phase A too)
+// The C = 32 pair with both convs on Winograd F(4,3) (resblock_pair4.hip): k = 3 / 7 / 11, dilation 1 / 3 / 5; the weights are the
+// F(4,3) group filters of both convs (pack_wino4_weight)
+bool fused_pair4_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
+int32_t launch_fused_pair4(int32_t channels, const float* x, float* y, const float* w1_wino4, const float* b1, const float* w2_wino4,
+                           const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
+                           int32_t mode, float div, float slope, hipStream_t stream);
 // Winograd F(2,3) path of the k = 3, dilation-1 convs (conv_wino.hip): routing test, launcher, host-side filter transform + packing
 int wino_route(const ConvParams& p);       // 0: direct kernel, 1: conv1d_wino_f32, 2: conv1d_wino2_f32, 3: conv1d_wino4_f32 (conv_wino.hip)
 int32_t launch_wino(const ConvParams& p, hipStream_t stream);

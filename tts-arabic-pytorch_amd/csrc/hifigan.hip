@@ -22,6 +22,12 @@ constexpr unsigned kFused2Mask = 0x00F;       // C = 32: k = 3 / 7 / 11; C = 64:
                                               // (06f) / 55.00 (05f) / 54.81 ms (04f); then with k = 3 on F(4,3) too: 54.68 (04f) / 55.11 (047: C = 64 k = 3
                                               // un-fused) / 54.59 (007) / 54.10 ms (00f: C = 128 k = 3 un-fused).  Round 5 on F(2,3): C = 64 k = 11 fused 61.93 vs
                                               // 62.45; C = 128 k = 3 fused 63.90 vs 64.06
+// Of those, the C = 32 k = 7 / 11 pairs run with both convs on Winograd F(4,3) (resblock_pair4.hip: 16 / 23 products per output quad
+// against 20 / 32 on F(2,3)) when the pair takes the 256-column kernel with both phases on Winograd; TTSAMD_PAIR4=0 keeps resblock_pair2.
+// One-stream kernel table at batch 32 (profiles/r7/NOTES.md): k = 11 3.61 -> 2.75 ms per step, k = 7 2.43 -> 2.12, but k = 3 1.22 -> 1.32
+// (memory-bound: 6 products per quad do not pay for the larger window and the extra LDS traffic), so k = 3 stays on resblock_pair2.
+// C = 64 k = 3 stays there too (resblock_pair4 is built for C = 32 only: MT = 1, one 32-row tile per wave).
+constexpr int kPair4MinK = 7;
 constexpr unsigned kFused2MaskN1 = 0x000;     // 128-column blocks (the direct-arithmetic kernels only): none by default
 constexpr int64_t kFused2SmallColumns = 2 * 256 * 252;   // batch x positions under which a stage counts as a small problem
 
@@ -30,7 +36,7 @@ struct ConvW {
     int64_t w16_off = 0, w_n = 0;  // bf16 planes (hi, lo) in the uint16 blob; packed element count
     int64_t wo_off = -1;           // bf16 octet engine (bfo.hpp): [Cin/16][K][2][CoutP][8] in the same uint16 blob (-1: not packed)
     int64_t wo3_off = -1;          // its split-bf16 mode (bfo3.hpp): [Cin/16][K][2][CoutP][hi 8 | lo 8]
-    int64_t ww4_off = -1;          // ... and as Winograd F(4,3) groups (conv_wino4.hip; the un-fused convs: Cout >= 128)
+    int64_t ww4_off = -1;          // ... and as Winograd F(4,3) groups (conv_wino4.hip: the un-fused convs, Cout >= 64; resblock_pair4.hip: the C = 32 pairs)
     int64_t ww_off = -1;           // k = 3 / 7 / 11: Winograd F(2,3) (sub-)filters + single taps as an NG-tap conv in the fp32 blob (conv_wino2.hip; -1: none)
     int cin = 0, cout = 0, k = 0;
 };
@@ -85,6 +91,7 @@ static bool use_branch_streams(const HifiGan* h, int32_t B, int32_t T) {
 struct Fused2Switches {
     bool on = true, mask_forced = false, small_on = false;
     bool wino_b = true, wino_a = true;   // phase B / phase A + B of the C = 32 / 64 pairs as Winograd F(2,3) (TTSAMD_FUSED2_WB=0: both direct, =1: phase B only)
+    bool pair4 = true;                   // ... the C = 32 ones with both phases on Winograd as F(4,3) instead (TTSAMD_PAIR4=0: resblock_pair2)
     unsigned mask = kFused2Mask, mask_n1 = kFused2MaskN1;
 };
 static bool parse_hex_mask(const char* txt, unsigned& out) {
@@ -107,6 +114,8 @@ static int32_t read_fused2_switches(Fused2Switches& sw) {
     const char* wb = opt_str(OPT_FUSED2_WB);
     sw.wino_b = !(wb && wb[0] == '0');
     sw.wino_a = sw.wino_b && !(wb && wb[0] == '1');
+    const char* p4 = opt_str(OPT_PAIR4);
+    sw.pair4 = !(p4 && p4[0] == '0');
     const char* se = exp_env("TTSAMD_FUSED2_SMALL");
     sw.small_on = se && se[0] == '1';
     return 0;
@@ -221,7 +230,7 @@ static int32_t add_conv(const TensorMap& tm, const std::string& base, int cin, i
         cw.ww_off = (int64_t)blob.size();
         blob.resize(blob.size() + (size_t)cin * wino2_groups(k) * cout_padded(cout));
         pack_wino2_weight(w.data(), cout, cin, k, blob.data() + cw.ww_off);
-        if (cout >= 64) {             // the un-fused ResBlock convs (stages with 64 / 128 / 256 channels): F(4,3) decomposition
+        if (cout >= 64 || (cout == 32 && cin == 32 && k >= kPair4MinK)) {   // the un-fused ResBlock convs (Cout >= 64) and the routed C = 32 pairs: F(4,3)
             blob.resize(align_up((int64_t)blob.size(), 64));
             cw.ww4_off = (int64_t)blob.size();
             blob.resize(blob.size() + (size_t)cin * wino4_groups(k) * cout_padded(cout));
@@ -473,7 +482,7 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
         p.w = h->dev + cw.w_off; p.bias = h->dev + cw.b_off;
         p.w_bf16 = h->dev16 + cw.w16_off; p.precision = default_precision();
         p.w_wino = cw.ww_off >= 0 ? h->dev + cw.ww_off : nullptr;
-        p.w_wino4 = cw.ww4_off >= 0 ? h->dev + cw.ww4_off : nullptr;
+        p.w_wino4 = (cw.ww4_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww4_off : nullptr;   // (C = 32: the fused pair's filters only)
         p.y = y; p.y_bs = (int64_t)cw.cout * L; p.y_cs = L; p.y_ts = 1;
         p.res = res; p.r_bs = (int64_t)cw.cout * L; p.r_cs = L;
         p.len_in_mul = mul; p.len_out_mul = mul; p.Lin = L; p.Nout = L;
@@ -675,12 +684,18 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                     const ConvW &w1 = h->c1[li], &w2 = h->c2[li];
                     const bool square = w1.cin == w1.cout && w2.cin == w1.cin && w2.cout == w1.cin && w1.k == w2.k;
                     const int ntw2 = (fused_ok && square) ? fused2_choice(f2sw, w1.cin, w1.k, d, L, src, dst, (int64_t)B * L) : 0;
+                    // the F(2,3) pair with both phases on Winograd -> its F(4,3) successor where it is built (C = 32)
+                    const bool f43 = ntw2 == 2 && f2sw.pair4 && f2sw.wino_a && w1.k >= kPair4MinK && w1.ww4_off >= 0 && w2.ww4_off >= 0 &&
+                                     fused_pair4_supported(w1.cin, w1.k, d, L, src, dst);
                     if (ntw2 != 0 || (fused_ok && square && fused_pair_supported(w1.cin, w1.k, d, L, src, dst))) {
                         const int mode = !last ? 0 : (cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2)));
                         if (multi && last && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
                         const double fl = 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * mul;
                         if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        const int32_t frc = ntw2 != 0
+                        const int32_t frc = f43
+                            ? launch_fused_pair4(w1.cin, src, dst, h->dev + w1.ww4_off, h->dev + w1.b_off, h->dev + w2.ww4_off,
+                                                 h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, st)
+                            : ntw2 != 0
                             ? launch_fused_pair2(w1.cin, src, dst, h->dev + w1.w_off, h->dev + w1.b_off, h->dev + w2.w_off,
                                                  h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, ntw2, st,
                                                  (f2sw.wino_b && w2.ww_off >= 0) ? h->dev + w2.ww_off : nullptr,
