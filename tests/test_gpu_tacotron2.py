@@ -280,7 +280,6 @@ def test_tacotron2_persistent_decoder_matches_oracle(dev, monkeypatch, num_speak
     mel_ref, lens_ref, al_ref = T.tacotron2_infer(sd, cfg, tok, sids, lens, max_step=steps, seed=seed)
     eng = Tacotron2Engine(sd, cfg, device=dev)
     ttsopt.set('TTSAMD_TACO_PERSISTENT', mode)
-    monkeypatch.setenv('TTSAMD_TACO_DEBUG', '1')
     mel, mel_lens, al = eng.infer(tok, sids, lens, max_step=steps, dropout_seed=seed)
     assert mel_lens.cpu().tolist() == np.asarray(lens_ref).tolist() == [steps] * B
     assert maxabs(al, al_ref) < ALIGN_TOL

@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of environment switches inside the bench step, ALTERNATED (box drift and run-to-run noise are 0.2-0.5 % of a step, so a
-# single pair decides nothing):   gpurun -- 'bash tools/ab_env.sh "TTSAMD_XCD_W=0" "TTSAMD_COMPACT=0"'
+# single pair decides nothing), from the repository root:   bash tools/ab_env.sh "TTSAMD_XCD_W=0" "TTSAMD_DEEP_SPLITK=0"
 #   AB_ROUNDS=5 (default 3) rounds of: baseline, then every variant; prints every run and min / median / max per variant.
 #   AB_ARGS="--precision bf16x3" adds bench.py arguments;  AB_STEPS (20)
 R=${AB_ROUNDS:-3}

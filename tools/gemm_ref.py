@@ -1,6 +1,6 @@
 """Vendor-library calibration: fp32 torch.mm (rocBLAS / hipBLASLt) on the GEMMs that are arithmetically equal to
 the HiFi-GAN ResBlock convs (M = C_out, K = C_in * taps, N = batch * positions) — no im2col, operands already in
-GEMM layout.  Prints TFLOP/s per shape next to the conv kernel's figure from tools/conv_bench (PROD=1)."""
+GEMM layout.  Prints TFLOP/s per shape, to be set against the conv kernels' figures."""
 import time
 
 import torch

@@ -192,9 +192,10 @@ int opt_find(const char* name) {
 }
 }  // namespace
 
-const char* opt_str(Opt o) {
+int64_t opt_int(Opt o, int64_t unset) {
     opt_init();
-    return g_opt[o].load(std::memory_order_acquire);
+    const char* v = g_opt[o].load(std::memory_order_acquire);     // validated: parses whole and in range
+    return v ? (int64_t)std::strtoll(v, nullptr, kOpts[o].kind == 1 ? 16 : 10) : unset;
 }
 
 }  // namespace ttsamd

@@ -247,15 +247,11 @@ static int32_t bfo_launch_conv_cfg(const BfoConvParams& p_in, hipStream_t stream
     const int64_t blocks = (int64_t)grid.x * grid.y * grid.z;
     const int n_slabs = ((p.Cin + 15) / 16 + G::SH - 1) / G::SH;
     const int64_t per = (int64_t)p.batch * p.Cout * p.Lin;
-    const char* ske = opt_str(OPT_BFO_SPLITK);              // 0 disables (A/B and parity runs)
-    const char* mse = exp_env("TTSAMD_BFO_SPLITK_MIN_SLABS");
-    const int min_slabs = mse ? atoi(mse) : 4;
-    const char* mbe = exp_env("TTSAMD_BFO_SPLITK_BLOCKS");
-    const int max_blocks = mbe ? atoi(mbe) : 256;   // under one block per CU
-    if (p.splitk_ws && blocks < max_blocks && n_slabs >= min_slabs && !(ske && ske[0] == '0')) {
-        const char* mk = exp_env("TTSAMD_BFO_SPLITK_MAX");
+    constexpr int min_slabs = 4, max_blocks = 256, max_ks = 4;   // max_blocks: under one block per CU
+    const bool splitk_on = opt_int(OPT_BFO_SPLITK, 1) != 0;    // 0 disables (A/B and parity runs)
+    if (p.splitk_ws && blocks < max_blocks && n_slabs >= min_slabs && splitk_on) {
         int64_t ks = std::min<int64_t>((256 + blocks - 1) / blocks, n_slabs);
-        ks = std::min<int64_t>(ks, mk ? atoi(mk) : 4);
+        ks = std::min<int64_t>(ks, max_ks);
         ks = std::min<int64_t>(ks, p.splitk_floats / std::max<int64_t>(per, 1));
         if (ks >= 2) p.ksplit = (int)ks;
     }
@@ -286,7 +282,7 @@ static int32_t bfo_launch_conv_k(const BfoConvParams& p, hipStream_t stream) {
     const int64_t blocks8 = (int64_t)((p.Lin + 255) / 256) * ((p.Cout + 127) / 128) * p.batch;
     // (a grid of 256-column tiles under one block per CU -- FastPitch's 1536 -> 384 conv at batch 32 is 192 blocks -- takes the 64-column
     // tiles too: bf16 one-stream step 11.89 -> 11.57 ms, two-stream unchanged; round 3 had the threshold at 48 blocks)
-    static const int64_t narrow_blocks = [] { const char* e = exp_env("TTSAMD_BFO_NARROW_BLOCKS"); return e ? (int64_t)atoi(e) : (int64_t)256; }();
+    constexpr int64_t narrow_blocks = 256;
     const bool narrow = p.Cout >= 128 && (p.Lin <= 96 || blocks8 < narrow_blocks);
     if (p.y_f32) {
         if (narrow) return bfo_launch_conv_cfg<K, 4, 1, 2, true>(p, stream);

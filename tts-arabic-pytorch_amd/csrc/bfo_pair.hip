@@ -25,7 +25,7 @@
 namespace ttsamd {
 
 // 32-column tiles per wave: 8 (256 columns), or 4 -- half the window, 3-4 blocks per CU -- for k = 3 at C <= 64 (152 -> 137 us at
-// C = 64, 118 -> 111 at C = 32 with the deeper weight ring below; no change at C = 128: tools/bfo_pair_bench) and for small
+// C = 64, 118 -> 111 at C = 32 with the deeper weight ring below; no change at C = 128) and for small
 // batches, where 256-column tiles leave CUs without a block (batch 1: 115 blocks at C = 128)
 template <int K, int C>
 constexpr int bfo_pair_default_nt() { return (K == 3 && C <= 64) ? 4 : 8; }
@@ -66,16 +66,6 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
     int len = L;
     if (p.lens) len = min(len, (int)p.lens[b] * p.len_mul);
     if (q0 >= len) return;
-#ifdef BFO_TIMING
-    const unsigned long long wc0 = wall_clock64();
-    unsigned long long tst[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) tst[i] = 0;
-    tst[0] = clock64();
-#define BFO_STAMP(i) tst[i] = clock64();
-#else
-#define BFO_STAMP(i)
-#endif
     const int dil = p.dil;
     const int W1 = G::NCOLS + (K - 1) * dil;                // staged columns actually used
     const int x0 = q0 - H - (K - 1) * dil / 2;              // position of staged column 0
@@ -99,7 +89,6 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
         }
     }
     __syncthreads();
-    BFO_STAMP(1)
 
     const int wv = (kk * C + 32 * wm + l31) * 16;           // this lane's A fragment inside a (h, tap) step
     const int cw = wn * (NT * 32) + l31;                    // this lane's column in tile 0
@@ -118,7 +107,6 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
     }
     bfo_mma<K, G::PH, NT>(acc, bfo_rsrc(p.w1, (unsigned)NH * K * 2 * C * 16), wv, 2 * C * 16, sB, NH, 2 * WS, dil);
 
-    BFO_STAMP(2)
     // residual (= the activated input at the output positions): 8 bytes per (tile, octet) in the C layout
     int vo[NT];
 #pragma unroll
@@ -138,9 +126,7 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
                 rv[j][g] = *reinterpret_cast<const bfo_i2*>(reinterpret_cast<const char*>(Xs + (4 * wm + g) * WS + rc0 + 32 * j) + 8 * kk);
     }
 
-    BFO_STAMP(6)
     __syncthreads();                                        // every wave is done with the window
-    BFO_STAMP(7)
     {
         const float ms = p.mid_slope;
 #pragma unroll
@@ -155,9 +141,7 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
             }
         }
     }
-    BFO_STAMP(8)
     __syncthreads();
-    BFO_STAMP(3)
 
     // ---- phase B: accumulators start from b2 + x (x = a >= 0 ? a : a / in_slope)
     {
@@ -176,10 +160,8 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
                 acc[j][4 * g + 3] = bv[4 * g + 3] + bfo_unrelu(a3, inv);
             }
     }
-    BFO_STAMP(9)
     bfo_mma<K, G::PH, NT>(acc, bfo_rsrc(p.w2, (unsigned)NH * K * 2 * C * 16), wv, 2 * C * 16, sB, NH, 2 * WS, 1);
 
-    BFO_STAMP(4)
     // ---- epilogue
     const bfo_i4 yrs = bfo_rsrc((char*)p.y + (int64_t)b * NO * L * 16, (unsigned)NO * L * 16);
     const float os = p.out_slope;
@@ -206,17 +188,6 @@ __global__ __launch_bounds__(256, (NT_ <= 4 ? 3 : 2)) void bfo_resblock_pair(con
                 bfo_st8(bfo_act4(acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3], os, -1), yrs, vo[j],
                         (4 * wm + g) * L * 16, 0);
     }
-#ifdef BFO_TIMING
-    tst[5] = clock64();
-    if (p.timing && tid == 0) {
-        unsigned long long* tp = p.timing + ((size_t)blockIdx.z * gridDim.x + blockIdx.x) * 16;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) tp[i] = tst[i];
-        tp[12] = wall_clock64();
-        tp[13] = wc0;
-    }
-#endif
-#undef BFO_STAMP
 }
 
 template <int K, int C, int NT>
@@ -239,8 +210,8 @@ static int32_t bfo_launch_pair_k(const BfoPairParams& p, hipStream_t stream) {
         // fewer than 1.5 blocks per CU with 256-column tiles: halve them (TTSAMD_BFO_SMALL_TILES=0/1 forces either)
         using G8 = BfoPairGeo<K, C, 8>;
         const int64_t blocks8 = (int64_t)((p.L + G8::TS - 1) / G8::TS) * p.batch;
-        const char* e = opt_str(OPT_BFO_SMALL_TILES);
-        const bool small = e ? e[0] == '1' : blocks8 < 384;
+        const int64_t e = opt_int(OPT_BFO_SMALL_TILES, -1);
+        const bool small = e >= 0 ? e == 1 : blocks8 < 384;
         if (small) return bfo_launch_pair_nt<K, C, 4>(p, stream);
     }
     return bfo_launch_pair_nt<K, C, NT0>(p, stream);

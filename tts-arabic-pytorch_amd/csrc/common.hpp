@@ -40,18 +40,6 @@ void set_error(const char* fmt, ...);
 
 inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
-// Switches of CLOSED experiments (tile orders, split-K thresholds, block-count sweeps: profiles/r2..r4) are read only by a library
-// built with `make EXTRA=-DTTS_EXPERIMENT` (tools/ A/B scripts); the product library ignores them and runs the measured defaults.
-// What stays a run-time switch routes between kernels that BOTH ship and is listed in INTEGRATION.md.
-inline const char* exp_env(const char* name) {
-#ifdef TTS_EXPERIMENT
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device).  `done` is the instantiation's bitmask of
 // devices already opted in; two host threads racing on a first launch both set the attribute (idempotent), devices >= 64 set it on
 // every launch.  (Rounds 2-4 kept an unsynchronised bool[16] indexed by device & 15: a data race, and device 16 aliased device 0.)
@@ -104,8 +92,8 @@ enum Opt : int {
 #undef TTS_OPT_ENUM
     OPT_COUNT
 };
-// current value as text (what the environment variable would hold), nullptr = unset (the documented default applies)
-const char* opt_str(Opt o);
+// current value as a number (parsed with the table's base), or `unset` when the option is not set (the documented default applies)
+int64_t opt_int(Opt o, int64_t unset);
 
 // Bump allocator over the caller-provided workspace (no hidden hipMalloc on hot calls).
 struct Arena {
@@ -168,10 +156,10 @@ struct ConvParams {
     float pack_slope;         // ... after applying leaky-relu with this slope
     int32_t x_packed;         // read x in that layout (x_cs = positions per row; in_slope is ignored)
     int32_t xcd_w;            // set by the launcher: gcd(n_co_tiles, 8) co-tile classes, one per XCD residue (weight locality; 0 = off)
-    int32_t tile_major;       // set by the launcher: blockIdx.x = utterance slot, blockIdx.z = time tile (ragged batches)
+    int32_t tile_major;       // 1: blockIdx.x = utterance slot, blockIdx.z = time tile (ragged batches); the launchers pass 0
     int32_t compact;          // set by the launcher (ragged batches): the (utterance, time tile) pair of a block is looked up in the
                               // utterance-major list of LIVE tiles (live_tile below), so every dead block sits at the end of the grid
-    unsigned long long* timing;   // tools/conv_bench -DTTS_TIMING only: [blocks][8] clock samples (nullptr otherwise)
+    unsigned long long* timing;   // unused (nullptr); kept so the kernel argument layout is unchanged
 };
 constexpr int64_t kSplitKFloats = 4 << 20;   // 16 MB covers every case the launchers pick (direct kernel: < 320 blocks, ~640 blocks wanted; conv_wino4.hip: four C-in slices of a 1 x 256 x 3584 launch = 3.7 M floats)
 constexpr int64_t kSplitKFloatsFp = 8 << 20; // FastPitch: 32 MB, the deep conv-FF conv (1536 -> 384) splits K at batch 4..13 too
@@ -179,7 +167,6 @@ constexpr int64_t kSplitKFloatsFp = 8 << 20; // FastPitch: 32 MB, the deep conv-
 void conv_log(const char* kind, int K, int cin, int cout, int nout, int batch, int has_res, int mode, int len_mul, int ragged,
               int n_phase);
 // block order of a launch (conv_mfma.hip)
-bool tile_major_order(const ConvParams& p, unsigned n_tiles);
 bool compact_order(const void* lens, int batch);
 // Launches the kernel; returns 0 or a negative code.
 int32_t launch_conv(const ConvParams& p, hipStream_t stream);
@@ -238,8 +225,8 @@ int32_t default_precision();
 // (tiles past the utterance's own length) behind every utterance; a dead block still needs a free slot (LDS, four
 // waves) to launch and exit, and the in-order workgroup dispatcher cannot place the live block queued behind it: with
 // utterances 16 % shorter than the padded length on average a stand-alone C = 128 k = 11 launch runs at 124.5 TFLOP/s
-// against 137 on a uniform batch (tools/conv_bench RAGGED=auto TTSAMD_DIRECT=0).  Instead, block number `lin` of the
-// utterance-major order takes the lin-th LIVE (utterance, tile) pair and all dead blocks sit at the end of the grid
+// against 137 on a uniform batch.  Instead, block number `lin` of the utterance-major order takes the lin-th LIVE
+// (utterance, tile) pair and all dead blocks sit at the end of the grid
 // (133.8 TFLOP/s on that launch; C = 256 k = 11 119 -> 130, C = 64 k = 11 120 -> 126): every wave loads the lengths
 // (64 per pass), takes a wave prefix sum of the tile counts and finds its utterance with one ballot -- a few dozen
 // cycles next to the length load the kernel does anyway.  Returns false past the last live pair.

@@ -47,7 +47,7 @@ template <int K, int NT_BLK, int CO_BLK>
 struct Geo {
     // octets (8 input channels) per chunk.  k = 3 on the 128 x 128 tile takes two: a one-octet chunk is 48 MFMAs per wave (1.3 us)
     // between barriers; two halve the barriers and still leave two blocks per CU (FastPitch's 384 -> 1536 conv 121 -> 128 TFLOP/s,
-    // HiFi-GAN C = 128 k = 3 106 -> 108; the smaller k = 3 tiles lose 2-3 % with it: tools/conv_bench -DTTS_NOCT3=2)
+    // HiFi-GAN C = 128 k = 3 106 -> 108; the smaller k = 3 tiles lose 2-3 % with it)
     static constexpr int NOCT = (K == 3 && NT_BLK == 128 && CO_BLK == 128) ? 2 : OctsOf<K>::NOCT;
     static constexpr int KC = 8 * NOCT;                       // input channels per chunk
     static constexpr int WS = NT_BLK + (K - 1) * DMAX;        // staged columns (one float4 each)
@@ -56,14 +56,10 @@ struct Geo {
     static constexpr int W4 = NOCT * K * 2 * CO_BLK;          // W float4s per stage
     static constexpr int NW = (W4 + 255) / 256;               // ... per thread
     static constexpr int BUF4 = XI + W4;                      // float4s per stage
-#ifdef TTS_FORCE_NSTAGE
-    static constexpr int NSTAGE = TTS_FORCE_NSTAGE;
-#else
     // three stages when they fit in half of the LDS; the 32-channel tiles (HiFi-GAN stage 4: 4 chunks per block, all
-    // prologue and epilogue) do better with two stages and one more resident block (+2...5 %, tools/conv_bench), and
+    // prologue and epilogue) do better with two stages and one more resident block (+2...5 %), and
     // so do the 64-channel k = 7 tiles (64 x 128: 4 resident blocks instead of 2, +3.8 % on stage 1; 64 x 256: +2.2 %)
     static constexpr int NSTAGE = (CO_BLK > 32 && 3 * BUF4 * 16 <= 80 * 1024 && !(K == 7 && CO_BLK == 64 && NT_BLK >= 128)) ? 3 : 2;
-#endif
     static constexpr int NGRP = NOCT * K;                     // operand groups per chunk
 };
 
@@ -90,23 +86,7 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
 
     int n_out = p.Nout;
     if (p.lens_out) n_out = min(n_out, (int)p.lens_out[b] * p.len_out_mul);
-#ifdef TTS_TIMING   /* tools/conv_bench: block timeline (start, prologue done, main loop done, end) per block */
-    const unsigned long long t_start = wall_clock64();
-    if (q0 >= n_out) {   // dead block of a ragged batch: stamp it too (pro = main = 0)
-        if (p.timing && threadIdx.x == 0) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            unsigned long long* tp = p.timing + (size_t)lin * 8;
-            tp[0] = t_start; tp[1] = 0; tp[2] = 0; tp[3] = wall_clock64();
-        }
-        return;
-    }
-#else
     if (q0 >= n_out) return;
-#endif
-#ifdef TTS_TIMING
-    const unsigned long long c_start = clock64();   // s_memtime: shader-clock ticks
-    unsigned long long t_pro = 0, t_main = 0, t_e1 = 0;
-#endif
     int in_len = p.Lin;
     if (p.lens_in) in_len = min(in_len, (int)p.lens_in[b] * p.len_in_mul);
 
@@ -304,9 +284,6 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
 #pragma unroll
     for (int P = 0; P < NF; ++P) TTS_FETCH_PART(0, 0, 0, P)
 
-#ifdef TTS_TIMING
-    t_pro = wall_clock64();
-#endif
     int stage = 0;  // c % NSTAGE
     for (int c = 0; c < n_chunks; ++c) {
         // chunk to stage during this chunk (clamped: at the tail the last chunk is re-staged
@@ -330,7 +307,6 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
                     if (g + 1 < NGRP) TTS_FETCH_PART(nxt, stage, g + 1, m)
                     else if (NSTAGE == 3) TTS_FETCH_PART(nxt, sn, 0, m)
                 }
-#if !defined(TTS_EXP_NOLOAD)
                 if (g + 1 < NGRP) {
 
                     const int t = g * NM + m;
@@ -338,20 +314,15 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
                     for (int J = 0; J < NLJ; ++J)
                         if (J >= t * NLJ / GL && J < (t + 1) * NLJ / GL) TTS_LOAD_JOB(J)
                 }
-#endif
-#if !defined(TTS_EXP_NOWRITE)
                 if (g + 1 == NGRP) {
 #pragma unroll
                     for (int J = 0; J < NWJ; ++J)
                         if (J >= m * NWJ / NM && J < (m + 1) * NWJ / NM) TTS_WRITE_JOB(J, sbf)
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifndef TTS_EXP_NOBARRIER
         __syncthreads();
-#endif
         if (NSTAGE == 3) {
             if ((NGRP & 1) != 0) {   // the prefetched group sits in slot 1: next chunk starts from slot 0
 #pragma unroll
@@ -377,9 +348,6 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
 #undef TTS_FETCH_PART
 #undef TTS_LRELU
 
-#ifdef TTS_TIMING
-    t_main = wall_clock64();
-#endif
     // ---- epilogue: bias, residual, activation, accumulate modes ------------------------------------------
     const int co_w0 = co_blk0 + wm * MT * 32;
     if constexpr (EPI != 2) {
@@ -412,9 +380,6 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
                                 ep[(row - ps * ROWS_P) * NT_BLK + qw0 + j * 32 + l31] = acc[i][j][r];
                         }
                 __syncthreads();
-#ifdef TTS_TIMING
-                if (ps == 0) t_e1 = wall_clock64();
-#endif
                 constexpr int RPI = LPR >= 64 ? 1 : 64 / LPR;                     // rows per wave instruction
                 constexpr int CPL = LPR >= 64 ? LPR / 64 : 1;                     // float4 columns groups per lane
                 constexpr int NR = (ROWS_P + 4 * RPI - 1) / (4 * RPI);            // row iterations per wave
@@ -508,16 +473,6 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
                 }
                 }   // !preload
             }
-#ifdef TTS_TIMING
-            if (p.timing && threadIdx.x == 0) {
-                const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-                unsigned hwid, xcc;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-                unsigned long long* tp = p.timing + (size_t)lin * 8;
-                tp[0] = t_start; tp[1] = t_pro; tp[2] = t_main; tp[3] = wall_clock64(); tp[4] = hwid; tp[5] = xcc; tp[6] = t_e1; tp[7] = clock64() - c_start;
-            }
-#endif
             return;
         }
     } else {
@@ -584,7 +539,7 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
 }
 
 template <int K, int MT, int NTL, int WM, int WN, int EPI>
-__global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_mfma_f32(const ConvParams p) {
+__global__ __launch_bounds__(256, kConvMinWaves) void conv1d_mfma_f32(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     constexpr int NT_BLK = WN * NTL * 32;
     // ragged batches: tile-major block order (x = utterance slot, z = time tile), see ConvParams::tile_major
@@ -670,25 +625,9 @@ static int32_t launch_epi(const ConvParams& q, dim3 grid, size_t lds, hipStream_
     return 0;
 }
 
-// Block order experiment for ragged batches (TTSAMD_TILE_MAJOR=1; default off).  With the time tile in blockIdx.x every
-// utterance ends in a run of dead blocks (tiles past its length).  On a stand-alone ragged launch whose utterances are
-// 16 % shorter than the padded length on average, the in-order workgroup dispatcher leaves slots empty behind those runs
-// (1.59 resident blocks per CU instead of 1.90, tools/conv_slots.py) and tile-major order (x = utterance slot, z = time
-// tile, utterance = (slot + tile) % batch so that the XCD <-> utterance assignment rotates) recovers +4-5 % there.  On the
-// bench workload (10 % shorter on average) it measures -0.5 % (84.2 vs 83.8 ms per step: neighbouring blocks no longer
-// share their halo columns in L2), so the default stays time-major.
-// Dead blocks last (live_tile, conv_mfma_common.hpp): default for every ragged launch; TTSAMD_COMPACT=0 restores the plain
-// (time tile, co tile, utterance) grid.
-bool compact_order(const void* lens, int batch) {
-    if (lens == nullptr || batch <= 1) return false;
-    const char* e = exp_env("TTSAMD_COMPACT");                  // read per call (a dozen ns next to a launch): tests and A/B runs flip it
-    return !(e && e[0] == '0');
-}
-
-bool tile_major_order(const ConvParams& p, unsigned n_tiles) {
-    static const int force = [] { const char* e = exp_env("TTSAMD_TILE_MAJOR"); return e ? atoi(e) : 0; }();
-    return force != 0 && p.lens_out != nullptr && p.batch > 1 && n_tiles <= 65535;
-}
+// Dead blocks last (live_tile, conv_mfma_common.hpp): every ragged launch.  (A tile-major block order -- x = utterance slot, z = time
+// tile -- measured -0.5 % on the bench workload: the kernels keep ConvParams::tile_major, the launchers pass 0.)
+bool compact_order(const void* lens, int batch) { return lens != nullptr && batch > 1; }
 
 // Weights one XCD's L2 is asked to keep when co-tiles share an XCD for the input window's sake.  Stand-alone, FETCH_SIZE per launch
 // (profiles/r4/xcd_probe.txt): C = 256 k = 3 / 7 / 11 519 -> 330 / 727 -> 342 / 755 -> 492 MB, C = 128 k = 11 1452 -> 1020 MB -- at the same
@@ -705,21 +644,18 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     dim3 grid((p.Nout + NT_BLK - 1) / NT_BLK, (p.CoutP / CO_BLK) * p.n_phase, p.batch);
     ConvParams q = p;
     q.ksplit = 1;
-    q.tile_major = tile_major_order(p, grid.x) ? 1 : 0;
-    if (q.tile_major) std::swap(grid.x, grid.z);
-    q.compact = (!q.tile_major && compact_order(p.lens_out, p.batch)) ? 1 : 0;
+    q.tile_major = 0;
+    q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
     {
-        const char* xe = opt_str(OPT_XCD_W);                    // read per call, like the other schedule switches
-        const bool xw = !(xe && xe[0] == '0');
+        const bool xw = opt_int(OPT_XCD_W, 1) != 0;             // read per call, like the other schedule switches
         const unsigned nct = grid.y;
         const unsigned g = (nct % 8 == 0) ? 8 : (nct % 4 == 0 ? 4 : (nct % 2 == 0 ? 2 : 1));
-        const bool can = xw && !q.tile_major && p.n_phase == 1 && ((int64_t)grid.x * grid.y * grid.z) % 8 == 0;
+        const bool can = xw && p.n_phase == 1 && ((int64_t)grid.x * grid.y * grid.z) % 8 == 0;
         q.xcd_w = (can && g > 1) ? (int)g : 0;
         // an XCD owns whole time tiles: the co-tiles of its class are consecutive slots and share the input window through its L2.  As few
         // classes (g2 <= g) as keep a class's weights under TTSAMD_XCD_WMAX_KB (0 = the plain map above); with more co-tiles than classes
         // (FastPitch's 384 -> 1536 conv: 12 co-tiles in 4 classes; 1536 -> 384: 3 in 1) the same g already saves the re-reads
-        const char* we = opt_str(OPT_XCD_WMAX_KB);
-        const int64_t wmax = (we ? (int64_t)atoi(we) : (int64_t)kXcdWeightKB) * 1024;
+        const int64_t wmax = opt_int(OPT_XCD_WMAX_KB, kXcdWeightKB) * 1024;
         if (can && wmax > 0 && nct > 1) {
             const int64_t wbytes = (int64_t)p.CoutP * p.Cin * K * 4;
             unsigned g2 = g;
@@ -730,9 +666,7 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     }
     const int64_t nblk = (int64_t)grid.x * grid.y * grid.z, per = (int64_t)p.batch * p.Cout * p.Nout;
     const int n_chunks = p.Cin / G::KC;
-    static const int sk_blocks = [] { const char* e = exp_env("TTSAMD_SPLITK_BLOCKS"); return e ? atoi(e) : 320; }();
-    static const int sk_target = [] { const char* e = exp_env("TTSAMD_SPLITK_TARGET"); return e ? atoi(e) : 640; }();
-    static const int sk_chunks = [] { const char* e = exp_env("TTSAMD_SPLITK_MIN_CHUNKS"); return e ? atoi(e) : 8; }();
+    constexpr int sk_blocks = 320, sk_target = 640, sk_chunks = 8;
     if (p.splitk_ws && p.n_phase == 1 && p.y_ts == 1 && nblk < sk_blocks && n_chunks >= sk_chunks) {
         int64_t ks = std::min<int64_t>((sk_target + nblk - 1) / nblk, n_chunks / 4);
         ks = std::min<int64_t>(ks, p.splitk_floats / per);
@@ -745,21 +679,13 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     const bool vec_ok = q.ksplit == 1 && p.y_ts == 1 && p.n_phase == 1 && (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 &&
                         ((uintptr_t)p.y & 15) == 0 &&
                         (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0));
-#ifdef TTS_NO_VEC_EPILOGUE
-    const int epi = 2;
-#else
     // GELU (Vocos pwconv1, k = 1) and tanh (Tacotron2 postnet, k = 5) are compiled into those kernel sizes only
     TTS_REQUIRE(p.relu_out < 2 || K == 1 || K == 5, "conv: GELU / tanh epilogues are built for kernel sizes 1 and 5 only (K=%d)", K);
     // the residual rides in through the accumulators (EPI 3) unless a per-channel scale sits between conv and residual
     // (Vocos gamma) or the kernel was built without it
-#ifdef TTS_NO_PRELOAD
-    const bool pre_ok = false;
-#else
     const bool pre_ok = p.res != nullptr && p.scale == nullptr && p.relu_out < 2 &&
                         (int64_t)p.Cout * std::max(p.r_cs, p.y_cs) * 4 < ((int64_t)1 << 31);
-#endif
     const int epi = !vec_ok ? 2 : (p.relu_out >= 2 ? 1 : (pre_ok ? 3 : 0));
-#endif
     int32_t rc;
     if (epi == 3) rc = launch_epi<K, MT, NTL, WM, WN, 3>(q, grid, lds, stream);
     else if (epi == 0) rc = launch_epi<K, MT, NTL, WM, WN, 0>(q, grid, lds, stream);
@@ -777,26 +703,13 @@ static int32_t launch_k(const ConvParams& p, hipStream_t stream) {
     auto blocks = [&](int co_blk, int nt_blk) -> int64_t {
         return (int64_t)((p.Nout + nt_blk - 1) / nt_blk) * (p.CoutP / co_blk) * p.n_phase * p.batch;
     };
-    static const int64_t want_env = [] { const char* e = exp_env("TTSAMD_WANT_BLOCKS"); return e ? (int64_t)atoi(e) : (int64_t)-1; }();
     // blocks a launch should have: 3 per CU -- unless the whole problem is about one round of the smallest tiles (batch 1: 914 tiles
     // of 64 x 64 for a stage-2 conv): then one block per CU of a LARGE tile (64 x 256: 230 blocks at 0.85 of the matrix peak) beats
-    // four of the small one (0.62): batch 1 5.04 -> 4.86 ms per call, measured with TTSAMD_WANT_BLOCKS=200 / 768
-    const int64_t want = want_env > 0 ? want_env : (blocks(64, 64) <= 1024 ? (int64_t)200 : (int64_t)768);
+    // four of the small one (0.62): batch 1 5.04 -> 4.86 ms per call (200 vs 768 blocks wanted)
+    const int64_t want = blocks(64, 64) <= 1024 ? (int64_t)200 : (int64_t)768;
     const bool tiny = p.Nout <= 96;
-#ifdef TTS_FORCE_CFG   /* tile autotuning with tools/conv_bench.hip */
-    switch (TTS_FORCE_CFG) {
-        case 0: if (p.CoutP % 128 == 0) return launch_cfg<K, 2, 2, 2, 2>(p, stream); break;
-        case 1: if (p.CoutP % 128 == 0) return launch_cfg<K, 1, 2, 4, 1>(p, stream); break;
-        case 2: if (p.CoutP % 64 == 0) return launch_cfg<K, 2, 2, 1, 4>(p, stream); break;
-        case 3: if (p.CoutP % 64 == 0) return launch_cfg<K, 1, 1, 2, 2>(p, stream); break;
-        case 4: return launch_cfg<K, 1, 2, 1, 4>(p, stream);
-        case 5: return launch_cfg<K, 1, 1, 1, 4>(p, stream);
-        case 6: if (p.CoutP % 64 == 0) return launch_cfg<K, 1, 2, 2, 2>(p, stream); break;   // 64 co x 128 t
-        case 7: if (p.CoutP % 128 == 0) return launch_cfg<K, 2, 1, 2, 2>(p, stream); break;  // 128 co x 64 t, 2x1 tiles per wave
-    }
-#endif
     // (measured and not kept, round 4: a 96 co x 128 t tile for FastPitch's second conv-FF conv -- 1536 -> 384, exactly two blocks per CU
-    // instead of 2.6-2.8 of the 128 x 64 tile -- runs the step in 77.83 vs 77.82 ms: tools/ab_tile96.sh)
+    // instead of 2.6-2.8 of the 128 x 64 tile -- runs the step in 77.83 vs 77.82 ms)
     if (p.CoutP % 128 == 0) {
         // deep-K layers on short sequences (HiFi-GAN stage 1: C = 256, 8 positions per frame) have few, long blocks;
         // a launch is then 2-4 rounds of blocks and its tail costs 15-19 %: finer tiles pay there
@@ -810,8 +723,7 @@ static int32_t launch_k(const ConvParams& p, hipStream_t stream) {
         // (launch_cfg: < 320 tiles -> 2..4 slices) instead of twice as many 64 x 64 tiles that each walk all 96 chunks
         if (p.splitk_ws && p.Cin >= 1024 && !tiny && blocks(128, 64) >= 160 && blocks(128, 64) < 320 &&
             (int64_t)2 * p.batch * p.Cout * p.Nout <= p.splitk_floats) {
-            const char* e = opt_str(OPT_DEEP_SPLITK);                    // read per launch of this (rare) shape: the tests flip it
-            if (!(e && e[0] == '0')) return launch_cfg<K, 1, 2, 4, 1>(p, stream);
+            if (opt_int(OPT_DEEP_SPLITK, 1) != 0) return launch_cfg<K, 1, 2, 4, 1>(p, stream);   // read per launch of this (rare) shape: the tests flip it
         }
         if (blocks(128, 64) >= want || (tiny && blocks(64, 64) < 2 * want)) return launch_cfg<K, 1, 2, 4, 1>(p, stream);   // 128 co x 64 t
         return launch_cfg<K, 1, 1, 2, 2>(p, stream);                                                    //  64 co x  64 t
@@ -844,17 +756,6 @@ int32_t launch_conv(const ConvParams& p, hipStream_t stream) {
              p.lens_out != nullptr, p.n_phase);
     if (p.precision != 0) return launch_conv_bf16_any(p, stream);
     TTS_REQUIRE(!p.x_packed && !p.y_packed, "conv: packed bf16 activations exist only in the bf16 mode");
-#ifdef TTS_WITH_DIRECT   /* tools/conv_bench.hip only: A/B against tools/conv_direct_f32.hip (round 3, no gain: DESIGN.md §4) */
-    {
-        const char* de = exp_env("TTSAMD_DIRECT");
-        if (de && de[0] == '1' && direct_supported(p)) return launch_direct(p, stream);   // opt in: the tool's default is the product kernel
-    }
-#endif
-#ifdef TTS_ONLY_K   /* kernel experiments: compile one kernel size only (tools/conv_bench, 10 s instead of 90 s) */
-    if (p.K == TTS_ONLY_K) return launch_k<TTS_ONLY_K>(p, stream);
-    set_error("conv: built with TTS_ONLY_K=%d", TTS_ONLY_K);
-    return TTSAMD_EINVAL;
-#else
     if (wino) return wino == 3 ? launch_wino4(p, stream) : (wino == 2 ? launch_wino2(p, stream) : launch_wino(p, stream));
     switch (p.K) {
         case 1: return launch_k<1>(p, stream);
@@ -867,7 +768,6 @@ int32_t launch_conv(const ConvParams& p, hipStream_t stream) {
             set_error("conv: kernel size %d not instantiated (1,2,3,5,7,11)", p.K);
             return TTSAMD_EINVAL;
     }
-#endif
 }
 
 // torch Conv1d weight [Cout][Cin][K] -> [Cin/8][K][2][CoutP][4]:

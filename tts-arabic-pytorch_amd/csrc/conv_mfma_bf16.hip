@@ -42,7 +42,7 @@ struct GeoB {
 // (polyphase upsamplers, unaligned rows, packed bf16 output); EPI 3: row epilogue with the residual (+ running sum) PRELOADED
 // into the accumulators and a load-free store loop, as conv_mfma.hip's EPI 3
 template <int K, int MT, int NTL, int WM, int WN, int NPL, int EPI, bool ACT>
-__global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_mfma_bf16(const ConvParams p) {
+__global__ __launch_bounds__(256, kConvMinWaves) void conv1d_mfma_bf16(const ConvParams p) {
     // NPL = 1: plain bf16 operands; NPL = 2: split bf16 (hi + lo planes, 3 MFMAs per product)
     extern __shared__ __attribute__((aligned(16))) uint2 smem4[];
     constexpr int CO_BLK = WM * MT * 32;
@@ -276,7 +276,6 @@ __global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_mfma_bf16(const Conv
                         if (g + 1 < NGRP) TTS_FETCH_PART(nxt, stage, g + 1, P)
                         else if (NSTAGE == 3) TTS_FETCH_PART(nxt, sn, 0, P)
                     }
-#if !defined(TTS_EXP_NOLOAD)
                 if (g + 1 < NGRP) {
 
                     const int t = g * NM + m;
@@ -284,20 +283,15 @@ __global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_mfma_bf16(const Conv
                     for (int J = 0; J < NLJ; ++J)
                         if (J >= t * NLJ / GL && J < (t + 1) * NLJ / GL) TTS_LOAD_JOB(J)
                 }
-#endif
-#if !defined(TTS_EXP_NOWRITE)
                 if (g + 1 == NGRP) {
 #pragma unroll
                     for (int J = 0; J < NWJ; ++J)
                         if (J >= m * NWJ / NM && J < (m + 1) * NWJ / NM) TTS_WRITE_JOB(J, sbf)
                 }
-#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#ifndef TTS_EXP_NOBARRIER
         __syncthreads();
-#endif
         if (NSTAGE == 3) {
             if ((NGRP & 1) != 0) {   // the prefetched group sits in slot 1: next chunk starts from slot 0
 #pragma unroll
@@ -550,8 +544,7 @@ static int32_t launch_cfg_bf16(const ConvParams& p_in, hipStream_t stream) {
     TTS_REQUIRE(p.relu_out < 2 || HAS_ACT, "conv: GELU / tanh epilogues are built for kernel sizes 1 and 5 only (K=%d)", K);
     const size_t lds = (size_t)G::NSTAGE * G::BUF4 * sizeof(uint2);
     dim3 grid((p.Nout + NT_BLK - 1) / NT_BLK, (p.CoutP / CO_BLK) * p.n_phase, p.batch);
-    p.tile_major = tile_major_order(p, grid.x) ? 1 : 0;
-    if (p.tile_major) std::swap(grid.x, grid.z);
+    p.tile_major = 0;
     const bool vec_ok = !p.y_packed && p.y_ts == 1 && p.n_phase == 1 && (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 &&
                         ((uintptr_t)p.y & 15) == 0 &&
                         (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0));

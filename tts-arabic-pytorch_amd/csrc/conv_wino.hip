@@ -48,7 +48,7 @@ struct WinoGeo {
 
 // EPI 0: row epilogue (bias / residual / ReLU / accumulate modes);  3: the same with the residual (and the previous y) preloaded
 template <int MT, int WM, int WN, int EPI>
-__global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_wino_f32(const ConvParams p) {
+__global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino_f32(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     using G = WinoGeo<MT, WM, WN>;
     constexpr int CO_BLK = G::CO_BLK, NPAIR = G::NPAIR, NT_BLK = G::NT_BLK, NW = G::NW, NGRP = G::NGRP, NSTAGE = G::NSTAGE;
@@ -408,13 +408,11 @@ static int32_t launch_wino_epi(const ConvParams& q, dim3 grid, hipStream_t strea
 //                        68.5 with k = 7 + 11, 67.5 with the three, 65.6 with dilations, 64.6-65.1 with Cout = 64)
 int wino_route(const ConvParams& p) {
     if (p.precision != 0) return 0;
-    const char* e = opt_str(OPT_WINO);
-    if (e && e[0] == '0') return 0;
+    if (opt_int(OPT_WINO, 1) == 0) return 0;
     if (p.K == 1) {
         // k = 1 (Vocos' pointwise convs and head, FastPitch's qkv / o_net projections) on the F(4,3) kernel's skeleton with nothing to transform
         // (conv_wino4.hip, Wino4Geo::WSHARE): the direct engine's packed weights as they are; TTSAMD_WINO4 bit 4.  Same tile as the F(4,3) launches.
-        const char* e4 = opt_str(OPT_WINO4);
-        const int mask4 = e4 ? atoi(e4) : 31;
+        const int mask4 = (int)opt_int(OPT_WINO4, 31);
         const bool ok1 = (mask4 & 16) && p.w != nullptr && p.dil == 1 && p.pad == 0 && p.n_phase == 1 && p.y_ts == 1 && p.CoutP % 64 == 0 &&
                          p.Cin % 32 == 0 && p.in_slope >= 0.f && p.in_slope <= 1.f && !p.x_packed && !p.y_packed &&
                          (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
@@ -432,8 +430,7 @@ int wino_route(const ConvParams& p) {
         // (k = 3 -- 6 instead of 8 products per quad -- did not pay with the kernel's first staging path: 414 / 330 vs 392 / 315 us on
         // FastPitch's conv-FF pair; with the aligned 16-byte window loads it does: same-box A/B of the step 55.46 (mask 14) vs 54.68 ms.)
         // 64 rows x 64 quads per block, float4-aligned rows, at least 192 blocks (below: the F(2,3) / direct routing that follows)
-        const char* e4 = opt_str(OPT_WINO4);
-        const int mask4 = e4 ? atoi(e4) : 31;
+        const int mask4 = (int)opt_int(OPT_WINO4, 31);
         const int kbit4 = p.K == 3 ? 1 : (p.K == 7 ? 2 : 4);
         const bool ok4 = (mask4 & kbit4) && (p.dil == 1 || (mask4 & 8)) && (p.K != 3 || p.Cin % 16 == 0) &&
                          (p.dil == 1 || p.dil == 3 || p.dil == 5) && p.pad == p.dil * (p.K - 1) / 2 && p.n_phase == 1 && p.y_ts == 1 &&
@@ -448,8 +445,7 @@ int wino_route(const ConvParams& p) {
         }
         if (p.w_wino == nullptr) return 0;
     }
-    const char* e2 = opt_str(OPT_WINO2);
-    const int mask = e2 ? atoi(e2) : 31;
+    const int mask = (int)opt_int(OPT_WINO2, 31);
     const int kbit = p.K == 3 ? 1 : (p.K == 7 ? 2 : 4);
     const bool rows64 = p.CoutP % 128 != 0;
     // what the decomposition kernel can take of this launch (its k = 3 chunks are 16 channels)

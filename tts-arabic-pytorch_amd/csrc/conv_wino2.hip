@@ -80,7 +80,7 @@ __device__ __host__ constexpr int wino2_plane(int g) {
 __device__ __host__ constexpr int wino2_tile(int d, int npair) { return (2 * npair / ((d & 1) ? 4 * d : 2 * d)) * ((d & 1) ? 4 * d : 2 * d); }
 
 template <int K, int NOCT_, int NSTAGE_, int WM_, int NPH_, int EPI>
-__global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_wino2_f32(const ConvParams p) {
+__global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino2_f32(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     using G = Wino2Geo<K, NOCT_, NSTAGE_, WM_, NPH_>;
     constexpr int MT = G::MT, WN = G::WN, NS = G::NS, NG = G::NG, NOCT = G::NOCT, NSTAGE = G::NSTAGE;

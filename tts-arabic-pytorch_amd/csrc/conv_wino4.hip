@@ -42,12 +42,6 @@
 #include "conv_mfma_common.hpp"
 #include "bfo.hpp"
 
-// timing experiments only (tools/w4_exp.sh builds its own libraries; results are WRONG by design): bit 0 no x loads in the main loop,
-// 1 no activation, 2 no plane writes, 3 no weight refill, 4 no B reads
-#ifndef TTS_W4_EXP
-#define TTS_W4_EXP 0
-#endif
-
 namespace ttsamd {
 
 typedef float w4_f32x4 __attribute__((ext_vector_type(4)));
@@ -134,7 +128,7 @@ struct Wino4Geo {
 __device__ __host__ constexpr int wino4_tile(int d, int ntup) { return (4 * ntup / (4 * d)) * (4 * d); }
 
 template <int K, int NOCT_, int NSTAGE_, int EPI, int LP>
-__global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_wino4_f32(const ConvParams p) {
+__global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     using G = Wino4Geo<K, NOCT_, NSTAGE_, EPI>;
     constexpr int WN = G::WN, NSF = G::NSF, NOCT = G::NOCT, NSTAGE = G::NSTAGE, NPL = G::NPL, NGPM = G::NGPM;
@@ -387,7 +381,7 @@ __global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_wino4_f32(const Conv
                 const w4_f32x4 a4 = aq[qs];
                 // refill the queue slot with the group PF ahead (k = 1: one fragment per octet, refilled behind its last group)
                 if (!G::WSHARE || gl == G::ngq(ph) - 1) {
-                    if (!(TTS_W4_EXP & 8)) aq[qs] = __builtin_bit_cast(w4_f32x4, bfo_ld16(wrs, wv, wso, 0));
+                    aq[qs] = __builtin_bit_cast(w4_f32x4, bfo_ld16(wrs, wv, wso, 0));
                     wso = min(wso + wstep, wlast);
                 }
                 if (gl >= G::ngp(ph)) continue;                    // the zero group of k = 11: fetched, never multiplied
@@ -395,8 +389,7 @@ __global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_wino4_f32(const Conv
                 const int cur = r & 1, nxt = cur ^ 1;
                 const int plane = G::plane(G::glo(ph) + gl);
                 // B operand of the next group: same stage, or (three stages) the first group of the next step's stage
-                if (TTS_W4_EXP & 16) bq[nxt] = bq[cur];
-                else if (r + 1 < NOCT * G::ngp(ph)) bq[nxt] = rd[(((r + 1) / G::ngp(ph)) * 2 * NGPM + (r + 1) % G::ngp(ph)) * NTUP];
+                if (r + 1 < NOCT * G::ngp(ph)) bq[nxt] = rd[(((r + 1) / G::ngp(ph)) * 2 * NGPM + (r + 1) % G::ngp(ph)) * NTUP];
                 else if (NSTAGE >= 3) bq[nxt] = sB[sn * G::BUF4];       // (an odd step leaves it in slot 1: moved to slot 0 behind the barrier)
                 __builtin_amdgcn_sched_barrier(0);
                 const float bv[4] = {bq[cur].x, bq[cur].y, bq[cur].z, bq[cur].w};
@@ -407,9 +400,9 @@ __global__ __launch_bounds__(256, TTS_MINWAVES) void conv1d_wino4_f32(const Conv
                     // the plane writes into the stage the previous step has left
                     const int t = r * NM + m;
                     if constexpr (D1) {
-                        if (!(TTS_W4_EXP & 1) && t < G::nljv(tph)) TTS_VLOAD_JOB(tph, t, xso)
-                        if (!(TTS_W4_EXP & 2) && t >= G::DAV && t - G::DAV < 2 * G::nljv(tph)) TTS_VACT_JOB(tph, t - G::DAV)
-                        if (!(TTS_W4_EXP & 4) && t >= G::tw0v(tph) && (t - G::tw0v(tph)) % G::wsv(tph) == 0 &&
+                        if (t < G::nljv(tph)) TTS_VLOAD_JOB(tph, t, xso)
+                        if (t >= G::DAV && t - G::DAV < 2 * G::nljv(tph)) TTS_VACT_JOB(tph, t - G::DAV)
+                        if (t >= G::tw0v(tph) && (t - G::tw0v(tph)) % G::wsv(tph) == 0 &&
                             (t - G::tw0v(tph)) / G::wsv(tph) < G::nwj(tph))
                             TTS_WRITE_JOB(tph, (t - G::tw0v(tph)) / G::wsv(tph), wr)
                     } else {

@@ -214,7 +214,7 @@ bool convt_supported(const ConvParams& p) {
     const bool u_ok = (p.n_phase == 8 || p.n_phase == 2) && p.phase_p * 2 == p.n_phase;
     // a grid that leaves most CUs without a block (batch 1: 32 blocks for the first upsampler) does
     // better on the polyphase launch of the generic engine, which has one block per (phase, co tile) and splits K
-    static const int min_blocks = [] { const char* e = exp_env("TTSAMD_CONVT_MIN_BLOCKS"); return e ? atoi(e) : 100; }();
+    constexpr int min_blocks = 100;
     if (u_ok && p.n_phase == 8 && (int64_t)((p.Nout + 63) / 64) * (p.CoutP / 64) * p.batch < min_blocks) return false;
     return p.precision == 0 && u_ok && p.K == 2 && p.dil == -1 && p.y_ts == p.n_phase && p.res == nullptr && p.mode == 0 &&
            p.scale == nullptr && p.relu_out == 0 && p.Cin % 8 == 0 && !p.x_packed && !p.y_packed &&

@@ -68,16 +68,15 @@ struct HifiGan {
 // TTSAMD_HIFIGAN_STREAMS=0/1 forces either schedule.
 static bool use_branch_streams(const HifiGan* h, int32_t B, int32_t T) {
     if (h->cfg.n_kernels != 3) return false;
-    const char* env = opt_str(OPT_HIFIGAN_STREAMS);   // read per call: the tests flip it
-    if (env) return env[0] == '1';
+    const int64_t streams = opt_int(OPT_HIFIGAN_STREAMS, -1);   // read per call: the tests flip it
+    if (streams >= 0) return streams == 1;
     // bf16 octet engine: the launches are power-bound at batch 32 and latency-bound below; the fork / join events cost more than the
     // overlap returns under ~8 k frames (batch 1: 2.09 -> 1.92 ms, batch 8: 4.35 -> 4.26 on one stream; batch 32: 10.02 -> 9.88 ms with
     // three under the two-stream pipeline)
     // (split bf16, round 6: three streams win at every size -- batch 1 1.18 vs 1.25 ms, 2: 1.87 / 1.94, 4: 3.37 / 3.53, 8: 6.15 / 6.40,
     // tools/b1_parts.py -- so the rule below is the plain-bf16 engine's only)
     if (default_precision() == 1 && h->bfo_ok) {
-        const char* bfo_env = opt_str(OPT_BFO);
-        if (!(bfo_env && bfo_env[0] == '0')) return (int64_t)B * T >= 8192;
+        if (opt_int(OPT_BFO, 1) != 0) return (int64_t)B * T >= 8192;
     }
     return true;
 }
@@ -89,36 +88,23 @@ static bool use_branch_streams(const HifiGan* h, int32_t B, int32_t T) {
 // The routing switches are read ONCE per forward call (snapshot below) and handed down: a forward used to make several hundred
 // getenv calls, each a window for a concurrent setenv from another host thread (os.environ writes in Python do exactly that).
 struct Fused2Switches {
-    bool on = true, mask_forced = false, small_on = false;
+    bool on = true, mask_forced = false;
     bool wino_b = true, wino_a = true;   // phase B / phase A + B of the C = 32 / 64 pairs as Winograd F(2,3) (TTSAMD_FUSED2_WB=0: both direct, =1: phase B only)
     bool pair4 = true;                   // ... the C = 32 ones with both phases on Winograd as F(4,3) instead (TTSAMD_PAIR4=0: resblock_pair2)
     unsigned mask = kFused2Mask, mask_n1 = kFused2MaskN1;
 };
-static bool parse_hex_mask(const char* txt, unsigned& out) {
-    if (!txt || !*txt) return false;
-    char* end = nullptr;
-    const unsigned long v = std::strtoul(txt, &end, 16);
-    if (end == txt || *end != '\0' || v > 0x1ff) return false;
-    out = (unsigned)v;
-    return true;
-}
-static int32_t read_fused2_switches(Fused2Switches& sw) {
-    const char* e = opt_str(OPT_FUSED2);
-    sw.on = !(e && e[0] == '0');
-    if (const char* m = opt_str(OPT_FUSED2_MASK)) {
-        TTS_REQUIRE(parse_hex_mask(m, sw.mask), "TTSAMD_FUSED2_MASK='%s' is not a hex mask of 9 bits (bit 3 * ci + ki; 1ff = every pair)", m);
-        sw.mask_forced = true;
-    }
-    if (const char* m = opt_str(OPT_FUSED2_MASK_N1))
-        TTS_REQUIRE(parse_hex_mask(m, sw.mask_n1), "TTSAMD_FUSED2_MASK_N1='%s' is not a hex mask of 9 bits", m);
-    const char* wb = opt_str(OPT_FUSED2_WB);
-    sw.wino_b = !(wb && wb[0] == '0');
-    sw.wino_a = sw.wino_b && !(wb && wb[0] == '1');
-    const char* p4 = opt_str(OPT_PAIR4);
-    sw.pair4 = !(p4 && p4[0] == '0');
-    const char* se = exp_env("TTSAMD_FUSED2_SMALL");
-    sw.small_on = se && se[0] == '1';
-    return 0;
+static Fused2Switches read_fused2_switches() {
+    Fused2Switches sw;
+    sw.on = opt_int(OPT_FUSED2, 1) != 0;
+    const int64_t m = opt_int(OPT_FUSED2_MASK, -1);
+    sw.mask_forced = m >= 0;
+    if (sw.mask_forced) sw.mask = (unsigned)m;
+    sw.mask_n1 = (unsigned)opt_int(OPT_FUSED2_MASK_N1, kFused2MaskN1);
+    const int64_t wb = opt_int(OPT_FUSED2_WB, 2);
+    sw.wino_b = wb != 0;
+    sw.wino_a = wb == 2;
+    sw.pair4 = opt_int(OPT_PAIR4, 1) != 0;
+    return sw;
 }
 
 static int fused2_choice(const Fused2Switches& sw, int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y,
@@ -127,19 +113,15 @@ static int fused2_choice(const Fused2Switches& sw, int32_t channels, int32_t k, 
     const int ci = channels == 32 ? 0 : (channels == 64 ? 1 : (channels == 128 ? 2 : -1));
     const int ki = k == 3 ? 0 : (k == 7 ? 1 : (k == 11 ? 2 : -1));
     if (ci < 0 || ki < 0) return 0;
-    unsigned mask = sw.mask, mask_n1 = sw.mask_n1;
     const unsigned bit = 1u << (3 * ci + ki);
-    // small problems (batch 1 ... 4: under two rounds of 256-column blocks).  Measured (tools/f2_small.sh): every pair as ONE launch of
+    // small problems (batch 1 ... 4: under two rounds of 256-column blocks).  Measured: every pair as ONE launch of
     // 128-column blocks -- half the launches of the un-fused engine -- is SLOWER there (batch 1: 5.27 vs 5.04 ms per step, batch 4: 13.35
     // vs 12.88; batch 8 equal): the un-fused engine's 64 x 64 tiles with split K put 3-4x more blocks on the chip.  So small problems
     // keep the un-fused engine (a forced TTSAMD_FUSED2_MASK overrides the rule: parity tests of the fused kernels on small inputs).
     const bool small = columns < (int64_t)kFused2SmallColumns && !sw.mask_forced;
-    if (small) {
-        if (!sw.small_on) return 0;
-        mask = 0x1ff; mask_n1 = 0x1ff;
-    }
-    if (!(mask & bit)) return 0;
-    int ntw = (mask_n1 & bit) ? 1 : 2;
+    if (small) return 0;
+    if (!(sw.mask & bit)) return 0;
+    int ntw = (sw.mask_n1 & bit) ? 1 : 2;
     if (!fused_pair2_supported(channels, k, dil, L, x, y, ntw)) {
         ntw = 3 - ntw;
         if (!fused_pair2_supported(channels, k, dil, L, x, y, ntw)) return 0;
@@ -466,14 +448,10 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
     p.splitk_ws = splitks[0]; p.splitk_floats = kSplitKFloats;     // batch 1: stage-1 launches have < 256 tiles
     // plain bf16 mode: the c1 -> c2 intermediate of a ResBlock only feeds c2, so it crosses HBM as packed bf16
     // (ConvParams::y_packed / x_packed; same rounding point as the fp32 buffer + round-on-load, bit-identical)
-    const char* pk_env = opt_str(OPT_BF16_PACKED_T);
-    const bool pack_t = default_precision() == 1 && !(pk_env && pk_env[0] == '0');
-    Fused2Switches f2sw;
-    TTS_TRY(read_fused2_switches(f2sw));
-    const char* fz_env = opt_str(OPT_FUSED_PAIR);
-    const bool fused_ok = default_precision() == 0 && !(fz_env && fz_env[0] == '0');
-    const char* ct_env = opt_str(OPT_CONVT);
-    const bool convt_ok = !(ct_env && ct_env[0] == '0');   // all-phases-per-wave transposed conv (convt_mfma.hip)
+    const bool pack_t = default_precision() == 1 && opt_int(OPT_BF16_PACKED_T, 1) != 0;
+    const Fused2Switches f2sw = read_fused2_switches();
+    const bool fused_ok = default_precision() == 0 && opt_int(OPT_FUSED_PAIR, 1) != 0;
+    const bool convt_ok = opt_int(OPT_CONVT, 1) != 0;   // all-phases-per-wave transposed conv (convt_mfma.hip)
     bool in_section = false;   // inside a multi-stream fork..join section (profiling brackets the section)
     int pack_io = 0;   // bit 0: x is packed, bit 1: write y packed (set around the c1 / c2 launches below)
     auto conv = [&](const ConvW& cw, const float* x, hipStream_t st, float* y, const float* res, int L, int mul,
@@ -504,9 +482,8 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
     // ---- config 3: plain bf16 (precision 1) and split bf16 (precision 2) run on the octet engine (bfo.hpp / bfo3.hpp):
     // v_mfma_f32_32x32x16_bf16, activations in HBM as octet entries (bf16, or hi + lo) stored pre-activated for their consumer,
     // fused c1 -> c2 pairs for C <= 128.  TTSAMD_BFO=0 keeps the round-2 bf16 engine (fp32 activations in HBM).
-    const char* bfo_env = opt_str(OPT_BFO);
     const int prec = default_precision();
-    if ((prec == 1 || prec == 2) && h->bfo_ok && !(bfo_env && bfo_env[0] == '0')) {
+    if ((prec == 1 || prec == 2) && h->bfo_ok && opt_int(OPT_BFO, 1) != 0) {
         const bool x3 = prec == 2;
         const uint16_t* W16 = h->dev16;
         const auto woff = [x3](const ConvW& cw) { return x3 ? cw.wo3_off : cw.wo_off; };
@@ -514,8 +491,7 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
         const auto l_convt = x3 ? bfo3_launch_convt : bfo_launch_convt;
         const auto l_pair = x3 ? bfo3_launch_pair : bfo_launch_pair;
         const auto pair_ok = x3 ? bfo3_pair_supported : bfo_pair_supported;
-        const char* c3e = opt_str(OPT_BFO_CHAIN);      // 0: three pair launches per k = 3 ResBlock (bit-identical; A/B and parity runs)
-        const bool chain3_on = !(c3e && c3e[0] == '0');
+        const bool chain3_on = opt_int(OPT_BFO_CHAIN, 1) != 0;   // 0: three pair launches per k = 3 ResBlock (bit-identical; A/B and parity runs)
         void *curo = cur, *upso = ups_out;                 // the fp32-sized buffers hold bf16 / x3 tensors of the same element count
         HG_TRY((x3 ? bfo3_launch_pack : bfo_launch_pack)(mel, B, cfg.num_mels, T, 1.f, mel_o, s));
         BfoConvParams cp;

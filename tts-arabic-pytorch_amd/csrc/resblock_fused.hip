@@ -51,11 +51,7 @@ struct FusedGeo {
     static constexpr int LDS4 = XT4 + 2 * WCH4;
     // prefetch distance in chunks (weights: register sets in flight; input octets): a k = 3 chunk is 24 MFMAs = 0.64 us,
     // shorter than one L2 / HBM round trip
-#ifdef TTS_FUSED_PF64
-    static constexpr int PFW = C > 32 ? TTS_FUSED_PF64 : (K <= 3 ? 3 : (K <= 7 ? 2 : 1));
-#else
     static constexpr int PFW = C > 32 ? (K <= 3 ? 2 : 1) : (K <= 3 ? 3 : (K <= 7 ? 2 : 1));
-#endif
     static constexpr int PFX = PFW;
     static_assert(C * 64 <= XT4, "the epilogue's [C][256] transposition buffer must fit in the input window");
 };
@@ -337,9 +333,7 @@ static int32_t launch_fused_k(const FusedPairParams& p, hipStream_t stream) {
 
 // true if the fused kernel covers this pair (C = 32: k = 3 / 7 / 11; C = 64: k = 3, the one that wins there; fp32, aligned rows)
 bool fused_pair_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y) {
-    const char* e64 = exp_env("TTSAMD_FUSED_PAIR_C64");         // read per call: the tests and A/B runs flip it
-    const bool c64 = !(e64 && e64[0] == '0');
-    const bool geo = (channels == 32 && (k == 3 || k == 7 || k == 11)) || (channels == 64 && k == 3 && c64);
+    const bool geo = (channels == 32 && (k == 3 || k == 7 || k == 11)) || (channels == 64 && k == 3);
     return geo && dil >= 1 && dil <= DMAX && (L & 3) == 0 &&
            (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && x != y && (int64_t)channels * L * 4 < ((int64_t)1 << 31);
 }

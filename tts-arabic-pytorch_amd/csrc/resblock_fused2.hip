@@ -40,8 +40,6 @@ struct FusedPair2Params {
     int32_t mode;          // 0: y = v   1: y = y + v   2: y = (y + v) / div
     float div, slope;
     int32_t compact;       // ragged batch: blocks take the lin-th LIVE tile (common.hpp: live_tile)
-    int32_t exp;           // -DTTS_F2_EXP builds only (timing experiments, results wrong): TTSAMD_F2_EXP bit 0 no window loads,
-                           // 1 no phase A, 2 no phase B, 3 no output stores
 };
 
 template <int K, int C, int NTW>
@@ -226,16 +224,16 @@ __device__ __forceinline__ void conv_phase2_wino(f32x16 (&acc)[4][MTW], float4 (
 
 // WM = 0: both convs direct; 1: phase B (c2, dilation 1) as Winograd F(2,3); 2: phase A too -- then the window is staged ACTIVATED (one
 // leaky-relu per value instead of one per use) and the residual comes from global memory in the row epilogue (an L2 hit).
-#ifndef TTS_F2_WA32_WAVES
-#define TTS_F2_WA32_WAVES 3     /* resident blocks per CU the C = 32 kernels with both phases on Winograd are compiled for: 170 registers, no spills (4: 128 registers, 40-56 bytes of scratch at k = 7 / 11; 61.80 vs 61.94 ms per step) */
-#endif
+// resident blocks per CU the C = 32 kernels with both phases on Winograd are compiled for: 170 registers, no spills (4: 128 registers,
+// 40-56 bytes of scratch at k = 7 / 11; 61.80 vs 61.94 ms per step)
+constexpr int kF2Wa32Waves = 3;
 // C = 128 with both phases on Winograd: EIGHT waves per block (two row halves x four column groups) -- four planes x 128 rows do not
 // fit one wave's registers; one block per CU (the 136 KB window).
 template <int C, int WM>
 constexpr int f2_row_halves() { return (WM == 2 && C == 128) ? 2 : 1; }
 
 template <int K, int C, int NTW, int WM>
-__global__ __launch_bounds__((256 * f2_row_halves<C, WM>()), ((WM == 2 && C == 32) ? TTS_F2_WA32_WAVES : Fused2Geo<K, C, NTW>::WAVES))
+__global__ __launch_bounds__((256 * f2_row_halves<C, WM>()), ((WM == 2 && C == 32) ? kF2Wa32Waves : Fused2Geo<K, C, NTW>::WAVES))
 void resblock_pair2(const FusedPair2Params p) {
     using G = Fused2Geo<K, C, NTW>;
     constexpr int NOCT = G::NOCT, MT = G::MT, H = G::H, NB = G::NB, TSTR = G::TSTR, PF = G::PF, TSH = G::TSH;
@@ -258,15 +256,6 @@ void resblock_pair2(const FusedPair2Params p) {
     int len = p.L;
     if (p.lens) len = min(len, (int)p.lens[b] * p.len_mul);
     if (q0 >= len) return;
-#ifdef TTS_F2_EXP
-    if (p.exp & 16) {      // desynchronise the co-resident blocks of the first round: the second block of every CU starts (exp >> 8) us late
-        const unsigned lin0 = blockIdx.z * gridDim.x + blockIdx.x;
-        if (lin0 >= 256 && lin0 < 512) {
-            const unsigned long long t0 = wall_clock64();
-            while (wall_clock64() - t0 < (unsigned long long)(p.exp >> 8) * 100) __builtin_amdgcn_s_sleep(8);
-        }
-    }
-#endif
     const int dil = p.dil, L = p.L;
     const int pad1 = H * dil;
     const int W1 = NB + (K - 1) * dil;                         // staged columns = row stride of the window
@@ -411,9 +400,6 @@ void resblock_pair2(const FusedPair2Params p) {
             for (int j = 0; j < NTW; ++j) acc[mt][j][r] = bv;
         }
 
-#ifdef TTS_F2_EXP
-    if (!(p.exp & 2))
-#endif
     conv_phase2<K, C, NTW, true>(acc, aq, Xs + kk * W1 + colw, W1, dil, wl1, wl2, slope);
 
     if constexpr (WB) {
@@ -564,9 +550,6 @@ void resblock_pair2(const FusedPair2Params p) {
     }
     __syncthreads();
 
-#ifdef TTS_F2_EXP
-    if (!(p.exp & 4))
-#endif
     conv_phase2<K, C, NTW, false>(acc2, aq, Xs + kk * TSTR + colw, TSTR, 1, wl2, wl2, slope);
 
     // ---- epilogue: + b2 [, / div], transposed through LDS (the intermediate is dead after the barrier), float4 row stores
@@ -612,9 +595,6 @@ void resblock_pair2(const FusedPair2Params p) {
             for (int e = 0; e < 4; ++e) vv[e] = vv[e] / div;
         }
         float* yp = yb + (int64_t)ch * L + q;
-#ifdef TTS_F2_EXP
-        if ((p.exp & 8) && vv[0] != 12345.678f) continue;
-#endif
         if (q + 3 < len) {
             *reinterpret_cast<float4*>(yp) = make_float4(vv[0], vv[1], vv[2], vv[3]);
         } else {
@@ -669,9 +649,6 @@ int32_t launch_fused_pair2(int32_t channels, const float* x, float* y, const flo
     p.b1 = b1; p.b2 = b2; p.lens = lens; p.len_mul = len_mul; p.L = L; p.dil = dil; p.batch = batch;
     p.mode = mode; p.div = div; p.slope = slope;
     p.compact = compact_order(lens, batch) ? 1 : 0;
-#ifdef TTS_F2_EXP
-    if (const char* e = exp_env("TTSAMD_F2_EXP")) p.exp = atoi(e);
-#endif
 #define TTS_F2W(KK, CC) if (wa && k == KK && channels == CC) return launch_fused2_k<KK, CC, 2, 2>(p, stream); \
                         if (wb && k == KK && channels == CC) return launch_fused2_k<KK, CC, 2, 1>(p, stream);
     TTS_F2W(3, 32) TTS_F2W(7, 32) TTS_F2W(11, 32) TTS_F2W(3, 64) TTS_F2W(7, 64) TTS_F2W(11, 64)

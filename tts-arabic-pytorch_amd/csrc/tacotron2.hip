@@ -10,7 +10,6 @@
 //             the LSTM cells are weight-streaming GEMVs (75 MB of fp32 weights per step, resident
 //             in L2/MALL), one wave64 per hidden unit; the stop test is read back every 8 steps
 //   postnet : 5 x [Conv1d k5 + BatchNorm folded (+ tanh)] on the conv engine, residual fused.
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -22,10 +21,6 @@
 #include "kernels.hpp"
 
 namespace ttsamd {
-
-#ifndef TP_SKIP
-#define TP_SKIP 0
-#endif
 
 struct TConv {
     int64_t w_off = 0, b_off = 0, w16_off = 0;
@@ -932,13 +927,9 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
     // computed ahead, while the fresh input is still on its way ("early" / "late" halves of a cell).
     constexpr unsigned SENT = 0xFFFFFFFFu;
     constexpr int POLL_LIM = 1 << 15;
-#ifndef TACO_POLL_SLEEP
-#define TACO_POLL_SLEEP 8
-#endif
-#ifndef TACO_POLL_GAP
-#define TACO_POLL_GAP 0                     /* s_sleep units between the first two polls: swept 0...64 on the box, 0 is best (tools/taco_gap_sweep.sh) */
-#endif
-#define TACO_BACKOFF __builtin_amdgcn_s_sleep(TACO_POLL_SLEEP);   /* between polls: the fabric carries everybody's polls AND the stores they wait for */
+    constexpr int POLL_SLEEP = 8;
+    constexpr int POLL_GAP = 0;             // s_sleep units between the first two polls: swept 0...64, 0 is best
+#define TACO_BACKOFF __builtin_amdgcn_s_sleep(POLL_SLEEP);   /* between polls: the fabric carries everybody's polls AND the stores they wait for */
     bool bad = false;
 #define TACO_OK4(v) (__builtin_bit_cast(unsigned, (v).x) != SENT && __builtin_bit_cast(unsigned, (v).y) != SENT && \
                      __builtin_bit_cast(unsigned, (v).z) != SENT && __builtin_bit_cast(unsigned, (v).w) != SENT)
@@ -1058,15 +1049,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
         taco_i4 rs, rq;                                              // this step's region (stores, fresh reads); the previous step's
         TACO_RSRC(rs, curw)
         TACO_RSRC(rq, p.xch + (int64_t)(s - p.s0) * p.step_floats)
-#ifdef TP_TIMING
-        unsigned fst[20];
-        int fsi = 0;
-#define TF_STAMP() fst[fsi++] = (unsigned)wall_clock64();
-#else
-#define TF_STAMP()
-#endif
-        TF_STAMP()   /* 0 top */
-        TF_STAMP()   /* 1 stop flags in */
         // ---------------- S1 late: the prenet super-steps of the attention cell, gates, new att_h
         {
             int vp = 0;
@@ -1117,7 +1099,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
             }
             __syncthreads();
         }
-        TF_STAMP()   /* 2 S1 late done (pre polled, att_h stored) */
         // ---------------- S2+S3: query rows of this block, partial energies of its tile
         {
             int vp = 0;
@@ -1179,7 +1160,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 taco_f4 xn[16];
 #pragma unroll
                 for (int n = 0; n < 16; ++n) xa[n] = TACO_LD4(rs, TR_ATT + (4 * (wid + 4 * n + vp) + kq) * 32 + bl * 4);
-                __builtin_amdgcn_s_sleep(TACO_POLL_GAP);
+                __builtin_amdgcn_s_sleep(POLL_GAP);
                 for (int spin = 0;; ++spin) {
                     bool okv = true;
 #pragma unroll
@@ -1192,7 +1173,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                     for (int n = 0; n < 16; ++n) xa[n] = xn[n];
                 }
             }
-            TF_STAMP()   /* 3 att_h in */
             {
                 taco_f4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0;
 #pragma unroll
@@ -1217,7 +1197,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                     if (d == 0) XST(R_EP + (g16 * 16 + tile) * PTp + pair, val);
                 }
             }
-            TF_STAMP()   /* 4 energies stored */
             // ---- tail: the att_h super-steps of the decoder cell (this step) and of the attention cell (next step), operands = xa
             {
                 const int wz = wid + vp;
@@ -1240,7 +1219,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 }
             }
         }
-        TF_STAMP()   /* 5 S2 tail done */
         // ---------------- S4: masked softmax over the tokens of utterance b4, context columns cg MC .. +MC
         if (b4 < B) {
             const int t = tid;
@@ -1251,7 +1229,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 float ev[16], en[16];
 #pragma unroll
                 for (int g = 0; g < 16; ++g) ev[g] = TACO_LD1(rs, eo + g * 16 * PTp);
-                __builtin_amdgcn_s_sleep(TACO_POLL_GAP);
+                __builtin_amdgcn_s_sleep(POLL_GAP);
                 for (int spin = 0;; ++spin) {
                     bool okv = true;
 #pragma unroll
@@ -1301,7 +1279,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
             }
         }
         __syncthreads();
-        TF_STAMP()   /* 6 S4 done (epart polled, ctx stored) */
         // ---------------- S5 late: the context super-steps of the decoder cell, gates, new dec_h
         {
             int vp = 0;
@@ -1317,7 +1294,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
             taco_f4 wc[NC];
 #pragma unroll
             for (int e = 0; e < NC; ++e) wc[e] = *reinterpret_cast<const taco_f4*>(wrowc + 16 * (64 + wz + 4 * e));
-            __builtin_amdgcn_s_sleep(TACO_POLL_GAP);
+            __builtin_amdgcn_s_sleep(POLL_GAP);
             for (int spin = 0;; ++spin) {
                 bool okv = true;
 #pragma unroll
@@ -1366,7 +1343,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
             }
         }
         __syncthreads();
-        TF_STAMP()   /* 7 S5 late done (ctx polled, dec_h stored, context tails) */
         // ---------------- S6: mel / gate row bid (< 81) and prenet layer-1 unit bid (folded) from [dec_h | ctx], on the matrix pipe:
         // tile rows alternate (row 81 + bid, row bid)
         {
@@ -1382,7 +1358,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 taco_f4 xn[16];
 #pragma unroll
                 for (int n = 0; n < 16; ++n) xd[n] = TACO_LD4(rs, TR_DEC + (4 * (wz + 4 * n) + kq) * 32 + bl * 4);
-                __builtin_amdgcn_s_sleep(TACO_POLL_GAP);
+                __builtin_amdgcn_s_sleep(POLL_GAP);
                 for (int spin = 0;; ++spin) {
                     bool okv = true;
 #pragma unroll
@@ -1419,7 +1395,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                     XST(R_FIN + bb, __builtin_bit_cast(float, fin));
                 }
             }
-            TF_STAMP()   /* 8 S6 done (dec_h polled, h0 stored) */
             // ---- tail: the dec_h super-steps of the NEXT step's decoder cell, operands = xd
             accD0 = taco_f4{0.f, 0.f, 0.f, 0.f};
             accD1 = accD0;
@@ -1434,14 +1409,13 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
             }
         }
         __syncthreads();
-        TF_STAMP()   /* 9 S6 tail done */
         // ---------------- S7: prenet layer 2, units 4 bid .. 4 bid + 3 on blocks 0..63
         if (bid < 64) {
             int vp = 0;
             asm volatile("" : "+v"(vp));
             const int tid = (int)threadIdx.x + vp;
             taco_f4 xa = TACO_LD4(rs, TR_H0 + tid * 32), xb = TACO_LD4(rs, TR_H0 + tid * 32 + 4);
-            __builtin_amdgcn_s_sleep(TACO_POLL_GAP);
+            __builtin_amdgcn_s_sleep(POLL_GAP);
             for (int spin = 0;; ++spin) {
                 const taco_f4 na = TACO_LD4(rs, TR_H0 + tid * 32), nb = TACO_LD4(rs, TR_H0 + tid * 32 + 4);
                 bool okv = true;                                      // (utterances >= B of a line are never written)
@@ -1471,11 +1445,6 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 if (bb < B) XST(TR_PRE + bid * 32 + bb * 4 + r, a);
             }
         }
-        TF_STAMP()   /* 10 S7 done */
-#ifdef TP_TIMING
-        if (threadIdx.x == 0)
-            for (int i = 0; i < 11; ++i) curw[TR_H0 + bid * 32 + 8 + i] = __builtin_bit_cast(float, fst[i]);
-#endif
         if (__syncthreads_or(bad)) {
             if (tid == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
@@ -1494,22 +1463,12 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
         const float* prv = p.xch + (int64_t)(s - p.s0) * p.step_floats;      // what step s - 1 left (region 0: zeros, or the previous segment's last region)
         float* curw = p.xch + (int64_t)(s - p.s0 + 1) * p.step_floats;       // what this step produces
         const float* cur = curw;
-#ifdef TP_TIMING
-        unsigned tstamp[13];
-        int tsi = 0;
-        const unsigned long long tp_c0 = clock64();
-#define TP_STAMP() tstamp[tsi++] = (unsigned)wall_clock64();
-#else
-#define TP_STAMP()
-#endif
-        TP_STAMP()
         taco_i4 rs;                                                  // raw buffer over this step's region: the coherent stores
         {
             const unsigned long long a = (unsigned long long)curw;
             rs.x = (int)(unsigned)a; rs.y = (int)(unsigned)(a >> 32); rs.z = p.step_floats * 4; rs.w = 0x00020000;
         }
         // ---------------- S1: attention LSTMCell on [pre | ctx | att_h]
-#if !(TP_SKIP & 1)
         {
             int vz = 0;
             asm volatile("" : "+v"(vz));                 // opaque zero: keeps the address arithmetic of this phase inside the
@@ -1562,11 +1521,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 if (bb < B) XST(TR_ATT + bid * 32 + bb * 4 + uu, sigmoidf_(go) * tanhf(c_att));
             }
         }
-#endif
-        TP_STAMP()
         if (!taco_grid_barrier(slots, ++epoch, err)) return;
-        TP_STAMP()
-#if !(TP_SKIP & 2)
         // ---------------- S2+S3: processed query of this block's 8 attention dims, partial energies of its tile
         {
             int vz = 0;
@@ -1617,11 +1572,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 if (d == 0) XST(R_EP + (g16 * 16 + tile) * PTp + pair, val);
             }
         }
-#endif
-        TP_STAMP()
         if (!taco_grid_barrier(slots, ++epoch, err)) return;
-        TP_STAMP()
-#if !(TP_SKIP & 4)
         // ---------------- S4: masked softmax over the tokens of utterance b4, context columns cg MC .. +MC
         if (b4 < B) {
             const int t = tid;
@@ -1666,11 +1617,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 XST(TR_CTX + (b4 * 32 + cg) * 32 + tid, a);
             }
         }
-#endif
-        TP_STAMP()
         if (!taco_grid_barrier(slots, ++epoch, err)) return;
-        TP_STAMP()
-#if !(TP_SKIP & 8)
         // ---------------- S5: decoder LSTMCell on [att_h | ctx | dec_h], weights in registers
         {
             int vz = 0;
@@ -1722,11 +1669,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 if (bb < B) XST(TR_DEC + bid * 32 + bb * 4 + uu, sigmoidf_(go) * tanhf(c_dec));
             }
         }
-#endif
-        TP_STAMP()
         if (!taco_grid_barrier(slots, ++epoch, err)) return;
-        TP_STAMP()
-#if !(TP_SKIP & 16)
         // ---------------- S6: mel / gate row bid (< 81) and prenet layer-1 unit bid (folded) from [dec_h | ctx]
         {
             float acc[16];
@@ -1774,10 +1717,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 }
             }
         }
-#endif
-        TP_STAMP()
         if (!taco_grid_barrier(slots, ++epoch, err)) return;
-        TP_STAMP()
         {
             int all = 1;
             for (int b = 0; b < B; ++b) all &= __builtin_bit_cast(int, cur[R_FIN + b]) != 0;
@@ -1806,16 +1746,7 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
                 if (bb < B) XST(TR_PRE + bid * 32 + bb * 4 + r, a);
             }
         }
-        TP_STAMP()
         if (!taco_grid_barrier(slots, ++epoch, err)) return;
-        TP_STAMP()
-#ifdef TP_TIMING
-        if (tid == 0)
-        {
-            for (int i = 0; i < 13; ++i) curw[TR_H0 + bid * 32 + 8 + i] = __builtin_bit_cast(float, tstamp[i]);
-            curw[TR_H0 + bid * 32 + 21] = __builtin_bit_cast(float, (unsigned)(clock64() - tp_c0));      // shader-clock cycles of this step
-        }
-#endif
     }
     }   // barrier schedule
     stp[0] = c_att; stp[1] = c_dec; stp[2] = cum;                    // for the next segment (if any)
@@ -1830,11 +1761,9 @@ __global__ __launch_bounds__(256) void taco_decoder_persistent(const TacoPersist
 // ------------------------------------------------------------------------------------ host
 
 // TTSAMD_TACO_PERSISTENT (read per call): see taco_persistent_mode()
-static int taco_persistent_mode() {          // 0 graph path (8-step hipGraph replay), 1 persistent kernel with grid barriers, 2 persistent kernel with
-    const char* e = opt_str(OPT_TACO_PERSISTENT);   // dataflow hand-offs and MFMA cells (default where it fits: 47.5 vs 57.5 us per step)
-    if (!e || !e[0]) return 2;
-    return (e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2;
-}
+// 0 graph path (8-step hipGraph replay), 1 persistent kernel with grid barriers, 2 persistent kernel with dataflow hand-offs and MFMA
+// cells (default where it fits: 47.5 vs 57.5 us per step)
+static int taco_persistent_mode() { return (int)opt_int(OPT_TACO_PERSISTENT, 2); }
 static bool taco_persistent_wanted() { return taco_persistent_mode() != 0; }
 
 struct TWs {
@@ -1851,11 +1780,7 @@ struct TWs {
 // steps per launch of the persistent decoder = regions of its exchange arena (TTSAMD_TACO_SEG: tests drive several segments on short runs).
 // Read by workspace_bytes and by infer alike; a value that grows between the two calls is caught by infer's own carve of the arena it was
 // given ("workspace of N bytes needed"), never written past.
-static int taco_segment_steps() {
-    const char* e = opt_str(OPT_TACO_SEG);
-    const int v = e ? atoi(e) : 512;
-    return std::max(8, v);
-}
+static int taco_segment_steps() { return (int)std::max<int64_t>(8, opt_int(OPT_TACO_SEG, 512)); }
 
 static void tcarve(const Taco2* h, Arena& a, int B, int L, int Tcap, TWs& w) {
     const ttsamd_tacotron2_cfg& c = h->cfg;
@@ -1944,7 +1869,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
     TTS_REQUIRE(B >= 1 && L >= 1 && L <= TACO_LMAX && max_step >= 1, "tacotron2_infer: bad batch/length/max_step");
     const ttsamd_tacotron2_cfg& c = h->cfg;
     TTS_REQUIRE(c.num_speakers <= 1 || speaker_ids, "tacotron2_infer: speaker_ids is null");
-    const double t_enter = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
     Arena a(ws, ws_bytes);
     TWs w;
     const int Tcap = max_step;
@@ -1984,8 +1908,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
     TTS_CHECK_HIP(hipMemsetAsync(w.dec_in, 0, (size_t)B * c.n_mels * sizeof(float), s));
     TTS_CHECK_HIP(hipMemsetAsync(mel_lens, 0, (size_t)B * sizeof(int32_t), s));
     TTS_CHECK_HIP(hipMemsetAsync(w.step, 0, sizeof(int32_t), s));
-    static const bool dbg = exp_env("TTSAMD_TACO_DEBUG") != nullptr;
-    auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     int steps = 0;
     bool done = false;
     // ---- the persistent decoder (one cooperative launch for the whole loop) when the geometry fits its residency plan
@@ -2000,14 +1922,14 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
         (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id);
         (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev_id);
         (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id);
-        const char* pe = opt_str(OPT_TACO_PERSISTENT);
-        const bool explicit_req = pe && (pe[0] == '1' || pe[0] == '2');          // an explicit request must run the persistent kernel or fail
+        const int req = (int)opt_int(OPT_TACO_PERSISTENT, 0);
+        const bool explicit_req = req != 0;                                     // an explicit request must run the persistent kernel or fail
         bool fits = want && B <= 8 && L <= 256 && (M == 512 || M == 640) && A == 1024 && D == 1024 && P == 256 && KS % 2 == 1 &&
                     (B * L + 15) / 16 + KS - 1 <= 256 &&      /* the alignment window of an energy tile: one word per thread */
                     lds <= (size_t)std::max(lds_max, 64 * 1024) && n_cu >= 256 && coop && w.tail_o > 0;
         if (explicit_req && !fits) {
-            set_error("tacotron2_infer: TTSAMD_TACO_PERSISTENT=%c but the persistent decoder does not fit (B=%d <= 8, L=%d <= 256, memory dim %d in "
-                      "{512, 640}, %zu B of LDS <= %d, %d CUs >= 256, cooperative launch %d)", pe[0], B, L, M, lds, lds_max, n_cu, coop);
+            set_error("tacotron2_infer: TTSAMD_TACO_PERSISTENT=%d but the persistent decoder does not fit (B=%d <= 8, L=%d <= 256, memory dim %d in "
+                      "{512, 640}, %zu B of LDS <= %d, %d CUs >= 256, cooperative launch %d)", req, B, L, M, lds, lds_max, n_cu, coop);
             return TTSAMD_EINVAL;
         }
         if (fits && !explicit_req) {
@@ -2033,7 +1955,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
             std::lock_guard<std::mutex> lock(h->mu);
             q.state = w.pstate;
             void* args[] = {&q};
-            const double t0 = now_us();
             int32_t tail[2] = {0, 0};                                   // err_o and steps_o are 64 floats apart: two copies
             // one cooperative launch per segment of at most w.seg steps (TacoPersist: why); a whole bench-size decode (448 steps) is one
             for (int s0 = 0; s0 < max_step; s0 += w.seg) {
@@ -2077,7 +1998,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
                 // an unfinished segment reports max_step): no extra segment (a region copy, an 82 MB memset and a cooperative launch for nothing)
                 if (tail[0] != 0 || (int64_t)tail[1] <= (int64_t)q.s1) break;
             }
-            if (dbg) fprintf(stderr, "[taco] persistent decoder: %.0f us for %d steps (%zu B of LDS per block)\n", now_us() - t0, (int)tail[1], lds);
             if (tail[0] != 0) {
                 // a block waited > 80 ms for another one: the 256 blocks were not all resident (CUs held by other streams).  The
                 // graph path below recomputes the whole loop from the same state; only an explicit request is an error.
@@ -2096,16 +2016,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
                 steps = tail[1];
                 done = true;
                 h->persist_backoff = 0;
-            }
-            if (const char* dump = done ? exp_env("TTSAMD_TACO_DUMP") : nullptr) {   // debugging aid: the region the last step produced
-                std::vector<float> hx((size_t)w.step_floats);
-                TTS_CHECK_HIP(hipMemcpy(hx.data(), w.xch + (int64_t)(steps - (steps > 0 ? (steps - 1) / w.seg * w.seg : 0)) * w.step_floats, hx.size() * sizeof(float), hipMemcpyDeviceToHost));
-                if (FILE* f = fopen(dump, "wb")) {
-                    const int32_t hdr[8] = {B, L, M, steps, w.Lp, w.PTp, w.step_floats, 0};
-                    fwrite(hdr, sizeof(hdr), 1, f);
-                    fwrite(hx.data(), sizeof(float), hx.size(), f);
-                    fclose(f);
-                }
             }
         }
     }
@@ -2131,9 +2041,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
     TTS_CHECK_HIP(hipEventRecord(h->ev_in, caller));          // encoder + state resets were queued on the caller's stream
     s = h->loop_stream;
     TTS_CHECK_HIP(hipStreamWaitEvent(s, h->ev_in, 0));
-    if (dbg) (void)hipStreamSynchronize(s);
-    const double t_cap0 = now_us();
-    if (dbg) fprintf(stderr, "[taco] encoder + state reset (synced): %.0f us\n", t_cap0 - t_enter);
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     TTS_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
@@ -2165,7 +2072,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
         set_error("tacotron2_infer: capturing the decoder step graph failed: %s", hipGetErrorString(cap_err));
         return TTSAMD_EHIP;
     }
-    const double t_loop0 = now_us();
     hipError_t run_err = hipSuccess;
     for (int g = 0; steps < max_step && run_err == hipSuccess; ++g) {
         run_err = hipGraphLaunch(exec, s);
@@ -2182,9 +2088,7 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
             if (all && c.decoder_early_stopping != 0) break;
         }
     }
-    const double t_loop1 = now_us();
     if (run_err == hipSuccess) run_err = hipStreamSynchronize(s);   // host-blocking: the caller's stream may go on
-    if (dbg) fprintf(stderr, "[taco] encoder+reset %.0f us (synced), capture+instantiate %.0f us, loop host %.0f us, loop total %.0f us for %d steps\n", 0.0, t_loop0 - t_cap0, t_loop1 - t_loop0, now_us() - t_loop0, steps);
     (void)hipGraphExecDestroy(exec);
     s = caller;
     if (run_err != hipSuccess) {
@@ -2214,10 +2118,6 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
         const int y_cs = last ? Tcap : T;
         TTS_TRY(tconv(h, cv, px, px_bs, px_cs, y, y_bs, y_cs, last ? mel_raw : nullptr, B, T, last ? 0 : 3, s));
         px = y; px_bs = y_bs; px_cs = y_cs;
-    }
-    if (dbg) {
-        (void)hipStreamSynchronize(s);
-        fprintf(stderr, "[taco] whole call (synced): %.0f us, T=%d\n", now_us() - t_enter, T);
     }
     return 0;
 }

@@ -3,7 +3,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# TTSAMD_LIB: another build of the SAME sources (tools/f2_exp.sh: a timing build in /tmp); the product path never sets it
+# TTSAMD_LIB: another build of the SAME sources (A/B of two builds: tools/fp_digest.py); the product path never sets it
 LIB_PATH = os.environ.get('TTSAMD_LIB') or os.path.join(_HERE, 'lib', 'libttsamd.so')
 
 
