@@ -1,6 +1,6 @@
 """bench.py — audio samples/s of the FastPitch -> HiFi-GAN hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--tokens 64] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--tokens 64] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): FastPitch+HiFi-GAN, synthetic 64-phoneme x batch 32
 per GPU, fp32, synthetic weights (ttsamd.synth, seed 0), forced durations dur_tgt in [2,12]
@@ -10,8 +10,11 @@ as the reference does) -> length regulator -> decoder -> ragged batched HiFi-GAN
 HBM.  N>1: one process per GPU — under torch.distributed.run, or started by this script itself when
 `--gpus N` is typed without it — weights broadcast once from rank 0 over RCCL (ttsamd_dp_*), B utterances
 PER RANK (weak scaling), every rank's lengths all-gathered in the step's one host sync and the packed
-audio fanned in to rank 0 every step.  Prints ONE JSON line on rank 0; at N=1 the line also carries
-`configs`: the batch-1 and batch-8 sub-results of the same step function.
+audio fanned in to rank 0 every step.  Prints ONE JSON line on rank 0: the headline and the roofline of the K timed
+steps, nothing that needs a run of its own.
+--full: at N=1 the line also carries `configs` (the batch-1 and batch-8 sub-results of the same step function, the
+other BASELINE configs), `d2h` and `cpu_baseline`, each timed after the headline's steps (--no-small, --no-extra and
+--no-cpu-baseline leave parts of it out).
 --dump-outputs DIR: what the last timed step returned (mel, dec_lens, wave of rank 0) as DIR/<name>.npy, so that two
 builds can be compared output for output on the same seeded inputs.
 """
@@ -519,8 +522,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32, help='utterances per GPU')
     ap.add_argument('--tokens', type=int, default=64)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-small', action='store_true', help='skip the batch 1 / batch 8 sub-results (N=1 only)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every sub-result (N=1 only): batch 1 / 8 and the other configs, the D2H '
+                         'copy, the CPU baselines; without it the run does only what the headline needs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-small', action='store_true', help='with --full: skip the batch 1 / batch 8 sub-results (N=1 only)')
     ap.add_argument('--pipeline', action='store_true', default=None,
                     help='two HIP streams (ttsamd.pipeline): FastPitch of step i+1 under HiFi-GAN of step i, same work and same '
                          'results per step (bit-identical).  The default at every precision and every N: fp32 +2 %% at B=32 (the conv '
@@ -531,7 +537,8 @@ def main():
                     help='N > 1: weak = --batch utterances PER RANK (default); strong = --batch utterances in total, B/N per rank '
                          '(north star: B=256 on 1/2/4/8 GPUs)')
     ap.add_argument('--no-extra', action='store_true',
-                    help='skip the extra driver-visible sub-results (config 3 bf16 share, config 4 Tacotron2, config 5 Vocos, D2H)')
+                    help='with --full: skip the extra driver-visible sub-results (config 3 bf16 share, config 4 Tacotron2, config 5 '
+                         'Vocos, D2H)')
     ap.add_argument('--precision', default='f32', choices=['f32', 'bf16', 'bf16x3'],
                     help='MFMA operand precision of the conv/linear GEMMs (f32 = BASELINE config 2; bf16 = config 3; '
                          'bf16x3 = split bf16, fp32-class accuracy)')
@@ -894,7 +901,8 @@ def main():
             sections[name] = round(now - t_sec, 1)
             t_sec = now
 
-        if world == 1 and not args.no_small and B > 8:
+        full = args.full and world == 1              # the sub-results below: only when asked for, N = 1 only
+        if full and not args.no_small and B > 8:
             out['configs'] = [small_config(1), small_config(8)]
             lap('batch 1 / 8')
             if args.precision == 'f32' and args.pipeline and B == 32:
@@ -909,9 +917,9 @@ def main():
                 lap('C2 predicted durations')
             if not args.no_extra:
                 out['configs'] += extra_configs(args, dev, fp, hg, ids, dur, hop, small_config, wall_roofline, sync, lap)
-        if world == 1 and not args.no_extra:
+        if full and not args.no_extra:
             out['d2h'] = d2h_probe(wave, dec_lens, hop)
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(fp_sd, hg_sd, Lt)
             lap('cpu_baseline')
             try:

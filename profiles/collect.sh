@@ -8,7 +8,7 @@ R=${1:-r6}
 O=gpurun_out/collect_$R
 mkdir -p $O
 export TMPDIR=/tmp
-python3 bench.py > $O/final_bench_line.json 2> $O/bench.err
+python3 bench.py --full > $O/final_bench_line.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-small --no-extra > $O/stats.log 2>&1
 # one-stream schedule: per-launch durations that do not overlap (per-instantiation TFLOP/s table)
 TTSAMD_HIFIGAN_STREAMS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1 -- python3 bench.py --no-pipeline --steps 5 --warmup 2 --no-cpu-baseline --no-small --no-extra > $O/stats1.log 2>&1
@@ -23,7 +23,7 @@ TTSAMD_HIFIGAN_STREAMS=0 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-form
 TTSAMD_HIFIGAN_STREAMS=0 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_mfma -- python3 bench.py --no-pipeline --steps 1 --warmup 1 --no-cpu-baseline --no-small --no-extra > $O/pmc_mfma.log 2>&1
 FRAMES=$(python3 -c "import json;print(json.load(open('$O/final_bench_line.json'))['config']['frames_per_step_rank0'])")
 python3 profiles/traffic_from_pmc.py $O/pmc_fetch $O/pmc_write $O/conv_log.csv $FRAMES $O/traffic_calib.json > $O/traffic.json
-for p in bf16x3 bf16; do python3 bench.py --precision $p --no-cpu-baseline --no-extra > $O/${p}_bench_line.json 2>> $O/bench.err; done
+for p in bf16x3 bf16; do python3 bench.py --full --precision $p --no-cpu-baseline --no-extra > $O/${p}_bench_line.json 2>> $O/bench.err; done
 python3 bench.py --precision bf16x3 --no-pipeline --no-cpu-baseline --no-small --no-extra > $O/bf16x3_one_stream_bench_line.json 2>> $O/bench.err
 # config 3 inside the 1e-3 / 1e-4 tolerance (split bf16 on the octet engine, round 5): kernel stats (one stream), MFMA counters, per-layer table
 TTSAMD_HIFIGAN_STREAMS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $O/xstats1 -- python3 bench.py --precision bf16x3 --no-pipeline --steps 5 --warmup 2 --no-cpu-baseline --no-small --no-extra > $O/xstats1.log 2>&1

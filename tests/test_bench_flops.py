@@ -4,6 +4,8 @@ utterance incl. the 0.26 GFLOP of attention scores that do not run in conv launc
 import importlib.util
 import os
 
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -93,3 +95,38 @@ def test_bench_rejects_zero_steps():
     import sys
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '0'], capture_output=True, text=True)
     assert r.returncode == 2 and '--steps' in r.stderr
+
+
+def test_bench_full_option_listed():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--help'], capture_output=True, text=True)
+    assert r.returncode == 0 and '--full' in r.stdout
+
+
+def _bench_line(*extra):
+    import json
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
+                        '--batch', '16', '--tokens', '16', *extra], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_and_full_adds_the_sub_results():
+    """A plain run prints the headline of its timed steps and runs nothing else; --full adds the sub-results after them (here
+    batch 1 / 8 only: --no-extra and --no-cpu-baseline keep the test short)."""
+    plain = _bench_line()
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'roofline'):
+        assert k in plain, k
+    assert plain['value'] > 0 and plain['ms_per_step'] > 0 and plain['dtype'] == 'f32'
+    for k in ('configs', 'd2h', 'cpu_baseline', 'bench_sections_s'):
+        assert k not in plain, k
+    full = _bench_line('--full', '--no-extra', '--no-cpu-baseline')
+    assert [c['batch'] for c in full['configs']] == [1, 8] and 'batch 1 / 8' in full['bench_sections_s']
+    assert 'd2h' not in full and 'cpu_baseline' not in full
+    assert full['config']['frames_per_step_rank0'] == plain['config']['frames_per_step_rank0']
