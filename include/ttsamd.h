@@ -50,6 +50,9 @@ typedef struct ttsamd_hifigan_cfg {
     int32_t resblock_kernel_sizes[8]; /* 3,7,11 */
     int32_t n_dilations;              /* 3 */
     int32_t resblock_dilations[8][8]; /* (1,3,5) each */
+    int32_t resblock;                 /* 1 = ResBlock1 (V1), 2 = ResBlock2 (V3: two convs per block, dilations [j][0] and [j][1];
+                                       * n_dilations >= 2); 0 is read as 1, anything else is TTSAMD_EINVAL at create.  A ResBlock2
+                                       * generator runs in exact fp32 only: under ttsamd_set_precision(1 | 2) its forward is TTSAMD_EINVAL */
 } ttsamd_hifigan_cfg;
 
 /* models/fastpitch/__init__.py:3-41 (net_config), only the fields inference reads */
@@ -108,9 +111,10 @@ const char* ttsamd_last_error(void);
 /* ABI revision of this header.  Bumped whenever a struct gains a field or an argument changes meaning (2: ttsamd_tacotron2_cfg
  * gained decoder_early_stopping, ttsamd_profile_read's third value became the number of timed sections; 3: ttsamd_dp_* may be
  * bound twice per process, one communicator per stream; 4: ttsamd_bfo_resblock_chain takes the kernel size as its last argument; 5: the ttsamd_bfo3_* entries, ttsamd_conv1d_ex; 6: ttsamd_set_option / ttsamd_get_option / ttsamd_option_name / ttsamd_options_check replace the per-call
- * environment reads, ttsamd_resblock_pair takes the size of `packed`, ttsamd_resblock_pair_packed_floats).  ttsamd_version() returns the value the library was BUILT with: a caller
+ * environment reads, ttsamd_resblock_pair takes the size of `packed`, ttsamd_resblock_pair_packed_floats; 7: ttsamd_fastpitch_set_batch_mode;
+ * 8: ttsamd_hifigan_cfg.resblock (ResBlock2 generators), ttsamd_resblock2 / ttsamd_resblock2_packed_floats).  ttsamd_version() returns the value the library was BUILT with: a caller
  * compiled against another revision must refuse to run (ttsamd/lib.py does). */
-#define TTSAMD_ABI_VERSION 7
+#define TTSAMD_ABI_VERSION 8
 int32_t ttsamd_version(void);
 /* Run-time routing options: every switch that routes between kernels / schedules that both ship (INTEGRATION.md lists them with their
  * defaults).  An option's value is seeded ONCE from the environment variable of the same name (TTSAMD_<NAME>) when the library is first
@@ -301,6 +305,19 @@ int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const fl
                              int32_t batch, int32_t mode, float div, float slope, int32_t variant, float* packed, int64_t packed_floats,
                              void* stream);
 
+/* One ResBlock2 (vocoder/hifigan/models.py:62-83) in exact fp32:
+ *   x1 = x + conv1d(lrelu(x, slope), w1, dilation dil1) + b1;  v = x1 + conv1d(lrelu(x1, slope), w2, dilation dil2) + b2;
+ *   y = v | y + v | (y + v) / div  (mode 0 | 1 | 2)
+ * x, y [B][C][L] (y != x), w1 / w2 [C][C][K] (torch layout, DEVICE), lens int64 [B] or NULL: every conv zero-pads at the true edge
+ * lens[b] * len_mul and nothing past it is written.  variant 1: two single-conv launches (C = 32 / 64 / 128, k = 3 / 5 / 7 / 11,
+ * dilation 1..16; x1 goes through a stream-ordered temporary of B * C * L floats), 2: both convs in one launch with x1 in LDS (C = 32 /
+ * 64, k = 3 / 5 / 7 / 11, dilation 1..16, (k - 1) * dil2 <= 256).  A geometry the variant does not cover is TTSAMD_EINVAL.  `packed` is
+ * scratch for the re-laid-out weights: ttsamd_resblock2_packed_floats(C, K, variant) floats; a smaller `packed_floats` is TTSAMD_EINVAL. */
+int64_t ttsamd_resblock2_packed_floats(int32_t channels, int32_t k, int32_t variant);
+int32_t ttsamd_resblock2(const float* x, float* y, const float* w1, const float* b1, const float* w2, const float* b2, int32_t channels,
+                         int32_t k, int32_t dil1, int32_t dil2, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch, int32_t mode,
+                         float div, float slope, int32_t variant, float* packed, int64_t packed_floats, void* stream);
+
 /* ---- bf16 octet engine (BASELINE config 3), kernel-level entries used by the parity tests and the roofline bench.
  *      Activations are [B][C/8][L][8] bf16 ("octet" layout: one 16-byte entry = 8 channels of one position = one lane's B
  *      operand of v_mfma_f32_32x32x16_bf16), stored PRE-ACTIVATED: a = leaky_relu(x, slope of the consumer).  Replaces
@@ -373,6 +390,7 @@ int32_t ttsamd_bfo3_conv_post(const void* x, const float* w, const float* bias, 
  *   1 bf16 operands, fp32 accumulate — config 3: HiFi-GAN on the octet engine above (v_mfma_f32_32x32x16_bf16, bf16
  *     activations in HBM), the other models on v_mfma_f32_32x32x8_bf16_1k with fp32 activations;
  *   2 split bf16 (x = hi + lo, 3 MFMAs per product): fp32-class accuracy at bf16 MFMA rate.
+ * A ResBlock2 (V3) HiFi-GAN generator is built for fp32 only: ttsamd_hifigan_forward refuses it under 1 / 2 (TTSAMD_EINVAL).
  * Activations, LayerNorm, softmax, tanh, the FFTs and all integer work stay fp32/int64. */
 int32_t ttsamd_set_precision(int32_t precision);
 int32_t ttsamd_get_precision(void);

@@ -589,6 +589,57 @@ int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const fl
     return rc;
 }
 
+int64_t ttsamd_resblock2_packed_floats(int32_t channels, int32_t k, int32_t variant) {
+    // the two direct packings (both variants read the same layout)
+    if (channels < 1 || k < 1 || (variant != 1 && variant != 2)) return 0;
+    return 2 * (int64_t)channels * k * channels;
+}
+
+int32_t ttsamd_resblock2(const float* x, float* y, const float* w1, const float* b1, const float* w2, const float* b2, int32_t channels,
+                         int32_t k, int32_t dil1, int32_t dil2, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch, int32_t mode,
+                         float div, float slope, int32_t variant, float* packed, int64_t packed_floats, void* stream) {
+    TTS_REQUIRE(x && y && w1 && b1 && w2 && b2 && packed && channels % 32 == 0 && channels >= 32 && k >= 1 && batch >= 1 && L >= 1 &&
+                len_mul >= 1 && mode >= 0 && mode <= 2 && x != y, "resblock2: bad argument");
+    TTS_REQUIRE(variant == 1 || variant == 2, "resblock2: variant %d (1: two single-conv launches, 2: both convs in one launch)", variant);
+    TTS_REQUIRE(packed_floats >= ttsamd_resblock2_packed_floats(channels, k, variant),
+                "resblock2: `packed` holds %lld floats, C = %d, k = %d needs %lld (ttsamd_resblock2_packed_floats)", (long long)packed_floats,
+                channels, k, (long long)ttsamd_resblock2_packed_floats(channels, k, variant));
+    if (variant == 1) {
+        TTS_REQUIRE(resblock2_conv_supported(channels, k, dil1, L, x, y) && resblock2_conv_supported(channels, k, dil2, L, x, y),
+                    "resblock2: variant 1 does not cover C = %d, k = %d, dilations %d / %d (C = 32 / 64 / 128, k = 3 / 5 / 7 / 11, "
+                    "dilation 1..16)", channels, k, dil1, dil2);
+    } else {
+        TTS_REQUIRE(resblock2_pair_supported(channels, k, dil1, dil2, L, x, y),
+                    "resblock2: variant 2 does not cover C = %d, k = %d, dilations %d / %d (C = 32 / 64, k = 3 / 5 / 7 / 11, dilation "
+                    "1..16, (k - 1) * dil2 <= 256)", channels, k, dil1, dil2);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)channels * k * channels;
+    for (int i = 0; i < 2; ++i) {
+        hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, i == 0 ? w1 : w2, channels,
+                           channels, k, channels, packed + i * n);
+        TTS_CHECK_HIP(hipGetLastError());
+    }
+    prof_begin(s, 2.0 * (2.0 * channels * channels * k));
+    int32_t rc;
+    if (variant == 2) {
+        rc = launch_resblock2_pair(channels, x, y, packed, b1, packed + n, b2, k, dil1, dil2, lens, len_mul, L, batch, mode, div, slope, s);
+    } else {
+        // x1 goes through a stream-ordered temporary of B * C * L floats
+        float* x1 = nullptr;
+        TTS_CHECK_HIP(hipMallocAsync((void**)&x1, (size_t)batch * channels * L * sizeof(float), s));
+        rc = launch_resblock2_conv(channels, x, x1, packed, b1, k, dil1, lens, len_mul, L, batch, 0, 1.f, slope, s);
+        if (rc == 0) rc = launch_resblock2_conv(channels, x1, y, packed + n, b2, k, dil2, lens, len_mul, L, batch, mode, div, slope, s);
+        const hipError_t e = hipFreeAsync(x1, s);
+        if (rc == 0 && e != hipSuccess) {
+            set_error("resblock2: hipFreeAsync failed: %s", hipGetErrorString(e));
+            rc = TTSAMD_EHIP;
+        }
+    }
+    prof_end(s);
+    return rc;
+}
+
 int32_t ttsamd_set_precision(int32_t precision) {
     TTS_REQUIRE(precision >= 0 && precision <= 2, "set_precision: 0 = fp32 MFMA, 1 = bf16 MFMA, 2 = split-bf16 MFMA");
     g_precision = precision;

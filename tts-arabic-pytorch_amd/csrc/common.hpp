@@ -85,7 +85,8 @@ inline hipError_t lds_opt_in(const void* fn, int bytes, std::atomic<uint64_t>& d
     X(XCD_WMAX_KB, 0, 0, 1 << 20) /* ... weight footprint per XCD that keeps co-tile classes together */    \
     X(DEEP_SPLITK, 0, 0, 1)       /* 128 x 64 tiles with split K for the deep conv-FF conv at batch 7..13 */ \
     X(TACO_PERSISTENT, 0, 0, 2)   /* Tacotron2 decoder: 0 graph replay, 1 grid-barrier kernel, 2 dataflow kernel */ \
-    X(TACO_SEG, 0, 8, 1 << 20)    /* ... decoder steps per persistent launch (default 512) */
+    X(TACO_SEG, 0, 8, 1 << 20)    /* ... decoder steps per persistent launch (default 512) */ \
+    X(RESBLOCK2_PAIR, 1, 0, 0x3f) /* ResBlock2 as one launch (resblock2.hip): bit 3 ci + ki, C = 32 / 64, k = 3 / 5 / 7 */
 enum Opt : int {
 #define TTS_OPT_ENUM(name, kind, lo, hi) OPT_##name,
     TTS_OPTIONS(TTS_OPT_ENUM)
@@ -193,6 +194,17 @@ bool fused_pair4_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, 
 int32_t launch_fused_pair4(int32_t channels, const float* x, float* y, const float* w1_wino4, const float* b1, const float* w2_wino4,
                            const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
                            int32_t mode, float div, float slope, hipStream_t stream);
+// HiFi-GAN ResBlock2 (resblock2.hip), exact fp32: one conv y = x + conv(lrelu(x), w, dil) + b with the stage-sum epilogue (C = 32 / 64 /
+// 128, k = 3 / 5 / 7 / 11, dilation 1..16), and both convs of a ResBlock2 in one launch (C = 32 / 64).  Direct weight packing
+// (pack_conv_weight); x != y.
+bool resblock2_conv_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
+int32_t launch_resblock2_conv(int32_t channels, const float* x, float* y, const float* w, const float* b, int32_t k, int32_t dil,
+                              const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch, int32_t mode, float div, float slope,
+                              hipStream_t stream);
+bool resblock2_pair_supported(int32_t channels, int32_t k, int32_t d1, int32_t d2, int32_t L, const float* x, const float* y);
+int32_t launch_resblock2_pair(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
+                              const float* b2, int32_t k, int32_t d1, int32_t d2, const int64_t* lens, int32_t len_mul, int32_t L,
+                              int32_t batch, int32_t mode, float div, float slope, hipStream_t stream);
 // Winograd F(2,3) path of the k = 3, dilation-1 convs (conv_wino.hip): routing test, launcher, host-side filter transform + packing
 int wino_route(const ConvParams& p);       // 0: direct kernel, 1: conv1d_wino_f32, 2: conv1d_wino2_f32, 3: conv1d_wino4_f32 (conv_wino.hip)
 int32_t launch_wino(const ConvParams& p, hipStream_t stream);

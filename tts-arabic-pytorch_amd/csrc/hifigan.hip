@@ -1,7 +1,8 @@
-// HiFi-GAN V1 generator on the MFMA conv engine: handle creation (weight-norm fold, weight
+// HiFi-GAN generator on the MFMA conv engine: handle creation (weight-norm fold, weight
 // re-layout, upload) and the batched ragged forward.
 // Replaces vocoder.load_hifigan (vocoder/__init__.py:3-20) and Generator.forward
-// (vocoder/hifigan/models.py:111-127) incl. ResBlock1.forward (:46-53).
+// (vocoder/hifigan/models.py:111-127) incl. ResBlock1.forward (:46-53) and, for V3 configs (resblock "2"),
+// ResBlock2.forward (:62-83) on resblock2.hip (fp32 only).
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -31,6 +32,22 @@ constexpr int kPair4MinK = 7;
 constexpr unsigned kFused2MaskN1 = 0x000;     // 128-column blocks (the direct-arithmetic kernels only): none by default
 constexpr int64_t kFused2SmallColumns = 2 * 256 * 252;   // batch x positions under which a stage counts as a small problem
 
+// ResBlock2 (V3) routing: which (C, k) go out as ONE resblock2_pair launch instead of two resblock2_conv launches.  Bit 3 ci + ki,
+// ci = 0 / 1 for C = 32 / 64, ki = 0 / 1 / 2 for k = 3 / 5 / 7; TTSAMD_RESBLOCK2_PAIR (hex) replaces the default, read per call.
+// Default none: same-run A/B of the V3 vocoder (tools/hifigan_v3_bench.py, profiles/r7/hifigan_v3_bench.jsonl) with every pair fused
+// (3f) against none (0): batch 1 0.975 vs 0.894 ms, batch 8 2.91 vs 2.58, batch 32 10.38 vs 8.82.  The fused launch writes the stage
+// sum, so on three streams it waits for the previous branch as a whole, where two conv launches overlap conv 1 of all branches
+// (per launch the fused kernel is the faster one).
+constexpr unsigned kResblock2PairMask = 0x00;
+
+static bool resblock2_pair_choice(unsigned mask, int32_t channels, int32_t k, int32_t d1, int32_t d2, int32_t L, const float* x,
+                                  const float* y) {
+    const int ci = channels == 32 ? 0 : (channels == 64 ? 1 : -1);
+    const int ki = k == 3 ? 0 : (k == 5 ? 1 : (k == 7 ? 2 : -1));
+    if (ci < 0 || ki < 0 || !(mask & (1u << (3 * ci + ki)))) return false;
+    return resblock2_pair_supported(channels, k, d1, d2, L, x, y);
+}
+
 struct ConvW {
     int64_t w_off = 0, b_off = 0;  // float offsets into the device weight blob
     int64_t w16_off = 0, w_n = 0;  // bf16 planes (hi, lo) in the uint16 blob; packed element count
@@ -50,6 +67,7 @@ struct HifiGan {
     std::vector<ConvW> ups;
     std::vector<ConvW> c1, c2;  // [stage*n_kernels + j][m]
     int hop = 1;
+    bool rb2 = false;    // ResBlock2 generator (cfg.resblock == 2): c1[r] / c2[r] are convs.0 / convs.1 of resblocks.r
     int64_t max_cl = 0;  // max over stages of C * (L / T)
     bool bfo_ok = false; // every layer fits the bf16 octet engine (config 3 path, hifigan_forward_bfo)
     // the three ResBlocks of a stage run on three streams (created and first dispatched in hifigan_create; guarded by mu)
@@ -195,8 +213,9 @@ static void add_bf16(std::vector<float>& blob, std::vector<uint16_t>& blob16, Co
     split_packed_bf16(blob.data() + cw.w_off, n, blob16.data() + cw.w16_off);
 }
 
+// direct_only: the direct packing and the bias only (the ResBlock2 convs: resblock2.hip reads nothing else)
 static int32_t add_conv(const TensorMap& tm, const std::string& base, int cin, int cout, int k,
-                        std::vector<float>& blob, std::vector<uint16_t>& blob16, ConvW& cw) {
+                        std::vector<float>& blob, std::vector<uint16_t>& blob16, ConvW& cw, bool direct_only = false) {
     std::vector<float> w;
     int64_t shp[3];
     TTS_TRY(folded_weight(tm, base, 3, w, shp));
@@ -206,6 +225,10 @@ static int32_t add_conv(const TensorMap& tm, const std::string& base, int cin, i
     cw.w_off = (int64_t)blob.size();
     blob.resize(blob.size() + (size_t)cin * k * cout_padded(cout));
     pack_conv_weight(w.data(), cout, cin, k, blob.data() + cw.w_off);
+    if (direct_only) {
+        blob.resize(align_up((int64_t)blob.size(), 64));
+        return get_bias(tm, base, cout, blob, cw.b_off);
+    }
     add_bf16(blob, blob16, cw, (int64_t)cin * k * cout_padded(cout));
     if ((k == 3 || k == 7 || k == 11) && cin % 8 == 0 && cout % 32 == 0) {      // (cout = 32: the fused pairs' Winograd phase B)
         blob.resize(align_up((int64_t)blob.size(), 64));
@@ -241,10 +264,16 @@ int32_t hifigan_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_hif
     TTS_REQUIRE(weights && cfg && out, "hifigan_create: null argument");
     TTS_REQUIRE(cfg->n_ups >= 1 && cfg->n_ups <= 8 && cfg->n_kernels >= 1 && cfg->n_kernels <= 8 &&
                 cfg->n_dilations >= 1 && cfg->n_dilations <= 8, "hifigan_create: bad config counts");
+    const int rb = cfg->resblock == 0 ? 1 : cfg->resblock;
+    TTS_REQUIRE(rb == 1 || rb == 2, "hifigan_create: resblock %d (1 = ResBlock1, 2 = ResBlock2)", cfg->resblock);
+    TTS_REQUIRE(rb == 1 || cfg->n_dilations >= 2, "hifigan_create: a ResBlock2 takes two dilations per kernel size, %d given",
+                cfg->n_dilations);
     TensorMap tm;
     for (int i = 0; i < n; ++i) tm[weights[i].name] = &weights[i];
     auto* h = new HifiGan();
     h->cfg = *cfg;
+    h->cfg.resblock = rb;
+    h->rb2 = rb == 2;
     std::vector<float> blob;
     std::vector<uint16_t> blob16;
     const int c0 = cfg->upsample_initial_channel;
@@ -294,6 +323,22 @@ int32_t hifigan_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_hif
         h->max_cl = std::max<int64_t>(h->max_cl, (int64_t)ch * mul);
         for (int j = 0; rc == 0 && j < cfg->n_kernels; ++j) {
             const int r = i * cfg->n_kernels + j, kk = cfg->resblock_kernel_sizes[j];
+            if (h->rb2) {
+                // exactly two convs per ResBlock2, dilations [j][0] / [j][1] (further entries are ignored, as by the reference)
+                if (!resblock2_conv_supported(ch, kk, cfg->resblock_dilations[j][0], 1, nullptr, blob.data()) ||
+                    !resblock2_conv_supported(ch, kk, cfg->resblock_dilations[j][1], 1, nullptr, blob.data())) {
+                    set_error("hifigan: ResBlock2 at C = %d, k = %d, dilations %d / %d is not built (C = 32 / 64 / 128, k = 3 / 5 / 7 / 11, "
+                              "dilation 1..16)", ch, kk, cfg->resblock_dilations[j][0], cfg->resblock_dilations[j][1]);
+                    rc = TTSAMD_EINVAL;
+                    break;
+                }
+                ConvW a, b;
+                rc = add_conv(tm, "resblocks." + std::to_string(r) + ".convs.0", ch, ch, kk, blob, blob16, a, true);
+                if (rc == 0) rc = add_conv(tm, "resblocks." + std::to_string(r) + ".convs.1", ch, ch, kk, blob, blob16, b, true);
+                h->c1.push_back(a);
+                h->c2.push_back(b);
+                continue;
+            }
             for (int m = 0; rc == 0 && m < cfg->n_dilations; ++m) {
                 ConvW a, b;
                 rc = add_conv(tm, "resblocks." + std::to_string(r) + ".convs1." + std::to_string(m), ch, ch, kk, blob, blob16, a);
@@ -305,7 +350,7 @@ int32_t hifigan_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_hif
         }
     }
     h->hop = mul;
-    if (rc == 0) {
+    if (rc == 0 && !h->rb2) {
         // the bf16 octet engine covers this generator if every layer was packed for it
         bool ok = h->conv_pre.wo_off >= 0 && ch == 32 && cfg->num_mels % 8 == 0;
         for (const ConvW& cw : h->ups) ok = ok && cw.wo_off >= 0;
@@ -406,6 +451,8 @@ int64_t hifigan_workspace_bytes(const HifiGan* h, int32_t B, int32_t T) {
 int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens, int32_t B, int32_t T, float* wave,
                         void* ws, int64_t ws_bytes, hipStream_t s) {
     TTS_REQUIRE(h && mel && wave && B >= 1 && T >= 1, "hifigan_forward: bad argument");
+    TTS_REQUIRE(!h->rb2 || default_precision() == 0, "hifigan_forward: a ResBlock2 generator is built for f32 only (precision %d "
+                "requested; ttsamd_set_precision(0))", default_precision());
     Arena a(ws, ws_bytes);
     const bool multi = use_branch_streams(h, B, T);
     const int nb = multi ? 3 : 1;
@@ -452,6 +499,7 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
     const Fused2Switches f2sw = read_fused2_switches();
     const bool fused_ok = default_precision() == 0 && opt_int(OPT_FUSED_PAIR, 1) != 0;
     const bool convt_ok = opt_int(OPT_CONVT, 1) != 0;   // all-phases-per-wave transposed conv (convt_mfma.hip)
+    const unsigned rb2_mask = (unsigned)opt_int(OPT_RESBLOCK2_PAIR, kResblock2PairMask);
     bool in_section = false;   // inside a multi-stream fork..join section (profiling brackets the section)
     int pack_io = 0;   // bit 0: x is packed, bit 1: write y packed (set around the c1 / c2 launches below)
     auto conv = [&](const ConvW& cw, const float* x, hipStream_t st, float* y, const float* res, int L, int mul,
@@ -643,7 +691,41 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
             in_section = true;
             HG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
         }
-        for (int j = 0; j < cfg.n_kernels; ++j) {
+        for (int j = 0; h->rb2 && j < cfg.n_kernels; ++j) {
+            // ResBlock2 (models.py:62-83): both convs as one resblock2_pair launch where routed, else two resblock2_conv launches
+            // through Tb (x != y: halo reads).  The second writes the stage sum into `cur` (mode / div as for ResBlock1)
+            hipStream_t st = bs[j % 3];
+            float* Tb = Tbs[j % 3];
+            if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_fork, 0));
+            const int r = i * cfg.n_kernels + j;
+            const ConvW &w1 = h->c1[r], &w2 = h->c2[r];
+            const int d1 = cfg.resblock_dilations[j][0], d2 = cfg.resblock_dilations[j][1];
+            const int mode = cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2));
+            const float div = (float)cfg.n_kernels;
+            const double fl = 2.0 * w1.cout * w1.cin * w1.k * mul;      // per conv
+            if (resblock2_pair_choice(rb2_mask, w1.cin, w1.k, d1, d2, L, ups_out, cur)) {
+                if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
+                if (in_section) prof_add(2 * fl); else prof_begin(st, 2 * fl);
+                const int32_t rc2 = launch_resblock2_pair(w1.cin, ups_out, cur, h->dev + w1.w_off, h->dev + w1.b_off, h->dev + w2.w_off,
+                                                          h->dev + w2.b_off, w1.k, d1, d2, lens, mul, L, B, mode, div, 0.1f, st);
+                if (!in_section) prof_end(st);
+                HG_TRY(rc2);
+            } else {
+                if (in_section) prof_add(fl); else prof_begin(st, fl);
+                int32_t rc2 = launch_resblock2_conv(w1.cin, ups_out, Tb, h->dev + w1.w_off, h->dev + w1.b_off, w1.k, d1, lens, mul, L, B,
+                                                    0, 1.f, 0.1f, st);
+                if (!in_section) prof_end(st);
+                HG_TRY(rc2);
+                if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
+                if (in_section) prof_add(fl); else prof_begin(st, fl);
+                rc2 = launch_resblock2_conv(w2.cin, Tb, cur, h->dev + w2.w_off, h->dev + w2.b_off, w2.k, d2, lens, mul, L, B, mode, div,
+                                            0.1f, st);
+                if (!in_section) prof_end(st);
+                HG_TRY(rc2);
+            }
+            if (multi) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
+        }
+        for (int j = 0; !h->rb2 && j < cfg.n_kernels; ++j) {
             hipStream_t st = bs[j % 3];
             float *Tb = Tbs[j % 3], *R = Rs[j % 3];
             p.splitk_ws = splitks[j % 3];

@@ -38,6 +38,19 @@ HIFIGAN_CONFIG = {
     'sampling_rate': 22050,
 }
 
+# HiFi-GAN V3 (the published speed configuration: ResBlock2, three upsamplers): same 80 mels, 22.05 kHz, hop 8 * 8 * 4 = 256 and
+# n_fft 1024 as V1, so the mel front-end, the Denoiser and the acoustic models fit unchanged
+HIFIGAN_V3_CONFIG = {
+    'resblock': '2',
+    'upsample_rates': [8, 8, 4],
+    'upsample_kernel_sizes': [16, 16, 8],
+    'upsample_initial_channel': 256,
+    'resblock_kernel_sizes': [3, 5, 7],
+    'resblock_dilation_sizes': [[1, 2], [2, 6], [3, 12]],
+    'num_mels': 80, 'n_fft': 1024, 'hop_size': 256, 'win_size': 1024,
+    'sampling_rate': 22050,
+}
+
 # vocoder/vocos/__init__.py:35-67 (config_22k): backbone + ISTFT head of MelVocos('22k')
 VOCOS_22K_CONFIG = {
     'input_channels': 80, 'dim': 512, 'intermediate_dim': 1536, 'num_layers': 8,

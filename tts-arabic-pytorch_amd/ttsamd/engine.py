@@ -76,19 +76,23 @@ class HifiGanEngine:
         self.lib = _require_gpu()
         self.device = torch.device(device if device != 'cuda' else 'cuda:0')
         h = dict(HIFIGAN_CONFIG if config is None else config)
-        if str(h.get('resblock', '1')) != '1':
-            raise L.TtsAmdError('only ResBlock1 generators are built (config.json:2)')
+        rb = str(h.get('resblock', '1'))
+        if rb not in ('1', '2'):
+            raise L.TtsAmdError(f'resblock {h.get("resblock")!r}: only "1" (ResBlock1) and "2" (ResBlock2) generators exist')
         cfg = L.HifiGanCfg()
+        cfg.resblock = int(rb)
         cfg.num_mels = h.get('num_mels', 80)
         cfg.upsample_initial_channel = h['upsample_initial_channel']
         cfg.n_ups = len(h['upsample_rates'])
         for i, (u, k) in enumerate(zip(h['upsample_rates'], h['upsample_kernel_sizes'])):
             cfg.upsample_rates[i], cfg.upsample_kernel_sizes[i] = u, k
         cfg.n_kernels = len(h['resblock_kernel_sizes'])
-        cfg.n_dilations = len(h['resblock_dilation_sizes'][0])
+        # ResBlock1: every dilation of the list; ResBlock2: the first two (models.py:62-70; the library refuses fewer)
+        n_dil = min(len(ds) for ds in h['resblock_dilation_sizes'])
+        cfg.n_dilations = min(n_dil, 2) if rb == '2' else len(h['resblock_dilation_sizes'][0])
         for j, (k, ds) in enumerate(zip(h['resblock_kernel_sizes'], h['resblock_dilation_sizes'])):
             cfg.resblock_kernel_sizes[j] = k
-            for m, d in enumerate(ds):
+            for m, d in enumerate(ds[:cfg.n_dilations] if rb == '2' else ds):
                 cfg.resblock_dilations[j][m] = d
         self.hop = int(np.prod(h['upsample_rates']))
         self.num_mels = cfg.num_mels
@@ -476,6 +480,30 @@ def resblock_pair(x, w1, b1, w2, b2, dil, lens=None, len_mul=1, y=None, mode=0, 
         L.check(lib.ttsamd_resblock_pair(_ptr(x), _ptr(y), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), Cc, k, int(dil), _ptr(lens),
                                          int(len_mul), Lx, B, int(mode), float(div), float(slope), int(variant), _ptr(packed),
                                          n_packed, _stream()), 'resblock_pair')
+    return y
+
+
+def resblock2(x, w1, b1, w2, b2, dil1, dil2, lens=None, len_mul=1, y=None, mode=0, div=1.0, slope=0.1, variant=2):
+    """Kernel-level entry (parity tests / roofline bench): one ResBlock2 in exact fp32,
+    x1 = x + conv1d(lrelu(x), w1, dilation=dil1) + b1, v = x1 + conv1d(lrelu(x1), w2, dilation=dil2) + b2;
+    y = v | y + v | (y + v) / div (mode 0 | 1 | 2).  variant 1: two single-conv launches, 2: one fused launch."""
+    lib = _require_gpu()
+    x = x.contiguous().float()
+    w1, w2, b1, b2 = (t.contiguous().float() for t in (w1, w2, b1, b2))
+    B, Cc, Lx = x.shape
+    k = w1.shape[2]
+    assert tuple(w1.shape) == tuple(w2.shape) == (Cc, Cc, k)
+    if y is None:
+        assert mode == 0
+        y = torch.zeros_like(x)
+    if lens is not None:
+        lens = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    n_packed = int(lib.ttsamd_resblock2_packed_floats(Cc, k, int(variant)))
+    packed = torch.empty(max(n_packed, 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(lib.ttsamd_resblock2(_ptr(x), _ptr(y), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), Cc, k, int(dil1), int(dil2), _ptr(lens),
+                                     int(len_mul), Lx, B, int(mode), float(div), float(slope), int(variant), _ptr(packed), n_packed,
+                                     _stream()), 'resblock2')
     return y
 
 

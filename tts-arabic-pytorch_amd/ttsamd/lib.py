@@ -20,7 +20,7 @@ class HifiGanCfg(C.Structure):
     _fields_ = [('num_mels', C.c_int32), ('upsample_initial_channel', C.c_int32), ('n_ups', C.c_int32),
                 ('upsample_rates', C.c_int32 * 8), ('upsample_kernel_sizes', C.c_int32 * 8),
                 ('n_kernels', C.c_int32), ('resblock_kernel_sizes', C.c_int32 * 8),
-                ('n_dilations', C.c_int32), ('resblock_dilations', (C.c_int32 * 8) * 8)]
+                ('n_dilations', C.c_int32), ('resblock_dilations', (C.c_int32 * 8) * 8), ('resblock', C.c_int32)]
 
 
 class FastPitchCfg(C.Structure):
@@ -96,6 +96,8 @@ SYMBOLS = {
     'ttsamd_conv1d_ex': (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _I32, _F, _P, _P, _P]),
     'ttsamd_resblock_pair_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
+    'ttsamd_resblock2_packed_floats': (_I64, [_I32, _I32, _I32]),
+    'ttsamd_resblock2': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
     'ttsamd_bfo_pack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
     'ttsamd_bfo_unpack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
     'ttsamd_bfo_weight_elems': (_I64, [_I32, _I32, _I32, _I32]),
@@ -129,7 +131,7 @@ SYMBOLS = {
 }
 
 _lib = None
-ABI_VERSION = 7            # == TTSAMD_ABI_VERSION of include/ttsamd.h (struct layouts and argument meanings of this binding)
+ABI_VERSION = 8            # == TTSAMD_ABI_VERSION of include/ttsamd.h (struct layouts and argument meanings of this binding)
 
 
 def load():

@@ -128,6 +128,12 @@ def hifigan_state_dict(config=None, seed=0, weight_norm=True):
         sd[f'ups.{i}.bias'] = _normal(seed, f'ups.{i}.b', (ch,), 0.1)
         for j, kk in enumerate(h['resblock_kernel_sizes']):
             r = i * len(h['resblock_kernel_sizes']) + j
+            if str(h.get('resblock', '1')) == '2':
+                # ResBlock2: two convs, `resblocks.r.convs.{0,1}` (models.py:62-70)
+                for m in range(2):
+                    put(f'resblocks.{r}.convs.{m}', (ch, ch, kk), ch * kk, 0.9)
+                    sd[f'resblocks.{r}.convs.{m}.bias'] = _normal(seed, f'rb{r}.c.{m}.b', (ch,), 0.05)
+                continue
             for m in range(len(h['resblock_dilation_sizes'][j])):
                 put(f'resblocks.{r}.convs1.{m}', (ch, ch, kk), ch * kk, 1.2)
                 sd[f'resblocks.{r}.convs1.{m}.bias'] = _normal(seed, f'rb{r}.c1.{m}.b', (ch,), 0.05)
