@@ -218,7 +218,7 @@ int32_t ttsamd_denoise(void* handle, float* wave, int64_t wave_stride, const int
                        int32_t batch, int32_t n_max, const float* bias_spec, float strength,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
-/* ---- MelVocos('22k') vocoder: replaces vocoder.vocos.pretrained.MelVocos
+/* ---- MelVocos('22k' / '24k') vocoder: replaces vocoder.vocos.pretrained.MelVocos
  *      (vocoder/vocos/pretrained.py:34-93; backbone models.py:26-89, ConvNeXtBlock modules.py:8-60,
  *      ISTFTHead heads.py:26-41, ISTFT "same" spectral_ops.py:33-75).  Weight names are the keys of
  *      MelVocos.state_dict() (backbone.*, head.out.*). ------------------------------------------- */
@@ -230,11 +230,38 @@ int64_t ttsamd_vocos_workspace_bytes(void* handle, int32_t batch, int32_t t_max)
  * (make_denoising_vector, pretrained.py:59-71). */
 int32_t ttsamd_vocos_bias_vec(void* handle, float* bias_vec, void* workspace, int64_t workspace_bytes,
                               void* stream);
-/* mel [B][80][t_max], lens int64 [B] (device) -> wave [B][256*t_max]; samples >= 256*lens[b] untouched.
+/* mel [B][input_channels][t_max], lens int64 [B] (device) -> wave [B][256*t_max]; samples >= 256*lens[b] untouched.
  * mag = clamp(exp(.) - denoise*bias_vec, 0, 100) (pretrained.py:79-88). */
 int32_t ttsamd_vocos_forward(void* handle, const float* mel, const int64_t* lens, int32_t batch,
                              int32_t t_max, float denoise, const float* bias_vec, float* wave,
                              void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- Added after ABI revision 8 WITHOUT a bump: ttsamd_vocos_set_padding and the ttsamd_melspec_* entries below are new symbols only;
+ *      no existing signature, struct or argument meaning changed, so TTSAMD_ABI_VERSION stays 8.  A library built before them lacks the
+ *      symbols, which a binding that lists them finds at load (ttsamd/lib.py resolves every name of its table; dlsym fails loudly). ----
+ * ISTFT trimming of the Vocos head: 0 = "same" (the default; spectral_ops.py:47-75: 256 * lens[b] samples per utterance), 1 = "center"
+ * (MelVocos('24k'); spectral_ops.py:44-46 = torch.istft(center=True): 256 * (lens[b] - 1) samples, none for one frame).  The wave rows keep
+ * the stride 256 * t_max in both modes.  input_channels of ttsamd_vocos_create may be any positive count (100 for '24k'): the embed
+ * conv's input channels are zero-padded to the engine's 8-channel chunks inside the library. */
+int32_t ttsamd_vocos_set_padding(void* handle, int32_t mode);
+
+/* ---- Mel analysis, wave -> (log-)mel, one launch: replaces utils.audio.MelSpectrogram.forward (utils/audio.py:35-46) and
+ *      MelSpectrogramFeatures.forward (vocoder/vocos/feature_extractors.py:58-64).  n_fft = win = 1024 and hop_length = 256 only (anything
+ *      else: TTSAMD_EINVAL), periodic hann, reflect padding at each utterance's own ends.
+ *      fbank [n_mels][513] fp32 on the HOST, dense, copied at create (1 <= n_mels <= 128);
+ *      framing 0 "same":   pad 384 per side, frames = n / 256      (needs n >= 385; utils.audio.MelSpectrogram, padding="same")
+ *              1 "center": pad 512 per side, frames = n / 256 + 1  (needs n >= 513; torch.stft(center=True), padding="center");
+ *      mag_mode 0: |X| (torchaudio power = 1), 1: sqrt(|X|^2 + 1e-9) (utils/audio.py:44);
+ *      log_clip > 0: log(max(mel, log_clip)) (modules.py safe_log, 1e-5), <= 0: linear mel. ------------------------------------------- */
+int32_t ttsamd_melspec_create(const float* fbank, int32_t n_mels, int32_t n_fft, int32_t hop_length, int32_t framing,
+                              int32_t mag_mode, float log_clip, void** handle);
+int32_t ttsamd_melspec_destroy(void* handle);
+/* wave [B][wave_stride], nsamples int64 [B] (device) -> mel [B][n_mels][t_max] (device), row b = the call on wave[b][0 : nsamples[b]]
+ * alone, bit for bit; frames at or past the row's own count are written as zero.  frames_out int64 [B] (device, may be NULL) receives
+ * min(frame count of the table above, t_max): the `lens` of the vocoder call that follows, no host synchronisation in between.
+ * A row shorter than the framing needs gives values but no meaning (indices are kept inside the row; the Python wrappers raise). */
+int32_t ttsamd_melspec_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
+                               int32_t t_max, float* mel, int64_t* frames_out, void* stream);
 
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of

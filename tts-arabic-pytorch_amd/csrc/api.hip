@@ -86,6 +86,11 @@ int64_t vocos_bias_workspace_bytes(const Vocos*);
 int32_t vocos_bias_vec(const Vocos*, float*, void*, int64_t, hipStream_t);
 int32_t vocos_forward(const Vocos*, const float*, const int64_t*, int32_t, int32_t, float, const float*, float*, void*,
                       int64_t, hipStream_t);
+int32_t vocos_set_padding(Vocos*, int32_t);
+struct MelSpec;
+int32_t melspec_create(const float*, int32_t, int32_t, int32_t, int32_t, int32_t, float, MelSpec**);
+void melspec_destroy(MelSpec*);
+int32_t melspec_forward(const MelSpec*, const float*, int64_t, const int64_t*, int32_t, int32_t, float*, int64_t*, hipStream_t);
 struct Taco2;
 int32_t tacotron2_create(const ttsamd_tensor*, int32_t, const ttsamd_tacotron2_cfg*, Taco2**);
 void tacotron2_destroy(Taco2*);
@@ -360,6 +365,25 @@ int32_t ttsamd_vocos_forward(void* handle, const float* mel, const int64_t* lens
                              int64_t workspace_bytes, void* stream) {
     return vocos_forward((Vocos*)handle, mel, lens, batch, t_max, denoise, bias_vec, wave, workspace, workspace_bytes,
                          (hipStream_t)stream);
+}
+
+int32_t ttsamd_vocos_set_padding(void* handle, int32_t mode) { return vocos_set_padding((Vocos*)handle, mode); }
+
+int32_t ttsamd_melspec_create(const float* fbank, int32_t n_mels, int32_t n_fft, int32_t hop_length, int32_t framing,
+                              int32_t mag_mode, float log_clip, void** handle) {
+    TTS_REQUIRE(handle, "melspec_create: null handle");
+    MelSpec* h = nullptr;
+    const int32_t rc = melspec_create(fbank, n_mels, n_fft, hop_length, framing, mag_mode, log_clip, &h);
+    if (rc == 0) *handle = h;
+    return rc;
+}
+int32_t ttsamd_melspec_destroy(void* handle) {
+    melspec_destroy((MelSpec*)handle);
+    return 0;
+}
+int32_t ttsamd_melspec_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
+                               int32_t t_max, float* mel, int64_t* frames_out, void* stream) {
+    return melspec_forward((const MelSpec*)handle, wave, wave_stride, nsamples, batch, t_max, mel, frames_out, (hipStream_t)stream);
 }
 
 int32_t ttsamd_tacotron2_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_tacotron2_cfg* cfg, void** handle) {

@@ -1,4 +1,4 @@
-// MelVocos('22k') on the MI355X: ConvNeXt backbone + ISTFT head with "same" padding.
+// MelVocos('22k' / '24k') on the MI355X: ConvNeXt backbone + ISTFT head with "same" (22k) or "center" (24k) padding.
 // Replaces vocoder/vocos/pretrained.py:34-93 (MelVocos.__init__/make_denoising_vector/forward),
 // models.py:77-89 (VocosBackbone.forward), modules.py:43-60 (ConvNeXtBlock.forward),
 // heads.py:41 (ISTFTHead.out) and spectral_ops.py:33-75 (ISTFT.forward, padding="same").
@@ -6,6 +6,7 @@
 // ISTFT is one 1024-point FFT per frame in LDS (vocos_istft_kernel, fft1024.hpp); depthwise conv,
 // LayerNorm (eps 1e-6), exp/cos/sin (+ the transposition to frame-major) and the overlap-add are HBM-bound kernels.  Ragged batches: every layer reads positions >= lens[b]
 // as zero, i.e. utterance b equals MelVocos.forward(mel[b:b+1, :, :lens[b]]).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -30,7 +31,8 @@ struct VBlock {
 struct Vocos {
     float* dev = nullptr;
     uint16_t* dev16 = nullptr;
-    int in_ch = 80, dim = 512, inter = 1536;
+    int in_ch = 80, in_chp = 80, dim = 512, inter = 1536;     // in_chp: in_ch rounded up to the conv engine's 8-channel chunks (100 -> 104)
+    int center = 0;                                           // ISTFT trimming: 0 "same" (pad 384, 256 T samples), 1 "center" (pad 512, 256 (T - 1))
     VConv embed, head;
     int64_t n0_g, n0_b, fl_g, fl_b, window, twiddle;
     std::vector<VBlock> blocks;
@@ -69,14 +71,21 @@ struct VBuilder {
         blob.resize(align_up((int64_t)blob.size(), 64));
         return off;
     }
-    VConv conv(const std::string& base, int cin, int cout, int k, int coutp) {
+    // cin_w: input channels of the stored weight; the cin - cin_w channels the engine's chunking adds carry zero weights
+    VConv conv(const std::string& base, int cin, int cout, int k, int coutp, int cin_w = 0) {
         VConv c;
+        if (cin_w == 0) cin_w = cin;
         c.cin = cin; c.cout = cout; c.k = k; c.coutp = coutp;
-        const ttsamd_tensor* w = get(base + ".weight", (int64_t)cin * cout * k);
+        const ttsamd_tensor* w = get(base + ".weight", (int64_t)cin_w * cout * k);
         if (!w) return c;
-        // pack with the padded channel count: rows >= cout are zero weights
+        // pack with the padded channel counts: rows >= cout (and input channels >= cin_w) are zero weights
         std::vector<float> wp((size_t)coutp * cin * k, 0.f);
-        std::memcpy(wp.data(), w->data, (size_t)cout * cin * k * sizeof(float));
+        if (cin_w == cin) {
+            std::memcpy(wp.data(), w->data, (size_t)cout * cin * k * sizeof(float));
+        } else {
+            for (int co = 0; co < cout; ++co)
+                std::memcpy(wp.data() + (size_t)co * cin * k, w->data + (size_t)co * cin_w * k, (size_t)cin_w * k * sizeof(float));
+        }
         c.w_off = (int64_t)blob.size();
         blob.resize(blob.size() + (size_t)cin * k * coutp);
         pack_conv_weight(wp.data(), coutp, cin, k, blob.data() + c.w_off);
@@ -95,13 +104,13 @@ struct VBuilder {
 int32_t vocos_create(const ttsamd_tensor* weights, int32_t n, int32_t in_ch, int32_t dim, int32_t inter,
                      int32_t n_layers, Vocos** out) {
     TTS_REQUIRE(weights && out, "vocos_create: null argument");
-    TTS_REQUIRE(dim % 128 == 0 && inter % 128 == 0 && in_ch % 8 == 0 && n_layers >= 1, "vocos_create: bad dims");
+    TTS_REQUIRE(dim % 128 == 0 && inter % 128 == 0 && in_ch >= 1 && n_layers >= 1, "vocos_create: bad dims");
     TensorMap tm;
     for (int i = 0; i < n; ++i) tm[weights[i].name] = &weights[i];
     VBuilder b(tm);
     auto* h = new Vocos();
-    h->in_ch = in_ch; h->dim = dim; h->inter = inter;
-    h->embed = b.conv("backbone.embed", in_ch, dim, 7, dim);
+    h->in_ch = in_ch; h->in_chp = (int)align_up(in_ch, 8); h->dim = dim; h->inter = inter;
+    h->embed = b.conv("backbone.embed", h->in_chp, dim, 7, dim, in_ch);
     h->n0_g = b.raw("backbone.norm.weight", dim);
     h->n0_b = b.raw("backbone.norm.bias", dim);
     for (int i = 0; i < n_layers && b.rc == 0; ++i) {
@@ -142,6 +151,12 @@ int32_t vocos_create(const ttsamd_tensor* weights, int32_t n, int32_t in_ch, int
         return rc;
     }
     *out = h;
+    return 0;
+}
+
+int32_t vocos_set_padding(Vocos* h, int32_t mode) {
+    TTS_REQUIRE(h && (mode == 0 || mode == 1), "vocos_set_padding: mode must be 0 (same) or 1 (center)");
+    h->center = mode;
     return 0;
 }
 
@@ -220,10 +235,20 @@ __global__ void vocos_bias_kernel(const float* __restrict__ O, int T, float* __r
     if (f < V_NBIN) out[f] = fminf(expf(O[(int64_t)f * T]), 100.f);
 }
 
+// mel [B][in_ch][T] -> [B][in_chp][T], the added channel rows zero (in_ch = 100: the embed conv reads 8-channel chunks)
+__global__ __launch_bounds__(256) void vocos_pad_channels_kernel(const float* __restrict__ mel, int in_ch, int in_chp, int T,
+                                                                 float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int64_t n = (int64_t)in_chp * T, n_in = (int64_t)in_ch * T;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
+        out[b * n + e] = e < n_in ? mel[b * n_in + e] : 0.f;
+}
+
 struct VWs {
-    float *x, *d, *h, *o, *y;
+    float *x, *d, *h, *o, *y, *m;
 };
 static void vcarve(const Vocos* h, Arena& a, int B, int T, VWs& w) {
+    w.m = h->in_chp != h->in_ch ? a.take<float>((int64_t)B * h->in_chp * T) : nullptr;      // staged mel (24k only)
     w.x = a.take<float>((int64_t)B * h->dim * T);
     w.d = a.take<float>((int64_t)B * h->dim * T);
     w.h = a.take<float>((int64_t)B * h->inter * T);
@@ -256,7 +281,7 @@ static int32_t vconv(const Vocos* h, const VConv& c, const float* x, float* y, c
     return rc;
 }
 
-// backbone + head.out -> w.o [B][V_SPEC_CP][T] holding (log-magnitude | phase | 0)
+// backbone + head.out -> w.o [B][V_SPEC_CP][T] holding (log-magnitude | phase | 0); mel [B][in_chp][T]
 static int32_t vocos_features(const Vocos* h, const float* mel, const int64_t* lens, int B, int T, const VWs& w,
                               hipStream_t s) {
     const int d = h->dim;
@@ -278,12 +303,12 @@ int32_t vocos_bias_vec(const Vocos* h, float* out513, void* ws, int64_t ws_bytes
     Arena a(ws, ws_bytes);
     VWs w;
     vcarve(h, a, 1, T, w);
-    float* zero_mel = a.take<float>((int64_t)h->in_ch * T);
+    float* zero_mel = a.take<float>((int64_t)h->in_chp * T);
     if (!ws || !a.ok) {
         set_error("vocos_bias_vec: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
         return TTSAMD_ENOMEM;
     }
-    TTS_CHECK_HIP(hipMemsetAsync(zero_mel, 0, (size_t)h->in_ch * T * sizeof(float), s));
+    TTS_CHECK_HIP(hipMemsetAsync(zero_mel, 0, (size_t)h->in_chp * T * sizeof(float), s));
     TTS_TRY(vocos_features(h, zero_mel, nullptr, 1, T, w, s));
     hipLaunchKernelGGL(vocos_bias_kernel, dim3((V_NBIN + 63) / 64), dim3(64), 0, s, w.o, T, out513);
     TTS_CHECK_HIP(hipGetLastError());
@@ -294,7 +319,7 @@ int64_t vocos_bias_workspace_bytes(const Vocos* h) {
     Arena a(nullptr, 0);
     VWs w;
     vcarve(h, a, 1, 88, w);
-    a.take<float>((int64_t)h->in_ch * 88);
+    a.take<float>((int64_t)h->in_chp * 88);
     return a.off;
 }
 
@@ -302,12 +327,19 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
                       const float* bias_vec, float* wave, void* ws, int64_t ws_bytes, hipStream_t s) {
     TTS_REQUIRE(h && mel && wave && lens && B >= 1 && T >= 1, "vocos_forward: bad argument");
     TTS_REQUIRE(denoise == 0.f || bias_vec, "vocos_forward: denoise > 0 needs bias_vec");
+    if (h->center && T == 1) return 0;       // the centred ISTFT of one frame has no sample left after trimming n_fft / 2 per side
     Arena a(ws, ws_bytes);
     VWs w;
     vcarve(h, a, B, T, w);
     if (!ws || !a.ok) {
         set_error("vocos_forward: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
         return TTSAMD_ENOMEM;
+    }
+    if (w.m) {
+        hipLaunchKernelGGL(vocos_pad_channels_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)h->in_chp * T + 255) / 256, 1024), B),
+                           dim3(256), 0, s, mel, h->in_ch, h->in_chp, T, w.m);
+        TTS_CHECK_HIP(hipGetLastError());
+        mel = w.m;
     }
     TTS_TRY(vocos_features(h, mel, lens, B, T, w, s));
     // complex spectrum frame-major into the (dead) hidden buffer of the backbone: 513 float2 per frame <= inter floats
@@ -318,6 +350,10 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
     hipLaunchKernelGGL(vocos_istft_kernel, dim3(T, B), dim3(256), 0, s, S, lens, h->dev + h->window,
                        reinterpret_cast<const float2*>(h->dev + h->twiddle), T, w.y);
     TTS_CHECK_HIP(hipGetLastError());
+    // "center" (24k): torch.istft(center=True) trimming, pad = n_fft / 2, n_out = hop * (frames - 1) per utterance; rows keep the stride hop * T
+    if (h->center)
+        return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, V_NFFT / 2, B, T, V_HOP * (T - 1), wave, (int64_t)V_HOP * T, s,
+                                  /*frame_major=*/1);
     // overlap-add with "same" trimming (pad = (n_fft - hop) / 2, n_out = hop * frames) over the frame-major time-domain frames
     return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, (V_NFFT - V_HOP) / 2, B, T, V_HOP * T, wave,
                               (int64_t)V_HOP * T, s, /*frame_major=*/1);

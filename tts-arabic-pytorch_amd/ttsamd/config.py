@@ -51,10 +51,24 @@ HIFIGAN_V3_CONFIG = {
     'sampling_rate': 22050,
 }
 
-# vocoder/vocos/__init__.py:35-67 (config_22k): backbone + ISTFT head of MelVocos('22k')
+# vocoder/vocos/__init__.py:35-67 (config_22k): backbone + ISTFT head of MelVocos('22k'), and its feature extractor's arguments.  The
+# reference's quirk is kept as data: config_22k builds its filterbank with sample_rate = 24000 (:46), f_max = 8000, slaney / slaney,
+# although the model runs at 22.05 kHz -- the band edges are those of a 24 kHz bin grid.
 VOCOS_22K_CONFIG = {
     'input_channels': 80, 'dim': 512, 'intermediate_dim': 1536, 'num_layers': 8,
     'n_fft': 1024, 'hop_length': 256, 'padding': 'same',
+    'sample_rate': 22050,
+    'feature_extractor': {'sample_rate': 24000, 'n_fft': 1024, 'hop_length': 256, 'n_mels': 80, 'padding': 'same',
+                          'f_min': 0, 'f_max': 8000, 'norm': 'slaney', 'mel_scale': 'slaney'},
+}
+
+# vocoder/vocos/__init__.py:8-32 (config_24k, the reference constructor's default and the published Vocos mel checkpoint's geometry):
+# 100 HTK bands without area norm, f_max = sr / 2, "center" framing on both sides (torch.stft / torch.istft with center=True)
+VOCOS_24K_CONFIG = {
+    'input_channels': 100, 'dim': 512, 'intermediate_dim': 1536, 'num_layers': 8,
+    'n_fft': 1024, 'hop_length': 256, 'padding': 'center',
+    'sample_rate': 24000,
+    'feature_extractor': {'sample_rate': 24000, 'n_fft': 1024, 'hop_length': 256, 'n_mels': 100, 'padding': 'center'},
 }
 
 # models/tacotron2/tacotron2_ms.py:152-205 constructor defaults as instantiated by

@@ -275,20 +275,73 @@ class DenoiserEngine:
         return wave
 
 
+class MelSpecEngine:
+    """Handle over ttsamd_melspec_* (csrc/melspec.hip): wave -> (log-)mel in one launch.  `fbank` [n_mels, 513] (numpy / tensor, copied);
+    framing 'same' (reflect pad 384, n // 256 frames) or 'center' (reflect pad 512, n // 256 + 1); mag 'abs' = |X| or 'eps' = sqrt(|X|^2 + 1e-9);
+    log_clip > 0: log(max(mel, log_clip)), None / 0: linear."""
+
+    MIN_SAMPLES = {'same': 385, 'center': 513}                 # reflect padding needs more samples than it adds per side
+
+    def __init__(self, fbank, framing='same', mag='abs', log_clip=None, n_fft=1024, hop_length=256, device='cuda'):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        if framing not in ('same', 'center') or mag not in ('abs', 'eps'):
+            raise L.TtsAmdError(f'MelSpecEngine: framing {framing!r} / mag {mag!r} (same | center, abs | eps)')
+        fb = fbank.detach().cpu().numpy() if hasattr(fbank, 'detach') else np.asarray(fbank)
+        fb = np.ascontiguousarray(fb, dtype=np.float32)
+        if fb.ndim != 2 or fb.shape[1] != n_fft // 2 + 1:
+            raise L.TtsAmdError(f'MelSpecEngine: filterbank of shape {fb.shape}, expected [n_mels, {n_fft // 2 + 1}]')
+        self.n_mels, self.framing, self.hop = fb.shape[0], framing, int(hop_length)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ttsamd_melspec_create(fb.ctypes.data_as(C.c_void_p), fb.shape[0], int(n_fft), int(hop_length),
+                                                   int(framing == 'center'), int(mag == 'eps'), float(log_clip or 0.0),
+                                                   C.byref(handle)), 'melspec_create')
+        self.handle = handle
+
+    def __del__(self):
+        if getattr(self, 'handle', None):
+            self.lib.ttsamd_melspec_destroy(self.handle)
+            self.handle = None
+
+    def frames(self, n):
+        return n // self.hop + (self.framing == 'center')
+
+    def forward(self, wave, nsamples=None):
+        """wave [B, n_max] float32, nsamples int64 [B] on the device or None (every row n_max long) ->
+        (mel [B, n_mels, frames(n_max)], frames int64 [B] on the device).  Row b is the call on wave[b, :nsamples[b]] alone; frames at
+        or past a row's own count are zero.  Nothing is read back to the host."""
+        wave = _f32(wave, self.device)
+        B, n_max = wave.shape
+        if nsamples is None:
+            nsamples = torch.full((B,), n_max, dtype=torch.int64, device=self.device)
+        nsamples = nsamples.to(device=self.device, dtype=torch.int64).contiguous()
+        T = self.frames(n_max)
+        mel = torch.empty(B, self.n_mels, T, dtype=torch.float32, device=self.device)
+        frames = torch.empty(B, dtype=torch.int64, device=self.device)
+        if B:
+            with torch.cuda.device(self.device):
+                L.check(self.lib.ttsamd_melspec_forward(self.handle, _ptr(wave), n_max, _ptr(nsamples), B, T, _ptr(mel), _ptr(frames),
+                                                        _stream()), 'melspec_forward')
+        return mel, frames
+
+
 class VocosEngine:
-    """Handle over ttsamd_vocos_* (replaces vocoder.vocos.pretrained.MelVocos('22k'))."""
+    """Handle over ttsamd_vocos_* (replaces vocoder.vocos.pretrained.MelVocos: '22k' = "same" head, 80 bands; '24k' = "center" head, 100)."""
 
     def __init__(self, state_dict, config=None, device='cuda'):
         self.lib = _require_gpu()
         self.device = torch.device(device if device != 'cuda' else 'cuda:0')
         c = dict(VOCOS_22K_CONFIG if config is None else config)
-        assert c['n_fft'] == 1024 and c['hop_length'] == 256 and c['padding'] == 'same'
-        self.hop, self.n_mels = c['hop_length'], c['input_channels']
+        assert c['n_fft'] == 1024 and c['hop_length'] == 256 and c['padding'] in ('same', 'center')
+        self.hop, self.n_mels, self.center = c['hop_length'], c['input_channels'], c['padding'] == 'center'
         arr, keep = L.make_tensors(state_dict)
         handle = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(self.lib.ttsamd_vocos_create(arr, len(arr), c['input_channels'], c['dim'], c['intermediate_dim'],
                                                  c['num_layers'], C.byref(handle)), 'vocos_create')
+            if self.center:
+                L.check(self.lib.ttsamd_vocos_set_padding(handle, 1), 'vocos_set_padding')
         self.handle = handle
         self.ws = _Workspace()
         self._bias = None
@@ -309,14 +362,16 @@ class VocosEngine:
         return self._bias
 
     def forward(self, mel, lens=None, denoise=0.0):
-        """mel [B,80,T] on the GPU, lens int64 [B] or None -> wave [B, 256*T] (zeros past 256*lens[b])."""
+        """mel [B,n_mels,T] on the GPU, lens int64 [B] or None -> wave [B, 256*T] (zeros past 256*lens[b]); with the "center" head ('24k':
+        torch.istft(center=True)) [B, 256*(T-1)], zeros past 256*(lens[b]-1)."""
         mel = _f32(mel, self.device)
         B, M, T0 = mel.shape
         assert M == self.n_mels
         if lens is None:
             lens = torch.full((B,), T0, dtype=torch.int64, device=self.device)
         lens = lens.to(device=self.device, dtype=torch.int64).contiguous()
-        if T0 == 0:
+        n0 = self.hop * (T0 - 1) if self.center else self.hop * T0
+        if T0 == 0 or n0 == 0:
             return torch.zeros(B, 0, dtype=torch.float32, device=self.device)
         # frame rows padded to a multiple of 4 (16 bytes): the conv engine's fast paths (the k = 1 GEMM route, float4 row epilogues) need aligned
         # rows and a real T is a multiple of 4 one time in four; every layer reads frames >= lens[b] as zero, so the extra columns change nothing
@@ -330,7 +385,7 @@ class VocosEngine:
             ws = self.ws.get(nb, self.device)
             L.check(self.lib.ttsamd_vocos_forward(self.handle, _ptr(mel), _ptr(lens), B, T, float(denoise), _ptr(bias),
                                                   _ptr(wave), _ptr(ws), nb, _stream()), 'vocos_forward')
-        return wave if T == T0 else wave[:, :self.hop * T0]
+        return wave if wave.shape[1] == n0 else wave[:, :n0]
 
 
 class Tacotron2Engine:

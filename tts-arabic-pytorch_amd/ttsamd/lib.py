@@ -82,6 +82,10 @@ SYMBOLS = {
     'ttsamd_vocos_workspace_bytes': (_I64, [_P, _I32, _I32]),
     'ttsamd_vocos_bias_vec': (_I32, [_P, _P, _P, _I64, _P]),
     'ttsamd_vocos_forward': (_I32, [_P, _P, _P, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
+    'ttsamd_vocos_set_padding': (_I32, [_P, _I32]),
+    'ttsamd_melspec_create': (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _F, C.POINTER(_P)]),
+    'ttsamd_melspec_destroy': (_I32, [_P]),
+    'ttsamd_melspec_forward': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

@@ -1,24 +1,30 @@
 """Drop-in for the inference part of the reference's vendored Vocos
-(vocoder/vocos/pretrained.py:34-97 `MelVocos`, config '22k' of vocoder/vocos/__init__.py:35-67):
-80-band mel -> waveform through the HIP ConvNeXt backbone + ISTFT head.  The reference never
-wires it to FastPitch; `FastPitch2Wave`-style use is: `wave = vocos(mel_batch, denoise=0.)`."""
+(vocoder/vocos/pretrained.py:34-97 `MelVocos`, configs '22k' and '24k' of vocoder/vocos/__init__.py:8-67):
+mel -> waveform through the HIP ConvNeXt backbone + ISTFT head, and waveform -> log-mel through the HIP analysis kernel
+(`feature_extractor`, `reconstruct`).  '22k': 80 slaney bands, "same" framing; '24k' (the published Vocos mel checkpoint's geometry):
+100 HTK bands, "center" framing.  The reference never wires it to FastPitch; `FastPitch2Wave`-style use is:
+`wave = vocos(mel_batch, denoise=0.)`.  The constructor default is '22k' here ('24k' in the reference): INTEGRATION.md."""
 import numpy as np
 import torch
 
-from ttsamd.config import VOCOS_22K_CONFIG
+from ttsamd.config import VOCOS_22K_CONFIG, VOCOS_24K_CONFIG
 from ttsamd.engine import VocosEngine
 from ttsamd.lib import TtsAmdError
 from vocoder.hifigan.models import _HipModule
+from vocoder.vocos.feature_extractors import MelSpectrogramFeatures
 
 config_22k = dict(VOCOS_22K_CONFIG)
+config_24k = dict(VOCOS_24K_CONFIG)
 
 
 class MelVocos(_HipModule):
     def __init__(self, config_name='22k'):
         super().__init__()
-        if config_name != '22k':
-            raise TtsAmdError("only MelVocos('22k') (80 mel bands, 22.05 kHz) is built")
-        self.n_mels = config_22k['input_channels']
+        if config_name not in ('22k', '24k'):
+            raise TtsAmdError(f"MelVocos({config_name!r}): only '22k' (80 mel bands, 22.05 kHz) and '24k' (100 bands, 24 kHz) are built")
+        self.config = {'22k': config_22k, '24k': config_24k}[config_name]
+        self.feature_extractor = MelSpectrogramFeatures(**self.config['feature_extractor'])
+        self.n_mels = self.config['input_channels']
         self._sd = None
 
     def load_state_dict(self, state_dict, strict=True):
@@ -32,7 +38,7 @@ class MelVocos(_HipModule):
     def engine(self):
         if self._sd is None:
             raise TtsAmdError('MelVocos has no weights: call load_state_dict first')
-        return self._engine(lambda dev: VocosEngine(self._sd, config_22k, device=dev))
+        return self._engine(lambda dev: VocosEngine(self._sd, self.config, device=dev))
 
     @property
     def bias_vec(self):
@@ -40,5 +46,17 @@ class MelVocos(_HipModule):
 
     @torch.inference_mode()
     def forward(self, mel_spec, denoise=0., lens=None):
-        """mel_spec [B, 80, frames] -> wave [B, 256*frames]  (pretrained.py:73-93)."""
-        return self.engine().forward(mel_spec, lens, denoise)
+        """mel_spec [B, n_mels, frames] -> wave [B, 256*frames] ('22k'; pretrained.py:73-93) or [B, 256*(frames-1)] ('24k')."""
+        eng = self.engine()
+        if self.config['padding'] == 'center' and mel_spec.shape[-1] < 2:
+            # torch.istft(center=True) of a single frame has no sample left after trimming n_fft / 2 per side and raises
+            raise ValueError("MelVocos('24k'): the centred ISTFT needs at least 2 frames (got %d)" % mel_spec.shape[-1])
+        return eng.forward(mel_spec, lens, denoise)
+
+    @torch.inference_mode()
+    def reconstruct(self, wave, denoise=0., lens=None):
+        """wave [B, n] -> forward(feature_extractor(wave), denoise) (pretrained.py:95-97).  `lens` int64 [B] (extension): samples per
+        row of a ragged batch; the frame counts go from the analysis kernel to the vocoder on the device, no host read in between."""
+        self.engine()                                   # (a module left on the CPU raises before any work)
+        mel, frames = self.feature_extractor.extract(wave, lens)
+        return self.forward(mel, denoise, frames)
