@@ -263,6 +263,53 @@ int32_t ttsamd_melspec_destroy(void* handle);
 int32_t ttsamd_melspec_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
                                int32_t t_max, float* mel, int64_t* frames_out, void* stream);
 
+/* ---- Oversmoothing analysis (utils/oversmoothing.py, utils/metrics.py of the reference; csrc/oversmooth.hip).  Like the ttsamd_melspec_*
+ *      entries these are new symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.  Every pointer is device memory, lengths are
+ *      int64 [batch]; a length is clamped to [0, t_max].  No call reads anything back to the host.
+ *      The longest series ttsamd_series_summary sorts and the longest side ttsamd_dtw aligns: */
+#define TTSAMD_OVERSMOOTH_MAX_FRAMES 4096
+/* mel [B][n_mels][t_max] -> series [B][4][t_max] fp32: per frame, from the power of an rFFT across the bands (Q = n_mels / 2 + 1 bins):
+ *   0 HQER      hqer_scale * sum P[q_c .. Q-1] / (sum P[1 .. Q-1] + 1e-12)   (q_c = -1: clamp(floor(0.25 Q), 1, Q - 1); the drop-in scales by 100)
+ *   1 CSlope    least-squares slope of 10 log10(P + 1e-8) over q = 1 .. Q-1 (NaN for fewer than two points)
+ *   2 CCentroid sum q P / (sum P + 1e-12) over q >= 1
+ *   3 CRoll95   first q whose cumulative power from q = 1 reaches 0.95 (total + 1e-12), 1 if none does
+ * center != 0 subtracts the frame's mean over the bands, hann != 0 applies np.hanning(n_mels) (symmetric, rounded once to fp32).
+ * 1 <= n_mels <= 128.  Intermediate arithmetic is float64.  Frames at or past lens[b] are written as zero; row b equals the call on
+ * row b alone, bit for bit.  `power` (may be NULL) receives P itself, [B][Q][t_max] fp32 (framewise_rfft_power). */
+int32_t ttsamd_cepstral_series(const float* mel, const int64_t* lens, int32_t batch, int32_t n_mels, int32_t t_max, int32_t center,
+                               int32_t hann, int32_t q_c, float hqer_scale, float* power, float* series, void* stream);
+/* The same four series from a power [B][n_q][t_max] the caller holds (hqer_from_power, slope_from_power, ... of the reference), with
+ * their parameters: the slope over q1 .. q2 (0 <= q1, q2 <= n_q - 1; NaN for fewer than two points) of 10 log10(P + eps), the roll-off
+ * at the fraction roll_p.  1 <= n_q <= 65. */
+int32_t ttsamd_cepstral_series_from_power(const float* power, const int64_t* lens, int32_t batch, int32_t n_q, int32_t t_max, int32_t q_c,
+                                          int32_t q1, int32_t q2, double eps, double roll_p, float hqer_scale, float* series,
+                                          void* stream);
+/* series [B][n_series][t_max], lens [B] (one length for the n_series series of a row) ->
+ *   stats [B][n_series][3]: count, mean and median of the finite values (NaN, NaN for none; the median of an even count is the mean of
+ *                           the two middle values);
+ *   feat  [B][n_series][t_max]: the copy DTW aligns: NaNs interpolated linearly between their finite neighbours (the ends clamp; all-NaN
+ *                           gives zeros), then (x - m) / s in fp32 with the mean m and the population standard deviation s computed in
+ *                           float64 and rounded to fp32; zeros when s is 0 or not finite, and past lens[b].
+ * t_max <= TTSAMD_OVERSMOOTH_MAX_FRAMES, else TTSAMD_EINVAL. */
+int32_t ttsamd_series_summary(const float* series, const int64_t* lens, int32_t batch, int32_t n_series, int32_t t_max, float* stats,
+                              float* feat, void* stream);
+/* DTW of a [B][channels][ta_max] against b [B][channels][tb_max] (channels = 1: plain series): metric 0 = L2, 1 = cosine; window -1 = no
+ * band, >= 0 the Sakoe-Chiba radius.  cost [B] fp32 = D[Ta][Tb]; path int32 [B][ta_max + tb_max][2] = (i, j) in ascending time, zeros past
+ * path_len [B] (int32).  All arithmetic is single fp32 operations in the reference's order (local cost summed over the channels in order,
+ * D = cost + best, unwritten cells read 1e30f, predecessor by strict < in the order up, left, diag), so path and cost are reproducible bit
+ * for bit, in a batch or alone.  A band narrower than |Ta - Tb| gives path_len 0 and cost 1e30f; an empty side gives path_len 0 and cost
+ * 1e30f (0 when both are empty).  ta_max, tb_max <= TTSAMD_OVERSMOOTH_MAX_FRAMES.  `workspace` (4-byte aligned) holds the backpointers,
+ * two bits per cell of the diagonal-major table: ttsamd_dtw_workspace_bytes() bytes (-1 for arguments ttsamd_dtw refuses); a smaller
+ * buffer is TTSAMD_EINVAL and nothing is launched. */
+int64_t ttsamd_dtw_workspace_bytes(int32_t batch, int32_t ta_max, int32_t tb_max, int32_t channels);
+int32_t ttsamd_dtw(const float* a, const int64_t* lens_a, const float* b, const int64_t* lens_b, int32_t batch, int32_t channels,
+                   int32_t ta_max, int32_t tb_max, int32_t metric, int32_t window, float* cost, int32_t* path, int32_t* path_len,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+/* mae [B] = mean over k < path_len[b] of |pred[b][path[b][k][0]] - ref[b][path[b][k][1]]| (pred [B][ta_max], ref [B][tb_max]; differences in
+ * fp32, the sum in float64; NaN for an empty path). */
+int32_t ttsamd_dtw_aligned_mae(const float* pred, const float* ref, int32_t batch, int32_t ta_max, int32_t tb_max, const int32_t* path,
+                               const int32_t* path_len, float* mae, void* stream);
+
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of
  *      Tacotron2MS.state_dict() (embedding.weight, speaker_embedding.weight, encoder.*, decoder.*,

@@ -91,6 +91,14 @@ struct MelSpec;
 int32_t melspec_create(const float*, int32_t, int32_t, int32_t, int32_t, int32_t, float, MelSpec**);
 void melspec_destroy(MelSpec*);
 int32_t melspec_forward(const MelSpec*, const float*, int64_t, const int64_t*, int32_t, int32_t, float*, int64_t*, hipStream_t);
+int32_t cepstral_series(const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, float, float*, float*, hipStream_t);
+int32_t cepstral_series_from_power(const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, double, double, float,
+                                   float*, hipStream_t);
+int32_t series_summary(const float*, const int64_t*, int32_t, int32_t, int32_t, float*, float*, hipStream_t);
+int64_t dtw_workspace_bytes(int32_t, int32_t, int32_t, int32_t);
+int32_t dtw(const float*, const int64_t*, const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, float*,
+            int32_t*, int32_t*, void*, int64_t, hipStream_t);
+int32_t dtw_aligned_mae(const float*, const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, float*, hipStream_t);
 struct Taco2;
 int32_t tacotron2_create(const ttsamd_tensor*, int32_t, const ttsamd_tacotron2_cfg*, Taco2**);
 void tacotron2_destroy(Taco2*);
@@ -384,6 +392,33 @@ int32_t ttsamd_melspec_destroy(void* handle) {
 int32_t ttsamd_melspec_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
                                int32_t t_max, float* mel, int64_t* frames_out, void* stream) {
     return melspec_forward((const MelSpec*)handle, wave, wave_stride, nsamples, batch, t_max, mel, frames_out, (hipStream_t)stream);
+}
+
+int32_t ttsamd_cepstral_series(const float* mel, const int64_t* lens, int32_t batch, int32_t n_mels, int32_t t_max, int32_t center,
+                               int32_t hann, int32_t q_c, float hqer_scale, float* power, float* series, void* stream) {
+    return cepstral_series(mel, lens, batch, n_mels, t_max, center, hann, q_c, hqer_scale, power, series, (hipStream_t)stream);
+}
+int32_t ttsamd_cepstral_series_from_power(const float* power, const int64_t* lens, int32_t batch, int32_t n_q, int32_t t_max, int32_t q_c,
+                                          int32_t q1, int32_t q2, double eps, double roll_p, float hqer_scale, float* series,
+                                          void* stream) {
+    return cepstral_series_from_power(power, lens, batch, n_q, t_max, q_c, q1, q2, eps, roll_p, hqer_scale, series, (hipStream_t)stream);
+}
+int32_t ttsamd_series_summary(const float* series, const int64_t* lens, int32_t batch, int32_t n_series, int32_t t_max, float* stats,
+                              float* feat, void* stream) {
+    return series_summary(series, lens, batch, n_series, t_max, stats, feat, (hipStream_t)stream);
+}
+int64_t ttsamd_dtw_workspace_bytes(int32_t batch, int32_t ta_max, int32_t tb_max, int32_t channels) {
+    return dtw_workspace_bytes(batch, ta_max, tb_max, channels);
+}
+int32_t ttsamd_dtw(const float* a, const int64_t* lens_a, const float* b, const int64_t* lens_b, int32_t batch, int32_t channels,
+                   int32_t ta_max, int32_t tb_max, int32_t metric, int32_t window, float* cost, int32_t* path, int32_t* path_len,
+                   void* workspace, int64_t workspace_bytes, void* stream) {
+    return dtw(a, lens_a, b, lens_b, batch, channels, ta_max, tb_max, metric, window, cost, path, path_len, workspace, workspace_bytes,
+               (hipStream_t)stream);
+}
+int32_t ttsamd_dtw_aligned_mae(const float* pred, const float* ref, int32_t batch, int32_t ta_max, int32_t tb_max, const int32_t* path,
+                               const int32_t* path_len, float* mae, void* stream) {
+    return dtw_aligned_mae(pred, ref, batch, ta_max, tb_max, path, path_len, mae, (hipStream_t)stream);
 }
 
 int32_t ttsamd_tacotron2_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_tacotron2_cfg* cfg, void** handle) {

@@ -573,3 +573,149 @@ def length_regulate(enc, reps, t_max):
         L.check(lib.ttsamd_length_regulate(_ptr(enc), _ptr(reps), B, Lt, Cc, t_max, _ptr(out), _ptr(idx), _stream()),
                 'length_regulate')
     return out, idx
+
+
+# ---- oversmoothing analysis (csrc/oversmooth.hip): plain functions, there is nothing to create ---------------------------------------
+OVERSMOOTH_KEYS = ('HQER', 'CSlope', 'CCentroid', 'CRoll95')
+OVERSMOOTH_MAX_FRAMES = 4096                                     # TTSAMD_OVERSMOOTH_MAX_FRAMES of include/ttsamd.h
+_dtw_ws = _Workspace()
+
+
+def _dev_f32(t, ndim, what):
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise L.TtsAmdError(f'{what}: expected a tensor on the ROCm device (there is no CPU fallback)')
+    if t.dim() != ndim:
+        raise L.TtsAmdError(f'{what}: expected {ndim} dimensions, got shape {tuple(t.shape)}')
+    return t.to(torch.float32).contiguous()
+
+
+def _dev_lens(lens, B, T, device):
+    if lens is None:
+        return torch.full((B,), T, dtype=torch.int64, device=device)
+    lens = torch.as_tensor(lens).to(device=device, dtype=torch.int64).contiguous()
+    if lens.shape != (B,):
+        raise L.TtsAmdError(f'lens of shape {tuple(lens.shape)} for a batch of {B}')
+    return lens
+
+
+def cepstral_series(mel, lens=None, center=True, hann=True, q_c=None, hqer_scale=100.0, return_power=False):
+    """mel [B, n_mels, T] on the device (+ lens int64 [B]) -> series [B, 4, T] fp32 in the order OVERSMOOTH_KEYS, one launch
+    (ttsamd_cepstral_series).  HQER is scaled by 100 as compute_mel_oversmoothing_metrics reports it; frames past a row's end are zero."""
+    lib = _require_gpu()
+    mel = _dev_f32(mel, 3, 'cepstral_series: mel')
+    B, M, T = mel.shape
+    lens = _dev_lens(lens, B, T, mel.device)
+    out = torch.empty(B, 4, T, dtype=torch.float32, device=mel.device)
+    power = torch.empty(B, M // 2 + 1, T, dtype=torch.float32, device=mel.device) if return_power else None
+    if B:
+        with torch.cuda.device(mel.device):
+            L.check(lib.ttsamd_cepstral_series(_ptr(mel), _ptr(lens), B, M, T, int(bool(center)), int(bool(hann)),
+                                               -1 if q_c is None else int(q_c), float(hqer_scale), _ptr(power), _ptr(out), _stream()),
+                    'cepstral_series')
+    return (out, power) if return_power else out
+
+
+def cepstral_series_from_power(power, lens=None, q_c=None, q1=1, q2=None, eps=1e-8, roll_p=0.95, hqer_scale=1.0):
+    """power [B, Q, T] on the device -> series [B, 4, T] (ttsamd_cepstral_series_from_power): the four measures with the parameters the
+    reference's *_from_power functions take."""
+    lib = _require_gpu()
+    power = _dev_f32(power, 3, 'cepstral_series_from_power: power')
+    B, Q, T = power.shape
+    lens = _dev_lens(lens, B, T, power.device)
+    out = torch.empty(B, 4, T, dtype=torch.float32, device=power.device)
+    if B:
+        with torch.cuda.device(power.device):
+            L.check(lib.ttsamd_cepstral_series_from_power(_ptr(power), _ptr(lens), B, Q, T, -1 if q_c is None else int(q_c), int(q1),
+                                                          Q - 1 if q2 is None else int(q2), float(eps), float(roll_p), float(hqer_scale),
+                                                          _ptr(out), _stream()), 'cepstral_series_from_power')
+    return out
+
+
+def series_summary(series, lens=None):
+    """series [B, K, T] (+ lens [B]) -> (stats [B, K, 3] = count / mean / median of the finite values, feat [B, K, T] = the NaN-interpolated,
+    z-scored copy the alignment uses).  One launch (ttsamd_series_summary)."""
+    lib = _require_gpu()
+    series = _dev_f32(series, 3, 'series_summary: series')
+    B, K, T = series.shape
+    lens = _dev_lens(lens, B, T, series.device)
+    stats = torch.empty(B, K, 3, dtype=torch.float32, device=series.device)
+    feat = torch.empty(B, K, T, dtype=torch.float32, device=series.device)
+    if B and K:
+        with torch.cuda.device(series.device):
+            L.check(lib.ttsamd_series_summary(_ptr(series), _ptr(lens), B, K, T, _ptr(stats), _ptr(feat), _stream()), 'series_summary')
+    return stats, feat
+
+
+def dtw(a, b, lens_a=None, lens_b=None, metric='l2', window=None, workspace=None):
+    """a [B, M, Ta], b [B, M, Tb] on the device -> (cost [B] fp32, path int32 [B, Ta + Tb, 2] in ascending time, path_len int32 [B]).
+    metric 'l2' | 'cosine', window None or the Sakoe-Chiba radius; all fp32, bit-reproducible (ttsamd_dtw).  `workspace`: a uint8 tensor
+    to use instead of the module's own (it must hold ttsamd_dtw_workspace_bytes)."""
+    lib = _require_gpu()
+    a, b = _dev_f32(a, 3, 'dtw: a'), _dev_f32(b, 3, 'dtw: b')
+    if a.shape[0] != b.shape[0] or a.shape[1] != b.shape[1]:
+        raise L.TtsAmdError(f'dtw: a {tuple(a.shape)} and b {tuple(b.shape)} differ in batch or channels')
+    m = str(metric).lower()
+    if m not in ('l2', 'cosine'):
+        raise L.TtsAmdError(f'dtw: metric {metric!r} (l2 | cosine)')
+    B, M, Ta = a.shape
+    Tb = b.shape[2]
+    lens_a, lens_b = _dev_lens(lens_a, B, Ta, a.device), _dev_lens(lens_b, B, Tb, a.device)
+    cost = torch.empty(B, dtype=torch.float32, device=a.device)
+    path = torch.empty(B, Ta + Tb, 2, dtype=torch.int32, device=a.device)
+    plen = torch.empty(B, dtype=torch.int32, device=a.device)
+    if not B:
+        return cost, path, plen
+    if M < 1:
+        raise L.TtsAmdError('dtw: no channels')
+    nb = int(lib.ttsamd_dtw_workspace_bytes(B, Ta, Tb, M))
+    if nb < 0:
+        raise L.TtsAmdError(f'dtw: {Ta} x {Tb} frames, at most {OVERSMOOTH_MAX_FRAMES} per side are built')
+    ws = _dtw_ws.get(max(nb, 8), a.device) if workspace is None else workspace
+    with torch.cuda.device(a.device):
+        L.check(lib.ttsamd_dtw(_ptr(a), _ptr(lens_a), _ptr(b), _ptr(lens_b), B, M, Ta, Tb, int(m == 'cosine'),
+                               -1 if window is None else int(window), _ptr(cost), _ptr(path), _ptr(plen), _ptr(ws),
+                               nb if workspace is None else int(ws.numel() * ws.element_size()), _stream()), 'dtw')
+    return cost, path, plen
+
+
+def dtw_aligned_mae(pred, ref, path, path_len):
+    """pred [B, Ta], ref [B, Tb], path / path_len of dtw() -> mae [B] = mean |pred[i] - ref[j]| along the path (ttsamd_dtw_aligned_mae)."""
+    lib = _require_gpu()
+    pred, ref = _dev_f32(pred, 2, 'dtw_aligned_mae: pred'), _dev_f32(ref, 2, 'dtw_aligned_mae: ref')
+    B, Ta = pred.shape
+    Tb = ref.shape[1]
+    if ref.shape[0] != B or tuple(path.shape) != (B, Ta + Tb, 2) or path.dtype != torch.int32 or path_len.dtype != torch.int32:
+        raise L.TtsAmdError(f'dtw_aligned_mae: pred {tuple(pred.shape)}, ref {tuple(ref.shape)}, path {tuple(path.shape)} do not belong together')
+    mae = torch.empty(B, dtype=torch.float32, device=pred.device)
+    if B:
+        with torch.cuda.device(pred.device):
+            L.check(lib.ttsamd_dtw_aligned_mae(_ptr(pred), _ptr(ref), B, Ta, Tb, _ptr(path.contiguous()), _ptr(path_len.contiguous()),
+                                               _ptr(mae), _stream()), 'dtw_aligned_mae')
+    return mae
+
+
+def oversmoothing_score(mel_pred, lens_pred, mel_ref, lens_ref, center=True, hann=True, q_c=None):
+    """The paper's comparison of a batch on the device: mel_pred [B, n_mels, Tp], mel_ref [B, n_mels, Tr] (+ lens, None = full rows) ->
+    (series_pred [B, 4, Tp], series_ref [B, 4, Tr], {mae_<k>, delta_u_<k>: [B] tensors for k in OVERSMOOTH_KEYS}).
+    mae_<k>: the two series of key k aligned by DTW on their NaN-interpolated z-scores (L2, no band), mean |difference| of the ORIGINAL
+    series along the path; delta_u_<k>: median(pred) - median(ref) over the finite frames.  Seven launches (2 series, 2 summaries, DTW of
+    the 4 B series pairs, the aligned error, one subtraction), nothing is read back to the host in between."""
+    mel_pred, mel_ref = _dev_f32(mel_pred, 3, 'oversmoothing_score: mel_pred'), _dev_f32(mel_ref, 3, 'oversmoothing_score: mel_ref')
+    if mel_pred.shape[:2] != mel_ref.shape[:2]:
+        raise L.TtsAmdError(f'oversmoothing_score: prediction {tuple(mel_pred.shape)} and reference {tuple(mel_ref.shape)} differ in batch '
+                            'or band count')
+    B, _, Tp = mel_pred.shape
+    Tr = mel_ref.shape[2]
+    lens_pred, lens_ref = _dev_lens(lens_pred, B, Tp, mel_pred.device), _dev_lens(lens_ref, B, Tr, mel_pred.device)
+    sp = cepstral_series(mel_pred, lens_pred, center, hann, q_c)
+    sr = cepstral_series(mel_ref, lens_ref, center, hann, q_c)
+    stp, fp = series_summary(sp, lens_pred)
+    st_r, fr = series_summary(sr, lens_ref)
+    _, path, plen = dtw(fp.view(B * 4, 1, Tp), fr.view(B * 4, 1, Tr), lens_pred.repeat_interleave(4), lens_ref.repeat_interleave(4))
+    mae = dtw_aligned_mae(sp.view(B * 4, Tp), sr.view(B * 4, Tr), path, plen).view(B, 4)
+    delta = stp[:, :, 2] - st_r[:, :, 2]
+    out = {}
+    for k, name in enumerate(OVERSMOOTH_KEYS):
+        out[f'mae_{name}'] = mae[:, k]
+        out[f'delta_u_{name}'] = delta[:, k]
+    return sp, sr, out

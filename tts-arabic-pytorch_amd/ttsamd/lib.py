@@ -86,6 +86,12 @@ SYMBOLS = {
     'ttsamd_melspec_create': (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _F, C.POINTER(_P)]),
     'ttsamd_melspec_destroy': (_I32, [_P]),
     'ttsamd_melspec_forward': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P]),
+    'ttsamd_cepstral_series': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
+    'ttsamd_cepstral_series_from_power': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, C.c_double, C.c_double, _F, _P, _P]),
+    'ttsamd_series_summary': (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
+    'ttsamd_dtw_workspace_bytes': (_I64, [_I32, _I32, _I32, _I32]),
+    'ttsamd_dtw': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    'ttsamd_dtw_aligned_mae': (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),
