@@ -310,6 +310,52 @@ int32_t ttsamd_dtw(const float* a, const int64_t* lens_a, const float* b, const 
 int32_t ttsamd_dtw_aligned_mae(const float* pred, const float* ref, int32_t batch, int32_t ta_max, int32_t tb_max, const int32_t* path,
                                const int32_t* path_len, float* mae, void* stream);
 
+/* ---- FastPitch forced alignment (the aligner path of FastPitch.forward, models/fastpitch/fastpitch/model.py:298-318,331-332: ConvAttention,
+ *      binarize_attention with mas_width1, average_pitch; csrc/aligner.hip).  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays
+ *      8.  Every pointer is device memory, lengths are int64 [batch] and are clamped to the padded size.  No call reads anything back to the
+ *      host.  ttsamd_set_precision does not reach these entries: the encoders' hidden layers are fp32 MFMA, their last 1 x 1 conv and the
+ *      squared distances accumulate in float64, the softmax and MAS are fp32.  The most tokens per row ttsamd_mas and ttsamd_aligner_forward take: */
+#define TTSAMD_MAS_MAX_TOKENS 1024
+typedef struct ttsamd_aligner_cfg {
+    int32_t n_mel;        /* 80: query channels (a multiple of 8) */
+    int32_t d_text;       /* 384: symbols_embedding_dim, the key channels (a multiple of 16) */
+    int32_t n_att;        /* 80: channels both encoders end in (<= 96) */
+    int32_t n_symbols;    /* rows of encoder.word_emb.weight */
+    int32_t padding_idx;  /* its row is loaded as given (zero in the reference's checkpoints) */
+} ttsamd_aligner_cfg;
+/* Weights by their names in FastPitch.state_dict(): encoder.word_emb.weight, attention.key_proj.{0,2}.conv.{weight,bias},
+ * attention.query_proj.{0,2,4}.conv.{weight,bias}.  attention.attn_proj.* is unused by the reference's forward and ignored; a missing
+ * tensor is TTSAMD_EINVAL naming it. */
+int32_t ttsamd_aligner_create(const ttsamd_tensor* weights, int32_t n_weights, const ttsamd_aligner_cfg* cfg, void** handle);
+int32_t ttsamd_aligner_destroy(void* handle);
+int64_t ttsamd_aligner_workspace_bytes(void* handle, int32_t batch, int32_t n_tokens, int32_t n_frames);
+/* ConvAttention.forward (attention.py:174-223): ids int64 [B][n_tokens], mel [B][n_mel][n_frames], attn_prior [B][n_frames][n_tokens] or
+ * NULL -> attn_soft, attn_logprob [B][n_frames][n_tokens] fp32.  Both encoders run over the padded batch without masks, as the reference
+ * runs them: frames and tokens past a row's length are read as the caller passed them.  logit = -0.0005 sum_c (q - k)^2, summed directly;
+ * with a prior, log_softmax over all n_tokens + log(prior + 1e-8); attn_logprob is that value before masking; tokens >= in_lens[b] are
+ * then masked (attn_soft exactly 0 there) and attn_soft is the softmax over the rest.  Frames >= mel_lens[b] are computed like the others
+ * (mel_lens may be NULL: the reference's attention never reads it).  n_tokens <= TTSAMD_MAS_MAX_TOKENS. */
+int32_t ttsamd_aligner_forward(void* handle, const int64_t* ids, const int64_t* in_lens, const float* mel, const int64_t* mel_lens,
+                               const float* attn_prior, int32_t batch, int32_t n_tokens, int32_t n_frames, float* attn_soft,
+                               float* attn_logprob, void* workspace, int64_t workspace_bytes, void* stream);
+/* Monotonic alignment search, mas_width1 of alignment.py:46-72 bit for bit, on row b's [:out_lens[b], :in_lens[b]] corner of attn
+ * [B][n_frames][n_tokens]: is_log != 0: attn holds the log-attention; 0: attn holds probabilities and logf of the stored fp32 value is
+ * taken first (model.py:248).  log_p[0][1:] = -inf; log_p[i][j] += max(log_p[i-1][j-1], log_p[i-1][j]) as one fp32 max and one fp32 add;
+ * the backtrack moves to j - 1 when log_p[i-1][j-1] >= log_p[i-1][j] (ties, two -inf among them, go to j - 1) and stays at token 0 once it
+ * is there.  n_frames < n_tokens follows the same rule.  in_lens[b] == 1: the reference indexes out of bounds there; defined as every
+ * frame assigned to token 0.  dur [B][n_tokens] fp32 = frames per token (zero past in_lens[b]; all zero when out_lens[b] or in_lens[b] is
+ * 0); attn_hard [B][n_frames][n_tokens] (may be NULL) = the 0 / 1 path, zero outside the corner.  `workspace` (8-byte aligned) holds the
+ * decisions at one bit per cell when they do not fit in LDS: ttsamd_mas_workspace_bytes() bytes (often 0; -1 for arguments ttsamd_mas
+ * refuses).  n_tokens > TTSAMD_MAS_MAX_TOKENS is TTSAMD_EINVAL. */
+int64_t ttsamd_mas_workspace_bytes(int32_t batch, int32_t n_frames, int32_t n_tokens);
+int32_t ttsamd_mas(const float* attn, int32_t is_log, const int64_t* in_lens, const int64_t* out_lens, int32_t batch, int32_t n_frames,
+                   int32_t n_tokens, float* dur, float* attn_hard, void* workspace, int64_t workspace_bytes, void* stream);
+/* average_pitch (model.py:93-111): pitch [B][n_formants][n_frames], dur [B][n_tokens] -> out [B][n_formants][n_tokens]: per token the mean
+ * of the non-zero values among its frames [e[l-1], e[l]), e = cumsum(dur) in fp32 truncated to an integer as the reference takes it
+ * (clamped to n_frames); 0 where no frame of the segment is non-zero.  Each segment is summed directly (float64, rounded once). */
+int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
+                             float* out, void* stream);
+
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of
  *      Tacotron2MS.state_dict() (embedding.weight, speaker_embedding.weight, encoder.*, decoder.*,

@@ -99,6 +99,15 @@ int64_t dtw_workspace_bytes(int32_t, int32_t, int32_t, int32_t);
 int32_t dtw(const float*, const int64_t*, const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, float*,
             int32_t*, int32_t*, void*, int64_t, hipStream_t);
 int32_t dtw_aligned_mae(const float*, const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, float*, hipStream_t);
+struct Aligner;
+int32_t aligner_create(const ttsamd_tensor*, int32_t, const ttsamd_aligner_cfg*, Aligner**);
+void aligner_destroy(Aligner*);
+int64_t aligner_workspace_bytes(const Aligner*, int32_t, int32_t, int32_t);
+int32_t aligner_forward(const Aligner*, const int64_t*, const int64_t*, const float*, const int64_t*, const float*, int32_t, int32_t, int32_t,
+                        float*, float*, void*, int64_t, hipStream_t);
+int64_t mas_workspace_bytes(int32_t, int32_t, int32_t);
+int32_t mas(const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, float*, float*, void*, int64_t, hipStream_t);
+int32_t average_pitch(const float*, const float*, int32_t, int32_t, int32_t, int32_t, float*, hipStream_t);
 struct Taco2;
 int32_t tacotron2_create(const ttsamd_tensor*, int32_t, const ttsamd_tacotron2_cfg*, Taco2**);
 void tacotron2_destroy(Taco2*);
@@ -419,6 +428,37 @@ int32_t ttsamd_dtw(const float* a, const int64_t* lens_a, const float* b, const 
 int32_t ttsamd_dtw_aligned_mae(const float* pred, const float* ref, int32_t batch, int32_t ta_max, int32_t tb_max, const int32_t* path,
                                const int32_t* path_len, float* mae, void* stream) {
     return dtw_aligned_mae(pred, ref, batch, ta_max, tb_max, path, path_len, mae, (hipStream_t)stream);
+}
+
+int32_t ttsamd_aligner_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_aligner_cfg* cfg, void** handle) {
+    TTS_REQUIRE(handle, "aligner_create: null handle");
+    Aligner* h = nullptr;
+    const int32_t rc = aligner_create(weights, n, cfg, &h);
+    if (rc == 0) *handle = h;
+    return rc;
+}
+int32_t ttsamd_aligner_destroy(void* handle) {
+    aligner_destroy((Aligner*)handle);
+    return 0;
+}
+int64_t ttsamd_aligner_workspace_bytes(void* handle, int32_t batch, int32_t n_tokens, int32_t n_frames) {
+    if (!handle || batch < 1 || n_tokens < 1 || n_frames < 1) return 0;
+    return aligner_workspace_bytes((const Aligner*)handle, batch, n_tokens, n_frames);
+}
+int32_t ttsamd_aligner_forward(void* handle, const int64_t* ids, const int64_t* in_lens, const float* mel, const int64_t* mel_lens,
+                               const float* attn_prior, int32_t batch, int32_t n_tokens, int32_t n_frames, float* attn_soft,
+                               float* attn_logprob, void* workspace, int64_t workspace_bytes, void* stream) {
+    return aligner_forward((const Aligner*)handle, ids, in_lens, mel, mel_lens, attn_prior, batch, n_tokens, n_frames, attn_soft, attn_logprob,
+                           workspace, workspace_bytes, (hipStream_t)stream);
+}
+int64_t ttsamd_mas_workspace_bytes(int32_t batch, int32_t n_frames, int32_t n_tokens) { return mas_workspace_bytes(batch, n_frames, n_tokens); }
+int32_t ttsamd_mas(const float* attn, int32_t is_log, const int64_t* in_lens, const int64_t* out_lens, int32_t batch, int32_t n_frames,
+                   int32_t n_tokens, float* dur, float* attn_hard, void* workspace, int64_t workspace_bytes, void* stream) {
+    return mas(attn, is_log, in_lens, out_lens, batch, n_frames, n_tokens, dur, attn_hard, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
+                             float* out, void* stream) {
+    return average_pitch(pitch, dur, batch, n_formants, n_frames, n_tokens, out, (hipStream_t)stream);
 }
 
 int32_t ttsamd_tacotron2_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_tacotron2_cfg* cfg, void** handle) {

@@ -9,6 +9,7 @@ Differences, all host-side: the vocoder runs ONCE on the ragged batch instead of
 per-utterance loop (:340-345) — results are identical because every layer pads at the true
 utterance edge — `vowelizer=` runs the Shakkelha / Shakkala taggers of models/diacritizers on the HIP tagger engine.
 """
+from collections import namedtuple
 from typing import List, Optional, Union
 
 import numpy as np
@@ -17,7 +18,8 @@ import torch
 import torch.nn as nn
 
 import text
-from ttsamd.engine import FastPitchEngine
+from ttsamd.engine import ALIGNER_KEYS, AlignerEngine, FastPitchEngine
+from ttsamd.engine import average_pitch as _average_pitch
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
@@ -33,6 +35,16 @@ def text_collate_fn(batch: List[torch.Tensor]):
     for i, j in enumerate(sort_ids):
         ids_pad[i, :batch[j].size(0)] = batch[j]
     return ids_pad, lens_sorted, sort_ids.argsort()
+
+
+# what FastPitch.align returns: dur_tgt [B, L], pitch_tgt / energy_tgt [B, 1, L] or None, the attention maps [B, 1, T, L] or None
+Alignment = namedtuple('Alignment', ['dur_tgt', 'pitch_tgt', 'energy_tgt', 'attn_soft', 'attn_hard', 'attn_logprob'])
+
+
+def _attention_tensors(model_sd):
+    """the aligner's tensors of a checkpoint (`attention.*`, reference model.py:234), kept apart from the inference weights"""
+    return {k: v.detach().cpu().float().numpy() for k, v in model_sd.items()
+            if torch.is_tensor(v) and v.is_floating_point() and k.startswith('attention.')}
 
 
 def pitch_trf(mul: float = 1, add: float = 0):
@@ -53,6 +65,8 @@ class FastPitch(_HipModule):
         self.arabic_in = arabic_in
         self._sd = {k: v.detach().cpu().float().numpy() for k, v in state_dicts['model'].items()
                     if torch.is_tensor(v) and v.is_floating_point() and not k.startswith('attention.')}
+        self._attn_sd = _attention_tensors(state_dicts['model'])      # host copies; nothing goes to the GPU before the first align()
+        self._aligners = {}
         self.config = get_basic_config()
         self.vowelizers = {}
         if vowelizer is not None:
@@ -72,9 +86,60 @@ class FastPitch(_HipModule):
         self._sd = {k: v.detach().cpu().float().numpy() for k, v in state_dict.items()
                     if torch.is_tensor(v) and v.is_floating_point() and not k.startswith('attention.')}
         self._engines.clear()
+        self._attn_sd = _attention_tensors(state_dict)
+        self._aligners.clear()
 
     def state_dict(self, *a, **k):
         return {k_: torch.from_numpy(v) for k_, v in self._sd.items()}
+
+    def release_device_memory(self):
+        super().release_device_memory()
+        self._aligners.clear()
+
+    # ---- forced alignment: the aligner path of FastPitch.forward (models/fastpitch/fastpitch/model.py:298-318,331-332) ----
+    def aligner(self):
+        """The AlignerEngine of the device the module is on, created on first use from the checkpoint's `attention.*` tensors."""
+        dev = self.device
+        if dev.type != 'cuda':
+            raise TtsAmdError(f'FastPitch is on {dev}: the MI355X path has no CPU fallback; move the module with .to("cuda")')
+        missing = [k for k in ALIGNER_KEYS if k != 'encoder.word_emb.weight' and k not in self._attn_sd]
+        if missing:
+            raise TtsAmdError(f'this checkpoint carries no aligner: missing {", ".join(missing)}')
+        if str(dev) not in self._aligners:
+            sd = dict(self._attn_sd)
+            sd['encoder.word_emb.weight'] = self._sd['encoder.word_emb.weight']
+            self._aligners[str(dev)] = AlignerEngine(sd, self.net_config, device=dev)
+        return self._aligners[str(dev)]
+
+    @torch.inference_mode()
+    def align(self, ids_or_text, mel, mel_lens=None, attn_prior=None, pitch=None, energy=None, return_attn=False):
+        """Forced alignment of a recording with its text, as the reference's training forward does it (model.py:298-318,331-332): the
+        checkpoint's ConvAttention scores every (frame, token) pair, monotonic alignment search picks the best monotonic path, and a token's
+        duration is the number of frames the path gives it.  ids_or_text: int64 ids [B, L] zero-padded at the end, or one utterance / a
+        list of utterances as text (tokenised like ttmel; rows keep the order given).  mel [B, n_mel, T] (+ mel_lens [B], None: T frames
+        each); attn_prior [B, T, L] or None; pitch [B, 1, T] / [B, T] and energy [B, T], frame-level tracks to average per token.
+        -> Alignment(dur_tgt [B, L], pitch_tgt [B, 1, L] | None, energy_tgt [B, 1, L] = log(1 + mean) | None, attn_soft, attn_hard,
+        attn_logprob [B, 1, T, L] with return_attn, else None); dur_tgt, pitch_tgt and energy_tgt feed infer() as they are."""
+        if isinstance(ids_or_text, str):
+            ids_or_text = [ids_or_text]
+        if isinstance(ids_or_text, (list, tuple)) and len(ids_or_text) and isinstance(ids_or_text[0], str):
+            rows = [text.tokens_to_ids(self._tokenize(line), self.phon_to_id) for line in ids_or_text]
+            ids = torch.full((len(rows), max(len(r) for r in rows)), self.net_config['padding_idx'], dtype=torch.int64)
+            for b, r in enumerate(rows):
+                ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.int64)
+        else:
+            ids = torch.as_tensor(ids_or_text).long()
+        eng = self.aligner()
+        out = eng.align(ids, mel, mel_lens, attn_prior=attn_prior, return_attn=return_attn)
+        dur, soft, hard, logprob = out if return_attn else (out, None, None, None)
+        pitch_tgt = energy_tgt = None
+        if pitch is not None:
+            pitch = torch.as_tensor(pitch).to(dur.device)
+            pitch_tgt = _average_pitch(pitch[:, None] if pitch.dim() == 2 else pitch, dur)
+        if energy is not None:
+            energy = torch.as_tensor(energy).to(dur.device)
+            energy_tgt = torch.log(1.0 + _average_pitch(energy[:, None] if energy.dim() == 2 else energy, dur))
+        return Alignment(dur, pitch_tgt, energy_tgt, soft, hard, logprob)
 
     # ---- FastPitch.infer (models/fastpitch/fastpitch/model.py:351-353) -------------------
     @torch.inference_mode()

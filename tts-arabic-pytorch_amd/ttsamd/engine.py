@@ -719,3 +719,125 @@ def oversmoothing_score(mel_pred, lens_pred, mel_ref, lens_ref, center=True, han
         out[f'mae_{name}'] = mae[:, k]
         out[f'delta_u_{name}'] = delta[:, k]
     return sp, sr, out
+
+
+# ---- FastPitch forced alignment (csrc/aligner.hip) ------------------------------------------------------------------------------------
+MAS_MAX_TOKENS = 1024                                            # TTSAMD_MAS_MAX_TOKENS of include/ttsamd.h
+ALIGNER_KEYS = ('encoder.word_emb.weight',) + tuple(
+    f'attention.{proj}.{i}.conv.{p}' for proj, idx in (('key_proj', (0, 2)), ('query_proj', (0, 2, 4))) for i in idx for p in ('weight', 'bias'))
+_mas_ws = _Workspace()
+
+
+def mas(log_attn, in_lens, out_lens, is_log=True, return_hard=True, workspace=None):
+    """Monotonic alignment search on the device (ttsamd_mas; the reference's mas_width1 bit for bit, one block per utterance).
+    log_attn [B, T, L] or [B, 1, T, L] fp32 on the device (is_log=False: probabilities, their fp32 log is taken first), in_lens / out_lens
+    [B] -> (dur [B, L] fp32, attn_hard in the shape of log_attn, or None with return_hard=False).  in_lens[b] == 1 assigns every frame to
+    token 0 (the reference indexes out of bounds there)."""
+    lib = _require_gpu()
+    if not isinstance(log_attn, torch.Tensor) or log_attn.device.type != 'cuda':
+        raise L.TtsAmdError('mas: expected a tensor on the ROCm device (there is no CPU fallback)')
+    shape = tuple(log_attn.shape)
+    if log_attn.dim() == 4 and shape[1] == 1:
+        a = log_attn[:, 0]
+    elif log_attn.dim() == 3:
+        a = log_attn
+    else:
+        raise L.TtsAmdError(f'mas: expected [B, T, L] or [B, 1, T, L], got shape {shape}')
+    a = a.to(torch.float32).contiguous()
+    B, T, Lt = a.shape
+    if Lt > MAS_MAX_TOKENS:
+        raise L.TtsAmdError(f'mas: {Lt} tokens, at most {MAS_MAX_TOKENS} are built (TTSAMD_MAS_MAX_TOKENS)')
+    in_lens, out_lens = _dev_lens(in_lens, B, Lt, a.device), _dev_lens(out_lens, B, T, a.device)
+    dur = torch.empty(B, Lt, dtype=torch.float32, device=a.device)
+    hard = torch.empty(B, T, Lt, dtype=torch.float32, device=a.device) if return_hard else None
+    if B and Lt:
+        nb = int(lib.ttsamd_mas_workspace_bytes(B, T, Lt))
+        ws = _mas_ws.get(max(nb, 8), a.device) if workspace is None else workspace
+        with torch.cuda.device(a.device):
+            L.check(lib.ttsamd_mas(_ptr(a), int(bool(is_log)), _ptr(in_lens), _ptr(out_lens), B, T, Lt, _ptr(dur), _ptr(hard), _ptr(ws),
+                                   nb if workspace is None else int(ws.numel() * ws.element_size()), _stream()), 'mas')
+    return dur, (hard.view(shape) if return_hard else None)
+
+
+def average_pitch(pitch, durs):
+    """The reference's average_pitch (model.py:93-111) on the device: pitch [B, F, T], durs [B, L] -> [B, F, L] fp32, per token the mean of
+    the non-zero values of its frames, 0 where there is none (ttsamd_average_pitch)."""
+    lib = _require_gpu()
+    pitch = _dev_f32(pitch, 3, 'average_pitch: pitch')
+    durs = _dev_f32(durs, 2, 'average_pitch: durs')
+    B, F, T = pitch.shape
+    if durs.shape[0] != B:
+        raise L.TtsAmdError(f'average_pitch: pitch {tuple(pitch.shape)} and durs {tuple(durs.shape)} differ in batch')
+    Lt = durs.shape[1]
+    out = torch.empty(B, F, Lt, dtype=torch.float32, device=pitch.device)
+    if B and F and Lt:
+        with torch.cuda.device(pitch.device):
+            L.check(lib.ttsamd_average_pitch(_ptr(pitch), _ptr(durs), B, F, T, Lt, _ptr(out), _stream()), 'average_pitch')
+    return out
+
+
+class AlignerEngine:
+    """Handle over ttsamd_aligner_* (replaces the aligner path of FastPitch.forward, model.py:298-318): `state_dict` holds
+    encoder.word_emb.weight and the attention.key_proj.* / attention.query_proj.* tensors under their reference names."""
+
+    def __init__(self, state_dict, config=None, device='cuda'):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        c = dict(NET_CONFIG if config is None else config)
+        missing = [k for k in ALIGNER_KEYS if k not in state_dict]
+        if missing:
+            raise L.TtsAmdError(f'the checkpoint holds no aligner: missing {", ".join(missing)}')
+        cfg = L.AlignerCfg()
+        cfg.n_mel, cfg.d_text = c['n_mel_channels'], c['symbols_embedding_dim']
+        cfg.n_att = int(np.asarray(state_dict['attention.key_proj.2.conv.bias']).shape[0])
+        cfg.n_symbols, cfg.padding_idx = c['n_symbols'], c['padding_idx']
+        self.n_mel, self.n_symbols, self.padding_idx = cfg.n_mel, cfg.n_symbols, cfg.padding_idx
+        arr, keep = L.make_tensors({k: state_dict[k] for k in ALIGNER_KEYS})
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ttsamd_aligner_create(arr, len(arr), C.byref(cfg), C.byref(handle)), 'aligner_create')
+        self.handle = handle
+        self.ws = _Workspace()
+
+    def __del__(self):
+        if getattr(self, 'handle', None):
+            self.lib.ttsamd_aligner_destroy(self.handle)
+            self.handle = None
+
+    def attention(self, ids, mel, attn_prior=None, in_lens=None):
+        """ConvAttention.forward on the padded batch: ids int64 [B, L], mel [B, n_mel, T], attn_prior [B, T, L] or None ->
+        (attn_soft, attn_logprob), both [B, 1, T, L]; in_lens None = the count of non-padding ids per row."""
+        dev = self.device
+        ids = torch.as_tensor(ids)
+        _check_ids(ids, self.n_symbols, 'aligner ids')
+        ids = ids.to(device=dev, dtype=torch.int64).contiguous()
+        mel = _f32(mel, dev)
+        B, Lt = ids.shape
+        if mel.dim() != 3 or mel.shape[0] != B or mel.shape[1] != self.n_mel:
+            raise L.TtsAmdError(f'aligner: mel of shape {tuple(mel.shape)} for {B} rows of {self.n_mel} bands')
+        T = mel.shape[2]
+        if Lt > MAS_MAX_TOKENS:
+            raise L.TtsAmdError(f'aligner: {Lt} tokens, at most {MAS_MAX_TOKENS} are built (TTSAMD_MAS_MAX_TOKENS)')
+        in_lens = (ids != self.padding_idx).sum(1) if in_lens is None else _dev_lens(in_lens, B, Lt, dev)
+        prior = _f32(attn_prior, dev)
+        if prior is not None and tuple(prior.shape) != (B, T, Lt):
+            raise L.TtsAmdError(f'aligner: attn_prior of shape {tuple(prior.shape)}, expected {(B, T, Lt)}')
+        soft = torch.empty(B, 1, T, Lt, dtype=torch.float32, device=dev)
+        logprob = torch.empty(B, 1, T, Lt, dtype=torch.float32, device=dev)
+        if B and T and Lt:
+            with torch.cuda.device(dev):
+                nb = self.lib.ttsamd_aligner_workspace_bytes(self.handle, B, Lt, T)
+                ws = self.ws.get(nb, dev)
+                L.check(self.lib.ttsamd_aligner_forward(self.handle, _ptr(ids), _ptr(in_lens), _ptr(mel), None, _ptr(prior), B, Lt, T,
+                                                        _ptr(soft), _ptr(logprob), _ptr(ws), nb, _stream()), 'aligner_forward')
+        return soft, logprob, in_lens
+
+    def align(self, ids, mel, mel_lens=None, attn_prior=None, return_attn=False):
+        """ids int64 [B, L] zero-padded at the end, mel [B, n_mel, T], mel_lens [B] (None: every row T frames) -> dur [B, L] fp32, the
+        frames MAS gives each token (model.py:306-314); with return_attn also attn_soft, attn_hard, attn_logprob, each [B, 1, T, L].
+        Two launches of this file's own plus the encoders' six; nothing is read back to the host."""
+        soft, logprob, in_lens = self.attention(ids, mel, attn_prior)
+        B, _, T, Lt = soft.shape
+        mel_lens = _dev_lens(mel_lens, B, T, self.device)
+        dur, hard = mas(soft, in_lens, mel_lens, is_log=False, return_hard=return_attn)
+        return (dur, soft, hard, logprob) if return_attn else dur

@@ -49,6 +49,10 @@ class TaggerCfg(C.Structure):
                 ('n_dense', C.c_int32), ('dense_dim', C.c_int32 * 4)]
 
 
+class AlignerCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('n_mel', 'd_text', 'n_att', 'n_symbols', 'padding_idx')]
+
+
 # every symbol include/ttsamd.h declares: name -> (restype, argtypes)
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -92,6 +96,13 @@ SYMBOLS = {
     'ttsamd_dtw_workspace_bytes': (_I64, [_I32, _I32, _I32, _I32]),
     'ttsamd_dtw': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_dtw_aligned_mae': (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    'ttsamd_aligner_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(AlignerCfg), C.POINTER(_P)]),
+    'ttsamd_aligner_destroy': (_I32, [_P]),
+    'ttsamd_aligner_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),
+    'ttsamd_aligner_forward': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+    'ttsamd_mas_workspace_bytes': (_I64, [_I32, _I32, _I32]),
+    'ttsamd_mas': (_I32, [_P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
+    'ttsamd_average_pitch': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

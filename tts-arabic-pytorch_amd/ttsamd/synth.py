@@ -90,6 +90,26 @@ def fastpitch_state_dict(config=None, seed=0):
     return sd
 
 
+def fastpitch_aligner_state_dict(config=None, seed=0, gain=1.0):
+    """The `attention.key_proj.*` / `attention.query_proj.*` tensors of the reference's FastPitch.state_dict() (ConvAttention,
+    models/fastpitch/fastpitch/attention.py:100-132), which fastpitch_state_dict leaves out.  `gain` scales the last conv of both encoders:
+    the logit is -0.0005 |q - k|^2, so encodings of order 1 give a nearly uniform attention and `gain` of some tens a peaked one."""
+    c = dict(NET_CONFIG if config is None else config)
+    d, m, a = c['symbols_embedding_dim'], c['n_mel_channels'], c['n_mel_channels']
+    sd = {}
+
+    def conv(name, cout, cin, k, g):
+        sd[f'attention.{name}.conv.weight'] = _normal(seed, f'attention.{name}.w', (cout, cin, k), g * 1.4 / np.sqrt(cin * k))
+        sd[f'attention.{name}.conv.bias'] = _normal(seed, f'attention.{name}.b', (cout,), g * 0.1)
+
+    conv('key_proj.0', 2 * d, d, 3, 1.0)
+    conv('key_proj.2', a, 2 * d, 1, gain)
+    conv('query_proj.0', 2 * m, m, 3, 1.0)
+    conv('query_proj.2', m, 2 * m, 1, 1.0)
+    conv('query_proj.4', a, m, 1, gain)
+    return sd
+
+
 def _inv_freq(demb):
     # models/fastpitch/fastpitch/transformer.py:37 — evaluated with torch so the buffer is
     # bit-identical to what the reference module registers.
