@@ -356,6 +356,68 @@ int32_t ttsamd_mas(const float* attn, int32_t is_log, const int64_t* in_lens, co
 int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
                              float* out, void* stream);
 
+/* ---- pYIN pitch tracking, wave -> (f0, voiced_flag, voiced_prob) per frame (librosa.pyin as the reference calls it in
+ *      scripts/extract_f0.py:34-39 and fastpitch/data_function.py:81-114; csrc/pyin.hip).  New symbols only, added WITHOUT a bump:
+ *      TTSAMD_ABI_VERSION stays 8.  Two launches per call whatever the length: a frame kernel (difference function, cumulative-mean
+ *      normalisation, troughs, threshold distribution, pitch bins; one block per frame) and a Viterbi kernel (one block per row, the
+ *      time loop and the backtrack inside).  The arithmetic (DESIGN.md section 4 states it in full):
+ *        W = win_length, pmin = max(floor(sr / fmax), 1), pmax = min(ceil(sr / fmin), frame_length - W - 1), nb = ceil(1 / resolution),
+ *        P = floor(12 nb log2(fmax / fmin)) + 1 pitch bins, tiny = the smallest normal double;
+ *        the row is padded by frame_length / 2 per side, frame t = padded[t hop, t hop + frame_length), frames = 1 + n / hop;
+ *        d(tau) = sum_{j < W} (x[j] - x[j + tau])^2, summed DIRECTLY in float64 over j ascending (the reference's FFT route and its
+ *        clamp of values below 1e-6 are deliberately not reproduced), d'(tau) = d(tau) / (cumsum(d)(tau) / tau + tiny);
+ *        troughs of d' over tau = pmin..pmax with parabolic refinement; thresholds k / n_thresholds weighted by the Beta(beta_a, beta_b)
+ *        CDF in closed form; Boltzmann prior over the troughs under each threshold; the lowest trough gains no_trough_prob times the
+ *        weight of the thresholds it is not under; candidates go to bins of 1 / nb semitone above fmin (two troughs in a bin: the
+ *        larger lag wins); a 2 P-state HMM (voiced bins, then unvoiced) with a triangular local transition of width
+ *        w = round(max_transition_rate 12 hop / sr) nb + 1 (cut at the ends, rows normalised) times the switch matrix, uniform start;
+ *        Viterbi in fp32 over tables computed in float64 and rounded, every log as log(x + tiny), ties to the LOWEST state index.
+ *      Byte parity with a particular librosa release is not pinned.
+ *      Limits (TTSAMD_EINVAL at create): frame_length even and <= 2048, 1 <= win_length < frame_length, P <= 1024, n_thresholds <= 128,
+ *      beta_a and beta_b positive integers (<= 64), w odd with min(P, w) * w <= 12288 table entries, at least three lags. */
+#define TTSAMD_PYIN_MAX_FRAMES 8192   /* 95 s at hop 256 / 22050 Hz; the workspace of one such row at the defaults: 27.9 MB */
+typedef struct ttsamd_pyin_cfg {
+    int32_t sample_rate;          /* 22050 */
+    int32_t frame_length;         /* 1024 in the reference's two calls (librosa's default: 2048) */
+    int32_t win_length;           /* frame_length / 2 */
+    int32_t hop_length;           /* 256 (librosa's default: frame_length / 4) */
+    double fmin, fmax;            /* C2 = 65.406..., C7 = 2093.004... */
+    int32_t n_thresholds;         /* 100 */
+    int32_t beta_a, beta_b;       /* 2, 18 */
+    double boltzmann;             /* 2 */
+    double resolution;            /* 0.1 */
+    double max_transition_rate;   /* 35.92 octaves per second */
+    double switch_prob;           /* 0.01 */
+    double no_trough_prob;        /* 0.01 */
+    int32_t pad_mode;             /* 0 constant (zeros), 1 reflect (periodic reflection about the row's own ends) */
+} ttsamd_pyin_cfg;
+/* The tables the kernels read, computed on the HOST in float64 from cfg alone (no device is touched; create uploads the same ones).
+ * dims [8] = pmin, pmax, P, nb, w, E (the most observations a frame can hold, (pmax - pmin + 2) / 2), n_kinds = min(P, w) distinct
+ * transition rows, 0.  Any table pointer may be NULL: beta [n_thresholds]; expn [E + 1] = exp(-boltzmann p); norm [E + 1] =
+ * (1 - exp(-boltzmann)) / (1 - exp(-boltzmann N)), norm[0] = 0: the prior of position p among N troughs is expn[p] * norm[N];
+ * trans [n_kinds][w][2] = probability of (source row kind, column d = destination - source + w / 2) without / with a voiced-unvoiced
+ * switch, 0 where the destination is cut off; logtrans fp32 [n_kinds][w][2] = log(trans + tiny) rounded; f0 fp32 [P].
+ * Row kind of source bin k: k when P <= w; else k for k < w / 2, k - (P - w) for k >= P - w / 2, w / 2 for every interior row. */
+int32_t ttsamd_pyin_tables(const ttsamd_pyin_cfg* cfg, int32_t* dims, double* beta, double* expn, double* norm, double* trans,
+                           float* logtrans, float* f0);
+int32_t ttsamd_pyin_create(const ttsamd_pyin_cfg* cfg, void** handle);
+int32_t ttsamd_pyin_destroy(void* handle);
+/* Bytes of `workspace` for a call of `batch` rows and t_max = n_frames: the sparse observations (per frame a count, the unvoiced
+ * log-probability and up to E (fp32 log-probability, uint16 bin) pairs) and the Viterbi back-pointers (uint16 [batch][n_frames][2 P]).
+ * -1 for arguments ttsamd_pyin_forward refuses (NULL handle, batch < 1, n_frames < 1 or > TTSAMD_PYIN_MAX_FRAMES). */
+int64_t ttsamd_pyin_workspace_bytes(void* handle, int32_t batch, int32_t n_frames);
+/* wave [B][wave_stride] fp32, nsamples int64 [B] (clamped to [0, wave_stride]) -> f0 [B][t_max] fp32 (Hz; 0 on unvoiced frames),
+ * voiced_flag uint8 [B][t_max], voiced_prob [B][t_max] FLOAT64 (as computed: a sum of table values), states int32 [B][t_max] (may be NULL: the Viterbi state, < P voiced bin,
+ * >= P unvoiced; -1 past the row), frames_out int64 [B] (may be NULL) = min(1 + nsamples[b] / hop, t_max).  Every pointer is device
+ * memory (256-byte aligned workspace), nothing is read back to the host.  Row b equals the call on wave[b][0 : nsamples[b]] alone, bit for
+ * bit; frames at or past a row's count are written as f0 = 0, flag = 0, prob = 0.  The workspace keeps the observations after the call
+ * at the byte offsets ttsamd_pyin_obs_offsets writes to obs_offsets int64 [4] (host): counts int32 [B][t_max], unvoiced fp32 [B][t_max],
+ * log-probabilities fp32 [B][t_max][E], bins uint16 [B][t_max][E] (descending within a frame; only the first count entries are written). */
+int32_t ttsamd_pyin_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t t_max,
+                            float* f0, uint8_t* voiced_flag, double* voiced_prob, int32_t* states, int64_t* frames_out,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int32_t ttsamd_pyin_obs_offsets(void* handle, int32_t batch, int32_t n_frames, int64_t* obs_offsets);
+
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of
  *      Tacotron2MS.state_dict() (embedding.weight, speaker_embedding.weight, encoder.*, decoder.*,

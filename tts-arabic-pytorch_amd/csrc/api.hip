@@ -108,6 +108,14 @@ int32_t aligner_forward(const Aligner*, const int64_t*, const int64_t*, const fl
 int64_t mas_workspace_bytes(int32_t, int32_t, int32_t);
 int32_t mas(const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, float*, float*, void*, int64_t, hipStream_t);
 int32_t average_pitch(const float*, const float*, int32_t, int32_t, int32_t, int32_t, float*, hipStream_t);
+struct Pyin;
+int32_t pyin_tables_host(const ttsamd_pyin_cfg*, int32_t*, double*, double*, double*, double*, float*, float*);
+int32_t pyin_create(const ttsamd_pyin_cfg*, Pyin**);
+void pyin_destroy(Pyin*);
+int64_t pyin_workspace_bytes(const Pyin*, int32_t, int32_t);
+int32_t pyin_obs_offsets(const Pyin*, int32_t, int32_t, int64_t*);
+int32_t pyin_forward(const Pyin*, const float*, int64_t, const int64_t*, int32_t, int32_t, float*, uint8_t*, double*, int32_t*, int64_t*, void*,
+                     int64_t, hipStream_t);
 struct Taco2;
 int32_t tacotron2_create(const ttsamd_tensor*, int32_t, const ttsamd_tacotron2_cfg*, Taco2**);
 void tacotron2_destroy(Taco2*);
@@ -455,6 +463,33 @@ int64_t ttsamd_mas_workspace_bytes(int32_t batch, int32_t n_frames, int32_t n_to
 int32_t ttsamd_mas(const float* attn, int32_t is_log, const int64_t* in_lens, const int64_t* out_lens, int32_t batch, int32_t n_frames,
                    int32_t n_tokens, float* dur, float* attn_hard, void* workspace, int64_t workspace_bytes, void* stream) {
     return mas(attn, is_log, in_lens, out_lens, batch, n_frames, n_tokens, dur, attn_hard, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int32_t ttsamd_pyin_tables(const ttsamd_pyin_cfg* cfg, int32_t* dims, double* beta, double* expn, double* norm, double* trans,
+                           float* logtrans, float* f0) {
+    return pyin_tables_host(cfg, dims, beta, expn, norm, trans, logtrans, f0);
+}
+int32_t ttsamd_pyin_create(const ttsamd_pyin_cfg* cfg, void** handle) {
+    TTS_REQUIRE(handle, "pyin_create: null handle");
+    Pyin* h = nullptr;
+    const int32_t rc = pyin_create(cfg, &h);
+    if (rc == 0) *handle = h;
+    return rc;
+}
+int32_t ttsamd_pyin_destroy(void* handle) {
+    pyin_destroy((Pyin*)handle);
+    return 0;
+}
+int64_t ttsamd_pyin_workspace_bytes(void* handle, int32_t batch, int32_t n_frames) {
+    return pyin_workspace_bytes((const Pyin*)handle, batch, n_frames);
+}
+int32_t ttsamd_pyin_obs_offsets(void* handle, int32_t batch, int32_t n_frames, int64_t* obs_offsets) {
+    return pyin_obs_offsets((const Pyin*)handle, batch, n_frames, obs_offsets);
+}
+int32_t ttsamd_pyin_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t t_max,
+                            float* f0, uint8_t* voiced_flag, double* voiced_prob, int32_t* states, int64_t* frames_out, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    return pyin_forward((const Pyin*)handle, wave, wave_stride, nsamples, batch, t_max, f0, voiced_flag, voiced_prob, states, frames_out,
+                        workspace, workspace_bytes, (hipStream_t)stream);
 }
 int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
                              float* out, void* stream) {

@@ -141,6 +141,27 @@ class FastPitch(_HipModule):
             energy_tgt = torch.log(1.0 + _average_pitch(energy[:, None] if energy.dim() == 2 else energy, dur))
         return Alignment(dur, pitch_tgt, energy_tgt, soft, hard, logprob)
 
+    @torch.inference_mode()
+    def pitch_track(self, wave, wave_lens=None, mel_len=None, normalize=True):
+        """Frame-level pitch of recordings at 22 050 Hz, ready for align(pitch=...): pYIN with the reference's settings (C2..C7, frames of
+        1024 every 256 samples; scripts/extract_f0.py:34-39) on the device (csrc/pyin.hip).  wave [B, n] or [n] (+ wave_lens [B], None: n
+        samples each) -> [B, 1, T], T = mel_len or 1 + n // 256 (trimmed at the end or zero-padded, as the reference fits the track to its
+        mel): f0 in Hz, or with normalize (f0 - pitch_mean) / pitch_std by the checkpoint's statistics (218.14 / 67.24 when it carries
+        none, as infer does); unvoiced frames are 0 either way."""
+        from utils.pitch import note_to_hz, pyin
+        dev = self.device
+        if dev.type != 'cuda':
+            raise TtsAmdError(f'FastPitch is on {dev}: the MI355X path has no CPU fallback; move the module with .to("cuda")')
+        x = torch.as_tensor(wave).to(device=dev, dtype=torch.float32)
+        x = x[None] if x.dim() == 1 else x
+        f0, flag, _ = pyin(x, fmin=note_to_hz('C2'), fmax=note_to_hz('C7'), frame_length=1024, hop_length=256, fill_na=0.0, lens=wave_lens)
+        if normalize:
+            mean, std = (218.14, 67.24) if self.pitch_std == 0.0 else (self.pitch_mean, self.pitch_std)
+            f0 = torch.where(flag, (f0 - mean) / std, torch.zeros_like(f0))
+        if mel_len is not None:
+            f0 = torch.nn.functional.pad(f0, (0, int(mel_len) - f0.shape[1]))
+        return f0[:, None]
+
     # ---- FastPitch.infer (models/fastpitch/fastpitch/model.py:351-353) -------------------
     @torch.inference_mode()
     def infer(self, inputs, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_transform=None,

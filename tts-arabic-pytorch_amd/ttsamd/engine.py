@@ -841,3 +841,124 @@ class AlignerEngine:
         mel_lens = _dev_lens(mel_lens, B, T, self.device)
         dur, hard = mas(soft, in_lens, mel_lens, is_log=False, return_hard=return_attn)
         return (dur, soft, hard, logprob) if return_attn else dur
+
+
+# ---- pYIN pitch tracking (csrc/pyin.hip) ------------------------------------------------------------------------------------------------
+PYIN_MAX_FRAMES = 8192                                          # TTSAMD_PYIN_MAX_FRAMES of include/ttsamd.h
+
+
+def _pyin_cfg(fmin, fmax, sr=22050, frame_length=2048, win_length=None, hop_length=None, n_thresholds=100, beta_parameters=(2, 18),
+              boltzmann_parameter=2, resolution=0.1, max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01,
+              pad_mode='constant'):
+    """librosa.pyin's names and defaults -> ttsamd_pyin_cfg.  What the struct cannot hold is refused here, naming what is built."""
+    a, b = beta_parameters
+    for name, v in (('sr', sr), ('frame_length', frame_length), ('n_thresholds', n_thresholds), ('beta_parameters[0]', a),
+                    ('beta_parameters[1]', b)):
+        if int(v) != v:
+            raise L.TtsAmdError(f'pyin: {name} = {v!r}: integers are built (the Beta CDF in closed form needs integer parameters)')
+    if pad_mode not in ('constant', 'reflect'):
+        raise L.TtsAmdError(f"pyin: pad_mode {pad_mode!r}: 'constant' and 'reflect' are built")
+    frame_length = int(frame_length)
+    cfg = L.PyinCfg()
+    cfg.sample_rate, cfg.frame_length = int(sr), frame_length
+    cfg.win_length = frame_length // 2 if win_length is None else int(win_length)
+    cfg.hop_length = frame_length // 4 if hop_length is None else int(hop_length)
+    cfg.fmin, cfg.fmax = float(fmin), float(fmax)
+    cfg.n_thresholds, cfg.beta_a, cfg.beta_b = int(n_thresholds), int(a), int(b)
+    cfg.boltzmann, cfg.resolution = float(boltzmann_parameter), float(resolution)
+    cfg.max_transition_rate, cfg.switch_prob, cfg.no_trough_prob = float(max_transition_rate), float(switch_prob), float(no_trough_prob)
+    cfg.pad_mode = int(pad_mode == 'reflect')
+    return cfg
+
+
+def pyin_tables(fmin, fmax, **kw):
+    """The tables csrc/pyin.hip builds on the host in float64 and uploads at create (ttsamd_pyin_tables; no GPU is needed):
+    dict(pmin, pmax, n_bins, bins_per_semitone, width, max_obs, n_kinds, beta [K], expn / norm [max_obs + 1], trans [n_kinds, width, 2]
+    float64, logtrans [n_kinds, width, 2] float32, f0 [n_bins] float32)."""
+    lib, cfg = L.load(), _pyin_cfg(fmin, fmax, **kw)
+    dims = (C.c_int32 * 8)()
+    none = C.c_void_p(0)
+    L.check(lib.ttsamd_pyin_tables(C.byref(cfg), dims, none, none, none, none, none, none), 'pyin_tables')
+    pmin, pmax, P, nb, w, E, kinds = list(dims)[:7]
+    beta, expn, norm = np.zeros(cfg.n_thresholds), np.zeros(E + 1), np.zeros(E + 1)
+    trans, logtrans, f0 = np.zeros((kinds, w, 2)), np.zeros((kinds, w, 2), dtype=np.float32), np.zeros(P, dtype=np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L.check(lib.ttsamd_pyin_tables(C.byref(cfg), dims, p(beta), p(expn), p(norm), p(trans), p(logtrans), p(f0)), 'pyin_tables')
+    return dict(pmin=pmin, pmax=pmax, n_bins=P, bins_per_semitone=nb, width=w, max_obs=E, n_kinds=kinds, beta=beta, expn=expn, norm=norm,
+                trans=trans, logtrans=logtrans, f0=f0)
+
+
+class PyinEngine:
+    """Handle over ttsamd_pyin_* (csrc/pyin.hip): wave -> (f0, voiced_flag, voiced_prob) per frame in two launches.  The keyword
+    arguments are librosa.pyin's (the reference's two calls: fmin = C2, fmax = C7, frame_length = 1024, hop_length 256, sr 22050)."""
+
+    def __init__(self, fmin, fmax, device='cuda', **kw):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        cfg = _pyin_cfg(fmin, fmax, **kw)
+        dims = (C.c_int32 * 8)()
+        none = C.c_void_p(0)
+        L.check(self.lib.ttsamd_pyin_tables(C.byref(cfg), dims, none, none, none, none, none, none), 'pyin: configuration')
+        self.n_bins, self.max_obs, self.hop, self.fmin = int(dims[2]), int(dims[5]), int(cfg.hop_length), float(fmin)
+        self.bins_per_semitone = int(dims[3])
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ttsamd_pyin_create(C.byref(cfg), C.byref(handle)), 'pyin_create')
+        self.handle = handle
+        self.ws = _Workspace()
+
+    def __del__(self):
+        if getattr(self, 'handle', None):
+            self.lib.ttsamd_pyin_destroy(self.handle)
+            self.handle = None
+
+    def frames(self, n):
+        return 1 + n // self.hop
+
+    def workspace_bytes(self, batch, n_frames):
+        return int(self.lib.ttsamd_pyin_workspace_bytes(self.handle, int(batch), int(n_frames)))
+
+    def forward(self, wave, nsamples=None, return_states=False, return_obs=False):
+        """wave [B, n_max] float32, nsamples int64 [B] on the device or None (every row n_max long) ->
+        (f0 [B, T] fp32, 0 where unvoiced; voiced_flag [B, T] bool; voiced_prob [B, T] float64; frames int64 [B]), T = frames(n_max),
+        all on the device.  Row b is the call on wave[b, :nsamples[b]] alone; frames at or past a row's own count are zero.  Nothing is
+        read back to the host.  return_states: + the Viterbi states int32 [B, T] (< n_bins voiced, -1 past the row);
+        return_obs: + the sparse observations the Viterbi kernel read, dict(count int32 [B, T], unvoiced fp32 [B, T],
+        logprob fp32 [B, T, max_obs], bin int16-as-int32 [B, T, max_obs]) copied out of the workspace."""
+        wave = _f32(wave, self.device)
+        if wave.dim() != 2:
+            raise L.TtsAmdError(f'PyinEngine.forward: wave of shape {tuple(wave.shape)}, expected [B, n]')
+        B, n_max = wave.shape
+        T = self.frames(n_max)
+        if T > PYIN_MAX_FRAMES:
+            raise L.TtsAmdError(f'PyinEngine.forward: {T} frames; at most {PYIN_MAX_FRAMES} per row are built')
+        if nsamples is None:
+            nsamples = torch.full((B,), n_max, dtype=torch.int64, device=self.device)
+        nsamples = nsamples.to(device=self.device, dtype=torch.int64).contiguous()
+        f0 = torch.empty(B, T, dtype=torch.float32, device=self.device)
+        flag = torch.empty(B, T, dtype=torch.uint8, device=self.device)
+        prob = torch.empty(B, T, dtype=torch.float64, device=self.device)
+        frames = torch.empty(B, dtype=torch.int64, device=self.device)
+        states = torch.empty(B, T, dtype=torch.int32, device=self.device) if return_states else None
+        out = [f0, flag.view(torch.bool), prob, frames]
+        if return_states:
+            out.append(states)
+        if B == 0:
+            return tuple(out) + (({},) if return_obs else ())
+        nbytes = self.workspace_bytes(B, T)
+        if nbytes < 0:
+            raise L.TtsAmdError(f'PyinEngine.forward: batch {B} x {T} frames is refused')
+        ws = self.ws.get(nbytes, self.device)
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ttsamd_pyin_forward(self.handle, _ptr(wave), n_max, _ptr(nsamples), B, T, _ptr(f0), _ptr(flag), _ptr(prob),
+                                                 _ptr(states), _ptr(frames), _ptr(ws), nbytes, _stream()), 'pyin_forward')
+        if return_obs:
+            off = (C.c_int64 * 4)()
+            L.check(self.lib.ttsamd_pyin_obs_offsets(self.handle, B, T, off), 'pyin_obs_offsets')
+            E, n = self.max_obs, B * T
+            obs = dict(count=ws[off[0]: off[0] + 4 * n].view(torch.int32).view(B, T).clone(),
+                       unvoiced=ws[off[1]: off[1] + 4 * n].view(torch.float32).view(B, T).clone(),
+                       logprob=ws[off[2]: off[2] + 4 * n * E].view(torch.float32).view(B, T, E).clone(),
+                       bin=ws[off[3]: off[3] + 2 * n * E].view(torch.int16).view(B, T, E).to(torch.int32))
+            out.append(obs)
+        return tuple(out)

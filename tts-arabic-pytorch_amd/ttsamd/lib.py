@@ -53,6 +53,13 @@ class AlignerCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('n_mel', 'd_text', 'n_att', 'n_symbols', 'padding_idx')]
 
 
+class PyinCfg(C.Structure):
+    _fields_ = [('sample_rate', C.c_int32), ('frame_length', C.c_int32), ('win_length', C.c_int32), ('hop_length', C.c_int32),
+                ('fmin', C.c_double), ('fmax', C.c_double), ('n_thresholds', C.c_int32), ('beta_a', C.c_int32), ('beta_b', C.c_int32),
+                ('boltzmann', C.c_double), ('resolution', C.c_double), ('max_transition_rate', C.c_double),
+                ('switch_prob', C.c_double), ('no_trough_prob', C.c_double), ('pad_mode', C.c_int32)]
+
+
 # every symbol include/ttsamd.h declares: name -> (restype, argtypes)
 _P, _I32, _I64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -103,6 +110,12 @@ SYMBOLS = {
     'ttsamd_mas_workspace_bytes': (_I64, [_I32, _I32, _I32]),
     'ttsamd_mas': (_I32, [_P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
     'ttsamd_average_pitch': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    'ttsamd_pyin_tables': (_I32, [C.POINTER(PyinCfg), _P, _P, _P, _P, _P, _P, _P]),
+    'ttsamd_pyin_create': (_I32, [C.POINTER(PyinCfg), C.POINTER(_P)]),
+    'ttsamd_pyin_destroy': (_I32, [_P]),
+    'ttsamd_pyin_workspace_bytes': (_I64, [_P, _I32, _I32]),
+    'ttsamd_pyin_obs_offsets': (_I32, [_P, _I32, _I32, _P]),
+    'ttsamd_pyin_forward': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

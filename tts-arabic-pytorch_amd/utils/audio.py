@@ -103,3 +103,33 @@ def peak_normalise(wave, peak=0.99):
     """wave / max|wave| * 0.99 (utils/app_utils.py:73-74); returns a new tensor/array."""
     m = abs(wave).max()
     return wave / m * peak if float(m) > 0 else wave
+
+
+def load_wav(path):
+    """Little-endian RIFF/WAVE -> (float32 array [n] in [-1, 1], sample_rate): 16-bit PCM (x / 32768) and 32-bit float, what save_wav
+    writes; several channels are averaged to one.  Anything else raises ValueError.  There is no resampler here."""
+    with open(path, 'rb') as f:
+        raw = f.read()
+    if len(raw) < 12 or raw[:4] != b'RIFF' or raw[8:12] != b'WAVE':
+        raise ValueError(f'{path}: not a RIFF/WAVE file')
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= len(raw):
+        tag, size = raw[pos:pos + 4], struct.unpack('<I', raw[pos + 4:pos + 8])[0]
+        body = raw[pos + 8:pos + 8 + size]
+        if tag == b'fmt ':
+            fmt = struct.unpack('<HHIIHH', body[:16])
+        elif tag == b'data':
+            data = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or data is None:
+        raise ValueError(f'{path}: no fmt / data chunk')
+    code, channels, rate, _, _, bits = fmt
+    if code == 1 and bits == 16:
+        a = np.frombuffer(data[:len(data) // 2 * 2], dtype='<i2').astype(np.float32) / 32768.0
+    elif code == 3 and bits == 32:
+        a = np.frombuffer(data[:len(data) // 4 * 4], dtype='<f4').astype(np.float32)
+    else:
+        raise ValueError(f'{path}: format {code} with {bits} bits: 16-bit PCM and 32-bit float are read')
+    if channels > 1:
+        a = a[:len(a) // channels * channels].reshape(-1, channels).mean(axis=1).astype(np.float32)
+    return a, int(rate)
