@@ -418,6 +418,61 @@ int32_t ttsamd_pyin_forward(void* handle, const float* wave, int64_t wave_stride
                             void* workspace, int64_t workspace_bytes, void* stream);
 int32_t ttsamd_pyin_obs_offsets(void* handle, int32_t batch, int32_t n_frames, int64_t* obs_offsets);
 
+/* ---- Recording preparation: polyphase sinc resampling (torchaudio.functional.resample, 'sinc_interp_hann', as the reference calls it in
+ *      scripts/preprocess_audio.py:33-47 and utils/data.py:59-67; csrc/resample.hip), silence trimming with peak normalisation
+ *      (librosa.effects.trim with ref = np.max and numpy's x / max|x| * 0.999) and removal of silent mel frames (utils/data.py
+ *      remove_silence; csrc/trim.hip).  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.  Every pointer is device memory
+ *      unless it says host, lengths are read on the device, nothing is read back to the host.
+ *      Resampler arithmetic (the table is built by the caller: ttsamd/resample.py): g = gcd(orig, new), o = orig / g, n = new / g,
+ *        base = min(o, n) rolloff, width = ceil(lowpass_filter_width o / base), J = 2 width + o; for j < J, p < n in float64:
+ *        t = clamp(((j - width) / o - p / n) base, -lfw, +lfw), taps[p][j] = sinc(t) cos^2(t pi / lfw / 2) base / o, rounded once to fp32;
+ *        out[f n + p] = sum_{j < J} taps[p][j] xz[f o + j - width], xz = the row, zero outside it, summed over j ascending as one fp32 fma
+ *        chain (both kernels); a row of L samples has ceil(n L / o) outputs.  Parity with a torchaudio release is not pinned.
+ *      Limits (TTSAMD_EINVAL at create): 1 <= o, n <= 4096, J <= 65536. */
+/* taps: HOST [n][J] fp32.  The handle keeps the table on the device, transposed and zero-padded to the kernels' tiles. */
+int32_t ttsamd_resample_create(const float* taps, int32_t o, int32_t n, int32_t width, void** handle);
+int32_t ttsamd_resample_destroy(void* handle);
+/* host helper: ceil(n nsamples / o) in int64 (0 for nsamples <= 0; -1 for a NULL handle) */
+int64_t ttsamd_resample_out_len(void* handle, int64_t nsamples);
+/* 1 when route 2 of ttsamd_resample_forward accepts this handle, else 0 */
+int32_t ttsamd_resample_mfma_eligible(void* handle);
+/* wave [B][wave_stride] fp32, nsamples int64 [B] (clamped to [0, wave_stride]) -> out [B][out_stride] fp32, nout int64 [B] (may be NULL)
+ * = ceil(n nsamples[b] / o).  Row b equals the call on wave[b][0 : nsamples[b]] alone, bit for bit (and both routes run the same fma chain);
+ * samples of out at or past nout[b], up to out_stride, are written as zero; nothing at or past nsamples[b] is read.  out_stride should
+ * be at least ttsamd_resample_out_len(handle, wave_stride): outputs past out_stride are dropped.
+ * route: 0 automatic, 1 the general kernel (VALU; every handle), 2 the MFMA kernel (v_mfma_f32_16x16x4_f32, exact fp32; a block owns
+ * 64 frames of one row and up to 256 phases).  Route 2 is eligible when n >= 16 and the block's LDS fits 160 KB: the skewed input strip,
+ * (63 o + J') (1 + pad / o) floats with J' = J rounded up to 16 and pad = (4 - o mod 8) mod 8, plus two tap tiles of 16 x (32 NTW + 16 ..
+ * 79) floats, NTW = ceil(n / (32 ceil(n / 256))); otherwise TTSAMD_EINVAL with a message.  Route 0 takes the MFMA kernel when it is
+ * eligible and the launch has at least 48 of its blocks, else the general kernel (profiles/r12/NOTES.md). */
+int32_t ttsamd_resample_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, float* out,
+                                int64_t out_stride, int64_t* nout, int32_t route, void* stream);
+
+/* librosa.effects.trim(y, top_db, ref=np.max, frame_length, hop_length) per row, specified by its arithmetic: T = 1 + L / hop frames,
+ * centred with zero padding of frame_length / 2 per side; ms_t = mean of the squares of frame t (fp32); r2_t = max(ms_t, 1e-10); frame t
+ * is non-silent iff r2_t > 10^(-top_db / 10) max_t r2_t; with the first and last non-silent frames a, z: bounds[b] = (a hop,
+ * min(L, (z + 1) hop)), (0, 0) when there is none.  peak [B] (may be NULL) = max |x| over the row, from the same pass.  gain > 0: the
+ * bounds are those of the row scaled to that peak (ms_t (gain / peak)^2 in place of ms_t: what ttsamd_trim_apply writes; the scale only
+ * moves the 1e-10 floor), gain = 0: of the row as given.  Limits: frame_length <= 8192, 1 <= hop_length <= frame_length.
+ * workspace: ttsamd_trim_workspace_bytes(batch, wave_stride, hop_length) bytes (256-byte aligned; -1 for arguments the call refuses). */
+int64_t ttsamd_trim_workspace_bytes(int32_t batch, int64_t wave_stride, int32_t hop_length);
+int32_t ttsamd_trim_bounds(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, float top_db,
+                           int32_t frame_length, int32_t hop_length, float gain, int64_t* bounds, float* peak, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+/* out[b][i] = fl32(fl32(wave[b][start + i] / peak[b]) * gain) for i < end - start (division first, then the multiplication, each rounded
+ * to fp32 as numpy's float32 `x / m * gain`), zero from there to out_stride; peak NULL or peak[b] == 0: the row is copied unscaled.
+ * lens_out int64 [B] (may be NULL) = min(end - start + tail, out_stride): `tail` zeros are counted into the length. */
+int32_t ttsamd_trim_apply(const float* wave, int64_t wave_stride, const int64_t* bounds, const float* peak, float gain, int64_t tail,
+                          int32_t batch, float* out, int64_t out_stride, int64_t* lens_out, void* stream);
+/* The reference's remove_silence + mel_log[:, keep] / pitch[:, keep] per row: mel [B][C][t_max], lens int64 [B], extra [B][C2][t_max]
+ * (may be NULL, then extra_out too).  e_t = the mean of frame t over the C channels (fp32, summed in channel order); keep_t = e_t > thresh;
+ * every frame behind the last kept one is kept as well; with no frame above the threshold frames 1 .. T - 1 are kept and frame 0 is not
+ * (the reference's loop, reproduced).  mel_out / extra_out (other buffers than the inputs): the kept columns in order, bit for bit, zero
+ * from the new length to t_max; lens_out int64 [B] = the new lengths. */
+int32_t ttsamd_frames_compact(const float* mel, const float* extra, const int64_t* lens, int32_t batch, int32_t n_channels,
+                              int32_t n_extra, int32_t t_max, float thresh, float* mel_out, float* extra_out, int64_t* lens_out,
+                              void* stream);
+
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of
  *      Tacotron2MS.state_dict() (embedding.weight, speaker_embedding.weight, encoder.*, decoder.*,

@@ -491,6 +491,41 @@ int32_t ttsamd_pyin_forward(void* handle, const float* wave, int64_t wave_stride
     return pyin_forward((const Pyin*)handle, wave, wave_stride, nsamples, batch, t_max, f0, voiced_flag, voiced_prob, states, frames_out,
                         workspace, workspace_bytes, (hipStream_t)stream);
 }
+int32_t ttsamd_resample_create(const float* taps, int32_t o, int32_t n, int32_t width, void** handle) {
+    TTS_REQUIRE(handle, "resample_create: null handle");
+    Resample* h = nullptr;
+    const int32_t rc = resample_create(taps, o, n, width, &h);
+    if (rc == 0) *handle = h;
+    return rc;
+}
+int32_t ttsamd_resample_destroy(void* handle) {
+    resample_destroy((Resample*)handle);
+    return 0;
+}
+int64_t ttsamd_resample_out_len(void* handle, int64_t nsamples) { return resample_out_len((const Resample*)handle, nsamples); }
+int32_t ttsamd_resample_mfma_eligible(void* handle) { return resample_mfma_eligible((const Resample*)handle); }
+int32_t ttsamd_resample_forward(void* handle, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, float* out,
+                                int64_t out_stride, int64_t* nout, int32_t route, void* stream) {
+    return resample_forward((const Resample*)handle, wave, wave_stride, nsamples, batch, out, out_stride, nout, route, (hipStream_t)stream);
+}
+int64_t ttsamd_trim_workspace_bytes(int32_t batch, int64_t wave_stride, int32_t hop_length) {
+    return trim_workspace_bytes(batch, wave_stride, hop_length);
+}
+int32_t ttsamd_trim_bounds(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, float top_db,
+                           int32_t frame_length, int32_t hop_length, float gain, int64_t* bounds, float* peak, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
+    return trim_bounds(wave, wave_stride, nsamples, batch, top_db, frame_length, hop_length, gain, bounds, peak, workspace, workspace_bytes,
+                       (hipStream_t)stream);
+}
+int32_t ttsamd_trim_apply(const float* wave, int64_t wave_stride, const int64_t* bounds, const float* peak, float gain, int64_t tail,
+                          int32_t batch, float* out, int64_t out_stride, int64_t* lens_out, void* stream) {
+    return trim_apply(wave, wave_stride, bounds, peak, gain, tail, batch, out, out_stride, lens_out, (hipStream_t)stream);
+}
+int32_t ttsamd_frames_compact(const float* mel, const float* extra, const int64_t* lens, int32_t batch, int32_t n_channels,
+                              int32_t n_extra, int32_t t_max, float thresh, float* mel_out, float* extra_out, int64_t* lens_out,
+                              void* stream) {
+    return frames_compact(mel, extra, lens, batch, n_channels, n_extra, t_max, thresh, mel_out, extra_out, lens_out, (hipStream_t)stream);
+}
 int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
                              float* out, void* stream) {
     return average_pitch(pitch, dur, batch, n_formants, n_frames, n_tokens, out, (hipStream_t)stream);

@@ -73,6 +73,22 @@ int32_t launch_overlap_add(const float* Y, const float* win, const int64_t* fram
                            int32_t pad, int32_t B, int32_t F, int32_t n_max, float* wave, int64_t wave_bs, hipStream_t s,
                            int32_t frame_major = 0);   // Y as [b][k][F] (0) or [b][F][k] (1)
 
+// Recording preparation (resample.hip, trim.hip; include/ttsamd.h states the arithmetic)
+struct Resample;
+int32_t resample_create(const float* taps, int32_t o, int32_t n, int32_t width, Resample** out);
+void resample_destroy(Resample* h);
+int64_t resample_out_len(const Resample* h, int64_t nsamples);
+int32_t resample_mfma_eligible(const Resample* h);
+int32_t resample_forward(const Resample* h, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t B, float* out,
+                         int64_t out_stride, int64_t* nout, int32_t route, hipStream_t s);
+int64_t trim_workspace_bytes(int32_t B, int64_t wave_stride, int32_t hop);
+int32_t trim_bounds(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t B, float top_db, int32_t frame_length,
+                    int32_t hop, float gain, int64_t* bounds, float* peak, void* workspace, int64_t workspace_bytes, hipStream_t s);
+int32_t trim_apply(const float* wave, int64_t wave_stride, const int64_t* bounds, const float* peak, float gain, int64_t tail, int32_t B,
+                   float* out, int64_t out_stride, int64_t* lens_out, hipStream_t s);
+int32_t frames_compact(const float* mel, const float* extra, const int64_t* lens, int32_t B, int32_t C, int32_t C2, int32_t t_max,
+                       float thresh, float* mel_out, float* extra_out, int64_t* lens_out, hipStream_t s);
+
 // Profiling of conv launches (bench roofline)
 void prof_begin(hipStream_t s, double flops);
 void prof_end(hipStream_t s);

@@ -962,3 +962,130 @@ class PyinEngine:
                        bin=ws[off[3]: off[3] + 2 * n * E].view(torch.int16).view(B, T, E).to(torch.int32))
             out.append(obs)
         return tuple(out)
+
+
+RESAMPLE_ROUTES = {'auto': 0, 'general': 1, 'mfma': 2}
+
+
+class ResampleEngine:
+    """Handle over ttsamd_resample_* (csrc/resample.hip): polyphase sinc resampling orig_freq -> new_freq with the table of
+    ttsamd.resample.resample_taps (Hann-windowed sinc: torchaudio's 'sinc_interp_hann').  route 'auto' | 'general' (VALU kernel) |
+    'mfma' (fp32 MFMA kernel; raises when the shape is not eligible: `mfma_eligible`)."""
+
+    def __init__(self, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, device='cuda'):
+        from . import resample as R
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        try:
+            taps, self.width, self.o, self.n = R.resample_taps(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        except ValueError as e:
+            raise L.TtsAmdError(str(e)) from None
+        self.taps_per_phase = taps.shape[1]
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(self.lib.ttsamd_resample_create(taps.ctypes.data_as(C.c_void_p), self.o, self.n, self.width, C.byref(handle)),
+                    'resample_create')
+        self.handle = handle
+        self.mfma_eligible = bool(self.lib.ttsamd_resample_mfma_eligible(handle))
+
+    def __del__(self):
+        if getattr(self, 'handle', None):
+            self.lib.ttsamd_resample_destroy(self.handle)
+            self.handle = None
+
+    def out_len(self, n):
+        return int(self.lib.ttsamd_resample_out_len(self.handle, int(n)))
+
+    def forward(self, wave, nsamples=None, route='auto', out_width=None):
+        """wave [B, n_max] float32, nsamples int64 [B] on the device or None (every row n_max long) ->
+        (out [B, out_len(n_max)] (or out_width columns, if wider), nout int64 [B] on the device).  Row b is the call on
+        wave[b, :nsamples[b]] alone, bit for bit; samples at or past a row's own count are zero.  Nothing is read back to the host."""
+        wave = _f32(wave, self.device)
+        if wave.dim() != 2:
+            raise L.TtsAmdError(f'ResampleEngine.forward: wave of shape {tuple(wave.shape)}, expected [B, n]')
+        B, n_max = wave.shape
+        if nsamples is None:
+            nsamples = torch.full((B,), n_max, dtype=torch.int64, device=self.device)
+        nsamples = nsamples.to(device=self.device, dtype=torch.int64).contiguous()
+        W = max(self.out_len(n_max), int(out_width or 0))
+        out = torch.empty(B, W, dtype=torch.float32, device=self.device)
+        nout = torch.empty(B, dtype=torch.int64, device=self.device)
+        if B:
+            with torch.cuda.device(self.device):
+                L.check(self.lib.ttsamd_resample_forward(self.handle, _ptr(wave), n_max, _ptr(nsamples), B, _ptr(out), W, _ptr(nout),
+                                                         RESAMPLE_ROUTES[route], _stream()), 'resample_forward')
+        return out, nout
+
+
+class TrimEngine:
+    """ttsamd_trim_bounds / ttsamd_trim_apply / ttsamd_frames_compact (csrc/trim.hip) with their workspace: librosa.effects.trim's
+    bounds with ref = max, the peak normalisation x / max|x| * gain over the kept span, and the removal of silent mel frames."""
+
+    def __init__(self, device='cuda'):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        self.ws = _Workspace()
+
+    def _wave(self, wave, nsamples):
+        wave = _f32(wave, self.device)
+        if wave.dim() != 2:
+            raise L.TtsAmdError(f'TrimEngine: wave of shape {tuple(wave.shape)}, expected [B, n]')
+        return wave, _dev_lens(nsamples, wave.shape[0], wave.shape[1], self.device)
+
+    def bounds(self, wave, nsamples=None, top_db=60.0, frame_length=2048, hop_length=512, gain=0.0):
+        """wave [B, n_max], nsamples int64 [B] or None -> (bounds int64 [B, 2] = (start, end), peak fp32 [B] = max |x| per row), on the
+        device.  gain > 0: the bounds of the row scaled to that peak (what `apply` writes)."""
+        wave, nsamples = self._wave(wave, nsamples)
+        B, n_max = wave.shape
+        frame_length, hop_length = int(frame_length), int(hop_length)
+        if not 1 <= frame_length <= 8192 or not 1 <= hop_length <= frame_length:
+            raise L.TtsAmdError(f'trim: frame_length {frame_length} / hop_length {hop_length}: frame_length <= 8192 and '
+                                '1 <= hop_length <= frame_length are built')
+        bounds = torch.zeros(B, 2, dtype=torch.int64, device=self.device)
+        peak = torch.zeros(B, dtype=torch.float32, device=self.device)
+        if B:
+            nbytes = int(self.lib.ttsamd_trim_workspace_bytes(B, n_max, hop_length))
+            ws = self.ws.get(nbytes, self.device)
+            with torch.cuda.device(self.device):
+                L.check(self.lib.ttsamd_trim_bounds(_ptr(wave), n_max, _ptr(nsamples), B, float(top_db), frame_length, hop_length,
+                                                    float(gain), _ptr(bounds), _ptr(peak), _ptr(ws), nbytes, _stream()), 'trim_bounds')
+        return bounds, peak
+
+    def apply(self, wave, bounds, peak=None, gain=1.0, tail=0, out_width=None):
+        """-> (out [B, out_width or n_max + tail]: fl32(fl32(x / peak) * gain) over [start, end), zeros behind; lens int64 [B] =
+        end - start + tail)."""
+        wave = _f32(wave, self.device)
+        B, n_max = wave.shape
+        W = int(out_width) if out_width is not None else n_max + int(tail)
+        out = torch.empty(B, W, dtype=torch.float32, device=self.device)
+        lens = torch.empty(B, dtype=torch.int64, device=self.device)
+        bounds = bounds.to(device=self.device, dtype=torch.int64).contiguous()
+        if peak is not None:
+            peak = _f32(peak, self.device)
+        if B:
+            with torch.cuda.device(self.device):
+                L.check(self.lib.ttsamd_trim_apply(_ptr(wave), n_max, _ptr(bounds), _ptr(peak), float(gain), int(tail), B, _ptr(out), W,
+                                                   _ptr(lens), _stream()), 'trim_apply')
+        return out, lens
+
+    def compact(self, mel, lens=None, thresh=-10.0, extra=None):
+        """mel [B, C, T] (+ extra [B, C2, T]) on the device -> (mel', extra' or None, lens'): the columns whose channel mean is above
+        `thresh`, plus everything behind the last such column (the reference's remove_silence), moved to the front; zeros behind."""
+        mel = _dev_f32(mel, 3, 'drop_silent_frames: mel')
+        B, Cn, T = mel.shape
+        lens = _dev_lens(lens, B, T, mel.device)
+        C2 = 0
+        if extra is not None:
+            extra = _dev_f32(extra, 3, 'drop_silent_frames: extra')
+            if extra.shape[0] != B or extra.shape[2] != T:
+                raise L.TtsAmdError(f'drop_silent_frames: extra of shape {tuple(extra.shape)} next to mel {tuple(mel.shape)}')
+            C2 = extra.shape[1]
+        mel_out = torch.empty_like(mel)
+        extra_out = torch.empty_like(extra) if extra is not None else None
+        lens_out = torch.empty(B, dtype=torch.int64, device=mel.device)
+        if B and Cn:
+            with torch.cuda.device(mel.device):
+                L.check(self.lib.ttsamd_frames_compact(_ptr(mel), _ptr(extra), _ptr(lens), B, Cn, C2, T, float(thresh), _ptr(mel_out),
+                                                       _ptr(extra_out), _ptr(lens_out), _stream()), 'frames_compact')
+        return mel_out, extra_out, lens_out

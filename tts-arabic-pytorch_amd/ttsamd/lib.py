@@ -116,6 +116,15 @@ SYMBOLS = {
     'ttsamd_pyin_workspace_bytes': (_I64, [_P, _I32, _I32]),
     'ttsamd_pyin_obs_offsets': (_I32, [_P, _I32, _I32, _P]),
     'ttsamd_pyin_forward': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    'ttsamd_resample_create': (_I32, [_P, _I32, _I32, _I32, C.POINTER(_P)]),
+    'ttsamd_resample_destroy': (_I32, [_P]),
+    'ttsamd_resample_out_len': (_I64, [_P, _I64]),
+    'ttsamd_resample_mfma_eligible': (_I32, [_P]),
+    'ttsamd_resample_forward': (_I32, [_P, _P, _I64, _P, _I32, _P, _I64, _P, _I32, _P]),
+    'ttsamd_trim_workspace_bytes': (_I64, [_I32, _I64, _I32]),
+    'ttsamd_trim_bounds': (_I32, [_P, _I64, _P, _I32, _F, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
+    'ttsamd_trim_apply': (_I32, [_P, _I64, _P, _P, _F, _I64, _I32, _P, _I64, _P, _P]),
+    'ttsamd_frames_compact': (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

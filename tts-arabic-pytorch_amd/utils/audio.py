@@ -2,7 +2,10 @@
 The reference calls torchaudio.save(path, wave[None], 22050) (inference.py:61-63, utils/app_utils.py:76-77);
 torchaudio is not a dependency here, so the RIFF container is written directly.
 Analysis side: `MelSpectrogram` (reference utils/audio.py:6-46), the 80-band mel the acoustic models and HiFi-GAN were trained on,
-as one HIP launch (csrc/melspec.hip)."""
+as one HIP launch (csrc/melspec.hip).
+Input side: `resample` / `Resample` (torchaudio.functional.resample's name and defaults), `trim` (librosa.effects.trim's) and
+`prepare_recording` = the clean-up of the reference's scripts/preprocess_audio.py:33-47 (resample with lowpass_filter_width=1024,
+peak 0.999, trim at 23 dB, 768 zeros appended), on the device (csrc/resample.hip, csrc/trim.hip)."""
 import struct
 
 import numpy as np
@@ -10,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from ttsamd import melfb
-from ttsamd.engine import MelSpecEngine
+from ttsamd.engine import MelSpecEngine, ResampleEngine, TrimEngine
 from ttsamd.lib import TtsAmdError
 
 
@@ -107,7 +110,8 @@ def peak_normalise(wave, peak=0.99):
 
 def load_wav(path):
     """Little-endian RIFF/WAVE -> (float32 array [n] in [-1, 1], sample_rate): 16-bit PCM (x / 32768) and 32-bit float, what save_wav
-    writes; several channels are averaged to one.  Anything else raises ValueError.  There is no resampler here."""
+    writes; several channels are averaged to one.  Anything else raises ValueError.  The samples come back at the file's own rate:
+`load_recording` adds the resampler."""
     with open(path, 'rb') as f:
         raw = f.read()
     if len(raw) < 12 or raw[:4] != b'RIFF' or raw[8:12] != b'WAVE':
@@ -133,3 +137,107 @@ def load_wav(path):
     if channels > 1:
         a = a[:len(a) // channels * channels].reshape(-1, channels).mean(axis=1).astype(np.float32)
     return a, int(rate)
+
+
+_resamplers, _trimmers = {}, {}
+
+
+def _device_wave(x, what):
+    if not isinstance(x, torch.Tensor) or x.device.type != 'cuda':
+        raise TtsAmdError(f'{what}: expected a tensor on the ROCm device; the MI355X path has no CPU fallback (move it with .to("cuda"))')
+    return x
+
+
+def _resampler(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, device):
+    """Checks the arguments; -> the cached engine, or None when the two rates are equal."""
+    if resampling_method != 'sinc_interp_hann':
+        raise TtsAmdError(f"resample: resampling_method {resampling_method!r}: only 'sinc_interp_hann' is built")
+    try:
+        ok = int(orig_freq) == orig_freq and int(new_freq) == new_freq and orig_freq > 0 and new_freq > 0 and lowpass_filter_width > 0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise TtsAmdError(f'resample: positive integer rates and a positive lowpass_filter_width are built (got {orig_freq}, {new_freq}, '
+                          f'{lowpass_filter_width})')
+    if int(orig_freq) == int(new_freq):
+        return None
+    key = (int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), str(device))
+    if key not in _resamplers:
+        _resamplers[key] = ResampleEngine(*key[:4], device=device)
+    return _resamplers[key]
+
+
+def _trimmer(device):
+    if str(device) not in _trimmers:
+        _trimmers[str(device)] = TrimEngine(device=device)
+    return _trimmers[str(device)]
+
+
+def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method='sinc_interp_hann', beta=None,
+             lens=None, route='auto'):
+    """torchaudio.functional.resample on the device: waveform [..., n] -> [..., ceil(n * new_freq / orig_freq)].  With `lens` (int64
+    [rows]: samples per row of a ragged batch) it returns (wave, new_lens), new_lens on the device; every row is then the call on its
+    own samples alone and is zero behind its new length.  Equal rates return the input unchanged.  Only 'sinc_interp_hann' is built."""
+    _device_wave(waveform, 'resample')
+    eng = _resampler(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, waveform.device)
+    if lens is not None:
+        lens = torch.as_tensor(lens).to(device=waveform.device, dtype=torch.int64)
+    if eng is None:
+        return waveform if lens is None else (waveform, lens)
+    shape = waveform.shape
+    out, nout = eng.forward(waveform.reshape(-1, shape[-1]), None if lens is None else lens.reshape(-1), route=route)
+    out = out.reshape(shape[:-1] + (out.shape[-1],))
+    return out if lens is None else (out, nout.reshape(lens.shape))
+
+
+class Resample(nn.Module):
+    """torchaudio.transforms.Resample's name and defaults over one ResampleEngine (the table is built once, at the first call on a
+    device)."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, resampling_method: str = 'sinc_interp_hann',
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99, beta=None):
+        super().__init__()
+        if resampling_method != 'sinc_interp_hann':
+            raise TtsAmdError(f"Resample: resampling_method {resampling_method!r}: only 'sinc_interp_hann' is built")
+        self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff = orig_freq, new_freq, lowpass_filter_width, rolloff
+        self.resampling_method = resampling_method
+
+    @torch.inference_mode()
+    def forward(self, waveform, lens=None):
+        return resample(waveform, self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, lens=lens)
+
+
+def trim(y, top_db=60, frame_length=2048, hop_length=512, lens=None):
+    """librosa.effects.trim (ref = max) on the device.  One row [n]: (y[start:end], (start, end)) -- two integers, read from the device.
+    A batch [B, n] (+ lens int64 [B]): bounds int64 [B, 2] on the device, no host read."""
+    _device_wave(y, 'trim')
+    eng = _trimmer(y.device)
+    if y.dim() == 1:
+        bounds, _ = eng.bounds(y[None], None, top_db, frame_length, hop_length)
+        start, end = (int(v) for v in bounds[0].tolist())
+        return y[start:end], (start, end)
+    bounds, _ = eng.bounds(y, lens, top_db, frame_length, hop_length)
+    return bounds
+
+
+@torch.inference_mode()
+def prepare_recording(wave, sample_rate, lens=None, sr_target=22050, lowpass_filter_width=1024, peak=0.999, top_db=23, frame_length=1024,
+                      hop_length=256, tail_silence=768):
+    """The reference's recording clean-up (scripts/preprocess_audio.py:33-47) for a batch on the device: resample to sr_target, scale
+    each row to the peak `peak` (x / max|x| * peak), trim leading and trailing silence (librosa.effects.trim at top_db on the scaled
+    row), append tail_silence zeros.  wave [B, n] (or [n]), lens int64 [B] -> (wave [B, width], lens int64 [B]) on the device, width =
+    the resampled width + tail_silence; rows are zero behind their length.  No host synchronisation."""
+    _device_wave(wave, 'prepare_recording')
+    x = wave.reshape(-1, wave.shape[-1])
+    if lens is None:
+        lens = torch.full((x.shape[0],), x.shape[1], dtype=torch.int64, device=x.device)
+    x, n = resample(x, sample_rate, sr_target, lowpass_filter_width, lens=lens)
+    eng = _trimmer(x.device)
+    bounds, pk = eng.bounds(x, n, top_db, frame_length, hop_length, gain=peak)
+    return eng.apply(x, bounds, pk, gain=peak, tail=tail_silence, out_width=x.shape[1] + int(tail_silence))
+
+
+def load_recording(path, sr_target=22050, device='cuda'):
+    """load_wav + resample: a wav file at any rate -> float32 tensor [n] at sr_target on the device (torchaudio's default filter)."""
+    a, rate = load_wav(path)
+    return resample(torch.from_numpy(a).to(device), rate, sr_target)
