@@ -310,6 +310,40 @@ int32_t ttsamd_dtw(const float* a, const int64_t* lens_a, const float* b, const 
 int32_t ttsamd_dtw_aligned_mae(const float* pred, const float* ref, int32_t batch, int32_t ta_max, int32_t tb_max, const int32_t* path,
                                const int32_t* path_len, float* mae, void* stream);
 
+/* ---- Objective evaluation of a prediction against a recording (csrc/objective.hip): mel-cepstral distortion, mel error, F0 errors and
+ *      voicing error along a path of ttsamd_dtw.  The reference has no such module: the arithmetic below is the specification.  New
+ *      symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.  Every pointer is device memory, lengths are int64 [batch], read
+ *      on the device and clamped to the padded size.  No call reads anything back to the host. */
+/* logmel [B][n_mels][t_max] fp32 -> cep [B][n_coef][t_max] fp32: the orthonormal DCT-II across the bands of every frame,
+ *   c_k[t] = s_k sum_{m < M} x_m[t] cos(pi k (2m + 1) / (2M)),  s_0 = sqrt(1 / M), s_k = sqrt(2 / M)
+ * (scipy.fft.dct(x, type=2, norm='ortho', axis=bands)[:n_coef]).  Products and sums are float64 over m ascending, the basis comes from a
+ * float64 table with the argument reduced mod 4M in integers; the result is rounded once to fp32.  1 <= n_mels <= 128,
+ * 1 <= n_coef <= min(n_mels, 64), else TTSAMD_EINVAL.  Frames at or past lens[b] are written as zero and never read; row b equals the
+ * call on row b alone, bit for bit. */
+int32_t ttsamd_mel_cepstrum(const float* logmel, const int64_t* lens, int32_t batch, int32_t n_mels, int32_t t_max, int32_t n_coef, float* cep,
+                            void* stream);
+/* The scores of pair b along its path: cep_a [B][n_coef][ta_max], cep_b [B][n_coef][tb_max]; mel_a / mel_b [B][n_mels][t*_max] (both may
+ * be NULL); f0_a / f0_b [B][t*_max] in Hz (both may be NULL); path int32 [B][ta_max + tb_max][2] and path_len int32 [B] exactly as
+ * ttsamd_dtw writes them (steps (i_p, j_p), p < n = path_len[b]; indices are clamped to the padded size).  A frame is voiced when its f0
+ * is finite and > 0.  stats [B][TTSAMD_EVAL_STATS] FLOAT64:
+ *   0 n              path_len[b]
+ *   1 mcd            scale mean_p sqrt(sum_{c = first_coef}^{n_coef - 1} (cep_a[c][i_p] - cep_b[c][j_p])^2)   (10 sqrt(2) / ln 10 gives dB;
+ *                    first_coef = 1 leaves c0, the level, out)
+ *   2 mel_mae        mean over p and m of |mel_a[m][i_p] - mel_b[m][j_p]|; NaN without mels
+ *   3 n_vv           steps where both frames are voiced
+ *   4 f0_rmse_cents  sqrt(mean over those steps of (1200 log2(f0_a / f0_b))^2)
+ *   5 f0_rmse_hz     sqrt(mean over those steps of (f0_a - f0_b)^2)
+ *   6 f0_corr        Pearson correlation of the two f0 over those steps, in two passes (the means, then the centred sums); NaN when
+ *                    n_vv < 2 or a centred sum of squares is 0
+ *   7 vuv_error      (steps whose two frames differ in voicing) / n
+ * Every input is widened to float64 before the first subtraction.  n = 0: n = 0, n_vv = 0, NaN elsewhere; n_vv = 0: NaN in 4..6; without
+ * f0: NaN in 3..7.  first_coef outside [0, n_coef) is TTSAMD_EINVAL.  One block per pair; step p is added by thread p mod 256 in
+ * ascending order and the block sum is a fixed tree, so row b equals the call on pair b alone, bit for bit. */
+#define TTSAMD_EVAL_STATS 8
+int32_t ttsamd_dtw_aligned_eval(const float* cep_a, const float* cep_b, int32_t n_coef, int32_t first_coef, const float* mel_a,
+                                const float* mel_b, int32_t n_mels, const float* f0_a, const float* f0_b, int32_t batch, int32_t ta_max,
+                                int32_t tb_max, const int32_t* path, const int32_t* path_len, double scale, double* stats, void* stream);
+
 /* ---- FastPitch forced alignment (the aligner path of FastPitch.forward, models/fastpitch/fastpitch/model.py:298-318,331-332: ConvAttention,
  *      binarize_attention with mas_width1, average_pitch; csrc/aligner.hip).  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays
  *      8.  Every pointer is device memory, lengths are int64 [batch] and are clamped to the padded size.  No call reads anything back to the

@@ -99,6 +99,9 @@ int64_t dtw_workspace_bytes(int32_t, int32_t, int32_t, int32_t);
 int32_t dtw(const float*, const int64_t*, const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, float*,
             int32_t*, int32_t*, void*, int64_t, hipStream_t);
 int32_t dtw_aligned_mae(const float*, const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, float*, hipStream_t);
+int32_t mel_cepstrum(const float*, const int64_t*, int32_t, int32_t, int32_t, int32_t, float*, hipStream_t);
+int32_t dtw_aligned_eval(const float*, const float*, int32_t, int32_t, const float*, const float*, int32_t, const float*, const float*, int32_t,
+                         int32_t, int32_t, const int32_t*, const int32_t*, double, double*, hipStream_t);
 struct Aligner;
 int32_t aligner_create(const ttsamd_tensor*, int32_t, const ttsamd_aligner_cfg*, Aligner**);
 void aligner_destroy(Aligner*);
@@ -436,6 +439,17 @@ int32_t ttsamd_dtw(const float* a, const int64_t* lens_a, const float* b, const 
 int32_t ttsamd_dtw_aligned_mae(const float* pred, const float* ref, int32_t batch, int32_t ta_max, int32_t tb_max, const int32_t* path,
                                const int32_t* path_len, float* mae, void* stream) {
     return dtw_aligned_mae(pred, ref, batch, ta_max, tb_max, path, path_len, mae, (hipStream_t)stream);
+}
+
+int32_t ttsamd_mel_cepstrum(const float* logmel, const int64_t* lens, int32_t batch, int32_t n_mels, int32_t t_max, int32_t n_coef, float* cep,
+                            void* stream) {
+    return mel_cepstrum(logmel, lens, batch, n_mels, t_max, n_coef, cep, (hipStream_t)stream);
+}
+int32_t ttsamd_dtw_aligned_eval(const float* cep_a, const float* cep_b, int32_t n_coef, int32_t first_coef, const float* mel_a,
+                                const float* mel_b, int32_t n_mels, const float* f0_a, const float* f0_b, int32_t batch, int32_t ta_max,
+                                int32_t tb_max, const int32_t* path, const int32_t* path_len, double scale, double* stats, void* stream) {
+    return dtw_aligned_eval(cep_a, cep_b, n_coef, first_coef, mel_a, mel_b, n_mels, f0_a, f0_b, batch, ta_max, tb_max, path, path_len, scale,
+                            stats, (hipStream_t)stream);
 }
 
 int32_t ttsamd_aligner_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_aligner_cfg* cfg, void** handle) {

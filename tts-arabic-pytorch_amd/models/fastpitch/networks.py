@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 import text
-from ttsamd.engine import ALIGNER_KEYS, AlignerEngine, FastPitchEngine
+from ttsamd.engine import ALIGNER_KEYS, OBJECTIVE_KEYS, AlignerEngine, FastPitchEngine, ObjectiveEngine
 from ttsamd.engine import average_pitch as _average_pitch
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
@@ -358,6 +358,65 @@ class FastPitch2Wave(nn.Module):
         for k in range(0, len(text_input), batch_size):
             wav_list += self.tts_batch(text_input[k:k + batch_size], **kw)
         return wav_list
+
+    # ---- objective evaluation against recordings (not in the reference; ttsamd.engine.ObjectiveEngine, csrc/objective.hip) ----
+    @staticmethod
+    def _pad_waves(waves, device):
+        """list of 1-D waves (tensors / arrays) -> (float32 [B, n_max] on the device, zero-padded; samples int64 [B] on the device)"""
+        rows = [torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).reshape(-1).float() for w in waves]
+        n = [int(r.numel()) for r in rows]
+        out = torch.zeros(len(rows), max(n), dtype=torch.float32, device=device)
+        for b, r in enumerate(rows):
+            out[b, :n[b]] = r.to(device)
+        return out, torch.tensor(n, dtype=torch.int64).to(device)
+
+    @torch.inference_mode()
+    def evaluate(self, text_input: Union[str, List[str]], recordings, teacher_forced: bool = False, align: str = 'dtw', n_coef: int = 13,
+                 window=None, **tts_options):
+        """Synthesise the lines and score every wave against its recording (a 22 050 Hz wave, already prepared: utils.audio.prepare_recording):
+        one dict of Python floats per line with the keys of ttsamd.engine.OBJECTIVE_KEYS (n, mcd, mel_mae, n_vv, f0_rmse_cents, f0_rmse_hz,
+        f0_corr, vuv_error) plus frames_pred / frames_ref.  Default: `tts(lines, **tts_options)`, then ObjectiveEngine.score_waves with
+        `align` ('dtw' | 'frames'), `n_coef`, `window`.  teacher_forced: the recording's log-mel, its pitch_track and its energy (the L2 norm
+        over the bands, as the reference's data_function takes it) go through FastPitch.align, the resulting dur / pitch / energy targets
+        go to infer, so the prediction has the recording's durations; tts_options are then speaker_id, denoise (default 0.005) and
+        vowelizer."""
+        dev = self.device
+        if dev.type != 'cuda':
+            raise TtsAmdError(f'FastPitch2Wave is on {dev}: the MI355X path has no CPU fallback; move the module with .to("cuda")')
+        lines = [text_input] if isinstance(text_input, str) else list(text_input)
+        if isinstance(text_input, str) and not (isinstance(recordings, (list, tuple)) and len(recordings) == 1):
+            recordings = [recordings]
+        if len(recordings) != len(lines) or not lines:
+            raise TtsAmdError(f'evaluate: {len(lines)} lines against {len(recordings)} recordings')
+        if getattr(self, '_objective', None) is None or self._objective.device != dev:
+            self._objective = ObjectiveEngine(device=dev)
+        obj = self._objective
+        rec, n_rec = self._pad_waves(recordings, dev)
+        if not teacher_forced:
+            waves = self.tts(lines, **tts_options)
+            wave, n = self._pad_waves(waves, dev)
+        else:
+            extra = set(tts_options) - {'speaker_id', 'denoise', 'vowelizer'}
+            if extra:
+                raise TtsAmdError(f'evaluate(teacher_forced=True): {sorted(extra)} do not apply (durations, pitch and energy come from the '
+                                  'recording); speaker_id, denoise and vowelizer are taken')
+            speaker, denoise = tts_options.get('speaker_id', 0), tts_options.get('denoise', 0.005)
+            model = self.model
+            rows = [text.tokens_to_ids(model._tokenize(line, tts_options.get('vowelizer')), model.phon_to_id) for line in lines]
+            ids = torch.full((len(rows), max(len(r) for r in rows)), model.net_config['padding_idx'], dtype=torch.int64)
+            for b, r in enumerate(rows):
+                ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.int64)
+            mel_rec, frames = obj.melspec.forward(rec, n_rec)
+            pitch = model.pitch_track(rec, n_rec, mel_len=mel_rec.shape[2])
+            tgt = model.align(ids, mel_rec, frames, pitch=pitch, energy=torch.linalg.vector_norm(mel_rec, dim=1))
+            mel, dec_lens, *_ = model.infer(ids, dur_tgt=tgt.dur_tgt, pitch_tgt=tgt.pitch_tgt, energy_tgt=tgt.energy_tgt, speaker=speaker)
+            eng = self.vocoder.engine()
+            wave, n = eng.forward(mel, dec_lens), dec_lens * eng.hop
+            if denoise > 0:
+                wave = self.denoiser.forward_batch(wave, n, denoise)
+        score = obj.score_waves(wave, n, rec, n_rec, n_coef=n_coef, align=align, window=window)
+        table = torch.stack([score[k] for k in OBJECTIVE_KEYS] + [score['lens_pred'].double(), score['lens_ref'].double()], dim=1).cpu().tolist()
+        return [dict(zip(OBJECTIVE_KEYS + ('frames_pred', 'frames_ref'), row)) for row in table]
 
     # utterances per vocoder call of the list pipeline: chunks of `batch_size` lines go through FastPitch one by one (a chunk is the
     # reference's padded batch: its results depend on the chunk's composition, SURVEY 3.4-1), their mels are vocoded together

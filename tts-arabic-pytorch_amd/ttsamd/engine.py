@@ -721,6 +721,166 @@ def oversmoothing_score(mel_pred, lens_pred, mel_ref, lens_ref, center=True, han
     return sp, sr, out
 
 
+# ---- objective evaluation (csrc/objective.hip): MCD, mel error, F0 and voicing errors along a DTW path ---------------------------------
+OBJECTIVE_KEYS = ('n', 'mcd', 'mel_mae', 'n_vv', 'f0_rmse_cents', 'f0_rmse_hz', 'f0_corr', 'vuv_error')   # TTSAMD_EVAL_STATS = 8
+MCD_SCALE = 10.0 * np.sqrt(2.0) / np.log(10.0)                   # cepstral distance of natural-log mels -> dB
+MEL_CEPSTRUM_MAX_MELS, MEL_CEPSTRUM_MAX_COEF = 128, 64
+
+
+def mel_cepstrum(logmel, lens=None, n_coef=13):
+    """logmel [B, n_mels, T] on the device (+ lens int64 [B]) -> cep [B, n_coef, T] fp32: the orthonormal DCT-II across the bands of
+    every frame (scipy.fft.dct(type=2, norm='ortho')[:n_coef]), float64 inside, rounded once; frames past a row's end are zero.  One
+    launch (ttsamd_mel_cepstrum)."""
+    lib = _require_gpu()
+    logmel = _dev_f32(logmel, 3, 'mel_cepstrum: logmel')
+    B, M, T = logmel.shape
+    if not 1 <= M <= MEL_CEPSTRUM_MAX_MELS:
+        raise L.TtsAmdError(f'mel_cepstrum: {M} bands; 1 to {MEL_CEPSTRUM_MAX_MELS} are built')
+    if int(n_coef) != n_coef or not 1 <= n_coef <= min(M, MEL_CEPSTRUM_MAX_COEF):
+        raise L.TtsAmdError(f'mel_cepstrum: n_coef = {n_coef!r}; 1 to min(n_mels = {M}, {MEL_CEPSTRUM_MAX_COEF}) coefficients are built')
+    lens = _dev_lens(lens, B, T, logmel.device)
+    cep = torch.empty(B, int(n_coef), T, dtype=torch.float32, device=logmel.device)
+    if B:
+        with torch.cuda.device(logmel.device):
+            L.check(lib.ttsamd_mel_cepstrum(_ptr(logmel), _ptr(lens), B, M, T, int(n_coef), _ptr(cep), _stream()), 'mel_cepstrum')
+    return cep
+
+
+def identity_path(lens_a, lens_b, ta_max, tb_max):
+    """The frame-by-frame comparison in ttsamd_dtw's layout: (path int32 [B, ta_max + tb_max, 2], path_len int32 [B]) with
+    min(lens_a[b], lens_b[b]) steps (p, p) and zeros past them (lengths clamped to the padded sizes).  torch ops on the device, no host
+    read."""
+    if not isinstance(lens_a, torch.Tensor) or lens_a.device.type != 'cuda':
+        raise L.TtsAmdError('identity_path: lens_a must be a tensor on the ROCm device')
+    la = lens_a.to(torch.int64).clamp(0, int(ta_max))
+    lb = torch.as_tensor(lens_b).to(device=la.device, dtype=torch.int64).clamp(0, int(tb_max))
+    if la.dim() != 1 or la.shape != lb.shape:
+        raise L.TtsAmdError(f'identity_path: lens of shapes {tuple(la.shape)} and {tuple(lb.shape)}')
+    n = torch.minimum(la, lb)
+    p = torch.arange(int(ta_max) + int(tb_max), dtype=torch.int64, device=la.device)[None]
+    path = torch.where(p < n[:, None], p, torch.zeros_like(p)).to(torch.int32)
+    return path[:, :, None].expand(-1, -1, 2).contiguous(), n.to(torch.int32)
+
+
+def dtw_aligned_eval(cep_a, cep_b, path, path_len, mel_a=None, mel_b=None, f0_a=None, f0_b=None, first_coef=1, scale=MCD_SCALE):
+    """cep_a [B, C, Ta], cep_b [B, C, Tb], path / path_len of dtw() (or identity_path) -> stats float64 [B, 8] in the order
+    OBJECTIVE_KEYS: along the path, scale x the mean Euclidean distance over coefficients first_coef .. C - 1 (mcd), the mean |difference|
+    of mel_a [B, M, Ta] / mel_b [B, M, Tb] (NaN without them) and, from f0_a [B, Ta] / f0_b [B, Tb] in Hz (voiced = finite and > 0; NaN
+    without them), the count of steps voiced on both sides, the RMSE in cents and in Hz and the Pearson correlation over those steps, and
+    the share of steps that differ in voicing.  One launch (ttsamd_dtw_aligned_eval); a row equals the call on its pair alone."""
+    lib = _require_gpu()
+    cep_a, cep_b = _dev_f32(cep_a, 3, 'dtw_aligned_eval: cep_a'), _dev_f32(cep_b, 3, 'dtw_aligned_eval: cep_b')
+    B, Cc, Ta = cep_a.shape
+    Tb = cep_b.shape[2]
+    if cep_b.shape[0] != B or cep_b.shape[1] != Cc:
+        raise L.TtsAmdError(f'dtw_aligned_eval: cep_a {tuple(cep_a.shape)} and cep_b {tuple(cep_b.shape)} differ in batch or coefficients')
+    if (not isinstance(path, torch.Tensor) or tuple(path.shape) != (B, Ta + Tb, 2) or path.dtype != torch.int32
+            or tuple(path_len.shape) != (B,) or path_len.dtype != torch.int32):
+        raise L.TtsAmdError(f'dtw_aligned_eval: cep_a {tuple(cep_a.shape)}, cep_b {tuple(cep_b.shape)} and the path do not belong together '
+                            f'(int32 [{B}, {Ta + Tb}, 2] and int32 [{B}] are what dtw() returns)')
+    if int(first_coef) != first_coef or not 0 <= first_coef < max(Cc, 1):
+        raise L.TtsAmdError(f'dtw_aligned_eval: first_coef = {first_coef!r} outside [0, {Cc})')
+    if (mel_a is None) != (mel_b is None) or (f0_a is None) != (f0_b is None):
+        raise L.TtsAmdError('dtw_aligned_eval: mel_a / mel_b (and f0_a / f0_b) come as a pair or not at all')
+    M = 0
+    if mel_a is not None:
+        mel_a, mel_b = _dev_f32(mel_a, 3, 'dtw_aligned_eval: mel_a'), _dev_f32(mel_b, 3, 'dtw_aligned_eval: mel_b')
+        M = mel_a.shape[1]
+        if tuple(mel_a.shape) != (B, M, Ta) or tuple(mel_b.shape) != (B, M, Tb):
+            raise L.TtsAmdError(f'dtw_aligned_eval: mel_a {tuple(mel_a.shape)} / mel_b {tuple(mel_b.shape)} for cepstra of {Ta} / {Tb} '
+                                f'frames in a batch of {B}')
+    if f0_a is not None:
+        f0_a, f0_b = _dev_f32(f0_a, 2, 'dtw_aligned_eval: f0_a'), _dev_f32(f0_b, 2, 'dtw_aligned_eval: f0_b')
+        if tuple(f0_a.shape) != (B, Ta) or tuple(f0_b.shape) != (B, Tb):
+            raise L.TtsAmdError(f'dtw_aligned_eval: f0_a {tuple(f0_a.shape)} / f0_b {tuple(f0_b.shape)} for cepstra of {Ta} / {Tb} frames '
+                                f'in a batch of {B}')
+    stats = torch.empty(B, len(OBJECTIVE_KEYS), dtype=torch.float64, device=cep_a.device)
+    if B:
+        with torch.cuda.device(cep_a.device):
+            L.check(lib.ttsamd_dtw_aligned_eval(_ptr(cep_a), _ptr(cep_b), Cc, int(first_coef), _ptr(mel_a), _ptr(mel_b), M, _ptr(f0_a),
+                                                _ptr(f0_b), B, Ta, Tb, _ptr(path.contiguous()), _ptr(path_len.contiguous()), float(scale),
+                                                _ptr(stats), _stream()), 'dtw_aligned_eval')
+    return stats
+
+
+def objective_score(mel_pred, lens_pred, mel_ref, lens_ref, f0_pred=None, f0_ref=None, n_coef=13, align='dtw', window=None):
+    """The objective scores of a batch on the device: log-mels mel_pred [B, n_mels, Tp], mel_ref [B, n_mels, Tr] (+ lens, None = full
+    rows), f0 tracks [B, Tp] / [B, Tr] in Hz or None -> {key: float64 [B] for key in OBJECTIVE_KEYS, 'path', 'path_len'[, 'dtw_cost']}.
+    align 'dtw': the two sides' cepstra 1 .. n_coef - 1 aligned by dtw() (L2; `window` = Sakoe-Chiba radius or None); 'frames': frame p
+    against frame p over the shorter side.  Four launches with 'dtw' (two cepstra, DTW, the evaluation); nothing is read back to the
+    host."""
+    mel_pred, mel_ref = _dev_f32(mel_pred, 3, 'objective_score: mel_pred'), _dev_f32(mel_ref, 3, 'objective_score: mel_ref')
+    if mel_pred.shape[:2] != mel_ref.shape[:2]:
+        raise L.TtsAmdError(f'objective_score: prediction {tuple(mel_pred.shape)} and reference {tuple(mel_ref.shape)} differ in batch '
+                            'or band count')
+    if align not in ('dtw', 'frames'):
+        raise L.TtsAmdError(f"objective_score: align {align!r} ('dtw' | 'frames')")
+    B, M, Tp = mel_pred.shape
+    Tr = mel_ref.shape[2]
+    if max(Tp, Tr) > OVERSMOOTH_MAX_FRAMES:
+        raise L.TtsAmdError(f'objective_score: {Tp} x {Tr} frames, at most {OVERSMOOTH_MAX_FRAMES} per side are built')
+    if int(n_coef) != n_coef or not 1 <= n_coef <= min(M, MEL_CEPSTRUM_MAX_COEF):
+        raise L.TtsAmdError(f'objective_score: n_coef = {n_coef!r}; 1 to min(n_mels = {M}, {MEL_CEPSTRUM_MAX_COEF}) coefficients are built')
+    if align == 'dtw' and n_coef < 2:
+        raise L.TtsAmdError("objective_score: align='dtw' aligns the coefficients 1 .. n_coef - 1 and needs n_coef >= 2")
+    lens_pred, lens_ref = _dev_lens(lens_pred, B, Tp, mel_pred.device), _dev_lens(lens_ref, B, Tr, mel_pred.device)
+    cp, cr = mel_cepstrum(mel_pred, lens_pred, n_coef), mel_cepstrum(mel_ref, lens_ref, n_coef)
+    out = {}
+    if align == 'dtw':
+        out['dtw_cost'], path, plen = dtw(cp[:, 1:], cr[:, 1:], lens_pred, lens_ref, 'l2', window)
+    else:
+        path, plen = identity_path(lens_pred, lens_ref, Tp, Tr)
+    stats = dtw_aligned_eval(cp, cr, path, plen, mel_pred, mel_ref, f0_pred, f0_ref, first_coef=min(1, n_coef - 1))
+    for k, name in enumerate(OBJECTIVE_KEYS):
+        out[name] = stats[:, k]
+    out['path'], out['path_len'] = path, plen
+    return out
+
+
+def _fit_width(x, width):
+    """[B, T] -> [B, width]: trimmed at the end or zero-padded, as FastPitch.pitch_track(mel_len=) fits a track to its mel"""
+    return torch.nn.functional.pad(x, (0, int(width) - x.shape[1]))
+
+
+class ObjectiveEngine:
+    """Wave against wave at 22 050 Hz: owns the reference's log-mel analysis (80-band slaney filterbank, 'same' framing, sqrt(|X|^2 +
+    1e-9), log(max(., 1e-5)): utils/audio.py of the reference with its safe log) and its pYIN settings (C2 .. C7, frames of 1024 every
+    256 samples: scripts/extract_f0.py), and scores with objective_score."""
+
+    def __init__(self, device='cuda'):
+        from . import melfb
+        _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        fb = melfb.mel_filterbank(22050, 1024, 80, 0, 8000.0, 'slaney', 'slaney')
+        self.melspec = MelSpecEngine(fb, 'same', 'eps', 1e-5, device=self.device)
+        c2, c7 = 440.0 * 2.0 ** ((36 - 69) / 12.0), 440.0 * 2.0 ** ((96 - 69) / 12.0)
+        self.pyin = PyinEngine(c2, c7, device=self.device, sr=22050, frame_length=1024, hop_length=256)
+
+    def features(self, wave, nsamples=None):
+        """wave [B, n] (+ nsamples int64 [B]) -> (logmel [B, 80, n // 256], frames int64 [B], f0 [B, n // 256] in Hz, 0 where unvoiced):
+        the track (1 + n // 256 frames) is fitted to the mel's width, trimmed at the end; no score reads a frame at or past `frames`."""
+        wave = _f32(wave, self.device)
+        if wave.dim() != 2:
+            raise L.TtsAmdError(f'ObjectiveEngine: wave of shape {tuple(wave.shape)}, expected [B, n]')
+        if wave.shape[1] < MelSpecEngine.MIN_SAMPLES['same']:
+            raise L.TtsAmdError(f'ObjectiveEngine: rows of {wave.shape[1]} samples; the mel analysis needs at least '
+                                f'{MelSpecEngine.MIN_SAMPLES["same"]} (reflect padding)')
+        mel, frames = self.melspec.forward(wave, nsamples)
+        f0, _, _, _ = self.pyin.forward(wave, nsamples)
+        return mel, frames, _fit_width(f0, mel.shape[2])
+
+    def score_waves(self, wave_pred, n_pred, wave_ref, n_ref, **kw):
+        """wave_pred [B, n], wave_ref [B, n'] (+ samples per row, int64 [B] or None) -> objective_score(...) of their log-mels and pYIN
+        tracks plus 'lens_pred' / 'lens_ref' (mel frames per row); **kw: n_coef, align, window.  Nothing is read back to the host."""
+        mp, lp, fp = self.features(wave_pred, n_pred)
+        mr, lr, fr = self.features(wave_ref, n_ref)
+        if mp.shape[0] != mr.shape[0]:
+            raise L.TtsAmdError(f'ObjectiveEngine.score_waves: {mp.shape[0]} predictions against {mr.shape[0]} recordings')
+        out = objective_score(mp, lp, mr, lr, fp, fr, **kw)
+        out['lens_pred'], out['lens_ref'] = lp, lr
+        return out
+
+
 # ---- FastPitch forced alignment (csrc/aligner.hip) ------------------------------------------------------------------------------------
 MAS_MAX_TOKENS = 1024                                            # TTSAMD_MAS_MAX_TOKENS of include/ttsamd.h
 ALIGNER_KEYS = ('encoder.word_emb.weight',) + tuple(

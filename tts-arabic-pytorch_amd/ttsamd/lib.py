@@ -103,6 +103,8 @@ SYMBOLS = {
     'ttsamd_dtw_workspace_bytes': (_I64, [_I32, _I32, _I32, _I32]),
     'ttsamd_dtw': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_dtw_aligned_mae': (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
+    'ttsamd_mel_cepstrum': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    'ttsamd_dtw_aligned_eval': (_I32, [_P, _P, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, C.c_double, _P, _P]),
     'ttsamd_aligner_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(AlignerCfg), C.POINTER(_P)]),
     'ttsamd_aligner_destroy': (_I32, [_P]),
     'ttsamd_aligner_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

@@ -1,0 +1,103 @@
+"""Objective evaluation of synthesised speech against a recording, on the device: mel-cepstral distortion (MCD) along a DTW path, the
+mel error along it, F0 RMSE in cents and in Hz, F0 correlation and the voiced/unvoiced error.  The reference has no such module; the
+arithmetic is this project's own, stated in DESIGN.md section 4 and include/ttsamd.h (ttsamd_mel_cepstrum, ttsamd_dtw_aligned_eval) and
+restated in float64 by tests/objective_ref.py.  Parity with a particular MCD package is not pinned: the cepstrum here is the orthonormal
+DCT-II of the natural-log mel, MCD = 10 sqrt(2) / ln 10 x the mean Euclidean distance of coefficients 1 .. n_coef - 1 along the path.
+All arithmetic runs in libttsamd.so (csrc/objective.hip, csrc/oversmooth.hip) through ttsamd.engine; there is no CPU fallback: without a
+gfx950 device every call raises ttsamd.lib.TtsAmdError.
+
+Conventions (those of utils/oversmoothing.py): numpy arrays in give numpy arrays and floats out, tensors in give tensors on the device
+out.  A batch is one more leading dimension ([B, n_mels, T] mels, [B, T] tracks) plus `lens_*` (int64 [B], None = full rows); batched
+results carry the leading dimension.  Mels are natural-log mels (log(max(mel, 1e-5)) in the reference); an f0 track is in Hz, a frame is
+voiced when its value is finite and > 0 (pyin's NaN fill and FastPitch.pitch_track(normalize=False)'s 0 both mean unvoiced).  At most
+ttsamd.engine.OVERSMOOTH_MAX_FRAMES frames per side."""
+import numpy as np
+import torch
+
+from ttsamd import engine as E
+from ttsamd.lib import TtsAmdError
+from utils.oversmoothing import _lens, _out, _prep
+
+KEYS = E.OBJECTIVE_KEYS
+MCD_SCALE = E.MCD_SCALE
+_F0_KEYS = ('n', 'n_vv', 'f0_rmse_cents', 'f0_rmse_hz', 'f0_corr', 'vuv_error')
+_engines = {}
+
+
+def _pair(a, b, nd, what):
+    """two inputs of the same kind -> (device tensors with a batch dimension, both came as numpy, came batched)"""
+    x, np_x, batched = _prep(a, nd, f'{what}: prediction')
+    y, np_y, batched_y = _prep(b, nd, f'{what}: reference')
+    if batched != batched_y or x.shape[0] != y.shape[0]:
+        raise TtsAmdError(f'{what}: prediction {tuple(x.shape)} and reference {tuple(y.shape)} differ in batch')
+    return x, y.to(x.device), np_x and np_y, batched
+
+
+def _scores(score, keys, was_np, batched):
+    return {k: _out(score[k], was_np, batched) for k in keys}
+
+
+def mel_cepstrum(logmel, n_coef=13, lens=None):
+    """logmel [n_mels, T] -> [n_coef, T]: the orthonormal DCT-II across the bands of every frame
+    (scipy.fft.dct(logmel, type=2, norm='ortho', axis=0)[:n_coef]), float64 inside, rounded once to float32."""
+    m, was_np, batched = _prep(logmel, 2, 'mel_cepstrum')
+    return _out(E.mel_cepstrum(m, _lens(lens, m, batched), n_coef), was_np, batched)
+
+
+def objective_metrics(mel_pred, mel_ref, f0_pred=None, f0_ref=None, n_coef=13, align='dtw', window=None, lens_pred=None, lens_ref=None):
+    """{n, mcd, mel_mae, n_vv, f0_rmse_cents, f0_rmse_hz, f0_corr, vuv_error} of a predicted log-mel [n_mels, Tp] against a reference
+    [n_mels, Tr], with their f0 tracks [Tp] / [Tr] in Hz if given (NaN in the f0 scores otherwise).  align 'dtw': along the DTW path of
+    the cepstra 1 .. n_coef - 1 (L2; `window` = Sakoe-Chiba radius or None); 'frames': frame by frame over the shorter side."""
+    p, r, was_np, batched = _pair(mel_pred, mel_ref, 2, 'objective_metrics')
+    if (f0_pred is None) != (f0_ref is None):
+        raise TtsAmdError('objective_metrics: f0_pred and f0_ref come as a pair or not at all')
+    fp = fr = None
+    if f0_pred is not None:
+        fp, fr, _, fb = _pair(f0_pred, f0_ref, 1, 'objective_metrics: f0')
+        if fb != batched or fp.shape != (p.shape[0], p.shape[2]) or fr.shape != (r.shape[0], r.shape[2]):
+            raise TtsAmdError(f'objective_metrics: f0 tracks {tuple(fp.shape)} / {tuple(fr.shape)} do not match the mels '
+                              f'{tuple(p.shape)} / {tuple(r.shape)} frame for frame')
+    score = E.objective_score(p, _lens(lens_pred, p, batched), r, _lens(lens_ref, r, batched), fp, fr, n_coef=n_coef, align=align,
+                              window=window)
+    return _scores(score, KEYS, was_np, batched)
+
+
+def mel_cepstral_distortion(mel_pred, mel_ref, n_coef=13, align='dtw', window=None, lens_pred=None, lens_ref=None):
+    """MCD in dB between two log-mels [n_mels, T]: 10 sqrt(2) / ln 10 x the mean over the path of the Euclidean distance between the
+    cepstral coefficients 1 .. n_coef - 1 (c0, the level, is left out)."""
+    return objective_metrics(mel_pred, mel_ref, None, None, n_coef, align, window, lens_pred, lens_ref)['mcd']
+
+
+def f0_metrics(f0_pred, f0_ref, path=None, path_len=None, lens_pred=None, lens_ref=None):
+    """{n, n_vv, f0_rmse_cents, f0_rmse_hz, f0_corr, vuv_error} of two f0 tracks [T] in Hz.  path None: frame by frame over the shorter
+    side; else the (i, j) steps to compare, [L, 2] for one pair (as dtw_align_mels returns them), or [B, Tp + Tr, 2] with path_len [B]
+    for a batch (as ttsamd.engine.dtw does)."""
+    a, b, was_np, batched = _pair(f0_pred, f0_ref, 1, 'f0_metrics')
+    B, Ta = a.shape
+    Tb = b.shape[1]
+    if path is None:
+        path, path_len = E.identity_path(_lens(lens_pred, a, batched), _lens(lens_ref, b, batched), Ta, Tb)
+    else:
+        path = torch.as_tensor(np.asarray(path) if not isinstance(path, torch.Tensor) else path).to(device=a.device, dtype=torch.int32)
+        if not batched:
+            if path.dim() != 2 or path.shape[1] != 2 or path.shape[0] > Ta + Tb:
+                raise TtsAmdError(f'f0_metrics: path of shape {tuple(path.shape)} for tracks of {Ta} and {Tb} frames ([L, 2] is expected)')
+            path_len = torch.full((1,), path.shape[0], dtype=torch.int32, device=a.device)
+            path = torch.nn.functional.pad(path, (0, 0, 0, Ta + Tb - path.shape[0]))[None]
+        elif path_len is None:
+            raise TtsAmdError('f0_metrics: a batched path goes with path_len')
+        path_len = torch.as_tensor(path_len).to(device=a.device, dtype=torch.int32)
+    zero = torch.zeros(B, 1, 1, dtype=torch.float32, device=a.device)
+    stats = E.dtw_aligned_eval(zero.expand(B, 1, Ta), zero.expand(B, 1, Tb), path.contiguous(), path_len, f0_a=a, f0_b=b, first_coef=0)
+    return {k: _out(stats[:, KEYS.index(k)], was_np, batched) for k in _F0_KEYS}
+
+
+def evaluate_waves(wave_pred, wave_ref, n_coef=13, align='dtw', window=None, lens_pred=None, lens_ref=None):
+    """The eight scores of a synthesised wave [n] against a recording [n'], both at 22 050 Hz: the reference's log-mel analysis and pYIN
+    settings on both (ttsamd.engine.ObjectiveEngine), then objective_metrics.  `lens_*`: samples per row of a batch."""
+    x, y, was_np, batched = _pair(wave_pred, wave_ref, 1, 'evaluate_waves')
+    if str(x.device) not in _engines:
+        _engines[str(x.device)] = E.ObjectiveEngine(device=x.device)
+    score = _engines[str(x.device)].score_waves(x, _lens(lens_pred, x, batched), y, _lens(lens_ref, y, batched), n_coef=n_coef, align=align,
+                                                window=window)
+    return _scores(score, KEYS, was_np, batched)
