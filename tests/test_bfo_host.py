@@ -16,14 +16,23 @@ def _bf16(x):
     return ((u >> 16) & 0xffff).astype(np.uint16)
 
 
-def _pack(w, up):
+def _split(x):
+    """hi = bf16(w), lo = bf16(w - hi), the difference taken in fp32 (csrc/bfo3.hpp)."""
+    x = np.ascontiguousarray(x, np.float32)
+    hi = _bf16(x)
+    lo = _bf16(x - (hi.astype(np.uint32) << 16).view(np.float32))
+    return hi, lo
+
+
+def _pack(w, up, prefix='bfo'):
     from ttsamd import lib as L
     lib = L.load()
     w = np.ascontiguousarray(w, np.float32)
     cin, cout, k = (w.shape if up > 1 else (w.shape[1], w.shape[0], w.shape[2]))
-    n = lib.ttsamd_bfo_weight_elems(cout, cin, k, up)
+    n = getattr(lib, f'ttsamd_{prefix}_weight_elems')(cout, cin, k, up)
     out = np.zeros(n, np.uint16)
-    L.check(lib.ttsamd_bfo_pack_weight(w.ctypes.data_as(C.c_void_p), cout, cin, k, up, out.ctypes.data_as(C.c_void_p)), 'pack')
+    L.check(getattr(lib, f'ttsamd_{prefix}_pack_weight')(w.ctypes.data_as(C.c_void_p), cout, cin, k, up,
+                                                        out.ctypes.data_as(C.c_void_p)), 'pack')
     return out
 
 
@@ -75,6 +84,49 @@ def test_conv_transpose_weight_layout():
         for q in range(n):
             y = wt[:, :, ka].T @ xp[:, q + dl + 1] + wt[:, :, ka + u].T @ xp[:, q + dl]
             assert torch.allclose(y, ref[:, q * u + rho])
+
+
+def test_conv_weight_layout_x3():
+    """Split-bf16 twin, [Cin/16][K][2 (kk)][CoutP][2 (hi, lo)][8] (csrc/bfo3.hpp): twice the plain element count, hi = bf16(w),
+    lo = bf16(w - hi), zero in the Cin / Cout padding.  Exact."""
+    rng = np.random.default_rng(0)
+    for cout, cin, k in ((64, 32, 3), (40, 80, 7), (128, 24, 1)):
+        w = rng.standard_normal((cout, cin, k)).astype(np.float32)
+        got = _pack(w, 1, 'bfo3')
+        cp, nh = (cout + 31) // 32 * 32, (cin + 15) // 16
+        assert got.size == 2 * _pack(w, 1).size == nh * k * 2 * cp * 2 * 8
+        got = got.reshape(nh, k, 2, cp, 2, 8)
+        want = np.zeros((nh, k, 2, cp, 2, 8), np.uint16)
+        for h in range(nh):
+            for kk in range(2):
+                for e in range(8):
+                    ci = 16 * h + 8 * kk + e
+                    if ci < cin:
+                        for plane, wb in enumerate(_split(w)):
+                            want[h, :, kk, :cout, plane, e] = wb[:, ci, :].T
+        assert np.array_equal(got, want)
+        assert want[..., 1, :].any()                       # the lo plane carries something
+
+
+def test_conv_transpose_weight_layout_x3():
+    """Split-bf16 twin of the polyphase layout: [u][Cin/16][2 (t2)][2 (kk)][CoutP][2 (hi, lo)][8], same phase -> kernel index map."""
+    rng = np.random.default_rng(1)
+    for cin, cout, u in ((32, 64, 2), (48, 32, 8)):
+        w = rng.standard_normal((cin, cout, 2 * u)).astype(np.float32)
+        cp = (cout + 31) // 32 * 32
+        got = _pack(w, u, 'bfo3')
+        assert got.size == 2 * _pack(w, u).size
+        got = got.reshape(u, cin // 16, 2, 2, cp, 2, 8)
+        want = np.zeros_like(got)
+        for rho in range(u):
+            ka = (rho + u // 2) % u
+            for t2 in range(2):
+                for h in range(cin // 16):
+                    for kk in range(2):
+                        for e in range(8):
+                            for plane, wb in enumerate(_split(w)):
+                                want[rho, h, t2, kk, :cout, plane, e] = wb[16 * h + 8 * kk + e, :, ka + t2 * u]
+        assert np.array_equal(got, want)
 
 
 def test_bf16_roofline_byte_counts():

@@ -14,6 +14,8 @@
 // Weights: [Cin/16][K][2 (kk)][CoutP][8 bf16] = the A operand per lane (row co, k = 16h + 8kk + e), streamed from L2
 // straight into registers (each wave reads only its own 32-row slab; no LDS ring, no barriers inside a conv).
 #pragma once
+#include <vector>
+
 #include "common.hpp"
 
 namespace ttsamd {
@@ -115,12 +117,53 @@ int32_t bfo_launch_unpack(const void* in, int32_t B, int32_t C, int32_t L, float
 // HiFi-GAN tail on an octet tensor activated with slope 0.01: wave = tanh(conv7(a) + b)   (models.py:123-125)
 int32_t bfo_launch_conv_post(const void* x, const float* w, const float* bias, const int64_t* lens, int32_t len_mul, int32_t B,
                              int32_t C, int32_t L, float* wave, int64_t wave_bs, hipStream_t s);
-// host: torch Conv1d weight [Cout][Cin][K] -> [Cin/16][K][2][CoutP][8] bf16 (Cin zero-padded to a multiple of 16)
-int64_t bfo_packed_conv_elems(int cout, int cin, int k);
-void bfo_pack_conv_weight(const float* w, int cout, int cin, int k, uint16_t* out);
-// host: torch ConvTranspose1d weight [Cin][Cout][2u] (stride u, padding u/2) -> u polyphase 2-tap filters in that layout
-int64_t bfo_packed_convt_elems(int cin, int cout, int u);
-void bfo_pack_convt_weight(const float* w, int cin, int cout, int u, uint16_t* out);
+// host weight packers, both modes (bfo_conv.hip).  `planes` = 1: every weight as bf16(w) (RNE); 2: as hi 8 | lo 8 bf16 side by side,
+// hi = bf16(w), lo = bf16(w - hi) (bfo3.hpp).  Element counts are in uint16.
+// torch Conv1d weight [Cout][Cin][K] -> [Cin/16][K][2][CoutP][planes][8] (Cin zero-padded to a multiple of 16)
+int64_t bfo_packed_conv_elems(int cout, int cin, int k, int planes);
+void bfo_pack_conv_weight(const float* w, int cout, int cin, int k, int planes, uint16_t* out);
+// torch ConvTranspose1d weight [Cin][Cout][2u] (stride u, padding u/2) -> u polyphase 2-tap filters in that layout
+int64_t bfo_packed_convt_elems(int cin, int cout, int u, int planes);
+void bfo_pack_convt_weight(const float* w, int cin, int cout, int u, int planes, uint16_t* out);
+
+// The engine's two modes as the host code sees them: plain bf16 (precision 1, bfo_*) and split bf16 (precision 2, bfo3_*, bfo3.hpp).
+// The kernels differ; everything that drives them (the C ABI in bfo_api.hip, hifigan.hip, fastpitch.hip) is written once against this table.
+struct BfoMode {
+    const char* prefix;        // "bfo" / "bfo3": error messages and the launch log
+    int32_t entry_bytes;       // per (octet, position) of an activation tensor: 16 / 32
+    int32_t (*pack)(const float* x, int32_t B, int32_t C, int32_t L, float slope, void* out, hipStream_t s);
+    int32_t (*unpack)(const void* in, int32_t B, int32_t C, int32_t L, float slope, float* out, hipStream_t s);
+    int32_t (*conv)(const BfoConvParams& p, hipStream_t s);
+    int32_t (*convt)(const BfoConvParams& p, hipStream_t s);
+    int32_t (*pair)(int32_t channels, int32_t k, const BfoPairParams& p, hipStream_t s);
+    bool (*pair_supported)(int32_t channels, int32_t k, int32_t dil, int32_t L);
+    int32_t (*chain)(int32_t channels, const BfoChainParams& p, hipStream_t s);
+    // does this ResBlock go out as one chained launch: what the kernel supports + the routing switches
+    bool (*chain_wanted)(int32_t channels, int32_t k, const int32_t* dil, int32_t n_pairs, int32_t L, int32_t batch);
+    int32_t (*conv_post)(const void* x, const float* w, const float* bias, const int64_t* lens, int32_t len_mul, int32_t B, int32_t C,
+                         int32_t L, float* wave, int64_t wave_bs, hipStream_t s);
+    // LayerNorm over the channels of a channel-first fp32 tensor + its copy in the mode's layout (launch_layernorm_cf_octet / _x3)
+    int32_t (*layernorm_cf)(const float* x, float* y, void* y_copy, const float* gamma, const float* beta, const int64_t* lens,
+                            int32_t apply_mask, int32_t B, int32_t C, int32_t S, hipStream_t s, float eps);
+
+    int index() const { return entry_bytes / 16 - 1; }         // 0 / 1: BfoWeightOffs
+    int planes() const { return entry_bytes / 16; }
+    int64_t conv_elems(int cout, int cin, int k) const { return bfo_packed_conv_elems(cout, cin, k, planes()); }
+    int64_t convt_elems(int cin, int cout, int u) const { return bfo_packed_convt_elems(cin, cout, u, planes()); }
+    void pack_conv_weight(const float* w, int cout, int cin, int k, uint16_t* out) const { bfo_pack_conv_weight(w, cout, cin, k, planes(), out); }
+    void pack_convt_weight(const float* w, int cin, int cout, int u, uint16_t* out) const { bfo_pack_convt_weight(w, cin, cout, u, planes(), out); }
+};
+const BfoMode& bfo_mode(int precision);       // 1 or 2 (bfo_api.hip)
+
+// Where one conv's packed weights sit in a model's uint16 blob, per mode (-1: not packed for the engine)
+struct BfoWeightOffs {
+    int64_t off[2] = {-1, -1};
+    bool packed() const { return off[0] >= 0; }
+    int64_t of(const BfoMode& m) const { return off[m.index()]; }
+};
+// appends the conv's (up = 1: w = [Cout][Cin][K]) or transposed conv's (up = u > 1: w = [Cin][Cout][2u]) weights for both modes to
+// `blob16`, each 64-element aligned
+BfoWeightOffs bfo_append_weights(const float* w, int cout, int cin, int k, int up, std::vector<uint16_t>& blob16);
 
 #ifdef __HIPCC__
 __device__ bfo_i4 bfo_ld16(bfo_i4 rsrc, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.buffer.load.v4i32");

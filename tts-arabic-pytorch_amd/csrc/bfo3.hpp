@@ -37,12 +37,7 @@ int32_t launch_layernorm_cf_x3(const float* x, float* y, void* y_x3, const float
 // HiFi-GAN tail on an x3 tensor activated with slope 0.01: wave = tanh(conv7(a) + b)   (models.py:123-125)
 int32_t bfo3_launch_conv_post(const void* x, const float* w, const float* bias, const int64_t* lens, int32_t len_mul, int32_t B,
                               int32_t C, int32_t L, float* wave, int64_t wave_bs, hipStream_t s);
-// host: torch Conv1d weight [Cout][Cin][K] -> [Cin/16][K][2][CoutP][hi 8 | lo 8] bf16 (uint16 elements)
-int64_t bfo3_packed_conv_elems(int cout, int cin, int k);
-void bfo3_pack_conv_weight(const float* w, int cout, int cin, int k, uint16_t* out);
-// host: torch ConvTranspose1d weight [Cin][Cout][2u] (stride u, padding u/2) -> u polyphase 2-tap filters in that layout
-int64_t bfo3_packed_convt_elems(int cin, int cout, int u);
-void bfo3_pack_convt_weight(const float* w, int cin, int cout, int u, uint16_t* out);
+// (weights: bfo_pack_conv_weight / bfo_pack_convt_weight of bfo.hpp with planes = 2)
 
 #ifdef __HIPCC__
 // 16-byte store of a freshly computed half entry.  MEASURED on gfx950 (tools/scratch history, tests/test_gpu_bfo3.py): a

@@ -4,7 +4,7 @@
 //   bfo3_convt    ConvTranspose1d(stride u, kernel 2u, padding u/2) as u polyphase 2-tap convs over ONE staged window
 //   bfo3_pack / bfo3_unpack   fp32 channel-first <-> x3 tensor
 //   bfo3_conv_post            leaky_relu(0.01) -> Conv1d(C -> 1, k7) -> tanh on an x3 tensor
-// and the host-side weight packers.  Reference ops: vocoder/hifigan/models.py:46-53 (ResBlock1), :96-99,114-115
+// (weight packers: bfo_conv.hip, both modes).  Reference ops: vocoder/hifigan/models.py:46-53 (ResBlock1), :96-99,114-115
 // (upsamplers), :112 (conv_pre), :123-125 (conv_post); models/fastpitch/fastpitch/transformer.py:72-90.
 #include <cstdlib>
 #include <cstring>
@@ -515,70 +515,6 @@ int32_t bfo3_launch_conv_post(const void* x, const float* w, const float* bias, 
     hipLaunchKernelGGL(bfo3_conv_post_kernel<4>, grid, dim3(256), 0, s, (const uint4*)x, w, bias, lens, len_mul, L, wave, wave_bs);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
-}
-
-// =====================================================================================================================
-// host-side weight packers: w = hi + lo, hi = bf16(w) (RNE), lo = bf16(w - hi)
-// =====================================================================================================================
-static inline uint16_t bfo3_host_bf16(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline void bfo3_host_split(float f, uint16_t& hi, uint16_t& lo) {
-    hi = bfo3_host_bf16(f);
-    const uint32_t hu = (uint32_t)hi << 16;
-    float hf;
-    std::memcpy(&hf, &hu, 4);
-    lo = bfo3_host_bf16(f - hf);
-}
-
-int64_t bfo3_packed_conv_elems(int cout, int cin, int k) {
-    return (int64_t)((cin + 15) / 16) * k * 2 * ((cout + 31) & ~31) * 16;
-}
-
-// out[((((h K + t) 2 + kk) CoutP + co) 2 + plane) 8 + e] = plane(w[co][16 h + 8 kk + e][t])
-void bfo3_pack_conv_weight(const float* w, int cout, int cin, int k, uint16_t* out) {
-    const int cp = (cout + 31) & ~31, nh = (cin + 15) / 16;
-    for (int h = 0; h < nh; ++h)
-        for (int t = 0; t < k; ++t)
-            for (int kk = 0; kk < 2; ++kk) {
-                uint16_t* dst = out + (((int64_t)h * k + t) * 2 + kk) * cp * 16;
-                for (int co = 0; co < cp; ++co)
-                    for (int e = 0; e < 8; ++e) {
-                        const int ci = 16 * h + 8 * kk + e;
-                        uint16_t hi = 0, lo = 0;
-                        if (co < cout && ci < cin) bfo3_host_split(w[((int64_t)co * cin + ci) * k + t], hi, lo);
-                        dst[co * 16 + e] = hi;
-                        dst[co * 16 + 8 + e] = lo;
-                    }
-            }
-}
-
-int64_t bfo3_packed_convt_elems(int cin, int cout, int u) {
-    return (int64_t)u * (cin / 16) * 2 * 2 * ((cout + 31) & ~31) * 16;
-}
-
-// torch ConvTranspose1d weight [Cin][Cout][2u]: phase rho, tap t2 -> kernel index (rho + u/2) % u + t2 u
-void bfo3_pack_convt_weight(const float* w, int cin, int cout, int u, uint16_t* out) {
-    const int cp = (cout + 31) & ~31, nh = cin / 16, kt = 2 * u, pd = u / 2;
-    for (int rho = 0; rho < u; ++rho) {
-        const int ka = (rho + pd) % u;
-        for (int h = 0; h < nh; ++h)
-            for (int t2 = 0; t2 < 2; ++t2)
-                for (int kk = 0; kk < 2; ++kk) {
-                    uint16_t* dst = out + ((((int64_t)rho * nh + h) * 2 + t2) * 2 + kk) * cp * 16;
-                    for (int co = 0; co < cp; ++co)
-                        for (int e = 0; e < 8; ++e) {
-                            const int ci = 16 * h + 8 * kk + e;
-                            uint16_t hi = 0, lo = 0;
-                            if (co < cout) bfo3_host_split(w[((int64_t)ci * cout + co) * kt + ka + t2 * u], hi, lo);
-                            dst[co * 16 + e] = hi;
-                            dst[co * 16 + 8 + e] = lo;
-                        }
-                }
-    }
 }
 
 }  // namespace ttsamd

@@ -621,7 +621,8 @@ int32_t bfo_launch_conv_post(const void* x, const float* w, const float* bias, c
 }
 
 // =====================================================================================================================
-// host-side weight packers
+// host-side weight packers, both modes: `planes` = 1 writes bf16(w), 2 writes hi 8 | lo 8 with w = hi + lo, hi = bf16(w) (RNE),
+// lo = bf16(w - hi)
 // =====================================================================================================================
 static inline uint16_t bfo_host_bf16(float f) {
     uint32_t u;
@@ -629,46 +630,75 @@ static inline uint16_t bfo_host_bf16(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
-
-int64_t bfo_packed_conv_elems(int cout, int cin, int k) {
-    return (int64_t)((cin + 15) / 16) * k * 2 * ((cout + 31) & ~31) * 8;
+// dst[0] (and, planes = 2, dst[8]) of one lane's entry
+static inline void bfo_host_put(float f, int planes, uint16_t* dst) {
+    const uint16_t hi = bfo_host_bf16(f);
+    dst[0] = hi;
+    if (planes == 2) {
+        const uint32_t hu = (uint32_t)hi << 16;
+        float hf;
+        std::memcpy(&hf, &hu, 4);
+        dst[8] = bfo_host_bf16(f - hf);
+    }
 }
 
-// out[(((h K + t) 2 + kk) CoutP + co) 8 + e] = w[co][16 h + 8 kk + e][t]
-void bfo_pack_conv_weight(const float* w, int cout, int cin, int k, uint16_t* out) {
-    const int cp = (cout + 31) & ~31, nh = (cin + 15) / 16;
+int64_t bfo_packed_conv_elems(int cout, int cin, int k, int planes) {
+    return (int64_t)((cin + 15) / 16) * k * 2 * ((cout + 31) & ~31) * 8 * planes;
+}
+
+// out[((((h K + t) 2 + kk) CoutP + co) planes + plane) 8 + e] = plane(w[co][16 h + 8 kk + e][t])
+void bfo_pack_conv_weight(const float* w, int cout, int cin, int k, int planes, uint16_t* out) {
+    const int cp = (cout + 31) & ~31, nh = (cin + 15) / 16, es = 8 * planes;
+    std::memset(out, 0, (size_t)bfo_packed_conv_elems(cout, cin, k, planes) * sizeof(uint16_t));
     for (int h = 0; h < nh; ++h)
         for (int t = 0; t < k; ++t)
             for (int kk = 0; kk < 2; ++kk) {
-                uint16_t* dst = out + (((int64_t)h * k + t) * 2 + kk) * cp * 8;
-                for (int co = 0; co < cp; ++co)
+                uint16_t* dst = out + (((int64_t)h * k + t) * 2 + kk) * cp * es;
+                for (int co = 0; co < cout; ++co)
                     for (int e = 0; e < 8; ++e) {
                         const int ci = 16 * h + 8 * kk + e;
-                        dst[co * 8 + e] = (co < cout && ci < cin) ? bfo_host_bf16(w[((int64_t)co * cin + ci) * k + t]) : 0;
+                        if (ci < cin) bfo_host_put(w[((int64_t)co * cin + ci) * k + t], planes, dst + co * es + e);
                     }
             }
 }
 
-int64_t bfo_packed_convt_elems(int cin, int cout, int u) {
-    return (int64_t)u * (cin / 16) * 2 * 2 * ((cout + 31) & ~31) * 8;
+int64_t bfo_packed_convt_elems(int cin, int cout, int u, int planes) {
+    return (int64_t)u * (cin / 16) * 2 * 2 * ((cout + 31) & ~31) * 8 * planes;
 }
 
 // torch ConvTranspose1d weight [Cin][Cout][2u]: phase rho, tap t2 -> kernel index (rho + u/2) % u + t2 u
-void bfo_pack_convt_weight(const float* w, int cin, int cout, int u, uint16_t* out) {
-    const int cp = (cout + 31) & ~31, nh = cin / 16, kt = 2 * u, pd = u / 2;
+void bfo_pack_convt_weight(const float* w, int cin, int cout, int u, int planes, uint16_t* out) {
+    const int cp = (cout + 31) & ~31, nh = cin / 16, kt = 2 * u, pd = u / 2, es = 8 * planes;
+    std::memset(out, 0, (size_t)bfo_packed_convt_elems(cin, cout, u, planes) * sizeof(uint16_t));
     for (int rho = 0; rho < u; ++rho) {
         const int ka = (rho + pd) % u;
         for (int h = 0; h < nh; ++h)
             for (int t2 = 0; t2 < 2; ++t2)
                 for (int kk = 0; kk < 2; ++kk) {
-                    uint16_t* dst = out + ((((int64_t)rho * nh + h) * 2 + t2) * 2 + kk) * cp * 8;
-                    for (int co = 0; co < cp; ++co)
+                    uint16_t* dst = out + ((((int64_t)rho * nh + h) * 2 + t2) * 2 + kk) * cp * es;
+                    for (int co = 0; co < cout; ++co)
                         for (int e = 0; e < 8; ++e) {
                             const int ci = 16 * h + 8 * kk + e;
-                            dst[co * 8 + e] = co < cout ? bfo_host_bf16(w[((int64_t)ci * cout + co) * kt + ka + t2 * u]) : 0;
+                            bfo_host_put(w[((int64_t)ci * cout + co) * kt + ka + t2 * u], planes, dst + co * es + e);
                         }
                 }
     }
+}
+
+BfoWeightOffs bfo_append_weights(const float* w, int cout, int cin, int k, int up, std::vector<uint16_t>& blob16) {
+    BfoWeightOffs o;
+    for (int planes = 1; planes <= 2; ++planes) {
+        blob16.resize(align_up((int64_t)blob16.size(), 64));
+        o.off[planes - 1] = (int64_t)blob16.size();
+        if (up > 1) {
+            blob16.resize(blob16.size() + (size_t)bfo_packed_convt_elems(cin, cout, up, planes));
+            bfo_pack_convt_weight(w, cin, cout, up, planes, blob16.data() + o.off[planes - 1]);
+        } else {
+            blob16.resize(blob16.size() + (size_t)bfo_packed_conv_elems(cout, cin, k, planes));
+            bfo_pack_conv_weight(w, cout, cin, k, planes, blob16.data() + o.off[planes - 1]);
+        }
+    }
+    return o;
 }
 
 }  // namespace ttsamd

@@ -19,8 +19,7 @@ namespace ttsamd {
 
 struct PConv {
     int64_t w_off = 0, b_off = -1, w16_off = 0;
-    int64_t wo_off = -1;   // bf16 octet engine weights [Cin/16][K][2][CoutP][8] in the uint16 blob (the conv-FF convs; -1: not packed)
-    int64_t wo3_off = -1;  // ... and their split-bf16 twin [Cin/16][K][2][CoutP][hi 8 | lo 8] (bfo3.hpp)
+    BfoWeightOffs wo;      // bf16 octet engine weights in the uint16 blob, per mode: [Cin/16][K][2][CoutP][8] / [..][hi 8 | lo 8] (the conv-FF convs)
     int64_t ww4_off = -1;  // ... and as Winograd F(4,3) groups (conv_wino4.hip)
     int64_t ww_off = -1;   // k = 3: Winograd F(2,3) filters as a 4-tap conv in the fp32 blob (conv_wino.hip; -1: none)
     int cin = 0, cout = 0, k = 0;
@@ -121,14 +120,7 @@ struct Builder {
         }
         if (octet && cin % 8 == 0 && cout % 32 == 0 && cout >= 128 && (k == 1 || k == 3 || k == 7 || k == 11)) {
             // the conv-FF pair also runs on the bf16 octet engine (config 3): v_mfma_f32_32x32x16_bf16, bf16 intermediate
-            blob16.resize(align_up((int64_t)blob16.size(), 64));
-            c.wo_off = (int64_t)blob16.size();
-            blob16.resize(blob16.size() + (size_t)bfo_packed_conv_elems(cout, cin, k));
-            bfo_pack_conv_weight(w->data, cout, cin, k, blob16.data() + c.wo_off);
-            blob16.resize(align_up((int64_t)blob16.size(), 64));
-            c.wo3_off = (int64_t)blob16.size();
-            blob16.resize(blob16.size() + (size_t)bfo3_packed_conv_elems(cout, cin, k));
-            bfo3_pack_conv_weight(w->data, cout, cin, k, blob16.data() + c.wo3_off);
+            c.wo = bfo_append_weights(w->data, cout, cin, k, 1, blob16);
         }
         blob.resize(align_up((int64_t)blob.size(), 64));
         if (bias) c.b_off = raw(base + ".bias", cout);
@@ -301,6 +293,26 @@ static int32_t run_conv(const FastPitch* h, const PConv& c, const float* x, floa
     return rc;
 }
 
+// What every FastPitch conv on the octet engine (either mode) starts from: stride 1, "same" padding, whole rows, no running sum.  The
+// caller adds what its path has and the other does not (lengths, split-K workspace, LayerNorm epilogue): a field one mode leaves zero
+// stays zero.
+static BfoConvParams octet_conv_params(const FastPitch* h, const BfoMode& M, const PConv& c, const void* in, void* out_o, float* out_f,
+                                       const float* res_f, float out_slope, int B, int S) {
+    BfoConvParams cp;
+    std::memset(&cp, 0, sizeof(cp));
+    cp.batch = B; cp.len_mul = 1; cp.Lin = S; cp.dil = 1; cp.up = 1; cp.div = 1.f; cp.res_slope = 1.f;
+    cp.x = in; cp.y = out_o; cp.y_f32 = out_f; cp.res_f32 = res_f;
+    cp.w = h->dev16 + c.wo.of(M); cp.bias = c.b_off >= 0 ? h->dev + c.b_off : nullptr;
+    cp.Cin = c.cin; cp.Cout = c.cout; cp.K = c.k; cp.out_slope = out_slope;
+    return cp;
+}
+static int32_t octet_conv(const BfoMode& M, const PConv& c, const BfoConvParams& cp, hipStream_t s) {
+    prof_begin(s, 2.0 * c.cout * c.cin * c.k);
+    const int32_t rc = M.conv(cp, s);
+    prof_end(s);
+    return rc;
+}
+
 // transformer.py:172-177 x n_layers.  x is updated in place.
 static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, int d_head, float* x,
                        const int64_t* lens, int B, int S, const FftWs& w, hipStream_t s) {
@@ -311,8 +323,9 @@ static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, 
     const bool ff_on = opt_int(OPT_BFO_FF, 1) != 0;     // read per call: the tests and A/B runs flip it
     bool octet = default_precision() == 1 && ff_on && d % 64 == 0 && d <= 512 && d_head == 64;
     for (const FftLayer& l : layers)
-        octet = octet && l.ff0.wo_off >= 0 && l.ff2.wo_off >= 0 && l.qkv.wo_off >= 0 && l.o_net.wo_off >= 0 && l.qkv.cout == 3 * d_head;
+        octet = octet && l.ff0.wo.packed() && l.ff2.wo.packed() && l.qkv.wo.packed() && l.o_net.wo.packed() && l.qkv.cout == 3 * d_head;
     if (octet) {
+        const BfoMode& M = bfo_mode(1);
         // ---- config 3: the whole FFT block on the bf16 matrix cores.  The residual stream x / y stays fp32 channel-first (LayerNorm
         // statistics, residual adds); every GEMM reads a bf16 octet copy of its input (bfo.hpp) that its producer writes alongside:
         //   xo (LayerNorm 2 / the initial pack) -> qkv conv -> fp32 q|k|v -> bf16 MFMA attention -> ao (octet)
@@ -327,22 +340,14 @@ static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, 
         void* ao = (char*)yo + (int64_t)B * d * S * 2;
         TTS_REQUIRE((int64_t)2 * (di + 2 * d + d_head) <= (int64_t)4 * di, "fastpitch: octet buffers do not fit the hidden buffer");
         TTS_TRY(bfo_launch_pack(x, B, d, S, 1.f, xo, s));
-        BfoConvParams cp;
         // ln_g != nullptr: LayerNorm (masked with `lens`) over the fp32 result in place + its octet copy `ln_o` (BfoConvParams::ln_*)
         auto conv = [&](const PConv& c, const void* in, void* out_o, float* out_f, const float* res_f, float out_slope,
                         const float* ln_g = nullptr, const float* ln_b = nullptr, void* ln_o = nullptr) -> int32_t {
-            std::memset(&cp, 0, sizeof(cp));
+            BfoConvParams cp = octet_conv_params(h, M, c, in, out_o, out_f, res_f, out_slope, B, S);
             cp.ln_g = ln_g; cp.ln_b = ln_b; cp.ln_octet = ln_o; cp.ln_lens = ln_g ? lens : nullptr;
-            cp.batch = B; cp.len_mul = 1; cp.Lin = S; cp.dil = 1; cp.up = 1; cp.div = 1.f; cp.res_slope = 1.f;
-            cp.x = in; cp.y = out_o; cp.y_f32 = out_f; cp.res_f32 = res_f;
             if (alone && &c == ff2_of) { cp.lens = lens; cp.out_all = 1; }      // batch mode 1: the hidden activation masked on load
-            cp.w = h->dev16 + c.wo_off; cp.bias = c.b_off >= 0 ? h->dev + c.b_off : nullptr;
-            cp.Cin = c.cin; cp.Cout = c.cout; cp.K = c.k; cp.out_slope = out_slope;
             cp.splitk_ws = t_splitk_ws; cp.splitk_floats = t_splitk_ws ? kSplitKFloatsFp : 0;
-            prof_begin(s, 2.0 * c.cout * c.cin * c.k);
-            const int32_t rc = bfo_launch_conv(cp, s);
-            prof_end(s);
-            return rc;
+            return octet_conv(M, c, cp, s);
         };
         for (const FftLayer& l : layers) {
             ff2_of = &l.ff2;
@@ -356,8 +361,9 @@ static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, 
     }
     bool x3 = default_precision() == 2 && !t_small_f32 && ff_on && (d == 384 || d == 256 || d == 512) && d_head % 8 == 0 && w.o3;
     for (const FftLayer& l : layers)
-        x3 = x3 && l.ff0.wo3_off >= 0 && l.ff2.wo3_off >= 0 && l.qkv.wo3_off >= 0 && l.o_net.wo3_off >= 0 && l.qkv.cout == 3 * d_head;
+        x3 = x3 && l.ff0.wo.packed() && l.ff2.wo.packed() && l.qkv.wo.packed() && l.o_net.wo.packed() && l.qkv.cout == 3 * d_head;
     if (x3) {
+        const BfoMode& M = bfo_mode(2);
         // ---- split bf16: the block above with every GEMM operand = hi + lo (bfo3.hpp).  The residual stream stays fp32 channel-first;
         // each GEMM reads an x3 copy of its input written by its producer (LayerNorm, the ReLU conv, or a pack of the attention output):
         //   xo -> qkv conv -> fp32 q|k|v -> exact fp32 attention -> a -> pack -> ao -> o_net conv + x -> y -> LayerNorm 1 -> y, yo
@@ -370,21 +376,13 @@ static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, 
         void* ao = (char*)yo + (int64_t)B * d * S * 4;
         void* hid_o = w.hid;
         TTS_TRY(bfo3_launch_pack(x, B, d, S, 1.f, xo, s));
-        BfoConvParams cp;
         auto conv = [&](const PConv& c, const void* in, void* out_o, float* out_f, const float* res_f, float out_slope) -> int32_t {
-            std::memset(&cp, 0, sizeof(cp));
-            cp.batch = B; cp.len_mul = 1; cp.Lin = S; cp.dil = 1; cp.up = 1; cp.div = 1.f; cp.res_slope = 1.f;
-            cp.x = in; cp.y = out_o; cp.y_f32 = out_f; cp.res_f32 = res_f;
+            BfoConvParams cp = octet_conv_params(h, M, c, in, out_o, out_f, res_f, out_slope, B, S);
             // ragged conv-FF as on the fp32 path below (one length per launch here -- it masks the input and bounds the output): hid on
             // [0, len], the second conv reads it masked past that and writes x on [0, len] (frame len: finite, zeroed by LayerNorm 2)
             if (w.ragged && (&c == ff2_of || &c == ff0_of)) cp.lens = (alone && &c == ff2_of) ? lens : w.lens1;
             else if (alone && &c == ff2_of) { cp.lens = lens; cp.out_all = 1; }
-            cp.w = h->dev16 + c.wo3_off; cp.bias = c.b_off >= 0 ? h->dev + c.b_off : nullptr;
-            cp.Cin = c.cin; cp.Cout = c.cout; cp.K = c.k; cp.out_slope = out_slope;
-            prof_begin(s, 2.0 * c.cout * c.cin * c.k);
-            const int32_t rc = bfo3_launch_conv(cp, s);
-            prof_end(s);
-            return rc;
+            return octet_conv(M, c, cp, s);
         };
         for (const FftLayer& l : layers) {
             ff2_of = &l.ff2; ff0_of = &l.ff0;
@@ -428,64 +426,36 @@ static int32_t run_predictor(const FastPitch* h, const Predictor& pr, const floa
                              float add, hipStream_t s, void* px3 = nullptr, const int64_t* lens1 = nullptr) {
     const float* src = x;
     float* bufs[2] = {t0, t1};
-    {
-        // config 3: Conv1d + ReLU -> LayerNorm chain on the bf16 octet engine (input packed once, masked on load; LayerNorm writes the
-        // next conv's octet copy).  The octet tensors sit behind the fp32 buffers' used part: t0 / t1 are sized for the widest filter.
-        bool octet = default_precision() == 1 && opt_int(OPT_BFO_FF, 1) != 0 && pr.convs.size() == 2 && pr.filter % 64 == 0 && pr.filter <= 512 &&
-                     pr.convs[0].cin % 8 == 0 && pr.convs[0].cin <= pr.filter * 2;
-        for (const PConv& c : pr.convs) octet = octet && c.wo_off >= 0;
+    const int prec = default_precision();
+    if ((prec == 1 || prec == 2) && opt_int(OPT_BFO_FF, 1) != 0 && pr.convs.size() == 2 && pr.convs[0].cin % 8 == 0 && pr.convs[0].cin <= pr.filter * 2) {
+        // config 3: Conv1d + ReLU -> LayerNorm chain on the bf16 octet engine, either mode (input packed once, masked on load; LayerNorm
+        // writes the next conv's copy).  What differs between the modes:
+        //   plain bf16: the octet tensors sit in t1 ([B][filter][S] fp32, sized for the widest filter), one after the other -- the packed
+        //     input ([B][cin/8][S][8] bf16, cin <= 2 filter), then, once the first conv has consumed it, the copy of the first LayerNorm's
+        //     output; the second conv's result goes to t0 (the fp32 LayerNorm output there is dead); split K for small batches
+        //   split bf16: the x3 tensors are as large as the fp32 ones (the packed input would not fit t1), so both go to `px3` and the
+        //     second conv writes t1; filter = 256 / 384 / 512 (the x3 LayerNorm), never under SmallBatchScope, no split K
+        const bool x3 = prec == 2;
+        const BfoMode& M = bfo_mode(prec);
+        bool octet = x3 ? (pr.filter == 256 || pr.filter == 384 || pr.filter == 512) && px3 != nullptr && !t_small_f32
+                        : pr.filter % 64 == 0 && pr.filter <= 512;
+        for (const PConv& c : pr.convs) octet = octet && c.wo.packed();
         if (octet) {
-            // t1 ([B][filter][S] fp32) holds the octet tensors one after the other: the packed input ([B][cin/8][S][8] bf16, cin <= 2 filter),
-            // then -- once the first conv has consumed it -- the octet copy of the first LayerNorm's output
-            void* xo = t1;
-            BfoConvParams cp;
+            void* xo = x3 ? px3 : (void*)t1;
+            float* y1 = x3 ? t1 : t0;
             auto conv = [&](const PConv& c, const void* in, float* out_f, const int64_t* lens_in) -> int32_t {
-                std::memset(&cp, 0, sizeof(cp));
-                cp.batch = B; cp.len_mul = 1; cp.Lin = S; cp.dil = 1; cp.up = 1; cp.div = 1.f; cp.res_slope = 1.f;
-                cp.x = in; cp.y_f32 = out_f; cp.lens = lens_in; cp.out_all = 1;
-                cp.w = h->dev16 + c.wo_off; cp.bias = c.b_off >= 0 ? h->dev + c.b_off : nullptr;
-                cp.Cin = c.cin; cp.Cout = c.cout; cp.K = c.k; cp.out_slope = 0.f;                      // ReLU
-                cp.splitk_ws = t_splitk_ws; cp.splitk_floats = t_splitk_ws ? kSplitKFloatsFp : 0;
-                prof_begin(s, 2.0 * c.cout * c.cin * c.k);
-                const int32_t rc = bfo_launch_conv(cp, s);
-                prof_end(s);
-                return rc;
+                BfoConvParams cp = octet_conv_params(h, M, c, in, nullptr, out_f, nullptr, 0.f, B, S);     // out_slope 0: ReLU
+                cp.lens = lens_in; cp.out_all = 1;
+                if (!x3) { cp.splitk_ws = t_splitk_ws; cp.splitk_floats = t_splitk_ws ? kSplitKFloatsFp : 0; }
+                return octet_conv(M, c, cp, s);
             };
-            TTS_TRY(bfo_launch_pack(x, B, pr.convs[0].cin, S, 1.f, xo, s));
+            TTS_TRY(M.pack(x, B, pr.convs[0].cin, S, 1.f, xo, s));
             TTS_TRY(conv(pr.convs[0], xo, t0, lens));
-            // LayerNorm of layer 0 in place (fp32, t0) + its octet copy into t1 (the packed input there is dead now)
-            TTS_TRY(launch_layernorm_cf_octet(t0, t0, t1, h->dev + pr.ln_g[0], h->dev + pr.ln_b[0], nullptr, 0, B, pr.filter, S, s));
-            // the second conv reads the octet copy; the fp32 LayerNorm output in t0 is dead, so its result goes there
-            TTS_TRY(conv(pr.convs[1], t1, t0, h->alone.load(std::memory_order_relaxed) ? lens : lens1));
-            TTS_TRY(launch_layernorm_cf(t0, t0, h->dev + pr.ln_g[1], h->dev + pr.ln_b[1], nullptr, 0, B, pr.filter, S, s));
-            return launch_pred_fc(t0, h->dev + pr.fc_w, h->dev + pr.fc_b, lens, B, pr.filter, S, out, out2, max_dur, mul, add, s);
-        }
-    }
-    {
-        // split bf16: the same chain on the x3 kernels.  The x3 tensors are as large as the fp32 ones: the packed input ([B][cin][S] x 4
-        // bytes, cin <= 2 filter would not fit) and the copy of the first LayerNorm's output both go to `px3`
-        bool x3 = default_precision() == 2 && !t_small_f32 && opt_int(OPT_BFO_FF, 1) != 0 && pr.convs.size() == 2 && (pr.filter == 256 || pr.filter == 384 || pr.filter == 512) &&
-                  pr.convs[0].cin % 8 == 0 && pr.convs[0].cin <= pr.filter * 2 && px3 != nullptr;
-        for (const PConv& c : pr.convs) x3 = x3 && c.wo3_off >= 0;
-        if (x3) {
-            BfoConvParams cp;
-            auto conv = [&](const PConv& c, const void* in, float* out_f, const int64_t* lens_in) -> int32_t {
-                std::memset(&cp, 0, sizeof(cp));
-                cp.batch = B; cp.len_mul = 1; cp.Lin = S; cp.dil = 1; cp.up = 1; cp.div = 1.f; cp.res_slope = 1.f;
-                cp.x = in; cp.y_f32 = out_f; cp.lens = lens_in; cp.out_all = 1;
-                cp.w = h->dev16 + c.wo3_off; cp.bias = c.b_off >= 0 ? h->dev + c.b_off : nullptr;
-                cp.Cin = c.cin; cp.Cout = c.cout; cp.K = c.k; cp.out_slope = 0.f;                      // ReLU
-                prof_begin(s, 2.0 * c.cout * c.cin * c.k);
-                const int32_t rc = bfo3_launch_conv(cp, s);
-                prof_end(s);
-                return rc;
-            };
-            TTS_TRY(bfo3_launch_pack(x, B, pr.convs[0].cin, S, 1.f, px3, s));
-            TTS_TRY(conv(pr.convs[0], px3, t0, lens));
-            TTS_TRY(launch_layernorm_cf_x3(t0, t0, px3, h->dev + pr.ln_g[0], h->dev + pr.ln_b[0], nullptr, 0, B, pr.filter, S, s));
-            TTS_TRY(conv(pr.convs[1], px3, t1, h->alone.load(std::memory_order_relaxed) ? lens : lens1));
-            TTS_TRY(launch_layernorm_cf(t1, t1, h->dev + pr.ln_g[1], h->dev + pr.ln_b[1], nullptr, 0, B, pr.filter, S, s));
-            return launch_pred_fc(t1, h->dev + pr.fc_w, h->dev + pr.fc_b, lens, B, pr.filter, S, out, out2, max_dur, mul, add, s);
+            // LayerNorm of layer 0 in place (fp32, t0) + its copy over the packed input, which is dead now
+            TTS_TRY(M.layernorm_cf(t0, t0, xo, h->dev + pr.ln_g[0], h->dev + pr.ln_b[0], nullptr, 0, B, pr.filter, S, s, 1e-5f));
+            TTS_TRY(conv(pr.convs[1], xo, y1, h->alone.load(std::memory_order_relaxed) ? lens : lens1));
+            TTS_TRY(launch_layernorm_cf(y1, y1, h->dev + pr.ln_g[1], h->dev + pr.ln_b[1], nullptr, 0, B, pr.filter, S, s));
+            return launch_pred_fc(y1, h->dev + pr.fc_w, h->dev + pr.fc_b, lens, B, pr.filter, S, out, out2, max_dur, mul, add, s);
         }
     }
     for (size_t i = 0; i < pr.convs.size(); ++i) {

@@ -12,7 +12,7 @@
 #include <vector>
 
 #include "kernels.hpp"
-#include "bfo3.hpp"
+#include "bfo.hpp"
 
 namespace ttsamd {
 
@@ -51,8 +51,7 @@ static bool resblock2_pair_choice(unsigned mask, int32_t channels, int32_t k, in
 struct ConvW {
     int64_t w_off = 0, b_off = 0;  // float offsets into the device weight blob
     int64_t w16_off = 0, w_n = 0;  // bf16 planes (hi, lo) in the uint16 blob; packed element count
-    int64_t wo_off = -1;           // bf16 octet engine (bfo.hpp): [Cin/16][K][2][CoutP][8] in the same uint16 blob (-1: not packed)
-    int64_t wo3_off = -1;          // its split-bf16 mode (bfo3.hpp): [Cin/16][K][2][CoutP][hi 8 | lo 8]
+    BfoWeightOffs wo;              // bf16 octet engine (bfo.hpp), per mode: [Cin/16][K][2][CoutP][8] / [..][hi 8 | lo 8] in the same uint16 blob
     int64_t ww4_off = -1;          // ... and as Winograd F(4,3) groups (conv_wino4.hip: the un-fused convs, Cout >= 64; resblock_pair4.hip: the C = 32 pairs)
     int64_t ww_off = -1;           // k = 3 / 7 / 11: Winograd F(2,3) (sub-)filters + single taps as an NG-tap conv in the fp32 blob (conv_wino2.hip; -1: none)
     int cin = 0, cout = 0, k = 0;
@@ -242,16 +241,7 @@ static int32_t add_conv(const TensorMap& tm, const std::string& base, int cin, i
             pack_wino4_weight(w.data(), cout, cin, k, blob.data() + cw.ww4_off);
         }
     }
-    if (cin % 8 == 0 && cout % 32 == 0) {
-        blob16.resize(align_up((int64_t)blob16.size(), 64));
-        cw.wo_off = (int64_t)blob16.size();
-        blob16.resize(blob16.size() + (size_t)bfo_packed_conv_elems(cout, cin, k));
-        bfo_pack_conv_weight(w.data(), cout, cin, k, blob16.data() + cw.wo_off);
-        blob16.resize(align_up((int64_t)blob16.size(), 64));
-        cw.wo3_off = (int64_t)blob16.size();
-        blob16.resize(blob16.size() + (size_t)bfo3_packed_conv_elems(cout, cin, k));
-        bfo3_pack_conv_weight(w.data(), cout, cin, k, blob16.data() + cw.wo3_off);
-    }
+    if (cin % 8 == 0 && cout % 32 == 0) cw.wo = bfo_append_weights(w.data(), cout, cin, k, 1, blob16);
     blob.resize(align_up((int64_t)blob.size(), 64));
     return get_bias(tm, base, cout, blob, cw.b_off);
 }
@@ -304,16 +294,7 @@ int32_t hifigan_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_hif
         blob.resize(blob.size() + (size_t)u * cin * 2 * cout_padded(cout));
         pack_convt_weight(w.data(), cin, cout, kt, u, (kt - u) / 2, blob.data() + cw.w_off);
         add_bf16(blob, blob16, cw, (int64_t)u * cin * 2 * cout_padded(cout));
-        if (cin % 16 == 0 && cout % 32 == 0 && (u == 8 || u == 2)) {
-            blob16.resize(align_up((int64_t)blob16.size(), 64));
-            cw.wo_off = (int64_t)blob16.size();
-            blob16.resize(blob16.size() + (size_t)bfo_packed_convt_elems(cin, cout, u));
-            bfo_pack_convt_weight(w.data(), cin, cout, u, blob16.data() + cw.wo_off);
-            blob16.resize(align_up((int64_t)blob16.size(), 64));
-            cw.wo3_off = (int64_t)blob16.size();
-            blob16.resize(blob16.size() + (size_t)bfo3_packed_convt_elems(cin, cout, u));
-            bfo3_pack_convt_weight(w.data(), cin, cout, u, blob16.data() + cw.wo3_off);
-        }
+        if (cin % 16 == 0 && cout % 32 == 0 && (u == 8 || u == 2)) cw.wo = bfo_append_weights(w.data(), cout, cin, kt, u, blob16);
         blob.resize(align_up((int64_t)blob.size(), 64));
         rc = get_bias(tm, "ups." + std::to_string(i), cout, blob, cw.b_off);
         if (rc) break;
@@ -352,9 +333,9 @@ int32_t hifigan_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_hif
     h->hop = mul;
     if (rc == 0 && !h->rb2) {
         // the bf16 octet engine covers this generator if every layer was packed for it
-        bool ok = h->conv_pre.wo_off >= 0 && ch == 32 && cfg->num_mels % 8 == 0;
-        for (const ConvW& cw : h->ups) ok = ok && cw.wo_off >= 0;
-        for (size_t i = 0; i < h->c1.size(); ++i) ok = ok && h->c1[i].wo_off >= 0 && h->c2[i].wo_off >= 0;
+        bool ok = h->conv_pre.wo.packed() && ch == 32 && cfg->num_mels % 8 == 0;
+        for (const ConvW& cw : h->ups) ok = ok && cw.wo.packed();
+        for (size_t i = 0; i < h->c1.size(); ++i) ok = ok && h->c1[i].wo.packed() && h->c2[i].wo.packed();
         for (int j = 0; j < cfg->n_kernels; ++j) {
             const int kk = cfg->resblock_kernel_sizes[j];
             ok = ok && (kk == 3 || kk == 7 || kk == 11);
@@ -532,25 +513,19 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
     // fused c1 -> c2 pairs for C <= 128.  TTSAMD_BFO=0 keeps the round-2 bf16 engine (fp32 activations in HBM).
     const int prec = default_precision();
     if ((prec == 1 || prec == 2) && h->bfo_ok && opt_int(OPT_BFO, 1) != 0) {
-        const bool x3 = prec == 2;
+        const BfoMode& M = bfo_mode(prec);
         const uint16_t* W16 = h->dev16;
-        const auto woff = [x3](const ConvW& cw) { return x3 ? cw.wo3_off : cw.wo_off; };
-        const auto l_conv = x3 ? bfo3_launch_conv : bfo_launch_conv;
-        const auto l_convt = x3 ? bfo3_launch_convt : bfo_launch_convt;
-        const auto l_pair = x3 ? bfo3_launch_pair : bfo_launch_pair;
-        const auto pair_ok = x3 ? bfo3_pair_supported : bfo_pair_supported;
-        const bool chain3_on = opt_int(OPT_BFO_CHAIN, 1) != 0;   // 0: three pair launches per k = 3 ResBlock (bit-identical; A/B and parity runs)
         void *curo = cur, *upso = ups_out;                 // the fp32-sized buffers hold bf16 / x3 tensors of the same element count
-        HG_TRY((x3 ? bfo3_launch_pack : bfo_launch_pack)(mel, B, cfg.num_mels, T, 1.f, mel_o, s));
+        HG_TRY(M.pack(mel, B, cfg.num_mels, T, 1.f, mel_o, s));
         BfoConvParams cp;
         std::memset(&cp, 0, sizeof(cp));
         cp.batch = B; cp.lens = lens; cp.div = 1.f; cp.res_slope = 1.f;
         // conv_pre (models.py:112); its consumer, the first upsampler, applies leaky_relu(0.1) (models.py:114)
-        cp.x = mel_o; cp.y = curo; cp.w = W16 + woff(h->conv_pre); cp.bias = h->dev + h->conv_pre.b_off;
+        cp.x = mel_o; cp.y = curo; cp.w = W16 + h->conv_pre.wo.of(M); cp.bias = h->dev + h->conv_pre.b_off;
         cp.len_mul = 1; cp.Lin = T; cp.Cin = h->conv_pre.cin; cp.Cout = h->conv_pre.cout; cp.K = 7; cp.dil = 1; cp.up = 1;
         cp.mode = 0; cp.out_slope = 0.1f;
         prof_begin(s, 2.0 * cp.Cout * cp.Cin * 7);
-        int32_t rc = l_conv(cp, s);
+        int32_t rc = M.conv(cp, s);
         prof_end(s);
         HG_TRY(rc);
         int L = T, mul = 1;
@@ -558,11 +533,11 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
             const int u = cfg.upsample_rates[i];
             const ConvW& uw = h->ups[i];
             // ConvTranspose1d on the activated stage input; the ResBlocks read its output through leaky_relu(0.1)
-            cp.x = curo; cp.y = upso; cp.w = W16 + woff(uw); cp.bias = h->dev + uw.b_off; cp.res = nullptr; cp.sum_in = nullptr;
+            cp.x = curo; cp.y = upso; cp.w = W16 + uw.wo.of(M); cp.bias = h->dev + uw.b_off; cp.res = nullptr; cp.sum_in = nullptr;
             cp.len_mul = mul; cp.Lin = L; cp.Cin = uw.cin; cp.Cout = uw.cout; cp.K = 2; cp.dil = 1; cp.up = u;
             cp.mode = 0; cp.out_slope = 0.1f;
             prof_begin(s, 2.0 * uw.cout * uw.cin * 2 * u * mul);
-            rc = l_convt(cp, s);
+            rc = M.convt(cp, s);
             prof_end(s);
             HG_TRY(rc);
             L *= u; mul *= u;
@@ -583,14 +558,14 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                     const int li0 = (i * cfg.n_kernels + j) * cfg.n_dilations;
                     int32_t dl[3] = {0, 0, 0};
                     for (int m = 0; m < cfg.n_dilations && m < 3; ++m) dl[m] = cfg.resblock_dilations[j][m];
-                    const bool chain3 = x3 && chain3_on && bfo3_chain_supported(h->c1[li0].cin, h->c1[li0].k, dl, cfg.n_dilations, L);
-                    if (chain3 || (!x3 && bfo_chain_wanted(h->c1[li0].cin, h->c1[li0].k, dl, cfg.n_dilations, L, B))) {
+                    // (TTSAMD_BFO_CHAIN=0: three pair launches per ResBlock; bit-identical, A/B and parity runs)
+                    if (M.chain_wanted(h->c1[li0].cin, h->c1[li0].k, dl, cfg.n_dilations, L, B)) {
                         BfoChainParams cc;
                         std::memset(&cc, 0, sizeof(cc));
                         cc.x = src; cc.y = curo; cc.sum_in = curo;
                         for (int m = 0; m < 3; ++m) {
                             const ConvW &w1 = h->c1[li0 + m], &w2 = h->c2[li0 + m];
-                            cc.w1[m] = W16 + woff(w1); cc.w2[m] = W16 + woff(w2); cc.b1[m] = h->dev + w1.b_off; cc.b2[m] = h->dev + w2.b_off;
+                            cc.w1[m] = W16 + w1.wo.of(M); cc.w2[m] = W16 + w2.wo.of(M); cc.b1[m] = h->dev + w1.b_off; cc.b2[m] = h->dev + w2.b_off;
                             cc.dil[m] = dl[m];
                         }
                         cc.lens = lens; cc.len_mul = mul; cc.L = L; cc.batch = B; cc.k = h->c1[li0].k;
@@ -600,7 +575,7 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                         if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
                         const double fl = 3 * 2.0 * (2.0 * h->c1[li0].cin * h->c1[li0].cin * h->c1[li0].k) * mul;
                         if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        rc = x3 ? bfo3_launch_chain(h->c1[li0].cin, cc, st) : bfo_launch_chain(h->c1[li0].cin, cc, st);
+                        rc = M.chain(h->c1[li0].cin, cc, st);
                         if (!in_section) prof_end(st);
                         HG_TRY(rc);
                         if (multi) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
@@ -618,15 +593,15 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                     const float out_slope = !last ? 0.1f : (j + 1 == cfg.n_kernels ? next_slope : 1.f);
                     if (multi && last && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
                     const double fl = 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * mul;
-                    if (pair_ok(w1.cin, w1.k, d, L)) {
+                    if (M.pair_supported(w1.cin, w1.k, d, L)) {
                         BfoPairParams pp;
                         std::memset(&pp, 0, sizeof(pp));
                         pp.x = src; pp.y = dst; pp.sum_in = curo;
-                        pp.w1 = W16 + woff(w1); pp.w2 = W16 + woff(w2); pp.b1 = h->dev + w1.b_off; pp.b2 = h->dev + w2.b_off;
+                        pp.w1 = W16 + w1.wo.of(M); pp.w2 = W16 + w2.wo.of(M); pp.b1 = h->dev + w1.b_off; pp.b2 = h->dev + w2.b_off;
                         pp.lens = lens; pp.len_mul = mul; pp.L = L; pp.dil = d; pp.batch = B;
                         pp.mode = mode; pp.div = (float)cfg.n_kernels; pp.in_slope = 0.1f; pp.mid_slope = 0.1f; pp.out_slope = out_slope;
                         if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        rc = l_pair(w1.cin, w1.k, pp, st);
+                        rc = M.pair(w1.cin, w1.k, pp, st);
                         if (!in_section) prof_end(st);
                         HG_TRY(rc);
                     } else {
@@ -634,16 +609,16 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                         // residual only at its own output positions, so it may run in place (dst == src == R)
                         void* t1 = Tb;
                         if (!last) dst = R;
-                        cp.x = src; cp.y = t1; cp.w = W16 + woff(w1); cp.bias = h->dev + w1.b_off; cp.res = nullptr; cp.sum_in = nullptr;
+                        cp.x = src; cp.y = t1; cp.w = W16 + w1.wo.of(M); cp.bias = h->dev + w1.b_off; cp.res = nullptr; cp.sum_in = nullptr;
                         cp.len_mul = mul; cp.Lin = L; cp.Cin = w1.cin; cp.Cout = w1.cout; cp.K = w1.k; cp.dil = d; cp.up = 1;
                         cp.mode = 0; cp.out_slope = 0.1f; cp.res_slope = 1.f;
                         cp.splitk_ws = splitks[j % 3]; cp.splitk_floats = kSplitKFloats;     // batch 1: 30 blocks per stage-1 conv
                         if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        rc = l_conv(cp, st);
+                        rc = M.conv(cp, st);
                         if (rc == 0) {
-                            cp.x = t1; cp.y = dst; cp.w = W16 + woff(w2); cp.bias = h->dev + w2.b_off; cp.res = src; cp.sum_in = curo;
+                            cp.x = t1; cp.y = dst; cp.w = W16 + w2.wo.of(M); cp.bias = h->dev + w2.b_off; cp.res = src; cp.sum_in = curo;
                             cp.dil = 1; cp.mode = mode; cp.div = (float)cfg.n_kernels; cp.out_slope = out_slope; cp.res_slope = 0.1f;
-                            rc = l_conv(cp, st);
+                            rc = M.conv(cp, st);
                         }
                         if (!in_section) prof_end(st);
                         HG_TRY(rc);
@@ -658,8 +633,7 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                 prof_section_end(s);
             }
         }
-        HG_TRY((x3 ? bfo3_launch_conv_post : bfo_launch_conv_post)(curo, h->dev + h->conv_post.w_off, h->dev + h->conv_post.b_off, lens, mul, B, h->conv_post.cin,
-                                    L, wave, (int64_t)L, s));
+        HG_TRY(M.conv_post(curo, h->dev + h->conv_post.w_off, h->dev + h->conv_post.b_off, lens, mul, B, h->conv_post.cin, L, wave, (int64_t)L, s));
         return 0;
     }
 

@@ -143,22 +143,6 @@ SYMBOLS = {
     'ttsamd_resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
     'ttsamd_resblock2_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_resblock2': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
-    'ttsamd_bfo_pack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
-    'ttsamd_bfo_unpack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
-    'ttsamd_bfo_weight_elems': (_I64, [_I32, _I32, _I32, _I32]),
-    'ttsamd_bfo_pack_weight': (_I32, [_P, _I32, _I32, _I32, _I32, _P]),
-    'ttsamd_bfo_conv1d': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _P, _P, _P, _P]),
-    'ttsamd_bfo_resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
-    'ttsamd_bfo_resblock_chain': (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P, _I32]),
-    'ttsamd_bfo_conv_post': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
-    'ttsamd_bfo3_pack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
-    'ttsamd_bfo3_unpack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
-    'ttsamd_bfo3_weight_elems': (_I64, [_I32, _I32, _I32, _I32]),
-    'ttsamd_bfo3_pack_weight': (_I32, [_P, _I32, _I32, _I32, _I32, _P]),
-    'ttsamd_bfo3_conv1d': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _P, _P, _P, _P]),
-    'ttsamd_bfo3_resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
-    'ttsamd_bfo3_resblock_chain': (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
-    'ttsamd_bfo3_conv_post': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     'ttsamd_set_precision': (_I32, [_I32]),
     'ttsamd_get_precision': (_I32, []),
     'ttsamd_dp_unique_id': (_I32, [_P]),
@@ -174,6 +158,21 @@ SYMBOLS = {
     'ttsamd_profile_enable': (_I32, [_I32]),
     'ttsamd_profile_read': (_I32, [C.POINTER(C.c_double)]),
 }
+# the bf16 octet engine's kernel-level entries, the same eight for both modes: ttsamd_bfo_* (plain bf16) and ttsamd_bfo3_* (split bf16)
+_BFO = {
+    'pack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
+    'unpack': (_I32, [_P, _I32, _I32, _I32, _F, _P, _P]),
+    'weight_elems': (_I64, [_I32, _I32, _I32, _I32]),
+    'pack_weight': (_I32, [_P, _I32, _I32, _I32, _I32, _P]),
+    'conv1d': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _P, _P, _P, _P]),
+    'resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P]),
+    'resblock_chain': (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P, _I32]),   # last: k
+    'conv_post': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P]),
+}
+for _prefix in ('bfo', 'bfo3'):
+    for _name, (_res, _args) in _BFO.items():
+        # the x3 chain entry takes no kernel size (k = 3)
+        SYMBOLS[f'ttsamd_{_prefix}_{_name}'] = (_res, _args[:-1] if (_prefix, _name) == ('bfo3', 'resblock_chain') else _args)
 
 _lib = None
 ABI_VERSION = 8            # == TTSAMD_ABI_VERSION of include/ttsamd.h (struct layouts and argument meanings of this binding)
