@@ -198,8 +198,36 @@ int32_t ttsamd_fastpitch_decode(void* handle, float* x, const int64_t* dec_lens,
  *      models/fastpitch/fastpitch/transformer.py:72-90, model.py:129-133) -- what tts(list, batch_size > 1) returns.
  *   1  every utterance as if it were alone in the call: those two convs read their input masked at the utterance's own length (every
  *      other op already masks), so row b equals FastPitch.infer(ids[b:b+1, :len_b]) -- the reference's batch_size = 1 loop
- *      (models/fastpitch/networks.py:402-411) as ONE ragged call.  Equal to the one-by-one calls within fp32 summation order. */
+ *      (models/fastpitch/networks.py:402-411) as ONE ragged call.  Equal to the one-by-one calls within fp32 summation order.
+ *      pitch_pred is 0 past a row's end in this mode -- a lone row's padding is zero -- where mode 0 holds pitch_add there, as the
+ *      reference's padded batch does (the transform is applied to the masked prediction); the k = 3 pitch embedding reads that
+ *      position at the row's last token. */
 int32_t ttsamd_fastpitch_set_batch_mode(void* handle, int32_t mode);
+
+/* ---- Mixed requests in one batch.  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.  The two calls above with
+ *      per-row controls and a per-call batch mode; workspaces are those of ttsamd_fastpitch_encode_workspace_bytes /
+ *      ttsamd_fastpitch_decode_workspace_bytes for the same batch and width.
+ *   speaker_rows int32 [B], pace_rows / pitch_mul_rows / pitch_add_rows float [B]: DEVICE arrays, each may be NULL, in which case the
+ *      scalar argument of the same name applies to every row (and is checked as the scalar entry checks it).  Row b is computed by the
+ *      kernels of the scalar entries with row b's values in the scalars' place, the same expressions in the same order: its bits equal
+ *      those of ttsamd_fastpitch_encode on the same ids with row b's values as scalars.
+ *      Device values are trusted as `ids` are -- memory-safe, not reported: a speaker outside [0, n_speakers) is clamped into the table, a
+ *      pace that is not > 0 is taken as 1.  Range errors are for the caller that has the values on the host (ttsamd/engine.py raises).
+ *   flags: bit 0 = every row as if it were alone in the call (mode 1 above) for THIS call; the handle's mode is neither read nor written,
+ *      so callers that share a handle cannot mix arithmetic.  Pass the same flags to both phases of a call.  Any other bit: TTSAMD_EINVAL. */
+int32_t ttsamd_fastpitch_encode_rows(void* handle, const int64_t* ids, int32_t batch, int32_t n_tokens,
+                                     int32_t speaker, float pace, const float* dur_tgt,
+                                     const float* pitch_tgt, const float* energy_tgt,
+                                     float pitch_mul, float pitch_add, float max_duration,
+                                     float* enc_cond, float* dur_pred, float* pitch_pred,
+                                     float* energy_pred, int64_t* reps, int64_t* dec_lens,
+                                     void* workspace, int64_t workspace_bytes,
+                                     const int32_t* speaker_rows, const float* pace_rows,
+                                     const float* pitch_mul_rows, const float* pitch_add_rows,
+                                     int32_t flags, void* stream);
+int32_t ttsamd_fastpitch_decode_rows(void* handle, float* x, const int64_t* dec_lens, int32_t batch,
+                                     int32_t t_max, float* mel, void* workspace,
+                                     int64_t workspace_bytes, int32_t flags, void* stream);
 
 /* ---- HiFi-GAN bias denoiser: replaces vocoder.hifigan.denoiser.Denoiser
  *      (vocoder/hifigan/denoiser.py:32-64 __init__, :66-72 forward).  STFT/ISTFT with
@@ -217,6 +245,12 @@ int32_t ttsamd_denoiser_bias_spec(void* handle, const float* audio, const int64_
 int32_t ttsamd_denoise(void* handle, float* wave, int64_t wave_stride, const int64_t* nsamples,
                        int32_t batch, int32_t n_max, const float* bias_spec, float strength,
                        void* workspace, int64_t workspace_bytes, void* stream);
+/* The same with one strength per row (new symbol, no ABI bump): strength_rows float [B] on the device, not NULL.  A row whose strength
+ * is > 0 gets the bits of ttsamd_denoise on the same batch with that scalar; any other row is left UNTOUCHED bit for bit (an STFT ->
+ * ISTFT round trip is no identity in bits; the wrappers skip the call for denoise <= 0). */
+int32_t ttsamd_denoise_rows(void* handle, float* wave, int64_t wave_stride, const int64_t* nsamples,
+                            int32_t batch, int32_t n_max, const float* bias_spec, const float* strength_rows,
+                            void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- MelVocos('22k' / '24k') vocoder: replaces vocoder.vocos.pretrained.MelVocos
  *      (vocoder/vocos/pretrained.py:34-93; backbone models.py:26-89, ConvNeXtBlock modules.py:8-60,
@@ -235,6 +269,11 @@ int32_t ttsamd_vocos_bias_vec(void* handle, float* bias_vec, void* workspace, in
 int32_t ttsamd_vocos_forward(void* handle, const float* mel, const int64_t* lens, int32_t batch,
                              int32_t t_max, float denoise, const float* bias_vec, float* wave,
                              void* workspace, int64_t workspace_bytes, void* stream);
+/* The same with one denoise strength per row (new symbol, no ABI bump): denoise_rows float [B] on the device, not NULL; bias_vec is
+ * needed.  Row b gets the bits of ttsamd_vocos_forward on the same batch with denoise_rows[b] as the scalar (0: no subtraction). */
+int32_t ttsamd_vocos_forward_rows(void* handle, const float* mel, const int64_t* lens, int32_t batch,
+                                  int32_t t_max, const float* denoise_rows, const float* bias_vec, float* wave,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- Added after ABI revision 8 WITHOUT a bump: ttsamd_vocos_set_padding and the ttsamd_melspec_* entries below are new symbols only;
  *      no existing signature, struct or argument meaning changed, so TTSAMD_ABI_VERSION stays 8.  A library built before them lacks the

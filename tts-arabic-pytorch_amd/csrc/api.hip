@@ -84,7 +84,7 @@ void vocos_destroy(Vocos*);
 int64_t vocos_workspace_bytes(const Vocos*, int32_t, int32_t);
 int64_t vocos_bias_workspace_bytes(const Vocos*);
 int32_t vocos_bias_vec(const Vocos*, float*, void*, int64_t, hipStream_t);
-int32_t vocos_forward(const Vocos*, const float*, const int64_t*, int32_t, int32_t, float, const float*, float*, void*,
+int32_t vocos_forward(const Vocos*, const float*, const int64_t*, int32_t, int32_t, float, const float*, const float*, float*, void*,
                       int64_t, hipStream_t);
 int32_t vocos_set_padding(Vocos*, int32_t);
 struct MelSpec;
@@ -134,7 +134,7 @@ int32_t denoiser_create(Denoiser**);
 void denoiser_destroy(Denoiser*);
 int64_t denoiser_workspace_bytes(int32_t, int32_t);
 int32_t denoiser_bias_spec(const Denoiser*, const float*, const int64_t*, int32_t, float*, void*, int64_t, hipStream_t);
-int32_t denoise(const Denoiser*, float*, int64_t, const int64_t*, int32_t, int32_t, const float*, float, void*, int64_t,
+int32_t denoise(const Denoiser*, float*, int64_t, const int64_t*, int32_t, int32_t, const float*, float, const float*, void*, int64_t,
                 hipStream_t);
 int32_t hifigan_create(const ttsamd_tensor*, int32_t, const ttsamd_hifigan_cfg*, HifiGan**);
 void hifigan_destroy(HifiGan*);
@@ -151,6 +151,11 @@ int32_t fastpitch_encode(const FastPitch*, const int64_t*, int32_t, int32_t, int
 void fastpitch_set_batch_mode(const FastPitch*, int);
 int32_t fastpitch_decode(const FastPitch*, float*, const int64_t*, int32_t, int32_t, float*, void*, int64_t,
                          hipStream_t);
+int32_t fastpitch_encode_rows(const FastPitch*, const int64_t*, int32_t, int32_t, int32_t, float, const float*,
+                              const float*, const float*, float, float, float, float*, float*, float*, float*, int64_t*,
+                              int64_t*, void*, int64_t, const int32_t*, const float*, const float*, const float*, int32_t, hipStream_t);
+int32_t fastpitch_decode_rows(const FastPitch*, float*, const int64_t*, int32_t, int32_t, float*, void*, int64_t, int32_t,
+                              hipStream_t);
 
 __global__ void pack_conv_weight_kernel(const float* __restrict__ w, int cout, int cin, int k, int cp,
                                         float* __restrict__ out) {
@@ -342,6 +347,23 @@ int32_t ttsamd_fastpitch_decode(void* handle, float* x, const int64_t* dec_lens,
     return fastpitch_decode((FastPitch*)handle, x, dec_lens, batch, t_max, mel, workspace, workspace_bytes,
                             (hipStream_t)stream);
 }
+int32_t ttsamd_fastpitch_encode_rows(void* handle, const int64_t* ids, int32_t batch, int32_t n_tokens, int32_t speaker,
+                                     float pace, const float* dur_tgt, const float* pitch_tgt, const float* energy_tgt,
+                                     float pitch_mul, float pitch_add, float max_duration, float* enc_cond,
+                                     float* dur_pred, float* pitch_pred, float* energy_pred, int64_t* reps,
+                                     int64_t* dec_lens, void* workspace, int64_t workspace_bytes,
+                                     const int32_t* speaker_rows, const float* pace_rows, const float* pitch_mul_rows,
+                                     const float* pitch_add_rows, int32_t flags, void* stream) {
+    return fastpitch_encode_rows((FastPitch*)handle, ids, batch, n_tokens, speaker, pace, dur_tgt, pitch_tgt, energy_tgt,
+                                 pitch_mul, pitch_add, max_duration, enc_cond, dur_pred, pitch_pred, energy_pred, reps,
+                                 dec_lens, workspace, workspace_bytes, speaker_rows, pace_rows, pitch_mul_rows, pitch_add_rows,
+                                 flags, (hipStream_t)stream);
+}
+int32_t ttsamd_fastpitch_decode_rows(void* handle, float* x, const int64_t* dec_lens, int32_t batch, int32_t t_max,
+                                     float* mel, void* workspace, int64_t workspace_bytes, int32_t flags, void* stream) {
+    return fastpitch_decode_rows((FastPitch*)handle, x, dec_lens, batch, t_max, mel, workspace, workspace_bytes, flags,
+                                 (hipStream_t)stream);
+}
 
 int32_t ttsamd_denoiser_create(void** handle) {
     Denoiser* h = nullptr;
@@ -365,7 +387,14 @@ int32_t ttsamd_denoiser_bias_spec(void* handle, const float* audio, const int64_
 int32_t ttsamd_denoise(void* handle, float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
                        int32_t n_max, const float* bias_spec, float strength, void* workspace,
                        int64_t workspace_bytes, void* stream) {
-    return denoise((Denoiser*)handle, wave, wave_stride, nsamples, batch, n_max, bias_spec, strength, workspace,
+    return denoise((Denoiser*)handle, wave, wave_stride, nsamples, batch, n_max, bias_spec, strength, nullptr, workspace,
+                   workspace_bytes, (hipStream_t)stream);
+}
+int32_t ttsamd_denoise_rows(void* handle, float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
+                            int32_t n_max, const float* bias_spec, const float* strength_rows, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+    TTS_REQUIRE(strength_rows, "denoise_rows: strength_rows is null");
+    return denoise((Denoiser*)handle, wave, wave_stride, nsamples, batch, n_max, bias_spec, 0.f, strength_rows, workspace,
                    workspace_bytes, (hipStream_t)stream);
 }
 
@@ -391,7 +420,14 @@ int32_t ttsamd_vocos_bias_vec(void* handle, float* bias_vec, void* workspace, in
 int32_t ttsamd_vocos_forward(void* handle, const float* mel, const int64_t* lens, int32_t batch, int32_t t_max,
                              float denoise, const float* bias_vec, float* wave, void* workspace,
                              int64_t workspace_bytes, void* stream) {
-    return vocos_forward((Vocos*)handle, mel, lens, batch, t_max, denoise, bias_vec, wave, workspace, workspace_bytes,
+    return vocos_forward((Vocos*)handle, mel, lens, batch, t_max, denoise, nullptr, bias_vec, wave, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+}
+int32_t ttsamd_vocos_forward_rows(void* handle, const float* mel, const int64_t* lens, int32_t batch, int32_t t_max,
+                                  const float* denoise_rows, const float* bias_vec, float* wave, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+    TTS_REQUIRE(denoise_rows, "vocos_forward_rows: denoise_rows is null");
+    return vocos_forward((Vocos*)handle, mel, lens, batch, t_max, 0.f, denoise_rows, bias_vec, wave, workspace, workspace_bytes,
                          (hipStream_t)stream);
 }
 

@@ -112,8 +112,10 @@ __global__ __launch_bounds__(256) void stft_frames_kernel(const float* __restric
 __global__ __launch_bounds__(256) void overlap_add_kernel(const float* __restrict__ Y, const float* __restrict__ win,
                                                           const int64_t* __restrict__ frames, int frames_mul,
                                                           int frames_add, int pad, int F, int ks, int ts,
-                                                          float* __restrict__ wave, int64_t wave_bs) {
+                                                          float* __restrict__ wave, int64_t wave_bs,
+                                                          const float* __restrict__ keep_rows) {
     const int b = blockIdx.y;
+    if (keep_rows && !(keep_rows[b] > 0.f)) return;            // denoise_rows: a row without denoising keeps its samples bit for bit
     const int m = blockIdx.x * 256 + threadIdx.x;
     const int fr = (int)frames[b] * frames_mul + frames_add;
     const int n_out = (fr - 1) * HOP + NFFT - 2 * pad;
@@ -133,10 +135,10 @@ __global__ __launch_bounds__(256) void overlap_add_kernel(const float* __restric
 
 int32_t launch_overlap_add(const float* Y, const float* win, const int64_t* frames, int32_t frames_mul, int32_t frames_add,
                            int32_t pad, int32_t B, int32_t F, int32_t n_max, float* wave, int64_t wave_bs, hipStream_t s,
-                           int32_t frame_major) {
+                           int32_t frame_major, const float* keep_rows) {
     if (n_max <= 0 || B <= 0) return 0;
     hipLaunchKernelGGL(overlap_add_kernel, dim3((n_max + 255) / 256, B), dim3(256), 0, s, Y, win, frames, frames_mul,
-                       frames_add, pad, F, frame_major ? 1 : F, frame_major ? NFFT : 1, wave, wave_bs);
+                       frames_add, pad, F, frame_major ? 1 : F, frame_major ? NFFT : 1, wave, wave_bs, keep_rows);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -157,6 +159,7 @@ __global__ void mag_frame0_kernel(const float* __restrict__ S, int F, float* __r
 // checked against numpy.fft in double before it was written: 4e-14).
 __global__ __launch_bounds__(256) void denoise_fft_kernel(const float* __restrict__ wave, int64_t wave_bs, const int64_t* __restrict__ ns,
                                                           const float* __restrict__ bias, float strength,
+                                                          const float* __restrict__ strength_rows,
                                                           const float* __restrict__ win, const float2* __restrict__ tw_g, int F,
                                                           float* __restrict__ Y) {
     __shared__ float2 buf[2][NFFT];
@@ -164,6 +167,10 @@ __global__ __launch_bounds__(256) void denoise_fft_kernel(const float* __restric
     const int b = blockIdx.y, t = blockIdx.x, i = threadIdx.x;
     const int n = (int)ns[b];
     if (t >= n / HOP + 1) return;                               // frames the overlap-add never reads
+    if (strength_rows) {
+        strength = strength_rows[b];
+        if (!(strength > 0.f)) return;                          // ... and a row the overlap-add leaves as it is (no denoising)
+    }
     const float* wb = wave + (int64_t)b * wave_bs;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -268,8 +275,11 @@ int32_t denoiser_bias_spec(const Denoiser* h, const float* audio, const int64_t*
     return 0;
 }
 
+// strength_rows: device [B] in place of the scalar (ttsamd_denoise_rows), nullptr: the scalar (ttsamd_denoise).  A row whose strength is
+// not > 0 is left untouched bit for bit -- an STFT -> ISTFT round trip is no identity in bits -- which is what the wrappers' `if denoise >
+// 0` does per call
 int32_t denoise(const Denoiser* h, float* wave, int64_t wave_bs, const int64_t* nsamples, int32_t B, int32_t n_max,
-                const float* bias_spec, float strength, void* ws, int64_t ws_bytes, hipStream_t s) {
+                const float* bias_spec, float strength, const float* strength_rows, void* ws, int64_t ws_bytes, hipStream_t s) {
     TTS_REQUIRE(h && wave && nsamples && bias_spec, "denoise: null argument");
     TTS_REQUIRE(B >= 1 && n_max > NFFT / 2, "denoise: needs more than %d samples per utterance", NFFT / 2);
     const int F = n_max / HOP + 1;
@@ -282,11 +292,13 @@ int32_t denoise(const Denoiser* h, float* wave, int64_t wave_bs, const int64_t* 
     }
     hipLaunchKernelGGL(frame_counts_kernel, dim3((B + 63) / 64), dim3(64), 0, s, nsamples, B, w.frames);
     // STFT -> gain -> ISTFT frames, one block per frame, time-domain frames into X as [b][frame][k]
-    hipLaunchKernelGGL(denoise_fft_kernel, dim3(F, B), dim3(256), 0, s, wave, wave_bs, nsamples, bias_spec, strength, h->dev + h->window,
+    hipLaunchKernelGGL(denoise_fft_kernel, dim3(F, B), dim3(256), 0, s, wave, wave_bs, nsamples, bias_spec, strength, strength_rows,
+                       h->dev + h->window,
                        reinterpret_cast<const float2*>(h->dev + h->twiddle), F, w.X);
     TTS_CHECK_HIP(hipGetLastError());
     // center=True: frames = n/HOP + 1 (w.frames), pad = NFFT/2, n_out = HOP*(frames-1)
-    return launch_overlap_add(w.X, h->dev + h->window, w.frames, 1, 0, NFFT / 2, B, F, n_max, wave, wave_bs, s, /*frame_major=*/1);
+    return launch_overlap_add(w.X, h->dev + h->window, w.frames, 1, 0, NFFT / 2, B, F, n_max, wave, wave_bs, s, /*frame_major=*/1,
+                              strength_rows);
 }
 
 }  // namespace ttsamd

@@ -229,14 +229,17 @@ int32_t launch_layernorm_cf(const float* x, float* y, const float* gamma, const 
 
 // ------------------------------------------------------------------------------------
 // Encoder embedding (transformer.py:212-219): word_emb gather + sinusoid table * mask + speaker.
-// pos_table is channel-first [C][pos_stride].
+// pos_table is channel-first [C][pos_stride].  spk_table: the pre-scaled speaker rows [n_speakers][C] or nullptr; a row's speaker is
+// speaker_rows[b] when the array is given, else `speaker`, clamped into the table (the host-side wrappers raise on a bad index).
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ ids,
                                                     const float* __restrict__ word_emb,
                                                     const float* __restrict__ pos, int pos_stride,
-                                                    const float* __restrict__ spk, int pad_idx, int n_symbols, int L, int C,
-                                                    float* __restrict__ x, int64_t* __restrict__ lens) {
+                                                    const float* __restrict__ spk_table, int speaker,
+                                                    const int32_t* __restrict__ speaker_rows, int n_speakers, int pad_idx,
+                                                    int n_symbols, int L, int C, float* __restrict__ x, int64_t* __restrict__ lens) {
     const int b = blockIdx.y;
+    const float* spk = spk_table ? spk_table + (int64_t)min(max(speaker_rows ? speaker_rows[b] : speaker, 0), n_speakers - 1) * C : nullptr;
     const int tl = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int t = blockIdx.x * 64 + tl;
     const int64_t* idb = ids + (int64_t)b * L;
@@ -260,10 +263,11 @@ __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ 
 }
 
 int32_t launch_embed(const int64_t* ids, const float* word_emb, const float* pos_table, int32_t pos_stride,
-                     const float* spk, int32_t pad_idx, int32_t n_symbols, int32_t B, int32_t L, int32_t C, float* x, int64_t* lens, hipStream_t s) {
+                     const float* spk_table, int32_t speaker, const int32_t* speaker_rows, int32_t n_speakers, int32_t pad_idx,
+                     int32_t n_symbols, int32_t B, int32_t L, int32_t C, float* x, int64_t* lens, hipStream_t s) {
     dim3 grid((L + 63) / 64, B, 8);     // z: channel slices (the kernel is latency-bound at one block per utterance)
-    hipLaunchKernelGGL(embed_kernel, grid, dim3(256), 0, s, ids, word_emb, pos_table, pos_stride, spk, pad_idx, n_symbols, L,
-                       C, x, lens);
+    hipLaunchKernelGGL(embed_kernel, grid, dim3(256), 0, s, ids, word_emb, pos_table, pos_stride, spk_table, speaker,
+                       speaker_rows, n_speakers, pad_idx, n_symbols, L, C, x, lens);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -551,7 +555,9 @@ __global__ __launch_bounds__(256) void pred_fc_kernel(const float* __restrict__ 
                                                       const float* __restrict__ bias,
                                                       const int64_t* __restrict__ lens, int C, int S,
                                                       float* __restrict__ out, float* __restrict__ out2,
-                                                      float max_dur, float mul, float add) {
+                                                      float max_dur, float mul, float add,
+                                                      const float* __restrict__ mul_rows, const float* __restrict__ add_rows,
+                                                      int zero_past_len) {
     __shared__ float part[16][17];
     const int b = blockIdx.y;
     const int tl = threadIdx.x & 15, g = threadIdx.x >> 4;
@@ -566,17 +572,22 @@ __global__ __launch_bounds__(256) void pred_fc_kernel(const float* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc += part[k][tl];
     acc += bias[0];
-    if (lens && t >= (int)lens[b]) acc = 0.f;   // "* enc_out_mask"
+    const bool past = lens && t >= (int)lens[b];
+    if (past) acc = 0.f;                        // "* enc_out_mask"
     if (out2) out2[(int64_t)b * S + t] = fminf(fmaxf(expf(acc) - 1.0f, 0.f), max_dur);
-    out[(int64_t)b * S + t] = mul * acc + add;
+    // pitch_trf per row: the array's value where one is given, the same expression either way
+    const float m = mul_rows ? mul_rows[b] : mul, a = add_rows ? add_rows[b] : add;
+    // the reference transforms the MASKED prediction, so in its padded batch the positions past a row's end hold `add`, which the k = 3
+    // pitch embedding reads at the row's last token; a row computed as if alone has no such positions (zero padding)
+    out[(int64_t)b * S + t] = (past && zero_past_len) ? 0.f : m * acc + a;
 }
 
 int32_t launch_pred_fc(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t B,
                        int32_t C, int32_t S, float* out, float* out2, float max_dur, float mul, float add,
-                       hipStream_t s) {
+                       hipStream_t s, const float* mul_rows, const float* add_rows, int32_t zero_past_len) {
     dim3 grid((S + 15) / 16, B);
     hipLaunchKernelGGL(pred_fc_kernel, grid, dim3(256), 0, s, x, w, bias, lens, C, S, out, out2, max_dur, mul,
-                       add);
+                       add, mul_rows, add_rows, zero_past_len);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -611,10 +622,15 @@ int32_t launch_scalar_emb_add(float* enc, const float* src, const float* w, cons
 // ------------------------------------------------------------------------------------
 // Length regulator, integer half (model.py:72-76).  One wave64 per utterance.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void durations_to_reps_kernel(const float* __restrict__ dur, float pace, int L,
+__global__ __launch_bounds__(64) void durations_to_reps_kernel(const float* __restrict__ dur, float pace,
+                                                               const float* __restrict__ pace_rows, int L,
                                                                int64_t* __restrict__ reps,
                                                                int64_t* __restrict__ dec_lens) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    if (pace_rows) {
+        pace = pace_rows[b];
+        if (!(pace > 0.f)) pace = 1.f;                           // the host-side wrappers raise; here a bad row only keeps its durations
+    }
     long long tot = 0;
     for (int i = lane; i < L; i += 64) {
         const float r = dur[(int64_t)b * L + i] / pace + 0.5f;   // fp32, as durations.float()/pace + 0.5
@@ -628,8 +644,8 @@ __global__ __launch_bounds__(64) void durations_to_reps_kernel(const float* __re
 }
 
 int32_t launch_durations_to_reps(const float* dur, float pace, int32_t B, int32_t L, int64_t* reps,
-                                 int64_t* dec_lens, hipStream_t s) {
-    hipLaunchKernelGGL(durations_to_reps_kernel, dim3(B), dim3(64), 0, s, dur, pace, L, reps, dec_lens);
+                                 int64_t* dec_lens, hipStream_t s, const float* pace_rows) {
+    hipLaunchKernelGGL(durations_to_reps_kernel, dim3(B), dim3(64), 0, s, dur, pace, pace_rows, L, reps, dec_lens);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }

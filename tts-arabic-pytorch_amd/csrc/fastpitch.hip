@@ -48,7 +48,9 @@ struct FastPitch {
     int pos_cap = 0;
     // ttsamd_fastpitch_set_batch_mode: 0 = the reference's padded-batch arithmetic (hidden activations of conv-FF / the predictors are NOT
     // masked, so an utterance's result depends on the longest one of its batch: SURVEY 3.4-1); 1 = every utterance as if it were alone --
-    // those two second convs read their input masked at the utterance's own length, which is all it takes: every other op already masks
+    // those two second convs read their input masked at the utterance's own length, which is all it takes: every other op already masks.
+    // The switch of the entries WITHOUT flags; ttsamd_fastpitch_encode_rows / _decode_rows take the mode per call (flags bit 0) and neither
+    // read nor write this
     mutable std::atomic<int> alone{0};
 };
 
@@ -313,12 +315,11 @@ static int32_t octet_conv(const BfoMode& M, const PConv& c, const BfoConvParams&
     return rc;
 }
 
-// transformer.py:172-177 x n_layers.  x is updated in place.
+// transformer.py:172-177 x n_layers.  x is updated in place.  alone: batch mode 1 for this call (the caller decides where it comes from)
 static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, int d_head, float* x,
-                       const int64_t* lens, int B, int S, const FftWs& w, hipStream_t s) {
+                       const int64_t* lens, int B, int S, const FftWs& w, bool alone, hipStream_t s) {
     const int d = h->cfg.d_model;
     const float scale = 1.0f / std::sqrt((float)d_head);
-    const bool alone = h->alone.load(std::memory_order_relaxed) != 0;
     const PConv *ff2_of = nullptr, *ff0_of = nullptr;   // the layer's conv-FF convs (octet paths: set per layer below)
     const bool ff_on = opt_int(OPT_BFO_FF, 1) != 0;     // read per call: the tests and A/B runs flip it
     bool octet = default_precision() == 1 && ff_on && d % 64 == 0 && d <= 512 && d_head == 64;
@@ -423,7 +424,8 @@ static int32_t run_fft(const FastPitch* h, const std::vector<FftLayer>& layers, 
 // it matters when the caller's rows are wider than the longest utterance)
 static int32_t run_predictor(const FastPitch* h, const Predictor& pr, const float* x, const int64_t* lens, int B,
                              int S, float* t0, float* t1, float* out, float* out2, float max_dur, float mul,
-                             float add, hipStream_t s, void* px3 = nullptr, const int64_t* lens1 = nullptr) {
+                             float add, bool alone, hipStream_t s, void* px3 = nullptr, const int64_t* lens1 = nullptr,
+                             const float* mul_rows = nullptr, const float* add_rows = nullptr) {
     const float* src = x;
     float* bufs[2] = {t0, t1};
     const int prec = default_precision();
@@ -453,19 +455,20 @@ static int32_t run_predictor(const FastPitch* h, const Predictor& pr, const floa
             TTS_TRY(conv(pr.convs[0], xo, t0, lens));
             // LayerNorm of layer 0 in place (fp32, t0) + its copy over the packed input, which is dead now
             TTS_TRY(M.layernorm_cf(t0, t0, xo, h->dev + pr.ln_g[0], h->dev + pr.ln_b[0], nullptr, 0, B, pr.filter, S, s, 1e-5f));
-            TTS_TRY(conv(pr.convs[1], xo, y1, h->alone.load(std::memory_order_relaxed) ? lens : lens1));
+            TTS_TRY(conv(pr.convs[1], xo, y1, alone ? lens : lens1));
             TTS_TRY(launch_layernorm_cf(y1, y1, h->dev + pr.ln_g[1], h->dev + pr.ln_b[1], nullptr, 0, B, pr.filter, S, s));
-            return launch_pred_fc(y1, h->dev + pr.fc_w, h->dev + pr.fc_b, lens, B, pr.filter, S, out, out2, max_dur, mul, add, s);
+            return launch_pred_fc(y1, h->dev + pr.fc_w, h->dev + pr.fc_b, lens, B, pr.filter, S, out, out2, max_dur, mul, add, s, mul_rows,
+                                  add_rows, alone);
         }
     }
     for (size_t i = 0; i < pr.convs.size(); ++i) {
         float* dst = bufs[i & 1];
-        TTS_TRY(run_conv(h, pr.convs[i], src, dst, nullptr, B, S, (i == 0 || h->alone.load(std::memory_order_relaxed)) ? lens : lens1, 1, s));
+        TTS_TRY(run_conv(h, pr.convs[i], src, dst, nullptr, B, S, (i == 0 || alone) ? lens : lens1, 1, s));
         TTS_TRY(launch_layernorm_cf(dst, dst, h->dev + pr.ln_g[i], h->dev + pr.ln_b[i], nullptr, 0, B, pr.filter, S, s));
         src = dst;
     }
     return launch_pred_fc(src, h->dev + pr.fc_w, h->dev + pr.fc_b, lens, B, pr.filter, S, out, out2, max_dur, mul,
-                          add, s);
+                          add, s, mul_rows, add_rows, alone);
 }
 
 struct EncWs {
@@ -499,17 +502,20 @@ int64_t fastpitch_encode_workspace_bytes(const FastPitch* h, int32_t B, int32_t 
     return a.off;
 }
 
-int32_t fastpitch_encode(const FastPitch* h, const int64_t* ids, int32_t B, int32_t L, int32_t speaker, float pace,
-                         const float* dur_tgt, const float* pitch_tgt, const float* energy_tgt, float pitch_mul,
-                         float pitch_add, float max_duration, float* enc_cond, float* dur_pred, float* pitch_pred,
-                         float* energy_pred, int64_t* reps, int64_t* dec_lens, void* ws, int64_t ws_bytes,
-                         hipStream_t s) {
+// One body for ttsamd_fastpitch_encode (no row arrays, alone = the handle's mode) and ttsamd_fastpitch_encode_rows (flags bit 0): the row
+// arrays reach the same kernels as the scalars, so a row's bits do not depend on which form delivered its value
+static int32_t encode_impl(const FastPitch* h, const int64_t* ids, int32_t B, int32_t L, int32_t speaker, float pace,
+                           const float* dur_tgt, const float* pitch_tgt, const float* energy_tgt, float pitch_mul,
+                           float pitch_add, float max_duration, float* enc_cond, float* dur_pred, float* pitch_pred,
+                           float* energy_pred, int64_t* reps, int64_t* dec_lens, void* ws, int64_t ws_bytes,
+                           const int32_t* speaker_rows, const float* pace_rows, const float* pitch_mul_rows, const float* pitch_add_rows,
+                           bool alone, hipStream_t s) {
     TTS_REQUIRE(h && ids && enc_cond && dur_pred && pitch_pred && reps && dec_lens, "fastpitch_encode: null argument");
     TTS_REQUIRE(B >= 1 && L >= 1 && L <= h->pos_cap, "fastpitch_encode: bad batch/n_tokens (%d, %d; cap %d)", B, L,
                 h->pos_cap);
-    TTS_REQUIRE(pace > 0.f, "fastpitch_encode: pace must be > 0");
+    TTS_REQUIRE(pace_rows || pace > 0.f, "fastpitch_encode: pace must be > 0");
     const ttsamd_fastpitch_cfg& c = h->cfg;
-    TTS_REQUIRE(c.n_speakers <= 1 || (speaker >= 0 && speaker < c.n_speakers), "fastpitch_encode: speaker %d out of range", speaker);
+    TTS_REQUIRE(speaker_rows || c.n_speakers <= 1 || (speaker >= 0 && speaker < c.n_speakers), "fastpitch_encode: speaker %d out of range", speaker);
     TTS_REQUIRE(!c.energy_conditioning || energy_pred || energy_tgt, "fastpitch_encode: energy_pred is null");
     Arena a(ws, ws_bytes);
     EncWs w;
@@ -522,30 +528,54 @@ int32_t fastpitch_encode(const FastPitch* h, const int64_t* ids, int32_t B, int3
     SplitKScope splitk(w.f.splitk);
     SmallBatchScope small_f32(B);
     float* x = enc_cond;
-    const float* spk = (c.n_speakers > 1 && h->spk_emb >= 0) ? h->dev + h->spk_emb + (int64_t)speaker * d : nullptr;
-    TTS_TRY(launch_embed(ids, h->dev + h->word_emb, h->dev + h->pos_enc, h->pos_cap, spk, c.padding_idx, c.n_symbols, B, L, d, x,
-                         w.lens, s));
+    const float* spk = (c.n_speakers > 1 && h->spk_emb >= 0) ? h->dev + h->spk_emb : nullptr;
+    TTS_TRY(launch_embed(ids, h->dev + h->word_emb, h->dev + h->pos_enc, h->pos_cap, spk, speaker, speaker_rows, c.n_speakers, c.padding_idx,
+                         c.n_symbols, B, L, d, x, w.lens, s));
     // (one frame past a row's end is what a k = 3 conv reads: the ragged schedule is built for the reference's kernel sizes)
     if (B >= 2 && c.in_fft_kernel == 3 && c.dur_kernel == 3 && c.pitch_kernel == 3 && (!c.energy_conditioning || c.energy_kernel == 3)) {
         TTS_TRY(launch_lens_plus1(w.lens, L, B, /*clamp_at_max=*/0, w.f.lens1, s));
         w.f.ragged = true;
     }
-    TTS_TRY(run_fft(h, h->enc, c.in_fft_d_head, x, w.lens, B, L, w.f, s));
+    TTS_TRY(run_fft(h, h->enc, c.in_fft_d_head, x, w.lens, B, L, w.f, alone, s));
     // durations (model.py:367-368)
-    TTS_TRY(run_predictor(h, h->dur, x, w.lens, B, L, w.p0, w.p1, w.log_dur, dur_pred, max_duration, 1.f, 0.f, s, w.f.o3, w.f.ragged ? w.f.lens1 : nullptr));
+    TTS_TRY(run_predictor(h, h->dur, x, w.lens, B, L, w.p0, w.p1, w.log_dur, dur_pred, max_duration, 1.f, 0.f, alone, s, w.f.o3, w.f.ragged ? w.f.lens1 : nullptr));
     // pitch (model.py:371-386); pitch_trf = mul*p + add (networks.py:38-42)
-    TTS_TRY(run_predictor(h, h->pitch, x, w.lens, B, L, w.p0, w.p1, pitch_pred, nullptr, 0.f, pitch_mul, pitch_add, s, w.f.o3, w.f.ragged ? w.f.lens1 : nullptr));
+    TTS_TRY(run_predictor(h, h->pitch, x, w.lens, B, L, w.p0, w.p1, pitch_pred, nullptr, 0.f, pitch_mul, pitch_add, alone, s, w.f.o3, w.f.ragged ? w.f.lens1 : nullptr,
+                          pitch_mul_rows, pitch_add_rows));
     TTS_TRY(launch_scalar_emb_add(x, pitch_tgt ? pitch_tgt : pitch_pred, h->dev + h->pitch_emb_w,
                                   h->dev + h->pitch_emb_b, B, d, L, c.pitch_emb_kernel, s));
     // energy (model.py:389-399)
     if (c.energy_conditioning) {
         if (energy_pred)
-            TTS_TRY(run_predictor(h, h->energy, x, w.lens, B, L, w.p0, w.p1, energy_pred, nullptr, 0.f, 1.f, 0.f, s, w.f.o3, w.f.ragged ? w.f.lens1 : nullptr));
+            TTS_TRY(run_predictor(h, h->energy, x, w.lens, B, L, w.p0, w.p1, energy_pred, nullptr, 0.f, 1.f, 0.f, alone, s, w.f.o3, w.f.ragged ? w.f.lens1 : nullptr));
         TTS_TRY(launch_scalar_emb_add(x, energy_tgt ? energy_tgt : energy_pred, h->dev + h->energy_emb_w,
                                       h->dev + h->energy_emb_b, B, d, L, c.energy_emb_kernel, s));
     }
     // integer half of regulate_len (model.py:72-76)
-    return launch_durations_to_reps(dur_tgt ? dur_tgt : dur_pred, pace, B, L, reps, dec_lens, s);
+    return launch_durations_to_reps(dur_tgt ? dur_tgt : dur_pred, pace, B, L, reps, dec_lens, s, pace_rows);
+}
+
+int32_t fastpitch_encode(const FastPitch* h, const int64_t* ids, int32_t B, int32_t L, int32_t speaker, float pace,
+                         const float* dur_tgt, const float* pitch_tgt, const float* energy_tgt, float pitch_mul,
+                         float pitch_add, float max_duration, float* enc_cond, float* dur_pred, float* pitch_pred,
+                         float* energy_pred, int64_t* reps, int64_t* dec_lens, void* ws, int64_t ws_bytes,
+                         hipStream_t s) {
+    return encode_impl(h, ids, B, L, speaker, pace, dur_tgt, pitch_tgt, energy_tgt, pitch_mul, pitch_add, max_duration, enc_cond, dur_pred,
+                       pitch_pred, energy_pred, reps, dec_lens, ws, ws_bytes, nullptr, nullptr, nullptr, nullptr,
+                       h && h->alone.load(std::memory_order_relaxed) != 0, s);
+}
+
+// flags: bit 0 = rows as if alone, for this call only (the handle's mode is neither read nor written)
+int32_t fastpitch_encode_rows(const FastPitch* h, const int64_t* ids, int32_t B, int32_t L, int32_t speaker, float pace,
+                              const float* dur_tgt, const float* pitch_tgt, const float* energy_tgt, float pitch_mul,
+                              float pitch_add, float max_duration, float* enc_cond, float* dur_pred, float* pitch_pred,
+                              float* energy_pred, int64_t* reps, int64_t* dec_lens, void* ws, int64_t ws_bytes,
+                              const int32_t* speaker_rows, const float* pace_rows, const float* pitch_mul_rows,
+                              const float* pitch_add_rows, int32_t flags, hipStream_t s) {
+    TTS_REQUIRE((flags & ~1) == 0, "fastpitch_encode_rows: unknown flag bits 0x%x (bit 0 = rows as if alone)", (unsigned)flags);
+    return encode_impl(h, ids, B, L, speaker, pace, dur_tgt, pitch_tgt, energy_tgt, pitch_mul, pitch_add, max_duration, enc_cond, dur_pred,
+                       pitch_pred, energy_pred, reps, dec_lens, ws, ws_bytes, speaker_rows, pace_rows, pitch_mul_rows, pitch_add_rows,
+                       (flags & 1) != 0, s);
 }
 
 static void carve_dec(const FastPitch* h, Arena& a, int B, int T, FftWs& w) {
@@ -567,8 +597,8 @@ int64_t fastpitch_decode_workspace_bytes(const FastPitch* h, int32_t B, int32_t 
     return a.off;
 }
 
-int32_t fastpitch_decode(const FastPitch* h, float* x, const int64_t* dec_lens, int32_t B, int32_t T, float* mel,
-                         void* ws, int64_t ws_bytes, hipStream_t s) {
+static int32_t decode_impl(const FastPitch* h, float* x, const int64_t* dec_lens, int32_t B, int32_t T, float* mel,
+                           void* ws, int64_t ws_bytes, bool alone, hipStream_t s) {
     TTS_REQUIRE(h && x && dec_lens && mel, "fastpitch_decode: null argument");
     TTS_REQUIRE(B >= 1 && T >= 1 && T <= h->pos_cap, "fastpitch_decode: bad batch/t_max (%d, %d; cap %d)", B, T,
                 h->pos_cap);
@@ -588,9 +618,20 @@ int32_t fastpitch_decode(const FastPitch* h, float* x, const int64_t* dec_lens, 
         TTS_TRY(launch_lens_plus1(dec_lens, T, B, /*clamp_at_max=*/1, w.lens1, s));     // t_max may be the caller's 16-byte-padded row width
         w.ragged = true;
     }
-    TTS_TRY(run_fft(h, h->dec, c.out_fft_d_head, x, dec_lens, B, T, w, s));
+    TTS_TRY(run_fft(h, h->dec, c.out_fft_d_head, x, dec_lens, B, T, w, alone, s));
     // proj + permute (model.py:406-408): channel-first output IS the permuted layout
     return run_conv(h, h->proj, x, mel, nullptr, B, T, nullptr, 0, s);
+}
+
+int32_t fastpitch_decode(const FastPitch* h, float* x, const int64_t* dec_lens, int32_t B, int32_t T, float* mel,
+                         void* ws, int64_t ws_bytes, hipStream_t s) {
+    return decode_impl(h, x, dec_lens, B, T, mel, ws, ws_bytes, h && h->alone.load(std::memory_order_relaxed) != 0, s);
+}
+
+int32_t fastpitch_decode_rows(const FastPitch* h, float* x, const int64_t* dec_lens, int32_t B, int32_t T, float* mel,
+                              void* ws, int64_t ws_bytes, int32_t flags, hipStream_t s) {
+    TTS_REQUIRE((flags & ~1) == 0, "fastpitch_decode_rows: unknown flag bits 0x%x (bit 0 = rows as if alone)", (unsigned)flags);
+    return decode_impl(h, x, dec_lens, B, T, mel, ws, ws_bytes, (flags & 1) != 0, s);
 }
 
 void fastpitch_set_batch_mode(const FastPitch* h, int mode) { h->alone.store(mode != 0 ? 1 : 0, std::memory_order_relaxed); }

@@ -23,11 +23,12 @@ int32_t launch_layernorm_cf_octet(const float* x, float* y, void* y_octet, const
                                   const int64_t* lens, int32_t apply_mask, int32_t B, int32_t C, int32_t S,
                                   hipStream_t s, float eps = 1e-5f);
 
-// Encoder input: x[b][c][t] = word_emb[ids[b][t]][c] + pos[t][c]*(ids!=pad) + spk[c]
-// (transformer.py:212-219; model.py:355-361).  Also writes lens[b] = #non-pad tokens.
+// Encoder input: x[b][c][t] = word_emb[ids[b][t]][c] + pos[t][c]*(ids!=pad) + spk_table[speaker of row b][c]
+// (transformer.py:212-219; model.py:355-361).  Also writes lens[b] = #non-pad tokens.  The row's speaker is speaker_rows[b] (device
+// int32 [B]) or, with nullptr, `speaker`; clamped into [0, n_speakers).  spk_table = nullptr: no speaker term.
 int32_t launch_embed(const int64_t* ids, const float* word_emb, const float* pos_table, int32_t pos_stride,
-                     const float* spk, int32_t pad_idx, int32_t n_symbols, int32_t B, int32_t L, int32_t C, float* x, int64_t* lens,
-                     hipStream_t s);
+                     const float* spk_table, int32_t speaker, const int32_t* speaker_rows, int32_t n_speakers, int32_t pad_idx,
+                     int32_t n_symbols, int32_t B, int32_t L, int32_t C, float* x, int64_t* lens, hipStream_t s);
 
 // 1-head self attention over channel-first q,k,v = rows [0,D),[D,2D),[2D,3D) of qkv [B][3D][S]
 // (transformer.py:131-141): out[b][d][i] = sum_j softmax_j(q_i.k_j * scale | j < lens[b]) v_j[d]
@@ -42,17 +43,20 @@ int32_t launch_attention_bf16(const float* qkv, const int64_t* lens, int32_t B, 
 
 // Predictor head (model.py:132): out[b][t] = (bias + sum_c w[c]*x[b][c][t]) * (t < lens[b]);
 // mode 1 additionally writes dur = clamp(exp(out)-1, 0, max_dur) (model.py:368) to out2.
+// mul_rows / add_rows: device [B] in place of the scalars (nullptr: the scalar), the same expression per row either way.
+// zero_past_len: out is 0 past lens[b] instead of `add` (rows computed as if alone: the padding of a lone row is zero).
 int32_t launch_pred_fc(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t B,
                        int32_t C, int32_t S, float* out, float* out2, float max_dur, float mul, float add,
-                       hipStream_t s);
+                       hipStream_t s, const float* mul_rows = nullptr, const float* add_rows = nullptr, int32_t zero_past_len = 0);
 
 // enc[b][c][t] += bias[c] + sum_k w[c][k] * src[b][t+k-K/2]   (Conv1d(1->C,k) embeddings, model.py:382-397)
 int32_t launch_scalar_emb_add(float* enc, const float* src, const float* w, const float* bias, int32_t B,
                               int32_t C, int32_t S, int32_t K, hipStream_t s);
 
 // Integer half of regulate_len (model.py:72-76): reps=(dur/pace+0.5).long(), dec_lens=sum.
+// pace_rows: device [B] in place of the scalar (nullptr: the scalar); a row's pace that is not > 0 is taken as 1.
 int32_t launch_durations_to_reps(const float* dur, float pace, int32_t B, int32_t L, int64_t* reps,
-                                 int64_t* dec_lens, hipStream_t s);
+                                 int64_t* dec_lens, hipStream_t s, const float* pace_rows = nullptr);
 
 // Gather half (model.py:77-85) + optional decoder positional embedding (transformer.py:215-219).
 int32_t launch_regulate_gather(const float* enc, const int64_t* reps, const float* pos_table, int32_t pos_stride, int32_t B,
@@ -71,7 +75,8 @@ int32_t launch_dwconv7(const float* x, const float* w, const float* bias, const 
 void hann_window_1024(std::vector<float>& window);   // periodic hann, n = 1024 (denoiser.hip)
 int32_t launch_overlap_add(const float* Y, const float* win, const int64_t* frames, int32_t frames_mul, int32_t frames_add,
                            int32_t pad, int32_t B, int32_t F, int32_t n_max, float* wave, int64_t wave_bs, hipStream_t s,
-                           int32_t frame_major = 0);   // Y as [b][k][F] (0) or [b][F][k] (1)
+                           int32_t frame_major = 0,    // Y as [b][k][F] (0) or [b][F][k] (1)
+                           const float* keep_rows = nullptr);   // device [B]: a row whose value is not > 0 is not written (denoise_rows)
 
 // Recording preparation (resample.hip, trim.hip; include/ttsamd.h states the arithmetic)
 struct Resample;

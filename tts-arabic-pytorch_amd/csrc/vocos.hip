@@ -174,11 +174,14 @@ void vocos_destroy(Vocos* h) {
 //    imaginary parts of DC and Nyquist dropped as irfft does), runs ONE 1024-point FFT in LDS (fft1024.hpp) and writes Re / 1024 * window as
 //    Y[b][t][k].  Rounds 1-5 ran the inverse DFT as a [1152 -> 1024] GEMM on the conv engine: 300 us per B = 32 call (40x the FLOPs).
 __global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restrict__ O, const float* __restrict__ bias, float denoise,
-                                                           const int64_t* __restrict__ lens, int T, float2* __restrict__ S) {
+                                                           const float* __restrict__ denoise_rows, const int64_t* __restrict__ lens, int T, float2* __restrict__ S) {
     __shared__ float2 tile[32][33];
     const int b = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int len = lens ? min((int)lens[b], T) : T;
     if (t0 >= len) return;
+    // the row's strength; the scalar entry passes bias = nullptr for 0, so a row at 0 takes the same (no) subtraction
+    const float dn = denoise_rows ? denoise_rows[b] : denoise;
+    const bool sub = bias != nullptr && dn != 0.f;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
     const float* ob = O + (int64_t)b * V_SPEC_CP * T;
 #pragma unroll
@@ -188,7 +191,7 @@ __global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restri
         if (f < V_NBIN && t < len) {
             const float lm = ob[(int64_t)f * T + t], ph = ob[(int64_t)(V_NBIN + f) * T + t];
             float mag = expf(lm);
-            if (bias) mag -= denoise * bias[f];
+            if (sub) mag -= dn * bias[f];
             mag = fminf(fmaxf(mag, 0.f), 100.f);
             v = make_float2(mag * cosf(ph), mag * sinf(ph));
         }
@@ -323,10 +326,11 @@ int64_t vocos_bias_workspace_bytes(const Vocos* h) {
     return a.off;
 }
 
+// denoise_rows: device [B] in place of the scalar (ttsamd_vocos_forward_rows), nullptr: the scalar (ttsamd_vocos_forward)
 int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int32_t B, int32_t T, float denoise,
-                      const float* bias_vec, float* wave, void* ws, int64_t ws_bytes, hipStream_t s) {
+                      const float* denoise_rows, const float* bias_vec, float* wave, void* ws, int64_t ws_bytes, hipStream_t s) {
     TTS_REQUIRE(h && mel && wave && lens && B >= 1 && T >= 1, "vocos_forward: bad argument");
-    TTS_REQUIRE(denoise == 0.f || bias_vec, "vocos_forward: denoise > 0 needs bias_vec");
+    TTS_REQUIRE((denoise == 0.f && !denoise_rows) || bias_vec, "vocos_forward: denoise > 0 needs bias_vec");
     if (h->center && T == 1) return 0;       // the centred ISTFT of one frame has no sample left after trimming n_fft / 2 per side
     Arena a(ws, ws_bytes);
     VWs w;
@@ -346,7 +350,7 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
     TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_forward: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
     float2* S = reinterpret_cast<float2*>(w.h);
     hipLaunchKernelGGL(vocos_spec_t_kernel, dim3((T + 31) / 32, (V_NBIN + 31) / 32, B), dim3(256), 0, s, w.o,
-                       denoise != 0.f ? bias_vec : nullptr, denoise, lens, T, S);
+                       (denoise != 0.f || denoise_rows) ? bias_vec : nullptr, denoise, denoise_rows, lens, T, S);
     hipLaunchKernelGGL(vocos_istft_kernel, dim3(T, B), dim3(256), 0, s, S, lens, h->dev + h->window,
                        reinterpret_cast<const float2*>(h->dev + h->twiddle), T, w.y);
     TTS_CHECK_HIP(hipGetLastError());

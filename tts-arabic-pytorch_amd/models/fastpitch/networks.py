@@ -20,6 +20,7 @@ import torch.nn as nn
 import text
 from ttsamd.engine import ALIGNER_KEYS, OBJECTIVE_KEYS, AlignerEngine, FastPitchEngine, ObjectiveEngine
 from ttsamd.engine import average_pitch as _average_pitch
+from ttsamd.engine import check_finite, check_speakers, per_row, row_values
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
@@ -35,6 +36,32 @@ def text_collate_fn(batch: List[torch.Tensor]):
     for i, j in enumerate(sort_ids):
         ids_pad[i, :batch[j].size(0)] = batch[j]
     return ids_pad, lens_sorted, sort_ids.argsort()
+
+
+# ---- mixed requests: `speed`, `speaker_id`, `pitch_mul`, `pitch_add` (and `denoise` on the wave side) are one scalar for all lines or a
+# list with one value per line.  A list follows its lines through every reordering (the collate sort, the chunks, the length-sorted
+# groups) by being indexed with the same positions as the lines: _take.
+def _take(value, idx):
+    """The control for the lines at positions `idx`: a scalar as it is, a per-line list picked in that order."""
+    return [value[i] for i in idx] if per_row(value) else value
+
+
+def _at(value, i):
+    return value[i] if per_row(value) else value
+
+
+def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1., pitch_add=0., denoise=0.):
+    """Host-side validation of per-line controls before any work: a list must have one value per line (ValueError), speakers lie in
+    [0, n_speakers) (IndexError), speeds are finite and > 0, pitch values and denoise strengths finite (ValueError).  Scalars pass
+    through to the checks of the calls that take them."""
+    for what, v in (('speed', speed), ('speaker_id', speaker_id), ('pitch_mul', pitch_mul), ('pitch_add', pitch_add), ('denoise', denoise)):
+        if not per_row(v):
+            continue
+        vals = row_values(v, n_lines, what)
+        if what == 'speaker_id':
+            check_speakers(vals, n_speakers, what)
+        else:
+            check_finite(vals, what, positive=(what == 'speed'))
 
 
 # what FastPitch.align returns: dur_tgt [B, L], pitch_tgt / energy_tgt [B, 1, L] or None, the attention maps [B, 1, T, L] or None
@@ -165,20 +192,24 @@ class FastPitch(_HipModule):
     # ---- FastPitch.infer (models/fastpitch/fastpitch/model.py:351-353) -------------------
     @torch.inference_mode()
     def infer(self, inputs, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_transform=None,
-              max_duration=75, speaker=0, alone=False):
+              max_duration=75, speaker=0, alone=False, pitch_mul=None, pitch_add=None):
         """`alone=True` (not in the reference): every row of the batch as if it were the only utterance of the call, i.e. row b ==
-        infer(inputs[b:b+1, :len_b]) within fp32 summation order (FastPitchEngine.infer) -- the batch_size = 1 loop as one ragged call."""
+        infer(inputs[b:b+1, :len_b]) within fp32 summation order (FastPitchEngine.infer) -- the batch_size = 1 loop as one ragged call.
+        Mixed requests (not in the reference): `pace` and `speaker` take a scalar or one value per row; `pitch_mul` / `pitch_add` (scalars
+        or per row) are pitch_trf's two numbers given directly -- together with a `pitch_transform` they are refused, since a callable
+        cannot be applied per row inside the predictor head."""
         ids = torch.as_tensor(inputs).long()
         if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.net_config['n_symbols']):
             raise IndexError(f'token id out of range [0, {self.net_config["n_symbols"]}) (nn.Embedding raises here too)')
-        if self.net_config['n_speakers'] > 1 and not 0 <= int(speaker) < self.net_config['n_speakers']:
+        if (pitch_mul is not None or pitch_add is not None) and pitch_transform is not None:
+            raise ValueError('infer: pitch_mul / pitch_add are given together with a pitch_transform; pass one or the other '
+                             '(per-row pitch values cannot go through a callable)')
+        mul, add = (1.0 if pitch_mul is None else pitch_mul), (0.0 if pitch_add is None else pitch_add)
+        check_line_controls(ids.shape[0], self.net_config['n_speakers'], speed=pace, speaker_id=speaker, pitch_mul=mul, pitch_add=add)
+        if not per_row(speaker) and self.net_config['n_speakers'] > 1 and not 0 <= int(speaker) < self.net_config['n_speakers']:
             raise IndexError(f'speaker {speaker} out of range [0, {self.net_config["n_speakers"]})')
-        nz = (ids != self.net_config['padding_idx'])
-        lens = nz.sum(1)
-        if not bool((nz == (torch.arange(ids.shape[1], device=ids.device)[None] < lens[:, None])).all()):
-            raise ValueError('ids must be zero-padded at the end of each row (text_collate_fn layout)')
+        lens = self._ends_padded(ids)
         eng = self.engine()
-        mul, add = 1.0, 0.0
         if pitch_transform is not None:
             if hasattr(pitch_transform, 'affine'):
                 mul, add = pitch_transform.affine
@@ -192,6 +223,14 @@ class FastPitch(_HipModule):
                 return out[0], out[1], out[2], pp, out[4]
         return eng.infer(ids, pace=pace, dur_tgt=dur_tgt, pitch_tgt=pitch_tgt, energy_tgt=energy_tgt,
                          pitch_mul=mul, pitch_add=add, max_duration=max_duration, speaker=speaker, alone=alone)
+
+    def _ends_padded(self, ids):
+        """token counts per row; ValueError unless every row is zero-padded at its end"""
+        nz = (ids != self.net_config['padding_idx'])
+        lens = nz.sum(1)
+        if not bool((nz == (torch.arange(ids.shape[1], device=ids.device)[None] < lens[:, None])).all()):
+            raise ValueError('ids must be zero-padded at the end of each row (text_collate_fn layout)')
+        return lens
 
     # ---- text -> mel (reference :77-253) -----------------------------------------------
     def _vowelize(self, utterance: str, vowelizer=None):
@@ -218,6 +257,16 @@ class FastPitch(_HipModule):
             return pitch_trf(pitch_mul, pitch_add)
         return pitch_transform
 
+    @classmethod
+    def _pitch_kw(cls, pitch_mul, pitch_add, pitch_transform):
+        """infer()'s pitch arguments: the tagged affine transform for scalars (as before), the two numbers themselves when either is given
+        per line -- a custom `pitch_transform` cannot be applied per row and is refused then."""
+        if per_row(pitch_mul) or per_row(pitch_add):
+            if pitch_transform is not None:
+                raise ValueError('per-line pitch_mul / pitch_add cannot be combined with a pitch_transform callable')
+            return dict(pitch_mul=pitch_mul, pitch_add=pitch_add)
+        return dict(pitch_transform=cls._ptrf(pitch_mul, pitch_add, pitch_transform))
+
     @torch.inference_mode()
     def ttmel_single(self, utterance: str, speed: float = 1, speaker_id: int = 0, vowelizer=None,
                      pitch_mul: float = 1., pitch_add: float = 0., dur_tgt=None, pitch_tgt=None,
@@ -231,14 +280,21 @@ class FastPitch(_HipModule):
 
     @torch.inference_mode()
     def _ttmel_batch_padded(self, batch, speed, speaker_id, vowelizer, pitch_mul, pitch_add, dur_tgt=None,
-                            pitch_tgt=None, energy_tgt=None, pitch_transform=None, max_duration=75):
+                            pitch_tgt=None, energy_tgt=None, pitch_transform=None, max_duration=75, alone=None):
+        """alone None: rows as if alone exactly when a control is given per line -- mixed requests are independent requests, and one's
+        mel must not depend on which others shared its batch (it equals ttmel_single with its options within fp32 summation order); all
+        scalars: the reference's padded-batch arithmetic, as before."""
         batch_ids = [torch.LongTensor(text.tokens_to_ids(self._tokenize(line, vowelizer), self.phon_to_id))
                      for line in batch]
+        check_line_controls(len(batch), self.net_config['n_speakers'], speed, speaker_id, pitch_mul, pitch_add)
         ids_pad, lens_sorted, reverse_ids = text_collate_fn(batch_ids)
-        mel, dec_lens, *_ = self.infer(ids_pad, pace=speed, speaker=speaker_id, dur_tgt=dur_tgt, pitch_tgt=pitch_tgt,
-                                       energy_tgt=energy_tgt,
-                                       pitch_transform=self._ptrf(pitch_mul, pitch_add, pitch_transform),
-                                       max_duration=max_duration)
+        # row i of the padded batch is line sort_ids[i]: per-line controls go through the same sort (a scalar stays a scalar)
+        sort_ids = reverse_ids.argsort().tolist()
+        if alone is None:
+            alone = any(per_row(v) for v in (speed, speaker_id, pitch_mul, pitch_add))
+        mel, dec_lens, *_ = self.infer(ids_pad, alone=alone, pace=_take(speed, sort_ids), speaker=_take(speaker_id, sort_ids), dur_tgt=dur_tgt,
+                                       pitch_tgt=pitch_tgt, energy_tgt=energy_tgt, max_duration=max_duration,
+                                       **self._pitch_kw(_take(pitch_mul, sort_ids), _take(pitch_add, sort_ids), pitch_transform))
         return mel, dec_lens, reverse_ids
 
     @torch.inference_mode()
@@ -246,13 +302,15 @@ class FastPitch(_HipModule):
                           pitch_mul: float = 1., pitch_add: float = 0., max_duration=75):
         """`[ttmel_single(l) for l in lines]` as ONE ragged FastPitch call (infer(..., alone=True)): (mel [B, 80, T_max], dec_lens int64
         [B]) in HBM, rows in the order of `lines`; mel[b, :, :dec_lens[b]] equals ttmel_single(lines[b]) within fp32 summation order
-        (frames past dec_lens[b] are undefined).  What `FastPitch2Wave.tts(list, batch_size=1)` runs per group of lines."""
+        (frames past dec_lens[b] are undefined).  What `FastPitch2Wave.tts(list, batch_size=1)` runs per group of lines.  speed,
+        speaker_id, pitch_mul and pitch_add: scalars or one value per line (the rows keep the order of `lines`)."""
+        check_line_controls(len(lines), self.net_config['n_speakers'], speed, speaker_id, pitch_mul, pitch_add)
         batch_ids = [text.tokens_to_ids(self._tokenize(line, vowelizer), self.phon_to_id) for line in lines]
         ids = torch.zeros(len(batch_ids), max(len(i) for i in batch_ids), dtype=torch.int64)
         for b, i in enumerate(batch_ids):
             ids[b, :len(i)] = torch.as_tensor(i, dtype=torch.int64)
-        mel, dec_lens, *_ = self.infer(ids, pace=speed, speaker=speaker_id, pitch_transform=self._ptrf(pitch_mul, pitch_add, None),
-                                       max_duration=max_duration, alone=True)
+        mel, dec_lens, *_ = self.infer(ids, pace=speed, speaker=speaker_id, max_duration=max_duration, alone=True,
+                                       **self._pitch_kw(pitch_mul, pitch_add, None))
         return mel, dec_lens
 
     @torch.inference_mode()
@@ -267,15 +325,19 @@ class FastPitch(_HipModule):
 
     def ttmel(self, text_input: Union[str, List[str]], speed: float = 1, speaker_id: int = 0, batch_size: int = 1,
               vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.):
-        kw = dict(speed=speed, speaker_id=speaker_id, vowelizer=vowelizer, pitch_mul=pitch_mul, pitch_add=pitch_add)
+        """speed, speaker_id, pitch_mul and pitch_add: scalars, or for a list of lines one value per line (each follows its line)."""
+        kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
         if isinstance(text_input, str):
-            return self.ttmel_single(text_input, **kw)
+            return self.ttmel_single(text_input, vowelizer=vowelizer, **kw)
         assert isinstance(text_input, list)
+        check_line_controls(len(text_input), self.net_config['n_speakers'], **kw)
         if batch_size == 1:
-            return [self.ttmel_single(sample, **kw) for sample in text_input]
+            return [self.ttmel_single(sample, vowelizer=vowelizer, **{k: _at(v, i) for k, v in kw.items()})
+                    for i, sample in enumerate(text_input)]
         mel_list = []
         for k in range(0, len(text_input), batch_size):
-            mel_list += self.ttmel_batch(text_input[k:k + batch_size], **kw)
+            idx = range(k, min(k + batch_size, len(text_input)))
+            mel_list += self.ttmel_batch(text_input[k:k + batch_size], vowelizer=vowelizer, **{n: _take(v, idx) for n, v in kw.items()})
         return mel_list
 
 
@@ -310,30 +372,34 @@ class FastPitch2Wave(nn.Module):
             return wave[0].cpu(), mel_spec
         return wave[0].cpu()
 
+    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add):
+        """What tts_batch and tts_batch_device share: (wave [B, n_max], n_samples int64 [B], reverse_ids), rows in the collate order (longest
+        first).  Every control is a scalar or one value per line of `batch`; a per-line denoise strength goes through the same sort as
+        the lines, and a line whose strength is not > 0 keeps its vocoder output bit for bit."""
+        check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise)
+        mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
+                                                                    pitch_add)
+        wave = self.vocoder.engine().forward(mel, dec_lens)             # one ragged batched launch sequence
+        n = (dec_lens * self.vocoder.engine().hop)
+        denoise = _take(denoise, reverse_ids.argsort().tolist())
+        if any(d > 0 for d in denoise) if per_row(denoise) else denoise > 0:
+            wave = self.denoiser.forward_batch(wave, n, denoise)
+        return wave, n, reverse_ids
+
     @torch.inference_mode()
     def tts_batch_device(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0,
                          vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False):
         """`tts_batch` without the device->host copy: (wave [B, n_max] float32, n_samples int64 [B]), both in HBM,
         rows in the order of `batch` (zeros past n_samples[b]).  What the data-parallel gather (ttsamd.dp) and
         any GPU-side consumer take; `tts_batch` is this plus one D2H."""
-        mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
-                                                                    pitch_add)
-        wave = self.vocoder.engine().forward(mel, dec_lens)             # one ragged batched launch sequence
-        n = (dec_lens * self.vocoder.engine().hop)
-        if denoise > 0:
-            wave = self.denoiser.forward_batch(wave, n, denoise)
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add)
         rev = reverse_ids.to(wave.device)
         return wave.index_select(0, rev), n.index_select(0, rev)
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0, vowelizer=None,
                   pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False):
-        mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
-                                                                    pitch_add)
-        wave = self.vocoder.engine().forward(mel, dec_lens)             # one ragged batched launch sequence
-        n = (dec_lens * self.vocoder.engine().hop)
-        if denoise > 0:
-            wave = self.denoiser.forward_batch(wave, n, denoise)
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add)
         n = n.tolist()
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:347-350); so do we
@@ -343,21 +409,48 @@ class FastPitch2Wave(nn.Module):
             batch_size: int = 2, vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.,
             return_mel: bool = False) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:352-435): str -> Tensor[n_samples] (CPU);
-        list -> list of tensors, chunked by `batch_size`."""
-        kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, vowelizer=vowelizer, pitch_mul=pitch_mul,
-                  pitch_add=pitch_add, return_mel=return_mel)
+        list -> list of tensors, chunked by `batch_size`.
+        Mixed requests (not in the reference): for a list of lines, speed, denoise, speaker_id, pitch_mul and pitch_add each take a scalar
+        or a list with one value per line; every value follows its line through the chunking, the collate sort and the length-sorted
+        groups of the batch_size = 1 pipeline, and wave i answers line i with its own options.  With a list for speed, speaker_id, pitch_mul or pitch_add the rows of every batch
+        are computed as if alone (FastPitch.infer(alone=True)): requests are independent, so wave i equals tts_single(line i, its options)
+        within fp32 summation order at every batch_size; all scalars keep the reference's padded-batch arithmetic (a `denoise` list
+        on its own does too: the strength has no bearing on FastPitch)."""
+        kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, pitch_mul=pitch_mul, pitch_add=pitch_add)
         if isinstance(text_input, str):
-            return self.tts_single(text_input, **kw)
+            return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw)
         assert isinstance(text_input, list)
+        check_line_controls(len(text_input), self.model.net_config['n_speakers'], **kw)
         if (len(text_input) > batch_size and not return_mel and self.device.type == 'cuda'
                 and os.environ.get('TTSAMD_TTS_PIPELINE', '1') != '0'):
-            return self._tts_list_pipelined(text_input, batch_size, **kw)
+            return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw)
         if batch_size == 1:
-            return [self.tts_single(sample, **kw) for sample in text_input]
+            return [self.tts_single(sample, vowelizer=vowelizer, return_mel=return_mel, **{k: _at(v, i) for k, v in kw.items()})
+                    for i, sample in enumerate(text_input)]
         wav_list = []
         for k in range(0, len(text_input), batch_size):
-            wav_list += self.tts_batch(text_input[k:k + batch_size], **kw)
+            idx = range(k, min(k + batch_size, len(text_input)))
+            wav_list += self.tts_batch(text_input[k:k + batch_size], vowelizer=vowelizer, return_mel=return_mel,
+                                       **{n: _take(v, idx) for n, v in kw.items()})
         return wav_list
+
+    # the options of one request of tts_requests and what a request that leaves one out gets: tts()'s own defaults
+    REQUEST_DEFAULTS = dict(speed=1., denoise=0.005, speaker_id=0, pitch_mul=1., pitch_add=0.)
+
+    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None):
+        """A server's queue in one go: `requests` is a list of dicts with `text` and any of speed, denoise, speaker_id, pitch_mul, pitch_add
+        (the per-request options of the reference's app); returns one wave per request, in request order, from ONE `tts` call with the
+        options as per-line lists -- requests with different options share batches instead of one call per distinct option tuple."""
+        requests = list(requests)
+        for i, r in enumerate(requests):
+            extra = set(r) - set(self.REQUEST_DEFAULTS) - {'text'}
+            if 'text' not in r or not isinstance(r['text'], str) or extra:
+                raise ValueError(f'request {i}: needs a `text` string and takes {sorted(self.REQUEST_DEFAULTS)}'
+                                 + (f' (got {sorted(extra)})' if extra else ''))
+        if not requests:
+            return []
+        lists = {k: [r.get(k, d) for r in requests] for k, d in self.REQUEST_DEFAULTS.items()}
+        return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
     # ---- objective evaluation against recordings (not in the reference; ttsamd.engine.ObjectiveEngine, csrc/objective.hip) ----
     @staticmethod
@@ -475,6 +568,8 @@ class FastPitch2Wave(nn.Module):
             n_groups = (n_in + self._ALONE_GROUP - 1) // self._ALONE_GROUP
             group = (n_in + n_groups - 1) // n_groups
             text_input = [text_input[i] for i in order]
+            # per-line controls take the sort of their lines; from here on position p of every list belongs to text_input[p]
+            speed, denoise, speaker_id, pitch_mul, pitch_add = (_take(v, order) for v in (speed, denoise, speaker_id, pitch_mul, pitch_add))
 
         def flush(item):
             wave, n, done = item
@@ -483,27 +578,34 @@ class FastPitch2Wave(nn.Module):
                 wave.record_stream(s_cp)
                 out.extend(wave[j, :n[j]].cpu() for j in range(len(n)))      # blocks the host on THIS group's audio only
 
-        chunks = [text_input[k:k + batch_size] for k in range(0, len(text_input), batch_size)]
+        # chunks and groups as POSITIONS into text_input, so that the per-line controls are picked with the lines
+        # a per-line FastPitch control: every chunk's rows as if alone (a denoise list alone has no bearing on FastPitch and changes no mel)
+        mixed = any(per_row(v) for v in (speed, speaker_id, pitch_mul, pitch_add))
+        chunks = [list(range(k, min(k + batch_size, len(text_input)))) for k in range(0, len(text_input), batch_size)]
         groups = [chunks[g0:g0 + group] for g0 in range(0, len(chunks), group)]
         if alone_ok:
-            groups = [[chunks[i] for i in g] for g in self._alone_groups([len(ch[0]) for ch in chunks], group, self._ALONE_CHARS)]
+            groups = [[chunks[i] for i in g] for g in self._alone_groups([len(text_input[ch[0]]) for ch in chunks], group, self._ALONE_CHARS)]
         for grp in groups:
             mels, lens = [], []                                     # this group's utterances in input order
+            pos = [p for ch in grp for p in ch]                     # ... = these positions, in this order
             with torch.cuda.stream(s_fp):
                 alone = alone_ok and len(grp) > 1
                 if alone:
                     # the batch_size = 1 loop of this group's lines as ONE ragged FastPitch call whose rows are computed as if alone
                     # (ttsamd_fastpitch_set_batch_mode 1); the mel batch and its lengths go to the vocoder as they are
-                    mel_b, lens_d = self.model.ttmel_lines_alone([c[0] for c in grp], speed, speaker_id, vowelizer,
-                                                                 pitch_mul=pitch_mul, pitch_add=pitch_add)
+                    mel_b, lens_d = self.model.ttmel_lines_alone([text_input[p] for p in pos], _take(speed, pos), _take(speaker_id, pos),
+                                                                 vowelizer, pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos))
                     lens = lens_d.cpu().tolist()
-                for chunk in ([] if alone else grp):
+                for ch in ([] if alone else grp):
+                    chunk = [text_input[p] for p in ch]
                     if batch_size == 1:
-                        mel = self.model.ttmel_single(chunk[0], speed, speaker_id, vowelizer, pitch_mul=pitch_mul, pitch_add=pitch_add)
+                        mel = self.model.ttmel_single(chunk[0], _at(speed, ch[0]), _at(speaker_id, ch[0]), vowelizer,
+                                                      pitch_mul=_at(pitch_mul, ch[0]), pitch_add=_at(pitch_add, ch[0]))
                         mels.append(mel)
                         lens.append(int(mel.shape[-1]))
                     else:
-                        mel, dec_lens, rev = self.model._ttmel_batch_padded(chunk, speed, speaker_id, vowelizer, pitch_mul, pitch_add)
+                        mel, dec_lens, rev = self.model._ttmel_batch_padded(chunk, _take(speed, ch), _take(speaker_id, ch), vowelizer,
+                                                                            _take(pitch_mul, ch), _take(pitch_add, ch), alone=mixed)
                         dl = dec_lens.cpu().tolist()                # (FastPitch has synchronised on these lengths already)
                         for j in rev.tolist():
                             mels.append(mel[j, :, :dl[j]])
@@ -524,8 +626,13 @@ class FastPitch2Wave(nn.Module):
                 lens_d.record_stream(s_hg)
                 wave = eng.forward(mel_b, lens_d)
                 n_host = [t * hop for t in lens]
-                if denoise > 0:
-                    wave = self.denoiser.forward_batch(wave, lens_d * hop, denoise, nsamples_min=min(n_host))
+                dn = _take(denoise, pos)                            # rows of `wave` are the positions `pos`, in that order
+                if per_row(dn):
+                    n_dn = [n for n, d in zip(n_host, dn) if d > 0]
+                    if n_dn:
+                        wave = self.denoiser.forward_batch(wave, lens_d * hop, dn, nsamples_min=min(n_dn))
+                elif dn > 0:
+                    wave = self.denoiser.forward_batch(wave, lens_d * hop, dn, nsamples_min=min(n_host))
                 done = torch.cuda.Event()
                 done.record(s_hg)
             if pending is not None:

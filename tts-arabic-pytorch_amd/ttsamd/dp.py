@@ -358,7 +358,11 @@ def tts_sharded(model, texts, batch_size=32, dst=0, dp=None, **tts_kwargs):
     rank `dst`, which does ONE device->host copy per chunk and returns the waves in the original order
     (other ranks: None).  Models without `tts_batch_device` (test stubs) go through `model.tts` + a host pad.
     NB padded-batch FastPitch results depend on batch composition: an utterance's wave equals
-    the single-GPU result for the same sub-batch, not for a different batching."""
+    the single-GPU result for the same sub-batch, not for a different batching.
+    Options are scalars here: per-line lists (FastPitch2Wave.tts) are refused -- the shards reorder the lines."""
+    for k, v in tts_kwargs.items():
+        if isinstance(v, (list, tuple)) or getattr(v, 'ndim', 0) > 0:
+            raise ValueError(f'tts_sharded: {k} is given per line; the data-parallel path takes scalar options only')
     dpx = dp if dp is not None else default(getattr(model, 'device', None))
     world, rank = dpx.world, dpx.rank
     order = sorted(range(len(texts)), key=lambda i: -len(texts[i]))

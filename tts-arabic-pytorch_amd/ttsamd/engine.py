@@ -59,6 +59,46 @@ def _check_ids(t, n, what):
             raise IndexError(f'{what}: index out of range [0, {n}) (got min {lo}, max {hi})')
 
 
+# ---- mixed requests in one batch: a control (speaker, pace, pitch_mul, pitch_add, denoise strength) is one scalar for the call or one
+# value per row.  The library trusts device values (it only clamps), so everything is checked here, on the host, before the upload.
+def per_row(value):
+    """True when a control is given per row (list / tuple / array / tensor with a dimension) rather than as one scalar."""
+    if isinstance(value, (torch.Tensor, np.ndarray)):
+        return value.ndim > 0
+    return isinstance(value, (list, tuple))
+
+
+def row_values(value, n, what):
+    """A per-row control as a host list of n Python numbers; ValueError when its length is not n."""
+    if isinstance(value, torch.Tensor):
+        value = value.detach().cpu()
+    vals = np.asarray(value).reshape(-1).tolist() if isinstance(value, (torch.Tensor, np.ndarray)) else list(value)
+    if len(vals) != n:
+        raise ValueError(f'{what}: {len(vals)} values for {n} rows')
+    return vals
+
+
+def check_speakers(vals, n_speakers, what='speaker'):
+    """IndexError (as nn.Embedding raises) for a speaker outside [0, n_speakers); a single-speaker model ignores the index."""
+    for v in vals:
+        if isinstance(v, float) and not v.is_integer():
+            raise ValueError(f'{what}: {v!r} is not an integer')
+        if n_speakers > 1 and not 0 <= int(v) < n_speakers:
+            raise IndexError(f'{what} {int(v)} out of range [0, {n_speakers})')
+
+
+def check_finite(vals, what, positive=False):
+    """ValueError for a value that is not finite or, with `positive`, not > 0 (a pace)."""
+    for v in vals:
+        v = float(v)
+        if not np.isfinite(v) or (positive and not v > 0.0):
+            raise ValueError(f'{what}: {v!r} is not ' + ('finite and > 0' if positive else 'finite'))
+
+
+def _rows_f32(vals, device):
+    return None if vals is None else torch.tensor([float(v) for v in vals], dtype=torch.float32).to(device)
+
+
 class _Workspace:
     def __init__(self):
         self.buf = None
@@ -177,13 +217,33 @@ class FastPitchEngine:
         `lens_hook(dec_lens_device) -> host ints [B]` replaces the one device->host read of the call (the
         data-parallel path all-gathers every rank's lengths in that same synchronisation, ttsamd.dp).
         `alone=True`: every row as if it were the only utterance of the call (ttsamd_fastpitch_set_batch_mode 1) -- row b equals
-        infer(ids[b:b+1, :len_b]) within fp32 summation order: the reference's batch_size = 1 loop as one ragged call."""
-        if bool(alone) != self._alone:
-            L.check(self.lib.ttsamd_fastpitch_set_batch_mode(self.handle, int(bool(alone))), 'fastpitch_set_batch_mode')
-            self._alone = bool(alone)
+        infer(ids[b:b+1, :len_b]) within fp32 summation order: the reference's batch_size = 1 loop as one ragged call.
+        Mixed requests: `pace`, `speaker`, `pitch_mul` and `pitch_add` each take a scalar or B values (list / array / tensor), checked
+        on the host (length B, speaker in range, pace finite and > 0: ValueError / IndexError) before they are uploaded.  With any
+        per-row control the call runs ttsamd_fastpitch_encode_rows / _decode_rows -- row b's bits are those of the scalar call with row
+        b's values -- and `alone` goes down as the per-call flag: the handle's mode is left alone.  All scalars: the route above."""
         dev = self.device
         ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int64).contiguous()
         B, Lt0 = ids.shape
+        rows = {k: row_values(v, B, k) if per_row(v) else None
+                for k, v in (('pace', pace), ('speaker', speaker), ('pitch_mul', pitch_mul), ('pitch_add', pitch_add))}
+        mixed = any(v is not None for v in rows.values())
+        if mixed:
+            if rows['speaker'] is not None:
+                check_speakers(rows['speaker'], int(self.config['n_speakers']))
+            if rows['pace'] is not None:
+                check_finite(rows['pace'], 'pace', positive=True)
+            for k in ('pitch_mul', 'pitch_add'):
+                if rows[k] is not None:
+                    check_finite(rows[k], k)
+            spk_rows = None if rows['speaker'] is None else torch.tensor([int(v) for v in rows['speaker']], dtype=torch.int32).to(dev)
+            pace_rows, mul_rows, add_rows = (_rows_f32(rows[k], dev) for k in ('pace', 'pitch_mul', 'pitch_add'))
+            speaker, pace = (0 if spk_rows is not None else speaker), (1.0 if pace_rows is not None else pace)
+            pitch_mul, pitch_add = (1.0 if mul_rows is not None else pitch_mul), (0.0 if add_rows is not None else pitch_add)
+            flags = int(bool(alone))
+        elif bool(alone) != self._alone:
+            L.check(self.lib.ttsamd_fastpitch_set_batch_mode(self.handle, int(bool(alone))), 'fastpitch_set_batch_mode')
+            self._alone = bool(alone)
         d = self.d_model
         dur_tgt, pitch_tgt, energy_tgt = _f32(dur_tgt, dev), _f32(pitch_tgt, dev), _f32(energy_tgt, dev)
         # Batches: the DECODER's frame rows padded to a multiple of 4 (16 bytes).  The conv engine's fast paths -- the Winograd F(4,3) kernel,
@@ -204,11 +264,14 @@ class FastPitchEngine:
         with torch.cuda.device(dev):
             nb = lib.ttsamd_fastpitch_encode_workspace_bytes(self.handle, B, Lt)
             ws = self.ws.get(nb, dev)
-            L.check(lib.ttsamd_fastpitch_encode(self.handle, _ptr(ids), B, Lt, int(speaker), float(pace), _ptr(dur_tgt),
-                                                _ptr(pitch_tgt), _ptr(energy_tgt), float(pitch_mul), float(pitch_add),
-                                                float(max_duration), _ptr(enc), _ptr(dur_pred), _ptr(pitch_pred),
-                                                _ptr(energy_pred), _ptr(reps), _ptr(dec_lens), _ptr(ws), nb, _stream()),
-                    'fastpitch_encode')
+            args = (self.handle, _ptr(ids), B, Lt, int(speaker), float(pace), _ptr(dur_tgt), _ptr(pitch_tgt), _ptr(energy_tgt),
+                    float(pitch_mul), float(pitch_add), float(max_duration), _ptr(enc), _ptr(dur_pred), _ptr(pitch_pred),
+                    _ptr(energy_pred), _ptr(reps), _ptr(dec_lens), _ptr(ws), nb)
+            if mixed:
+                L.check(lib.ttsamd_fastpitch_encode_rows(*args, _ptr(spk_rows), _ptr(pace_rows), _ptr(mul_rows), _ptr(add_rows), flags,
+                                                         _stream()), 'fastpitch_encode_rows')
+            else:
+                L.check(lib.ttsamd_fastpitch_encode(*args, _stream()), 'fastpitch_encode')
             if lens_hook is None:
                 t_max0 = int(dec_lens.max().item())     # the reference syncs here too (model.py:76)
             else:
@@ -222,8 +285,11 @@ class FastPitchEngine:
                         'length_regulate')
                 nb = lib.ttsamd_fastpitch_decode_workspace_bytes(self.handle, B, t_max)
                 ws = self.ws.get(nb, dev)
-                L.check(lib.ttsamd_fastpitch_decode(self.handle, _ptr(x), _ptr(dec_lens), B, t_max, _ptr(mel), _ptr(ws), nb,
-                                                    _stream()), 'fastpitch_decode')
+                args = (self.handle, _ptr(x), _ptr(dec_lens), B, t_max, _ptr(mel), _ptr(ws), nb)
+                if mixed:
+                    L.check(lib.ttsamd_fastpitch_decode_rows(*args, flags, _stream()), 'fastpitch_decode_rows')
+                else:
+                    L.check(lib.ttsamd_fastpitch_decode(*args, _stream()), 'fastpitch_decode')
         if t_max != t_max0:
             mel = mel[:, :, :t_max0]
             idx = None if idx is None else idx[:, :t_max0]
@@ -262,16 +328,26 @@ class DenoiserEngine:
         return out.reshape(1, 513, 1)
 
     def denoise(self, wave, nsamples, bias_spec, strength):
-        """wave [B, n_max] (modified in place and returned), nsamples int64 [B] on the device."""
+        """wave [B, n_max] (modified in place and returned), nsamples int64 [B] on the device.  `strength`: a scalar, or B values -- then
+        a row whose strength is > 0 gets the bits of the scalar call with that value and any other row is left untouched."""
         assert wave.is_contiguous() and wave.dtype == torch.float32
         B, n_max = wave.shape
+        rows = None
+        if per_row(strength):
+            vals = row_values(strength, B, 'denoise strength')
+            check_finite(vals, 'denoise strength')
+            rows = _rows_f32(vals, self.device)
         nsamples = nsamples.to(device=self.device, dtype=torch.int64).contiguous()
         bias = _f32(bias_spec, self.device).reshape(-1)
         with torch.cuda.device(self.device):
             nb = self.lib.ttsamd_denoiser_workspace_bytes(B, n_max)
             ws = self.ws.get(nb, self.device)
-            L.check(self.lib.ttsamd_denoise(self.handle, _ptr(wave), n_max, _ptr(nsamples), B, n_max, _ptr(bias),
-                                            float(strength), _ptr(ws), nb, _stream()), 'denoise')
+            if rows is not None:
+                L.check(self.lib.ttsamd_denoise_rows(self.handle, _ptr(wave), n_max, _ptr(nsamples), B, n_max, _ptr(bias),
+                                                     _ptr(rows), _ptr(ws), nb, _stream()), 'denoise_rows')
+            else:
+                L.check(self.lib.ttsamd_denoise(self.handle, _ptr(wave), n_max, _ptr(nsamples), B, n_max, _ptr(bias),
+                                                float(strength), _ptr(ws), nb, _stream()), 'denoise')
         return wave
 
 
@@ -363,10 +439,16 @@ class VocosEngine:
 
     def forward(self, mel, lens=None, denoise=0.0):
         """mel [B,n_mels,T] on the GPU, lens int64 [B] or None -> wave [B, 256*T] (zeros past 256*lens[b]); with the "center" head ('24k':
-        torch.istft(center=True)) [B, 256*(T-1)], zeros past 256*(lens[b]-1)."""
+        torch.istft(center=True)) [B, 256*(T-1)], zeros past 256*(lens[b]-1).  `denoise`: a scalar or B values, one per row (row b then
+        has the bits of the scalar call with its value)."""
         mel = _f32(mel, self.device)
         B, M, T0 = mel.shape
         assert M == self.n_mels
+        rows = None
+        if per_row(denoise):
+            vals = row_values(denoise, B, 'denoise')
+            check_finite(vals, 'denoise')
+            rows = _rows_f32(vals, self.device)
         if lens is None:
             lens = torch.full((B,), T0, dtype=torch.int64, device=self.device)
         lens = lens.to(device=self.device, dtype=torch.int64).contiguous()
@@ -379,12 +461,16 @@ class VocosEngine:
         if T != T0:
             mel = torch.nn.functional.pad(mel, (0, T - T0))
         wave = torch.zeros(B, self.hop * T, dtype=torch.float32, device=self.device)
-        bias = self.bias_vec().reshape(-1) if denoise != 0 else None
+        bias = self.bias_vec().reshape(-1) if rows is not None or denoise != 0 else None
         with torch.cuda.device(self.device):
             nb = self.lib.ttsamd_vocos_workspace_bytes(self.handle, B, T)
             ws = self.ws.get(nb, self.device)
-            L.check(self.lib.ttsamd_vocos_forward(self.handle, _ptr(mel), _ptr(lens), B, T, float(denoise), _ptr(bias),
-                                                  _ptr(wave), _ptr(ws), nb, _stream()), 'vocos_forward')
+            if rows is not None:
+                L.check(self.lib.ttsamd_vocos_forward_rows(self.handle, _ptr(mel), _ptr(lens), B, T, _ptr(rows), _ptr(bias),
+                                                           _ptr(wave), _ptr(ws), nb, _stream()), 'vocos_forward_rows')
+            else:
+                L.check(self.lib.ttsamd_vocos_forward(self.handle, _ptr(mel), _ptr(lens), B, T, float(denoise), _ptr(bias),
+                                                      _ptr(wave), _ptr(ws), nb, _stream()), 'vocos_forward')
         return wave if wave.shape[1] == n0 else wave[:, :n0]
 
 

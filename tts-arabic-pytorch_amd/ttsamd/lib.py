@@ -83,16 +83,22 @@ SYMBOLS = {
     'ttsamd_length_regulate': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     'ttsamd_fastpitch_decode': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
     'ttsamd_fastpitch_set_batch_mode': (_I32, [_P, _I32]),
+    # ... with per-row speaker / pace / pitch_mul / pitch_add arrays (device, each may be NULL) and flags (bit 0: rows as if alone)
+    'ttsamd_fastpitch_encode_rows': (_I32, [_P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _F, _F, _F,
+                                            _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _I32, _P]),
+    'ttsamd_fastpitch_decode_rows': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _I64, _I32, _P]),
     'ttsamd_denoiser_create': (_I32, [C.POINTER(_P)]),
     'ttsamd_denoiser_destroy': (_I32, [_P]),
     'ttsamd_denoiser_workspace_bytes': (_I64, [_I32, _I32]),
     'ttsamd_denoiser_bias_spec': (_I32, [_P, _P, _P, _I32, _P, _P, _I64, _P]),
     'ttsamd_denoise': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _F, _P, _I64, _P]),
+    'ttsamd_denoise_rows': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _P]),
     'ttsamd_vocos_create': (_I32, [C.POINTER(Tensor), _I32, _I32, _I32, _I32, _I32, C.POINTER(_P)]),
     'ttsamd_vocos_destroy': (_I32, [_P]),
     'ttsamd_vocos_workspace_bytes': (_I64, [_P, _I32, _I32]),
     'ttsamd_vocos_bias_vec': (_I32, [_P, _P, _P, _I64, _P]),
     'ttsamd_vocos_forward': (_I32, [_P, _P, _P, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
+    'ttsamd_vocos_forward_rows': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_vocos_set_padding': (_I32, [_P, _I32]),
     'ttsamd_melspec_create': (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _F, C.POINTER(_P)]),
     'ttsamd_melspec_destroy': (_I32, [_P]),

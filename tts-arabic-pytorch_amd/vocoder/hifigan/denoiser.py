@@ -2,7 +2,7 @@
 bias spectrum.  STFT / spectral gain / ISTFT run in libttsamd.so (csrc/denoiser.hip)."""
 import torch
 
-from ttsamd.engine import DenoiserEngine
+from ttsamd.engine import DenoiserEngine, per_row, row_values
 from vocoder.hifigan.models import _HipModule
 
 
@@ -48,7 +48,16 @@ class Denoiser(_HipModule):
     def forward_batch(self, wave, nsamples, strength, nsamples_min=None):
         """Ragged batch (extension): wave [B, n_max] float32 on the GPU, nsamples int64 [B].  `nsamples_min`: the smallest
         length if the caller has it on the host already (FastPitch synchronises on the lengths anyway) -- reading it from the
-        device here would stall the host until the vocoder has finished, which is what the pipelined `tts` list path overlaps."""
+        device here would stall the host until the vocoder has finished, which is what the pipelined `tts` list path overlaps.
+        `strength`: a scalar, or one value per row -- a row whose strength is not > 0 is then left untouched bit for bit (what `if denoise
+        > 0` around a call does for a whole batch) and does not count for the length check."""
+        if per_row(strength):
+            strength = row_values(strength, wave.shape[0], 'denoise strength')
+            on = [float(v) > 0 for v in strength]
+            if not any(on):
+                return wave
+            if nsamples_min is None:
+                nsamples_min = int(nsamples[torch.tensor(on, device=nsamples.device)].min())
         if nsamples_min is None and wave.shape[0]:
             nsamples_min = int(nsamples.min())
         if wave.shape[0] and nsamples_min <= 512:
