@@ -429,6 +429,45 @@ int32_t ttsamd_mas(const float* attn, int32_t is_log, const int64_t* in_lens, co
 int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
                              float* out, void* stream);
 
+/* ---- The alignment prior and the alignment scores of the reference's aligner training, forward only (BetaBinomialInterpolator and
+ *      beta_binomial_prior_distribution of fastpitch/data_function.py:45-78; AttentionCTCLoss and AttentionBinarizationLoss of
+ *      fastpitch/attn_loss_function.py; csrc/attn_loss.hip).  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.  Every
+ *      pointer is device memory (ttsamd_attn_prior_tables: host), lengths are int64 [batch] and are clamped to the padded size.  No call
+ *      reads anything back to the host.  ttsamd_set_precision does not reach these entries: everything is float64 up to the stored value.
+ *      No gradient is built.
+ *
+ * The prior of row b: its [mel_lens[b], in_lens[b]] corner of out [B][n_frames][n_tokens] fp32, ZERO outside it (as TTSCollate pads).
+ *   mode 0, exact: out[i-1][k] = betabinom(n = P, a = scaling i, b = scaling (M + 1 - i)).pmf(k), k = 0 .. P - 1, with P = in_lens[b] and
+ *     M = mel_lens[b] (n = P, not P - 1: a row does not add up to 1; the reference's behaviour, kept).
+ *   mode 1, interpolated: what BetaBinomialInterpolator()(w = mel_len, h = in_len) returns, the prior the checkpoints were trained with:
+ *     bw = max(1, rint((w + 1) / 100)) 100 and bh = max(1, rint((h + 1) / 20)) 20 (halves to even, as np.round), the bank
+ *     beta_binomial_prior_distribution(phoneme_count = bw, mel_count = bh) transposed (the reference passes the rounded MEL length as the
+ *     phoneme count; reproduced), sampled as scipy.ndimage.zoom(bank, (w / bw, h / bh), order=1) does: cell (o, p) at x = o (bw - 1) /
+ *     (w - 1), y = p (bh - 1) / (h - 1) (0 when the extent is 1), bilinear between floor and floor + 1 clamped to the last index, float64.
+ *   mode | TTSAMD_ATTN_PRIOR_F64: out is float64 [B][n_frames][n_tokens] (the values before the rounding to fp32).
+ * Only scaling == 1.0 is built (anything else: TTSAMD_EINVAL): with integer a, b the pmf is exp of nine entries of lf[n] = log n!, a table
+ * built once per device on the host in float64 (std::lgamma) and uploaded at the first call that needs it.  ttsamd_attn_prior_tables
+ * writes lf[0 .. n) to HOST memory: the table, for checking it without a device. */
+#define TTSAMD_ATTN_PRIOR_F64 2
+int32_t ttsamd_attn_prior(const int64_t* in_lens, const int64_t* mel_lens, int32_t batch, int32_t n_tokens, int32_t n_frames, int32_t mode,
+                          double scaling, void* out, void* stream);
+int32_t ttsamd_attn_prior_tables(int32_t n, double* lf);
+/* Forward-sum loss per row: nll [B] float64 = the CTC negative log-likelihood of the targets 0 .. in_lens[b] - 1 (in order, blanks between)
+ * over the frames t < out_lens[b], frame t's distribution being [blank_logprob, attn_logprob[b][t][:in_lens[b]]] log-softmaxed (tokens past
+ * in_lens[b] masked).  attn_logprob [B][n_frames][n_tokens] fp32; all arithmetic is float64 in the log domain.  out_lens[b] < in_lens[b] (no
+ * path; also 0 frames for some tokens): +inf.  in_lens[b] == 0: 0.  AttentionCTCLoss's scalar is the mean over rows of (nll, 0 where
+ * infinite) / max(in_lens, 1).  Two launches whatever the length: the per-frame normalisers into `workspace` (8-byte aligned,
+ * ttsamd_attn_ctc_loss_workspace_bytes() bytes; -1 for arguments the call refuses), then one block per row.  n_tokens >
+ * TTSAMD_MAS_MAX_TOKENS is TTSAMD_EINVAL. */
+int64_t ttsamd_attn_ctc_loss_workspace_bytes(int32_t batch, int32_t n_frames, int32_t n_tokens);
+int32_t ttsamd_attn_ctc_loss(const float* attn_logprob, const int64_t* in_lens, const int64_t* out_lens, int32_t batch, int32_t n_frames,
+                             int32_t n_tokens, double blank_logprob, double* nll, void* workspace, int64_t workspace_bytes, void* stream);
+/* Binarization loss per row: sum_log [B] = the sum of log(max(attn_soft, eps)) over the cells with attn_hard == 1, count [B] = how many
+ * there are; attn_hard, attn_soft [B][n_frames][n_tokens] fp32, the sums float64 in a fixed order (the same bits run to run).
+ * AttentionBinarizationLoss's scalar is -sum(sum_log) / sum(count). */
+int32_t ttsamd_attn_bin_loss(const float* attn_hard, const float* attn_soft, int32_t batch, int32_t n_frames, int32_t n_tokens, double eps,
+                             double* sum_log, double* count, void* stream);
+
 /* ---- pYIN pitch tracking, wave -> (f0, voiced_flag, voiced_prob) per frame (librosa.pyin as the reference calls it in
  *      scripts/extract_f0.py:34-39 and fastpitch/data_function.py:81-114; csrc/pyin.hip).  New symbols only, added WITHOUT a bump:
  *      TTSAMD_ABI_VERSION stays 8.  Two launches per call whatever the length: a frame kernel (difference function, cumulative-mean

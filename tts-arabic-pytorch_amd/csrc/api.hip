@@ -111,6 +111,11 @@ int32_t aligner_forward(const Aligner*, const int64_t*, const int64_t*, const fl
 int64_t mas_workspace_bytes(int32_t, int32_t, int32_t);
 int32_t mas(const float*, int32_t, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, float*, float*, void*, int64_t, hipStream_t);
 int32_t average_pitch(const float*, const float*, int32_t, int32_t, int32_t, int32_t, float*, hipStream_t);
+int32_t attn_prior(const int64_t*, const int64_t*, int32_t, int32_t, int32_t, int32_t, double, void*, hipStream_t);
+int32_t attn_prior_tables_host(int32_t, double*);
+int64_t attn_ctc_workspace_bytes(int32_t, int32_t, int32_t);
+int32_t attn_ctc_loss(const float*, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, double, double*, void*, int64_t, hipStream_t);
+int32_t attn_bin_loss(const float*, const float*, int32_t, int32_t, int32_t, double, double*, double*, hipStream_t);
 struct Pyin;
 int32_t pyin_tables_host(const ttsamd_pyin_cfg*, int32_t*, double*, double*, double*, double*, float*, float*);
 int32_t pyin_create(const ttsamd_pyin_cfg*, Pyin**);
@@ -513,6 +518,23 @@ int64_t ttsamd_mas_workspace_bytes(int32_t batch, int32_t n_frames, int32_t n_to
 int32_t ttsamd_mas(const float* attn, int32_t is_log, const int64_t* in_lens, const int64_t* out_lens, int32_t batch, int32_t n_frames,
                    int32_t n_tokens, float* dur, float* attn_hard, void* workspace, int64_t workspace_bytes, void* stream) {
     return mas(attn, is_log, in_lens, out_lens, batch, n_frames, n_tokens, dur, attn_hard, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int32_t ttsamd_attn_prior(const int64_t* in_lens, const int64_t* mel_lens, int32_t batch, int32_t n_tokens, int32_t n_frames, int32_t mode,
+                          double scaling, void* out, void* stream) {
+    return attn_prior(in_lens, mel_lens, batch, n_tokens, n_frames, mode, scaling, out, (hipStream_t)stream);
+}
+int32_t ttsamd_attn_prior_tables(int32_t n, double* lf) { return attn_prior_tables_host(n, lf); }
+int64_t ttsamd_attn_ctc_loss_workspace_bytes(int32_t batch, int32_t n_frames, int32_t n_tokens) {
+    return attn_ctc_workspace_bytes(batch, n_frames, n_tokens);
+}
+int32_t ttsamd_attn_ctc_loss(const float* attn_logprob, const int64_t* in_lens, const int64_t* out_lens, int32_t batch, int32_t n_frames,
+                             int32_t n_tokens, double blank_logprob, double* nll, void* workspace, int64_t workspace_bytes, void* stream) {
+    return attn_ctc_loss(attn_logprob, in_lens, out_lens, batch, n_frames, n_tokens, blank_logprob, nll, workspace, workspace_bytes,
+                         (hipStream_t)stream);
+}
+int32_t ttsamd_attn_bin_loss(const float* attn_hard, const float* attn_soft, int32_t batch, int32_t n_frames, int32_t n_tokens, double eps,
+                             double* sum_log, double* count, void* stream) {
+    return attn_bin_loss(attn_hard, attn_soft, batch, n_frames, n_tokens, eps, sum_log, count, (hipStream_t)stream);
 }
 int32_t ttsamd_pyin_tables(const ttsamd_pyin_cfg* cfg, int32_t* dims, double* beta, double* expn, double* norm, double* trans,
                            float* logtrans, float* f0) {

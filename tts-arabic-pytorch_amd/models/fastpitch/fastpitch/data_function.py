@@ -1,5 +1,7 @@
-"""Drop-in for the pitch part of the reference's models/fastpitch/fastpitch/data_function.py (:81-122): `estimate_pitch` and
-`normalize_pitch` with the reference's signatures.  The track comes from utils.pitch.pyin (csrc/pyin.hip) with the reference's
+"""Drop-in for the reference's models/fastpitch/fastpitch/data_function.py: the alignment prior (:45-78), `BetaBinomialInterpolator` and
+`beta_binomial_prior_distribution`, computed by ttsamd_attn_prior (csrc/attn_loss.hip) in float64 on the device and copied back, float64 on
+the CPU as the reference returns them (a batch of priors that stays on the device: ttsamd.engine.attention_prior); and the pitch part
+(:81-122), `estimate_pitch` and `normalize_pitch`, with the reference's signatures.  The track comes from utils.pitch.pyin (csrc/pyin.hip) with the reference's
 settings: C2..C7, frame_length 1024, hop 256, 22 050 Hz.  The reference loads the file with librosa.load, which resamples to 22 050 Hz;
 there is no resampler here, so a file at another rate raises.  No CPU fallback."""
 import numpy as np
@@ -11,6 +13,41 @@ from utils.audio import load_wav
 from utils.pitch import note_to_hz, pyin
 
 SAMPLE_RATE = 22050
+
+
+def _prior(in_len, mel_len, mode, scaling=1.0):
+    from ttsamd.engine import attention_prior
+    return attention_prior([int(in_len)], [int(mel_len)], n_tokens=int(in_len), n_frames=int(mel_len), mode=mode, scaling=scaling,
+                           dtype=torch.float64)[0].cpu()
+
+
+def beta_binomial_prior_distribution(phoneme_count, mel_count, scaling=1.0):
+    """-> float64 tensor [mel_count, phoneme_count] on the CPU: row i - 1 is betabinom(n = phoneme_count, a = scaling i, b = scaling
+    (mel_count + 1 - i)).pmf(0 .. phoneme_count - 1).  n is phoneme_count, not phoneme_count - 1, so a row does not add up to 1: the
+    reference's behaviour.  Only scaling = 1 is built."""
+    return _prior(phoneme_count, mel_count, 'exact', scaling)
+
+
+class BetaBinomialInterpolator:
+    """The reference's prior bank: the exact prior of sizes rounded to 100 frames / 20 tokens, resized to the sizes asked for with
+    scipy.ndimage.zoom(order=1).  Here nothing is cached or resized: every cell is computed where it is asked for, with the same
+    arithmetic (the four bank values around it, interpolated in float64)."""
+
+    def __init__(self, round_mel_len_to=100, round_text_len_to=20):
+        if (round_mel_len_to, round_text_len_to) != (100, 20):
+            raise TtsAmdError(f'BetaBinomialInterpolator: rounding to {round_mel_len_to} frames / {round_text_len_to} tokens; 100 / 20, '
+                              'the values every caller of the reference uses, are built')
+        self.round_mel_len_to = round_mel_len_to
+        self.round_text_len_to = round_text_len_to
+
+    def round(self, val, to):
+        return max(1, int(np.round((val + 1) / to))) * to
+
+    def __call__(self, w, h):
+        """w = mel length, h = text length -> float64 numpy [w, h]"""
+        ret = _prior(h, w, 'interpolated').numpy()
+        assert ret.shape == (w, h), ret.shape
+        return ret
 
 
 def normalize_pitch(pitch, mean, std):

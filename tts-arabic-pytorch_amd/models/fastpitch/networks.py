@@ -20,6 +20,9 @@ import torch.nn as nn
 import text
 from ttsamd.engine import ALIGNER_KEYS, OBJECTIVE_KEYS, AlignerEngine, FastPitchEngine, ObjectiveEngine
 from ttsamd.engine import average_pitch as _average_pitch
+from ttsamd.engine import binarization_loss as _binarization_loss
+from ttsamd.engine import forward_sum_loss as _forward_sum_loss
+from ttsamd.engine import mas as _mas
 from ttsamd.engine import check_finite, check_speakers, per_row, row_values
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
@@ -66,6 +69,9 @@ def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1
 
 # what FastPitch.align returns: dur_tgt [B, L], pitch_tgt / energy_tgt [B, 1, L] or None, the attention maps [B, 1, T, L] or None
 Alignment = namedtuple('Alignment', ['dur_tgt', 'pitch_tgt', 'energy_tgt', 'attn_soft', 'attn_hard', 'attn_logprob'])
+# what FastPitch.alignment_score returns: per row the forward-sum cost per token and the binarization cost per frame [B] float64, the
+# durations [B, L], and the two batch scalars as the reference's AttentionCTCLoss / AttentionBinarizationLoss report them
+AlignmentScore = namedtuple('AlignmentScore', ['forward_sum', 'binarization', 'dur_tgt', 'ctc_loss', 'bin_loss'])
 
 
 def _attention_tensors(model_sd):
@@ -138,15 +144,8 @@ class FastPitch(_HipModule):
             self._aligners[str(dev)] = AlignerEngine(sd, self.net_config, device=dev)
         return self._aligners[str(dev)]
 
-    @torch.inference_mode()
-    def align(self, ids_or_text, mel, mel_lens=None, attn_prior=None, pitch=None, energy=None, return_attn=False):
-        """Forced alignment of a recording with its text, as the reference's training forward does it (model.py:298-318,331-332): the
-        checkpoint's ConvAttention scores every (frame, token) pair, monotonic alignment search picks the best monotonic path, and a token's
-        duration is the number of frames the path gives it.  ids_or_text: int64 ids [B, L] zero-padded at the end, or one utterance / a
-        list of utterances as text (tokenised like ttmel; rows keep the order given).  mel [B, n_mel, T] (+ mel_lens [B], None: T frames
-        each); attn_prior [B, T, L] or None; pitch [B, 1, T] / [B, T] and energy [B, T], frame-level tracks to average per token.
-        -> Alignment(dur_tgt [B, L], pitch_tgt [B, 1, L] | None, energy_tgt [B, 1, L] = log(1 + mean) | None, attn_soft, attn_hard,
-        attn_logprob [B, 1, T, L] with return_attn, else None); dur_tgt, pitch_tgt and energy_tgt feed infer() as they are."""
+    def _align_ids(self, ids_or_text):
+        """ids int64 [B, L] as they are; one utterance or a list of utterances as text: tokenised like ttmel and zero-padded at the end"""
         if isinstance(ids_or_text, str):
             ids_or_text = [ids_or_text]
         if isinstance(ids_or_text, (list, tuple)) and len(ids_or_text) and isinstance(ids_or_text[0], str):
@@ -154,8 +153,20 @@ class FastPitch(_HipModule):
             ids = torch.full((len(rows), max(len(r) for r in rows)), self.net_config['padding_idx'], dtype=torch.int64)
             for b, r in enumerate(rows):
                 ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.int64)
-        else:
-            ids = torch.as_tensor(ids_or_text).long()
+            return ids
+        return torch.as_tensor(ids_or_text).long()
+
+    @torch.inference_mode()
+    def align(self, ids_or_text, mel, mel_lens=None, attn_prior=None, pitch=None, energy=None, return_attn=False):
+        """Forced alignment of a recording with its text, as the reference's training forward does it (model.py:298-318,331-332): the
+        checkpoint's ConvAttention scores every (frame, token) pair, monotonic alignment search picks the best monotonic path, and a token's
+        duration is the number of frames the path gives it.  ids_or_text: int64 ids [B, L] zero-padded at the end, or one utterance / a
+        list of utterances as text (tokenised like ttmel; rows keep the order given).  mel [B, n_mel, T] (+ mel_lens [B], None: T frames
+        each); attn_prior [B, T, L], None, or 'interpolated' / 'exact': the beta-binomial prior of the rows' own lengths, built on the device
+        ('interpolated' is what the reference's data loader hands the model in training); pitch [B, 1, T] / [B, T] and energy [B, T], frame-level tracks to average per token.
+        -> Alignment(dur_tgt [B, L], pitch_tgt [B, 1, L] | None, energy_tgt [B, 1, L] = log(1 + mean) | None, attn_soft, attn_hard,
+        attn_logprob [B, 1, T, L] with return_attn, else None); dur_tgt, pitch_tgt and energy_tgt feed infer() as they are."""
+        ids = self._align_ids(ids_or_text)
         eng = self.aligner()
         out = eng.align(ids, mel, mel_lens, attn_prior=attn_prior, return_attn=return_attn)
         dur, soft, hard, logprob = out if return_attn else (out, None, None, None)
@@ -167,6 +178,27 @@ class FastPitch(_HipModule):
             energy = torch.as_tensor(energy).to(dur.device)
             energy_tgt = torch.log(1.0 + _average_pitch(energy[:, None] if energy.dim() == 2 else energy, dur))
         return Alignment(dur, pitch_tgt, energy_tgt, soft, hard, logprob)
+
+    @torch.inference_mode()
+    def alignment_score(self, ids_or_text, mel, mel_lens=None, attn_prior='interpolated'):
+        """How far a forced alignment can be trusted: align() as above (the prior defaults to the one the checkpoint was trained with), then
+        the reference's two alignment losses, forward only (csrc/attn_loss.hip).  -> AlignmentScore(forward_sum [B] float64: the
+        forward-sum negative log-likelihood of the row's text given its frames, per token (+inf where the row has fewer frames than
+        tokens) -- a recording whose transcript is wrong or truncated lies far from the corpus' bulk; binarization [B] float64: minus the
+        mean log of attn_soft along the MAS path; dur_tgt [B, L]; ctc_loss, bin_loss: the batch scalars as AttentionCTCLoss() and
+        AttentionBinarizationLoss() report them).  Nothing is read back to the host."""
+        ids = self._align_ids(ids_or_text)
+        eng = self.aligner()
+        soft, logprob, in_lens = eng.attention(ids, mel, attn_prior, mel_lens=mel_lens)
+        B, _, T, Lt = soft.shape
+        out_lens = torch.full((B,), T, dtype=torch.int64, device=soft.device) if mel_lens is None else \
+            torch.as_tensor(mel_lens).to(device=soft.device, dtype=torch.int64)
+        dur, hard = _mas(soft, in_lens, out_lens, is_log=False, return_hard=True)
+        nll = _forward_sum_loss(logprob, in_lens, out_lens)
+        sum_log, count = _binarization_loss(hard, soft)
+        forward_sum = nll / in_lens.clamp(min=1).double()
+        ctc = (torch.where(torch.isinf(nll), torch.zeros_like(nll), nll) / in_lens.clamp(min=1).double()).mean()
+        return AlignmentScore(forward_sum, -sum_log / count, dur, ctc, -sum_log.sum() / count.sum())
 
     @torch.inference_mode()
     def pitch_track(self, wave, wave_lens=None, mel_len=None, normalize=True):
@@ -471,7 +503,8 @@ class FastPitch2Wave(nn.Module):
         f0_corr, vuv_error) plus frames_pred / frames_ref.  Default: `tts(lines, **tts_options)`, then ObjectiveEngine.score_waves with
         `align` ('dtw' | 'frames'), `n_coef`, `window`.  teacher_forced: the recording's log-mel, its pitch_track and its energy (the L2 norm
         over the bands, as the reference's data_function takes it) go through FastPitch.align, the resulting dur / pitch / energy targets
-        go to infer, so the prediction has the recording's durations; tts_options are then speaker_id, denoise (default 0.005) and
+        go to infer, so the prediction has the recording's durations, and every dict also carries align_forward_sum and align_binarization,
+        the two scores of that alignment (FastPitch.alignment_score, with the prior align used: none); tts_options are then speaker_id, denoise (default 0.005) and
         vowelizer."""
         dev = self.device
         if dev.type != 'cuda':
@@ -501,7 +534,11 @@ class FastPitch2Wave(nn.Module):
                 ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.int64)
             mel_rec, frames = obj.melspec.forward(rec, n_rec)
             pitch = model.pitch_track(rec, n_rec, mel_len=mel_rec.shape[2])
-            tgt = model.align(ids, mel_rec, frames, pitch=pitch, energy=torch.linalg.vector_norm(mel_rec, dim=1))
+            tgt = model.align(ids, mel_rec, frames, pitch=pitch, energy=torch.linalg.vector_norm(mel_rec, dim=1), return_attn=True)
+            in_lens = (ids != model.net_config['padding_idx']).sum(1).to(dev)
+            nll = _forward_sum_loss(tgt.attn_logprob, in_lens, frames)
+            sum_log, count = _binarization_loss(tgt.attn_hard, tgt.attn_soft)
+            extra_scores = {'align_forward_sum': (nll / in_lens.clamp(min=1).double()).cpu().tolist(), 'align_binarization': (-sum_log / count).cpu().tolist()}
             mel, dec_lens, *_ = model.infer(ids, dur_tgt=tgt.dur_tgt, pitch_tgt=tgt.pitch_tgt, energy_tgt=tgt.energy_tgt, speaker=speaker)
             eng = self.vocoder.engine()
             wave, n = eng.forward(mel, dec_lens), dec_lens * eng.hop
@@ -509,7 +546,11 @@ class FastPitch2Wave(nn.Module):
                 wave = self.denoiser.forward_batch(wave, n, denoise)
         score = obj.score_waves(wave, n, rec, n_rec, n_coef=n_coef, align=align, window=window)
         table = torch.stack([score[k] for k in OBJECTIVE_KEYS] + [score['lens_pred'].double(), score['lens_ref'].double()], dim=1).cpu().tolist()
-        return [dict(zip(OBJECTIVE_KEYS + ('frames_pred', 'frames_ref'), row)) for row in table]
+        out = [dict(zip(OBJECTIVE_KEYS + ('frames_pred', 'frames_ref'), row)) for row in table]
+        if teacher_forced:
+            for b, row in enumerate(out):
+                row.update({k: v[b] for k, v in extra_scores.items()})
+        return out
 
     # utterances per vocoder call of the list pipeline: chunks of `batch_size` lines go through FastPitch one by one (a chunk is the
     # reference's padded batch: its results depend on the chunk's composition), their mels are vocoded together

@@ -1050,9 +1050,11 @@ class AlignerEngine:
             self.lib.ttsamd_aligner_destroy(self.handle)
             self.handle = None
 
-    def attention(self, ids, mel, attn_prior=None, in_lens=None):
+    def attention(self, ids, mel, attn_prior=None, in_lens=None, mel_lens=None):
         """ConvAttention.forward on the padded batch: ids int64 [B, L], mel [B, n_mel, T], attn_prior [B, T, L] or None ->
-        (attn_soft, attn_logprob), both [B, 1, T, L]; in_lens None = the count of non-padding ids per row."""
+        (attn_soft, attn_logprob), both [B, 1, T, L]; in_lens None = the count of non-padding ids per row.  attn_prior 'interpolated' /
+        'exact': the beta-binomial prior of the rows' own lengths (in_lens, mel_lens; None: T frames each), built on the device by
+        attention_prior."""
         dev = self.device
         ids = torch.as_tensor(ids)
         _check_ids(ids, self.n_symbols, 'aligner ids')
@@ -1065,6 +1067,8 @@ class AlignerEngine:
         if Lt > MAS_MAX_TOKENS:
             raise L.TtsAmdError(f'aligner: {Lt} tokens, at most {MAS_MAX_TOKENS} are built (TTSAMD_MAS_MAX_TOKENS)')
         in_lens = (ids != self.padding_idx).sum(1) if in_lens is None else _dev_lens(in_lens, B, Lt, dev)
+        if isinstance(attn_prior, str):
+            attn_prior = attention_prior(in_lens, _dev_lens(mel_lens, B, T, dev), n_tokens=Lt, n_frames=T, mode=attn_prior, device=dev)
         prior = _f32(attn_prior, dev)
         if prior is not None and tuple(prior.shape) != (B, T, Lt):
             raise L.TtsAmdError(f'aligner: attn_prior of shape {tuple(prior.shape)}, expected {(B, T, Lt)}')
@@ -1082,11 +1086,104 @@ class AlignerEngine:
         """ids int64 [B, L] zero-padded at the end, mel [B, n_mel, T], mel_lens [B] (None: every row T frames) -> dur [B, L] fp32, the
         frames MAS gives each token (model.py:306-314); with return_attn also attn_soft, attn_hard, attn_logprob, each [B, 1, T, L].
         Two launches of this file's own plus the encoders' six; nothing is read back to the host."""
-        soft, logprob, in_lens = self.attention(ids, mel, attn_prior)
+        soft, logprob, in_lens = self.attention(ids, mel, attn_prior, mel_lens=mel_lens)
         B, _, T, Lt = soft.shape
         mel_lens = _dev_lens(mel_lens, B, T, self.device)
         dur, hard = mas(soft, in_lens, mel_lens, is_log=False, return_hard=return_attn)
         return (dur, soft, hard, logprob) if return_attn else dur
+
+
+# ---- the alignment prior and the alignment scores (csrc/attn_loss.hip) ----------------------------------------------------------------
+PRIOR_MODES = {'exact': 0, 'interpolated': 1}
+_PRIOR_F64 = 2                                                   # TTSAMD_ATTN_PRIOR_F64 of include/ttsamd.h
+_ctc_ws = _Workspace()
+
+
+def attn_prior_tables(n):
+    """lf[k] = log k! for k < n, float64: the table csrc/attn_loss.hip builds on the host (std::lgamma) and uploads for the prior
+    (ttsamd_attn_prior_tables; no GPU is needed)."""
+    lf = np.zeros(int(n), dtype=np.float64)
+    L.check(L.load().ttsamd_attn_prior_tables(int(n), lf.ctypes.data_as(C.c_void_p)), 'attn_prior_tables')
+    return lf
+
+
+def _host_max(lens):
+    return int(torch.as_tensor(lens).max()) if torch.as_tensor(lens).numel() else 0
+
+
+def attention_prior(in_lens, mel_lens, n_tokens=None, n_frames=None, mode='interpolated', scaling=1.0, dtype=torch.float32, device='cuda'):
+    """The aligner's beta-binomial prior on the device (ttsamd_attn_prior, one launch): in_lens / mel_lens [B] -> [B, n_frames, n_tokens]
+    (None: the longest row; given sizes save the read-back of the lengths), row b's [mel_lens[b], in_lens[b]] corner filled and zero
+    outside it, as TTSCollate pads.  mode 'interpolated': what the reference's BetaBinomialInterpolator()(mel_len, in_len) returns, the
+    prior the checkpoints were trained with; 'exact': beta_binomial_prior_distribution(in_len, mel_len).  float64 arithmetic, rounded
+    once to `dtype` (torch.float32, or torch.float64 for the values before that rounding).  Only scaling = 1 is built."""
+    lib = _require_gpu()
+    if mode not in PRIOR_MODES:
+        raise L.TtsAmdError(f"attention_prior: mode {mode!r}: 'interpolated' and 'exact' are built")
+    if dtype not in (torch.float32, torch.float64):
+        raise L.TtsAmdError(f'attention_prior: dtype {dtype}: torch.float32 and torch.float64 are built')
+    dev = torch.device(device if device != 'cuda' else 'cuda:0')
+    Lt = _host_max(in_lens) if n_tokens is None else int(n_tokens)
+    T = _host_max(mel_lens) if n_frames is None else int(n_frames)
+    in_lens = torch.as_tensor(in_lens).to(device=dev, dtype=torch.int64).contiguous().reshape(-1)
+    B = in_lens.numel()
+    mel_lens = _dev_lens(torch.as_tensor(mel_lens).reshape(-1), B, T, dev)
+    out = torch.empty(B, T, Lt, dtype=dtype, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            L.check(lib.ttsamd_attn_prior(_ptr(in_lens), _ptr(mel_lens), B, Lt, T, PRIOR_MODES[mode] | (_PRIOR_F64 if dtype == torch.float64 else 0),
+                                          float(scaling), _ptr(out), _stream()), 'attn_prior')
+    return out
+
+
+def _attn_map(t, what):
+    """[B, T, L] or [B, 1, T, L] on the device -> contiguous fp32 [B, T, L]"""
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise L.TtsAmdError(f'{what}: expected a tensor on the ROCm device (there is no CPU fallback)')
+    if t.requires_grad:
+        raise L.TtsAmdError(f'{what}: the input requires grad, and the backward of this loss is not built (forward only: detach it)')
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    elif t.dim() != 3:
+        raise L.TtsAmdError(f'{what}: expected [B, T, L] or [B, 1, T, L], got shape {tuple(t.shape)}')
+    return t.to(torch.float32).contiguous()
+
+
+def forward_sum_loss(attn_logprob, in_lens, out_lens, blank_logprob=-1):
+    """The forward-sum (CTC) negative log-likelihood of every row's text given its frames, as the reference's AttentionCTCLoss takes it
+    (ttsamd_attn_ctc_loss, two launches): attn_logprob [B, T, L] or [B, 1, T, L] fp32 on the device, in_lens / out_lens [B] -> nll [B]
+    float64; +inf where out_lens[b] < in_lens[b] (no path), 0 where in_lens[b] == 0.  Forward only: no grad history."""
+    lib = _require_gpu()
+    a = _attn_map(attn_logprob, 'forward_sum_loss')
+    B, T, Lt = a.shape
+    if Lt > MAS_MAX_TOKENS:
+        raise L.TtsAmdError(f'forward_sum_loss: {Lt} tokens, at most {MAS_MAX_TOKENS} are built (TTSAMD_MAS_MAX_TOKENS)')
+    in_lens, out_lens = _dev_lens(in_lens, B, Lt, a.device), _dev_lens(out_lens, B, T, a.device)
+    nll = torch.empty(B, dtype=torch.float64, device=a.device)
+    if B:
+        nb = int(lib.ttsamd_attn_ctc_loss_workspace_bytes(B, T, Lt))
+        ws = _ctc_ws.get(max(nb, 8), a.device)
+        with torch.cuda.device(a.device):
+            L.check(lib.ttsamd_attn_ctc_loss(_ptr(a), _ptr(in_lens), _ptr(out_lens), B, T, Lt, float(blank_logprob), _ptr(nll), _ptr(ws), nb,
+                                             _stream()), 'attn_ctc_loss')
+    return nll
+
+
+def binarization_loss(hard, soft, eps=1e-12):
+    """Per row the sum of log(max(soft, eps)) over the cells where hard == 1, and their count (ttsamd_attn_bin_loss, one launch): hard, soft
+    [B, T, L] or [B, 1, T, L] on the device -> (sum_log [B], count [B]) float64, summed in a fixed order (the same bits run to run).  The
+    reference's AttentionBinarizationLoss is -sum_log.sum() / count.sum().  Forward only: no grad history."""
+    lib = _require_gpu()
+    h, s = _attn_map(hard, 'binarization_loss: hard'), _attn_map(soft, 'binarization_loss: soft')
+    if h.shape != s.shape:
+        raise L.TtsAmdError(f'binarization_loss: hard {tuple(h.shape)} and soft {tuple(s.shape)} differ')
+    B, T, Lt = h.shape
+    sum_log = torch.empty(B, dtype=torch.float64, device=h.device)
+    count = torch.empty(B, dtype=torch.float64, device=h.device)
+    if B:
+        with torch.cuda.device(h.device):
+            L.check(lib.ttsamd_attn_bin_loss(_ptr(h), _ptr(s), B, T, Lt, float(eps), _ptr(sum_log), _ptr(count), _stream()), 'attn_bin_loss')
+    return sum_log, count
 
 
 # ---- pYIN pitch tracking (csrc/pyin.hip) ------------------------------------------------------------------------------------------------

@@ -118,6 +118,11 @@ SYMBOLS = {
     'ttsamd_mas_workspace_bytes': (_I64, [_I32, _I32, _I32]),
     'ttsamd_mas': (_I32, [_P, _I32, _P, _P, _I32, _I32, _I32, _P, _P, _P, _I64, _P]),
     'ttsamd_average_pitch': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
+    'ttsamd_attn_prior': (_I32, [_P, _P, _I32, _I32, _I32, _I32, C.c_double, _P, _P]),
+    'ttsamd_attn_prior_tables': (_I32, [_I32, _P]),
+    'ttsamd_attn_ctc_loss_workspace_bytes': (_I64, [_I32, _I32, _I32]),
+    'ttsamd_attn_ctc_loss': (_I32, [_P, _P, _P, _I32, _I32, _I32, C.c_double, _P, _P, _I64, _P]),
+    'ttsamd_attn_bin_loss': (_I32, [_P, _P, _I32, _I32, _I32, C.c_double, _P, _P, _P]),
     'ttsamd_pyin_tables': (_I32, [C.POINTER(PyinCfg), _P, _P, _P, _P, _P, _P, _P]),
     'ttsamd_pyin_create': (_I32, [C.POINTER(PyinCfg), C.POINTER(_P)]),
     'ttsamd_pyin_destroy': (_I32, [_P]),
