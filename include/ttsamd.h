@@ -780,6 +780,39 @@ int32_t ttsamd_dp_pack_audio(const float* wave, int64_t wave_stride, const int64
 int32_t ttsamd_dp_gather_audio(void* comm, const float* packed, float* recv, const int64_t* counts,
                                const int64_t* offsets, int32_t root, void* stream);
 
+/* ---- Streaming synthesis: chunked HiFi-GAN over windows of many open utterances (csrc/stream.hip; ttsamd/stream.py is the scheduler).
+ *      No reference counterpart: the reference vocodes whole utterances.  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays
+ *      8.  The generator is a stack of zero-padded convolutions, so a window of mel frames with `halo` extra frames per side (fewer
+ *      where the utterance ends sooner: a window that touches an utterance edge starts or ends exactly there) gives on its core the
+ *      samples of the whole-utterance call.  One step of the scheduler is gather -> forward of the HiFi-GAN handle -> denoise_rows of the
+ *      denoiser (optional) -> emit, all on one stream, no host synchronisation.
+ * The receptive field of the handle's generator in mel frames per side, from its own config: walking back from one frame of samples,
+ * conv_post widens the sample interval by 3, every stage by its longest ResBlock branch (ResBlock1: the sum over m of (k - 1) / 2 *
+ * (d_m + 1); ResBlock2: (k - 1) / 2 * (d_0 + d_1)), every transposed conv (kernel kt, stride u, padding p = (kt - u) / 2) maps
+ * [lo, hi] to [ceil((lo + p - kt + 1) / u), floor((hi + p) / u)], conv_pre widens by 3.  13 / 13 for the V1 config. */
+int32_t ttsamd_hifigan_halo_frames(void* handle, int32_t* left /* host, out */, int32_t* right /* host, out */);
+/* ... and of the bias denoiser, in frames of 256 samples: a sample's STFT frames reach 512 samples to either side and their inverse
+ * transforms another 512 back, so a sample depends on 768 to either side: 3 for the 1024 / 256 STFT, the only one the library builds. */
+int32_t ttsamd_denoiser_halo_frames(void);
+/* The most windows one gather / emit call takes (the descriptors travel as launch arguments: no staging copy, no synchronisation). */
+#define TTSAMD_STREAM_MAX_WINDOWS 64
+/* pool [n_slots][num_mels][t_cap] fp32 (one slot per open utterance) -> batch [n_windows][num_mels][w_max] fp32 and lens int64
+ * [n_windows] (device; may be NULL), which is what the forward of the HiFi-GAN handle takes: window w holds frames [start[w], start[w] + len[w])
+ * of slot slot[w]; columns past len[w] are written as zeros, lens[w] = len[w].  slot / start / len: HOST int32 [n_windows], read
+ * during the call.  Required: 1 <= n_windows <= TTSAMD_STREAM_MAX_WINDOWS, 0 <= slot < n_slots, 0 <= start, 1 <= len <= w_max,
+ * start + len <= t_cap; anything else is TTSAMD_EINVAL and nothing is launched.  The kernel reads nothing outside those windows. */
+int32_t ttsamd_stream_gather(const float* pool, int32_t n_slots, int32_t num_mels, int32_t t_cap, const int32_t* slot /* host */,
+                             const int32_t* start /* host */, const int32_t* len /* host */, int32_t n_windows, int32_t w_max,
+                             float* batch, int64_t* lens, void* stream);
+/* wave [n_windows][hop * w_max] fp32 (the window waves) -> out [n_windows][c_max]: row w = samples [core_off[w], core_off[w] +
+ * core_len[w]) of wave row w, zeros behind them.  core_off / core_len: HOST int32 [n_windows] in SAMPLES, multiples of hop,
+ * 0 <= core_off, 0 <= core_len <= c_max, core_off + core_len <= hop * w_max; hop and c_max multiples of 8, wave and out 16-byte
+ * aligned (16-byte loads, packed stores); anything else is TTSAMD_EINVAL and nothing is launched.
+ * format 0: out is fp32, a copy.  format 1: out is little-endian int16 PCM, clip(rint(x * 32767), -32768, 32767) with the product in
+ * fp32 and the rounding to nearest even (numpy's np.round of the fp32 product), NaN -> 0. */
+int32_t ttsamd_stream_emit(const float* wave, int32_t n_windows, int32_t w_max, int32_t hop, const int32_t* core_off /* host */,
+                           const int32_t* core_len /* host */, int32_t c_max, int32_t format, void* out, void* stream);
+
 /* Timing hooks for bench.py (roofline of the dominant kernel): when enabled, hifigan
  * forward brackets its ResBlock conv launches with HIP events on the launch stream. */
 int32_t ttsamd_profile_enable(int32_t on);

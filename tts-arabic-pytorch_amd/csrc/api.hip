@@ -141,6 +141,10 @@ int64_t denoiser_workspace_bytes(int32_t, int32_t);
 int32_t denoiser_bias_spec(const Denoiser*, const float*, const int64_t*, int32_t, float*, void*, int64_t, hipStream_t);
 int32_t denoise(const Denoiser*, float*, int64_t, const int64_t*, int32_t, int32_t, const float*, float, const float*, void*, int64_t,
                 hipStream_t);
+int32_t hifigan_halo_frames(const HifiGan*, int32_t*, int32_t*);
+int32_t stream_gather(const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, const int32_t*, int32_t, int32_t, float*,
+                      int64_t*, hipStream_t);
+int32_t stream_emit(const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, int32_t, int32_t, void*, hipStream_t);
 int32_t hifigan_create(const ttsamd_tensor*, int32_t, const ttsamd_hifigan_cfg*, HifiGan**);
 void hifigan_destroy(HifiGan*);
 int64_t hifigan_workspace_bytes(const HifiGan*, int32_t, int32_t);
@@ -304,6 +308,20 @@ int32_t ttsamd_hifigan_forward(void* handle, const float* mel, const int64_t* le
                                float* wave, void* workspace, int64_t workspace_bytes, void* stream) {
     return hifigan_forward((HifiGan*)handle, mel, lens, batch, t_max, wave, workspace, workspace_bytes,
                            (hipStream_t)stream);
+}
+
+// streaming synthesis (stream.hip)
+int32_t ttsamd_hifigan_halo_frames(void* handle, int32_t* left, int32_t* right) {
+    return hifigan_halo_frames((HifiGan*)handle, left, right);
+}
+int32_t ttsamd_denoiser_halo_frames(void) { return 3; }   // (1024 / 2 + 1024 / 2 - 256) / 256: ttsamd.h
+int32_t ttsamd_stream_gather(const float* pool, int32_t n_slots, int32_t num_mels, int32_t t_cap, const int32_t* slot, const int32_t* start,
+                             const int32_t* len, int32_t n_windows, int32_t w_max, float* batch, int64_t* lens, void* stream) {
+    return stream_gather(pool, n_slots, num_mels, t_cap, slot, start, len, n_windows, w_max, batch, lens, (hipStream_t)stream);
+}
+int32_t ttsamd_stream_emit(const float* wave, int32_t n_windows, int32_t w_max, int32_t hop, const int32_t* core_off, const int32_t* core_len,
+                           int32_t c_max, int32_t format, void* out, void* stream) {
+    return stream_emit(wave, n_windows, w_max, hop, core_off, core_len, c_max, format, out, (hipStream_t)stream);
 }
 
 int32_t ttsamd_fastpitch_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_fastpitch_cfg* cfg,

@@ -775,6 +775,9 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
     return 0;
 }
 
+// the config a handle was created with (resblock already 1 / 2): what stream.hip derives the receptive field from
+const ttsamd_hifigan_cfg* hifigan_config(const HifiGan* h) { return &h->cfg; }
+
 void hifigan_blobs(const void* hv, void** f32, int64_t* n_f32, void** b16, int64_t* n_b16) {
     const HifiGan* h = (const HifiGan*)hv;
     *f32 = h->dev; *n_f32 = h->dev_n; *b16 = h->dev16; *n_b16 = h->dev16_n;

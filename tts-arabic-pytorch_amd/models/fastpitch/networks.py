@@ -484,6 +484,70 @@ class FastPitch2Wave(nn.Module):
         lists = {k: [r.get(k, d) for r in requests] for k, d in self.REQUEST_DEFAULTS.items()}
         return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
+    # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
+    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames):
+        """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
+        from ttsamd.stream import StreamingVocoder
+        key = (str(self.device), int(chunk_frames), int(first_chunk_frames), bool(pcm16), int(max_streams), int(max_frames))
+        if getattr(self, '_stream_key', None) != key:
+            self._stream_voc = StreamingVocoder(self.vocoder, self.denoiser, max_streams=max_streams, max_frames=max_frames,
+                                                chunk_frames=chunk_frames, first_chunk_frames=first_chunk_frames, pcm16=pcm16)
+            self._stream_key = key
+        for sid in self._stream_voc.open_streams:           # a generator that was abandoned half-way
+            self._stream_voc.close(sid)
+        return self._stream_voc
+
+    def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
+                   max_streams: int = 32, max_frames: int = 4096, speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
+                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.):
+        """`tts` that hands out audio while it is being made (a generator; one at a time per model).  FastPitch is not autoregressive, so
+        the whole mel exists at once; the vocoder then runs over windows of it (ttsamd.stream.StreamingVocoder), the first of
+        first_chunk_frames frames, the following of chunk_frames.
+        str -> CPU chunks (float32, or int16 PCM with pcm16) whose concatenation has tts_single's 256 T samples and equals it within
+        fp32 summation order.
+        list of lines (the options as scalars or per-line lists, as in `tts`) -> (i, chunk, last) as the steps produce them: every line
+        is a request of its own (the mels come from the rows-as-if-alone path of the mixed requests, so line i's audio is
+        tts_single(line i, its options)); at most max_streams lines are open at a time, each step vocodes the next window of all of
+        them in one call, a line that ends frees its slot and the next line joins mid-flight.  Line i's chunks arrive in order and
+        `last` once.  No peak normalisation: that needs the whole wave."""
+        kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
+        if isinstance(text_input, str):
+            mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw)
+            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames)
+            sv.open(mel, denoise)
+            while sv.open_streams:
+                for _, chunk, _ in sv.step():
+                    yield chunk.cpu()
+            return
+        lines = list(text_input)
+        check_line_controls(len(lines), self.model.net_config['n_speakers'], denoise=denoise, **kw)
+        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames)
+        # FastPitch over the lines in input order, in ragged calls of up to _ALONE_GROUP rows computed as if alone; a group is made when
+        # a slot is free and no mel is waiting
+        groups, fill, longest = [], [], 0
+        for i, line in enumerate(lines):
+            if fill and (len(fill) >= self._ALONE_GROUP or (len(fill) + 1) * max(longest, len(line)) > self._ALONE_CHARS):
+                groups.append(fill)
+                fill, longest = [], 0
+            fill.append(i)
+            longest = max(longest, len(line))
+        if fill:
+            groups.append(fill)
+        waiting, line_of = [], {}
+        while True:
+            while sv.free_slots and (waiting or groups):
+                if not waiting:
+                    pos = groups.pop(0)
+                    mel_b, lens_d = self.model.ttmel_lines_alone([lines[p] for p in pos], _take(speed, pos), _take(speaker_id, pos), vowelizer,
+                                                                 pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos))
+                    waiting = [(p, mel_b[b, :, :t]) for b, (p, t) in enumerate(zip(pos, lens_d.cpu().tolist()))]
+                p, mel = waiting.pop(0)
+                line_of[sv.open(mel, _at(denoise, p))] = p
+            if not line_of:
+                return
+            for sid, chunk, last in sv.step():
+                yield (line_of.pop(sid) if last else line_of[sid]), chunk.cpu(), last
+
     # ---- objective evaluation against recordings (not in the reference; ttsamd.engine.ObjectiveEngine, csrc/objective.hip) ----
     @staticmethod
     def _pad_waves(waves, device):

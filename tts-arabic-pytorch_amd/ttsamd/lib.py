@@ -74,6 +74,11 @@ SYMBOLS = {
     'ttsamd_hifigan_destroy': (_I32, [_P]),
     'ttsamd_hifigan_workspace_bytes': (_I64, [_P, _I32, _I32]),
     'ttsamd_hifigan_forward': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
+    # streaming synthesis (csrc/stream.hip): the window descriptors are HOST int32 arrays
+    'ttsamd_hifigan_halo_frames': (_I32, [_P, C.POINTER(_I32), C.POINTER(_I32)]),
+    'ttsamd_denoiser_halo_frames': (_I32, []),
+    'ttsamd_stream_gather': (_I32, [_P, _I32, _I32, _I32, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    'ttsamd_stream_emit': (_I32, [_P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     'ttsamd_fastpitch_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(FastPitchCfg), C.POINTER(_P)]),
     'ttsamd_fastpitch_destroy': (_I32, [_P]),
     'ttsamd_fastpitch_encode_workspace_bytes': (_I64, [_P, _I32, _I32]),

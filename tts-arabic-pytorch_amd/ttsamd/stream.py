@@ -1,0 +1,220 @@
+"""Streaming synthesis: chunked HiFi-GAN with continuous batching of windows (csrc/stream.hip).
+
+HiFi-GAN is a stack of zero-padded convolutions, so a window of mel frames with `halo` extra frames on each side gives, on its core, the
+samples of the whole-utterance call; a window that touches an utterance edge starts or ends exactly there, which keeps the per-layer
+zero padding (and the denoiser's reflect padding) what the whole-utterance call sees.  `plan_chunks` cuts an utterance into such
+windows; `StreamingVocoder` keeps the mels of the open utterances in a pool and, per `step()`, takes the next window of every one of
+them through ONE gather -> ttsamd_hifigan_forward -> ttsamd_denoise_rows -> emit sequence: utterances at different points of their
+lengths share one chip-filling vocoder call, and audio leaves while the rest is still being made."""
+import ctypes as C
+
+import numpy as np
+
+from . import lib as L
+
+MAX_WINDOWS = 64            # TTSAMD_STREAM_MAX_WINDOWS of include/ttsamd.h
+DENOISER_HALO = 3           # ttsamd_denoiser_halo_frames(): 768 samples of the 1024 / 256 STFT -> ISTFT round trip
+
+
+def hifigan_halo_frames(config):
+    """(left, right): the receptive field of a HiFi-GAN generator in mel frames per side, from its config dict -- the derivation of
+    ttsamd_hifigan_halo_frames (include/ttsamd.h) restated on the host.  The samples [0, hop - 1] of one frame are walked back to the
+    mel frames they depend on: conv_post widens the interval by 3, every stage by its longest ResBlock branch, every transposed conv
+    (kernel kt, stride u, padding (kt - u) / 2) maps [lo, hi] to [ceil((lo + p - kt + 1) / u), floor((hi + p) / u)], conv_pre widens by 3."""
+    rates, kts = list(config['upsample_rates']), list(config['upsample_kernel_sizes'])
+    rb2 = str(config.get('resblock', '1')) == '2'
+    reach = 0
+    for k, ds in zip(config['resblock_kernel_sizes'], config['resblock_dilation_sizes']):
+        half = (k - 1) // 2
+        reach = max(reach, half * (ds[0] + ds[1]) if rb2 else sum(half * (d + 1) for d in ds))
+    lo, hi = -3, int(np.prod(rates)) - 1 + 3
+    for u, kt in zip(reversed(rates), reversed(kts)):
+        p = (kt - u) // 2
+        lo, hi = lo - reach, hi + reach
+        lo, hi = -((-(lo + p - kt + 1)) // u), (hi + p) // u
+    return 3 - lo, hi + 3
+
+
+def pcm16(x):
+    """float samples -> int16 PCM with save_wav's arithmetic (utils/audio.py): clip(rint(x * 32767), -32768, 32767) on the fp32 product,
+    round-half-even, NaN -> 0.  What ttsamd_stream_emit(format = 1) writes."""
+    a = np.asarray(x, dtype=np.float32)
+    with np.errstate(invalid='ignore'):
+        v = np.clip(np.rint(a * np.float32(32767.0)), -32768, 32767)
+    return np.where(np.isnan(a), np.float32(0), v).astype('<i2')
+
+
+def plan_chunks(T, first_chunk_frames, chunk_frames, halo_left, halo_right):
+    """[(core_start, core_len, win_start, win_len)] for an utterance of T frames.  The cores partition [0, T) in order: the first is
+    min(first_chunk_frames, T) frames (a short one: time to first audio), the following ones chunk_frames; a remainder shorter than
+    chunk_frames // 2 is folded into the core before it.  A window is its core plus min(halo, distance to the utterance edge) frames
+    on each side."""
+    T, first, chunk, hl, hr = int(T), int(first_chunk_frames), int(chunk_frames), int(halo_left), int(halo_right)
+    if T < 1 or first < 1 or chunk < 1 or hl < 0 or hr < 0:
+        raise ValueError(f'plan_chunks: T {T}, first_chunk_frames {first}, chunk_frames {chunk}, halos {hl} / {hr}')
+    cores, pos = [], 0
+    while pos < T:
+        n = min(first if not cores else chunk, T - pos)
+        cores.append([pos, n])
+        pos += n
+    if len(cores) > 1 and cores[-1][1] < chunk // 2:
+        cores[-2][1] += cores.pop()[1]
+    plan = []
+    for s, n in cores:
+        ws, we = s - min(hl, s), s + n + min(hr, T - s - n)
+        plan.append((s, n, ws, we - ws))
+    return plan
+
+
+def max_core_frames(first_chunk_frames, chunk_frames):
+    """the longest core plan_chunks can return: a core that took a folded remainder"""
+    return max(int(first_chunk_frames), int(chunk_frames)) + max(int(chunk_frames) // 2 - 1, 0)
+
+
+class _Open:
+    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise')
+
+    def __init__(self, sid, slot, plan, denoise):
+        self.sid, self.slot, self.plan, self.next, self.denoise = sid, slot, plan, 0, denoise
+
+
+class StreamingVocoder:
+    """Chunked vocoding of up to `max_streams` open utterances of up to `max_frames` frames each.
+
+    vocoder: a vocoder.hifigan.models.Generator (V1 or V3) on the GPU; denoiser: the vocoder.hifigan.denoiser.Denoiser of that
+    generator, needed only for open(denoise > 0).  Every buffer is allocated here, once.  open(mel, denoise) -> sid copies a mel into a
+    free slot; step() returns the next chunk of every open utterance; an utterance closes itself after its last chunk.  Precision is
+    the library's (ttsamd.engine.set_precision): the step calls the forward entry the one-shot path calls."""
+
+    def __init__(self, vocoder, denoiser=None, max_streams=32, max_frames=4096, chunk_frames=64, first_chunk_frames=32, pcm16=False):
+        import torch
+        from .engine import DenoiserEngine
+        if min(int(max_streams), int(max_frames), int(chunk_frames), int(first_chunk_frames)) < 1:
+            raise ValueError('StreamingVocoder: max_streams, max_frames, chunk_frames and first_chunk_frames must be >= 1')
+        self.eng = vocoder.engine()
+        self.lib, self.device = self.eng.lib, self.eng.device
+        self.hop, self.num_mels = self.eng.hop, self.eng.num_mels
+        left, right = C.c_int32(), C.c_int32()
+        L.check(self.lib.ttsamd_hifigan_halo_frames(self.eng.handle, C.byref(left), C.byref(right)), 'hifigan_halo_frames')
+        self._halo = (left.value, right.value)
+        self.max_streams, self.max_frames = int(max_streams), int(max_frames)
+        self.chunk_frames, self.first_chunk_frames, self.pcm16 = int(chunk_frames), int(first_chunk_frames), bool(pcm16)
+        self.denoiser = denoiser
+        self._dn_eng = self._bias = None
+        dn_halo = 0
+        if denoiser is not None:
+            dn_halo = int(self.lib.ttsamd_denoiser_halo_frames())
+            if denoiser.device != self.device:
+                denoiser.to(self.device)
+            self._dn_eng = denoiser._engine(lambda d: DenoiserEngine(device=d))
+            self._bias = denoiser._bias_spec(self.device).reshape(-1).contiguous()
+        self._dn_halo = dn_halo
+        dev = self.device
+        self._core_cap = max_core_frames(first_chunk_frames, chunk_frames)
+        self._w_cap = (self._core_cap + left.value + right.value + 2 * dn_halo + 3) & ~3
+        self._rows = min(MAX_WINDOWS, self.max_streams)
+        self._pool = torch.zeros(self.max_streams, self.num_mels, self.max_frames, dtype=torch.float32, device=dev)
+        self._batch = torch.empty(self._rows * self.num_mels * self._w_cap, dtype=torch.float32, device=dev)
+        self._lens = torch.empty(self._rows, dtype=torch.int64, device=dev)
+        self._wave = torch.empty(self._rows * self.hop * self._w_cap, dtype=torch.float32, device=dev)
+        out_dtype = torch.int16 if self.pcm16 else torch.float32
+        self._out = [torch.empty(self._rows * self.hop * self._core_cap, dtype=out_dtype, device=dev) for _ in range(2)]
+        self._flip = 0
+        self._free = list(range(self.max_streams))
+        self._open = {}                 # sid -> _Open, in opening order (oldest first)
+        self._next_sid = 0
+
+    @property
+    def halo(self):
+        """(left, right) receptive field of the vocoder in mel frames: ttsamd_hifigan_halo_frames of its handle"""
+        return self._halo
+
+    @property
+    def free_slots(self):
+        return len(self._free)
+
+    @property
+    def open_streams(self):
+        return list(self._open)
+
+    def open(self, mel, denoise=0.0):
+        """mel [num_mels, T] (a device tensor: copied device to device) -> sid.  ValueError: T > max_frames, no free slot, a denoise
+        strength that is not finite, denoise > 0 without a denoiser or on an utterance of at most 512 samples (as the one-shot Denoiser)."""
+        import torch
+        mel = torch.as_tensor(mel)
+        if mel.dim() != 2 or mel.shape[0] != self.num_mels or mel.shape[1] < 1:
+            raise ValueError(f'StreamingVocoder.open: mel must be [{self.num_mels}, T >= 1], got {tuple(mel.shape)}')
+        T = int(mel.shape[1])
+        denoise = float(denoise)
+        if not np.isfinite(denoise):
+            raise ValueError(f'StreamingVocoder.open: denoise {denoise!r} is not finite')
+        if T > self.max_frames:
+            raise ValueError(f'StreamingVocoder.open: {T} frames, the pool holds utterances of up to max_frames = {self.max_frames}')
+        if denoise > 0:
+            if self._dn_eng is None:
+                raise ValueError('StreamingVocoder.open: denoise > 0 needs the denoiser (StreamingVocoder(vocoder, denoiser=...))')
+            if self.hop * T <= 512:
+                raise ValueError('Denoiser: every utterance needs more than 512 samples (reflect padding of n_fft/2); '
+                                 f'shortest has {self.hop * T}')
+        if not self._free:
+            raise ValueError(f'StreamingVocoder.open: all {self.max_streams} slots are taken (max_streams)')
+        halo = self._dn_halo if denoise > 0 else 0
+        plan = plan_chunks(T, self.first_chunk_frames, self.chunk_frames, self._halo[0] + halo, self._halo[1] + halo)
+        slot = self._free.pop(0)
+        self._pool[slot, :, :T].copy_(mel.to(dtype=torch.float32), non_blocking=True)
+        sid = self._next_sid
+        self._next_sid += 1
+        self._open[sid] = _Open(sid, slot, plan, denoise)
+        return sid
+
+    def close(self, sid):
+        """Drop an open utterance (its remaining chunks are not made) and free its slot.  KeyError for a sid that is not open."""
+        self._free.append(self._open.pop(sid).slot)
+
+    def step(self):
+        """The next chunk of every open utterance, oldest first, at most 64 -> [(sid, chunk, last)]: chunk is a device tensor of
+        hop * core_len samples (float32, or int16 with pcm16), valid until the step after next; `last` marks an utterance's final
+        chunk, after which it is closed.  One gather, one vocoder forward, one denoise (when a row asks for it) and one emit on the
+        current stream; the host waits for none of them."""
+        import torch
+        from .engine import _ptr, _stream
+        rows = list(self._open.values())[:self._rows]
+        if not rows:
+            return []
+        W = len(rows)
+        i32 = C.c_int32 * W
+        chunks = [st.plan[st.next] for st in rows]
+        w_max = (max(c[3] for c in chunks) + 3) & ~3
+        c_max = self.hop * max(c[1] for c in chunks)
+        slot, start, length = i32(*[st.slot for st in rows]), i32(*[c[2] for c in chunks]), i32(*[c[3] for c in chunks])
+        off, n = i32(*[self.hop * (c[0] - c[2]) for c in chunks]), i32(*[self.hop * c[1] for c in chunks])
+        out = self._out[self._flip]
+        self._flip ^= 1
+        lib, eng = self.lib, self.eng
+        with torch.cuda.device(self.device):
+            L.check(lib.ttsamd_stream_gather(_ptr(self._pool), self.max_streams, self.num_mels, self.max_frames, slot, start, length, W,
+                                             w_max, _ptr(self._batch), _ptr(self._lens), _stream()), 'stream_gather')
+            nbytes = lib.ttsamd_hifigan_workspace_bytes(eng.handle, W, w_max)
+            ws = eng.ws.get(nbytes, self.device)
+            L.check(lib.ttsamd_hifigan_forward(eng.handle, _ptr(self._batch), _ptr(self._lens), W, w_max, _ptr(self._wave), _ptr(ws), nbytes,
+                                               _stream()), 'hifigan_forward')
+            if any(st.denoise > 0 for st in rows):
+                # the strengths go up from pinned memory, asynchronously; a row at 0 is left untouched by ttsamd_denoise_rows
+                strength = torch.tensor([st.denoise for st in rows], dtype=torch.float32).pin_memory().to(self.device, non_blocking=True)
+                nsamples = self._lens[:W] * self.hop
+                n_max = self.hop * w_max
+                nb = lib.ttsamd_denoiser_workspace_bytes(W, n_max)
+                dws = self._dn_eng.ws.get(nb, self.device)
+                L.check(lib.ttsamd_denoise_rows(self._dn_eng.handle, _ptr(self._wave), n_max, _ptr(nsamples), W, n_max, _ptr(self._bias),
+                                                _ptr(strength), _ptr(dws), nb, _stream()), 'denoise_rows')
+            L.check(lib.ttsamd_stream_emit(_ptr(self._wave), W, w_max, self.hop, off, n, c_max, 1 if self.pcm16 else 0, _ptr(out),
+                                           _stream()), 'stream_emit')
+        view = out[:W * c_max].view(W, c_max)
+        res = []
+        for w, (st, c) in enumerate(zip(rows, chunks)):
+            st.next += 1
+            last = st.next == len(st.plan)
+            res.append((st.sid, view[w, :self.hop * c[1]], last))
+            if last:
+                self.close(st.sid)
+        return res

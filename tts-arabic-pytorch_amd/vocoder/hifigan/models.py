@@ -77,3 +77,15 @@ class Generator(_HipModule):
         if x.dim() == 2:
             return eng.forward(x[None])
         return eng.forward(x, lens)[:, None, :]
+
+    def stream(self, mel, chunk_frames=64, first_chunk_frames=32, pcm16=False, denoiser=None, denoise=0.0):
+        """Extension (ttsamd.stream): mel [80, T] -> a generator of device chunks (float32, or int16 PCM with pcm16) whose concatenation
+        is forward(mel)'s 256 T samples within fp32 summation order, the first after first_chunk_frames frames of work instead of T.
+        `denoiser` + `denoise` > 0: the bias denoiser per chunk.  A chunk stays valid until the one after next has been taken."""
+        from ttsamd.stream import StreamingVocoder
+        sv = StreamingVocoder(self, denoiser=denoiser, max_streams=1, max_frames=int(mel.shape[-1]), chunk_frames=chunk_frames,
+                              first_chunk_frames=first_chunk_frames, pcm16=pcm16)
+        sv.open(mel, denoise)
+        while sv.open_streams:
+            for _, chunk, _ in sv.step():
+                yield chunk
