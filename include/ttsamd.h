@@ -812,6 +812,42 @@ int32_t ttsamd_stream_gather(const float* pool, int32_t n_slots, int32_t num_mel
  * fp32 and the rounding to nearest even (numpy's np.round of the fp32 product), NaN -> 0. */
 int32_t ttsamd_stream_emit(const float* wave, int32_t n_windows, int32_t w_max, int32_t hop, const int32_t* core_off /* host */,
                            const int32_t* core_len /* host */, int32_t c_max, int32_t format, void* out, void* stream);
+/* Stream delivery formats: ttsamd_stream_emit with the polyphase resampler of ttsamd_resample_create and an encoder between the window
+ * waves and the chunk rows.  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.
+ * resample_handle: a handle of ttsamd_resample_create (o, n, width, J = 2 * width + o and its device table), or NULL for "rate
+ * unchanged", which behaves as o = n = 1, width = 0 and one tap of 1.0.  wave [n_windows][hop * w_max] fp32 as for ttsamd_stream_emit.
+ * Five HOST int32 arrays [n_windows], read during the call, all in SAMPLES OF THE UTTERANCE: win_start[w] = the utterance index of the
+ * row's sample 0, win_len[w] = the valid samples of the row, utt_len[w] = L, core_start[w] = S0, core_end[w] = S1, with
+ * 0 <= win_start <= S0 < S1 <= min(L, win_start + win_len).  Every product with n is taken in int64.
+ * Row w of out [n_windows][c_max] (elements of the format) holds the resampler's outputs k in [K0, K1), K0 = ceil(n * S0 / o),
+ * K1 = ceil(n * S1 / o): nout[w] = K1 - K0 values (nout: HOST int32 [n_windows] or NULL, written before the call returns); the entries
+ * from there up to c_max are written as zero.  The cores of an utterance partition [0, L), so its chunks partition
+ * [0, ceil(n * L / o)) = [0, ttsamd_resample_out_len(L)): nothing is emitted twice or dropped.
+ * Value: out[f * n + p] = sum_{j < J} taps[p][j] * xz[f * o + j - width], xz = the utterance, read from the row at index - win_start
+ * and zero outside [0, L); over j ascending as ONE fp32 fma chain from +0.f over all J taps, the chain of ttsamd_resample_forward's
+ * general kernel: a chunk holds the bits of the whole-utterance call on the same samples.
+ * Checked on the host (TTSAMD_EINVAL with a message, nothing launched, nout untouched): 1 <= n_windows <= TTSAMD_STREAM_MAX_WINDOWS;
+ * the inequalities above; 1 <= win_len <= hop * w_max; nout[w] <= c_max; format in 0..3; wave and out 4-byte aligned; and the window
+ * holds every in-utterance sample its outputs read: with f0 = K0 / n and f1 = (K1 - 1) / n, the interval
+ * [max(0, f0 * o - width), min(L, f1 * o - width + J)) lies inside [win_start, win_start + win_len).  The kernel reads nothing of the
+ * row outside that interval: the rest may hold anything.
+ * format 0: fp32.  1: little-endian int16 PCM, s = clip(rint(x * 32767), -32768, 32767), fp32 product, ties to even, NaN -> 0
+ * (ttsamd_stream_emit's format 1).  2: G.711 mu-law, one byte from s: a = s >> 2 (arithmetic), neg = a < 0,
+ * m = min((neg ? -a : a) + 33, 8191), e = floor(log2(m)) - 5, byte = ~(neg << 7 | e << 4 | ((m >> (e + 1)) & 15)) & 0xff.
+ * 3: G.711 A-law, one byte from s: a = s >> 3, pos = a >= 0, a = pos ? a : ~a, seg = a < 32 ? 0 : floor(log2(a)) - 4,
+ * mant = seg < 2 ? (a >> 1) & 15 : (a >> seg) & 15, byte = (pos << 7 | seg << 4 | mant) ^ 0x55.  (tests/golden/g711.npz holds both
+ * for every int16 value.) */
+int32_t ttsamd_stream_emit_resampled(void* resample_handle, const float* wave, int32_t n_windows, int32_t w_max, int32_t hop,
+                                     const int32_t* win_start /* host */, const int32_t* win_len /* host */,
+                                     const int32_t* utt_len /* host */, const int32_t* core_start /* host */,
+                                     const int32_t* core_end /* host */, int32_t c_max, int32_t format, void* out,
+                                     int32_t* nout /* host, out, may be NULL */, void* stream);
+/* The encoder alone, for finished waves: wave [batch][wave_stride] fp32 -> out [batch][out_stride] elements of format 1 (int16), 2 or 3
+ * (one byte) as above.  nsamples: device int64 [batch], clamped to [0, wave_stride], or NULL for the full stride; samples
+ * [0, nsamples[b]) of row b are converted, the entries behind them up to min(wave_stride, out_stride) are written as zero.  wave and
+ * out 4-byte aligned, 1 <= batch <= 65535.  Nothing is read back to the host. */
+int32_t ttsamd_wave_encode(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t format, void* out,
+                           int64_t out_stride, void* stream);
 
 /* Timing hooks for bench.py (roofline of the dominant kernel): when enabled, hifigan
  * forward brackets its ResBlock conv launches with HIP events on the launch stream. */

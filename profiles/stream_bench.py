@@ -9,7 +9,13 @@
 Host clock around work that ends in a device-to-host copy (a synchronise); every shape is warmed up first; medians over --reps runs,
 the two sides of a comparison alternating inside one process.  Synthetic V1 weights, random mels from a seed.
 
-    python profiles/stream_bench.py [--reps 15] [--warmup 3] [--precision f32] [--out FILE.jsonl]"""
+  (c) the delivery formats (profiles/r18/NOTES.md): 32 open streams of T = 512 at chunk_frames 64, first_chunk_frames 32, leaving at
+      --sample-rate as --encoding: the time per step (the whole run without copies / its steps) and the time from the first open to
+      the first step's 32 chunks on the host.  Without the two flags the constructor gets no new argument, so the same file measures
+      the commit before them.
+
+    python profiles/stream_bench.py [--reps 15] [--warmup 3] [--precision f32] [--out FILE.jsonl]
+                                    [--sample-rate 8000] [--encoding mulaw] [--only-c]"""
 import argparse
 import json
 import os
@@ -27,7 +33,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--precision', default='f32')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--sample-rate', type=int, default=None)
+    ap.add_argument('--encoding', default=None, choices=['float32', 'pcm16', 'mulaw', 'alaw'])
+    ap.add_argument('--only-c', action='store_true', help='case (c) alone')
     args = ap.parse_args()
+    delivery = {k: v for k, v in (('sample_rate', args.sample_rate), ('encoding', args.encoding)) if v is not None}
 
     import numpy as np
     import torch
@@ -50,6 +60,13 @@ def main():
         rows.append(kw)
         print(json.dumps(kw), flush=True)
 
+    def save():
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                for r in rows:
+                    f.write(json.dumps(r) + '\n')
+
     def ms(fn):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -58,6 +75,35 @@ def main():
 
     def med(xs):
         return round(statistics.median(xs), 3), round(min(xs), 3), round(max(xs), 3)
+
+    # ---- (c) 32 open streams at a delivery format: time per step, time to the first chunks ------------------------------------------------
+    B, T = 32, 512
+    mels_c = torch.from_numpy((np.random.default_rng(1).standard_normal((B, 80, T)) * 1.5 - 4.0).astype(np.float32)).to(dev)
+    sv = StreamingVocoder(gen, max_streams=B, max_frames=T, chunk_frames=64, first_chunk_frames=32, **delivery)
+    steps, first_c, run_c = [0], [], []
+
+    def first_chunks():
+        for b in range(B):
+            sv.open(mels_c[b])
+        [c.cpu() for _, c, _ in sv.step()]
+
+    def rest_on_device():
+        steps[0] = 1
+        while sv.open_streams:
+            steps[0] += 1
+            sv.step()
+        torch.cuda.synchronize()
+
+    for i in range(args.warmup + args.reps):
+        a, b = ms(first_chunks), ms(rest_on_device)
+        if i >= args.warmup:
+            first_c.append(a)
+            run_c.append(b / (steps[0] - 1))
+    emit(case='c', streams=B, frames=T, chunk_frames=64, first_chunk_frames=32, steps=steps[0], halo=sv.halo,
+         sample_rate=getattr(sv, 'sample_rate', 22050), encoding=getattr(sv, 'encoding', 'float32'), first_chunks_ms=med(first_c),
+         step_ms=med(run_c))
+    if args.only_c:
+        return save()
 
     # ---- (a) time to first audio of one long line ------------------------------------------------------------------------------------
     T = 2048
@@ -127,11 +173,7 @@ def main():
              streamed_ms=med(t['streamed']), oneshot_ms=med(t['oneshot']), streamed_device_ms=med(t['streamed_device']),
              oneshot_device_ms=med(t['oneshot_device']), ratio=round(m['streamed'] / m['oneshot'], 3),
              ratio_device=round(m['streamed_device'] / m['oneshot_device'], 3), arithmetic_ratio=round((chunk + 2 * halo) / chunk, 3))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            for r in rows:
-                f.write(json.dumps(r) + '\n')
+    save()
 
 
 if __name__ == '__main__':

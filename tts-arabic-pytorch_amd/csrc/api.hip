@@ -145,6 +145,9 @@ int32_t hifigan_halo_frames(const HifiGan*, int32_t*, int32_t*);
 int32_t stream_gather(const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, const int32_t*, int32_t, int32_t, float*,
                       int64_t*, hipStream_t);
 int32_t stream_emit(const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, int32_t, int32_t, void*, hipStream_t);
+int32_t stream_emit_resampled(const Resample*, const float*, int32_t, int32_t, int32_t, const int32_t*, const int32_t*, const int32_t*,
+                              const int32_t*, const int32_t*, int32_t, int32_t, void*, int32_t*, hipStream_t);
+int32_t wave_encode(const float*, int64_t, const int64_t*, int32_t, int32_t, void*, int64_t, hipStream_t);
 int32_t hifigan_create(const ttsamd_tensor*, int32_t, const ttsamd_hifigan_cfg*, HifiGan**);
 void hifigan_destroy(HifiGan*);
 int64_t hifigan_workspace_bytes(const HifiGan*, int32_t, int32_t);
@@ -322,6 +325,16 @@ int32_t ttsamd_stream_gather(const float* pool, int32_t n_slots, int32_t num_mel
 int32_t ttsamd_stream_emit(const float* wave, int32_t n_windows, int32_t w_max, int32_t hop, const int32_t* core_off, const int32_t* core_len,
                            int32_t c_max, int32_t format, void* out, void* stream) {
     return stream_emit(wave, n_windows, w_max, hop, core_off, core_len, c_max, format, out, (hipStream_t)stream);
+}
+int32_t ttsamd_stream_emit_resampled(void* resample_handle, const float* wave, int32_t n_windows, int32_t w_max, int32_t hop,
+                                     const int32_t* win_start, const int32_t* win_len, const int32_t* utt_len, const int32_t* core_start,
+                                     const int32_t* core_end, int32_t c_max, int32_t format, void* out, int32_t* nout, void* stream) {
+    return stream_emit_resampled((const Resample*)resample_handle, wave, n_windows, w_max, hop, win_start, win_len, utt_len, core_start,
+                                 core_end, c_max, format, out, nout, (hipStream_t)stream);
+}
+int32_t ttsamd_wave_encode(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t format, void* out,
+                           int64_t out_stride, void* stream) {
+    return wave_encode(wave, wave_stride, nsamples, batch, format, out, out_stride, (hipStream_t)stream);
 }
 
 int32_t ttsamd_fastpitch_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_fastpitch_cfg* cfg,

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "stream_plan.hpp"
 
 namespace ttsamd {
 
@@ -84,6 +85,7 @@ int32_t resample_create(const float* taps, int32_t o, int32_t n, int32_t width, 
 void resample_destroy(Resample* h);
 int64_t resample_out_len(const Resample* h, int64_t nsamples);
 int32_t resample_mfma_eligible(const Resample* h);
+ResampleView resample_view(const Resample* h);        // stream_plan.hpp: what stream.hip's emit kernel needs of a handle
 int32_t resample_forward(const Resample* h, const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t B, float* out,
                          int64_t out_stride, int64_t* nout, int32_t route, hipStream_t s);
 int64_t trim_workspace_bytes(int32_t B, int64_t wave_stride, int32_t hop);

@@ -91,6 +91,8 @@ int64_t resample_out_len(const Resample* h, int64_t nsamples) { return h ? rs_ou
 
 int32_t resample_mfma_eligible(const Resample* h) { return h && h->mfma_ok ? 1 : 0; }
 
+ResampleView resample_view(const Resample* h) { return ResampleView{h->tapsT, h->o, h->n, h->width, h->J, h->NP}; }
+
 // ---- (a) general kernel -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(RS_GEN_THREADS) void resample_general_kernel(
     const float* __restrict__ wave, int64_t wave_bs, const int64_t* __restrict__ ns, const float* __restrict__ tapsT, int NP, int J, int o,

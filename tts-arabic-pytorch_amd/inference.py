@@ -10,7 +10,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from utils import read_lines_from_file  # noqa: E402
-from utils.audio import save_wav  # noqa: E402
+from utils.audio import resample, save_wav  # noqa: E402
+
+WAV_ENCODINGS = {'pcm16': ('PCM_S', 16), 'float32': ('PCM_F', 32), 'mulaw': ('ULAW', 8), 'alaw': ('ALAW', 8)}
 
 
 def infer(args):
@@ -26,12 +28,16 @@ def infer(args):
     os.makedirs(os.path.join(args.out_dir, 'wavs'), exist_ok=True)
     lines = [ln for ln in read_lines_from_file(args.list) if ln]
     idx = 0
+    rate = args.sample_rate or 22_050
+    enc, bits = WAV_ENCODINGS[args.encoding]
     with open(os.path.join(args.out_dir, 'index.tsv'), 'w', encoding='utf-8') as index:
         for k in range(0, len(lines), args.batch_size):
             batch = lines[k:k + args.batch_size]
             wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed)
             for line, wav in zip(batch, wavs):
-                save_wav(os.path.join(args.out_dir, 'wavs', f'static{idx}.wav'), wav, 22_050)
+                if rate != 22_050:                      # the finished wave through the device resampler, then the matching file format
+                    wav = resample(wav.reshape(1, -1).to('cuda'), 22_050, rate)[0]
+                save_wav(os.path.join(args.out_dir, 'wavs', f'static{idx}.wav'), wav, rate, encoding=enc, bits_per_sample=bits)
                 index.write(f'wavs/static{idx}.wav\t{wav.numel()}\t{line}\n')
                 idx += 1
     print(f'Saved files to: {args.out_dir}')
@@ -49,6 +55,9 @@ def main(argv=None):
     p.add_argument('--denoise', type=float, default=0)
     p.add_argument('--batch_size', type=int, default=2)
     p.add_argument('--cpu', action='store_true')
+    # not in the reference: the rate and the encoding of the files (8000 + mulaw / alaw: G.711 telephony files, WAVE format 7 / 6)
+    p.add_argument('--sample_rate', type=int, default=None)
+    p.add_argument('--encoding', type=str, default='pcm16', choices=sorted(WAV_ENCODINGS))
     infer(p.parse_args(argv))
 
 

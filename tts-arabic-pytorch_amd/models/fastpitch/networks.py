@@ -485,13 +485,15 @@ class FastPitch2Wave(nn.Module):
         return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
     # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
-    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames):
+    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None):
         """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
         from ttsamd.stream import StreamingVocoder
-        key = (str(self.device), int(chunk_frames), int(first_chunk_frames), bool(pcm16), int(max_streams), int(max_frames))
+        key = (str(self.device), int(chunk_frames), int(first_chunk_frames), bool(pcm16), int(max_streams), int(max_frames),
+               None if sample_rate is None else int(sample_rate), encoding)
         if getattr(self, '_stream_key', None) != key:
             self._stream_voc = StreamingVocoder(self.vocoder, self.denoiser, max_streams=max_streams, max_frames=max_frames,
-                                                chunk_frames=chunk_frames, first_chunk_frames=first_chunk_frames, pcm16=pcm16)
+                                                chunk_frames=chunk_frames, first_chunk_frames=first_chunk_frames, pcm16=pcm16,
+                                                sample_rate=sample_rate, encoding=encoding)
             self._stream_key = key
         for sid in self._stream_voc.open_streams:           # a generator that was abandoned half-way
             self._stream_voc.close(sid)
@@ -499,7 +501,7 @@ class FastPitch2Wave(nn.Module):
 
     def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
                    max_streams: int = 32, max_frames: int = 4096, speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
-                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.):
+                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., sample_rate=None, encoding=None):
         """`tts` that hands out audio while it is being made (a generator; one at a time per model).  FastPitch is not autoregressive, so
         the whole mel exists at once; the vocoder then runs over windows of it (ttsamd.stream.StreamingVocoder), the first of
         first_chunk_frames frames, the following of chunk_frames.
@@ -509,11 +511,14 @@ class FastPitch2Wave(nn.Module):
         is a request of its own (the mels come from the rows-as-if-alone path of the mixed requests, so line i's audio is
         tts_single(line i, its options)); at most max_streams lines are open at a time, each step vocodes the next window of all of
         them in one call, a line that ends frees its slot and the next line joins mid-flight.  Line i's chunks arrive in order and
-        `last` once.  No peak normalisation: that needs the whole wave."""
+        `last` once.  No peak normalisation: that needs the whole wave.
+        sample_rate / encoding ('float32' | 'pcm16' | 'mulaw' | 'alaw'): the chunks leave at that rate and in that encoding (8 000 Hz
+        'mulaw' is telephony's G.711: uint8 chunks); put together they are utils.audio.resample of the line's 22 050 Hz samples,
+        encoded, bit for bit -- no seam at a chunk border."""
         kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
         if isinstance(text_input, str):
             mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw)
-            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames)
+            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding)
             sv.open(mel, denoise)
             while sv.open_streams:
                 for _, chunk, _ in sv.step():
@@ -521,7 +526,7 @@ class FastPitch2Wave(nn.Module):
             return
         lines = list(text_input)
         check_line_controls(len(lines), self.model.net_config['n_speakers'], denoise=denoise, **kw)
-        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames)
+        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding)
         # FastPitch over the lines in input order, in ragged calls of up to _ALONE_GROUP rows computed as if alone; a group is made when
         # a slot is free and no mel is waiting
         groups, fill, longest = [], [], 0

@@ -50,6 +50,23 @@ def resample_taps(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
     return taps, width, o, n
 
 
+MAX_RATIO, MAX_TAPS = 4096, 65536       # the limits of ttsamd_resample_create (csrc/resample.hip) on o, n and on J = 2 * width + o
+
+
+def geometry(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """-> (o, n, width) without building the table.  ValueError, with ttsamd_resample_create's words, for a pair of rates whose reduced
+    ratio or filter the device resampler refuses (22 050 -> 8 003 Hz: no common factor, o = 22 050)."""
+    if lowpass_filter_width <= 0:
+        raise ValueError('resample: lowpass_filter_width must be positive')
+    o, n = rates(orig_freq, new_freq)
+    if o > MAX_RATIO or n > MAX_RATIO:
+        raise ValueError(f'resample_create: o = {o} / n = {n} outside [1, {MAX_RATIO}] ({int(orig_freq)} -> {int(new_freq)} Hz)')
+    width = int(math.ceil(int(lowpass_filter_width) * o / (min(o, n) * float(rolloff))))
+    if 2 * width + o > MAX_TAPS:
+        raise ValueError(f'resample_create: width {width}: J = 2 * width + o is at most {MAX_TAPS}')
+    return o, n, width
+
+
 def out_len(n_samples, o, n):
     """ceil(n * n_samples / o) in exact integers."""
     return (n * int(n_samples) + o - 1) // o if n_samples > 0 else 0

@@ -14,6 +14,7 @@ from . import lib as L
 
 MAX_WINDOWS = 64            # TTSAMD_STREAM_MAX_WINDOWS of include/ttsamd.h
 DENOISER_HALO = 3           # ttsamd_denoiser_halo_frames(): 768 samples of the 1024 / 256 STFT -> ISTFT round trip
+ENCODINGS = {'float32': 0, 'pcm16': 1, 'mulaw': 2, 'alaw': 3}       # the format codes of ttsamd_stream_emit_resampled
 
 
 def hifigan_halo_frames(config):
@@ -44,6 +45,39 @@ def pcm16(x):
     return np.where(np.isnan(a), np.float32(0), v).astype('<i2')
 
 
+def resample_reach(o, width):
+    """the samples before S0 and after S1 - 1 that the resampler's outputs of a core [S0, S1) can read: width + o - 1.  With
+    K0 = ceil(n S0 / o), K1 = ceil(n S1 / o), f0 = K0 // n and f1 = (K1 - 1) // n: K0 o / n >= S0 gives f0 o >= S0 - o + 1, and
+    (K1 - 1) o / n < S1 gives f1 o <= S1 - 1; frame f reads the samples f o - width ... f o + width + o - 1."""
+    return int(width) + int(o) - 1
+
+
+def resample_halo_frames(o, n, width, hop):
+    """resample_reach in frames of hop samples, rounded up: 2 for 22 050 -> 8 000, 16 000 or 32 000 Hz, 1 for 11 025, 24 000, 44 100, 48 000"""
+    return -(-resample_reach(o, width) // int(hop))
+
+
+def chunk_outputs(core_start, core_end, o, n):
+    """(K0, K1): the resampler's outputs that belong to the core [core_start, core_end) (samples): ceil(n S / o) at both ends, in
+    exact integers.  The cores of an utterance partition [0, L), so these ranges partition [0, out_len(L))."""
+    return -(-n * int(core_start) // o), -(-n * int(core_end) // o)
+
+
+def delivery(source_rate, sample_rate=None, encoding=None, pcm16=False, lowpass_filter_width=6, rolloff=0.99):
+    """The delivery arguments of StreamingVocoder, checked on the host -> (encoding, sample_rate, (o, n, width) or None when the rate
+    stays).  ValueError: an unknown encoding, pcm16=True next to another encoding, a rate the resampler refuses."""
+    from . import resample as R
+    if encoding is not None and encoding not in ENCODINGS:
+        raise ValueError(f'StreamingVocoder: encoding {encoding!r}: one of {sorted(ENCODINGS)}')
+    if pcm16 and encoding not in (None, 'pcm16'):
+        raise ValueError(f"StreamingVocoder: pcm16=True means encoding='pcm16', got encoding={encoding!r}")
+    encoding = 'pcm16' if pcm16 else (encoding or 'float32')
+    source_rate = int(source_rate)
+    if sample_rate is None or sample_rate == source_rate:
+        return encoding, source_rate, None
+    return encoding, int(sample_rate), R.geometry(source_rate, sample_rate, lowpass_filter_width, rolloff)
+
+
 def plan_chunks(T, first_chunk_frames, chunk_frames, halo_left, halo_right):
     """[(core_start, core_len, win_start, win_len)] for an utterance of T frames.  The cores partition [0, T) in order: the first is
     min(first_chunk_frames, T) frames (a short one: time to first audio), the following ones chunk_frames; a remainder shorter than
@@ -72,10 +106,10 @@ def max_core_frames(first_chunk_frames, chunk_frames):
 
 
 class _Open:
-    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise')
+    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise', 'frames')
 
-    def __init__(self, sid, slot, plan, denoise):
-        self.sid, self.slot, self.plan, self.next, self.denoise = sid, slot, plan, 0, denoise
+    def __init__(self, sid, slot, plan, denoise, frames):
+        self.sid, self.slot, self.plan, self.next, self.denoise, self.frames = sid, slot, plan, 0, denoise, frames
 
 
 class StreamingVocoder:
@@ -84,13 +118,23 @@ class StreamingVocoder:
     vocoder: a vocoder.hifigan.models.Generator (V1 or V3) on the GPU; denoiser: the vocoder.hifigan.denoiser.Denoiser of that
     generator, needed only for open(denoise > 0).  Every buffer is allocated here, once.  open(mel, denoise) -> sid copies a mel into a
     free slot; step() returns the next chunk of every open utterance; an utterance closes itself after its last chunk.  Precision is
-    the library's (ttsamd.engine.set_precision): the step calls the forward entry the one-shot path calls."""
+    the library's (ttsamd.engine.set_precision): the step calls the forward entry the one-shot path calls.
 
-    def __init__(self, vocoder, denoiser=None, max_streams=32, max_frames=4096, chunk_frames=64, first_chunk_frames=32, pcm16=False):
+    sample_rate: the rate the chunks leave at (None: the vocoder's own, vocoder.sampling_rate or 22 050 Hz), through the polyphase
+    resampler of utils.audio.resample with lowpass_filter_width and rolloff; encoding: 'float32' (default) | 'pcm16' | 'mulaw' |
+    'alaw' (G.711, one byte per sample); pcm16=True means encoding='pcm16'.  Put together, the chunks of a stream are the bits of
+    utils.audio.resample on the samples the stream has at the vocoder's rate, encoded.  The vocoder's rate as float32 or PCM16 is the
+    path without a resampler, ttsamd_stream_emit."""
+
+    def __init__(self, vocoder, denoiser=None, max_streams=32, max_frames=4096, chunk_frames=64, first_chunk_frames=32, pcm16=False,
+                 sample_rate=None, encoding=None, lowpass_filter_width=6, rolloff=0.99):
         import torch
         from .engine import DenoiserEngine
         if min(int(max_streams), int(max_frames), int(chunk_frames), int(first_chunk_frames)) < 1:
             raise ValueError('StreamingVocoder: max_streams, max_frames, chunk_frames and first_chunk_frames must be >= 1')
+        source_rate = int(getattr(vocoder, 'sampling_rate', None) or (getattr(vocoder, 'h', None) or {}).get('sampling_rate') or 22050)
+        self._encoding, self._sample_rate, self._rs = delivery(source_rate, sample_rate, encoding, pcm16, lowpass_filter_width, rolloff)
+        pcm16 = self._encoding == 'pcm16'
         self.eng = vocoder.engine()
         self.lib, self.device = self.eng.lib, self.eng.device
         self.hop, self.num_mels = self.eng.hop, self.eng.num_mels
@@ -110,15 +154,25 @@ class StreamingVocoder:
             self._bias = denoiser._bias_spec(self.device).reshape(-1).contiguous()
         self._dn_halo = dn_halo
         dev = self.device
+        # the resampled / G.711 path (ttsamd_stream_emit_resampled); None: ttsamd_stream_emit, as before there was one
+        self._resampled = self._rs is not None or self._encoding in ('mulaw', 'alaw')
+        self._rs_eng, self._rs_halo = None, 0
+        if self._rs is not None:
+            from utils.audio import _resampler
+            self._rs_eng = _resampler(source_rate, self._sample_rate, lowpass_filter_width, rolloff, 'sinc_interp_hann', dev)
+            assert (self._rs_eng.o, self._rs_eng.n, self._rs_eng.width) == self._rs
+            self._rs_halo = resample_halo_frames(*self._rs, self.hop)
         self._core_cap = max_core_frames(first_chunk_frames, chunk_frames)
-        self._w_cap = (self._core_cap + left.value + right.value + 2 * dn_halo + 3) & ~3
+        self._w_cap = (self._core_cap + left.value + right.value + 2 * dn_halo + 2 * self._rs_halo + 3) & ~3
         self._rows = min(MAX_WINDOWS, self.max_streams)
         self._pool = torch.zeros(self.max_streams, self.num_mels, self.max_frames, dtype=torch.float32, device=dev)
         self._batch = torch.empty(self._rows * self.num_mels * self._w_cap, dtype=torch.float32, device=dev)
         self._lens = torch.empty(self._rows, dtype=torch.int64, device=dev)
         self._wave = torch.empty(self._rows * self.hop * self._w_cap, dtype=torch.float32, device=dev)
-        out_dtype = torch.int16 if self.pcm16 else torch.float32
-        self._out = [torch.empty(self._rows * self.hop * self._core_cap, dtype=out_dtype, device=dev) for _ in range(2)]
+        out_dtype = {'float32': torch.float32, 'pcm16': torch.int16}.get(self._encoding, torch.uint8)
+        o, n = self._rs[:2] if self._rs else (1, 1)
+        self._c_cap = self.hop * self._core_cap if not self._resampled else -(-n * self.hop * self._core_cap // o) + 1
+        self._out = [torch.empty(self._rows * self._c_cap, dtype=out_dtype, device=dev) for _ in range(2)]
         self._flip = 0
         self._free = list(range(self.max_streams))
         self._open = {}                 # sid -> _Open, in opening order (oldest first)
@@ -128,6 +182,16 @@ class StreamingVocoder:
     def halo(self):
         """(left, right) receptive field of the vocoder in mel frames: ttsamd_hifigan_halo_frames of its handle"""
         return self._halo
+
+    @property
+    def sample_rate(self):
+        """the rate the chunks leave at, Hz"""
+        return self._sample_rate
+
+    @property
+    def encoding(self):
+        """'float32' | 'pcm16' | 'mulaw' | 'alaw'"""
+        return self._encoding
 
     @property
     def free_slots(self):
@@ -158,13 +222,13 @@ class StreamingVocoder:
                                  f'shortest has {self.hop * T}')
         if not self._free:
             raise ValueError(f'StreamingVocoder.open: all {self.max_streams} slots are taken (max_streams)')
-        halo = self._dn_halo if denoise > 0 else 0
+        halo = (self._dn_halo if denoise > 0 else 0) + self._rs_halo
         plan = plan_chunks(T, self.first_chunk_frames, self.chunk_frames, self._halo[0] + halo, self._halo[1] + halo)
         slot = self._free.pop(0)
         self._pool[slot, :, :T].copy_(mel.to(dtype=torch.float32), non_blocking=True)
         sid = self._next_sid
         self._next_sid += 1
-        self._open[sid] = _Open(sid, slot, plan, denoise)
+        self._open[sid] = _Open(sid, slot, plan, denoise, T)
         return sid
 
     def close(self, sid):
@@ -173,9 +237,10 @@ class StreamingVocoder:
 
     def step(self):
         """The next chunk of every open utterance, oldest first, at most 64 -> [(sid, chunk, last)]: chunk is a device tensor of
-        hop * core_len samples (float32, or int16 with pcm16), valid until the step after next; `last` marks an utterance's final
-        chunk, after which it is closed.  One gather, one vocoder forward, one denoise (when a row asks for it) and one emit on the
-        current stream; the host waits for none of them."""
+        hop * core_len samples (float32, or int16 with pcm16) -- at another sample_rate, of the resampler's outputs that belong to the
+        core (`chunk_outputs`: float32, int16, or uint8 for G.711) --, valid until the step after next; `last` marks an utterance's
+        final chunk, after which it is closed.  One gather, one vocoder forward, one denoise (when a row asks for it) and one emit on
+        the current stream; the host waits for none of them (the chunk lengths are host arithmetic)."""
         import torch
         from .engine import _ptr, _stream
         rows = list(self._open.values())[:self._rows]
@@ -185,7 +250,13 @@ class StreamingVocoder:
         i32 = C.c_int32 * W
         chunks = [st.plan[st.next] for st in rows]
         w_max = (max(c[3] for c in chunks) + 3) & ~3
-        c_max = self.hop * max(c[1] for c in chunks)
+        if self._resampled:
+            o, n = self._rs[:2] if self._rs else (1, 1)
+            k = [chunk_outputs(self.hop * c[0], self.hop * (c[0] + c[1]), o, n) for c in chunks]
+            counts = [k1 - k0 for k0, k1 in k]
+        else:
+            counts = [self.hop * c[1] for c in chunks]
+        c_max = max(max(counts), 1)
         slot, start, length = i32(*[st.slot for st in rows]), i32(*[c[2] for c in chunks]), i32(*[c[3] for c in chunks])
         off, n = i32(*[self.hop * (c[0] - c[2]) for c in chunks]), i32(*[self.hop * c[1] for c in chunks])
         out = self._out[self._flip]
@@ -207,14 +278,22 @@ class StreamingVocoder:
                 dws = self._dn_eng.ws.get(nb, self.device)
                 L.check(lib.ttsamd_denoise_rows(self._dn_eng.handle, _ptr(self._wave), n_max, _ptr(nsamples), W, n_max, _ptr(self._bias),
                                                 _ptr(strength), _ptr(dws), nb, _stream()), 'denoise_rows')
-            L.check(lib.ttsamd_stream_emit(_ptr(self._wave), W, w_max, self.hop, off, n, c_max, 1 if self.pcm16 else 0, _ptr(out),
-                                           _stream()), 'stream_emit')
+            if self._resampled:
+                hop = self.hop
+                L.check(lib.ttsamd_stream_emit_resampled(self._rs_eng.handle if self._rs_eng else None, _ptr(self._wave), W, w_max, hop,
+                                                         i32(*[hop * c[2] for c in chunks]), i32(*[hop * c[3] for c in chunks]),
+                                                         i32(*[hop * st.frames for st in rows]), i32(*[hop * c[0] for c in chunks]),
+                                                         i32(*[hop * (c[0] + c[1]) for c in chunks]), c_max, ENCODINGS[self._encoding],
+                                                         _ptr(out), None, _stream()), 'stream_emit_resampled')
+            else:
+                L.check(lib.ttsamd_stream_emit(_ptr(self._wave), W, w_max, self.hop, off, n, c_max, 1 if self.pcm16 else 0, _ptr(out),
+                                               _stream()), 'stream_emit')
         view = out[:W * c_max].view(W, c_max)
         res = []
         for w, (st, c) in enumerate(zip(rows, chunks)):
             st.next += 1
             last = st.next == len(st.plan)
-            res.append((st.sid, view[w, :self.hop * c[1]], last))
+            res.append((st.sid, view[w, :counts[w]], last))
             if last:
                 self.close(st.sid)
         return res

@@ -84,8 +84,22 @@ class MelSpectrogram(_MelModule):
 
 def save_wav(path, wave, sample_rate=22_050, encoding='PCM_S', bits_per_sample=16):
     """wave: 1-D (or [1, n]) float tensor/array in [-1, 1].  'PCM_S' 16-bit (torchaudio.save's default for
-    .wav from float32 is 32-bit float: pass encoding='PCM_F') -> little-endian RIFF/WAVE, mono."""
+    .wav from float32 is 32-bit float: pass encoding='PCM_F') -> little-endian RIFF/WAVE, mono.
+    'ULAW' / 'ALAW' with bits_per_sample=8 (torchaudio's names): G.711, WAVE format 7 / 6 with an 18-byte fmt chunk and a fact chunk;
+    wave is then float samples (encoded as `encode` does: PCM16 first) or uint8 data that is already encoded."""
     a = wave.detach().cpu().numpy() if hasattr(wave, 'detach') else np.asarray(wave)
+    if encoding in ('ULAW', 'ALAW') and bits_per_sample == 8:
+        from ttsamd import g711
+        from ttsamd.stream import pcm16
+        a = a.reshape(-1)
+        if a.dtype != np.uint8:
+            a = (g711.lin2ulaw if encoding == 'ULAW' else g711.lin2alaw)(pcm16(a))
+        data = a.tobytes()
+        fmt = struct.pack('<IHHIIHHH', 18, 7 if encoding == 'ULAW' else 6, 1, sample_rate, sample_rate, 1, 8, 0)
+        body = b'WAVE' + b'fmt ' + fmt + b'fact' + struct.pack('<II', 4, len(data)) + b'data' + struct.pack('<I', len(data)) + data
+        with open(path, 'wb') as f:
+            f.write(b'RIFF' + struct.pack('<I', len(body) + (len(data) & 1)) + body + b'\0' * (len(data) & 1))
+        return
     a = np.asarray(a, dtype=np.float32).reshape(-1)
     if encoding == 'PCM_F':
         fmt, bits, data = 3, 32, a.astype('<f4').tobytes()
@@ -109,8 +123,8 @@ def peak_normalise(wave, peak=0.99):
 
 
 def load_wav(path):
-    """Little-endian RIFF/WAVE -> (float32 array [n] in [-1, 1], sample_rate): 16-bit PCM (x / 32768) and 32-bit float, what save_wav
-    writes; several channels are averaged to one.  Anything else raises ValueError.  The samples come back at the file's own rate:
+    """Little-endian RIFF/WAVE -> (float32 array [n] in [-1, 1], sample_rate): 16-bit PCM (x / 32768), 32-bit float and 8-bit G.711
+    (format 7 mu-law, 6 A-law: decoded to 16 bits, then x / 32768), what save_wav writes; several channels are averaged to one.  Anything else raises ValueError.  The samples come back at the file's own rate:
 `load_recording` adds the resampler."""
     with open(path, 'rb') as f:
         raw = f.read()
@@ -132,11 +146,53 @@ def load_wav(path):
         a = np.frombuffer(data[:len(data) // 2 * 2], dtype='<i2').astype(np.float32) / 32768.0
     elif code == 3 and bits == 32:
         a = np.frombuffer(data[:len(data) // 4 * 4], dtype='<f4').astype(np.float32)
+    elif code in (6, 7) and bits == 8:
+        a = decode(np.frombuffer(data, dtype=np.uint8), 'mulaw' if code == 7 else 'alaw')
     else:
-        raise ValueError(f'{path}: format {code} with {bits} bits: 16-bit PCM and 32-bit float are read')
+        raise ValueError(f'{path}: format {code} with {bits} bits: 16-bit PCM, 32-bit float and 8-bit G.711 are read')
     if channels > 1:
         a = a[:len(a) // channels * channels].reshape(-1, channels).mean(axis=1).astype(np.float32)
     return a, int(rate)
+
+
+def encode(wave, encoding, lens=None):
+    """Device tensor [..., n] of float samples -> int16 ('pcm16': clip(rint(x * 32767)), save_wav's arithmetic) or uint8 G.711 bytes
+    ('mulaw' | 'alaw', from that PCM16 value) of the same shape, on the device (ttsamd_wave_encode: the encoder of the streaming emit).
+    lens (int64 [rows]): samples per row of a ragged batch; a row is zero behind its length.  Nothing is read back to the host."""
+    import ctypes as C
+    from ttsamd import lib as L
+    from ttsamd.stream import ENCODINGS
+    _device_wave(wave, 'encode')
+    if encoding not in ('pcm16', 'mulaw', 'alaw'):
+        raise ValueError(f"encode: encoding {encoding!r}: one of 'pcm16', 'mulaw', 'alaw'")
+    x = wave.to(torch.float32).contiguous()
+    shape = x.shape
+    rows, n = (x.numel() // shape[-1] if shape[-1] else 0), shape[-1]
+    out = torch.zeros(shape, dtype=torch.int16 if encoding == 'pcm16' else torch.uint8, device=x.device)
+    if rows and n:
+        if lens is not None:
+            lens = torch.as_tensor(lens).to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+            if lens.numel() != rows:
+                raise ValueError(f'encode: {lens.numel()} lengths for {rows} rows')
+        with torch.cuda.device(x.device):
+            L.check(L.load().ttsamd_wave_encode(C.c_void_p(x.data_ptr()), n, C.c_void_p(lens.data_ptr()) if lens is not None else None, rows,
+                                                ENCODINGS[encoding], C.c_void_p(out.data_ptr()), n,
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'wave_encode')
+    return out
+
+
+def decode(data, encoding):
+    """Host array or tensor of 'pcm16' (int16) or 'mulaw' / 'alaw' (uint8) data -> float32 numpy array, value / 32768 (load_wav's
+    convention); the G.711 decoders are the standard's (ttsamd/g711.py)."""
+    from ttsamd import g711
+    a = data.detach().cpu().numpy() if hasattr(data, 'detach') else np.asarray(data)
+    if encoding == 'pcm16':
+        pcm = a.astype(np.int16)
+    elif encoding in g711.DECODERS:
+        pcm = g711.DECODERS[encoding](a.astype(np.uint8))
+    else:
+        raise ValueError(f"decode: encoding {encoding!r}: one of 'pcm16', 'mulaw', 'alaw'")
+    return pcm.astype(np.float32) / np.float32(32768.0)
 
 
 _resamplers, _trimmers = {}, {}

@@ -78,13 +78,14 @@ class Generator(_HipModule):
             return eng.forward(x[None])
         return eng.forward(x, lens)[:, None, :]
 
-    def stream(self, mel, chunk_frames=64, first_chunk_frames=32, pcm16=False, denoiser=None, denoise=0.0):
+    def stream(self, mel, chunk_frames=64, first_chunk_frames=32, pcm16=False, denoiser=None, denoise=0.0, sample_rate=None, encoding=None):
         """Extension (ttsamd.stream): mel [80, T] -> a generator of device chunks (float32, or int16 PCM with pcm16) whose concatenation
         is forward(mel)'s 256 T samples within fp32 summation order, the first after first_chunk_frames frames of work instead of T.
-        `denoiser` + `denoise` > 0: the bias denoiser per chunk.  A chunk stays valid until the one after next has been taken."""
+        `denoiser` + `denoise` > 0: the bias denoiser per chunk.  sample_rate / encoding ('float32' | 'pcm16' | 'mulaw' | 'alaw'): the
+        chunks leave resampled to that rate and encoded (StreamingVocoder).  A chunk stays valid until the one after next has been taken."""
         from ttsamd.stream import StreamingVocoder
         sv = StreamingVocoder(self, denoiser=denoiser, max_streams=1, max_frames=int(mel.shape[-1]), chunk_frames=chunk_frames,
-                              first_chunk_frames=first_chunk_frames, pcm16=pcm16)
+                              first_chunk_frames=first_chunk_frames, pcm16=pcm16, sample_rate=sample_rate, encoding=encoding)
         sv.open(mel, denoise)
         while sv.open_streams:
             for _, chunk, _ in sv.step():
