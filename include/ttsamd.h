@@ -849,6 +849,49 @@ int32_t ttsamd_stream_emit_resampled(void* resample_handle, const float* wave, i
 int32_t ttsamd_wave_encode(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t format, void* out,
                            int64_t out_stride, void* stream);
 
+/* ---- output levelling (csrc/loudness.hip): ITU-R BS.1770-4 integrated loudness and peak per row of a ragged mono batch, and one
+ * gain per row towards a target.  wave [batch][wave_stride] fp32; nsamples: device int64 [batch], clamped to [0, wave_stride];
+ * nothing at or past nsamples[b] is read or written, and nothing is read back to the host.
+ *
+ * K-weighting at sample_rate fs (8000 <= fs <= 192000): two biquads by the bilinear transform, in float64.  Stage 1 (shelf):
+ * f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ * Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2, b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],
+ * a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0].  Stage 2 (high-pass): f0 = 38.13547087602444, Q = 0.5003270373238773,
+ * b = [1, -2, 1], a as in stage 1 with this stage's K and Q.  (At 48 kHz: the standard's table to its 14 decimals.)
+ * y = stage 2 of stage 1 of the row from a zero state, in float64.  step = (fs + 5) / 10 samples (integer division: fs / 10 rounded,
+ * a half upwards), block = 4 step.  A row of n >= block samples has J = (n - block) / step + 1 blocks, z_j = mean of y^2 over
+ * [j step, j step + block); a row of 0 < n < block samples has the one block z_0 = mean of y^2 over its n samples (the standard
+ * leaves such rows undefined); n = 0 has none.  l_j = -0.691 + 10 log10 z_j; absolute gate l_j > -70;
+ * Gamma = -0.691 + 10 log10(mean of the z_j that pass it) - 10; L = -0.691 + 10 log10(mean of the z_j with l_j > -70 and
+ * l_j > Gamma), -inf when no block passes the absolute gate.  peak = max |x| over the row, exact.
+ * The filter runs as a scan: a row is cut into segments of S samples (S = the largest divisor of step that is <= 64), each segment's
+ * zero-state response ends in a state that a second launch carries along the row with the 4 x 4 transition matrix of one segment
+ * (built on the host with the coefficients), a third launch filters every segment again from its true state and sums y^2.  Four
+ * launches whatever the lengths; every reduction has a fixed order that depends on the row's own length only, so row b of a batch
+ * has the bits the row has alone. */
+/* HOST out[10] float64: b1[0..2], a1[1..2], b2[0..2], a2[1..2]; TTSAMD_EINVAL outside 8000..192000.  Needs no GPU. */
+int32_t ttsamd_loudness_coefficients(int32_t sample_rate, double* out);
+/* bytes of workspace ttsamd_loudness_measure needs for this batch, stride and rate; -1: refused (batch < 1, a negative stride or
+ * one of 2^40 and more, a rate outside 8000..192000) */
+int64_t ttsamd_loudness_workspace_bytes(int32_t batch, int64_t wave_stride, int32_t sample_rate);
+/* loudness: device float64 [batch] (LUFS, -inf for a silent or empty row); peak: device fp32 [batch].  1 <= batch <= 65535.
+ * TTSAMD_EINVAL (nothing launched): a NULL pointer, batch < 1, a rate out of range, a workspace smaller than
+ * ttsamd_loudness_workspace_bytes. */
+int32_t ttsamd_loudness_measure(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t sample_rate,
+                                double* loudness, float* peak, void* workspace, int64_t workspace_bytes, void* stream);
+/* One launch: every row's gain from its loudness and peak (what ttsamd_loudness_measure wrote) and its mode and target (device int32 /
+ * fp32 [batch], as ttsamd_denoise_rows takes its strengths), applied in place to samples [0, nsamples[b]); gain_out: device fp32 [batch].
+ * mode 0: the row is not written, gain 1.  mode 1 (peak): x <- fl32(fl32(x / peak) * target) (numpy's float32 `x / m * 0.99`,
+ * ttsamd_trim_apply's convention), gain_out = fl32(target / peak); peak == 0: not written, gain 1.  mode 2 (loudness, target in LUFS):
+ * g = 10^((target - L) / 20) in float64; if peak g > ceiling, g = ceiling / peak (a cap on the gain, no limiter); g is rounded once
+ * to fp32 (and taken one fp32 step down if fl32(peak g) > ceiling, so that the levelled peak never exceeds the ceiling) and
+ * x <- fl32(x g); L not finite or peak == 0: not written, gain 1.
+ * TTSAMD_EINVAL (nothing launched): a NULL pointer, batch < 1, a ceiling that is not in (0, 1].  The modes live on the device and are
+ * not read back: the callers check them on the host before the upload (ttsamd.engine.LoudnessEngine.level refuses a mode outside
+ * 0 .. 2 there), and the kernel leaves a row whose device value is outside 0 .. 2 as mode 0 does. */
+int32_t ttsamd_wave_level(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
+                          const float* target, float ceiling, const double* loudness, const float* peak, float* gain_out, void* stream);
+
 /* Timing hooks for bench.py (roofline of the dominant kernel): when enabled, hifigan
  * forward brackets its ResBlock conv launches with HIP events on the launch stream. */
 int32_t ttsamd_profile_enable(int32_t on);

@@ -15,6 +15,16 @@ from utils.audio import resample, save_wav  # noqa: E402
 WAV_ENCODINGS = {'pcm16': ('PCM_S', 16), 'float32': ('PCM_F', 32), 'mulaw': ('ULAW', 8), 'alaw': ('ALAW', 8)}
 
 
+def normalize_option(text):
+    """--normalize: 'peak', 'lufs' or a number (a target in LUFS)"""
+    if text in ('peak', 'lufs'):
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r}: 'peak', 'lufs' or a target in LUFS such as -16")
+
+
 def infer(args):
     if args.cpu or not torch.cuda.is_available():
         raise SystemExit('inference.py: this build runs on an MI355X only (no CPU path); drop --cpu')
@@ -33,7 +43,7 @@ def infer(args):
     with open(os.path.join(args.out_dir, 'index.tsv'), 'w', encoding='utf-8') as index:
         for k in range(0, len(lines), args.batch_size):
             batch = lines[k:k + args.batch_size]
-            wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed)
+            wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, normalize=args.normalize)
             for line, wav in zip(batch, wavs):
                 if rate != 22_050:                      # the finished wave through the device resampler, then the matching file format
                     wav = resample(wav.reshape(1, -1).to('cuda'), 22_050, rate)[0]
@@ -58,6 +68,8 @@ def main(argv=None):
     # not in the reference: the rate and the encoding of the files (8000 + mulaw / alaw: G.711 telephony files, WAVE format 7 / 6)
     p.add_argument('--sample_rate', type=int, default=None)
     p.add_argument('--encoding', type=str, default='pcm16', choices=sorted(WAV_ENCODINGS))
+    # ... and the level of every wave, set on the device: peak (x / max|x| * 0.99), lufs (-23 LUFS, ITU-R BS.1770-4) or a target in LUFS
+    p.add_argument('--normalize', type=normalize_option, default=None, metavar='peak|lufs|<LUFS>')
     infer(p.parse_args(argv))
 
 

@@ -23,7 +23,7 @@ from ttsamd.engine import average_pitch as _average_pitch
 from ttsamd.engine import binarization_loss as _binarization_loss
 from ttsamd.engine import forward_sum_loss as _forward_sum_loss
 from ttsamd.engine import mas as _mas
-from ttsamd.engine import check_finite, check_speakers, per_row, row_values
+from ttsamd.engine import check_finite, check_normalize, check_speakers, level_waves, per_row, row_values
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
@@ -41,7 +41,7 @@ def text_collate_fn(batch: List[torch.Tensor]):
     return ids_pad, lens_sorted, sort_ids.argsort()
 
 
-# ---- mixed requests: `speed`, `speaker_id`, `pitch_mul`, `pitch_add` (and `denoise` on the wave side) are one scalar for all lines or a
+# ---- mixed requests: `speed`, `speaker_id`, `pitch_mul`, `pitch_add` (and `denoise` and `normalize` on the wave side) are one scalar for all lines or a
 # list with one value per line.  A list follows its lines through every reordering (the collate sort, the chunks, the length-sorted
 # groups) by being indexed with the same positions as the lines: _take.
 def _take(value, idx):
@@ -53,10 +53,12 @@ def _at(value, i):
     return value[i] if per_row(value) else value
 
 
-def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1., pitch_add=0., denoise=0.):
+def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1., pitch_add=0., denoise=0., normalize=None):
     """Host-side validation of per-line controls before any work: a list must have one value per line (ValueError), speakers lie in
     [0, n_speakers) (IndexError), speeds are finite and > 0, pitch values and denoise strengths finite (ValueError).  Scalars pass
-    through to the checks of the calls that take them."""
+    through to the checks of the calls that take them.  `normalize` (the level of the wave: None, 'peak', 'lufs' or a finite target in
+    LUFS, one for all lines or one per line) is checked in both forms: nothing below looks at it before the vocoder has run."""
+    check_normalize(normalize, n_lines)
     for what, v in (('speed', speed), ('speaker_id', speaker_id), ('pitch_mul', pitch_mul), ('pitch_add', pitch_add), ('denoise', denoise)):
         if not per_row(v):
             continue
@@ -392,23 +394,29 @@ class FastPitch2Wave(nn.Module):
     def forward(self, x):
         return x
 
+    sample_rate = 22050         # of the vocoder's wave: what `normalize` measures the loudness at
+
     @torch.inference_mode()
     def tts_single(self, text_buckw: str, speed: float = 1, speaker_id: int = 0, denoise: float = 0,
-                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False):
+                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None):
+        check_normalize(normalize, 1)
         mel_spec = self.model.ttmel_single(text_buckw, speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
                                            pitch_add=pitch_add)
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
+        if normalize is not None:
+            wave = level_waves(wave, None, normalize, self.sample_rate)
         if return_mel:
             return wave[0].cpu(), mel_spec
         return wave[0].cpu()
 
-    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add):
+    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize=None):
         """What tts_batch and tts_batch_device share: (wave [B, n_max], n_samples int64 [B], reverse_ids), rows in the collate order (longest
         first).  Every control is a scalar or one value per line of `batch`; a per-line denoise strength goes through the same sort as
-        the lines, and a line whose strength is not > 0 keeps its vocoder output bit for bit."""
-        check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise)
+        the lines, and a line whose strength is not > 0 keeps its vocoder output bit for bit.  `normalize` takes the same sort; the
+        rows are levelled on the device after the denoiser (ttsamd.engine.level_waves)."""
+        check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise, normalize=normalize)
         mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
                                                                     pitch_add)
         wave = self.vocoder.engine().forward(mel, dec_lens)             # one ragged batched launch sequence
@@ -416,22 +424,24 @@ class FastPitch2Wave(nn.Module):
         denoise = _take(denoise, reverse_ids.argsort().tolist())
         if any(d > 0 for d in denoise) if per_row(denoise) else denoise > 0:
             wave = self.denoiser.forward_batch(wave, n, denoise)
+        if normalize is not None:
+            wave = level_waves(wave, n, _take(normalize, reverse_ids.argsort().tolist()), self.sample_rate)
         return wave, n, reverse_ids
 
     @torch.inference_mode()
     def tts_batch_device(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0,
-                         vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False):
+                         vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None):
         """`tts_batch` without the device->host copy: (wave [B, n_max] float32, n_samples int64 [B]), both in HBM,
         rows in the order of `batch` (zeros past n_samples[b]).  What the data-parallel gather (ttsamd.dp) and
         any GPU-side consumer take; `tts_batch` is this plus one D2H."""
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add)
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize)
         rev = reverse_ids.to(wave.device)
         return wave.index_select(0, rev), n.index_select(0, rev)
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0, vowelizer=None,
-                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False):
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add)
+                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None):
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize)
         n = n.tolist()
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:347-350); so do we
@@ -439,7 +449,7 @@ class FastPitch2Wave(nn.Module):
 
     def tts(self, text_input: Union[str, List[str]], speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
             batch_size: int = 2, vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.,
-            return_mel: bool = False) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:352-435): str -> Tensor[n_samples] (CPU);
         list -> list of tensors, chunked by `batch_size`.
         Mixed requests (not in the reference): for a list of lines, speed, denoise, speaker_id, pitch_mul and pitch_add each take a scalar
@@ -447,12 +457,19 @@ class FastPitch2Wave(nn.Module):
         groups of the batch_size = 1 pipeline, and wave i answers line i with its own options.  With a list for speed, speaker_id, pitch_mul or pitch_add the rows of every batch
         are computed as if alone (FastPitch.infer(alone=True)): requests are independent, so wave i equals tts_single(line i, its options)
         within fp32 summation order at every batch_size; all scalars keep the reference's padded-batch arithmetic (a `denoise` list
-        on its own does too: the strength has no bearing on FastPitch)."""
+        on its own does too: the strength has no bearing on FastPitch).
+        normalize (not in the reference, whose server ends with wave / max|wave| * 0.99 on the host): the level of every wave, set on
+        the device after the denoiser and before the copy to the host -- None (as it comes from the vocoder), 'peak' (x / max|x| * 0.99:
+        the bits of utils.audio.peak_normalise on that wave), 'lufs' (ITU-R BS.1770-4 integrated loudness -23 LUFS) or a target in LUFS
+        (one gain per wave, capped so that the peak stays <= 0.99), or for a list of lines one such value per line.  It changes
+        nothing in front of it: a wave is its un-normalised wave, levelled."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, pitch_mul=pitch_mul, pitch_add=pitch_add)
+        if normalize is not None and not (per_row(normalize) and all(v is None for v in normalize)):
+            kw['normalize'] = normalize         # (None, or only None: the calls below get exactly the arguments they got before)
         if isinstance(text_input, str):
             return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw)
         assert isinstance(text_input, list)
-        check_line_controls(len(text_input), self.model.net_config['n_speakers'], **kw)
+        check_line_controls(len(text_input), self.model.net_config['n_speakers'], **dict(kw, normalize=normalize))
         if (len(text_input) > batch_size and not return_mel and self.device.type == 'cuda'
                 and os.environ.get('TTSAMD_TTS_PIPELINE', '1') != '0'):
             return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw)
@@ -470,18 +487,20 @@ class FastPitch2Wave(nn.Module):
     REQUEST_DEFAULTS = dict(speed=1., denoise=0.005, speaker_id=0, pitch_mul=1., pitch_add=0.)
 
     def tts_requests(self, requests, batch_size: int = 32, vowelizer=None):
-        """A server's queue in one go: `requests` is a list of dicts with `text` and any of speed, denoise, speaker_id, pitch_mul, pitch_add
+        """A server's queue in one go: `requests` is a list of dicts with `text` and any of speed, denoise, speaker_id, pitch_mul, pitch_add, normalize
         (the per-request options of the reference's app); returns one wave per request, in request order, from ONE `tts` call with the
         options as per-line lists -- requests with different options share batches instead of one call per distinct option tuple."""
         requests = list(requests)
         for i, r in enumerate(requests):
-            extra = set(r) - set(self.REQUEST_DEFAULTS) - {'text'}
+            extra = set(r) - set(self.REQUEST_DEFAULTS) - {'text', 'normalize'}
             if 'text' not in r or not isinstance(r['text'], str) or extra:
-                raise ValueError(f'request {i}: needs a `text` string and takes {sorted(self.REQUEST_DEFAULTS)}'
+                raise ValueError(f'request {i}: needs a `text` string and takes {sorted(self.REQUEST_DEFAULTS) + ["normalize"]}'
                                  + (f' (got {sorted(extra)})' if extra else ''))
         if not requests:
             return []
         lists = {k: [r.get(k, d) for r in requests] for k, d in self.REQUEST_DEFAULTS.items()}
+        if any(r.get('normalize') is not None for r in requests):
+            lists['normalize'] = [r.get('normalize') for r in requests]
         return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
     # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
@@ -644,7 +663,7 @@ class FastPitch2Wave(nn.Module):
 
     @torch.inference_mode()
     def _tts_list_pipelined(self, text_input, batch_size, speed, denoise, speaker_id, vowelizer, pitch_mul, pitch_add,
-                            return_mel=False):
+                            return_mel=False, normalize=None):
         """The list path of `tts` over several chunks, as a three-stage pipeline on three HIP streams: tokenisation + FastPitch
         of the next chunks (host work and ~150 short launches that leave most CUs idle) run under the vocoder + denoiser of the
         previous ones, whose audio is copied to the host on a third stream.  FastPitch sees exactly the chunks of the one-stream
@@ -679,7 +698,8 @@ class FastPitch2Wave(nn.Module):
             group = (n_in + n_groups - 1) // n_groups
             text_input = [text_input[i] for i in order]
             # per-line controls take the sort of their lines; from here on position p of every list belongs to text_input[p]
-            speed, denoise, speaker_id, pitch_mul, pitch_add = (_take(v, order) for v in (speed, denoise, speaker_id, pitch_mul, pitch_add))
+            speed, denoise, speaker_id, pitch_mul, pitch_add, normalize = (_take(v, order) for v in (speed, denoise, speaker_id, pitch_mul,
+                                                                                                     pitch_add, normalize))
 
         def flush(item):
             wave, n, done = item
@@ -743,6 +763,8 @@ class FastPitch2Wave(nn.Module):
                         wave = self.denoiser.forward_batch(wave, lens_d * hop, dn, nsamples_min=min(n_dn))
                 elif dn > 0:
                     wave = self.denoiser.forward_batch(wave, lens_d * hop, dn, nsamples_min=min(n_host))
+                if normalize is not None:
+                    wave = level_waves(wave, lens_d * hop, _take(normalize, pos), self.sample_rate)
                 done = torch.cuda.Event()
                 done.record(s_hg)
             if pending is not None:

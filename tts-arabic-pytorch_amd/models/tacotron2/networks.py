@@ -19,6 +19,7 @@ from text.symbols import EOS_TOKENS, SEPARATOR_TOKEN
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
 from vocoder import load_hifigan
+from ttsamd.engine import check_normalize, level_waves, per_row
 from vocoder.hifigan.denoiser import Denoiser
 
 from .tacotron2_ms import Tacotron2MS
@@ -173,20 +174,26 @@ class Tacotron2Wave(nn.Module):
     def forward(self, x):
         return x
 
+    sample_rate = 22050         # of the vocoder's wave: what `normalize` measures the loudness at
+
     @torch.inference_mode()
     def tts_single(self, text_input: str, speed: Union[int, float, None] = None, speaker_id: int = 0,
-                   denoise: float = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False):
+                   denoise: float = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False, normalize=None):
+        check_normalize(normalize, 1)
         mel_spec = self.model.ttmel_single(text_input, speaker_id, speed, vowelizer, postprocess_mel)
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
+        if normalize is not None:
+            wave = level_waves(wave, None, normalize, self.sample_rate)
         if return_mel:
             return wave[0].cpu(), mel_spec
         return wave[0].cpu()
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: Union[int, float, None] = None, denoise: float = 0,
-                  speaker_id: int = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False):
+                  speaker_id: int = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False, normalize=None):
+        check_normalize(normalize, len(batch))
         mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel)
         eng = self.vocoder.engine()
         lens_host = [m.shape[-1] for m in mel_list]
@@ -198,23 +205,31 @@ class Tacotron2Wave(nn.Module):
         n = [t * eng.hop for t in lens_host]
         if denoise > 0:
             wave = self.denoiser.forward_batch(wave, lens * eng.hop, denoise, nsamples_min=min(n))
+        if normalize is not None:
+            wave = level_waves(wave, lens * eng.hop, normalize, self.sample_rate)       # on the device, after the denoiser
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:348-351); so do we
         return [wave[i, :n[i]].cpu() for i in range(len(mel_list))]
 
     def tts(self, text_buckw: Union[str, List[str]], speed: Union[int, float, None] = None, denoise: float = 0.005,
             speaker_id: int = 0, batch_size: int = 8, vowelizer=None, postprocess_mel: bool = True,
-            return_mel: bool = False) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:353-426): str -> Tensor[n_samples] (CPU); list -> list of
-        tensors, chunked by `batch_size`."""
+        tensors, chunked by `batch_size`.
+        normalize (not in the reference): the level of every wave, set on the device after the denoiser -- None, 'peak' (x / max|x| *
+        0.99), 'lufs' (-23 LUFS, ITU-R BS.1770-4) or a target in LUFS, or for a list of lines one such value per line (as
+        FastPitch2Wave.tts takes it)."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, vowelizer=vowelizer,
                   postprocess_mel=postprocess_mel, return_mel=return_mel)
         if isinstance(text_buckw, str):
-            return self.tts_single(text_buckw, **kw)
+            return self.tts_single(text_buckw, normalize=normalize, **kw)
         assert isinstance(text_buckw, list)
+        check_normalize(normalize, len(text_buckw))
+        at = (lambda i: normalize[i]) if per_row(normalize) else (lambda i: normalize)
         if batch_size == 1:
-            return [self.tts_single(sample, **kw) for sample in text_buckw]
+            return [self.tts_single(sample, normalize=at(i), **kw) for i, sample in enumerate(text_buckw)]
         wav_list = []
         for k in range(0, len(text_buckw), batch_size):
-            wav_list += self.tts_batch(text_buckw[k:k + batch_size], **kw)
+            idx = range(k, min(k + batch_size, len(text_buckw)))
+            wav_list += self.tts_batch(text_buckw[k:k + batch_size], normalize=[at(i) for i in idx] if per_row(normalize) else normalize, **kw)
         return wav_list

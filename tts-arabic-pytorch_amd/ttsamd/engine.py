@@ -1432,3 +1432,120 @@ class TrimEngine:
                 L.check(self.lib.ttsamd_frames_compact(_ptr(mel), _ptr(extra), _ptr(lens), B, Cn, C2, T, float(thresh), _ptr(mel_out),
                                                        _ptr(extra_out), _ptr(lens_out), _stream()), 'frames_compact')
         return mel_out, extra_out, lens_out
+
+
+LEVEL_MODES = {'off': 0, 'peak': 1, 'lufs': 2}
+
+
+class LoudnessEngine:
+    """ttsamd_loudness_measure / ttsamd_wave_level (csrc/loudness.hip) with their workspace: ITU-R BS.1770-4 integrated loudness and the
+    peak per row of a ragged mono batch at `sample_rate`, and one gain per row towards a target.  Nothing is read back to the host."""
+
+    def __init__(self, sample_rate=22050, device='cuda'):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        self.sample_rate = int(sample_rate)
+        coef = (C.c_double * 10)()
+        L.check(self.lib.ttsamd_loudness_coefficients(self.sample_rate, coef), 'loudness_coefficients')
+        self.coefficients = np.array(coef)      # b1[0..2], a1[1..2], b2[0..2], a2[1..2]
+        self.ws = _Workspace()
+
+    def _wave(self, wave, lens):
+        wave = _dev_f32(wave, 2, 'LoudnessEngine: wave')
+        return wave, _dev_lens(lens, wave.shape[0], wave.shape[1], wave.device)
+
+    def measure(self, wave, lens=None):
+        """wave [B, n_max], lens int64 [B] or None -> (loudness float64 [B] in LUFS, -inf for a silent or empty row; peak fp32 [B] =
+        max |x| per row), on the device."""
+        wave, lens = self._wave(wave, lens)
+        B, n_max = wave.shape
+        loud = torch.full((B,), float('-inf'), dtype=torch.float64, device=wave.device)
+        peak = torch.zeros(B, dtype=torch.float32, device=wave.device)
+        if B:
+            nbytes = int(self.lib.ttsamd_loudness_workspace_bytes(B, n_max, self.sample_rate))
+            if nbytes < 0:
+                raise L.TtsAmdError(f'loudness: a batch of {B} rows of {n_max} samples at {self.sample_rate} Hz is refused')
+            ws = self.ws.get(max(nbytes, 1), wave.device)
+            with torch.cuda.device(wave.device):
+                L.check(self.lib.ttsamd_loudness_measure(_ptr(wave), n_max, _ptr(lens), B, self.sample_rate, _ptr(loud), _ptr(peak),
+                                                         _ptr(ws), nbytes, _stream()), 'loudness_measure')
+        return loud, peak
+
+    def level(self, wave, lens, mode, target, ceiling=0.99):
+        """wave [B, n_max] fp32 contiguous on the device, scaled IN PLACE up to lens[b] and returned with the gains fp32 [B].
+        mode: 0 / 'off', 1 / 'peak' (x / max|x| * target), 2 / 'lufs' (towards `target` LUFS, the gain capped so that the peak stays
+        <= ceiling); mode and target are scalars or one value per row, checked here on the host before they go to the device."""
+        if not isinstance(wave, torch.Tensor) or wave.device.type != 'cuda' or wave.dtype != torch.float32 or not wave.is_contiguous() \
+                or wave.dim() != 2:
+            raise L.TtsAmdError('LoudnessEngine.level: expected a contiguous float32 tensor [B, n] on the ROCm device (it is scaled in place)')
+        B, n_max = wave.shape
+        lens = _dev_lens(lens, B, n_max, wave.device)
+        modes = row_values(mode, B, 'level mode') if per_row(mode) else [mode] * B
+        modes = [LEVEL_MODES.get(m, m) if isinstance(m, str) else m for m in modes]
+        for m in modes:
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= int(m) <= 2:
+                raise L.TtsAmdError(f"level: mode {m!r}: one of 0 / 'off', 1 / 'peak', 2 / 'lufs'")
+        targets = row_values(target, B, 'level target') if per_row(target) else [target] * B
+        check_finite(targets, 'level target')
+        if not 0.0 < float(ceiling) <= 1.0:
+            raise L.TtsAmdError(f'level: ceiling {ceiling!r} is not in (0, 1]')
+        gain = torch.ones(B, dtype=torch.float32, device=wave.device)
+        if B:
+            loud, peak = self.measure(wave, lens)
+            mode_d = torch.tensor([int(m) for m in modes], dtype=torch.int32).to(wave.device)
+            with torch.cuda.device(wave.device):
+                L.check(self.lib.ttsamd_wave_level(_ptr(wave), n_max, _ptr(lens), B, _ptr(mode_d), _ptr(_rows_f32(targets, wave.device)),
+                                                   float(ceiling), _ptr(loud), _ptr(peak), _ptr(gain), _stream()), 'wave_level')
+        return wave, gain
+
+
+_levellers = {}
+
+
+def leveller(sample_rate, device):
+    """the LoudnessEngine of (sample rate, device), made once"""
+    key = (int(sample_rate), str(device))
+    if key not in _levellers:
+        _levellers[key] = LoudnessEngine(int(sample_rate), device=device)
+    return _levellers[key]
+
+
+def level_spec(normalize):
+    """One line's `normalize` option of the tts wrappers -> None (off) or (mode, target): 'peak' -> (1, 0.99), 'lufs' -> (2, -23.0), a
+    number -> (2, that many LUFS).  ValueError for anything else."""
+    if normalize is None:
+        return None
+    if isinstance(normalize, str):
+        if normalize == 'peak':
+            return 1, 0.99
+        if normalize == 'lufs':
+            return 2, -23.0
+        raise ValueError(f"normalize: {normalize!r}: None, 'peak', 'lufs' or a target in LUFS")
+    if isinstance(normalize, bool) or not isinstance(normalize, (int, float, np.integer, np.floating)) or not np.isfinite(float(normalize)):
+        raise ValueError(f"normalize: {normalize!r}: None, 'peak', 'lufs' or a finite target in LUFS")
+    return 2, float(normalize)
+
+
+def check_normalize(normalize, n_lines):
+    """Host-side validation of `normalize`: one option, or a list with one option per line (ValueError otherwise)."""
+    if per_row(normalize):
+        vals = row_values(normalize, n_lines, 'normalize')
+        for v in vals:
+            level_spec(v)
+    else:
+        level_spec(normalize)
+
+
+def level_waves(wave, nsamples, normalize, sample_rate=22050, ceiling=0.99):
+    """The levelling step of the tts wrappers, after the denoiser and before the copy to the host: wave [B, n_max] on the device, row b
+    levelled by its option (`normalize`: one option or one per row) over its nsamples[b] samples.  Only None: the wave as it is."""
+    rows = list(normalize) if per_row(normalize) else [normalize] * wave.shape[0]
+    specs = [level_spec(v) for v in rows]
+    if not any(s is not None for s in specs):
+        return wave
+    if len(specs) != wave.shape[0]:
+        raise ValueError(f'normalize: {len(specs)} values for {wave.shape[0]} rows')
+    shape = wave.shape
+    wave = wave.to(torch.float32).reshape(-1, shape[-1]).contiguous()
+    leveller(sample_rate, wave.device).level(wave, nsamples, [s[0] if s else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling)
+    return wave.reshape(shape)

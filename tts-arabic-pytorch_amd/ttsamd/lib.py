@@ -147,6 +147,11 @@ SYMBOLS = {
     'ttsamd_trim_bounds': (_I32, [_P, _I64, _P, _I32, _F, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
     'ttsamd_trim_apply': (_I32, [_P, _I64, _P, _P, _F, _I64, _I32, _P, _I64, _P, _P]),
     'ttsamd_frames_compact': (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    # output levelling (csrc/loudness.hip): the coefficients go to a HOST float64 [10] and need no GPU
+    'ttsamd_loudness_coefficients': (_I32, [_I32, C.POINTER(C.c_double)]),
+    'ttsamd_loudness_workspace_bytes': (_I64, [_I32, _I64, _I32]),
+    'ttsamd_loudness_measure': (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _P]),
+    'ttsamd_wave_level': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _P, _P, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

@@ -5,7 +5,9 @@ Analysis side: `MelSpectrogram` (reference utils/audio.py:6-46), the 80-band mel
 as one HIP launch (csrc/melspec.hip).
 Input side: `resample` / `Resample` (torchaudio.functional.resample's name and defaults), `trim` (librosa.effects.trim's) and
 `prepare_recording` = the clean-up of the reference's scripts/preprocess_audio.py:33-47 (resample with lowpass_filter_width=1024,
-peak 0.999, trim at 23 dB, 768 zeros appended), on the device (csrc/resample.hip, csrc/trim.hip)."""
+peak 0.999, trim at 23 dB, 768 zeros appended), on the device (csrc/resample.hip, csrc/trim.hip).
+Level: `loudness` (ITU-R BS.1770-4 integrated loudness per row), `normalize_loudness` and `peak_normalize`, on the device and per row
+of a ragged batch (csrc/loudness.hip); `peak_normalise` is the host helper for one wave."""
 import struct
 
 import numpy as np
@@ -14,6 +16,7 @@ import torch.nn as nn
 
 from ttsamd import melfb
 from ttsamd.engine import MelSpecEngine, ResampleEngine, TrimEngine
+from ttsamd.engine import leveller as _leveller
 from ttsamd.lib import TtsAmdError
 
 
@@ -227,6 +230,50 @@ def _trimmer(device):
     if str(device) not in _trimmers:
         _trimmers[str(device)] = TrimEngine(device=device)
     return _trimmers[str(device)]
+
+
+def _level_rows(wave, lens, what):
+    """-> (rows [R, n] float32 contiguous, a COPY the levelling kernels may write; lens int64 [R] on the device or None)"""
+    _device_wave(wave, what)
+    x = wave.to(torch.float32).reshape(-1, wave.shape[-1]).contiguous()
+    if lens is not None:
+        lens = torch.as_tensor(lens).to(device=x.device, dtype=torch.int64).reshape(-1).contiguous()
+        if lens.numel() != x.shape[0]:
+            raise ValueError(f'{what}: {lens.numel()} lengths for {x.shape[0]} rows')
+    return x, lens
+
+
+@torch.inference_mode()
+def loudness(wave, sample_rate=22050, lens=None):
+    """Integrated loudness (ITU-R BS.1770-4 / EBU R 128: K-weighting, 400 ms blocks every 100 ms, the absolute gate at -70 LUFS and the
+    relative gate 10 LU under the gated mean) of every row of wave [..., n] -> float64 tensor [rows] in LUFS on the device; -inf for a
+    row with no block above -70 LUFS.  A row shorter than 400 ms is measured as one block over its samples.  lens (int64 [rows]):
+    samples per row of a ragged batch; nothing behind a row's length is read.  No host synchronisation."""
+    x, lens = _level_rows(wave, lens, 'loudness')
+    return _leveller(sample_rate, x.device).measure(x, lens)[0]
+
+
+def _level(wave, lens, sample_rate, mode, target, ceiling, what):
+    x, lens = _level_rows(wave, lens, what)
+    if x.data_ptr() == wave.data_ptr():
+        x = x.clone()                           # the caller's tensor stays as it is
+    out, _ = _leveller(sample_rate, x.device).level(x, lens, mode, target, ceiling)
+    return out.reshape(wave.shape)
+
+
+@torch.inference_mode()
+def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None):
+    """Every row of wave [..., n] scaled by ONE gain to target_lufs (a float or one per row); where that would lift the row's peak
+    above peak_ceiling, the gain is ceiling / peak instead (a cap on the gain, no limiter).  A silent row is returned as it is.  A new
+    tensor on the device; the samples behind lens[row] are copied unchanged."""
+    return _level(wave, lens, sample_rate, 2, target_lufs, peak_ceiling, 'normalize_loudness')
+
+
+@torch.inference_mode()
+def peak_normalize(wave, peak=0.99, lens=None):
+    """`peak_normalise` for a batch on the device: every row of wave [..., n] becomes x / max|x| * peak over its own samples (the bits
+    of peak_normalise on that row); an all-zero row is returned as it is.  A new tensor on the device."""
+    return _level(wave, lens, 22050, 1, peak, 0.99, 'peak_normalize')
 
 
 def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method='sinc_interp_hann', beta=None,
