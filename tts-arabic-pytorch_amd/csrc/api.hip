@@ -214,7 +214,11 @@ bool opt_valid(const OptDesc& d, const char* v) {
     char* end = nullptr;
     errno = 0;
     const long long x = std::strtoll(v, &end, d.kind == 1 ? 16 : 10);
-    return errno == 0 && end != v && *end == '\0' && x >= d.lo && x <= d.hi;
+    if (!(errno == 0 && end != v && *end == '\0' && x >= d.lo && x <= d.hi)) return false;
+    // TTSAMD_WINO4 bits 5 / 6 say HOW the F(4,3) kernel runs k = 7 / 11 (seven-point groups): without bit 1 / 2 it does not run that k at
+    // all and the mask contradicts itself -- an error like any malformed value, not a bit that is quietly ignored
+    if (&d == &kOpts[OPT_WINO4] && (((x & 32) && !(x & 2)) || ((x & 64) && !(x & 4)))) return false;
+    return true;
 }
 void opt_init() {
     std::call_once(g_opt_once, [] {
@@ -678,9 +682,10 @@ int32_t ttsamd_tagger_forward(void* handle, const int64_t* ids, int32_t batch, i
 }
 
 int64_t ttsamd_conv1d_packed_floats(int32_t cout, int32_t cin, int32_t k) {
-    // fp32 packed + bf16 hi/lo planes (+ k = 3 / 7 / 11: the Winograd group filters, conv_wino.hip / conv_wino2.hip)
+    // fp32 packed + bf16 hi/lo planes (+ k = 3 / 7 / 11: the Winograd group filters, conv_wino.hip / conv_wino2.hip / conv_wino4.hip:
+    // F(2,3), F(4,3) six-point and -- k = 7 / 11 -- seven-point)
     return 2 * (int64_t)cin * k * cout_padded(cout) +
-           ((k == 3 || k == 7 || k == 11) ? (int64_t)cin * (wino2_groups(k) + wino4_groups(k)) * cout_padded(cout) : 0);
+           ((k == 3 || k == 7 || k == 11) ? (int64_t)cin * (wino2_groups(k) + wino4_groups(k) + wino44_groups(k)) * cout_padded(cout) : 0);
 }
 
 // [Cout][Cin][k] -> the F(4,3) group filters in the packed layout [cin/8][NGQ][2][cp][4] (same values as pack_wino4_weight, conv_wino4.hip)
@@ -707,6 +712,32 @@ __global__ void pack_wino4_weight_kernel(const float* __restrict__ w, int cout, 
         } else {
             v = g[6];                       // k = 7: the single tap, four copies (planes P0 / P6 / P7 / P5)
         }
+    }
+    out[i] = v;
+}
+
+// [Cout][Cin][k], k = 7 / 11 -> the seven-point group filters in the packed layout [cin/8][NG][2][cp][4] (same values as pack_wino44_weight,
+// conv_wino4.hip: sub-filter s = taps 4 s .. 4 s + 3, the last one has three taps and no U6)
+__global__ void pack_wino44_weight_kernel(const float* __restrict__ w, int cout, int cin, int k, int cp, float* __restrict__ out) {
+    const int ng = k == 7 ? 13 : 20;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = (int64_t)cin * ng * cp;
+    if (i >= n) return;
+    const int pq = (int)(i & 3);
+    const int64_t r = i >> 2;
+    const int co = (int)(r % cp);
+    const int64_t r2 = r / cp;
+    const int kk = (int)(r2 & 1);
+    const int64_t r3 = r2 >> 1;
+    const int t = (int)(r3 % ng), o = (int)(r3 / ng);
+    float v = 0.f;
+    if (co < cout) {
+        const float* g = w + ((int64_t)co * cin + (8 * o + 2 * pq + kk)) * k;
+        const int s = t / 7, j = t % 7;
+        const double g0 = g[4 * s], g1 = g[4 * s + 1], g2 = g[4 * s + 2], g3 = 4 * s + 3 < k ? g[4 * s + 3] : 0.0;
+        v = j == 0 ? (float)(g0 / 4) : (j == 1 ? (float)((g0 + g1 + g2 + g3) / 6) : (j == 2 ? (float)((g0 - g1 + g2 - g3) / 18) :
+            (j == 3 ? (float)((g0 + 2 * g1 + 4 * g2 + 8 * g3) / 72) : (j == 4 ? (float)((g0 - 2 * g1 + 4 * g2 - 8 * g3) / 120) :
+            (j == 5 ? (float)((32 * g0 + 16 * g1 + 8 * g2 + 4 * g3) / 45) : (float)(g3 / 2))))));
     }
     out[i] = v;
 }
@@ -775,6 +806,13 @@ int32_t ttsamd_conv1d_ex(const float* x, const float* w, const float* bias, cons
         hipLaunchKernelGGL(pack_wino4_weight_kernel, dim3((unsigned)((nw4 + 255) / 256)), dim3(256), 0, s, w, cout, cin, k, cp, wino4);
         TTS_CHECK_HIP(hipGetLastError());
         p.w_wino4 = wino4;
+        if (wino44_groups(k) != 0) {
+            float* wino44 = wino4 + nw4;
+            const int64_t nw44 = (int64_t)cin * wino44_groups(k) * cp;
+            hipLaunchKernelGGL(pack_wino44_weight_kernel, dim3((unsigned)((nw44 + 255) / 256)), dim3(256), 0, s, w, cout, cin, k, cp, wino44);
+            TTS_CHECK_HIP(hipGetLastError());
+            p.w_wino44 = wino44;
+        }
     }
     p.y = y; p.y_bs = (int64_t)cout * lin; p.y_cs = lin; p.y_ts = 1;
     p.lens_in = lens; p.lens_out = lens; p.len_in_mul = 1; p.len_out_mul = 1;

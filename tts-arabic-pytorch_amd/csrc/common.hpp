@@ -63,7 +63,7 @@ inline hipError_t lds_opt_in(const void* fn, int bytes, std::atomic<uint64_t>& d
     X(HIFIGAN_STREAMS, 0, 0, 1)   /* ResBlock branches of a HiFi-GAN stage on one / three streams (default: by size) */ \
     X(WINO, 0, 0, 1)              /* fp32 engine: 0 = direct kernels only */                                \
     X(WINO2, 0, 0, 31)            /* F(2,3) decomposition kernel: bit 0 / 1 / 2 = k 3 / 7 / 11, 3 = dilated, 4 = Cout 64 */ \
-    X(WINO4, 0, 0, 31)            /* F(4,3) decomposition kernel: bit 0 / 1 / 2 = k 3 / 7 / 11, 3 = dilated, 4 = k 1 (default 31) */ \
+    X(WINO4, 0, 0, 127)           /* F(4,3) decomposition kernel: bit 0 / 1 / 2 = k 3 / 7 / 11, 3 = dilated, 4 = k 1, 5 / 6 = k 7 / 11 on seven-point groups */ \
     X(FUSED_PAIR, 0, 0, 1)        /* fp32 fused c1 -> c2 pairs: 0 = every pair as two launches */           \
     X(FUSED2, 0, 0, 1)            /* second-generation fused pair off / on */                               \
     X(FUSED2_MASK, 1, 0, 0x1ff)   /* which (C, k) pairs it takes: bit 3 ci + ki (default 00f) */            \
@@ -161,6 +161,8 @@ struct ConvParams {
     int32_t compact;          // set by the launcher (ragged batches): the (utterance, time tile) pair of a block is looked up in the
                               // utterance-major list of LIVE tiles (live_tile below), so every dead block sits at the end of the grid
     unsigned long long* timing;   // unused (nullptr); kept so the kernel argument layout is unchanged
+    const float* w_wino44; // k = 7 / 11: the same conv as SEVEN-point groups [Cin/8][wino44_groups(k)][2][CoutP][4] (conv_wino4.hip, TTSAMD_WINO4 bits 5 / 6;
+                           // nullptr = none: the launch stays on w_wino4).  Both forms travel with a launch, the switch picks one per launch
 };
 constexpr int64_t kSplitKFloats = 4 << 20;   // 16 MB covers every case the launchers pick (direct kernel: < 320 blocks, ~640 blocks wanted; conv_wino4.hip: four C-in slices of a 1 x 256 x 3584 launch = 3.7 M floats)
 constexpr int64_t kSplitKFloatsFp = 8 << 20; // FastPitch: 32 MB, the deep conv-FF conv (1536 -> 384) splits K at batch 4..13 too
@@ -217,12 +219,17 @@ int32_t launch_wino2(const ConvParams& p, hipStream_t stream);
 void pack_wino2_weight(const float* w, int cout, int cin, int k, float* out);   // out: cin * wino2_groups(k) * cout_padded(cout) floats
 // ... and the F(4,3) decomposition (conv_wino4.hip: 6 / 16 / 23 products per output QUAD at k = 3 / 7 / 11): 64 rows x 64 quads per block
 int wino4_groups(int k);                         // groups per octet in the packed weights: 6 / 16 / 24 (k = 11: 23 + one zero group)
+int wino44_groups(int k);                        // ... of the seven-point form: 13 / 20 at k = 7 / 11 (0: no such form)
+constexpr int kWino4Default = 127;               // TTSAMD_WINO4 when unset
+bool wino44_wanted(const ConvParams& p);         // the launch goes to the seven-point groups (has them, and its k's bit is set)
 int wino4_block_outputs(int dil);
 int wino4_ksplit(const ConvParams& p);           // C-in slices the launcher will use for this launch (1 = none)
 int32_t launch_splitk_reduce(const ConvParams& q, hipStream_t stream);   // conv_mfma.hip: y = epilogue(sum of the ksplit partial tensors)
 int32_t launch_wino4(const ConvParams& p, hipStream_t stream);
 void wino4_filter_groups(const float* g, int k, float* o);                      // one (co, ci) filter -> its wino4_groups(k) group filters
 void pack_wino4_weight(const float* w, int cout, int cin, int k, float* out);   // out: cin * wino4_groups(k) * cout_padded(cout) floats
+void wino44_filter_groups(const float* g, int k, float* o);                     // k = 7 / 11: one filter -> its wino44_groups(k) seven-point group filters
+void pack_wino44_weight(const float* w, int cout, int cin, int k, float* out);  // out: cin * wino44_groups(k) * cout_padded(cout) floats
 // Host-side weight re-layout: torch Conv1d [Cout][Cin][K] -> [Cin][K][CoutP]
 void pack_conv_weight(const float* w, int cout, int cin, int k, float* out);
 // torch ConvTranspose1d [Cin][Cout][Kt] (Kt = 2u, stride u, padding p) -> [u][Cin][2][CoutP]

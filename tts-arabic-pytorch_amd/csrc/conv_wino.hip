@@ -412,7 +412,7 @@ int wino_route(const ConvParams& p) {
     if (p.K == 1) {
         // k = 1 (Vocos' pointwise convs and head, FastPitch's qkv / o_net projections) on the F(4,3) kernel's skeleton with nothing to transform
         // (conv_wino4.hip, Wino4Geo::WSHARE): the direct engine's packed weights as they are; TTSAMD_WINO4 bit 4.  Same tile as the F(4,3) launches.
-        const int mask4 = (int)opt_int(OPT_WINO4, 31);
+        const int mask4 = (int)opt_int(OPT_WINO4, kWino4Default);
         const bool ok1 = (mask4 & 16) && p.w != nullptr && p.dil == 1 && p.pad == 0 && p.n_phase == 1 && p.y_ts == 1 && p.CoutP % 64 == 0 &&
                          p.Cin % 32 == 0 && p.in_slope >= 0.f && p.in_slope <= 1.f && !p.x_packed && !p.y_packed &&
                          (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
@@ -426,11 +426,13 @@ int wino_route(const ConvParams& p) {
     }
     if ((p.w_wino == nullptr && p.w_wino4 == nullptr) || (p.K != 3 && p.K != 7 && p.K != 11)) return 0;
     if (p.w_wino4 != nullptr) {
-        // F(4,3) decomposition (conv_wino4.hip): TTSAMD_WINO4=<mask>, bit 0 / 1 / 2 = k 3 / 7 / 11, bit 3 = their dilated convs; default 15.
+        // F(4,3) decomposition (conv_wino4.hip): TTSAMD_WINO4=<mask>, bit 0 / 1 / 2 = k 3 / 7 / 11, bit 3 = their dilated convs, bit 4 = k 1
+        // (above), bit 5 / 6 = what it takes of k = 7 / 11 runs on seven-point groups (13 / 20 products per quad instead of 16 / 23:
+        // launch_wino4 picks the kernel, same tile, same conditions); default 127.
         // (k = 3 -- 6 instead of 8 products per quad -- did not pay with the kernel's first staging path: 414 / 330 vs 392 / 315 us on
         // FastPitch's conv-FF pair; with the aligned 16-byte window loads it does: same-box A/B of the step 55.46 (mask 14) vs 54.68 ms.)
         // 64 rows x 64 quads per block, float4-aligned rows, at least 192 blocks (below: the F(2,3) / direct routing that follows)
-        const int mask4 = (int)opt_int(OPT_WINO4, 31);
+        const int mask4 = (int)opt_int(OPT_WINO4, kWino4Default);
         const int kbit4 = p.K == 3 ? 1 : (p.K == 7 ? 2 : 4);
         const bool ok4 = (mask4 & kbit4) && (p.dil == 1 || (mask4 & 8)) && (p.K != 3 || p.Cin % 16 == 0) &&
                          (p.dil == 1 || p.dil == 3 || p.dil == 5) && p.pad == p.dil * (p.K - 1) / 2 && p.n_phase == 1 && p.y_ts == 1 &&
