@@ -637,6 +637,32 @@ int32_t ttsamd_conv1d(const float* x, const float* w, const float* bias, const i
 int32_t ttsamd_conv1d_ex(const float* x, const float* w, const float* bias, const float* res, const int64_t* lens, int32_t batch,
                          int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
                          int32_t relu_out, int32_t mode, float div, float* y, float* packed, void* stream);
+/* ---- the launches a model forward takes at batch 1, for the parity tests.  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION
+ *      stays 8; ttsamd_conv1d_ex is ttsamd_conv1d_splitk(..., NULL, 0, ...), bit for bit what it was.
+ * ttsamd_conv1d_splitk: ttsamd_conv1d_ex with the split-K workspace the models hand their convs (ConvParams::splitk_ws): `splitk_ws` =
+ * `splitk_floats` floats of device scratch, or NULL / 0.  With it a launch of few blocks cuts its input channels into slices (direct
+ * kernel: under 320 blocks and from 8 chunks; F(4,3) kernel: under 192 blocks), each slice writes raw partial sums
+ * [slice][B][Cout][lin] into the workspace and a second launch sums them in slice order and applies the epilogue.  No more slices than
+ * the workspace holds: under 2 * B * Cout * lin floats nothing is split.  The models pass 4 << 20 floats (FastPitch: 8 << 20). */
+int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, const float* res, const int64_t* lens, int32_t batch,
+                             int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
+                             int32_t relu_out, int32_t mode, float div, float* y, float* packed, float* splitk_ws, int64_t splitk_floats,
+                             void* stream);
+/* What the calling thread's last fp32 conv launch decided (ttsamd_conv1d*, ttsamd_conv_transpose1d, or the last conv of a model forward
+ * on this thread): *route = 0 direct kernel, 1 / 2 the two Winograd F(2,3) kernels, 3 / 4 Winograd F(4,3) on six- / seven-point groups,
+ * 5 the all-phase transposed conv; *ksplit = its input-channel slices (1 = not split).  -1 / 0 before the first launch.  Host state of
+ * the thread only: nothing is read from the device.  The bf16 engines and the fused ResBlock launches do not record. */
+int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit);
+/* One HiFi-GAN upsampler (vocoder/hifigan/models.py:96-99, 114-115) as the generator runs it: y = conv_transpose1d(lrelu_slope(x), w,
+ * stride u, padding u / 2) + b with the kernel size 2 u (u even), the only form the engine packs.  x [B][Cin][lin] (Cin a multiple of
+ * 8), w [Cin][Cout][2u] (torch layout, DEVICE), y [B][Cout][lin * u], bias [Cout] or NULL, lens int64 [B] or NULL: row b reads lens[b]
+ * inputs and writes lens[b] * u outputs; y past them is left untouched (both kernels, as for ttsamd_conv1d; the generator's next layers
+ * never read there).  The all-phase kernel (csrc/convt_mfma.hip; route 5) takes u = 2 / 8 with 16-byte aligned rows of y and, at u = 8,
+ * at least 100 blocks; everything else, and everything under TTSAMD_CONVT=0, is the direct kernel's polyphase launch (route 0).
+ * `packed`: ttsamd_convt_packed_floats(Cin, Cout, u) floats of scratch for the re-laid-out weights. */
+int64_t ttsamd_convt_packed_floats(int32_t cin, int32_t cout, int32_t u);
+int32_t ttsamd_conv_transpose1d(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t batch, int32_t cin,
+                                int32_t cout, int32_t u, int32_t lin, float in_slope, float* y, float* packed, void* stream);
 
 /* One c1 -> c2 pair of a ResBlock1 (vocoder/hifigan/models.py:46-53) in exact fp32, intermediate in LDS:
  *   v = x + conv1d(lrelu(conv1d(lrelu(x, slope), w1, dilation dil) + b1, slope), w2) + b2;  y = v | y + v | (y + v) / div  (mode 0 | 1 | 2)

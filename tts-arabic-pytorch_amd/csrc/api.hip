@@ -183,6 +183,22 @@ __global__ void pack_conv_weight_kernel(const float* __restrict__ w, int cout, i
     out[i] = co < cout ? w[((int64_t)co * cin + (8 * o + 2 * pq + kk)) * k + t] : 0.f;
 }
 
+// torch ConvTranspose1d weight [cin][cout][2u] (stride u, padding u / 2) -> the u polyphase 2-tap filters [u][cin/8][2][2][cp][4]
+// (same layout and values as pack_convt_weight, conv_mfma.hip)
+__global__ void pack_convt_weight_kernel(const float* __restrict__ w, int cin, int cout, int u, int cp, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = (int64_t)u * cin * 2 * cp;
+    if (i >= n) return;
+    const int pq = (int)(i % 4);
+    const int co = (int)((i / 4) % cp);
+    const int kk = (int)((i / (4 * (int64_t)cp)) % 2);
+    const int t = (int)((i / (8 * (int64_t)cp)) % 2);
+    const int o = (int)((i / (16 * (int64_t)cp)) % (cin / 8));
+    const int rho = (int)(i / (16 * (int64_t)cp * (cin / 8)));
+    const int kidx = (rho + u / 2) % u + t * u;
+    out[i] = co < cout ? w[((int64_t)(8 * o + 2 * pq + kk) * cout + co) * (2 * u) + kidx] : 0.f;
+}
+
 __global__ void split_bf16_kernel(const float* __restrict__ packed, int64_t n, unsigned short* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -774,7 +790,17 @@ __global__ void pack_wino2_weight_kernel(const float* __restrict__ w, int cout, 
 int32_t ttsamd_conv1d_ex(const float* x, const float* w, const float* bias, const float* res, const int64_t* lens, int32_t batch,
                          int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
                          int32_t relu_out, int32_t mode, float div, float* y, float* packed, void* stream) {
+    return ttsamd_conv1d_splitk(x, w, bias, res, lens, batch, cin, cout, k, dilation, lin, in_slope, relu_out, mode, div, y, packed, nullptr,
+                                0, stream);
+}
+
+int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, const float* res, const int64_t* lens, int32_t batch,
+                             int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
+                             int32_t relu_out, int32_t mode, float div, float* y, float* packed, float* splitk_ws, int64_t splitk_floats,
+                             void* stream) {
     TTS_REQUIRE(x && w && y && packed, "conv1d: null argument");
+    TTS_REQUIRE(splitk_floats >= 0 && (splitk_ws != nullptr || splitk_floats == 0), "conv1d: %lld split-K floats without a workspace",
+                (long long)splitk_floats);
     TTS_REQUIRE(mode >= 0 && mode <= 2 && (mode != 2 || div != 0.f), "conv1d: bad mode / div");
     // the residual-preload epilogues apply the activation to y_prev + res + conv + b: only mode 0 has the documented meaning with relu_out
     TTS_REQUIRE(relu_out == 0 || mode == 0, "conv1d: relu_out with an accumulate mode (mode %d) is not defined", mode);
@@ -820,6 +846,7 @@ int32_t ttsamd_conv1d_ex(const float* x, const float* w, const float* bias, cons
     p.dil = dilation; p.pad = (k * dilation - dilation) / 2;
     p.res = res; p.r_bs = (int64_t)cout * lin; p.r_cs = lin;
     p.n_phase = 1; p.in_slope = in_slope; p.relu_out = relu_out; p.mode = mode; p.div = div; p.batch = batch;
+    if (splitk_ws != nullptr && splitk_floats > 0) { p.splitk_ws = splitk_ws; p.splitk_floats = splitk_floats; }
     prof_begin(s, 2.0 * cout * cin * k);
     const int32_t rc = launch_conv(p, s);
     prof_end(s);
@@ -830,6 +857,46 @@ int32_t ttsamd_conv1d(const float* x, const float* w, const float* bias, const i
                       int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
                       int32_t relu_out, float* y, float* packed, void* stream) {
     return ttsamd_conv1d_ex(x, w, bias, nullptr, lens, batch, cin, cout, k, dilation, lin, in_slope, relu_out, 0, 1.f, y, packed, stream);
+}
+
+int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit) {
+    TTS_REQUIRE(route && ksplit, "conv_last_launch: null argument");
+    last_conv_launch(route, ksplit);
+    return 0;
+}
+
+int64_t ttsamd_convt_packed_floats(int32_t cin, int32_t cout, int32_t u) {
+    // the u polyphase 2-tap filters in fp32 + their bf16 hi / lo planes
+    if (cin < 1 || cout < 1 || u < 1) return 0;
+    return 2 * (int64_t)u * cin * 2 * cout_padded(cout);
+}
+
+int32_t ttsamd_conv_transpose1d(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t batch, int32_t cin,
+                                int32_t cout, int32_t u, int32_t lin, float in_slope, float* y, float* packed, void* stream) {
+    TTS_REQUIRE(x && w && y && packed, "conv_transpose1d: null argument");
+    TTS_REQUIRE(batch >= 1 && cin >= 8 && cin % 8 == 0 && cout >= 1 && lin >= 1, "conv_transpose1d: batch %d, cin %d (a multiple of 8), cout %d, lin %d",
+                batch, cin, cout, lin);
+    TTS_REQUIRE(u >= 2 && u % 2 == 0, "conv_transpose1d: stride %d (kernel 2 u, padding u / 2: u even)", u);
+    TTS_REQUIRE((int64_t)lin * u < ((int64_t)1 << 31) / 4 / cout, "conv_transpose1d: %d x %d x %d outputs per row", cout, lin, u);
+    hipStream_t s = (hipStream_t)stream;
+    const int cp = cout_padded(cout);
+    const int64_t n = (int64_t)u * cin * 2 * cp;
+    hipLaunchKernelGGL(pack_convt_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, cin, cout, u, cp, packed);
+    TTS_CHECK_HIP(hipGetLastError());
+    unsigned short* planes = nullptr;
+    if (default_precision() != 0) {
+        planes = reinterpret_cast<unsigned short*>(packed + n);
+        hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, packed, n, planes);
+        TTS_CHECK_HIP(hipGetLastError());
+    }
+    ConvParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.batch = batch;
+    p.lens_in = lens; p.lens_out = lens;
+    prof_begin(s, 2.0 * cout * cin * 2 * u);
+    const int32_t rc = launch_upsampler(p, x, packed, planes, bias, y, cin, cout, u, 2 * u, lin, 1, in_slope, opt_int(OPT_CONVT, 1) != 0, s);
+    prof_end(s);
+    return rc;
 }
 
 int64_t ttsamd_resblock_pair_packed_floats(int32_t channels, int32_t k, int32_t variant) {

@@ -173,9 +173,20 @@ void conv_log(const char* kind, int K, int cin, int cout, int nout, int batch, i
 bool compact_order(const void* lens, int batch);
 // Launches the kernel; returns 0 or a negative code.
 int32_t launch_conv(const ConvParams& p, hipStream_t stream);
+// What the calling thread's last fp32 conv launch decided (ttsamd_conv_last_launch; conv_mfma.hip): two thread_local ints, written by
+// the launcher that takes the decision.  route 0: direct kernel, 1 / 2: the F(2,3) kernels (conv_wino.hip / conv_wino2.hip), 3 / 4: F(4,3)
+// on six- / seven-point groups, 5: the all-phase transposed conv (convt_mfma.hip).  Host only, no atomics.
+void note_conv_launch(int32_t route, int32_t ksplit);
+void last_conv_launch(int32_t* route, int32_t* ksplit);
 // ConvTranspose1d with all output phases per wave (convt_mfma.hip): takes the polyphase ConvParams of the generic engine
 bool convt_supported(const ConvParams& p);
 int32_t launch_convt(const ConvParams& p, hipStream_t stream);
+// One HiFi-GAN upsampler, leaky_relu + ConvTranspose1d(stride u, kernel kt, padding (kt - u) / 2): fills the polyphase fields of `p`
+// (the caller has set batch, lens_in / lens_out and whatever it shares between its launches) and launches the all-phase kernel where
+// `convt_ok` and convt_supported(p) say so, else the generic engine.  x [B][cin][L], y [B][cout][L * u], w / w_bf16 packed by
+// pack_convt_weight (and split_packed_bf16); valid lengths lens * len_mul in, lens * len_mul * u out.
+int32_t launch_upsampler(ConvParams& p, const float* x, const float* w, const void* w_bf16, const float* bias, float* y, int cin, int cout,
+                         int u, int kt, int L, int len_mul, float in_slope, bool convt_ok, hipStream_t stream);
 // One launch for a c1 -> c2 pair of a C = 32 ResBlock1 with the intermediate in LDS (resblock_fused.hip); x != y.
 bool fused_pair_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
 int32_t launch_fused_pair(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,

@@ -608,6 +608,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ConvParams p) 
     *yp = v;
 }
 
+static thread_local int32_t t_last_route = -1, t_last_ksplit = 0;
+void note_conv_launch(int32_t route, int32_t ksplit) { t_last_route = route; t_last_ksplit = ksplit; }
+void last_conv_launch(int32_t* route, int32_t* ksplit) { *route = t_last_route; *ksplit = t_last_ksplit; }
+
 int32_t launch_splitk_reduce(const ConvParams& q, hipStream_t stream) {
     dim3 rg((q.Nout + 255) / 256, q.Cout, q.batch);
     hipLaunchKernelGGL(splitk_reduce_kernel, rg, dim3(256), 0, stream, q);
@@ -675,6 +679,7 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     }
     if (q.xcd_w & 0x100) q.xcd_w &= 0x1ff;
     grid.y *= q.ksplit;
+    note_conv_launch(0, q.ksplit);
     // epilogue kind (see the kernel): the float4 row epilogue needs 16-byte aligned rows of y (and of the residual)
     const bool vec_ok = q.ksplit == 1 && p.y_ts == 1 && p.n_phase == 1 && (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 &&
                         ((uintptr_t)p.y & 15) == 0 &&

@@ -419,6 +419,8 @@ int wino_route(const ConvParams& p) {
                          (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0)) &&
                          (int64_t)p.Cout * std::max(std::max(p.r_cs, p.y_cs), 1) * 4 < ((int64_t)1 << 31);
         if (!ok1) return 0;
+        // (k = 1 never splits K here: wino4_ksplit answers > 1 only under 192 blocks and then aims at 224, so blocks1 stays under the 512
+        // this route asks for -- the two rules exclude each other, and the factor below is always 1 on a launch that passes)
         const int64_t blocks1 = (int64_t)((p.Nout + 255) / 256) * (p.CoutP / 64) * p.batch * wino4_ksplit(p);
         // one full round of the chip's 512 block slots or more: Vocos' GEMMs (512 ... 1536 blocks); FastPitch's qkv / o_net at batch 32 (192 / 384
         // blocks) stay on the direct kernel's smaller tiles -- same-box A/B of the step: 52.43 ms with them here, 52.33 without
@@ -475,6 +477,7 @@ static int32_t launch_wino_cfg(const ConvParams& p, hipStream_t stream) {
     dim3 grid((p.Nout + G::NT_BLK - 1) / G::NT_BLK, p.CoutP / G::CO_BLK, p.batch);
     ConvParams q = p;
     q.ksplit = 1;
+    note_conv_launch(1, 1);
     q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
     if (p.res != nullptr) return launch_wino_epi<MT, WM, WN, 3>(q, grid, stream);
     return launch_wino_epi<MT, WM, WN, 0>(q, grid, stream);

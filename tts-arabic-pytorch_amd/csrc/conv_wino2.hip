@@ -459,6 +459,7 @@ static int32_t launch_wino2_cfg(const ConvParams& p, hipStream_t stream) {
     dim3 grid((p.Nout + nt - 1) / nt, p.CoutP / G::CO_BLK, p.batch);
     ConvParams q = p;
     q.ksplit = 1;
+    note_conv_launch(2, 1);
     q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
     if (p.res != nullptr) return launch_wino2_epi<K, NOCT, NSTAGE, WM, NPH, 3>(q, grid, stream);
     return launch_wino2_epi<K, NOCT, NSTAGE, WM, NPH, 0>(q, grid, stream);

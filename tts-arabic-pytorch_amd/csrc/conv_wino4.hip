@@ -667,6 +667,7 @@ static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
     const int nt = wino4_tile(p.dil, G::NTUP);
     ConvParams q = p;
     q.ksplit = EPI == 0 ? wino4_ksplit(p) : 1;
+    note_conv_launch(PT == 7 ? 4 : 3, q.ksplit);
     // 1-D grid: (time tiles of the whole batch, rounded up to groups of 8) x row blocks x C-in slices; the kernel maps it XCD-aware
     const int64_t n_tiles = (int64_t)((p.Nout + nt - 1) / nt) * p.batch;
     const int64_t n_blocks = ((n_tiles + 7) / 8) * 8 * (p.CoutP / G::CO_BLK) * q.ksplit;

@@ -106,22 +106,15 @@ __global__ __launch_bounds__(256, 2) void convt_mfma_f32(const ConvParams p) {
 
     TTS_CT_LOAD(0)
 
-    // accumulators start from the bias: acc[rho][i][j][r] = b[co], co = co_w + 32i + (r&3) + 8(r>>2) + 4kk
     f32x16 acc[U][MT][NTL];
-    {
-        const int co_w = co_blk0 + wm * MT * 32;
+#pragma unroll
+    for (int rho = 0; rho < U; ++rho)
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = min(co_w + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk, p.Cout - 1);
-                const float bv = p.bias ? p.bias[co] : 0.f;
+            for (int j = 0; j < NTL; ++j)
 #pragma unroll
-                for (int rho = 0; rho < U; ++rho)
-#pragma unroll
-                    for (int j = 0; j < NTL; ++j) acc[rho][i][j][r] = bv;
-            }
-    }
+                for (int r = 0; r < 16; ++r) acc[rho][i][j][r] = 0.f;
     TTS_CT_WRITE(smem4)
     __syncthreads();
 
@@ -168,8 +161,20 @@ __global__ __launch_bounds__(256, 2) void convt_mfma_f32(const ConvParams p) {
 #undef TTS_CT_LRELU
 
     // ---- epilogue: lane (kk, l31) owns y[co][q*U .. q*U+U) for its 16 rows per co-tile: contiguous across the lanes ----
+    // The bias is added AFTER the sum, as the per-lane epilogue of conv_mfma.hip does: octets, taps and channel pairs go through the
+    // same MFMA in the same order in both kernels, so the two launches of an upsampler give the same bits and a row's samples do not
+    // depend on which one its batch takes (started from the bias, the chain rounds differently: up to 7e-6 apart on unit-variance
+    // outputs, tests/test_gpu_convt.py).  Loaded here and not before the loop: 16 more live registers spill in the 32 co x 512 q tile.
     float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
     const int y_cs = p.y_cs, Cout = p.Cout;
+    float bias_v[MT][16];   // bias_v[i][r] = b[co], co = co_w + 32i + (r&3) + 8(r>>2) + 4kk
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = min(co_blk0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk, Cout - 1);
+            bias_v[i][r] = p.bias ? p.bias[co] : 0.f;
+        }
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -181,14 +186,15 @@ __global__ __launch_bounds__(256, 2) void convt_mfma_f32(const ConvParams p) {
                 const int co = co_blk0 + wm * MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
                 if (co >= Cout) continue;
                 float* yp = yb + (int64_t)co * y_cs + (int64_t)q * U;
+                const float bv = bias_v[i][r];
                 if constexpr (U % 4 == 0) {
 #pragma unroll
                     for (int g = 0; g < U / 4; ++g)
-                        *reinterpret_cast<float4*>(yp + 4 * g) = make_float4(acc[4 * g][i][j][r], acc[4 * g + 1][i][j][r],
-                                                                             acc[4 * g + 2][i][j][r], acc[4 * g + 3][i][j][r]);
+                        *reinterpret_cast<float4*>(yp + 4 * g) = make_float4(acc[4 * g][i][j][r] + bv, acc[4 * g + 1][i][j][r] + bv,
+                                                                             acc[4 * g + 2][i][j][r] + bv, acc[4 * g + 3][i][j][r] + bv);
                 } else {
                     static_assert(U == 2, "phase count");
-                    *reinterpret_cast<float2*>(yp) = make_float2(acc[0][i][j][r], acc[1][i][j][r]);
+                    *reinterpret_cast<float2*>(yp) = make_float2(acc[0][i][j][r] + bv, acc[1][i][j][r] + bv);
                 }
             }
         }
@@ -213,7 +219,8 @@ static int32_t launch_convt_cfg(const ConvParams& p, hipStream_t stream) {
 bool convt_supported(const ConvParams& p) {
     const bool u_ok = (p.n_phase == 8 || p.n_phase == 2) && p.phase_p * 2 == p.n_phase;
     // a grid that leaves most CUs without a block (batch 1: 32 blocks for the first upsampler) does
-    // better on the polyphase launch of the generic engine, which has one block per (phase, co tile) and splits K
+    // better on the polyphase launch of the generic engine, which has one block per (phase, co tile): u times the blocks (it does not
+    // split K: launch_cfg refuses a split when n_phase != 1)
     constexpr int min_blocks = 100;
     if (u_ok && p.n_phase == 8 && (int64_t)((p.Nout + 63) / 64) * (p.CoutP / 64) * p.batch < min_blocks) return false;
     return p.precision == 0 && u_ok && p.K == 2 && p.dil == -1 && p.y_ts == p.n_phase && p.res == nullptr && p.mode == 0 &&
@@ -226,9 +233,27 @@ int32_t launch_convt(const ConvParams& p, hipStream_t stream) {
     TTS_REQUIRE(convt_supported(p), "convt: unsupported geometry");
     if (p.Nout <= 0) return 0;
     conv_log("convt", 2, p.Cin, p.Cout, p.Nout, p.batch, 0, 0, p.len_out_mul, p.lens_out != nullptr, p.n_phase);
+    note_conv_launch(5, 1);
     if (p.n_phase == 8) return launch_convt_cfg<8, 1, 1, 2>(p, stream);                 // 64 co x 64 q (x 8 phases)
     if (p.CoutP % 64 == 0) return launch_convt_cfg<2, 1, 2, 2>(p, stream);              // 64 co x 128 q (x 2)
     return launch_convt_cfg<2, 1, 4, 1>(p, stream);                                     // 32 co x 512 q (x 2)
+}
+
+// leaky_relu + ConvTranspose1d as u polyphase 2-tap convs (vocoder/hifigan/models.py:114-115): the one place that fills the polyphase
+// ConvParams and chooses between the two launches -- the model (hifigan.hip) and the kernel-level entry (ttsamd_conv_transpose1d)
+int32_t launch_upsampler(ConvParams& p, const float* x, const float* w, const void* w_bf16, const float* bias, float* y, int cin, int cout,
+                         int u, int kt, int L, int len_mul, float in_slope, bool convt_ok, hipStream_t stream) {
+    p.x = x; p.x_bs = (int64_t)cin * L; p.x_cs = L;
+    p.w = w; p.bias = bias;
+    p.w_bf16 = w_bf16; p.precision = default_precision(); p.w_wino = nullptr; p.w_wino4 = nullptr; p.w_wino44 = nullptr;
+    p.y = y; p.y_bs = (int64_t)cout * L * u; p.y_cs = L * u; p.y_ts = u;
+    p.res = nullptr;
+    p.len_in_mul = len_mul; p.len_out_mul = len_mul; p.Lin = L; p.Nout = L;
+    p.Cin = cin; p.Cout = cout; p.CoutP = cout_padded(cout); p.K = 2;
+    p.dil = -1; p.pad = 0; p.n_phase = u; p.phase_p = (kt - u) / 2;
+    p.in_slope = in_slope; p.relu_out = 0; p.mode = 0; p.div = 1.f;
+    p.x_packed = 0; p.y_packed = 0;
+    return (convt_ok && convt_supported(p)) ? launch_convt(p, stream) : launch_conv(p, stream);
 }
 
 }  // namespace ttsamd

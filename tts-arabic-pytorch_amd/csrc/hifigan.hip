@@ -652,18 +652,9 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
         const int u = cfg.upsample_rates[i], kt = cfg.upsample_kernel_sizes[i];
         const ConvW& uw = h->ups[i];
         // leaky_relu(0.1) + ConvTranspose1d as u polyphase 2-tap convs (models.py:114-115)
-        p.x = cur; p.x_bs = (int64_t)uw.cin * L; p.x_cs = L;
-        p.w = h->dev + uw.w_off; p.bias = h->dev + uw.b_off;
-        p.w_bf16 = h->dev16 + uw.w16_off; p.precision = default_precision(); p.w_wino = nullptr; p.w_wino4 = nullptr; p.w_wino44 = nullptr;
-        p.y = ups_out; p.y_bs = (int64_t)uw.cout * L * u; p.y_cs = L * u; p.y_ts = u;
-        p.res = nullptr;
-        p.len_in_mul = mul; p.len_out_mul = mul; p.Lin = L; p.Nout = L;
-        p.Cin = uw.cin; p.Cout = uw.cout; p.CoutP = cout_padded(uw.cout); p.K = 2;
-        p.dil = -1; p.pad = 0; p.n_phase = u; p.phase_p = (kt - u) / 2;
-        p.in_slope = 0.1f; p.relu_out = 0; p.mode = 0; p.div = 1.f;
-        p.x_packed = 0; p.y_packed = 0;
         prof_begin(s, 2.0 * uw.cout * uw.cin * 2 * u * mul);
-        int32_t rc = (convt_ok && convt_supported(p)) ? launch_convt(p, s) : launch_conv(p, s);
+        int32_t rc = launch_upsampler(p, cur, h->dev + uw.w_off, h->dev16 + uw.w16_off, h->dev + uw.b_off, ups_out, uw.cin, uw.cout, u, kt, L,
+                                      mul, 0.1f, convt_ok, s);
         prof_end(s);
         HG_TRY(rc);
         L *= u; mul *= u;

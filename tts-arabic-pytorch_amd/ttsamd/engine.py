@@ -583,9 +583,12 @@ class TaggerEngine:
         return probs
 
 
-def conv1d(x, w, bias=None, lens=None, dilation=1, in_slope=1.0, relu_out=False, res=None, mode=0, div=1.0, y=None):
+def conv1d(x, w, bias=None, lens=None, dilation=1, in_slope=1.0, relu_out=False, res=None, mode=0, div=1.0, y=None, splitk_floats=None):
     """Kernel-level entry (parity tests / roofline bench): y = act(conv1d(lrelu(x), w) + b [+ res]), 'same' padding;
-    mode 1 / 2: y <- y + that / (y + that) / div (the ResBlock sum of HiFi-GAN); res may be y itself (in place)."""
+    mode 1 / 2: y <- y + that / (y + that) / div (the ResBlock sum of HiFi-GAN); res may be y itself (in place).
+    `splitk_floats`: the call carries a split-K workspace of that many floats, as the models' convs do (ttsamd_conv1d_splitk; the models
+    pass 4 << 20), allocated here for every call and filled with NaN: a reduce that reads a partial sum nobody wrote shows in y.
+    last_conv_launch() then tells which kernel ran and in how many slices."""
     lib = _require_gpu()
     x = x.contiguous().float()
     w = w.contiguous().float()
@@ -596,8 +599,45 @@ def conv1d(x, w, bias=None, lens=None, dilation=1, in_slope=1.0, relu_out=False,
         y = torch.zeros(B, cout, lin, dtype=torch.float32, device=x.device)
     packed = torch.empty(lib.ttsamd_conv1d_packed_floats(cout, cin, k), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        L.check(lib.ttsamd_conv1d_ex(_ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(lens), B, cin, cout, k, dilation, lin,
-                                     float(in_slope), int(relu_out), int(mode), float(div), _ptr(y), _ptr(packed), _stream()), 'conv1d')
+        if splitk_floats is None:
+            L.check(lib.ttsamd_conv1d_ex(_ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(lens), B, cin, cout, k, dilation, lin,
+                                         float(in_slope), int(relu_out), int(mode), float(div), _ptr(y), _ptr(packed), _stream()), 'conv1d')
+        else:
+            ws = torch.full((max(int(splitk_floats), 1),), float('nan'), dtype=torch.float32, device=x.device)
+            L.check(lib.ttsamd_conv1d_splitk(_ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(lens), B, cin, cout, k, dilation, lin,
+                                             float(in_slope), int(relu_out), int(mode), float(div), _ptr(y), _ptr(packed), _ptr(ws),
+                                             int(splitk_floats), _stream()), 'conv1d_splitk')
+    return y
+
+
+def last_conv_launch():
+    """(route, ksplit) of this thread's last fp32 conv launch (ttsamd_conv_last_launch): route 0 direct kernel, 1 / 2 Winograd F(2,3),
+    3 / 4 Winograd F(4,3) on six- / seven-point groups, 5 the all-phase transposed conv; ksplit = input-channel slices (1: not split)."""
+    route, ksplit = C.c_int32(-1), C.c_int32(0)
+    L.check(L.load().ttsamd_conv_last_launch(C.byref(route), C.byref(ksplit)), 'conv_last_launch')
+    return route.value, ksplit.value
+
+
+def conv_transpose1d(x, w, bias=None, lens=None, in_slope=1.0, y=None):
+    """Kernel-level entry (parity tests): one HiFi-GAN upsampler as the generator launches it (ttsamd_conv_transpose1d),
+    y = conv_transpose1d(lrelu(x), w, stride=u, padding=u // 2) + b for w [Cin][Cout][2u] (torch layout); x [B][Cin][L] -> y [B][Cout][L * u];
+    row b reads lens[b] inputs and writes lens[b] * u outputs, the rest of `y` stays as given."""
+    lib = _require_gpu()
+    x = x.contiguous().float()
+    w = w.contiguous().float()
+    B, cin, lin = x.shape
+    cin2, cout, kt = w.shape
+    assert cin == cin2 and kt % 2 == 0
+    u = kt // 2
+    if y is None:
+        y = torch.zeros(B, cout, lin * u, dtype=torch.float32, device=x.device)
+    assert tuple(y.shape) == (B, cout, lin * u) and y.is_contiguous() and y.dtype == torch.float32
+    if lens is not None:
+        lens = lens.to(device=x.device, dtype=torch.int64).contiguous()
+    packed = torch.empty(max(int(lib.ttsamd_convt_packed_floats(cin, cout, u)), 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(lib.ttsamd_conv_transpose1d(_ptr(x), _ptr(w), _ptr(bias), _ptr(lens), B, cin, cout, u, lin, float(in_slope), _ptr(y),
+                                            _ptr(packed), _stream()), 'conv_transpose1d')
     return y
 
 
