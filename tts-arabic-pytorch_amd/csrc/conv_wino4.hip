@@ -66,9 +66,27 @@ typedef float w4_f32x2 __attribute__((ext_vector_type(2)));
 // the LAST one, so the windows keep their 10 / 14 positions.  Group g = 7 * sub-filter + point accumulates into plane g % 7; P0
 // reaches y0 only and P6 y3 only, so the residual preload (EPI 3) needs two more planes for r1 / r2: r0 -> P0, r1 -> P7, r2 -> P8,
 // r3 -> P6 (nine planes).  Numerics: tests/test_wino44_numerics_cpu.py (about 1.2x the six-point rms on one conv, nothing on the wave).
+// The ROWS ARE EVALUATED on shared partial sums, every multiplier a power of two, so each line below is one fma / add with ONE rounding
+// (21 per channel for a four-tap sub-filter, 18 for the three-tap one, against 32 / 26 term by term):
+//     f(i) = x[i+2] - 4 x[i]   (i = 0..4)           e(i) = f(i) - 2 f(i+1)   (i = 0..3)
+//     d(i) = x[i] - x[i+2]     (i = 1..3)           h(i) = d(i) - 2 d(i+1)   (i = 1, 2)
+//     V0 = e(2) - e(0)     V1 = e(1) + e(2)     V2 = e(1) - e(2)     V6 = e(1) - e(3)
+//     V3 = 2 h(1) + h(2)   V4 = 2 h(1) - h(2)   V5 = f(3) - f(1)
+// f(4) of a sub-filter is f(0) of the next one (its window starts four positions on) and is kept when both are staged in the same phase;
+// the three-tap sub-filter forms neither f(4) nor e(3).  Per-row rms against float64 0.95-1.09x that of the rows written out term by term
+// (tests/test_wino44_shared_rows_cpu.py).  The work of a sub-filter is cut into Wino4Geo::JSF = 10 JOB SLOTS, one per MFMA gap, none
+// above three fma / add per channel (6 VALU instructions for the item's two channels) and one ds_write_b64:
+//     0: f(0) [or kept], f(1), f(2)     1: f(3), e(0)     2: e(2), V0 -> P0     3: e(1), V1 -> P1     4: V2 -> P2     5: V5 -> P5
+//     6: f(4), e(3), V6 -> P6 [four taps]     7: d(1), d(2), d(3)     8: h(1), h(2), V3 -> P3     9: V4 -> P4
+// A job reads window values only behind their activation job (the first write job follows the last activation / strip read) and partial
+// sums only of its own phase: with the strip, phase 0 of k = 11 ends on V0 of the second sub-filter (its slots 0..2, f(0) kept from the
+// first one) and phase 1 starts at its V1 with slots 0..2 run again WITHOUT f(0), e(0) and V0 -- f(1..3) and e(2) are formed a second
+// time (8 VALU instructions per step) rather than carried across a step in registers.  The prologue runs the same job list.
 // Schedule: k = 7 runs its 13 groups in one phase (26 KB per stage); 13 is no multiple of the queue depth, so the 13th group of a
 // step has a queue slot of its own (QX below) instead of three padding groups per octet.  k = 11 at dilation 1 runs its 20 groups in
 // one phase (two stages = 80 KB); with the strip (dilation 3 / 5) in two phases of 8 + 12 groups (two stages of 12 slots = 48 KB).
+// Write jobs per step and the gaps they have (one job per gap, from the first gap behind the activations): k = 7 20 slots (one empty) in
+// 24 gaps (strip: 21), k = 11 at dilation 1 30 in 44, with the strip 13 in 21 (phase 0) and 20 in 21 (phase 1); Wino4Geo::wsv / wst assert it.
 template <int K, int NOCT_, int NSTAGE_, int EPI_ = 0, int PT_ = 6, int LP_ = 1>
 struct Wino4Geo {
     static constexpr bool PT7 = PT_ == 7;
@@ -130,7 +148,19 @@ struct Wino4Geo {
     // phase ph is staged NSTAGE - 1 steps ahead: in the gaps of the step of phase sph(ph)
     __host__ __device__ static constexpr int sph(int ph) { return ((ph - (NSTAGE - 1)) % NPH + NPH) % NPH; }
     __host__ __device__ static constexpr int sgap(int ph) { return ngap(sph(ph)); }
-    __host__ __device__ static constexpr int nwj(int ph) { return NOCT * ngp(ph); }           // write jobs (one plane each)
+    // write jobs.  Six-point groups: one per plane.  Seven-point groups: JSF job slots per sub-filter (the list in front of this struct), of
+    // which a phase runs those of its sub-filters up to its last row -- a phase that ends on V0 of a sub-filter stops behind that
+    // sub-filter's slot 2; slot 6 (V6) of the three-tap sub-filter is empty
+    static constexpr int JSF = 10;
+    __host__ __device__ static constexpr int sflo(int ph) { return glo(ph) / 7; }             // first sub-filter of a phase
+    __host__ __device__ static constexpr bool inph(int ph, int g) { return g >= glo(ph) && g < glo(ph) + ngp(ph); }
+    __host__ __device__ static constexpr int glast_ph(int ph) { return glo(ph) + ngp(ph) - 1; }
+    __host__ __device__ static constexpr int nwj(int ph) {
+        return PT7 ? JSF * (glast_ph(ph) / 7 - sflo(ph)) + (glast_ph(ph) % 7 == 0 ? 3 : JSF) : NOCT * ngp(ph);
+    }
+    static_assert(!PT7 || (NOCT == 1 && glo(0) % 7 <= 1 && glo(NPH - 1) % 7 <= 1 &&
+                           (glast_ph(0) % 7 == 0 || glast_ph(0) % 7 >= 5) && glast_ph(NPH - 1) % 7 >= 5),
+                  "seven-point phases: start on V0 / V1 of a sub-filter (the partial sums are formed per phase), end on V0 or the last row");
     // dilation 1 (D1 kernels): the window is fetched as ALIGNED 16-byte vectors -- vector v of a lane = positions 4 (tuple + v) .. + 3 of the
     // row (a vector is entirely left of position 0 -> zeros by the range check, which drops a WHOLE dwordx4 whose first dword is out of range
     // and checks the right edge dword by dword: tools/buf_range_probe.hip) -- instead of one dword per position: a wave instruction then
@@ -293,6 +323,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     w4_f32x2 sx[D1 ? 1 : NOCT][D1 ? 1 : NPOSP];              // strip path: [pp] = the two channels of the item, one entry per position of the phase
     w4_f32x4 sv[D1 ? NOCT : 1][2][D1 ? G::NVP : 1];          // D1: [octet][pp][vector]
     w4_f32x2 ta[NOCT], tb[NOCT];                             // partial sums shared by two consecutive plane jobs
+    w4_f32x2 tf[PT7 ? 5 : 1], te[PT7 ? 4 : 1], td[PT7 ? 3 : 1], th[PT7 ? 2 : 1];    // seven-point groups: f(0..4), e(0..3), d(1..3), h(1, 2) of the sub-filter in work
     const int spe = min(lane, ntup_eff - 1);                 // idle tuple slots (d > 1) repeat the last tuple: never stored
     const int xw0 = (q0 + 4 * lane) * 4;                      // D1: byte offset of the lane's vector 0 in its row
     constexpr int pad_c = (K - 1) / 2;
@@ -360,22 +391,48 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
 #define TTS_WRITE_JOB(PH, J, WR)                                                                     \
     {                                                                                                \
         const int PH_ = (PH);                                                                        \
-        const int ol_ = (J) / G::ngp(PH_), gl_ = (J) % G::ngp(PH_), g_ = G::glo(PH_) + gl_;         \
+        const int ol_ = PT7 ? 0 : (J) / G::ngp(PH_), gl_ = (J) % G::ngp(PH_), g_ = G::glo(PH_) + gl_;                          \
         w4_f32x2 v2;                                                                                 \
-        if (PT7) {                                                                                   \
-            const int s4 = 4 * (g_ / 7), i_ = g_ % 7;                                                \
-            if (i_ == 0) v2 = (4.f * TTS_SX(s4) - 8.f * TTS_SX(s4 + 1)) + (10.f * TTS_SX(s4 + 3) - 5.f * TTS_SX(s4 + 2)) +      \
-                              (TTS_SX(s4 + 4) - 2.f * TTS_SX(s4 + 5));                               \
-            else if (i_ == 1) v2 = 4.f * (TTS_SX(s4 + 2) - TTS_SX(s4 + 1)) + (9.f * TTS_SX(s4 + 3) - TTS_SX(s4 + 4)) -           \
-                                   2.f * TTS_SX(s4 + 5);                                             \
-            else if (i_ == 2) v2 = (12.f * TTS_SX(s4 + 2) - 4.f * TTS_SX(s4 + 1)) + (2.f * TTS_SX(s4 + 5) - 3.f * TTS_SX(s4 + 4)) - \
-                                   7.f * TTS_SX(s4 + 3);                                             \
-            else if (i_ == 3) v2 = 2.f * (TTS_SX(s4 + 1) + TTS_SX(s4 + 5)) + 3.f * (TTS_SX(s4 + 4) - TTS_SX(s4 + 2)) -           \
-                                   4.f * TTS_SX(s4 + 3);                                             \
-            else if (i_ == 4) v2 = 2.f * (TTS_SX(s4 + 1) - TTS_SX(s4 + 5)) + 5.f * (TTS_SX(s4 + 4) - TTS_SX(s4 + 2));            \
-            else if (i_ == 5) v2 = 4.f * TTS_SX(s4 + 1) + (TTS_SX(s4 + 5) - 5.f * TTS_SX(s4 + 3));  \
-            else v2 = (8.f * TTS_SX(s4 + 2) - 4.f * TTS_SX(s4 + 1)) + (5.f * TTS_SX(s4 + 3) - 10.f * TTS_SX(s4 + 4)) +          \
-                      (2.f * TTS_SX(s4 + 6 < G::NPOS ? s4 + 6 : s4) - TTS_SX(s4 + 5));               \
+        if constexpr (PT7) {                                                                         \
+            /* job slot kd_ of sub-filter sf_ (Wino4Geo::JSF): partial sums in tf / te / td / th, at most three fma / add per channel */ \
+            const int sf_ = G::sflo(PH_) + (J) / G::JSF, kd_ = (J) % G::JSF, s4 = 4 * sf_, g0_ = 7 * sf_;                      \
+            const bool v0_ = G::inph(PH_, g0_), tap4_ = g0_ + 6 < G::NG;                             \
+            int row_ = -1;                                                                           \
+            if (kd_ == 0) {           /* f(0) is f(4) of the sub-filter before (same phase: its slot 6 has run) */              \
+                if (v0_) tf[0] = sf_ > G::sflo(PH_) ? tf[4] : TTS_SX(s4 + 2) - 4.f * TTS_SX(s4);    \
+                tf[1] = TTS_SX(s4 + 3) - 4.f * TTS_SX(s4 + 1);                                       \
+                tf[2] = TTS_SX(s4 + 4) - 4.f * TTS_SX(s4 + 2);                                       \
+            } else if (kd_ == 1) {                                                                   \
+                tf[3] = TTS_SX(s4 + 5) - 4.f * TTS_SX(s4 + 3);                                       \
+                if (v0_) te[0] = tf[0] - 2.f * tf[1];                                                \
+            } else if (kd_ == 2) {                                                                   \
+                te[2] = tf[2] - 2.f * tf[3];                                                         \
+                if (v0_) { v2 = te[2] - te[0]; row_ = 0; }                                           \
+            } else if (kd_ == 3) {                                                                   \
+                te[1] = tf[1] - 2.f * tf[2];                                                         \
+                v2 = te[1] + te[2]; row_ = 1;                                                        \
+            } else if (kd_ == 4) {                                                                   \
+                v2 = te[1] - te[2]; row_ = 2;                                                        \
+            } else if (kd_ == 5) {                                                                   \
+                v2 = tf[3] - tf[1]; row_ = 5;                                                        \
+            } else if (kd_ == 6) {                                                                   \
+                if (tap4_) {                                                                         \
+                    tf[4] = TTS_SX(s4 + 6) - 4.f * TTS_SX(s4 + 4);                                   \
+                    te[3] = tf[3] - 2.f * tf[4];                                                     \
+                    v2 = te[1] - te[3]; row_ = 6;                                                    \
+                }                                                                                    \
+            } else if (kd_ == 7) {                                                                   \
+                td[0] = TTS_SX(s4 + 1) - TTS_SX(s4 + 3);                                             \
+                td[1] = TTS_SX(s4 + 2) - TTS_SX(s4 + 4);                                             \
+                td[2] = TTS_SX(s4 + 3) - TTS_SX(s4 + 5);                                             \
+            } else if (kd_ == 8) {                                                                   \
+                th[0] = td[0] - 2.f * td[1];                                                         \
+                th[1] = td[1] - 2.f * td[2];                                                         \
+                v2 = 2.f * th[0] + th[1]; row_ = 3;                                                  \
+            } else {                                                                                 \
+                v2 = 2.f * th[0] - th[1]; row_ = 4;                                                  \
+            }                                                                                        \
+            if (row_ >= 0) (WR)[2 * ((g0_ + row_ - G::glo(PH_)) * NTUP)] = v2;                       \
         } else if (g_ < 6 * NSF) {                                                                   \
             const int s3 = 3 * (g_ / 6), i_ = g_ % 6;                                                \
             /* the pairs (V1, V2) and (V3, V4) share their two partial sums: kept in ta / tb from the odd job to the even one */ \
@@ -394,7 +451,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
         } else {                                                                                     \
             v2 = TTS_SX(3 * NSF + (g_ - 6 * NSF));                                                   \
         }                                                                                            \
-        (WR)[2 * ((ol_ * 2 * NGPM + gl_) * NTUP)] = v2;                                              \
+        if constexpr (!PT7) (WR)[2 * ((ol_ * 2 * NGPM + gl_) * NTUP)] = v2;                          \
     }
 
     const float4* sB = smem4 + kk * NGPM * NTUP + wn * 32 + l31;      // + stage * BUF4 + (ol * 2 NGPM + g) * NTUP
