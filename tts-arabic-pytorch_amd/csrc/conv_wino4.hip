@@ -36,6 +36,19 @@
 // fragment per octet (the direct engine's packed weights as they are) feeds 16 MFMAs, the epilogue also knows GELU / tanh / the per-row
 // factor of the direct kernel.  Same products in the same order as conv1d_mfma_f32<1>; 251 / 217 vs 263 / 233 us on Vocos' two GEMMs
 // (512 <-> 1536 rows x 15 872 frames: matrix pipe 65 / 75 % busy against 61 / 70 %), Vocos at batch 32 4.99 -> 4.67 ms.
+// EPILOGUES.  EPI 0 (strip kernels, C-in slices, k = 1): the output transform goes through the dead ring (64 KB + the bias, two barriers)
+// and leaves as whole rows -- the row epilogue of conv_mfma.hip.  EPI 3 / 4 (every other dilation-1 launch, with / without a residual):
+// the REGISTER epilogue.  After the output transform a lane holds y0..y3 of one quad for 16 rows, and for a fixed accumulator row a wave
+// covers two rows x 32 adjacent quads = two runs of 512 bytes, so the rows are stored straight from registers: no barrier and no LDS
+// behind the loop, and the ring alone sets the LDS size (k = 7: 52 KB instead of 64.25).  The last step of the loop is PEELED at compile
+// time: it multiplies what is staged and stages nothing (the branch-free tail of the other kernels re-stages the last chunk into a dead
+// stage: at C = 64 an eighth of all staging), so its staging registers are free for the residual's 16 quads, one 16-byte load per gap
+// in its first 16 gaps, and the bias (four loads behind them); they land under the step's 48-92 MFMAs.  Accumulators start at zero;
+// bias, residual, ReLU and the accumulate modes are applied in the row epilogue's order.  mode != 0 (one c2 conv in three) also needs the
+// running ResBlock sum's quads, which do not fit beside the residual's under the last step: they are fetched in the epilogue, eight rows
+// at a time (four with eight planes), in front of those rows' transform.  (Before round 23 the residual was PRELOADED into planes that
+// reach one output each, two of them extra: 16-32 loads per lane in front of the weight queue and the first window, in a queue that
+// returns in order, with no MFMA beside them -- 798 against 733 us on the k = 7 launches at C = 128 / 64; profiles/r23/NOTES.md.)
 #include <cstdlib>
 #include <cstring>
 
@@ -63,9 +76,8 @@ typedef float w4_f32x2 __attribute__((ext_vector_type(2)));
 //     y2 = (P1 + P2) + 4 (P3 + P4) + P5 / 4         y3 = (P1 - P2) + 8 (P3 - P4) + P5 / 8 + P6
 // and a THREE-tap sub-filter on the same points has U6 = 0: six products, x6 never read.  k = 7 = taps (0..3) + (4..6): 7 + 6 = 13
 // products per quad (six-point: 16), k = 11 = (0..3) + (4..7) + (8..10): 7 + 7 + 6 = 20 (six-point: 23); the three-tap sub-filter is
-// the LAST one, so the windows keep their 10 / 14 positions.  Group g = 7 * sub-filter + point accumulates into plane g % 7; P0
-// reaches y0 only and P6 y3 only, so the residual preload (EPI 3) needs two more planes for r1 / r2: r0 -> P0, r1 -> P7, r2 -> P8,
-// r3 -> P6 (nine planes).  Numerics: tests/test_wino44_numerics_cpu.py (about 1.2x the six-point rms on one conv, nothing on the wave).
+// the LAST one, so the windows keep their 10 / 14 positions.  Group g = 7 * sub-filter + point accumulates into plane g % 7 (seven
+// planes; the residual is added in the epilogue, no plane starts from it).  Numerics: tests/test_wino44_numerics_cpu.py (about 1.2x the six-point rms on one conv, nothing on the wave).
 // The ROWS ARE EVALUATED on shared partial sums, every multiplier a power of two, so each line below is one fma / add with ONE rounding
 // (21 per channel for a four-tap sub-filter, 18 for the three-tap one, against 32 / 26 term by term):
 //     f(i) = x[i+2] - 4 x[i]   (i = 0..4)           e(i) = f(i) - 2 f(i+1)   (i = 0..3)
@@ -87,7 +99,7 @@ typedef float w4_f32x2 __attribute__((ext_vector_type(2)));
 // one phase (two stages = 80 KB); with the strip (dilation 3 / 5) in two phases of 8 + 12 groups (two stages of 12 slots = 48 KB).
 // Write jobs per step and the gaps they have (one job per gap, from the first gap behind the activations): k = 7 20 slots (one empty) in
 // 24 gaps (strip: 21), k = 11 at dilation 1 30 in 44, with the strip 13 in 21 (phase 0) and 20 in 21 (phase 1); Wino4Geo::wsv / wst assert it.
-template <int K, int NOCT_, int NSTAGE_, int EPI_ = 0, int PT_ = 6, int LP_ = 1>
+template <int K, int NOCT_, int NSTAGE_, int PT_ = 6, int LP_ = 1>
 struct Wino4Geo {
     static constexpr bool PT7 = PT_ == 7;
     static_assert(PT_ == 6 || (PT7 && (K == 7 || K == 11)), "seven-point groups: k = 7 / 11");
@@ -103,8 +115,8 @@ struct Wino4Geo {
     // [Cin/8][1][2][CoutP][4] as they are -- and each fragment feeds 16 MFMAs
     static constexpr bool WSHARE = K == 1;
     static constexpr int NGW = WSHARE ? 1 : NGQ;                     // weight groups per octet in memory
-    // accumulator planes (six-point P6 / P7: the single tap of k = 7, the preloaded residual; seven-point P7 / P8: the preloaded residual)
-    static constexpr int NPL = PT7 ? (EPI_ == 3 ? 9 : 7) : ((NL || EPI_ == 3) ? 8 : 6);
+    // accumulator planes (six-point P6 / P7: the single tap of k = 7 / k = 1)
+    static constexpr int NPL = PT7 ? 7 : (NL ? 8 : 6);
     static constexpr int NPOS = K == 1 ? 4 : (K == 3 ? 6 : (K == 7 ? 10 : 14));     // input positions of a tuple's window
     static constexpr int NOCT = NOCT_, NSTAGE = NSTAGE_;
     static constexpr int NPH = PT7 ? ((K == 11 && LP_ == 2) ? 2 : 1) : (K == 11 ? 2 : 1);
@@ -133,8 +145,6 @@ struct Wino4Geo {
         if (PT7) return g % 7;
         return g < 6 * NSF ? g % 6 : ((g - 6 * NSF) == 0 ? 0 : ((g - 6 * NSF) == 1 ? 6 : ((g - 6 * NSF) == 2 ? 7 : 5)));
     }
-    // planes that take the preloaded residual of the outputs 0..3 (each reaches exactly that output)
-    __host__ __device__ static constexpr int rplane(int j) { return PT7 ? (j == 0 ? 0 : (j == 1 ? 7 : (j == 2 ? 8 : 6))) : (j == 0 ? 0 : (j == 1 ? 6 : (j == 2 ? 7 : 5))); }
     __host__ __device__ static constexpr int mlo(int ph) { return gfirst(glo(ph)); }
     __host__ __device__ static constexpr int mhi(int ph) {
         int m = 0;
@@ -206,7 +216,7 @@ __device__ __host__ constexpr int wino4_tile(int d, int ntup) { return (4 * ntup
 template <int K, int NOCT_, int NSTAGE_, int EPI, int LP, int PT = 6>
 __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
-    using G = Wino4Geo<K, NOCT_, NSTAGE_, EPI, PT, LP>;
+    using G = Wino4Geo<K, NOCT_, NSTAGE_, PT, LP>;
     constexpr bool PT7 = G::PT7;
     constexpr int WN = G::WN, NSF = G::NSF, NOCT = G::NOCT, NSTAGE = G::NSTAGE, NPL = G::NPL, NGPM = G::NGPM;
     constexpr int CO_BLK = G::CO_BLK, NTUP = G::NTUP, NT_BLK = G::NT_BLK, PF = G::PF;
@@ -253,8 +263,15 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     const float* __restrict__ xb = p.x + (int64_t)b * p.x_bs;
     const float in_slope = p.in_slope;
 
+    // EPI 3 / 4 (dilation 1, one C-in slice, k != 1: the launcher's choice): the REGISTER epilogue -- the last step of the loop is peeled,
+    // stages nothing and fetches in its gaps what the epilogue adds (EPI 3: the residual quads; the bias), the rows go from the output
+    // transform straight to memory.  EPI 0: the row epilogue through LDS.
+    constexpr bool REG = EPI >= 3, RES = EPI == 3;
+    static_assert(!REG || (LP == 1 && K != 1), "register epilogue: dilation 1, k = 3 / 7 / 11");
     float ep_bias = 0.f;
-    if (tid < CO_BLK && p.bias) ep_bias = p.bias[min(co_blk0 + tid, p.Cout - 1)];
+    if constexpr (!REG) {
+        if (tid < CO_BLK && p.bias) ep_bias = p.bias[min(co_blk0 + tid, p.Cout - 1)];
+    }
 
     const int kk = lane >> 5, l31 = lane & 31;
     const int pe = wn * 32 + l31;                                           // the tuple this lane holds in the accumulators
@@ -264,36 +281,24 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     for (int g = 0; g < NPL; ++g)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[g][r] = 0.f;
-    // EPI 3 (dilation 1 only: the launcher's choice): residual [+ running ResBlock sum] of the lane's quad -- one 16-byte load per row --
-    // straight into the planes that reach exactly one output each: r0 -> P0 (y0), r1 -> P6 (y1), r2 -> P7 (y2), r3 -> P5 (y3)
-    // (seven-point groups: P0 / P7 / P8 / P6, Wino4Geo::rplane).
-    // A quad cut by the utterance end loads values that are never stored; past the tensor the range check returns zeros.
-    constexpr bool preload = EPI == 3;
-    if constexpr (preload) {
-        const int wm_s = __builtin_amdgcn_readfirstlane(wm);
-        const int row0 = co_blk0 + wm_s * 32;
-        const int qv = q0 + col_e;
-        const int voff = (qv < n_out ? qv : 0) * 4;
-        {
-            const int r_cs = p.r_cs;
-            const bfo_i4 rs = bfo_rsrc(p.res + (int64_t)b * p.r_bs, (unsigned)p.Cout * (unsigned)r_cs * 4u);
-            const int vk = 4 * kk * r_cs * 4;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const w4_f32x4 t = __builtin_bit_cast(w4_f32x4, bfo_ld16(rs, voff + vk, (row0 + (r & 3) + 8 * (r >> 2)) * r_cs * 4, 0));
-                acc[G::rplane(0)][r] = t.x; acc[G::rplane(1)][r] = t.y; acc[G::rplane(2)][r] = t.z; acc[G::rplane(3)][r] = t.w;
-            }
-        }
-        if (p.mode != 0) {
-            const int y_cs_ = p.y_cs;
-            const bfo_i4 ys = bfo_rsrc(p.y + (int64_t)b * p.y_bs, (unsigned)p.Cout * (unsigned)y_cs_ * 4u);
-            const int vk = 4 * kk * y_cs_ * 4;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const w4_f32x4 t = __builtin_bit_cast(w4_f32x4, bfo_ld16(ys, voff + vk, (row0 + (r & 3) + 8 * (r >> 2)) * y_cs_ * 4, 0));
-                acc[G::rplane(0)][r] += t.x; acc[G::rplane(1)][r] += t.y; acc[G::rplane(2)][r] += t.z; acc[G::rplane(3)][r] += t.w;
-            }
-        }
+    // register epilogue: accumulator row r of a lane = row (r & 3) + 8 (r >> 2) + 4 kk of the wave's 32, its quad = columns q0 + 4 pe .. + 3.
+    // Residual [running ResBlock sum]: one 16-byte load per row at that quad; a quad cut by the utterance end loads values that are never
+    // stored (one wholly past it reads column 0).  The row is part of the VECTOR offset, the one the range check covers (the scalar offset
+    // is not checked), so the padded rows past Cout read zeros, not memory behind the tensor.  res may be y itself: a lane reads exactly
+    // the quads it writes later.  Bias: the four rows of r >> 2 are one 16-byte load (rows past Cout: zeros, never stored).
+    const int ep_row0 = REG ? co_blk0 + __builtin_amdgcn_readfirstlane(wm) * 32 : 0;
+    const int ep_voff = (q0 + col_e < n_out ? q0 + col_e : 0) * 4;             // bytes
+    const int ep_rrow = ep_row0 + 4 * kk;                                   // accumulator row 0 of the lane
+    const bfo_i4 ep_rs = bfo_rsrc(RES ? p.res + (int64_t)b * p.r_bs : nullptr, RES ? (unsigned)p.Cout * (unsigned)p.r_cs * 4u : 0u);
+    const bfo_i4 ep_bs = bfo_rsrc(p.bias, (REG && p.bias) ? (unsigned)p.Cout * 4u : 0u);
+    w4_f32x4 rq[RES ? 16 : 1], bsq[REG ? 4 : 1];
+    constexpr int EP_T0 = RES ? 16 : 0;                                     // first gap of the bias loads (behind the residual's)
+#define TTS_EPLOAD_JOB(T)                                                                            \
+    {                                                                                                \
+        if (RES && (T) < 16)                                                                         \
+            rq[RES ? (T) : 0] = __builtin_bit_cast(w4_f32x4, bfo_ld16(ep_rs, ep_voff + (ep_rrow + ((T) & 3) + 8 * ((T) >> 2)) * p.r_cs * 4, 0, 0)); \
+        if ((T) >= EP_T0 && (T) < EP_T0 + 4)                                                         \
+            bsq[REG ? (T) - EP_T0 : 0] = __builtin_bit_cast(w4_f32x4, bfo_ld16(ep_bs, (ep_rrow + 8 * ((T) - EP_T0)) * 4, 0, 0)); \
     }
 
     // ---- weight queue: group gf = octet * NGQ + g sits at w_wino4 + gf * 2 CoutP float4 (the scalar offset of the buffer load, advanced by
@@ -488,69 +493,84 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     bq[0] = sB[0];
 
     int stage = 0;  // step % NSTAGE
-    for (int c = c_beg; c < n_chunks; ++c) {
-#pragma unroll
-        for (int ph = 0; ph < NPH; ++ph) {
-            // the step being staged: NSTAGE - 1 ahead (tail: the last chunk is re-staged into a dead stage -- branch-free body)
-            const int tph = (ph + NSTAGE - 1) % NPH;
-            const int xso = min(c + (ph + NSTAGE - 1) / NPH, n_chunks - 1) * 8 * NOCT * x_cs;
-            const int stage_next = (stage + 1 == NSTAGE) ? 0 : stage + 1;
-            const int stage_fill = (stage == 0) ? NSTAGE - 1 : stage - 1;
-            w4_f32x2* wr = sW + 2 * stage_fill * G::BUF4;
-            const float4* rd = sB + stage * G::BUF4;
-            const int sn = (c + 1 < n_chunks || ph + 1 < NPH) ? stage_next : stage;
-#pragma unroll
-            for (int gs = 0; gs < NOCT * G::ngq(ph); ++gs) {
-                const int ol = gs / G::ngq(ph), gl = gs % G::ngq(ph);
-                const int qs = G::WSHARE ? ol % PF : ((G::QX && gs >= G::QMAIN) ? PF + gs - G::QMAIN : gs % PF);
-                const w4_f32x4 a4 = aq[qs];
-                // refill the queue slot with the group PF ahead (k = 1: one fragment per octet, refilled behind its last group)
-                if constexpr (G::QX != 0) {
-                    // ... with the slot's next group (Wino4Geo::QX): this step's gs + PF, or the next step's gs + PF - QMAIN / gs
-                    const int nx = gs < G::QMAIN - PF ? gs + PF : (gs < G::QMAIN ? G::NGQ + gs + PF - G::QMAIN : G::NGQ + gs);
-                    aq[qs] = __builtin_bit_cast(w4_f32x4, bfo_ld16(wrs, wv, min(wso + nx * wstep, wlast), 0));
-                    if (gs == G::NGQ - 1) wso += G::NGQ * wstep;
-                } else if (!G::WSHARE || gl == G::ngq(ph) - 1) {
-                    aq[qs] = __builtin_bit_cast(w4_f32x4, bfo_ld16(wrs, wv, wso, 0));
-                    wso = min(wso + wstep, wlast);
-                }
-                if (gl >= G::ngp(ph)) continue;                    // the zero group of k = 11: fetched, never multiplied
-                const int r = ol * G::ngp(ph) + gl;                // multiplied groups of the step so far
-                const int cur = r & 1, nxt = cur ^ 1;
-                const int plane = G::plane(G::glo(ph) + gl);
-                // B operand of the next group: same stage, or (three stages) the first group of the next step's stage
-                if (r + 1 < NOCT * G::ngp(ph)) bq[nxt] = rd[(((r + 1) / G::ngp(ph)) * 2 * NGPM + (r + 1) % G::ngp(ph)) * NTUP];
-                else if (NSTAGE >= 3) bq[nxt] = sB[sn * G::BUF4];       // (an odd step leaves it in slot 1: moved to slot 0 behind the barrier)
-                __builtin_amdgcn_sched_barrier(0);
-                const float bv[4] = {bq[cur].x, bq[cur].y, bq[cur].z, bq[cur].w};
-#pragma unroll
-                for (int m = 0; m < NM; ++m) {
-                    acc[plane] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m], bv[m], acc[plane], 0, 0, 0);
-                    // ---- gap work for the step NSTAGE - 1 ahead: the window loads first, each value activated DAV / DAT gaps later, then
-                    // the plane writes into the stage the previous step has left
-                    const int t = r * NM + m;
-                    if constexpr (D1) {
-                        if (t < G::nljv(tph)) TTS_VLOAD_JOB(tph, t, xso)
-                        if (t >= G::DAV && t - G::DAV < 2 * G::nljv(tph)) TTS_VACT_JOB(tph, t - G::DAV)
-                        if (t >= G::tw0v(tph) && (t - G::tw0v(tph)) % G::wsv(tph) == 0 &&
-                            (t - G::tw0v(tph)) / G::wsv(tph) < G::nwj(tph))
-                            TTS_WRITE_JOB(tph, (t - G::tw0v(tph)) / G::wsv(tph), wr)
-                    } else {
-                        if (G::loads_in(tph) && t < 2 * G::NROW) TTS_TLOAD_JOB(t, xso)
-                        if (G::loads_in(tph) && t >= G::DAT && t < G::DAT + 2 * G::NROW) TTS_TSTORE_JOB(t - G::DAT)
-                        if (t >= G::tr_r0(tph) && t - G::tr_r0(tph) < G::nrj(tph)) TTS_TREAD_JOB(tph, t - G::tr_r0(tph))
-                        if (t >= G::tw0t(tph) && (t - G::tw0t(tph)) % G::wst(tph) == 0 && (t - G::tw0t(tph)) / G::wst(tph) < G::nwj(tph))
-                            TTS_WRITE_JOB(tph, (t - G::tw0t(tph)) / G::wst(tph), wr)
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();
-            if (NSTAGE < 3) bq[0] = sB[sn * G::BUF4];            // two stages: the next step's stage has only just been written
-            else if ((NOCT * G::ngp(ph)) % 2 != 0) bq[0] = bq[1];
-            stage = stage_next;
+    // the steps of chunk C.  LAST (register epilogue only): the block's last chunk, whose final step is PEELED -- it multiplies what is
+    // staged and reads the weight queue to its end, stages nothing, refills no queue slot for a step that does not exist, and ends without
+    // a barrier; its first gaps issue the loads of the epilogue (TTS_EPLOAD_JOB), which land under its MFMAs
+#define TTS_CHUNK_STEPS(LAST, C) \
+        _Pragma("unroll")                                                                                                                                    \
+        for (int ph = 0; ph < NPH; ++ph) {                                                                                                                   \
+            const bool peel = (LAST) && ph == NPH - 1;                                                                                                       \
+            /* the step being staged: NSTAGE - 1 ahead (tail: the last chunk is re-staged into a dead stage -- branch-free body) */                          \
+            const int tph = (ph + NSTAGE - 1) % NPH;                                                                                                         \
+            const int xso = min((C) + (ph + NSTAGE - 1) / NPH, n_chunks - 1) * 8 * NOCT * x_cs;                                                                \
+            const int stage_next = (stage + 1 == NSTAGE) ? 0 : stage + 1;                                                                                    \
+            const int stage_fill = (stage == 0) ? NSTAGE - 1 : stage - 1;                                                                                    \
+            w4_f32x2* wr = sW + 2 * stage_fill * G::BUF4;                                                                                                    \
+            const float4* rd = sB + stage * G::BUF4;                                                                                                         \
+            const int sn = ((C) + 1 < n_chunks || ph + 1 < NPH) ? stage_next : stage;                                                                          \
+        _Pragma("unroll")                                                                                                                                    \
+            for (int gs = 0; gs < NOCT * G::ngq(ph); ++gs) {                                                                                                 \
+                const int ol = gs / G::ngq(ph), gl = gs % G::ngq(ph);                                                                                        \
+                const int qs = G::WSHARE ? ol % PF : ((G::QX && gs >= G::QMAIN) ? PF + gs - G::QMAIN : gs % PF);                                             \
+                const w4_f32x4 a4 = aq[qs];                                                                                                                  \
+                /* refill the queue slot with the group PF ahead (k = 1: one fragment per octet, refilled behind its last group) */                          \
+                if constexpr (G::QX != 0) {                                                                                                                  \
+                    /* ... with the slot's next group (Wino4Geo::QX): this step's gs + PF, or the next step's gs + PF - QMAIN / gs */                        \
+                    const int nx = gs < G::QMAIN - PF ? gs + PF : (gs < G::QMAIN ? G::NGQ + gs + PF - G::QMAIN : G::NGQ + gs);                               \
+                    if (!peel || nx < G::NGQ) aq[qs] = __builtin_bit_cast(w4_f32x4, bfo_ld16(wrs, wv, min(wso + nx * wstep, wlast), 0));                     \
+                    if (gs == G::NGQ - 1) wso += G::NGQ * wstep;                                                                                             \
+                } else if ((!G::WSHARE || gl == G::ngq(ph) - 1) && (!peel || gs + PF < NOCT * G::ngq(ph))) {                                                 \
+                    aq[qs] = __builtin_bit_cast(w4_f32x4, bfo_ld16(wrs, wv, wso, 0));                                                                        \
+                    wso = min(wso + wstep, wlast);                                                                                                           \
+                }                                                                                                                                            \
+                if (gl >= G::ngp(ph)) continue;                    /* the zero group of k = 11: fetched, never multiplied */                                 \
+                const int r = ol * G::ngp(ph) + gl;                /* multiplied groups of the step so far */                                                \
+                const int cur = r & 1, nxt = cur ^ 1;                                                                                                        \
+                const int plane = G::plane(G::glo(ph) + gl);                                                                                                 \
+                /* B operand of the next group: same stage, or (three stages) the first group of the next step's stage */                                    \
+                if (r + 1 < NOCT * G::ngp(ph)) bq[nxt] = rd[(((r + 1) / G::ngp(ph)) * 2 * NGPM + (r + 1) % G::ngp(ph)) * NTUP];                              \
+                else if (NSTAGE >= 3 && !peel) bq[nxt] = sB[sn * G::BUF4];       /* (an odd step leaves it in slot 1: moved to slot 0 behind the barrier) */ \
+                __builtin_amdgcn_sched_barrier(0);                                                                                                           \
+                const float bv[4] = {bq[cur].x, bq[cur].y, bq[cur].z, bq[cur].w};                                                                            \
+        _Pragma("unroll")                                                                                                                                    \
+                for (int m = 0; m < NM; ++m) {                                                                                                               \
+                    acc[plane] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m], bv[m], acc[plane], 0, 0, 0);                                                    \
+                    /* ---- gap work for the step NSTAGE - 1 ahead: the window loads first, each value activated DAV / DAT gaps later, then */               \
+                    /* the plane writes into the stage the previous step has left */                                                                         \
+                    const int t = r * NM + m;                                                                                                                \
+                    if (peel) {                                                                                                                              \
+                        TTS_EPLOAD_JOB(t)                                                                                                                    \
+                    } else if constexpr (D1) {                                                                                                               \
+                        if (t < G::nljv(tph)) TTS_VLOAD_JOB(tph, t, xso)                                                                                     \
+                        if (t >= G::DAV && t - G::DAV < 2 * G::nljv(tph)) TTS_VACT_JOB(tph, t - G::DAV)                                                      \
+                        if (t >= G::tw0v(tph) && (t - G::tw0v(tph)) % G::wsv(tph) == 0 &&                                                                    \
+                            (t - G::tw0v(tph)) / G::wsv(tph) < G::nwj(tph))                                                                                  \
+                            TTS_WRITE_JOB(tph, (t - G::tw0v(tph)) / G::wsv(tph), wr)                                                                         \
+                    } else {                                                                                                                                 \
+                        if (G::loads_in(tph) && t < 2 * G::NROW) TTS_TLOAD_JOB(t, xso)                                                                       \
+                        if (G::loads_in(tph) && t >= G::DAT && t < G::DAT + 2 * G::NROW) TTS_TSTORE_JOB(t - G::DAT)                                          \
+                        if (t >= G::tr_r0(tph) && t - G::tr_r0(tph) < G::nrj(tph)) TTS_TREAD_JOB(tph, t - G::tr_r0(tph))                                     \
+                        if (t >= G::tw0t(tph) && (t - G::tw0t(tph)) % G::wst(tph) == 0 && (t - G::tw0t(tph)) / G::wst(tph) < G::nwj(tph))                    \
+                            TTS_WRITE_JOB(tph, (t - G::tw0t(tph)) / G::wst(tph), wr)                                                                         \
+                    }                                                                                                                                        \
+                    __builtin_amdgcn_sched_barrier(0);                                                                                                       \
+                }                                                                                                                                            \
+            }                                                                                                                                                \
+            if (peel) break;                                                                                                                                 \
+            __syncthreads();                                                                                                                                 \
+            if (NSTAGE < 3) bq[0] = sB[sn * G::BUF4];            /* two stages: the next step's stage has only just been written */                          \
+            else if ((NOCT * G::ngp(ph)) % 2 != 0) bq[0] = bq[1];                                                                                            \
+            stage = stage_next;                                                                                                                              \
         }
+    for (int c = c_beg; c < n_chunks - (REG ? 1 : 0); ++c) {
+        TTS_CHUNK_STEPS(false, c)
     }
+    if constexpr (REG) {
+        const int c = n_chunks - 1;
+        TTS_CHUNK_STEPS(true, c)
+    }
+#undef TTS_CHUNK_STEPS
+#undef TTS_EPLOAD_JOB
 #undef TTS_TLOAD_JOB
 #undef TTS_TSTORE_JOB
 #undef TTS_TREAD_JOB
@@ -561,41 +581,95 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
 #undef TTS_SX
 #undef TTS_WRITE_JOB
 
-    // ---- epilogue: output transform into the dead ring, then the row epilogue of conv_mfma.hip (bias, residual, ReLU, accumulate modes)
+    // ---- output transform of accumulator row R: the lane's quad y0..y3
+#define TTS_OUT_QUAD(R)                                                                              \
+        const float s12 = acc[1][R] + acc[2][R], d12 = acc[1][R] - acc[2][R];                        \
+        const float s34 = acc[3][R] + acc[4][R], d34 = acc[3][R] - acc[4][R];                        \
+        float y0 = acc[0][R] + s12 + s34;                                                            \
+        float y1 = d12 + 2.f * d34;                                                                  \
+        float y2 = s12 + 4.f * s34;                                                                  \
+        float y3 = d12 + 8.f * d34 + acc[PT7 ? 6 : 5][R];                                            \
+        if constexpr (NSF == 0) { y0 = acc[0][R]; y1 = 0.f; y2 = 0.f; y3 = acc[5][R]; }     /* k = 1: P1..P4 do not exist */          \
+        if constexpr (PT7) {                                                                  /* the point 1/2: P5 (1, 1/2, 1/4, 1/8) */ \
+            y0 += acc[5][R];                                                                         \
+            y1 += 0.5f * acc[5][R];                                                                  \
+            y2 += 0.25f * acc[5][R];                                                                 \
+            y3 += 0.125f * acc[5][R];                                                                \
+        } else if constexpr (NPL == 8) {                                                             \
+            y1 += acc[6][R];                                                                         \
+            y2 += acc[7][R];                                                                         \
+        }
+    float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
+    const int mode = p.mode, relu_out = p.relu_out, Cout = p.Cout;
+    const float div = p.div;
+    // ---- register epilogue: the row epilogue's arithmetic in its order (bias, residual, ReLU, accumulate modes) on the lane's quad of each
+    // row, one 16-byte store per lane and row -- for fixed r a wave writes two rows x 32 adjacent quads = two runs of 512 bytes.  No barrier,
+    // no LDS.  mode != 0 (one c2 conv in three): the running sum's quads do not fit beside the residual's under the last step, so they are
+    // fetched here, eight rows at a time, in front of those rows' transform.
+    if constexpr (REG) {
+        const int q = q0 + col_e, y_cs = p.y_cs;
+        if (q >= n_out) return;
+        const bool full = q + 3 < n_out;
+        const bfo_i4 ys = bfo_rsrc(yb, (unsigned)Cout * (unsigned)y_cs * 4u);
+        const float lo = relu_out == 1 ? 0.f : -__builtin_inff();           // ReLU or nothing in one v_max (the row epilogue's way)
+        constexpr int PB = NPL >= 8 ? 4 : 8;                               // rows per batch of the running sum's loads
+#pragma unroll
+        for (int h = 0; h < 16 / PB; ++h) {
+            w4_f32x4 pq[PB];
+#pragma unroll
+            for (int i = 0; i < PB; ++i) {
+                const int r = PB * h + i;
+                pq[i] = w4_f32x4{0.f, 0.f, 0.f, 0.f};
+                if (mode != 0)
+                    pq[i] = __builtin_bit_cast(w4_f32x4, bfo_ld16(ys, ep_voff + (ep_rrow + (r & 3) + 8 * (r >> 2)) * y_cs * 4, 0, 0));
+            }
+#pragma unroll
+            for (int i = 0; i < PB; ++i) {
+                const int r = PB * h + i;
+                const int co = ep_rrow + (r & 3) + 8 * (r >> 2);
+                TTS_OUT_QUAD(r)
+                w4_f32x4 v = {y0, y1, y2, y3};
+                const float bsv = bsq[REG ? r >> 2 : 0][r & 3];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float x = v[e] + bsv;
+                    if constexpr (RES) x += rq[RES ? r : 0][e];
+                    v[e] = fmaxf(x, lo);
+                }
+                if (mode != 0) {                                            // uniform
+                    v = pq[i] + v;
+                    if (mode == 2) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) v[e] = v[e] / div;
+                    }
+                }
+                if (co >= Cout) continue;                                   // padded rows of the last row block
+                float* yp = yb + (int64_t)co * y_cs + q;
+                if (full) {
+                    *reinterpret_cast<w4_f32x4*>(yp) = v;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (q + e < n_out) yp[e] = v[e];
+                }
+            }
+        }
+        return;
+    }
+    // ---- row epilogue (strip kernels, C-in slices, k = 1): output transform into the dead ring, then the row epilogue of conv_mfma.hip
+    // (bias, residual, ReLU, accumulate modes)
     constexpr int LDS_F = CO_BLK * NT_BLK + CO_BLK;                     // floats of LDS this block owns (the launcher allocates max(ring, this))
     constexpr int LPR = NT_BLK / 4;                                     // lanes per row (one float4 each) = 64
     static_assert(LPR == 64, "one wave instruction per row");
     float* ep = reinterpret_cast<float*>(smem4);
     float* epb = ep + LDS_F - CO_BLK;                                   // [CO_BLK] bias
-    float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
-    const float* __restrict__ rb = (p.res && !preload) ? p.res + (int64_t)b * p.r_bs : nullptr;
-    const int mode = p.mode, relu_out = p.relu_out, Cout = p.Cout;
-    const float div = p.div;
+    const float* __restrict__ rb = p.res ? p.res + (int64_t)b * p.r_bs : nullptr;
     __syncthreads();                                                    // ring stages are dead
     if (tid < CO_BLK) epb[tid] = ep_bias;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-        const float s12 = acc[1][r] + acc[2][r], d12 = acc[1][r] - acc[2][r];
-        const float s34 = acc[3][r] + acc[4][r], d34 = acc[3][r] - acc[4][r];
-        float y0 = acc[0][r] + s12 + s34;
-        float y1 = d12 + 2.f * d34;
-        float y2 = s12 + 4.f * s34;
-        float y3 = d12 + 8.f * d34 + acc[PT7 ? 6 : 5][r];
-        if constexpr (NSF == 0) { y0 = acc[0][r]; y1 = 0.f; y2 = 0.f; y3 = acc[5][r]; }     // k = 1: P1..P4 do not exist
-        if constexpr (PT7) {                                                                  // the point 1/2: P5 (1, 1/2, 1/4, 1/8)
-            y0 += acc[5][r];
-            y1 += 0.5f * acc[5][r];
-            y2 += 0.25f * acc[5][r];
-            y3 += 0.125f * acc[5][r];
-            if constexpr (NPL == 9) {
-                y1 += acc[7][r];
-                y2 += acc[8][r];
-            }
-        } else if constexpr (NPL == 8) {
-            y1 += acc[6][r];
-            y2 += acc[7][r];
-        }
+        TTS_OUT_QUAD(r)
         if (pe < ntup_eff) {
             if (dil == 1) {
                 *reinterpret_cast<float4*>(ep + row * NT_BLK + col_e) = make_float4(y0, y1, y2, y3);
@@ -607,6 +681,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
             }
         }
     }
+#undef TTS_OUT_QUAD
     __syncthreads();
     constexpr int NR = CO_BLK / 4;                                      // row iterations per wave
     const int col = lane * 4, q = q0 + col;
@@ -635,10 +710,9 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     // k = 1 only (Vocos' pointwise convs): GELU behind the bias, a per-row factor before the residual, tanh at the end (conv_mfma.hip's epilogue)
     const float* __restrict__ scale = K == 1 ? p.scale : nullptr;
     const bool plain_act = K != 1 || (relu_out < 2 && scale == nullptr);
-    if (plain_act && (preload || (!rb && mode == 0))) {
+    if (plain_act && !rb && mode == 0) {
         // nothing to read from memory: a loop without a single vmcnt wait (conv_mfma.hip: why)
         const float lo = relu_out == 1 ? 0.f : -__builtin_inff();
-        const bool do_div = preload && mode == 2;
 #pragma unroll 4
         for (int it = 0; it < NR; ++it) {
             const int rl = wid + it * 4;
@@ -647,10 +721,6 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
             const float bsv = epb[rl];
             const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
             float v[4] = {fmaxf(a4.x + bsv, lo), fmaxf(a4.y + bsv, lo), fmaxf(a4.z + bsv, lo), fmaxf(a4.w + bsv, lo)};
-            if (do_div) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = v[e] / div;
-            }
             float* yp = yb + (int64_t)co * p.y_cs + q;
             if (full) {
                 *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
@@ -662,7 +732,6 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
         }
         return;
     }
-    if constexpr (preload) return;
 #pragma unroll 2
     for (int it = 0; it < NR; ++it) {
         const int rl = wid + it * 4;
@@ -712,12 +781,14 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
 
 template <int K, int NOCT, int NSTAGE, int EPI, int LP, int PT = 6>
 static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
-    using G = Wino4Geo<K, NOCT, NSTAGE, EPI, PT, LP>;
+    using G = Wino4Geo<K, NOCT, NSTAGE, PT, LP>;
     constexpr size_t ring = (size_t)G::NSTAGE * G::BUF4 * sizeof(float4);
     constexpr size_t epi = ((size_t)G::CO_BLK * G::NT_BLK + G::CO_BLK) * sizeof(float);
     constexpr size_t strip = LP == 2 ? (size_t)G::RAW_BYTES : 0;
-    constexpr size_t lds = ring + strip > epi ? ring + strip : epi;
+    // the register epilogue (EPI 3 / 4) touches no LDS: such a launch allocates the ring alone
+    constexpr size_t lds = (EPI >= 3 || ring + strip > epi) ? ring + strip : epi;
     static_assert(lds <= 80 * 1024, "two blocks per CU");
+    static_assert(EPI < 3 || lds == ring, "register epilogue: the ring sets the LDS size");
     static std::atomic<uint64_t> lds_done{0};
     const auto kern = conv1d_wino4_f32<K, NOCT, NSTAGE, EPI, LP, PT>;
     TTS_CHECK_HIP(lds_opt_in((const void*)kern, (int)lds, lds_done));
@@ -739,11 +810,13 @@ static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
 
 template <int K, int NOCT, int NSTAGE>
 static int32_t launch_wino4_cfg(const ConvParams& p, hipStream_t stream) {
-    // residual preload (16-byte loads of the lane's quad): dilation 1 -- every c2 conv of a ResBlock, the second conv-FF conv
-    // dilation 1: the window as aligned 16-byte vectors (D1)
+    // dilation 1: the window as aligned 16-byte vectors (D1).  One C-in slice: the register epilogue, with the residual's quads fetched
+    // under the last step (EPI 3: every c2 conv of a ResBlock, the second conv-FF conv) or without a residual (EPI 4: conv_pre, c1 at
+    // d = 1, the first conv-FF conv).  C-in slices write raw partial sums through the row epilogue (EPI 0)
     if (p.dil == 1) {
-        if (p.res != nullptr && wino4_ksplit(p) == 1) return launch_wino4_epi<K, NOCT, NSTAGE, 3, 1>(p, stream);
-        return launch_wino4_epi<K, NOCT, NSTAGE, 0, 1>(p, stream);
+        if (wino4_ksplit(p) != 1) return launch_wino4_epi<K, NOCT, NSTAGE, 0, 1>(p, stream);
+        if (p.res != nullptr) return launch_wino4_epi<K, NOCT, NSTAGE, 3, 1>(p, stream);
+        return launch_wino4_epi<K, NOCT, NSTAGE, 4, 1>(p, stream);
     }
     // dilation 3 / 5: the window through the per-wave LDS strip (two stages: the strip takes 10 / 20 KB)
     return launch_wino4_epi<K, NOCT, 2, 0, 2>(p, stream);
@@ -754,8 +827,9 @@ static int32_t launch_wino4_cfg(const ConvParams& p, hipStream_t stream) {
 template <int K>
 static int32_t launch_wino44_cfg(const ConvParams& p, hipStream_t stream) {
     if (p.dil == 1) {
-        if (p.res != nullptr && wino4_ksplit(p) == 1) return launch_wino4_epi<K, 1, 2, 3, 1, 7>(p, stream);
-        return launch_wino4_epi<K, 1, 2, 0, 1, 7>(p, stream);
+        if (wino4_ksplit(p) != 1) return launch_wino4_epi<K, 1, 2, 0, 1, 7>(p, stream);
+        if (p.res != nullptr) return launch_wino4_epi<K, 1, 2, 3, 1, 7>(p, stream);
+        return launch_wino4_epi<K, 1, 2, 4, 1, 7>(p, stream);
     }
     return launch_wino4_epi<K, 1, 2, 0, 2, 7>(p, stream);
 }
