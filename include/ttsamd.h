@@ -868,6 +868,36 @@ int32_t ttsamd_stream_emit_resampled(void* resample_handle, const float* wave, i
                                      const int32_t* utt_len /* host */, const int32_t* core_start /* host */,
                                      const int32_t* core_end /* host */, int32_t c_max, int32_t format, void* out,
                                      int32_t* nout /* host, out, may be NULL */, void* stream);
+/* Vocos in the stream (csrc/vocos.hip).  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.
+ * The receptive field of a Vocos handle in mel frames per side, from its own num_layers and padding mode.  The backbone is the embed
+ * conv (k = 7) and num_layers ConvNeXt blocks whose only mixing along time is a depthwise conv (k = 7), all zero-padded; LayerNorm, the
+ * pointwise convs and head.out are per frame: 3 + 3 * num_layers frames per side (27 for 8 layers).  The ISTFT adds the frames whose
+ * 1024-sample segments overlap a frame of samples.  Sample m = 256 c + j (0 <= j < 256) of frame c sums the frames t with
+ * 0 <= m + pad - 256 t < 1024.  "same" (pad 384): 256 (c - t) + j + 384 in [0, 1024) holds for t = c - 2 (j < 128) ... c + 2
+ * (j >= 128): frames c - 2 ... c + 2.  "center" (pad 512): 256 (c - t) + j + 512 in [0, 1024) holds for t = c - 1 ... c + 2, for no
+ * j at t = c - 2.  So left / right = 3 + 3 * num_layers + (2, 2) for "same", + (1, 2) for "center": 29 / 29 for '22k', 28 / 29 for
+ * '24k'.  With these halos the float64 oracle's window core equals its whole-utterance wave exactly; one frame less on either side
+ * does not (2e-10 ... 1e-9 with the synthetic weights).  The spectral bias subtraction is per frame and adds nothing. */
+int32_t ttsamd_vocos_halo_frames(void* handle, int32_t* left /* host, out */, int32_t* right /* host, out */);
+/* The vocoder call of one streaming step.  mel [n_windows][input_channels][w_max] and lens int64 [n_windows] (device) are what
+ * ttsamd_stream_gather writes; wave [n_windows][256 * w_max] is what both emit entries read.  need_start / need_len: HOST int32
+ * [n_windows], read during the call and passed on as launch arguments (no staging copy, no host synchronisation): the FRAMES of window w
+ * whose samples the caller will read, 0 <= need_start, 1 <= need_len, need_start + need_len <= lens[w] <= w_max.  denoise_rows: device
+ * float [n_windows] or NULL (every row at 0); with it bias_vec is needed.
+ * The backbone and head.out run over the whole windows as in ttsamd_vocos_forward_rows.  The head behind them runs only where the
+ * needed samples can see it: the spectrum (with the row's denoise strength) and one 1024-point inverse FFT for the frames
+ * [need_start - r_l, need_start + need_len + 2) within [0, lens[w]), r_l = 2 for "same" and 1 for "center" (the derivation above); the
+ * overlap-add with the envelope for the samples [256 * need_start, 256 * (need_start + need_len)) within [0, n_out(lens[w])), n_out(L)
+ * = 256 L for "same" and 256 (L - 1) for "center".  Those samples have the BITS of ttsamd_vocos_forward_rows on the same batch (the same
+ * frames, summed in the same order); every other element of wave is NOT written.
+ * ttsamd_vocos_workspace_bytes(handle, n_windows, w_max) is enough workspace (less: TTSAMD_ENOMEM).  Checked on the host
+ * (TTSAMD_EINVAL with a message, nothing launched): NULL handle, mel, lens, wave or descriptor arrays; 1 <= n_windows <=
+ * TTSAMD_STREAM_MAX_WINDOWS; w_max >= 1; 0 <= need_start, 1 <= need_len, need_start + need_len <= w_max; denoise_rows without
+ * bias_vec.  lens[w] lives on the device and is not read back: the kernels clip both ranges to it, as stated above. */
+int32_t ttsamd_vocos_forward_windows(void* handle, const float* mel, const int64_t* lens, int32_t n_windows, int32_t w_max,
+                                     const int32_t* need_start /* host */, const int32_t* need_len /* host */,
+                                     const float* denoise_rows /* device, may be NULL = 0 */, const float* bias_vec, float* wave,
+                                     void* workspace, int64_t workspace_bytes, void* stream);
 /* The encoder alone, for finished waves: wave [batch][wave_stride] fp32 -> out [batch][out_stride] elements of format 1 (int16), 2 or 3
  * (one byte) as above.  nsamples: device int64 [batch], clamped to [0, wave_stride], or NULL for the full stride; samples
  * [0, nsamples[b]) of row b are converted, the entries behind them up to min(wave_stride, out_stride) are written as zero.  wave and

@@ -87,6 +87,9 @@ int32_t vocos_bias_vec(const Vocos*, float*, void*, int64_t, hipStream_t);
 int32_t vocos_forward(const Vocos*, const float*, const int64_t*, int32_t, int32_t, float, const float*, const float*, float*, void*,
                       int64_t, hipStream_t);
 int32_t vocos_set_padding(Vocos*, int32_t);
+int32_t vocos_halo_frames(const Vocos*, int32_t*, int32_t*);
+int32_t vocos_forward_windows(const Vocos*, const float*, const int64_t*, int32_t, int32_t, const int32_t*, const int32_t*, const float*,
+                              const float*, float*, void*, int64_t, hipStream_t);
 struct MelSpec;
 int32_t melspec_create(const float*, int32_t, int32_t, int32_t, int32_t, int32_t, float, MelSpec**);
 void melspec_destroy(MelSpec*);
@@ -488,6 +491,16 @@ int32_t ttsamd_vocos_forward_rows(void* handle, const float* mel, const int64_t*
 }
 
 int32_t ttsamd_vocos_set_padding(void* handle, int32_t mode) { return vocos_set_padding((Vocos*)handle, mode); }
+
+int32_t ttsamd_vocos_halo_frames(void* handle, int32_t* left, int32_t* right) {
+    return vocos_halo_frames((Vocos*)handle, left, right);
+}
+int32_t ttsamd_vocos_forward_windows(void* handle, const float* mel, const int64_t* lens, int32_t n_windows, int32_t w_max,
+                                     const int32_t* need_start, const int32_t* need_len, const float* denoise_rows, const float* bias_vec,
+                                     float* wave, void* workspace, int64_t workspace_bytes, void* stream) {
+    return vocos_forward_windows((Vocos*)handle, mel, lens, n_windows, w_max, need_start, need_len, denoise_rows, bias_vec, wave, workspace,
+                                 workspace_bytes, (hipStream_t)stream);
+}
 
 int32_t ttsamd_melspec_create(const float* fbank, int32_t n_mels, int32_t n_fft, int32_t hop_length, int32_t framing,
                               int32_t mag_mode, float log_clip, void** handle) {

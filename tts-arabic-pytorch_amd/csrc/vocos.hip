@@ -173,14 +173,10 @@ void vocos_destroy(Vocos* h) {
 // 2. one block per frame reads its 513 bins contiguously, builds conj(X) of the Hermitian extension (X[k] = S[k], X[1024 - k] = conj S[k]; the
 //    imaginary parts of DC and Nyquist dropped as irfft does), runs ONE 1024-point FFT in LDS (fft1024.hpp) and writes Re / 1024 * window as
 //    Y[b][t][k].  Rounds 1-5 ran the inverse DFT as a [1152 -> 1024] GEMM on the conv engine: 300 us per B = 32 call (40x the FLOPs).
-__global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restrict__ O, const float* __restrict__ bias, float denoise,
-                                                           const float* __restrict__ denoise_rows, const int64_t* __restrict__ lens, int T, float2* __restrict__ S) {
+// one 32 x 32 tile of row b: bins f0 ..., frames t0 ... of which those in [t_lo, t_hi) are computed and written, no other
+__device__ __forceinline__ void vocos_spec_tile(const float* __restrict__ O, const float* __restrict__ bias, float dn, int b, int f0, int t0,
+                                                int t_lo, int t_hi, int T, float2* __restrict__ S) {
     __shared__ float2 tile[32][33];
-    const int b = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
-    const int len = lens ? min((int)lens[b], T) : T;
-    if (t0 >= len) return;
-    // the row's strength; the scalar entry passes bias = nullptr for 0, so a row at 0 takes the same (no) subtraction
-    const float dn = denoise_rows ? denoise_rows[b] : denoise;
     const bool sub = bias != nullptr && dn != 0.f;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
     const float* ob = O + (int64_t)b * V_SPEC_CP * T;
@@ -188,7 +184,7 @@ __global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restri
     for (int r = 0; r < 4; ++r) {
         const int f = f0 + ty + 8 * r, t = t0 + tx;
         float2 v = make_float2(0.f, 0.f);
-        if (f < V_NBIN && t < len) {
+        if (f < V_NBIN && t >= t_lo && t < t_hi) {
             const float lm = ob[(int64_t)f * T + t], ph = ob[(int64_t)(V_NBIN + f) * T + t];
             float mag = expf(lm);
             if (sub) mag -= dn * bias[f];
@@ -201,17 +197,25 @@ __global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restri
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int t = t0 + ty + 8 * r, f = f0 + tx;
-        if (t < len && f < V_NBIN) S[((int64_t)b * T + t) * V_NBIN + f] = tile[tx][ty + 8 * r];
+        if (t >= t_lo && t < t_hi && f < V_NBIN) S[((int64_t)b * T + t) * V_NBIN + f] = tile[tx][ty + 8 * r];
     }
 }
 
-__global__ __launch_bounds__(256) void vocos_istft_kernel(const float2* __restrict__ S, const int64_t* __restrict__ lens,
-                                                          const float* __restrict__ win, const float2* __restrict__ tw_g, int T,
-                                                          float* __restrict__ Y) {
+__global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restrict__ O, const float* __restrict__ bias, float denoise,
+                                                           const float* __restrict__ denoise_rows, const int64_t* __restrict__ lens, int T, float2* __restrict__ S) {
+    const int b = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
+    const int len = lens ? min((int)lens[b], T) : T;
+    if (t0 >= len) return;
+    // the row's strength; the scalar entry passes bias = nullptr for 0, so a row at 0 takes the same (no) subtraction
+    vocos_spec_tile(O, bias, denoise_rows ? denoise_rows[b] : denoise, b, f0, t0, 0, len, T, S);
+}
+
+// frame t of row b: its 513 bins -> 1024 windowed samples, by the block's 256 threads
+__device__ __forceinline__ void vocos_istft_frame(const float2* __restrict__ S, const float* __restrict__ win, const float2* __restrict__ tw_g,
+                                                  int b, int t, int T, float* __restrict__ Y) {
     __shared__ float2 buf[2][V_NFFT];
     __shared__ float2 tw[V_NFFT];
-    const int b = blockIdx.y, t = blockIdx.x, i = threadIdx.x;
-    if (lens && t >= (int)lens[b]) return;                       // frames the overlap-add never reads
+    const int i = threadIdx.x;
     const float2* sb = S + ((int64_t)b * T + t) * V_NBIN;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -230,6 +234,73 @@ __global__ __launch_bounds__(256) void vocos_istft_kernel(const float2* __restri
         const int k = i + 256 * r;
         yb[k] = buf[1][k].x * (1.0f / V_NFFT) * win[k];
     }
+}
+
+__global__ __launch_bounds__(256) void vocos_istft_kernel(const float2* __restrict__ S, const int64_t* __restrict__ lens,
+                                                          const float* __restrict__ win, const float2* __restrict__ tw_g, int T,
+                                                          float* __restrict__ Y) {
+    const int b = blockIdx.y, t = blockIdx.x;
+    if (lens && t >= (int)lens[b]) return;                       // frames the overlap-add never reads
+    vocos_istft_frame(S, win, tw_g, b, t, T, Y);
+}
+
+// ---- the head of one streaming step (ttsamd_vocos_forward_windows): the three launches above on the frames and samples a window's
+// needed range can see.  Window w needs the samples of its frames [start[w], start[w] + len[w]) (host values, by value in the launch
+// arguments); lens[w] is read on the device, where gather wrote it.  A sample of frame c is the overlap-add of the frames c - r_l ...
+// c + 2 (r_l = 2 "same", 1 "center"; ttsamd.h), so spectrum and inverse FFT run on [start - r_l, start + len + 2) clipped to the window
+// and the overlap-add, a block per frame of samples, reads no other frame and writes no other sample.
+struct VocosWinTable {
+    int32_t start[TTSAMD_STREAM_MAX_WINDOWS], len[TTSAMD_STREAM_MAX_WINDOWS];
+};
+__device__ __forceinline__ void vocos_window_frames(const VocosWinTable& tab, int w, int len, int r_l, int& f_lo, int& f_hi) {
+    f_lo = max(tab.start[w] - r_l, 0);
+    f_hi = min(tab.start[w] + tab.len[w] + 2, len);
+}
+
+__global__ __launch_bounds__(256) void vocos_spec_t_windows_kernel(const float* __restrict__ O, const float* __restrict__ bias,
+                                                                   const float* __restrict__ denoise_rows, const int64_t* __restrict__ lens,
+                                                                   const VocosWinTable tab, int r_l, int T, float2* __restrict__ S) {
+    const int w = blockIdx.z, f0 = blockIdx.y * 32;
+    int f_lo, f_hi;
+    vocos_window_frames(tab, w, min((int)lens[w], T), r_l, f_lo, f_hi);
+    const int t0 = (f_lo & ~31) + blockIdx.x * 32;
+    if (t0 >= f_hi) return;
+    vocos_spec_tile(O, bias, denoise_rows ? denoise_rows[w] : 0.f, w, f0, t0, f_lo, f_hi, T, S);
+}
+
+__global__ __launch_bounds__(256) void vocos_istft_windows_kernel(const float2* __restrict__ S, const int64_t* __restrict__ lens,
+                                                                  const VocosWinTable tab, int r_l, const float* __restrict__ win,
+                                                                  const float2* __restrict__ tw_g, int T, float* __restrict__ Y) {
+    const int w = blockIdx.y;
+    int f_lo, f_hi;
+    vocos_window_frames(tab, w, min((int)lens[w], T), r_l, f_lo, f_hi);
+    const int t = f_lo + blockIdx.x;
+    if (t >= f_hi) return;
+    vocos_istft_frame(S, win, tw_g, w, t, T, Y);
+}
+
+// overlap_add_kernel (denoiser.hip) on frame-major Y for the samples of frame start[w] + blockIdx.x alone: the same terms over t
+// ascending, the same envelope, so the same bits
+__global__ __launch_bounds__(256) void vocos_overlap_add_windows_kernel(const float* __restrict__ Y, const float* __restrict__ win,
+                                                                        const int64_t* __restrict__ lens, const VocosWinTable tab, int pad,
+                                                                        int T, float* __restrict__ wave) {
+    const int w = blockIdx.y;
+    if ((int)blockIdx.x >= tab.len[w]) return;
+    const int fr = min((int)lens[w], T);
+    const int m = (tab.start[w] + blockIdx.x) * V_HOP + threadIdx.x;
+    const int n_out = (fr - 1) * V_HOP + V_NFFT - 2 * pad;
+    if (m >= n_out) return;
+    const int mp = m + pad;
+    const int t_hi = min(fr - 1, mp / V_HOP);
+    const int t_lo = mp >= V_NFFT ? (mp - V_NFFT) / V_HOP + 1 : 0;
+    float acc = 0.f, env = 0.f;
+    for (int t = t_lo; t <= t_hi; ++t) {
+        const int k = mp - t * V_HOP;
+        if (k < 0 || k >= V_NFFT) continue;
+        acc += Y[(int64_t)w * V_NFFT * T + (int64_t)k + (int64_t)t * V_NFFT];
+        env += win[k] * win[k];
+    }
+    wave[(int64_t)w * V_HOP * T + m] = acc / env;
 }
 
 // bias_vec[f] = min(exp(O[f][0]), 100)   (pretrained.py:65-69)
@@ -326,6 +397,17 @@ int64_t vocos_bias_workspace_bytes(const Vocos* h) {
     return a.off;
 }
 
+// the channel padding of '24k', then backbone + head.out
+static int32_t vocos_padded_features(const Vocos* h, const float* mel, const int64_t* lens, int B, int T, const VWs& w, hipStream_t s) {
+    if (w.m) {
+        hipLaunchKernelGGL(vocos_pad_channels_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)h->in_chp * T + 255) / 256, 1024), B),
+                           dim3(256), 0, s, mel, h->in_ch, h->in_chp, T, w.m);
+        TTS_CHECK_HIP(hipGetLastError());
+        mel = w.m;
+    }
+    return vocos_features(h, mel, lens, B, T, w, s);
+}
+
 // denoise_rows: device [B] in place of the scalar (ttsamd_vocos_forward_rows), nullptr: the scalar (ttsamd_vocos_forward)
 int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int32_t B, int32_t T, float denoise,
                       const float* denoise_rows, const float* bias_vec, float* wave, void* ws, int64_t ws_bytes, hipStream_t s) {
@@ -339,15 +421,9 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
         set_error("vocos_forward: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
         return TTSAMD_ENOMEM;
     }
-    if (w.m) {
-        hipLaunchKernelGGL(vocos_pad_channels_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)h->in_chp * T + 255) / 256, 1024), B),
-                           dim3(256), 0, s, mel, h->in_ch, h->in_chp, T, w.m);
-        TTS_CHECK_HIP(hipGetLastError());
-        mel = w.m;
-    }
-    TTS_TRY(vocos_features(h, mel, lens, B, T, w, s));
     // complex spectrum frame-major into the (dead) hidden buffer of the backbone: 513 float2 per frame <= inter floats
     TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_forward: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
+    TTS_TRY(vocos_padded_features(h, mel, lens, B, T, w, s));
     float2* S = reinterpret_cast<float2*>(w.h);
     hipLaunchKernelGGL(vocos_spec_t_kernel, dim3((T + 31) / 32, (V_NBIN + 31) / 32, B), dim3(256), 0, s, w.o,
                        (denoise != 0.f || denoise_rows) ? bias_vec : nullptr, denoise, denoise_rows, lens, T, S);
@@ -361,6 +437,55 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
     // overlap-add with "same" trimming (pad = (n_fft - hop) / 2, n_out = hop * frames) over the frame-major time-domain frames
     return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, (V_NFFT - V_HOP) / 2, B, T, V_HOP * T, wave,
                               (int64_t)V_HOP * T, s, /*frame_major=*/1);
+}
+
+// 3 (embed, k = 7) + 3 per ConvNeXt block (depthwise k = 7; LayerNorm, the pointwise convs and head.out are per frame), then the ISTFT's
+// reach in frames (ttsamd.h)
+int32_t vocos_halo_frames(const Vocos* h, int32_t* left, int32_t* right) {
+    TTS_REQUIRE(h && left && right, "vocos_halo_frames: null argument");
+    const int32_t reach = 3 + 3 * (int32_t)h->blocks.size();
+    *left = reach + (h->center ? 1 : 2);
+    *right = reach + 2;
+    return 0;
+}
+
+int32_t vocos_forward_windows(const Vocos* h, const float* mel, const int64_t* lens, int32_t W, int32_t T, const int32_t* need_start,
+                              const int32_t* need_len, const float* denoise_rows, const float* bias_vec, float* wave, void* ws,
+                              int64_t ws_bytes, hipStream_t s) {
+    TTS_REQUIRE(h && mel && lens && wave && need_start && need_len, "vocos_forward_windows: null argument");
+    TTS_REQUIRE(W >= 1 && W <= TTSAMD_STREAM_MAX_WINDOWS, "vocos_forward_windows: %d windows (1 .. %d)", W, TTSAMD_STREAM_MAX_WINDOWS);
+    TTS_REQUIRE(T >= 1 && (int64_t)V_NFFT * T * W < (1ll << 31), "vocos_forward_windows: bad w_max %d", T);
+    TTS_REQUIRE(!denoise_rows || bias_vec, "vocos_forward_windows: denoise_rows needs bias_vec");
+    TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_forward_windows: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
+    VocosWinTable tab = {};
+    int max_len = 0;
+    for (int w = 0; w < W; ++w) {
+        TTS_REQUIRE(need_start[w] >= 0 && need_len[w] >= 1 && (int64_t)need_start[w] + need_len[w] <= T,
+                    "vocos_forward_windows: window %d: needed frames [%d, %d + %d) outside [0, w_max = %d)", w, need_start[w], need_start[w],
+                    need_len[w], T);
+        tab.start[w] = need_start[w]; tab.len[w] = need_len[w];
+        max_len = std::max(max_len, (int)need_len[w]);
+    }
+    Arena a(ws, ws_bytes);
+    VWs v;
+    vcarve(h, a, W, T, v);
+    if (!ws || !a.ok) {
+        set_error("vocos_forward_windows: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
+        return TTSAMD_ENOMEM;
+    }
+    if (h->center && T == 1) return 0;       // as vocos_forward: no sample left
+    TTS_TRY(vocos_padded_features(h, mel, lens, W, T, v, s));
+    float2* S = reinterpret_cast<float2*>(v.h);
+    const int r_l = h->center ? 1 : 2, n_frames = std::min(max_len + r_l + 2, (int)T);
+    // the tiles start at the 32-frame boundary at or below a window's first frame
+    hipLaunchKernelGGL(vocos_spec_t_windows_kernel, dim3((n_frames + 31 + 31) / 32, (V_NBIN + 31) / 32, W), dim3(256), 0, s, v.o,
+                       denoise_rows ? bias_vec : nullptr, denoise_rows, lens, tab, r_l, T, S);
+    hipLaunchKernelGGL(vocos_istft_windows_kernel, dim3(n_frames, W), dim3(256), 0, s, S, lens, tab, r_l, h->dev + h->window,
+                       reinterpret_cast<const float2*>(h->dev + h->twiddle), T, v.y);
+    hipLaunchKernelGGL(vocos_overlap_add_windows_kernel, dim3(max_len, W), dim3(256), 0, s, v.y, h->dev + h->window, lens, tab,
+                       h->center ? V_NFFT / 2 : (V_NFFT - V_HOP) / 2, T, wave);
+    TTS_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace ttsamd

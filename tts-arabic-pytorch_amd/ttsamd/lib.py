@@ -82,6 +82,10 @@ SYMBOLS = {
     # ... resampled and encoded (format 0 fp32, 1 int16 PCM, 2 mu-law, 3 A-law): handle (or NULL), wave, W, w_max, hop, five HOST int32
     # arrays in utterance samples, c_max, format, out, nout (HOST int32, out), stream
     'ttsamd_stream_emit_resampled': (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    # Vocos in the stream (csrc/vocos.hip): handle, mel, lens, W, w_max, need_start / need_len (HOST int32), denoise_rows, bias_vec, wave,
+    # workspace, bytes, stream
+    'ttsamd_vocos_halo_frames': (_I32, [_P, C.POINTER(_I32), C.POINTER(_I32)]),
+    'ttsamd_vocos_forward_windows': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_wave_encode': (_I32, [_P, _I64, _P, _I32, _I32, _P, _I64, _P]),
     'ttsamd_fastpitch_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(FastPitchCfg), C.POINTER(_P)]),
     'ttsamd_fastpitch_destroy': (_I32, [_P]),

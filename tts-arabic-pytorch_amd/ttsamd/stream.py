@@ -1,11 +1,16 @@
-"""Streaming synthesis: chunked HiFi-GAN with continuous batching of windows (csrc/stream.hip).
+"""Streaming synthesis: chunked HiFi-GAN or Vocos with continuous batching of windows (csrc/stream.hip, csrc/vocos.hip).
 
 HiFi-GAN is a stack of zero-padded convolutions, so a window of mel frames with `halo` extra frames on each side gives, on its core, the
 samples of the whole-utterance call; a window that touches an utterance edge starts or ends exactly there, which keeps the per-layer
 zero padding (and the denoiser's reflect padding) what the whole-utterance call sees.  `plan_chunks` cuts an utterance into such
 windows; `StreamingVocoder` keeps the mels of the open utterances in a pool and, per `step()`, takes the next window of every one of
 them through ONE gather -> ttsamd_hifigan_forward -> ttsamd_denoise_rows -> emit sequence: utterances at different points of their
-lengths share one chip-filling vocoder call, and audio leaves while the rest is still being made."""
+lengths share one chip-filling vocoder call, and audio leaves while the rest is still being made.
+
+Vocos (MelVocos '22k' / '24k') goes the same way with its own receptive field (`vocos_halo_frames`): its backbone is zero-padded
+convolutions with a per-frame LayerNorm, its head an ISTFT whose frames overlap by three hops.  A step is gather ->
+ttsamd_vocos_forward_windows -> emit; the bias denoise is a per-frame spectral subtraction inside that call (no Denoiser, no halo of its
+own).  The "center" framing of '24k' gives an utterance of T frames 256 (T - 1) samples: `plan_chunks_center` cuts those."""
 import ctypes as C
 
 import numpy as np
@@ -34,6 +39,18 @@ def hifigan_halo_frames(config):
         lo, hi = lo - reach, hi + reach
         lo, hi = -((-(lo + p - kt + 1)) // u), (hi + p) // u
     return 3 - lo, hi + 3
+
+
+def vocos_halo_frames(config):
+    """(left, right): the receptive field of a Vocos vocoder in mel frames per side, from its config dict -- the derivation of
+    ttsamd_vocos_halo_frames (include/ttsamd.h) restated on the host.  The backbone (embed k = 7, then num_layers depthwise k = 7; the
+    rest is per frame) reaches 3 + 3 num_layers frames; sample 256 c + j sums the ISTFT frames t with 0 <= 256 (c - t) + j + pad < 1024:
+    c - 2 ... c + 2 with "same" (pad 384), c - 1 ... c + 2 with "center" (pad 512).  (29, 29) for '22k', (28, 29) for '24k'."""
+    reach = 3 + 3 * int(config['num_layers'])
+    padding = config.get('padding', 'same')
+    if padding not in ('same', 'center'):
+        raise ValueError(f'vocos_halo_frames: padding {padding!r}')
+    return reach + (1 if padding == 'center' else 2), reach + 2
 
 
 def pcm16(x):
@@ -100,6 +117,21 @@ def plan_chunks(T, first_chunk_frames, chunk_frames, halo_left, halo_right):
     return plan
 
 
+def plan_chunks_center(T, first_chunk_frames, chunk_frames, halo_left, halo_right):
+    """plan_chunks for the "center" framing (MelVocos '24k'), where an utterance of T >= 2 mel frames has hop * (T - 1) samples:
+    [(core_start, core_len, win_start, win_len)] with the cores in frames of hop SAMPLES, partitioning [0, T - 1) by plan_chunks' rule
+    (none is empty), and the windows in MEL frames: the frames the core's samples depend on, [core_start - halo_left, core_start +
+    core_len + halo_right) clipped to [0, T) -- up to T, one frame past the last core's end, which that core's samples read."""
+    T, hl, hr = int(T), int(halo_left), int(halo_right)
+    if T < 2:
+        raise ValueError(f'plan_chunks_center: {T} frame(s): the centred ISTFT needs at least 2')
+    plan = []
+    for s, n, _, _ in plan_chunks(T - 1, first_chunk_frames, chunk_frames, hl, hr):
+        ws = max(s - hl, 0)
+        plan.append((s, n, ws, min(s + n + hr, T) - ws))
+    return plan
+
+
 def max_core_frames(first_chunk_frames, chunk_frames):
     """the longest core plan_chunks can return: a core that took a folded remainder"""
     return max(int(first_chunk_frames), int(chunk_frames)) + max(int(chunk_frames) // 2 - 1, 0)
@@ -116,7 +148,9 @@ class StreamingVocoder:
     """Chunked vocoding of up to `max_streams` open utterances of up to `max_frames` frames each.
 
     vocoder: a vocoder.hifigan.models.Generator (V1 or V3) on the GPU; denoiser: the vocoder.hifigan.denoiser.Denoiser of that
-    generator, needed only for open(denoise > 0).  Every buffer is allocated here, once.  open(mel, denoise) -> sid copies a mel into a
+    generator, needed only for open(denoise > 0).  Or a vocoder.vocos.MelVocos ('22k' / '24k'): its bias denoise is part of the vocoder
+    call, so denoiser must stay None and open() takes any strength >= 0; with '24k' an utterance of T frames has 256 (T - 1) samples
+    and needs T >= 2.  Every buffer is allocated here, once.  open(mel, denoise) -> sid copies a mel into a
     free slot; step() returns the next chunk of every open utterance; an utterance closes itself after its last chunk.  Precision is
     the library's (ttsamd.engine.set_precision): the step calls the forward entry the one-shot path calls.
 
@@ -135,11 +169,19 @@ class StreamingVocoder:
         source_rate = int(getattr(vocoder, 'sampling_rate', None) or (getattr(vocoder, 'h', None) or {}).get('sampling_rate') or 22050)
         self._encoding, self._sample_rate, self._rs = delivery(source_rate, sample_rate, encoding, pcm16, lowpass_filter_width, rolloff)
         pcm16 = self._encoding == 'pcm16'
+        from vocoder.vocos import MelVocos
+        self._vocos = isinstance(vocoder, MelVocos)
+        if self._vocos and denoiser is not None:
+            raise ValueError('StreamingVocoder: a Vocos vocoder subtracts its bias inside the vocoder call: denoiser must be None')
         self.eng = vocoder.engine()
         self.lib, self.device = self.eng.lib, self.eng.device
-        self.hop, self.num_mels = self.eng.hop, self.eng.num_mels
+        self.hop, self.num_mels = self.eng.hop, self.eng.n_mels if self._vocos else self.eng.num_mels
+        self._center = bool(self._vocos and self.eng.center)          # utterance samples: hop * (T - 1)
         left, right = C.c_int32(), C.c_int32()
-        L.check(self.lib.ttsamd_hifigan_halo_frames(self.eng.handle, C.byref(left), C.byref(right)), 'hifigan_halo_frames')
+        if self._vocos:
+            L.check(self.lib.ttsamd_vocos_halo_frames(self.eng.handle, C.byref(left), C.byref(right)), 'vocos_halo_frames')
+        else:
+            L.check(self.lib.ttsamd_hifigan_halo_frames(self.eng.handle, C.byref(left), C.byref(right)), 'hifigan_halo_frames')
         self._halo = (left.value, right.value)
         self.max_streams, self.max_frames = int(max_streams), int(max_frames)
         self.chunk_frames, self.first_chunk_frames, self.pcm16 = int(chunk_frames), int(first_chunk_frames), bool(pcm16)
@@ -153,6 +195,8 @@ class StreamingVocoder:
             self._dn_eng = denoiser._engine(lambda d: DenoiserEngine(device=d))
             self._bias = denoiser._bias_spec(self.device).reshape(-1).contiguous()
         self._dn_halo = dn_halo
+        if self._vocos:
+            self._bias = self.eng.bias_vec().reshape(-1)
         dev = self.device
         # the resampled / G.711 path (ttsamd_stream_emit_resampled); None: ttsamd_stream_emit, as before there was one
         self._resampled = self._rs is not None or self._encoding in ('mulaw', 'alaw')
@@ -180,7 +224,7 @@ class StreamingVocoder:
 
     @property
     def halo(self):
-        """(left, right) receptive field of the vocoder in mel frames: ttsamd_hifigan_halo_frames of its handle"""
+        """(left, right) receptive field of the vocoder in mel frames: ttsamd_hifigan_halo_frames / ttsamd_vocos_halo_frames of its handle"""
         return self._halo
 
     @property
@@ -203,7 +247,8 @@ class StreamingVocoder:
 
     def open(self, mel, denoise=0.0):
         """mel [num_mels, T] (a device tensor: copied device to device) -> sid.  ValueError: T > max_frames, no free slot, a denoise
-        strength that is not finite, denoise > 0 without a denoiser or on an utterance of at most 512 samples (as the one-shot Denoiser)."""
+        strength that is not finite, denoise > 0 without a denoiser or on an utterance of at most 512 samples (as the one-shot Denoiser).
+        A Vocos vocoder takes any denoise >= 0 on any length; '24k' refuses one frame, as MelVocos.forward does."""
         import torch
         mel = torch.as_tensor(mel)
         if mel.dim() != 2 or mel.shape[0] != self.num_mels or mel.shape[1] < 1:
@@ -214,7 +259,12 @@ class StreamingVocoder:
             raise ValueError(f'StreamingVocoder.open: denoise {denoise!r} is not finite')
         if T > self.max_frames:
             raise ValueError(f'StreamingVocoder.open: {T} frames, the pool holds utterances of up to max_frames = {self.max_frames}')
-        if denoise > 0:
+        if self._vocos:
+            if denoise < 0:
+                raise ValueError(f'StreamingVocoder.open: denoise {denoise!r} is negative')
+            if self._center and T < 2:
+                raise ValueError("MelVocos('24k'): the centred ISTFT needs at least 2 frames (got %d)" % T)
+        elif denoise > 0:
             if self._dn_eng is None:
                 raise ValueError('StreamingVocoder.open: denoise > 0 needs the denoiser (StreamingVocoder(vocoder, denoiser=...))')
             if self.hop * T <= 512:
@@ -222,13 +272,14 @@ class StreamingVocoder:
                                  f'shortest has {self.hop * T}')
         if not self._free:
             raise ValueError(f'StreamingVocoder.open: all {self.max_streams} slots are taken (max_streams)')
-        halo = (self._dn_halo if denoise > 0 else 0) + self._rs_halo
-        plan = plan_chunks(T, self.first_chunk_frames, self.chunk_frames, self._halo[0] + halo, self._halo[1] + halo)
+        halo = (self._dn_halo if denoise > 0 and not self._vocos else 0) + self._rs_halo
+        plan = (plan_chunks_center if self._center else plan_chunks)(T, self.first_chunk_frames, self.chunk_frames, self._halo[0] + halo,
+                                                                     self._halo[1] + halo)
         slot = self._free.pop(0)
         self._pool[slot, :, :T].copy_(mel.to(dtype=torch.float32), non_blocking=True)
         sid = self._next_sid
         self._next_sid += 1
-        self._open[sid] = _Open(sid, slot, plan, denoise, T)
+        self._open[sid] = _Open(sid, slot, plan, denoise, T - 1 if self._center else T)        # frames of hop samples
         return sid
 
     def close(self, sid):
@@ -240,7 +291,8 @@ class StreamingVocoder:
         hop * core_len samples (float32, or int16 with pcm16) -- at another sample_rate, of the resampler's outputs that belong to the
         core (`chunk_outputs`: float32, int16, or uint8 for G.711) --, valid until the step after next; `last` marks an utterance's
         final chunk, after which it is closed.  One gather, one vocoder forward, one denoise (when a row asks for it) and one emit on
-        the current stream; the host waits for none of them (the chunk lengths are host arithmetic)."""
+        the current stream; the host waits for none of them (the chunk lengths are host arithmetic).  Vocos: one gather, one
+        ttsamd_vocos_forward_windows (whose head runs only on the core, widened by the resampler's reach), one emit."""
         import torch
         from .engine import _ptr, _stream
         rows = list(self._open.values())[:self._rows]
@@ -265,23 +317,35 @@ class StreamingVocoder:
         with torch.cuda.device(self.device):
             L.check(lib.ttsamd_stream_gather(_ptr(self._pool), self.max_streams, self.num_mels, self.max_frames, slot, start, length, W,
                                              w_max, _ptr(self._batch), _ptr(self._lens), _stream()), 'stream_gather')
-            nbytes = lib.ttsamd_hifigan_workspace_bytes(eng.handle, W, w_max)
-            ws = eng.ws.get(nbytes, self.device)
-            L.check(lib.ttsamd_hifigan_forward(eng.handle, _ptr(self._batch), _ptr(self._lens), W, w_max, _ptr(self._wave), _ptr(ws), nbytes,
-                                               _stream()), 'hifigan_forward')
-            if any(st.denoise > 0 for st in rows):
-                # the strengths go up from pinned memory, asynchronously; a row at 0 is left untouched by ttsamd_denoise_rows
-                strength = torch.tensor([st.denoise for st in rows], dtype=torch.float32).pin_memory().to(self.device, non_blocking=True)
-                nsamples = self._lens[:W] * self.hop
-                n_max = self.hop * w_max
-                nb = lib.ttsamd_denoiser_workspace_bytes(W, n_max)
-                dws = self._dn_eng.ws.get(nb, self.device)
-                L.check(lib.ttsamd_denoise_rows(self._dn_eng.handle, _ptr(self._wave), n_max, _ptr(nsamples), W, n_max, _ptr(self._bias),
-                                                _ptr(strength), _ptr(dws), nb, _stream()), 'denoise_rows')
+            if self._vocos:
+                # the samples the emit reads: the core, with another rate the resampler's reach around it, inside the utterance
+                need = [(max(c[0] - self._rs_halo, 0) - c[2], min(c[0] + c[1] + self._rs_halo, st.frames) - c[2]) for st, c in zip(rows, chunks)]
+                strength = None
+                if any(st.denoise > 0 for st in rows):
+                    strength = torch.tensor([st.denoise for st in rows], dtype=torch.float32).pin_memory().to(self.device, non_blocking=True)
+                nbytes = lib.ttsamd_vocos_workspace_bytes(eng.handle, W, w_max)
+                ws = eng.ws.get(nbytes, self.device)
+                L.check(lib.ttsamd_vocos_forward_windows(eng.handle, _ptr(self._batch), _ptr(self._lens), W, w_max, i32(*[a for a, _ in need]),
+                                                         i32(*[b - a for a, b in need]), _ptr(strength), _ptr(self._bias), _ptr(self._wave),
+                                                         _ptr(ws), nbytes, _stream()), 'vocos_forward_windows')
+            else:
+                nbytes = lib.ttsamd_hifigan_workspace_bytes(eng.handle, W, w_max)
+                ws = eng.ws.get(nbytes, self.device)
+                L.check(lib.ttsamd_hifigan_forward(eng.handle, _ptr(self._batch), _ptr(self._lens), W, w_max, _ptr(self._wave), _ptr(ws), nbytes,
+                                                   _stream()), 'hifigan_forward')
+                if any(st.denoise > 0 for st in rows):
+                    # the strengths go up from pinned memory, asynchronously; a row at 0 is left untouched by ttsamd_denoise_rows
+                    strength = torch.tensor([st.denoise for st in rows], dtype=torch.float32).pin_memory().to(self.device, non_blocking=True)
+                    nsamples = self._lens[:W] * self.hop
+                    n_max = self.hop * w_max
+                    nb = lib.ttsamd_denoiser_workspace_bytes(W, n_max)
+                    dws = self._dn_eng.ws.get(nb, self.device)
+                    L.check(lib.ttsamd_denoise_rows(self._dn_eng.handle, _ptr(self._wave), n_max, _ptr(nsamples), W, n_max, _ptr(self._bias),
+                                                    _ptr(strength), _ptr(dws), nb, _stream()), 'denoise_rows')
             if self._resampled:
                 hop = self.hop
                 L.check(lib.ttsamd_stream_emit_resampled(self._rs_eng.handle if self._rs_eng else None, _ptr(self._wave), W, w_max, hop,
-                                                         i32(*[hop * c[2] for c in chunks]), i32(*[hop * c[3] for c in chunks]),
+                                                         i32(*[hop * c[2] for c in chunks]), i32(*[hop * (c[3] - self._center) for c in chunks]),
                                                          i32(*[hop * st.frames for st in rows]), i32(*[hop * c[0] for c in chunks]),
                                                          i32(*[hop * (c[0] + c[1]) for c in chunks]), c_max, ENCODINGS[self._encoding],
                                                          _ptr(out), None, _stream()), 'stream_emit_resampled')

@@ -25,6 +25,8 @@ class MelVocos(_HipModule):
         self.config = {'22k': config_22k, '24k': config_24k}[config_name]
         self.feature_extractor = MelSpectrogramFeatures(**self.config['feature_extractor'])
         self.n_mels = self.config['input_channels']
+        # the rate of the wave: 22 050 / 24 000 Hz ('22k''s feature extractor keeps the reference's 24 000, which is not it)
+        self.sampling_rate = self.config['sample_rate']
         self._sd = None
 
     def load_state_dict(self, state_dict, strict=True):
@@ -52,6 +54,19 @@ class MelVocos(_HipModule):
             # torch.istft(center=True) of a single frame has no sample left after trimming n_fft / 2 per side and raises
             raise ValueError("MelVocos('24k'): the centred ISTFT needs at least 2 frames (got %d)" % mel_spec.shape[-1])
         return eng.forward(mel_spec, lens, denoise)
+
+    def stream(self, mel, chunk_frames=64, first_chunk_frames=32, pcm16=False, denoise=0.0, sample_rate=None, encoding=None):
+        """Extension (ttsamd.stream), as Generator.stream: mel [n_mels, T] -> a generator of device chunks whose concatenation is
+        forward(mel, denoise)'s 256 T ('22k') or 256 (T - 1) ('24k') samples, the first after first_chunk_frames frames of work plus
+        the halo instead of T.  sample_rate / encoding ('float32' | 'pcm16' | 'mulaw' | 'alaw'): the chunks leave resampled to that rate
+        and encoded (StreamingVocoder).  A chunk stays valid until the one after next has been taken."""
+        from ttsamd.stream import StreamingVocoder
+        sv = StreamingVocoder(self, max_streams=1, max_frames=int(mel.shape[-1]), chunk_frames=chunk_frames,
+                              first_chunk_frames=first_chunk_frames, pcm16=pcm16, sample_rate=sample_rate, encoding=encoding)
+        sv.open(mel, denoise)
+        while sv.open_streams:
+            for _, chunk, _ in sv.step():
+                yield chunk
 
     @torch.inference_mode()
     def reconstruct(self, wave, denoise=0., lens=None):
