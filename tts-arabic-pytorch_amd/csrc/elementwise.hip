@@ -507,7 +507,9 @@ __global__ __launch_bounds__(256) void attention_merge_kernel(const float* __res
     }
     const int i = blockIdx.x * 16 + ti;
     if (i >= S) return;
-    const float inv = 1.0f / l;
+    // a row of length 0 has no tile: l = 0, and 0 * (1 / 0) would put NaN where attention_kernel writes zeros (the split-bf16 conv-FF
+    // writes frame `len` of x from it, which LayerNorm's mask multiply cannot clear)
+    const float inv = len > 0 ? 1.0f / l : 0.f;
     float* ob = out + (int64_t)b * ATT_D * S;
 #pragma unroll
     for (int c = 0; c < 4; ++c) ob[(int64_t)(j0 + c) * S + i] = o[c] * inv;

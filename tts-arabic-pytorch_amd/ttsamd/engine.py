@@ -208,23 +208,21 @@ class FastPitchEngine:
             self.lib.ttsamd_fastpitch_destroy(self.handle)
             self.handle = None
 
-    def infer(self, ids, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_mul=1.0, pitch_add=0.0,
-              max_duration=75, speaker=0, return_idx=False, lens_hook=None, alone=False):
-        """Same contract as FastPitch.infer (model.py:351-353) with pitch_transform restricted to
-        the affine pitch_trf the reference wrappers install (networks.py:38-42,121-122).
-        ids int64 [B,L] zero-padded at the end.  Returns (mel [B,80,T_max], dec_lens int64 [B],
-        dur_pred [B,L], pitch_pred [B,1,L], energy_pred [B,L] or None).
-        `lens_hook(dec_lens_device) -> host ints [B]` replaces the one device->host read of the call (the
-        data-parallel path all-gathers every rank's lengths in that same synchronisation, ttsamd.dp).
-        `alone=True`: every row as if it were the only utterance of the call (ttsamd_fastpitch_set_batch_mode 1) -- row b equals
-        infer(ids[b:b+1, :len_b]) within fp32 summation order: the reference's batch_size = 1 loop as one ragged call.
-        Mixed requests: `pace`, `speaker`, `pitch_mul` and `pitch_add` each take a scalar or B values (list / array / tensor), checked
-        on the host (length B, speaker in range, pace finite and > 0: ValueError / IndexError) before they are uploaded.  With any
-        per-row control the call runs ttsamd_fastpitch_encode_rows / _decode_rows -- row b's bits are those of the scalar call with row
-        b's values -- and `alone` goes down as the per-call flag: the handle's mode is left alone.  All scalars: the route above."""
+    def set_batch_mode(self, alone):
+        """ttsamd_fastpitch_set_batch_mode: how the calls WITHOUT per-row controls treat a batch from now on (False: the reference's padded
+        batch; True: every row as if alone).  encode / decode / infer set it from their `alone` argument."""
+        if bool(alone) != self._alone:
+            L.check(self.lib.ttsamd_fastpitch_set_batch_mode(self.handle, int(bool(alone))), 'fastpitch_set_batch_mode')
+            self._alone = bool(alone)
+
+    def encode(self, ids, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_mul=1.0, pitch_add=0.0, max_duration=75,
+               speaker=0, alone=False):
+        """Phase A of `infer` (ttsamd_fastpitch_encode / _encode_rows; model.py:355-399 and the integer half of regulate_len), arguments as
+        there.  Returns (enc_cond [B,d_model,L] channel-first -- the input of length_regulate --, dur_pred [B,L], pitch_pred [B,1,L],
+        energy_pred [B,L] or None, reps int64 [B,L], dec_lens int64 [B]), all on the device; nothing is read back to the host."""
         dev = self.device
         ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int64).contiguous()
-        B, Lt0 = ids.shape
+        B, Lt = ids.shape
         rows = {k: row_values(v, B, k) if per_row(v) else None
                 for k, v in (('pace', pace), ('speaker', speaker), ('pitch_mul', pitch_mul), ('pitch_add', pitch_add))}
         mixed = any(v is not None for v in rows.values())
@@ -241,19 +239,10 @@ class FastPitchEngine:
             speaker, pace = (0 if spk_rows is not None else speaker), (1.0 if pace_rows is not None else pace)
             pitch_mul, pitch_add = (1.0 if mul_rows is not None else pitch_mul), (0.0 if add_rows is not None else pitch_add)
             flags = int(bool(alone))
-        elif bool(alone) != self._alone:
-            L.check(self.lib.ttsamd_fastpitch_set_batch_mode(self.handle, int(bool(alone))), 'fastpitch_set_batch_mode')
-            self._alone = bool(alone)
+        else:
+            self.set_batch_mode(alone)
         d = self.d_model
         dur_tgt, pitch_tgt, energy_tgt = _f32(dur_tgt, dev), _f32(pitch_tgt, dev), _f32(energy_tgt, dev)
-        # Batches: the DECODER's frame rows padded to a multiple of 4 (16 bytes).  The conv engine's fast paths -- the Winograd F(4,3) kernel,
-        # the float4 row epilogue -- need 16-byte-aligned rows, and a real batch's longest utterance is a multiple of 4 one time in four (config
-        # 1: three of the four FastPitch calls ran the decoder conv-FF on the direct kernel's per-lane epilogue, 2x the time).  The decoder
-        # takes the batch's length from dec_lens, not from the row width (lens_plus1_kernel), so the extra columns are plain padding; mel is
-        # returned as a view of the un-padded shape.  (Batch 1 keeps its exact shape: one launch more would cost what alignment gains; the
-        # bf16 octet path has no ragged schedule; the encoder's rows stay as given -- the caller's ids tensor IS the reference's padded batch.)
-        pad = B >= 2 and self._pad_ok and get_precision() != 'bf16'
-        Lt = Lt0
         enc = torch.empty(B, d, Lt, dtype=torch.float32, device=dev)
         dur_pred = torch.empty(B, Lt, dtype=torch.float32, device=dev)
         pitch_pred = torch.empty(B, 1, Lt, dtype=torch.float32, device=dev)
@@ -272,6 +261,63 @@ class FastPitchEngine:
                                                          _stream()), 'fastpitch_encode_rows')
             else:
                 L.check(lib.ttsamd_fastpitch_encode(*args, _stream()), 'fastpitch_encode')
+        return enc, dur_pred, pitch_pred, energy_pred, reps, dec_lens
+
+    def decode(self, x, dec_lens, alone=False, rows=False):
+        """Phase B of `infer` (ttsamd_fastpitch_decode; model.py:405-408): x [B,d_model,T] float32 channel-first on the device (the output
+        of length_regulate: zero past a row's length; used as scratch and CLOBBERED), dec_lens int64 [B] -> mel [B,80,T], rows exactly as
+        wide as x's.  `rows=True`: ttsamd_fastpitch_decode_rows with `alone` as the per-call flag (the phase B of a call with per-row
+        controls: the handle's mode is left alone)."""
+        dev = self.device
+        B, d, T = x.shape
+        assert d == self.d_model and x.dtype == torch.float32 and x.is_contiguous() and x.device == dev
+        dec_lens = torch.as_tensor(dec_lens).to(device=dev, dtype=torch.int64).contiguous()
+        if not rows:
+            self.set_batch_mode(alone)
+        mel = torch.empty(B, self.n_mel, T, dtype=torch.float32, device=dev)
+        if T > 0:
+            lib = self.lib
+            with torch.cuda.device(dev):
+                nb = lib.ttsamd_fastpitch_decode_workspace_bytes(self.handle, B, T)
+                ws = self.ws.get(nb, dev)
+                args = (self.handle, _ptr(x), _ptr(dec_lens), B, T, _ptr(mel), _ptr(ws), nb)
+                if rows:
+                    L.check(lib.ttsamd_fastpitch_decode_rows(*args, int(bool(alone)), _stream()), 'fastpitch_decode_rows')
+                else:
+                    L.check(lib.ttsamd_fastpitch_decode(*args, _stream()), 'fastpitch_decode')
+        return mel
+
+    def infer(self, ids, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_mul=1.0, pitch_add=0.0,
+              max_duration=75, speaker=0, return_idx=False, lens_hook=None, alone=False):
+        """Same contract as FastPitch.infer (model.py:351-353) with pitch_transform restricted to
+        the affine pitch_trf the reference wrappers install (networks.py:38-42,121-122).
+        ids int64 [B,L] zero-padded at the end.  Returns (mel [B,80,T_max], dec_lens int64 [B],
+        dur_pred [B,L], pitch_pred [B,1,L], energy_pred [B,L] or None).
+        `lens_hook(dec_lens_device) -> host ints [B]` replaces the one device->host read of the call (the
+        data-parallel path all-gathers every rank's lengths in that same synchronisation, ttsamd.dp).
+        `alone=True`: every row as if it were the only utterance of the call (ttsamd_fastpitch_set_batch_mode 1) -- row b equals
+        infer(ids[b:b+1, :len_b]) within fp32 summation order: the reference's batch_size = 1 loop as one ragged call.
+        Mixed requests: `pace`, `speaker`, `pitch_mul` and `pitch_add` each take a scalar or B values (list / array / tensor), checked
+        on the host (length B, speaker in range, pace finite and > 0: ValueError / IndexError) before they are uploaded.  With any
+        per-row control the call runs ttsamd_fastpitch_encode_rows / _decode_rows -- row b's bits are those of the scalar call with row
+        b's values -- and `alone` goes down as the per-call flag: the handle's mode is left alone.  All scalars: the route above.
+        The two phases are `encode` and `decode`; between them the one host read and the length regulator."""
+        dev = self.device
+        ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int64).contiguous()
+        B, Lt = ids.shape
+        mixed = any(per_row(v) for v in (pace, speaker, pitch_mul, pitch_add))
+        enc, dur_pred, pitch_pred, energy_pred, reps, dec_lens = self.encode(
+            ids, pace=pace, dur_tgt=dur_tgt, pitch_tgt=pitch_tgt, energy_tgt=energy_tgt, pitch_mul=pitch_mul, pitch_add=pitch_add,
+            max_duration=max_duration, speaker=speaker, alone=alone)
+        d = self.d_model
+        # Batches: the DECODER's frame rows padded to a multiple of 4 (16 bytes).  The conv engine's fast paths -- the Winograd F(4,3) kernel,
+        # the float4 row epilogue -- need 16-byte-aligned rows, and a real batch's longest utterance is a multiple of 4 one time in four (config
+        # 1: three of the four FastPitch calls ran the decoder conv-FF on the direct kernel's per-lane epilogue, 2x the time).  The decoder
+        # takes the batch's length from dec_lens, not from the row width (lens_plus1_kernel), so the extra columns are plain padding; mel is
+        # returned as a view of the un-padded shape.  (Batch 1 keeps its exact shape: one launch more would cost what alignment gains; the
+        # bf16 octet path has no ragged schedule; the encoder's rows stay as given -- the caller's ids tensor IS the reference's padded batch.)
+        pad = B >= 2 and self._pad_ok and get_precision() != 'bf16'
+        with torch.cuda.device(dev):
             if lens_hook is None:
                 t_max0 = int(dec_lens.max().item())     # the reference syncs here too (model.py:76)
             else:
@@ -279,17 +325,10 @@ class FastPitchEngine:
             t_max = (t_max0 + 3) & ~3 if pad else t_max0
             x = torch.empty(B, d, t_max, dtype=torch.float32, device=dev)
             idx = torch.empty(B, t_max, dtype=torch.int32, device=dev) if return_idx else None
-            mel = torch.empty(B, self.n_mel, t_max, dtype=torch.float32, device=dev)
             if t_max > 0:
-                L.check(lib.ttsamd_length_regulate(_ptr(enc), _ptr(reps), B, Lt, d, t_max, _ptr(x), _ptr(idx), _stream()),
+                L.check(self.lib.ttsamd_length_regulate(_ptr(enc), _ptr(reps), B, Lt, d, t_max, _ptr(x), _ptr(idx), _stream()),
                         'length_regulate')
-                nb = lib.ttsamd_fastpitch_decode_workspace_bytes(self.handle, B, t_max)
-                ws = self.ws.get(nb, dev)
-                args = (self.handle, _ptr(x), _ptr(dec_lens), B, t_max, _ptr(mel), _ptr(ws), nb)
-                if mixed:
-                    L.check(lib.ttsamd_fastpitch_decode_rows(*args, flags, _stream()), 'fastpitch_decode_rows')
-                else:
-                    L.check(lib.ttsamd_fastpitch_decode(*args, _stream()), 'fastpitch_decode')
+        mel = self.decode(x, dec_lens, alone=alone, rows=mixed)
         if t_max != t_max0:
             mel = mel[:, :, :t_max0]
             idx = None if idx is None else idx[:, :t_max0]
