@@ -898,6 +898,21 @@ int32_t ttsamd_vocos_forward_windows(void* handle, const float* mel, const int64
                                      const int32_t* need_start /* host */, const int32_t* need_len /* host */,
                                      const float* denoise_rows /* device, may be NULL = 0 */, const float* bias_vec, float* wave,
                                      void* workspace, int64_t workspace_bytes, void* stream);
+/* Backbone and head of a Vocos handle apart (csrc/vocos.hip).  New symbols only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.
+ * ttsamd_vocos_features: mel and lens as for ttsamd_vocos_forward -> out [batch][1026][t_max], what head.out returns: rows 0 .. 512 the
+ * log-magnitudes, rows 513 .. 1025 the phases, without the padding rows of the library's own buffer; frames t >= lens[b] are written
+ * as zero.  The launches are those of ttsamd_vocos_forward up to the spectrum, so the values have its bits.
+ * ttsamd_vocos_head: feats [batch][1026][t_max] in that layout -> wave [batch][256 * t_max] as ttsamd_vocos_forward_rows writes it:
+ * mag = clamp(exp(log-magnitude) - denoise_rows[b] * bias_vec, 0, 100), times (cos, sin)(phase), one 1024-point inverse FFT per frame
+ * t < lens[b], overlap-add with the handle's trimming ("same" / "center", ttsamd_vocos_set_padding); samples at or past a row's end are
+ * not written, and "center" with t_max = 1 writes nothing.  denoise_rows: device float [batch] or NULL (no subtraction; a row at 0 has
+ * the same bits); with it bias_vec is needed.  ttsamd_vocos_head(ttsamd_vocos_features(mel)) has the bits of ttsamd_vocos_forward_rows(mel).
+ * ttsamd_vocos_workspace_bytes(handle, batch, t_max) is enough workspace for either (less: TTSAMD_ENOMEM). */
+int32_t ttsamd_vocos_features(void* handle, const float* mel, const int64_t* lens, int32_t batch, int32_t t_max, float* out,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int32_t ttsamd_vocos_head(void* handle, const float* feats, const int64_t* lens, int32_t batch, int32_t t_max,
+                          const float* denoise_rows /* device, may be NULL = 0 */, const float* bias_vec, float* wave, void* workspace,
+                          int64_t workspace_bytes, void* stream);
 /* The encoder alone, for finished waves: wave [batch][wave_stride] fp32 -> out [batch][out_stride] elements of format 1 (int16), 2 or 3
  * (one byte) as above.  nsamples: device int64 [batch], clamped to [0, wave_stride], or NULL for the full stride; samples
  * [0, nsamples[b]) of row b are converted, the entries behind them up to min(wave_stride, out_stride) are written as zero.  wave and

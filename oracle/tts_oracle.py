@@ -282,10 +282,11 @@ def denoiser_bias_spec(w_folded, cfg, dtype=torch.float32):
     return spec[:, :, 0][:, :, None]
 
 
-def denoise(wave, bias_spec, strength):
+def denoise(wave, bias_spec, strength, dtype=torch.float32):
     """vocoder/hifigan/denoiser.py:66-72.  wave [1,n]."""
-    wave = wave.float()
-    win = torch.hann_window(1024)
+    wave = wave.to(dtype)
+    bias_spec = _t(bias_spec, dtype)
+    win = torch.hann_window(1024, dtype=dtype)
     spec = torch.stft(wave, 1024, 256, 1024, win, center=True, pad_mode='reflect',
                       normalized=False, onesided=True, return_complex=True)
     mag, ph = spec.abs(), spec.angle()

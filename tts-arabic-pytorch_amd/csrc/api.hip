@@ -88,6 +88,9 @@ int32_t vocos_forward(const Vocos*, const float*, const int64_t*, int32_t, int32
                       int64_t, hipStream_t);
 int32_t vocos_set_padding(Vocos*, int32_t);
 int32_t vocos_halo_frames(const Vocos*, int32_t*, int32_t*);
+int32_t vocos_features_out(const Vocos*, const float*, const int64_t*, int32_t, int32_t, float*, void*, int64_t, hipStream_t);
+int32_t vocos_head(const Vocos*, const float*, const int64_t*, int32_t, int32_t, const float*, const float*, float*, void*, int64_t,
+                   hipStream_t);
 int32_t vocos_forward_windows(const Vocos*, const float*, const int64_t*, int32_t, int32_t, const int32_t*, const int32_t*, const float*,
                               const float*, float*, void*, int64_t, hipStream_t);
 struct MelSpec;
@@ -490,6 +493,15 @@ int32_t ttsamd_vocos_forward_rows(void* handle, const float* mel, const int64_t*
                          (hipStream_t)stream);
 }
 
+int32_t ttsamd_vocos_features(void* handle, const float* mel, const int64_t* lens, int32_t batch, int32_t t_max, float* out,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    return vocos_features_out((Vocos*)handle, mel, lens, batch, t_max, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int32_t ttsamd_vocos_head(void* handle, const float* feats, const int64_t* lens, int32_t batch, int32_t t_max, const float* denoise_rows,
+                          const float* bias_vec, float* wave, void* workspace, int64_t workspace_bytes, void* stream) {
+    return vocos_head((Vocos*)handle, feats, lens, batch, t_max, denoise_rows, bias_vec, wave, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
 int32_t ttsamd_vocos_set_padding(void* handle, int32_t mode) { return vocos_set_padding((Vocos*)handle, mode); }
 
 int32_t ttsamd_vocos_halo_frames(void* handle, int32_t* left, int32_t* right) {

@@ -174,12 +174,13 @@ void vocos_destroy(Vocos* h) {
 //    imaginary parts of DC and Nyquist dropped as irfft does), runs ONE 1024-point FFT in LDS (fft1024.hpp) and writes Re / 1024 * window as
 //    Y[b][t][k].  Rounds 1-5 ran the inverse DFT as a [1152 -> 1024] GEMM on the conv engine: 300 us per B = 32 call (40x the FLOPs).
 // one 32 x 32 tile of row b: bins f0 ..., frames t0 ... of which those in [t_lo, t_hi) are computed and written, no other
-__device__ __forceinline__ void vocos_spec_tile(const float* __restrict__ O, const float* __restrict__ bias, float dn, int b, int f0, int t0,
-                                                int t_lo, int t_hi, int T, float2* __restrict__ S) {
+// o_bs: batch stride of O in floats (V_SPEC_CP * T for the backbone's own buffer, 1026 * T for a caller's features)
+__device__ __forceinline__ void vocos_spec_tile(const float* __restrict__ O, int64_t o_bs, const float* __restrict__ bias, float dn, int b, int f0,
+                                                int t0, int t_lo, int t_hi, int T, float2* __restrict__ S) {
     __shared__ float2 tile[32][33];
     const bool sub = bias != nullptr && dn != 0.f;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 32 x 8
-    const float* ob = O + (int64_t)b * V_SPEC_CP * T;
+    const float* ob = O + (int64_t)b * o_bs;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int f = f0 + ty + 8 * r, t = t0 + tx;
@@ -201,13 +202,13 @@ __device__ __forceinline__ void vocos_spec_tile(const float* __restrict__ O, con
     }
 }
 
-__global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restrict__ O, const float* __restrict__ bias, float denoise,
+__global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restrict__ O, int64_t o_bs, const float* __restrict__ bias, float denoise,
                                                            const float* __restrict__ denoise_rows, const int64_t* __restrict__ lens, int T, float2* __restrict__ S) {
     const int b = blockIdx.z, f0 = blockIdx.y * 32, t0 = blockIdx.x * 32;
     const int len = lens ? min((int)lens[b], T) : T;
     if (t0 >= len) return;
     // the row's strength; the scalar entry passes bias = nullptr for 0, so a row at 0 takes the same (no) subtraction
-    vocos_spec_tile(O, bias, denoise_rows ? denoise_rows[b] : denoise, b, f0, t0, 0, len, T, S);
+    vocos_spec_tile(O, o_bs, bias, denoise_rows ? denoise_rows[b] : denoise, b, f0, t0, 0, len, T, S);
 }
 
 // frame t of row b: its 513 bins -> 1024 windowed samples, by the block's 256 threads
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(256) void vocos_spec_t_windows_kernel(const float* 
     vocos_window_frames(tab, w, min((int)lens[w], T), r_l, f_lo, f_hi);
     const int t0 = (f_lo & ~31) + blockIdx.x * 32;
     if (t0 >= f_hi) return;
-    vocos_spec_tile(O, bias, denoise_rows ? denoise_rows[w] : 0.f, w, f0, t0, f_lo, f_hi, T, S);
+    vocos_spec_tile(O, (int64_t)V_SPEC_CP * T, bias, denoise_rows ? denoise_rows[w] : 0.f, w, f0, t0, f_lo, f_hi, T, S);
 }
 
 __global__ __launch_bounds__(256) void vocos_istft_windows_kernel(const float2* __restrict__ S, const int64_t* __restrict__ lens,
@@ -408,6 +409,24 @@ static int32_t vocos_padded_features(const Vocos* h, const float* mel, const int
     return vocos_features(h, mel, lens, B, T, w, s);
 }
 
+// the ISTFT head on O [B][>= 1026 rows][T] with batch stride o_bs: spectrum -> inverse FFT -> overlap-add
+static int32_t vocos_head_run(const Vocos* h, const float* O, int64_t o_bs, const int64_t* lens, int B, int T, float denoise,
+                              const float* denoise_rows, const float* bias_vec, float* wave, const VWs& w, hipStream_t s) {
+    float2* S = reinterpret_cast<float2*>(w.h);
+    hipLaunchKernelGGL(vocos_spec_t_kernel, dim3((T + 31) / 32, (V_NBIN + 31) / 32, B), dim3(256), 0, s, O, o_bs,
+                       (denoise != 0.f || denoise_rows) ? bias_vec : nullptr, denoise, denoise_rows, lens, T, S);
+    hipLaunchKernelGGL(vocos_istft_kernel, dim3(T, B), dim3(256), 0, s, S, lens, h->dev + h->window,
+                       reinterpret_cast<const float2*>(h->dev + h->twiddle), T, w.y);
+    TTS_CHECK_HIP(hipGetLastError());
+    // "center" (24k): torch.istft(center=True) trimming, pad = n_fft / 2, n_out = hop * (frames - 1) per utterance; rows keep the stride hop * T
+    if (h->center)
+        return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, V_NFFT / 2, B, T, V_HOP * (T - 1), wave, (int64_t)V_HOP * T, s,
+                                  /*frame_major=*/1);
+    // overlap-add with "same" trimming (pad = (n_fft - hop) / 2, n_out = hop * frames) over the frame-major time-domain frames
+    return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, (V_NFFT - V_HOP) / 2, B, T, V_HOP * T, wave,
+                              (int64_t)V_HOP * T, s, /*frame_major=*/1);
+}
+
 // denoise_rows: device [B] in place of the scalar (ttsamd_vocos_forward_rows), nullptr: the scalar (ttsamd_vocos_forward)
 int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int32_t B, int32_t T, float denoise,
                       const float* denoise_rows, const float* bias_vec, float* wave, void* ws, int64_t ws_bytes, hipStream_t s) {
@@ -424,19 +443,52 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
     // complex spectrum frame-major into the (dead) hidden buffer of the backbone: 513 float2 per frame <= inter floats
     TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_forward: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
     TTS_TRY(vocos_padded_features(h, mel, lens, B, T, w, s));
-    float2* S = reinterpret_cast<float2*>(w.h);
-    hipLaunchKernelGGL(vocos_spec_t_kernel, dim3((T + 31) / 32, (V_NBIN + 31) / 32, B), dim3(256), 0, s, w.o,
-                       (denoise != 0.f || denoise_rows) ? bias_vec : nullptr, denoise, denoise_rows, lens, T, S);
-    hipLaunchKernelGGL(vocos_istft_kernel, dim3(T, B), dim3(256), 0, s, S, lens, h->dev + h->window,
-                       reinterpret_cast<const float2*>(h->dev + h->twiddle), T, w.y);
+    return vocos_head_run(h, w.o, (int64_t)V_SPEC_CP * T, lens, B, T, denoise, denoise_rows, bias_vec, wave, w, s);
+}
+
+// rows f < 1026 of the backbone's [B][V_SPEC_CP][T] buffer -> a caller's [B][1026][T]; frames t >= lens[b], which no conv writes, as zero
+__global__ __launch_bounds__(256) void vocos_copy_features_kernel(const float* __restrict__ O, const int64_t* __restrict__ lens, int T,
+                                                                  float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int len = min((int)lens[b], T);
+    const int64_t n = (int64_t)(V_NFFT + 2) * T;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
+        out[b * n + e] = (int)(e % T) < len ? O[(int64_t)b * V_SPEC_CP * T + e] : 0.f;
+}
+
+// backbone + head.out alone (ttsamd_vocos_features): the launches of vocos_forward up to the spectrum, then the copy above
+int32_t vocos_features_out(const Vocos* h, const float* mel, const int64_t* lens, int32_t B, int32_t T, float* out, void* ws,
+                           int64_t ws_bytes, hipStream_t s) {
+    TTS_REQUIRE(h && mel && out && lens && B >= 1 && T >= 1, "vocos_features: bad argument");
+    Arena a(ws, ws_bytes);
+    VWs w;
+    vcarve(h, a, B, T, w);
+    if (!ws || !a.ok) {
+        set_error("vocos_features: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
+        return TTSAMD_ENOMEM;
+    }
+    TTS_TRY(vocos_padded_features(h, mel, lens, B, T, w, s));
+    hipLaunchKernelGGL(vocos_copy_features_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)(V_NFFT + 2) * T + 255) / 256, 1024), B),
+                       dim3(256), 0, s, w.o, lens, T, out);
     TTS_CHECK_HIP(hipGetLastError());
-    // "center" (24k): torch.istft(center=True) trimming, pad = n_fft / 2, n_out = hop * (frames - 1) per utterance; rows keep the stride hop * T
-    if (h->center)
-        return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, V_NFFT / 2, B, T, V_HOP * (T - 1), wave, (int64_t)V_HOP * T, s,
-                                  /*frame_major=*/1);
-    // overlap-add with "same" trimming (pad = (n_fft - hop) / 2, n_out = hop * frames) over the frame-major time-domain frames
-    return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, (V_NFFT - V_HOP) / 2, B, T, V_HOP * T, wave,
-                              (int64_t)V_HOP * T, s, /*frame_major=*/1);
+    return 0;
+}
+
+// spectrum, inverse FFT and overlap-add alone (ttsamd_vocos_head) on a caller's [B][1026][T]: the launches of vocos_forward behind head.out
+int32_t vocos_head(const Vocos* h, const float* feats, const int64_t* lens, int32_t B, int32_t T, const float* denoise_rows,
+                   const float* bias_vec, float* wave, void* ws, int64_t ws_bytes, hipStream_t s) {
+    TTS_REQUIRE(h && feats && wave && lens && B >= 1 && T >= 1, "vocos_head: bad argument");
+    TTS_REQUIRE(!denoise_rows || bias_vec, "vocos_head: denoise_rows needs bias_vec");
+    if (h->center && T == 1) return 0;       // as vocos_forward: no sample left
+    Arena a(ws, ws_bytes);
+    VWs w;
+    vcarve(h, a, B, T, w);
+    if (!ws || !a.ok) {
+        set_error("vocos_head: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
+        return TTSAMD_ENOMEM;
+    }
+    TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_head: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
+    return vocos_head_run(h, feats, (int64_t)(V_NFFT + 2) * T, lens, B, T, 0.f, denoise_rows, bias_vec, wave, w, s);
 }
 
 // 3 (embed, k = 7) + 3 per ConvNeXt block (depthwise k = 7; LayerNorm, the pointwise convs and head.out are per frame), then the ISTFT's

@@ -512,6 +512,56 @@ class VocosEngine:
                                                       _ptr(wave), _ptr(ws), nb, _stream()), 'vocos_forward')
         return wave if wave.shape[1] == n0 else wave[:, :n0]
 
+    def features(self, mel, lens=None):
+        """mel [B, n_mels, T] with T a multiple of 4 (what forward() pads to), lens int64 [B] or None -> head.out's output [B, 1026, T]
+        (log-magnitude | phase): the backbone of forward() alone, the same launches and bits."""
+        mel = _f32(mel, self.device)
+        B, M, T = mel.shape
+        assert M == self.n_mels and B >= 1 and T >= 1 and T % 4 == 0
+        if lens is None:
+            lens = torch.full((B,), T, dtype=torch.int64, device=self.device)
+        lens = lens.to(device=self.device, dtype=torch.int64).contiguous()
+        out = torch.empty(B, 1026, T, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            nb = self.lib.ttsamd_vocos_workspace_bytes(self.handle, B, T)
+            ws = self.ws.get(nb, self.device)
+            L.check(self.lib.ttsamd_vocos_features(self.handle, _ptr(mel), _ptr(lens), B, T, _ptr(out), _ptr(ws), nb, _stream()),
+                    'vocos_features')
+        return out
+
+    def head(self, feats, lens=None, denoise=0.0, bias_vec=None):
+        """feats [B, 1026, T] (log-magnitude | phase), lens int64 [B] or None -> wave [B, 256 T] ("same") or [B, 256 (T - 1)] ("center"),
+        zeros past a row's end: the ISTFT head of forward() alone.  `denoise`: a scalar or B values; `bias_vec` [513]: the engine's own
+        when None."""
+        feats = _f32(feats, self.device)
+        B, C2, T = feats.shape
+        assert C2 == 1026 and B >= 1
+        rows = None
+        if per_row(denoise):
+            vals = row_values(denoise, B, 'denoise')
+            check_finite(vals, 'denoise')
+            rows = _rows_f32(vals, self.device)
+        elif denoise != 0:
+            check_finite([float(denoise)], 'denoise')
+            rows = _rows_f32([float(denoise)] * B, self.device)
+        if lens is None:
+            lens = torch.full((B,), T, dtype=torch.int64, device=self.device)
+        lens = lens.to(device=self.device, dtype=torch.int64).contiguous()
+        n0 = self.hop * (T - 1) if self.center else self.hop * T
+        if T == 0 or n0 == 0:
+            return torch.zeros(B, 0, dtype=torch.float32, device=self.device)
+        wave = torch.zeros(B, self.hop * T, dtype=torch.float32, device=self.device)
+        bias = None
+        if rows is not None:
+            bias = (self.bias_vec() if bias_vec is None else _f32(bias_vec, self.device)).reshape(-1)
+            assert bias.numel() == 513
+        with torch.cuda.device(self.device):
+            nb = self.lib.ttsamd_vocos_workspace_bytes(self.handle, B, T)
+            ws = self.ws.get(nb, self.device)
+            L.check(self.lib.ttsamd_vocos_head(self.handle, _ptr(feats), _ptr(lens), B, T, _ptr(rows), _ptr(bias), _ptr(wave), _ptr(ws),
+                                               nb, _stream()), 'vocos_head')
+        return wave if wave.shape[1] == n0 else wave[:, :n0]
+
 
 class Tacotron2Engine:
     """Handle over ttsamd_tacotron2_* (replaces Tacotron2MS.infer, models/tacotron2/tacotron2_ms.py:279-332)."""

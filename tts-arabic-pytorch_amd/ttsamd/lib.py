@@ -113,6 +113,10 @@ SYMBOLS = {
     'ttsamd_vocos_forward': (_I32, [_P, _P, _P, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
     'ttsamd_vocos_forward_rows': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_vocos_set_padding': (_I32, [_P, _I32]),
+    # backbone and head apart (csrc/vocos.hip): handle, mel, lens, B, T, out [B][1026][T], ws, ws_bytes, stream /
+    # handle, feats, lens, B, T, denoise_rows or NULL, bias_vec, wave, ws, ws_bytes, stream
+    'ttsamd_vocos_features': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _I64, _P]),
+    'ttsamd_vocos_head': (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     'ttsamd_melspec_create': (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _F, C.POINTER(_P)]),
     'ttsamd_melspec_destroy': (_I32, [_P]),
     'ttsamd_melspec_forward': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P]),
