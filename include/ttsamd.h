@@ -650,7 +650,7 @@ int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, 
                              void* stream);
 /* What the calling thread's last fp32 conv launch decided (ttsamd_conv1d*, ttsamd_conv_transpose1d, or the last conv of a model forward
  * on this thread): *route = 0 direct kernel, 1 / 2 the two Winograd F(2,3) kernels, 3 / 4 Winograd F(4,3) on six- / seven-point groups,
- * 5 the all-phase transposed conv; *ksplit = its input-channel slices (1 = not split).  -1 / 0 before the first launch.  Host state of
+ * 5 the all-phase transposed conv, 6 the transposed conv as a two-tap conv on Winograd F(4,2); *ksplit = its input-channel slices (1 = not split).  -1 / 0 before the first launch.  Host state of
  * the thread only: nothing is read from the device.  The bf16 engines and the fused ResBlock launches do not record. */
 int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit);
 /* One HiFi-GAN upsampler (vocoder/hifigan/models.py:96-99, 114-115) as the generator runs it: y = conv_transpose1d(lrelu_slope(x), w,
@@ -659,8 +659,17 @@ int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit);
  * inputs and writes lens[b] * u outputs; y past them is left untouched (both kernels, as for ttsamd_conv1d; the generator's next layers
  * never read there).  The all-phase kernel (csrc/convt_mfma.hip; route 5) takes u = 2 / 8 with 16-byte aligned rows of y and, at u = 8,
  * at least 100 blocks; everything else, and everything under TTSAMD_CONVT=0, is the direct kernel's polyphase launch (route 0).
+ * In fp32, u = 2 / 8 with Cin a multiple of 16, u Cout a multiple of 64 and 16-byte aligned rows of x and y can also run as a two-tap
+ * conv with u Cout rows on Winograd F(4,2) (csrc/conv_wino4.hip; route 6): TTSAMD_CONVT_WINO=2 wherever that holds, =1 / unset only
+ * the (Cin, u) classes and sizes the generator routes there by default (batch x lin >= 8192), =0 never.
  * `packed`: ttsamd_convt_packed_floats(Cin, Cout, u) floats of scratch for the re-laid-out weights. */
 int64_t ttsamd_convt_packed_floats(int32_t cin, int32_t cout, int32_t u);
+/* HOST: the weights of that F(4,2) launch as the generator keeps them -- w [Cin][Cout][2u] (torch layout, host), bias [Cout] or NULL ->
+ * out[0 .. 6 Cin u Cout): the group filters U0..U4 and a zero group of the taps (w[..][j + u], w[..][j], 0), row = co u + j, as
+ * [Cin/8][6][2][u Cout][4]; behind them u Cout floats: the bias per row.  ttsamd_convt_wino_packed_floats = (6 Cin + 1) u Cout, 0 for a
+ * shape the launch does not take (then ttsamd_convt_wino_pack_weight is TTSAMD_EINVAL).  No GPU needed. */
+int64_t ttsamd_convt_wino_packed_floats(int32_t cin, int32_t cout, int32_t u);
+int32_t ttsamd_convt_wino_pack_weight(const float* w, const float* bias, int32_t cin, int32_t cout, int32_t u, float* out);
 int32_t ttsamd_conv_transpose1d(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t batch, int32_t cin,
                                 int32_t cout, int32_t u, int32_t lin, float in_slope, float* y, float* packed, void* stream);
 

@@ -205,6 +205,33 @@ __global__ void pack_convt_weight_kernel(const float* __restrict__ w, int cin, i
     out[i] = co < cout ? w[((int64_t)(8 * o + 2 * pq + kk) * cout + co) * (2 * u) + kidx] : 0.f;
 }
 
+// torch ConvTranspose1d weight [cin][cout][2u] -> the F(4,2) group filters of the (u cout)-row two-tap conv [cin/8][6][2][u cout][4], row =
+// co u + j, taps (g0, g1) = (w[..][j + u], w[..][j]); the u cout floats behind them: the bias per row (same values as pack_convt_wino_weight,
+// conv_wino4.hip)
+__global__ void pack_convt_wino_kernel(const float* __restrict__ w, const float* __restrict__ bias, int cin, int cout, int u,
+                                       float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int rows = u * cout;
+    const int64_t n = (int64_t)6 * cin * rows;
+    if (i >= n + rows) return;
+    if (i >= n) {
+        out[i] = bias ? bias[(i - n) / u] : 0.f;
+        return;
+    }
+    const int pq = (int)(i & 3);
+    const int64_t r = i >> 2;
+    const int row = (int)(r % rows);
+    const int64_t r2 = r / rows;
+    const int kk = (int)(r2 & 1);
+    const int64_t r3 = r2 >> 1;
+    const int t = (int)(r3 % 6), o = (int)(r3 / 6);
+    const int co = row / u, j = row % u;
+    const float* g = w + ((int64_t)(8 * o + 2 * pq + kk) * cout + co) * 2 * u;
+    const double g0 = g[j + u], g1 = g[j];
+    out[i] = t == 0 ? (float)(g0 / 4) : (t == 1 ? (float)(-(g0 + g1) / 6) : (t == 2 ? (float)(-(g0 - g1) / 6) :
+             (t == 3 ? (float)(g0 / 24 + g1 / 12) : (t == 4 ? (float)(g0 / 24 - g1 / 12) : 0.f))));
+}
+
 __global__ void split_bf16_kernel(const float* __restrict__ packed, int64_t n, unsigned short* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -892,8 +919,21 @@ int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit) {
 
 int64_t ttsamd_convt_packed_floats(int32_t cin, int32_t cout, int32_t u) {
     // the u polyphase 2-tap filters in fp32 + their bf16 hi / lo planes
+    // ... and, where the F(4,2) launch exists (convt_wino_packable), its six group filters per tap pair and the bias per row
     if (cin < 1 || cout < 1 || u < 1) return 0;
-    return 2 * (int64_t)u * cin * 2 * cout_padded(cout);
+    return 2 * (int64_t)u * cin * 2 * cout_padded(cout) + (convt_wino_packable(cin, cout, u) ? (int64_t)(6 * cin + 1) * u * cout : 0);
+}
+
+int64_t ttsamd_convt_wino_packed_floats(int32_t cin, int32_t cout, int32_t u) {
+    return convt_wino_packable(cin, cout, u) ? (int64_t)(6 * cin + 1) * u * cout : 0;
+}
+
+int32_t ttsamd_convt_wino_pack_weight(const float* w, const float* bias, int32_t cin, int32_t cout, int32_t u, float* out) {
+    TTS_REQUIRE(w && out, "convt_wino_pack_weight: null argument");
+    TTS_REQUIRE(convt_wino_packable(cin, cout, u), "convt_wino_pack_weight: cin %d (a multiple of 16), cout %d, u %d (2 / 8, u cout a multiple of 64)",
+                cin, cout, u);
+    pack_convt_wino_weight(w, bias, cin, cout, u, out, out + (int64_t)6 * cin * u * cout);
+    return 0;
 }
 
 int32_t ttsamd_conv_transpose1d(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t batch, int32_t cin,
@@ -914,12 +954,20 @@ int32_t ttsamd_conv_transpose1d(const float* x, const float* w, const float* bia
         hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, packed, n, planes);
         TTS_CHECK_HIP(hipGetLastError());
     }
+    float* wino = nullptr;
+    if (default_precision() == 0 && convt_wino_packable(cin, cout, u) && opt_int(OPT_CONVT_WINO, 1) != 0) {
+        wino = packed + 2 * n;
+        const int64_t nw = (int64_t)(6 * cin + 1) * u * cout;
+        hipLaunchKernelGGL(pack_convt_wino_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, bias, cin, cout, u, wino);
+        TTS_CHECK_HIP(hipGetLastError());
+    }
     ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.batch = batch;
     p.lens_in = lens; p.lens_out = lens;
     prof_begin(s, 2.0 * cout * cin * 2 * u);
-    const int32_t rc = launch_upsampler(p, x, packed, planes, bias, y, cin, cout, u, 2 * u, lin, 1, in_slope, opt_int(OPT_CONVT, 1) != 0, s);
+    const int32_t rc = launch_upsampler(p, x, packed, planes, bias, y, cin, cout, u, 2 * u, lin, 1, in_slope, opt_int(OPT_CONVT, 1) != 0, s, wino,
+                                        wino ? wino + (int64_t)6 * cin * u * cout : nullptr);
     prof_end(s);
     return rc;
 }

@@ -71,6 +71,7 @@ inline hipError_t lds_opt_in(const void* fn, int bytes, std::atomic<uint64_t>& d
     X(FUSED2_WB, 0, 0, 2)         /* its Winograd phases: 0 none, 1 phase B, 2 both (default) */            \
     X(PAIR4, 0, 0, 1)             /* C = 32 fused pairs with both convs on Winograd F(4,3) (resblock_pair4) off / on */ \
     X(CONVT, 0, 0, 1)             /* all-phase transposed conv (convt_mfma.hip) off / on */                 \
+    X(CONVT_WINO, 0, 0, 2)        /* fp32 upsamplers on Winograd F(4,2) (conv_wino4.hip): 0 off, 1 default routing, 2 wherever supported */ \
     X(BFO, 0, 0, 1)               /* bf16 modes: 0 = the round-2 bf16 conv engine instead of the octet engine */ \
     X(BFO_CHAIN, 0, 0, 1)         /* whole k = 3 ResBlock in one launch (octet engines) */                  \
     X(BFO_CHAIN7, 0, 0, 1)        /* ... and k = 7 (default: small batches only) */                         \
@@ -175,7 +176,8 @@ bool compact_order(const void* lens, int batch);
 int32_t launch_conv(const ConvParams& p, hipStream_t stream);
 // What the calling thread's last fp32 conv launch decided (ttsamd_conv_last_launch; conv_mfma.hip): two thread_local ints, written by
 // the launcher that takes the decision.  route 0: direct kernel, 1 / 2: the F(2,3) kernels (conv_wino.hip / conv_wino2.hip), 3 / 4: F(4,3)
-// on six- / seven-point groups, 5: the all-phase transposed conv (convt_mfma.hip).  Host only, no atomics.
+// on six- / seven-point groups, 5: the all-phase transposed conv (convt_mfma.hip), 6: the transposed conv as a two-tap conv on F(4,2)
+// (launch_convt_wino, conv_wino4.hip).  Host only, no atomics.
 void note_conv_launch(int32_t route, int32_t ksplit);
 void last_conv_launch(int32_t* route, int32_t* ksplit);
 // ConvTranspose1d with all output phases per wave (convt_mfma.hip): takes the polyphase ConvParams of the generic engine
@@ -185,8 +187,20 @@ int32_t launch_convt(const ConvParams& p, hipStream_t stream);
 // (the caller has set batch, lens_in / lens_out and whatever it shares between its launches) and launches the all-phase kernel where
 // `convt_ok` and convt_supported(p) say so, else the generic engine.  x [B][cin][L], y [B][cout][L * u], w / w_bf16 packed by
 // pack_convt_weight (and split_packed_bf16); valid lengths lens * len_mul in, lens * len_mul * u out.
+// w_wino / bias_wino: the same upsampler packed by pack_convt_wino_weight (nullptr = not packed: never routed to the F(4,2) launch).
 int32_t launch_upsampler(ConvParams& p, const float* x, const float* w, const void* w_bf16, const float* bias, float* y, int cin, int cout,
-                         int u, int kt, int L, int len_mul, float in_slope, bool convt_ok, hipStream_t stream);
+                         int u, int kt, int L, int len_mul, float in_slope, bool convt_ok, hipStream_t stream, const float* w_wino = nullptr,
+                         const float* bias_wino = nullptr);
+// ConvTranspose1d(stride u, kernel 2u, padding u/2) as a two-tap Conv1d with u Cout rows on the F(4,3) kernel's k = 3 form with a zero
+// third tap = F(4,2), five products per output quad and phase instead of eight (conv_wino4.hip: launch_convt_wino; route 6).
+// convt_wino_packable: the shapes the packing exists for (u = 2 / 8, Cin % 16 == 0, u Cout % 64 == 0).  pack_convt_wino_weight: torch
+// [Cin][Cout][2u] -> the group filters U0..U4 + a zero group of the taps (W[..][j + u], W[..][j], 0), row = co u + j, in the layout
+// [Cin/8][6][2][u Cout][4] (6 cin u cout floats), and the bias per ROW (bias[row / u]; u cout floats, zeros without a bias).
+// convt_wino_supported takes the polyphase ConvParams that launch_upsampler fills.
+bool convt_wino_packable(int cin, int cout, int u);
+void pack_convt_wino_weight(const float* w, const float* bias, int cin, int cout, int u, float* out_w, float* out_bias);
+bool convt_wino_supported(const ConvParams& p, const float* w_wino, const float* bias_wino);
+int32_t launch_convt_wino(const ConvParams& p, const float* w_wino, const float* bias_wino, hipStream_t stream);
 // One launch for a c1 -> c2 pair of a C = 32 ResBlock1 with the intermediate in LDS (resblock_fused.hip); x != y.
 bool fused_pair_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
 int32_t launch_fused_pair(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
@@ -262,13 +276,22 @@ int32_t default_precision();
 // cycles next to the length load the kernel does anyway.  Returns false past the last live pair.
 // (A persistent variant -- as many blocks as the chip holds, tiles handed out by a device counter -- measured 1-3 %
 // BELOW this on the ragged launches and 3-4 % below the plain grid on uniform ones; not kept.)
+// EXTRA = 1 (the transposed conv on the F(4,2) kernel, conv_wino4.hip): a row of length len > 0 has len + 1 positions, one of length 0 none.
+template <int EXTRA = 0>
 __device__ __forceinline__ bool live_tile(const int64_t* __restrict__ lens, const int mul, const int n_max, const int tile_w,
                                           const int batch, const unsigned lin, int& b, int& tile) {
     const int lane = threadIdx.x & 63;
     unsigned base = 0;
     for (int u0 = 0; u0 < batch; u0 += 64) {
         int n = 0;
-        if (u0 + lane < batch) n = (max(min(n_max, (int)lens[u0 + lane] * mul), 0) + tile_w - 1) / tile_w;
+        if constexpr (EXTRA != 0) {
+            if (u0 + lane < batch) {
+                const int len = (int)lens[u0 + lane] * mul;
+                n = (max(min(n_max, len > 0 ? len + EXTRA : 0), 0) + tile_w - 1) / tile_w;
+            }
+        } else {
+            if (u0 + lane < batch) n = (max(min(n_max, (int)lens[u0 + lane] * mul), 0) + tile_w - 1) / tile_w;
+        }
         int incl = n;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {

@@ -11,6 +11,13 @@
 // matrix pipe.  Here a wave keeps u accumulators per (co-tile, q-tile), one per phase: the phases share the staged input
 // (two column shifts, d = 0 / 1) and differ only in the A operand, and in the C layout lane q then owns the u consecutive
 // outputs y[co][q*u .. q*u+u) of every row: u = 8 -> two float4 stores per row, u = 2 -> one float2, full lines either way.
+//
+// This kernel multiplies every product: 2 taps x Cin per output, and its launches are bound by the matrix pipe (73-83 % busy at batch 32).
+// Since round 27 the large fp32 launches of the generator leave it for the F(4,3) kernel: shifted by u/2 the phases take the SAME two
+// input positions, so the transposed conv is a two-tap Conv1d with u Cout rows, i.e. the k = 3 six-point form with a zero third tap --
+// F(4,2), five products per output quad and phase instead of eight (conv_wino4.hip: launch_convt_wino, route 6).  launch_upsampler below
+// chooses per launch (TTSAMD_CONVT_WINO); this kernel keeps u = 2 / 8 launches under 8192 input positions (the streaming vocoder's windows,
+// small batches), Cin not a multiple of 16, rows that are not 16-byte aligned in x, and everything TTSAMD_CONVT_WINO=0 sends back.
 #include <cstring>
 
 #include <cstdlib>
@@ -241,8 +248,20 @@ int32_t launch_convt(const ConvParams& p, hipStream_t stream) {
 
 // leaky_relu + ConvTranspose1d as u polyphase 2-tap convs (vocoder/hifigan/models.py:114-115): the one place that fills the polyphase
 // ConvParams and chooses between the two launches -- the model (hifigan.hip) and the kernel-level entry (ttsamd_conv_transpose1d)
+// TTSAMD_CONVT_WINO (read per launch): 0 = never, 2 = every launch convt_wino_supported takes (tests, A/B), 1 / unset = the default
+// routing of convt_wino_default below.  TTSAMD_CONVT=0 forces the direct kernel whatever it says.
+// Default: the four (Cin, u) classes of the V1 generator, each measured faster at batch 32 (profiles/r27/NOTES.md), from 8192 input positions
+// (batch x L) upwards -- under that the 64-row x 256-position blocks do not fill the chip (4 x 2048 positions at Cin 128, u = 2: 80 blocks);
+// other classes (the V3 generator's Cin 128, u = 8) have not been measured and stay.
+constexpr int64_t kConvtWinoMinPositions = 8192;
+static bool convt_wino_default(int cin, int u, int64_t positions) {
+    if (positions < kConvtWinoMinPositions) return false;
+    return (u == 8 && (cin == 512 || cin == 256)) || (u == 2 && (cin == 128 || cin == 64));
+}
+
 int32_t launch_upsampler(ConvParams& p, const float* x, const float* w, const void* w_bf16, const float* bias, float* y, int cin, int cout,
-                         int u, int kt, int L, int len_mul, float in_slope, bool convt_ok, hipStream_t stream) {
+                         int u, int kt, int L, int len_mul, float in_slope, bool convt_ok, hipStream_t stream, const float* w_wino,
+                         const float* bias_wino) {
     p.x = x; p.x_bs = (int64_t)cin * L; p.x_cs = L;
     p.w = w; p.bias = bias;
     p.w_bf16 = w_bf16; p.precision = default_precision(); p.w_wino = nullptr; p.w_wino4 = nullptr; p.w_wino44 = nullptr;
@@ -253,6 +272,10 @@ int32_t launch_upsampler(ConvParams& p, const float* x, const float* w, const vo
     p.dil = -1; p.pad = 0; p.n_phase = u; p.phase_p = (kt - u) / 2;
     p.in_slope = in_slope; p.relu_out = 0; p.mode = 0; p.div = 1.f;
     p.x_packed = 0; p.y_packed = 0;
+    const int64_t wino = opt_int(OPT_CONVT_WINO, 1);
+    if (convt_ok && wino != 0 && kt == 2 * u && convt_wino_supported(p, w_wino, bias_wino) &&
+        (wino == 2 || convt_wino_default(cin, u, (int64_t)p.batch * L)))
+        return launch_convt_wino(p, w_wino, bias_wino, stream);
     return (convt_ok && convt_supported(p)) ? launch_convt(p, stream) : launch_conv(p, stream);
 }
 

@@ -54,6 +54,7 @@ struct ConvW {
     BfoWeightOffs wo;              // bf16 octet engine (bfo.hpp), per mode: [Cin/16][K][2][CoutP][8] / [..][hi 8 | lo 8] in the same uint16 blob
     int64_t ww44_off = -1;         // ... k = 7 / 11, Cout >= 64: and as seven-point groups (conv_wino4.hip, TTSAMD_WINO4 bits 5 / 6 pick the form per launch)
     int64_t ww4_off = -1;          // ... and as Winograd F(4,3) groups (conv_wino4.hip: the un-fused convs, Cout >= 64; resblock_pair4.hip: the C = 32 pairs)
+    int64_t wct_off = -1, bct_off = -1;   // upsamplers: the F(4,2) group filters of the (u Cout)-row two-tap conv and its per-row bias (pack_convt_wino_weight; -1: none)
     int64_t ww_off = -1;           // k = 3 / 7 / 11: Winograd F(2,3) (sub-)filters + single taps as an NG-tap conv in the fp32 blob (conv_wino2.hip; -1: none)
     int cin = 0, cout = 0, k = 0;
 };
@@ -305,6 +306,14 @@ int32_t hifigan_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_hif
         blob.resize(align_up((int64_t)blob.size(), 64));
         rc = get_bias(tm, "ups." + std::to_string(i), cout, blob, cw.b_off);
         if (rc) break;
+        if (convt_wino_packable(cin, cout, u)) {   // the same upsampler for the F(4,2) launch (conv_wino4.hip); the routing switch is read per launch
+            cw.wct_off = (int64_t)blob.size();
+            blob.resize(blob.size() + (size_t)6 * cin * u * cout);
+            cw.bct_off = (int64_t)blob.size();
+            blob.resize(align_up((int64_t)blob.size() + (int64_t)u * cout, 64));
+            // (blob may have been reallocated: take the bias pointer after the resize)
+            pack_convt_wino_weight(w.data(), blob.data() + cw.b_off, cin, cout, u, blob.data() + cw.wct_off, blob.data() + cw.bct_off);
+        }
         h->ups.push_back(cw);
         ch = cout;
         mul *= u;
@@ -654,7 +663,8 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
         // leaky_relu(0.1) + ConvTranspose1d as u polyphase 2-tap convs (models.py:114-115)
         prof_begin(s, 2.0 * uw.cout * uw.cin * 2 * u * mul);
         int32_t rc = launch_upsampler(p, cur, h->dev + uw.w_off, h->dev16 + uw.w16_off, h->dev + uw.b_off, ups_out, uw.cin, uw.cout, u, kt, L,
-                                      mul, 0.1f, convt_ok, s);
+                                      mul, 0.1f, convt_ok, s, uw.wct_off >= 0 ? h->dev + uw.wct_off : nullptr,
+                                      uw.bct_off >= 0 ? h->dev + uw.bct_off : nullptr);
         prof_end(s);
         HG_TRY(rc);
         L *= u; mul *= u;

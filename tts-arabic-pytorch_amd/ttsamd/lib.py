@@ -176,6 +176,8 @@ SYMBOLS = {
     'ttsamd_conv_last_launch': (_I32, [C.POINTER(_I32), C.POINTER(_I32)]),
     'ttsamd_convt_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_conv_transpose1d': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
+    'ttsamd_convt_wino_packed_floats': (_I64, [_I32, _I32, _I32]),
+    'ttsamd_convt_wino_pack_weight': (_I32, [_P, _P, _I32, _I32, _I32, _P]),
     'ttsamd_resblock_pair_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
     'ttsamd_resblock2_packed_floats': (_I64, [_I32, _I32, _I32]),
