@@ -680,8 +680,9 @@ int32_t ttsamd_conv_transpose1d(const float* x, const float* w, const float* bia
  * k = 3), 2 / 3: second generation (weights from L2 into a register queue, raw window; 256- / 128-column blocks; C = 32 / 64 /
  * 128, k = 3 / 7 / 11), 4 / 5: 256-column blocks with conv 2 (4) or both convs (5) on Winograd F(2,3) (C = 32 / 64, k = 3 / 7 / 11;
  * 5 also C = 128), 6: C = 32 with both convs on Winograd F(4,3) (512-column blocks, k = 3 / 7 / 11, dilation 1 / 3 / 5; L a multiple
- * of 4).  `packed` is scratch for the re-laid-out weights: ttsamd_resblock_pair_packed_floats(C, K, variant) floats (the two
- * direct packings, + the Winograd group filters of variants 4 / 5 / 6); `packed_floats` = what the caller allocated, a smaller buffer is
+ * of 4), 7: the same launch with both convs on its seven-point groups (13 / 20 products per output quad; C = 32, k = 7 / 11 only).
+ * `packed` is scratch for the re-laid-out weights: ttsamd_resblock_pair_packed_floats(C, K, variant) floats (the two
+ * direct packings, + the Winograd group filters of variants 4 / 5 / 6 / 7); `packed_floats` = what the caller allocated, a smaller buffer is
  * TTSAMD_EINVAL (nothing is written). */
 int64_t ttsamd_resblock_pair_packed_floats(int32_t channels, int32_t k, int32_t variant);
 int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const float* b1, const float* w2, const float* b2,

@@ -978,6 +978,7 @@ int64_t ttsamd_resblock_pair_packed_floats(int32_t channels, int32_t k, int32_t 
     const int64_t n = 2 * (int64_t)channels * k * channels;
     const int nwino = (variant == 4 ? 1 : (variant == 5 ? 2 : 0));
     if (variant == 6) return n + ((k == 3 || k == 7 || k == 11) ? 2 * (int64_t)channels * wino4_groups(k) * channels : 0);   // both convs as F(4,3) groups
+    if (variant == 7) return n + 2 * (int64_t)channels * wino44_groups(k) * channels;                                         // ... as seven-point groups
     return n + ((k == 3 || k == 7 || k == 11) ? nwino * (int64_t)channels * wino2_groups(k) * channels : 0);
 }
 
@@ -1029,10 +1030,21 @@ int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const fl
         }
         rc = launch_fused_pair4(channels, x, y, packed + 2 * n, b1, packed + 2 * n + nw4, b2, k, dil, lens, len_mul, L, batch, mode, div,
                                 slope, s);
+    } else if (variant == 7) {
+        // ... both convs on seven-point groups (13 / 20 products per quad)
+        TTS_REQUIRE(channels == 32 && (k == 7 || k == 11), "resblock_pair: variant 7 is built for C = 32, k = 7 / 11");
+        const int64_t nw44 = (int64_t)channels * wino44_groups(k) * channels;
+        for (int i = 0; i < 2; ++i) {
+            hipLaunchKernelGGL(pack_wino44_weight_kernel, dim3((unsigned)((nw44 + 255) / 256)), dim3(256), 0, s, i == 0 ? w1 : w2, channels,
+                               channels, k, channels, packed + 2 * n + i * nw44);
+            TTS_CHECK_HIP(hipGetLastError());
+        }
+        rc = launch_fused_pair4(channels, x, y, packed + 2 * n, b1, packed + 2 * n + nw44, b2, k, dil, lens, len_mul, L, batch, mode, div,
+                                slope, s, 7);
     } else if (variant == -1) {
         rc = 0;                                    // the two weight re-layout launches only (tools/fused_pair_bench.py subtracts them)
     } else {
-        set_error("resblock_pair: variant %d (1: first generation, 2 / 3: second generation with 256- / 128-column blocks, 4 / 5: 256 columns + Winograd phase B / both phases, 6: C = 32 with both phases on Winograd F(4,3))", variant);
+        set_error("resblock_pair: variant %d (1: first generation, 2 / 3: second generation with 256- / 128-column blocks, 4 / 5: 256 columns + Winograd phase B / both phases, 6: C = 32 with both phases on Winograd F(4,3), 7: ... on its seven-point groups, k = 7 / 11)", variant);
         rc = TTSAMD_EINVAL;
     }
     prof_end(s);

@@ -69,7 +69,7 @@ inline hipError_t lds_opt_in(const void* fn, int bytes, std::atomic<uint64_t>& d
     X(FUSED2_MASK, 1, 0, 0x1ff)   /* which (C, k) pairs it takes: bit 3 ci + ki (default 00f) */            \
     X(FUSED2_MASK_N1, 1, 0, 0x1ff) /* ... with 128-column direct-arithmetic blocks (default 000) */         \
     X(FUSED2_WB, 0, 0, 2)         /* its Winograd phases: 0 none, 1 phase B, 2 both (default) */            \
-    X(PAIR4, 0, 0, 1)             /* C = 32 fused pairs with both convs on Winograd F(4,3) (resblock_pair4) off / on */ \
+    X(PAIR4, 0, 0, 2)             /* C = 32 fused pairs with both convs on Winograd F(4,3) (resblock_pair4): 0 off, 1 on (seven-point groups where routed), 2 on six-point groups */ \
     X(CONVT, 0, 0, 1)             /* all-phase transposed conv (convt_mfma.hip) off / on */                 \
     X(CONVT_WINO, 0, 0, 2)        /* fp32 upsamplers on Winograd F(4,2) (conv_wino4.hip): 0 off, 1 default routing, 2 wherever supported */ \
     X(BFO, 0, 0, 1)               /* bf16 modes: 0 = the round-2 bf16 conv engine instead of the octet engine */ \
@@ -216,11 +216,12 @@ int32_t launch_fused_pair2(int32_t channels, const float* x, float* y, const flo
 // (w2_wino: conv 2 as Winograd F(2,3) groups -- pack_wino2_weight; C = 32 / 64, ntw = 2: phase B of the pair runs on them; w1_wino:
 // conv 1 likewise -> phase A too)
 // The C = 32 pair with both convs on Winograd F(4,3) (resblock_pair4.hip): k = 3 / 7 / 11, dilation 1 / 3 / 5; the weights are the
-// F(4,3) group filters of both convs (pack_wino4_weight)
+// F(4,3) group filters of both convs (points = 6: pack_wino4_weight; points = 7, k = 7 / 11 only: the seven-point groups of
+// pack_wino44_weight at 32 x 32, [4][wino44_groups(k)][2][32][4])
 bool fused_pair4_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
 int32_t launch_fused_pair4(int32_t channels, const float* x, float* y, const float* w1_wino4, const float* b1, const float* w2_wino4,
                            const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                           int32_t mode, float div, float slope, hipStream_t stream);
+                           int32_t mode, float div, float slope, hipStream_t stream, int32_t points = 6);
 // HiFi-GAN ResBlock2 (resblock2.hip), exact fp32: one conv y = x + conv(lrelu(x), w, dil) + b with the stage-sum epilogue (C = 32 / 64 /
 // 128, k = 3 / 5 / 7 / 11, dilation 1..16), and both convs of a ResBlock2 in one launch (C = 32 / 64).  Direct weight packing
 // (pack_conv_weight); x != y.

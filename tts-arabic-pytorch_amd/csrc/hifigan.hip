@@ -25,10 +25,14 @@ constexpr unsigned kFused2Mask = 0x00F;       // C = 32: k = 3 / 7 / 11; C = 64:
                                               // 62.45; C = 128 k = 3 fused 63.90 vs 64.06
 // Of those, the C = 32 k = 7 / 11 pairs run with both convs on Winograd F(4,3) (resblock_pair4.hip: 16 / 23 products per output quad
 // against 20 / 32 on F(2,3)) when the pair takes the 256-column kernel with both phases on Winograd; TTSAMD_PAIR4=0 keeps resblock_pair2.
+// Since round 28 the launch runs on SEVEN-point groups (13 / 20 products per quad, the arithmetic of the un-fused k = 7 / 11 convs) at
+// the k of kPair44Mask (bit 0: k = 7, bit 1: k = 11; both: 749 / 712 / 707 -> 665 / 629 / 630 us and 972 / 920 / 894 -> 905 / 869 / 842 us
+// per launch at batch 32, step 47.74 -> 47.15 ms, profiles/r28/NOTES.md); TTSAMD_PAIR4=2 keeps every pair on the six-point groups.
 // One-stream kernel table at batch 32 (profiles/r7/NOTES.md): k = 11 3.61 -> 2.75 ms per step, k = 7 2.43 -> 2.12, but k = 3 1.22 -> 1.32
 // (memory-bound: 6 products per quad do not pay for the larger window and the extra LDS traffic), so k = 3 stays on resblock_pair2.
 // C = 64 k = 3 stays there too (resblock_pair4 is built for C = 32 only: MT = 1, one 32-row tile per wave).
 constexpr int kPair4MinK = 7;
+constexpr unsigned kPair44Mask = 0x3;
 constexpr unsigned kFused2MaskN1 = 0x000;     // 128-column blocks (the direct-arithmetic kernels only): none by default
 constexpr int64_t kFused2SmallColumns = 2 * 256 * 252;   // batch x positions under which a stage counts as a small problem
 
@@ -52,7 +56,8 @@ struct ConvW {
     int64_t w_off = 0, b_off = 0;  // float offsets into the device weight blob
     int64_t w16_off = 0, w_n = 0;  // bf16 planes (hi, lo) in the uint16 blob; packed element count
     BfoWeightOffs wo;              // bf16 octet engine (bfo.hpp), per mode: [Cin/16][K][2][CoutP][8] / [..][hi 8 | lo 8] in the same uint16 blob
-    int64_t ww44_off = -1;         // ... k = 7 / 11, Cout >= 64: and as seven-point groups (conv_wino4.hip, TTSAMD_WINO4 bits 5 / 6 pick the form per launch)
+    int64_t ww44_off = -1;         // ... k = 7 / 11, Cout >= 64: and as seven-point groups (conv_wino4.hip, TTSAMD_WINO4 bits 5 / 6 pick the form per launch);
+                                   // C = 32: the routed fused pairs' seven-point groups (resblock_pair4.hip, TTSAMD_PAIR4)
     int64_t ww4_off = -1;          // ... and as Winograd F(4,3) groups (conv_wino4.hip: the un-fused convs, Cout >= 64; resblock_pair4.hip: the C = 32 pairs)
     int64_t wct_off = -1, bct_off = -1;   // upsamplers: the F(4,2) group filters of the (u Cout)-row two-tap conv and its per-row bias (pack_convt_wino_weight; -1: none)
     int64_t ww_off = -1;           // k = 3 / 7 / 11: Winograd F(2,3) (sub-)filters + single taps as an NG-tap conv in the fp32 blob (conv_wino2.hip; -1: none)
@@ -110,6 +115,7 @@ struct Fused2Switches {
     bool on = true, mask_forced = false;
     bool wino_b = true, wino_a = true;   // phase B / phase A + B of the C = 32 / 64 pairs as Winograd F(2,3) (TTSAMD_FUSED2_WB=0: both direct, =1: phase B only)
     bool pair4 = true;                   // ... the C = 32 ones with both phases on Winograd as F(4,3) instead (TTSAMD_PAIR4=0: resblock_pair2)
+    bool pair44 = true;                  // ... on seven-point groups at the k of kPair44Mask (TTSAMD_PAIR4=2: six-point groups at every k)
     unsigned mask = kFused2Mask, mask_n1 = kFused2MaskN1;
 };
 static Fused2Switches read_fused2_switches() {
@@ -122,7 +128,9 @@ static Fused2Switches read_fused2_switches() {
     const int64_t wb = opt_int(OPT_FUSED2_WB, 2);
     sw.wino_b = wb != 0;
     sw.wino_a = wb == 2;
-    sw.pair4 = opt_int(OPT_PAIR4, 1) != 0;
+    const int64_t p4 = opt_int(OPT_PAIR4, 1);
+    sw.pair4 = p4 != 0;
+    sw.pair44 = p4 == 1;
     return sw;
 }
 
@@ -242,7 +250,8 @@ static int32_t add_conv(const TensorMap& tm, const std::string& base, int cin, i
             blob.resize(blob.size() + (size_t)cin * wino4_groups(k) * cout_padded(cout));
             pack_wino4_weight(w.data(), cout, cin, k, blob.data() + cw.ww4_off);
         }
-        if (cout >= 64 && wino44_groups(k) != 0) {   // both forms are kept: the routing switch is read per launch
+        // both forms are kept: the routing switch is read per launch (Cout >= 64) / per forward (the routed C = 32 pairs)
+        if ((cout >= 64 || (cout == 32 && cin == 32 && k >= kPair4MinK)) && wino44_groups(k) != 0) {
             blob.resize(align_up((int64_t)blob.size(), 64));
             cw.ww44_off = (int64_t)blob.size();
             blob.resize(blob.size() + (size_t)cin * wino44_groups(k) * cout_padded(cout));
@@ -506,7 +515,7 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
         p.w_bf16 = h->dev16 + cw.w16_off; p.precision = default_precision();
         p.w_wino = cw.ww_off >= 0 ? h->dev + cw.ww_off : nullptr;
         p.w_wino4 = (cw.ww4_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww4_off : nullptr;   // (C = 32: the fused pair's filters only)
-        p.w_wino44 = cw.ww44_off >= 0 ? h->dev + cw.ww44_off : nullptr;
+        p.w_wino44 = (cw.ww44_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww44_off : nullptr;   // (likewise: 32 rows are no launch of the 64-row kernel)
         p.y = y; p.y_bs = (int64_t)cw.cout * L; p.y_cs = L; p.y_ts = 1;
         p.res = res; p.r_bs = (int64_t)cw.cout * L; p.r_cs = L;
         p.len_in_mul = mul; p.len_out_mul = mul; p.Lin = L; p.Nout = L;
@@ -728,12 +737,17 @@ int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens,
                     // the F(2,3) pair with both phases on Winograd -> its F(4,3) successor where it is built (C = 32)
                     const bool f43 = ntw2 == 2 && f2sw.pair4 && f2sw.wino_a && w1.k >= kPair4MinK && w1.ww4_off >= 0 && w2.ww4_off >= 0 &&
                                      fused_pair4_supported(w1.cin, w1.k, d, L, src, dst);
+                    const bool f44 = f43 && f2sw.pair44 && (kPair44Mask & (w1.k == 7 ? 1u : (w1.k == 11 ? 2u : 0u))) != 0 &&
+                                     w1.ww44_off >= 0 && w2.ww44_off >= 0;
                     if (ntw2 != 0 || (fused_ok && square && fused_pair_supported(w1.cin, w1.k, d, L, src, dst))) {
                         const int mode = !last ? 0 : (cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2)));
                         if (multi && last && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
                         const double fl = 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * mul;
                         if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        const int32_t frc = f43
+                        const int32_t frc = f44
+                            ? launch_fused_pair4(w1.cin, src, dst, h->dev + w1.ww44_off, h->dev + w1.b_off, h->dev + w2.ww44_off,
+                                                 h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, st, 7)
+                            : f43
                             ? launch_fused_pair4(w1.cin, src, dst, h->dev + w1.ww4_off, h->dev + w1.b_off, h->dev + w2.ww4_off,
                                                  h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, st)
                             : ntw2 != 0
