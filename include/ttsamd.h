@@ -973,6 +973,58 @@ int32_t ttsamd_loudness_measure(const float* wave, int64_t wave_stride, const in
 int32_t ttsamd_wave_level(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
                           const float* target, float ceiling, const double* loudness, const float* peak, float* gain_out, void* stream);
 
+/* ---- wave-against-wave scores (csrc/wavescore.hip): STOI / ESTOI at 10 kHz, SI-SDR / SNR and a log-spectral distance between the rows
+ * of two ragged mono batches that are sample-aligned (copy synthesis, a precision mode against fp32, a delivery format against the float
+ * wave; free-running synthesis is NOT aligned with a recording and has no meaningful score here).  Both waves are [batch][wave_stride]
+ * fp32 and share nsamples: device int64 [batch], clamped to [0, wave_stride].  Nothing at or past nsamples[b] is read into a result and
+ * nothing is read back to the host.  All arithmetic after the fp32 samples are loaded is float64: window products, the transforms
+ * (radix-4 Stockham passes in LDS, with one radix-2 pass at 512 points; twiddles from a float64 table the block builds in LDS), powers, band sums and every statistic.  No
+ * floating-point atomics and a fixed order in every reduction, which depends on the row's own length only: row b of a batch has the
+ * bits of the call on row b alone, and two runs give the same bits.  1 <= batch <= 65535.
+ * The scores are specified by the arithmetic below; parity with a release of pystoi (or any other package) is not pinned.
+ *
+ * STOI / ESTOI.  x = ref[b][0:n] (the clean signal), y = deg[b][0:n], both ALREADY at 10 000 Hz (ttsamd.engine.WaveScoreEngine resamples
+ * with the project's own resampler, which is not pystoi's).  EPS = 2^-52, w = numpy.hanning(258)[1:-1] (256 points), hop 128, N = 30.
+ *  1. F = (n - 256) / 128 + 1 frames for n >= 256, else 0; xf[f] = w * x[128 f : 128 f + 256], yf likewise.
+ *  2. Silent frames go, decided on the clean signal: e[f] = 20 log10(sqrt(sum xf[f]^2) + EPS); frame f is kept when
+ *     max_f e - 40 - e[f] < 0.  K kept frames, in order; both signals are rebuilt by overlap-add of their kept frames at hop 128
+ *     (length 128 (K - 1) + 256; formed on the fly from the two kept frames that overlap a position).
+ *  3. The rebuilt signals are framed again with w at hop 128 (K frames), zero-padded to 512 and transformed; P[k] = |X[k]|^2,
+ *     tob[j] = sqrt(sum_{k = lo[j]}^{hi[j] - 1} P[k]) for the fifteen third-octave bands lo = 7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69,
+ *     87, 109, 138, 174 and hi = 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219 (the bins nearest to
+ *     150 * 2^((2 j -/+ 1) / 6) Hz on the grid k * 10000 / 512).
+ *  4. K < 30 (F = 0 included): score = 1e-5, the conventional "too short" value.
+ *  5. For m = 30 .. K the segment is X_m = tob_x[:, m - 30 : m] (15 x 30), Y_m likewise; M = K - 29 segments.
+ *  6. extended == 0 (STOI), per segment and band j: c = ||X_m[j]|| / (||Y_m[j]|| + EPS), Y' = min(c Y_m[j], X_m[j] (1 + 10^(15 / 20)));
+ *     both rows are centred over the 30 frames and divided by (norm + EPS); score = the sum over m, j and t of the products / (15 M).
+ *  7. extended != 0 (ESTOI), per segment: every row of X_m is centred over time and divided by (norm + EPS), then every column is
+ *     centred over the bands and divided by (norm + EPS); the same for Y_m; score = sum over m of sum(Xn * Yn) / 30 / M.
+ * An all-zero pair follows the arithmetic as written (every frame is kept, the score is 0).
+ * score: device float64 [batch]; frames: device int32 [batch][2] = (F, K); tob_ref / tob_deg: device float64 [batch][15][f_max] or
+ * NULL: the band magnitudes of step 3 for frames < min(K, f_max), zero from frame K on.  Three launches whatever the lengths. */
+/* bytes of workspace ttsamd_stoi needs; -1: refused (batch < 1, a negative wave_stride or one of 2^31 and more) */
+int64_t ttsamd_stoi_workspace_bytes(int32_t batch, int64_t wave_stride);
+/* TTSAMD_EINVAL (nothing launched): a NULL pointer other than tob_ref / tob_deg, a batch or stride ttsamd_stoi_workspace_bytes refuses,
+ * f_max < 0, a workspace smaller than ttsamd_stoi_workspace_bytes. */
+int32_t ttsamd_stoi(const float* ref, const float* deg, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t extended,
+                    double* score, int32_t* frames, double* tob_ref, double* tob_deg, int32_t f_max, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+/* SI-SDR and SNR of est against ref over n = nsamples[b] samples; out: device float64 [batch][2].  zero_mean != 0: both rows are
+ * centred first (means in float64 over n, a pass of its own).  alpha = <est, ref> / <ref, ref>;
+ * out[b][0] = 10 log10(sum (alpha ref)^2 / sum (alpha ref - est)^2), out[b][1] = 10 log10(sum ref^2 / sum (ref - est)^2).
+ * IEEE results are kept as they fall: +inf for identical rows, NaN for n = 0, NaN (SI-SDR) for an all-zero reference.
+ * One launch, one block per row: sample i is added by thread i mod 256 in ascending order and the block sum is a fixed tree
+ * (ttsamd_dtw_aligned_eval's scheme).  TTSAMD_EINVAL: a NULL pointer, batch < 1, wave_stride < 0. */
+int32_t ttsamd_wave_sdr(const float* ref, const float* est, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t zero_mean,
+                        double* out, void* stream);
+/* Log-spectral distance; out: device float64 [batch][2] = (lsd in dB, frames).  Frames of 1024 samples every 256, no padding:
+ * F = (n - 1024) / 256 + 1, or 0 below 1024 samples; the periodic Hann window of the mel analysis (0.5 - 0.5 cos(2 pi i / 1024));
+ * 1024-point transforms (the template of the 512-point one), P[k] = |X[k]|^2 for k = 0 .. 512, L[k] = 10 log10(max(P[k], 1e-10));
+ * lsd = mean_f sqrt(mean_k (L_ref[k] - L_est[k])^2), NaN for F = 0.  One launch, one block per row, frames in order.
+ * TTSAMD_EINVAL: a NULL pointer, batch < 1, wave_stride < 0. */
+int32_t ttsamd_log_spectral_distance(const float* ref, const float* est, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
+                                     double* out, void* stream);
+
 /* Timing hooks for bench.py (roofline of the dominant kernel): when enabled, hifigan
  * forward brackets its ResBlock conv launches with HIP events on the launch stream. */
 int32_t ttsamd_profile_enable(int32_t on);

@@ -1628,6 +1628,127 @@ class LoudnessEngine:
         return wave, gain
 
 
+STOI_BANDS, STOI_SEGMENT = 15, 30                               # third-octave bands, frames per segment (include/ttsamd.h)
+_wavescore_ws = _Workspace()
+
+
+def _wave_pair(ref, other, lens, what):
+    """two sample-aligned batches [B, n], [B, n'] on the device -> (ref, other, lens int64 [B], B, width): rows of different padded width
+    are compared over the narrower one, so the lengths are clamped to it (on the device)."""
+    ref, other = _dev_f32(ref, 2, f'{what}: reference wave'), _dev_f32(other, 2, f'{what}: second wave')
+    if ref.shape[0] != other.shape[0]:
+        raise L.TtsAmdError(f'{what}: waves of shape {tuple(ref.shape)} and {tuple(other.shape)} differ in batch')
+    other = other.to(ref.device)
+    W = min(ref.shape[1], other.shape[1])
+    if ref.shape[1] != W:
+        ref = ref[:, :W].contiguous()
+    if other.shape[1] != W:
+        other = other[:, :W].contiguous()
+    lens = _dev_lens(lens, ref.shape[0], W, ref.device).clamp(max=W)
+    return ref, other, lens, ref.shape[0], W
+
+
+def stoi_10k(wave_ref, wave_deg, lens=None, extended=False, return_bands=False):
+    """STOI (extended: ESTOI) of wave_deg against the clean wave_ref, both [B, n] fp32 on the device and ALREADY at 10 000 Hz, lens int64
+    [B] or None -> (score float64 [B], frames int32 [B, 2] = (all, kept after the silent-frame removal)); return_bands: + the third-octave
+    magnitudes of both, float64 [B, 15, F], zero from a row's kept count on.  Three launches (ttsamd_stoi), float64 throughout; a row
+    with fewer than 30 kept frames scores 1e-5.  Specified by the arithmetic in include/ttsamd.h; parity with pystoi is not pinned."""
+    lib = _require_gpu()
+    ref, deg, lens, B, W = _wave_pair(wave_ref, wave_deg, lens, 'stoi_10k')
+    score = torch.empty(B, dtype=torch.float64, device=ref.device)
+    frames = torch.zeros(B, 2, dtype=torch.int32, device=ref.device)
+    f_max = max((W - 256) // 128 + 1, 0) if W >= 256 else 0
+    tob_r = torch.zeros(B, STOI_BANDS, f_max, dtype=torch.float64, device=ref.device) if return_bands else None
+    tob_d = torch.zeros_like(tob_r) if return_bands else None
+    if B:
+        nbytes = int(lib.ttsamd_stoi_workspace_bytes(B, W))
+        if nbytes < 0:
+            raise L.TtsAmdError(f'stoi_10k: a batch of {B} rows of {W} samples is refused')
+        ws = _wavescore_ws.get(max(nbytes, 1), ref.device)
+        with torch.cuda.device(ref.device):
+            L.check(lib.ttsamd_stoi(_ptr(ref), _ptr(deg), W, _ptr(lens), B, int(bool(extended)), _ptr(score), _ptr(frames),
+                                    _ptr(tob_r) if f_max else None, _ptr(tob_d) if f_max else None, f_max, _ptr(ws), nbytes, _stream()), 'stoi')
+    return (score, frames, tob_r, tob_d) if return_bands else (score, frames)
+
+
+def wave_sdr(wave_ref, wave_est, lens=None, zero_mean=True):
+    """wave_ref, wave_est [B, n] on the device, lens int64 [B] or None -> float64 [B, 2] = (SI-SDR, SNR) in dB of wave_est against
+    wave_ref, one launch (ttsamd_wave_sdr).  zero_mean: both rows are centred first.  +inf for identical rows, NaN for an empty row."""
+    lib = _require_gpu()
+    ref, est, lens, B, W = _wave_pair(wave_ref, wave_est, lens, 'wave_sdr')
+    out = torch.empty(B, 2, dtype=torch.float64, device=ref.device)
+    if B:
+        with torch.cuda.device(ref.device):
+            L.check(lib.ttsamd_wave_sdr(_ptr(ref), _ptr(est), W, _ptr(lens), B, int(bool(zero_mean)), _ptr(out), _stream()), 'wave_sdr')
+    return out
+
+
+def log_spectral_distance(wave_ref, wave_est, lens=None):
+    """wave_ref, wave_est [B, n] on the device, lens int64 [B] or None -> float64 [B, 2] = (log-spectral distance in dB, frames): frames
+    of 1024 samples every 256 without padding, periodic Hann, 10 log10 max(|X|^2, 1e-10) over bins 0 .. 512, the mean over the frames of
+    the rms difference over the bins; NaN for a row under 1024 samples.  One launch (ttsamd_log_spectral_distance)."""
+    lib = _require_gpu()
+    ref, est, lens, B, W = _wave_pair(wave_ref, wave_est, lens, 'log_spectral_distance')
+    out = torch.empty(B, 2, dtype=torch.float64, device=ref.device)
+    if B:
+        with torch.cuda.device(ref.device):
+            L.check(lib.ttsamd_log_spectral_distance(_ptr(ref), _ptr(est), W, _ptr(lens), B, _ptr(out), _stream()), 'log_spectral_distance')
+    return out
+
+
+class WaveScoreEngine:
+    """Wave against wave at `sample_rate`, sample for sample (csrc/wavescore.hip): STOI / ESTOI (after the engine's own
+    ResampleEngine(sample_rate, 10000, lowpass_filter_width=64, rolloff=0.99): the project's resampler, not pystoi's), SI-SDR / SNR and
+    the log-spectral distance at the waves' own rate.  float64 throughout; nothing is read back to the host.  The two waves must be
+    sample-aligned (copy synthesis, one precision mode against another, a delivery format against the float wave): free-running
+    synthesis is not aligned with a recording, and a wave-level score of it means nothing."""
+
+    def __init__(self, sample_rate=22050, device='cuda'):
+        _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        self.sample_rate = int(sample_rate)
+        self.resampler = ResampleEngine(self.sample_rate, 10000, lowpass_filter_width=64, rolloff=0.99, device=self.device) \
+            if self.sample_rate != 10000 else None
+
+    def to_10k(self, wave, lens=None):
+        """wave [B, n] (+ lens) -> (wave at 10 kHz, its lengths int64 [B] on the device)"""
+        wave = _dev_f32(wave, 2, 'WaveScoreEngine: wave')
+        lens = _dev_lens(lens, wave.shape[0], wave.shape[1], wave.device)
+        if self.resampler is None:
+            return wave, lens
+        return self.resampler.forward(wave, lens)
+
+    def stoi(self, wave_ref, wave_deg, lens=None, extended=False):
+        """-> (score float64 [B], frames int32 [B, 2]) of stoi_10k on both waves resampled to 10 kHz with the shared lengths"""
+        ref, deg, lens, _, _ = _wave_pair(wave_ref, wave_deg, lens, 'WaveScoreEngine.stoi')
+        r10, n10 = self.to_10k(ref, lens)
+        d10, _ = self.to_10k(deg, lens)
+        return stoi_10k(r10, d10, n10, extended=extended)
+
+    def metrics(self, wave_ref, wave_est, lens=None):
+        """-> dict(stoi, estoi, si_sdr, snr, lsd float64 [B]; frames, frames_kept int32 [B]: the STOI frames at 10 kHz before and
+        after the silent-frame removal) of wave_est against wave_ref; the waves are resampled once for both STOI variants."""
+        ref, est, lens, _, _ = _wave_pair(wave_ref, wave_est, lens, 'WaveScoreEngine.metrics')
+        r10, n10 = self.to_10k(ref, lens)
+        e10, _ = self.to_10k(est, lens)
+        st, fr = stoi_10k(r10, e10, n10, extended=False)
+        es, _ = stoi_10k(r10, e10, n10, extended=True)
+        sdr = wave_sdr(ref, est, lens)
+        lsd = log_spectral_distance(ref, est, lens)
+        return dict(stoi=st, estoi=es, si_sdr=sdr[:, 0], snr=sdr[:, 1], lsd=lsd[:, 0], frames=fr[:, 0], frames_kept=fr[:, 1])
+
+
+_wave_scorers = {}
+
+
+def wave_scorer(sample_rate, device):
+    """the WaveScoreEngine of (sample rate, device), made once"""
+    key = (int(sample_rate), str(device))
+    if key not in _wave_scorers:
+        _wave_scorers[key] = WaveScoreEngine(int(sample_rate), device=device)
+    return _wave_scorers[key]
+
+
 _levellers = {}
 
 

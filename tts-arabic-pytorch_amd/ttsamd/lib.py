@@ -160,6 +160,11 @@ SYMBOLS = {
     'ttsamd_loudness_workspace_bytes': (_I64, [_I32, _I64, _I32]),
     'ttsamd_loudness_measure': (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _P]),
     'ttsamd_wave_level': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _P, _P, _P, _P]),
+    # wave-against-wave scores (csrc/wavescore.hip): float64 results, lengths int64 on the device
+    'ttsamd_stoi_workspace_bytes': (_I64, [_I32, _I64]),
+    'ttsamd_stoi': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I64, _P]),
+    'ttsamd_wave_sdr': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P]),
+    'ttsamd_log_spectral_distance': (_I32, [_P, _P, _I64, _P, _I32, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

@@ -101,3 +101,84 @@ def evaluate_waves(wave_pred, wave_ref, n_coef=13, align='dtw', window=None, len
     score = _engines[str(x.device)].score_waves(x, _lens(lens_pred, x, batched), y, _lens(lens_ref, y, batched), n_coef=n_coef, align=align,
                                                 window=window)
     return _scores(score, KEYS, was_np, batched)
+
+
+# ---- wave against wave, sample for sample (csrc/wavescore.hip) -------------------------------------------------------------------------
+# STOI / ESTOI, SI-SDR / SNR and a log-spectral distance between two SAMPLE-ALIGNED waves: copy synthesis (a recording against its own
+# analysis and resynthesis), one precision mode against another, a delivery format against the float wave.  Free-running synthesis is
+# not sample-aligned with a recording, so a wave-level score of it would be meaningless: evaluate_waves and FastPitch2Wave.evaluate stay
+# on the DTW-aligned feature scores above and do not call these.  Specified by their arithmetic (include/ttsamd.h, restated in float64
+# by tests/wavescore_ref.py); parity with a release of pystoi is not pinned, and the 10 kHz resampling is the project's own resampler
+# (lowpass_filter_width = 64), not pystoi's.  float64 throughout.  Out of scope: PESQ, multi-resolution STFT losses, VISQOL, use as
+# training losses, time alignment of unaligned waves.
+WAVE_KEYS = ('stoi', 'estoi', 'si_sdr', 'snr', 'lsd', 'frames', 'frames_kept')
+
+
+def _wave_pair(wave_a, wave_b, lens, what):
+    """-> (a, b [B, n] on the device, lens int64 [B], both numpy, batched).  The two waves of a pair share one length per row; rows of
+    different padded width are compared over the min of the two."""
+    a, np_a, batched = _prep(wave_a, 1, f'{what}: first wave')
+    b, np_b, batched_b = _prep(wave_b, 1, f'{what}: second wave')
+    if batched != batched_b or a.shape[0] != b.shape[0]:
+        raise TtsAmdError(f'{what}: waves of shape {tuple(a.shape)} and {tuple(b.shape)} differ in batch')
+    b = b.to(a.device)
+    W = min(a.shape[1], b.shape[1])
+    a, b = a[:, :W].contiguous(), b[:, :W].contiguous()
+    return a, b, _lens(lens, a, batched), np_a and np_b, batched
+
+
+def stoi(wave_ref, wave_deg, fs=22050, extended=False, lens=None):
+    """Short-time objective intelligibility (extended: ESTOI) of wave_deg [n] against the clean wave_ref [n], both at `fs` Hz: resampled
+    to 10 kHz on the device, silent frames removed on the clean signal, fifteen third-octave bands, segments of 30 frames.  1e-5 for a
+    row with fewer than 30 kept frames.  The two waves share `lens`; rows of different padded width are compared over the min of the two."""
+    r, d, n, was_np, batched = _wave_pair(wave_ref, wave_deg, lens, 'stoi')
+    return _out(E.wave_scorer(fs, r.device).stoi(r, d, n, extended=extended)[0], was_np, batched)
+
+
+def si_sdr(wave_est, wave_ref, zero_mean=True, lens=None):
+    """Scale-invariant signal-to-distortion ratio in dB of wave_est [n] against wave_ref [n] (zero_mean: both centred first); +inf for
+    identical rows.  The two waves share `lens`; rows of different padded width are compared over the min of the two."""
+    e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'si_sdr')
+    return _out(E.wave_sdr(r, e, n, zero_mean=zero_mean)[:, 0], was_np, batched)
+
+
+def snr(wave_est, wave_ref, zero_mean=True, lens=None):
+    """Signal-to-noise ratio in dB, 10 log10(sum ref^2 / sum (ref - est)^2), with si_sdr's conventions (it is NOT invariant to the
+    scale of wave_est)."""
+    e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'snr')
+    return _out(E.wave_sdr(r, e, n, zero_mean=zero_mean)[:, 1], was_np, batched)
+
+
+def log_spectral_distance(wave_est, wave_ref, lens=None):
+    """Log-spectral distance in dB of wave_est [n] against wave_ref [n]: frames of 1024 every 256 samples (no padding), periodic Hann,
+    the mean over frames of the rms over bins 0 .. 512 of the difference of 10 log10 max(|X|^2, 1e-10); NaN under 1024 samples.  The two
+    waves share `lens`; rows of different padded width are compared over the min of the two."""
+    e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'log_spectral_distance')
+    return _out(E.log_spectral_distance(r, e, n)[:, 0], was_np, batched)
+
+
+def wave_metrics(wave_est, wave_ref, fs=22050, lens=None):
+    """{stoi, estoi, si_sdr (zero-mean), snr, lsd, frames, frames_kept} of wave_est [n] against the sample-aligned wave_ref [n] at `fs`
+    Hz; frames / frames_kept are the STOI frames at 10 kHz before and after the silent-frame removal.  The two waves share `lens`; rows
+    of different padded width are compared over the min of the two."""
+    e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'wave_metrics')
+    return _scores(E.wave_scorer(fs, r.device).metrics(r, e, n), WAVE_KEYS, was_np, batched)
+
+
+def copy_synthesis(vocoder, wave, lens=None):
+    """Copy synthesis, the standard way to judge a vocoder: `wave` [n] at 22 050 Hz is analysed with ObjectiveEngine's log-mel analysis,
+    the HiFi-GAN `Generator` resynthesises it (vocoder.engine().forward(mel, frames)) under the current ttsamd.engine.set_precision
+    mode, and the result is scored against the input over 256 * frames samples.  -> (wave_metrics dict, the resynthesised wave
+    [256 * frames] on the device, or numpy for numpy input).  Vocos and Tacotron2 are out of scope for this helper."""
+    x, was_np, batched = _prep(wave, 1, 'copy_synthesis')
+    n = _lens(lens, x, batched)
+    if str(x.device) not in _engines:
+        _engines[str(x.device)] = E.ObjectiveEngine(device=x.device)
+    if x.shape[1] < E.MelSpecEngine.MIN_SAMPLES['same']:
+        raise TtsAmdError(f'copy_synthesis: rows of {x.shape[1]} samples; the mel analysis needs at least '
+                          f'{E.MelSpecEngine.MIN_SAMPLES["same"]}')
+    mel, frames = _engines[str(x.device)].melspec.forward(x, n)
+    out = vocoder.engine().forward(mel, frames)
+    W = min(out.shape[1], x.shape[1])
+    score = E.wave_scorer(22050, x.device).metrics(x[:, :W].contiguous(), out[:, :W].contiguous(), 256 * frames)
+    return _scores(score, WAVE_KEYS, was_np, batched), _out(out, was_np, batched)
