@@ -422,6 +422,38 @@ def test_conv1d_kernel_bf16_modes(dev, precision, mode, tol):
         ref = torch.nn.functional.conv1d(torch.nn.functional.leaky_relu(x.double(), 0.1), w.double(), b.double(),
                                          dilation=dil, padding=(k * dil - dil) // 2)
         assert maxabs(y, ref) < tol, (mode, cin, cout, k)
+    # the epilogues of conv1d_mfma_bf16 behind the conv: ReLU; a residual in mode 0 / 1 / 2 (div 3), which rides in through the accumulators
+    # (EPI 3); the running sum without a residual, which the loading row loop adds.  L = 515: unaligned rows, the per-lane epilogue (EPI 2);
+    # L = 516, dilation 1: the float4 row epilogue (csrc/conv_row_epilogue.hpp).  A ragged batch of four: lengths L, L - 1 (a quad cut by the
+    # utterance end), 131 (cut inside a quad) and 1.  Checker: conv1d in float64 per row at its exact length, the epilogue applied to it in
+    # float64; positions past a row's length keep their bits.  The bounds are the conv's own: the epilogue terms are added in fp32 and are
+    # exact to one rounding.
+    div = 3.0
+    epilogues = {'relu': (True, False, 0), 'res0': (False, True, 0), 'res1': (False, True, 1), 'res2': (False, True, 2), 'sum1': (False, False, 1)}
+    for (cin, cout, k, dil, lin) in [(128, 128, 11, 5, 515), (128, 128, 3, 1, 516)]:
+        x = torch.randn(4, cin, lin, generator=g)
+        w = torch.randn(cout, cin, k, generator=g) / np.sqrt(cin * k)
+        b = torch.randn(cout, generator=g)
+        r = torch.randn(4, cout, lin, generator=g)
+        y0 = torch.randn(4, cout, lin, generator=g)
+        ln = torch.tensor([lin, lin - 1, 131, 1])
+        convs = [torch.nn.functional.conv1d(torch.nn.functional.leaky_relu(x[i:i + 1, :, :n].double(), 0.1), w.double(), b.double(),
+                                            dilation=dil, padding=(k * dil - dil) // 2)[0] for i, n in enumerate(ln.tolist())]
+        xd, wd, bd, rd, ld = x.to(dev), w.to(dev), b.to(dev), r.to(dev), ln.to(dev)
+        for name, (relu, res, emode) in epilogues.items():
+            y = conv1d(xd, wd, bd, lens=ld, dilation=dil, in_slope=0.1, relu_out=relu, res=rd if res else None, mode=emode, div=div,
+                       y=y0.clone().to(dev)).cpu()
+            worst = 0.0
+            for i, n in enumerate(ln.tolist()):
+                v = convs[i] + (r[i, :, :n].double() if res else 0.0)
+                if relu:
+                    v = v.clamp_min(0.0)
+                if emode != 0:
+                    v = (y0[i, :, :n].double() + v) / (div if emode == 2 else 1.0)
+                worst = max(worst, maxabs(y[i, :, :n].double(), v))
+                assert torch.equal(y[i, :, n:], y0[i, :, n:]), (mode, k, name, 'positions past the utterance must keep their bits')
+            print(f'{mode} k={k} d={dil} L={lin} {name}: max-abs {worst:.2e} against float64 (bound {tol:.0e})')
+            assert worst < tol, (mode, cin, cout, k, name)
 
 
 @pytest.mark.parametrize('mode,tol', [('bf16x3', 5e-5), ('bf16', 4e-2)])

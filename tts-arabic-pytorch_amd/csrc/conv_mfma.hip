@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "conv_mfma_common.hpp"
+#include "conv_row_epilogue.hpp"
 
 namespace ttsamd {
 
@@ -357,14 +358,9 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
             constexpr int ROWS_FIT = (LDS_F - 2 * CO_BLK) / NT_BLK;             // whole rows next to the bias/scale vectors
             constexpr int NPASS = (CO_BLK + ROWS_FIT - 1) / ROWS_FIT;           // the tile goes through in NPASS row slabs
             constexpr int ROWS_P = (CO_BLK + NPASS - 1) / NPASS;
-            constexpr int LPR = NT_BLK / 4;                                     // lanes per row (one float4 each)
-            static_assert(ROWS_FIT >= 1 && (64 % LPR == 0 || LPR % 64 == 0), "epilogue slab");
+            static_assert(ROWS_FIT >= 1, "epilogue slab");
             float* ep = reinterpret_cast<float*>(smem4);
             float* epb = ep + LDS_F - 2 * CO_BLK;                               // [CO_BLK] bias, [CO_BLK] scale
-            float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
-            const float* __restrict__ rb = (p.res && !preload) ? p.res + (int64_t)b * p.r_bs : nullptr;
-            const int mode = p.mode, relu_out = p.relu_out, Cout = p.Cout;
-            const float div = p.div;
 #pragma unroll
             for (int ps = 0; ps < NPASS; ++ps) {
                 __syncthreads();                                                // ring stages / previous slab are dead
@@ -380,98 +376,9 @@ __device__ __forceinline__ void conv_tile(const ConvParams& p, float4* smem4, co
                                 ep[(row - ps * ROWS_P) * NT_BLK + qw0 + j * 32 + l31] = acc[i][j][r];
                         }
                 __syncthreads();
-                constexpr int RPI = LPR >= 64 ? 1 : 64 / LPR;                     // rows per wave instruction
-                constexpr int CPL = LPR >= 64 ? LPR / 64 : 1;                     // float4 columns groups per lane
-                constexpr int NR = (ROWS_P + 4 * RPI - 1) / (4 * RPI);            // row iterations per wave
-                if (preload || (!rb && mode == 0 && relu_out < 2)) {
-                    // nothing to read from memory (no residual, or it came in through the accumulators): a loop without
-                    // a single vmcnt wait -- on this ISA a vmcnt wait also drains the wave's previous STORE, which made
-                    // every row iteration of the generic loop below one full memory round trip (~1.7 us)
-                    const float lo = relu_out == 1 ? 0.f : -__builtin_inff();
-                    const bool do_div = mode == 2;
-#pragma unroll 4
-                    for (int it = 0; it < NR; ++it) {
-                        const int r0 = wid * RPI + it * 4 * RPI;
-                        const int rl = r0 + (LPR >= 64 ? 0 : lane / LPR);
-                        const int co = co_blk0 + ps * ROWS_P + rl;
-                        if (rl >= ROWS_P || ps * ROWS_P + rl >= CO_BLK || co >= Cout) continue;
-                        const float bsv = epb[ps * ROWS_P + rl], scv = epb[CO_BLK + ps * ROWS_P + rl];
-#pragma unroll
-                        for (int cg = 0; cg < CPL; ++cg) {
-                            const int col = ((LPR >= 64 ? lane : lane % LPR) + 64 * cg) * 4;
-                            const int q = q0 + col;
-                            if (q >= n_out) continue;
-                            const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-                            float v[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float x = fmaxf((v[e] + bsv) * scv, lo);
-                                if (do_div) x = x / div;
-                                v[e] = x;
-                            }
-                            float* yp = yb + (int64_t)co * p.y_cs + q;
-                            if (q + 3 < n_out) {
-                                *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e)
-                                    if (q + e < n_out) yp[e] = v[e];
-                            }
-                        }
-                    }
-                    continue;
-                }
-                if constexpr (!preload) {
-#pragma unroll 2
-                for (int it = 0; it < NR; ++it) {
-                    const int r0 = wid * RPI + it * 4 * RPI;
-                    const int rl = r0 + (LPR >= 64 ? 0 : lane / LPR);
-                    const int co = co_blk0 + ps * ROWS_P + rl;
-                    if (rl >= ROWS_P || ps * ROWS_P + rl >= CO_BLK || co >= Cout) continue;   // NPASS * ROWS_P may exceed the tile
-                    const float bsv = epb[ps * ROWS_P + rl], scv = epb[CO_BLK + ps * ROWS_P + rl];
-#pragma unroll
-                    for (int cg = 0; cg < CPL; ++cg) {
-                        const int col = ((LPR >= 64 ? lane : lane % LPR) + 64 * cg) * 4;
-                        const int q = q0 + col;
-                        if (q >= n_out) continue;
-                        const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-                        float v[4] = {a4.x, a4.y, a4.z, a4.w};
-                        float* yp = yb + (int64_t)co * p.y_cs + q;
-                        const float* rp = rb ? rb + (int64_t)co * p.r_cs + q : nullptr;
-                        const bool full = q + 3 < n_out;
-                        float rr4[4] = {0.f, 0.f, 0.f, 0.f}, pp4[4] = {0.f, 0.f, 0.f, 0.f};
-                        if (full) {
-                            if (rp) { const float4 t = *reinterpret_cast<const float4*>(rp); rr4[0] = t.x; rr4[1] = t.y; rr4[2] = t.z; rr4[3] = t.w; }
-                            if (mode != 0) { const float4 t = *reinterpret_cast<const float4*>(yp); pp4[0] = t.x; pp4[1] = t.y; pp4[2] = t.z; pp4[3] = t.w; }
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (q + e < n_out) {
-                                    if (rp) rr4[e] = rp[e];
-                                    if (mode != 0) pp4[e] = yp[e];
-                                }
-                        }
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            float x = v[e] + bsv;
-                            if constexpr (EPI == 1) { if (relu_out == 2) x = 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-                            x = x * scv + rr4[e];
-                            if (relu_out == 1) x = fmaxf(x, 0.f);
-                            if constexpr (EPI == 1) { if (relu_out == 3) x = tanhf(x); }
-                            if (mode == 1) x = pp4[e] + x;
-                            else if (mode == 2) x = (pp4[e] + x) / div;
-                            v[e] = x;
-                        }
-                        if (full) {
-                            *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (q + e < n_out) yp[e] = v[e];
-                        }
-                    }
-                }
-                }   // !preload
+                // NPASS * ROWS_P may exceed the tile: the last slab has fewer rows
+                conv_row_epilogue<NT_BLK, ROWS_P, kRowScaleLds, EPI == 1, preload, false>(
+                    p, ep, epb + ps * ROWS_P, epb + CO_BLK + ps * ROWS_P, b, co_blk0 + ps * ROWS_P, min(ROWS_P, CO_BLK - ps * ROWS_P), q0, n_out, 0);
             }
             return;
         }

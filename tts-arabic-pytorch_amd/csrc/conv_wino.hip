@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "conv_mfma_common.hpp"
+#include "conv_row_epilogue.hpp"
 
 namespace ttsamd {
 
@@ -275,17 +276,11 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino_f32(const Conv
 #undef TTS_FETCH_PART
 #undef TTS_XA
 
-    // ---- epilogue: output transform, then the row epilogue of conv_mfma.hip (bias, residual, ReLU, accumulate modes)
+    // ---- epilogue: output transform, then the shared row epilogue (conv_row_epilogue.hpp: bias, residual, ReLU, accumulate modes)
     constexpr int LDS_F = NSTAGE * G::BUF4 * 4;                         // floats of LDS this block owns
     static_assert(LDS_F >= CO_BLK * NT_BLK + CO_BLK, "the tile goes through the dead ring in one pass");
-    constexpr int LPR = NT_BLK / 4;                                     // lanes per row (one float4 each)
-    static_assert(64 % LPR == 0 || LPR % 64 == 0, "epilogue rows");
     float* ep = reinterpret_cast<float*>(smem4);
     float* epb = ep + LDS_F - CO_BLK;                                   // [CO_BLK] bias
-    float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
-    const float* __restrict__ rb = (p.res && !preload) ? p.res + (int64_t)b * p.r_bs : nullptr;
-    const int mode = p.mode, relu_out = p.relu_out, Cout = p.Cout;
-    const float div = p.div;
     __syncthreads();                                                    // ring stages are dead
     if (tid < CO_BLK) epb[tid] = ep_bias;
 #pragma unroll
@@ -299,91 +294,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino_f32(const Conv
             *reinterpret_cast<float2*>(ep + row * NT_BLK + 2 * (wn * 32 + l31)) = y2;
         }
     __syncthreads();
-    constexpr int RPI = LPR >= 64 ? 1 : 64 / LPR;                       // rows per wave instruction
-    constexpr int CPL = LPR >= 64 ? LPR / 64 : 1;                       // float4 column groups per lane
-    constexpr int NR = (CO_BLK + 4 * RPI - 1) / (4 * RPI);              // row iterations per wave
-    if (preload || (!rb && mode == 0)) {
-        // nothing to read from memory: a loop without a single vmcnt wait (conv_mfma.hip: why)
-        const float lo = relu_out == 1 ? 0.f : -__builtin_inff();
-        const bool do_div = mode == 2;
-#pragma unroll 4
-        for (int it = 0; it < NR; ++it) {
-            const int rl = wid * RPI + it * 4 * RPI + (LPR >= 64 ? 0 : lane / LPR);
-            const int co = co_blk0 + rl;
-            if (rl >= CO_BLK || co >= Cout) continue;
-            const float bsv = epb[rl];
-#pragma unroll
-            for (int cg = 0; cg < CPL; ++cg) {
-                const int col = ((LPR >= 64 ? lane : lane % LPR) + 64 * cg) * 4;
-                const int q = q0 + col;
-                if (q >= n_out) continue;
-                const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-                float v[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float x = fmaxf(v[e] + bsv, lo);
-                    if (do_div) x = x / div;
-                    v[e] = x;
-                }
-                float* yp = yb + (int64_t)co * p.y_cs + q;
-                if (q + 3 < n_out) {
-                    *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (q + e < n_out) yp[e] = v[e];
-                }
-            }
-        }
-        return;
-    }
-    if constexpr (!preload) {
-#pragma unroll 2
-        for (int it = 0; it < NR; ++it) {
-            const int rl = wid * RPI + it * 4 * RPI + (LPR >= 64 ? 0 : lane / LPR);
-            const int co = co_blk0 + rl;
-            if (rl >= CO_BLK || co >= Cout) continue;
-            const float bsv = epb[rl];
-#pragma unroll
-            for (int cg = 0; cg < CPL; ++cg) {
-                const int col = ((LPR >= 64 ? lane : lane % LPR) + 64 * cg) * 4;
-                const int q = q0 + col;
-                if (q >= n_out) continue;
-                const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-                float v[4] = {a4.x, a4.y, a4.z, a4.w};
-                float* yp = yb + (int64_t)co * p.y_cs + q;
-                const float* rp = rb ? rb + (int64_t)co * p.r_cs + q : nullptr;
-                const bool full = q + 3 < n_out;
-                float rr4[4] = {0.f, 0.f, 0.f, 0.f}, pp4[4] = {0.f, 0.f, 0.f, 0.f};
-                if (full) {
-                    if (rp) { const float4 t = *reinterpret_cast<const float4*>(rp); rr4[0] = t.x; rr4[1] = t.y; rr4[2] = t.z; rr4[3] = t.w; }
-                    if (mode != 0) { const float4 t = *reinterpret_cast<const float4*>(yp); pp4[0] = t.x; pp4[1] = t.y; pp4[2] = t.z; pp4[3] = t.w; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (q + e < n_out) {
-                            if (rp) rr4[e] = rp[e];
-                            if (mode != 0) pp4[e] = yp[e];
-                        }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float x = v[e] + bsv + rr4[e];
-                    if (relu_out == 1) x = fmaxf(x, 0.f);
-                    if (mode == 1) x = pp4[e] + x;
-                    else if (mode == 2) x = (pp4[e] + x) / div;
-                    v[e] = x;
-                }
-                if (full) {
-                    *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (q + e < n_out) yp[e] = v[e];
-                }
-            }
-        }
-    }
+    conv_row_epilogue<NT_BLK, CO_BLK, kRowScaleNone, false, preload, false>(p, ep, epb, nullptr, b, co_blk0, CO_BLK, q0, n_out, 0);
 }
 
 template <int MT, int WM, int WN, int EPI>
@@ -396,6 +307,14 @@ static int32_t launch_wino_epi(const ConvParams& q, dim3 grid, hipStream_t strea
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, q);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// What the row epilogue and the residual preload of the three Winograd kernels ask of a launch: rows of y (and of the residual) are
+// 16-byte aligned, and a row block addresses within 2^31 bytes (32-bit buffer offsets)
+static bool rows_vec_ok(const ConvParams& p) {
+    return (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
+           (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0)) &&
+           (int64_t)p.Cout * std::max(std::max(p.r_cs, p.y_cs), 1) * 4 < ((int64_t)1 << 31);
 }
 
 // Routing of an exact-fp32 conv launch: 0 = the direct kernel, 1 = conv1d_wino_f32 (this file: k = 3, dilation 1, 128-row tiles),
@@ -415,9 +334,7 @@ int wino_route(const ConvParams& p) {
         const int mask4 = (int)opt_int(OPT_WINO4, kWino4Default);
         const bool ok1 = (mask4 & 16) && p.w != nullptr && p.dil == 1 && p.pad == 0 && p.n_phase == 1 && p.y_ts == 1 && p.CoutP % 64 == 0 &&
                          p.Cin % 32 == 0 && p.in_slope >= 0.f && p.in_slope <= 1.f && !p.x_packed && !p.y_packed &&
-                         (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
-                         (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0)) &&
-                         (int64_t)p.Cout * std::max(std::max(p.r_cs, p.y_cs), 1) * 4 < ((int64_t)1 << 31);
+                         rows_vec_ok(p);
         if (!ok1) return 0;
         // (k = 1 never splits K here: wino4_ksplit answers > 1 only under 192 blocks and then aims at 224, so blocks1 stays under the 512
         // this route asks for -- the two rules exclude each other, and the factor below is always 1 on a launch that passes)
@@ -439,9 +356,7 @@ int wino_route(const ConvParams& p) {
         const bool ok4 = (mask4 & kbit4) && (p.dil == 1 || (mask4 & 8)) && (p.K != 3 || p.Cin % 16 == 0) &&
                          (p.dil == 1 || p.dil == 3 || p.dil == 5) && p.pad == p.dil * (p.K - 1) / 2 && p.n_phase == 1 && p.y_ts == 1 &&
                          p.CoutP % 64 == 0 && p.Cin % 8 == 0 && p.scale == nullptr && p.relu_out < 2 && p.in_slope >= 0.f && p.in_slope <= 1.f &&
-                         (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
-                         (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0)) &&
-                         (int64_t)p.Cout * std::max(std::max(p.r_cs, p.y_cs), 1) * 4 < ((int64_t)1 << 31);
+                         rows_vec_ok(p);
         if (ok4) {
             const int bo4 = wino4_block_outputs(p.dil);
             const int64_t blocks4 = (int64_t)((p.Nout + bo4 - 1) / bo4) * (p.CoutP / 64) * p.batch * wino4_ksplit(p);
@@ -459,9 +374,7 @@ int wino_route(const ConvParams& p) {
     if ((p.dil != 1 && p.dil != 3 && p.dil != 5) || p.pad != p.dil * (p.K - 1) / 2 || p.n_phase != 1 || p.y_ts != 1) return 0;
     if (p.CoutP % 64 != 0 || p.Cin % 8 != 0 || p.scale != nullptr || p.relu_out >= 2) return 0;
     if (!(p.in_slope >= 0.f && p.in_slope <= 1.f)) return 0;         // conv_wino2.hip activates with max(x, slope x)
-    const bool vec_ok = (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
-                        (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0));
-    if (!vec_ok || (int64_t)p.Cout * std::max(std::max(p.r_cs, p.y_cs), 1) * 4 >= ((int64_t)1 << 31)) return 0;
+    if (!rows_vec_ok(p)) return 0;
     const int bo = wino2_block_outputs(p.CoutP, p.dil);
     const int64_t blocks = (int64_t)((p.Nout + bo - 1) / bo) * (p.CoutP / (rows64 ? 64 : 128)) * p.batch;
     // under ~3/4 of a block per CU the direct kernel's 64 x 64 tiles with split K fill the chip better (batch 1: 3.68 ms per step with

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "conv_mfma_common.hpp"
+#include "conv_row_epilogue.hpp"
 #include "bfo.hpp"
 
 namespace ttsamd {
@@ -322,17 +323,10 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino2_f32(const Con
 #undef TTS_SX
 #undef TTS_WRITE_JOB
 
-    // ---- epilogue: output transform, then the row epilogue of conv_mfma.hip (bias, residual, ReLU, accumulate modes)
-    constexpr int LDS_F = CO_BLK * NT_BLK + CO_BLK;                       // the launcher allocates max(ring, this)                         // floats of LDS this block owns
-    static_assert(LDS_F >= CO_BLK * NT_BLK + CO_BLK, "the tile goes through the dead ring in one pass");
-    constexpr int LPR = NT_BLK / 4;                                     // lanes per row (one float4 each)
-    static_assert(64 % LPR == 0 || LPR % 64 == 0, "epilogue rows");
+    // ---- epilogue: output transform, then the shared row epilogue (conv_row_epilogue.hpp: bias, residual, ReLU, accumulate modes)
+    constexpr int LDS_F = CO_BLK * NT_BLK + CO_BLK;                     // floats of LDS this block owns (the launcher allocates max(ring, this))
     float* ep = reinterpret_cast<float*>(smem4);
     float* epb = ep + LDS_F - CO_BLK;                                   // [CO_BLK] bias
-    float* __restrict__ yb = p.y + (int64_t)b * p.y_bs;
-    const float* __restrict__ rb = (p.res && !preload) ? p.res + (int64_t)b * p.r_bs : nullptr;
-    const int mode = p.mode, relu_out = p.relu_out, Cout = p.Cout;
-    const float div = p.div;
     __syncthreads();                                                    // ring stages are dead
     if (tid < CO_BLK) epb[tid] = ep_bias;
 #pragma unroll
@@ -349,91 +343,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino2_f32(const Con
             }
         }
     __syncthreads();
-    constexpr int RPI = LPR >= 64 ? 1 : 64 / LPR;                       // rows per wave instruction
-    constexpr int CPL = LPR >= 64 ? LPR / 64 : 1;                       // float4 column groups per lane
-    constexpr int NR = (CO_BLK + 4 * RPI - 1) / (4 * RPI);              // row iterations per wave
-    if (preload || (!rb && mode == 0)) {
-        // nothing to read from memory: a loop without a single vmcnt wait (conv_mfma.hip: why)
-        const float lo = relu_out == 1 ? 0.f : -__builtin_inff();
-        const bool do_div = mode == 2;
-#pragma unroll 4
-        for (int it = 0; it < NR; ++it) {
-            const int rl = wid * RPI + it * 4 * RPI + (LPR >= 64 ? 0 : lane / LPR);
-            const int co = co_blk0 + rl;
-            if (rl >= CO_BLK || co >= Cout) continue;
-            const float bsv = epb[rl];
-#pragma unroll
-            for (int cg = 0; cg < CPL; ++cg) {
-                const int col = ((LPR >= 64 ? lane : lane % LPR) + 64 * cg) * 4;
-                const int q = q0 + col;
-                if (q >= n_out || col >= nt_eff) continue;
-                const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-                float v[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float x = fmaxf(v[e] + bsv, lo);
-                    if (do_div) x = x / div;
-                    v[e] = x;
-                }
-                float* yp = yb + (int64_t)co * p.y_cs + q;
-                if (q + 3 < n_out) {
-                    *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (q + e < n_out) yp[e] = v[e];
-                }
-            }
-        }
-        return;
-    }
-    if constexpr (!preload) {
-#pragma unroll 2
-        for (int it = 0; it < NR; ++it) {
-            const int rl = wid * RPI + it * 4 * RPI + (LPR >= 64 ? 0 : lane / LPR);
-            const int co = co_blk0 + rl;
-            if (rl >= CO_BLK || co >= Cout) continue;
-            const float bsv = epb[rl];
-#pragma unroll
-            for (int cg = 0; cg < CPL; ++cg) {
-                const int col = ((LPR >= 64 ? lane : lane % LPR) + 64 * cg) * 4;
-                const int q = q0 + col;
-                if (q >= n_out || col >= nt_eff) continue;
-                const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-                float v[4] = {a4.x, a4.y, a4.z, a4.w};
-                float* yp = yb + (int64_t)co * p.y_cs + q;
-                const float* rp = rb ? rb + (int64_t)co * p.r_cs + q : nullptr;
-                const bool full = q + 3 < n_out;
-                float rr4[4] = {0.f, 0.f, 0.f, 0.f}, pp4[4] = {0.f, 0.f, 0.f, 0.f};
-                if (full) {
-                    if (rp) { const float4 t = *reinterpret_cast<const float4*>(rp); rr4[0] = t.x; rr4[1] = t.y; rr4[2] = t.z; rr4[3] = t.w; }
-                    if (mode != 0) { const float4 t = *reinterpret_cast<const float4*>(yp); pp4[0] = t.x; pp4[1] = t.y; pp4[2] = t.z; pp4[3] = t.w; }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (q + e < n_out) {
-                            if (rp) rr4[e] = rp[e];
-                            if (mode != 0) pp4[e] = yp[e];
-                        }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float x = v[e] + bsv + rr4[e];
-                    if (relu_out == 1) x = fmaxf(x, 0.f);
-                    if (mode == 1) x = pp4[e] + x;
-                    else if (mode == 2) x = (pp4[e] + x) / div;
-                    v[e] = x;
-                }
-                if (full) {
-                    *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (q + e < n_out) yp[e] = v[e];
-                }
-            }
-        }
-    }
+    conv_row_epilogue<NT_BLK, CO_BLK, kRowScaleNone, false, preload, true>(p, ep, epb, nullptr, b, co_blk0, CO_BLK, q0, n_out, nt_eff);
 }
 
 

@@ -56,6 +56,7 @@
 #include <vector>
 
 #include "conv_mfma_common.hpp"
+#include "conv_row_epilogue.hpp"
 #include "bfo.hpp"
 
 namespace ttsamd {
@@ -746,14 +747,12 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
         }
         return;
     }
-    // ---- row epilogue (strip kernels, C-in slices, k = 1): output transform into the dead ring, then the row epilogue of conv_mfma.hip
-    // (bias, residual, ReLU, accumulate modes)
+    // ---- row epilogue (strip kernels, C-in slices, k = 1): output transform into the dead ring, then the shared row epilogue
+    // (conv_row_epilogue.hpp: bias, residual, ReLU, accumulate modes)
     constexpr int LDS_F = CO_BLK * NT_BLK + CO_BLK;                     // floats of LDS this block owns (the launcher allocates max(ring, this))
-    constexpr int LPR = NT_BLK / 4;                                     // lanes per row (one float4 each) = 64
-    static_assert(LPR == 64, "one wave instruction per row");
+    static_assert(NT_BLK / 4 == 64, "one wave instruction per row: a lane's columns are the same in every row");
     float* ep = reinterpret_cast<float*>(smem4);
     float* epb = ep + LDS_F - CO_BLK;                                   // [CO_BLK] bias
-    const float* __restrict__ rb = p.res ? p.res + (int64_t)b * p.r_bs : nullptr;
     __syncthreads();                                                    // ring stages are dead
     if (tid < CO_BLK) epb[tid] = ep_bias;
 #pragma unroll
@@ -773,11 +772,11 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     }
 #undef TTS_OUT_QUAD
     __syncthreads();
-    constexpr int NR = CO_BLK / 4;                                      // row iterations per wave
     const int col = lane * 4, q = q0 + col;
     if (q >= n_out || col >= nt_eff) return;
-    const bool full = q + 3 < n_out;
     if (p.ksplit > 1) {                                                 // raw partial sums of this C-in slice
+        constexpr int NR = CO_BLK / 4;                                  // row iterations per wave
+        const bool full = q + 3 < n_out;
         float* __restrict__ pb = p.splitk_ws + ((int64_t)ks * p.batch + b) * Cout * p.Nout;
 #pragma unroll 4
         for (int it = 0; it < NR; ++it) {
@@ -797,76 +796,9 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
         }
         return;
     }
-    // k = 1 only (Vocos' pointwise convs): GELU behind the bias, a per-row factor before the residual, tanh at the end (conv_mfma.hip's epilogue)
-    const float* __restrict__ scale = K == 1 ? p.scale : nullptr;
-    const bool plain_act = K != 1 || (relu_out < 2 && scale == nullptr);
-    if (plain_act && !rb && mode == 0) {
-        // nothing to read from memory: a loop without a single vmcnt wait (conv_mfma.hip: why)
-        const float lo = relu_out == 1 ? 0.f : -__builtin_inff();
-#pragma unroll 4
-        for (int it = 0; it < NR; ++it) {
-            const int rl = wid + it * 4;
-            const int co = co_blk0 + rl;
-            if (co >= Cout) continue;
-            const float bsv = epb[rl];
-            const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-            float v[4] = {fmaxf(a4.x + bsv, lo), fmaxf(a4.y + bsv, lo), fmaxf(a4.z + bsv, lo), fmaxf(a4.w + bsv, lo)};
-            float* yp = yb + (int64_t)co * p.y_cs + q;
-            if (full) {
-                *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (q + e < n_out) yp[e] = v[e];
-            }
-        }
-        return;
-    }
-#pragma unroll 2
-    for (int it = 0; it < NR; ++it) {
-        const int rl = wid + it * 4;
-        const int co = co_blk0 + rl;
-        if (co >= Cout) continue;
-        const float bsv = epb[rl];
-        const float4 a4 = *reinterpret_cast<const float4*>(ep + rl * NT_BLK + col);
-        float v[4] = {a4.x, a4.y, a4.z, a4.w};
-        float* yp = yb + (int64_t)co * p.y_cs + q;
-        const float* rp = rb ? rb + (int64_t)co * p.r_cs + q : nullptr;
-        float rr4[4] = {0.f, 0.f, 0.f, 0.f}, pp4[4] = {0.f, 0.f, 0.f, 0.f};
-        if (full) {
-            if (rp) { const float4 t = *reinterpret_cast<const float4*>(rp); rr4[0] = t.x; rr4[1] = t.y; rr4[2] = t.z; rr4[3] = t.w; }
-            if (mode != 0) { const float4 t = *reinterpret_cast<const float4*>(yp); pp4[0] = t.x; pp4[1] = t.y; pp4[2] = t.z; pp4[3] = t.w; }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (q + e < n_out) {
-                    if (rp) rr4[e] = rp[e];
-                    if (mode != 0) pp4[e] = yp[e];
-                }
-        }
-        const float scv = (K == 1 && scale) ? scale[co] : 1.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float x = v[e] + bsv;
-            if constexpr (K == 1) {
-                if (relu_out == 2) x = 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));   // nn.GELU()
-                x = x * scv;
-            }
-            x += rr4[e];
-            if (relu_out == 1) x = fmaxf(x, 0.f);
-            if constexpr (K == 1) { if (relu_out == 3) x = tanhf(x); }
-            if (mode == 1) x = pp4[e] + x;
-            else if (mode == 2) x = (pp4[e] + x) / div;
-            v[e] = x;
-        }
-        if (full) {
-            *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (q + e < n_out) yp[e] = v[e];
-        }
-    }
+    // k = 1 only (Vocos' pointwise convs): GELU behind the bias, a per-row factor (read from global memory) before the residual, tanh at the end
+    conv_row_epilogue<NT_BLK, CO_BLK, K == 1 ? kRowScaleGlobal : kRowScaleNone, K == 1, false, true>(p, ep, epb, K == 1 ? p.scale : nullptr, b,
+                                                                                                      co_blk0, CO_BLK, q0, n_out, nt_eff);
 }
 
 template <int K, int NOCT, int NSTAGE, int EPI, int LP, int PT = 6>
