@@ -973,6 +973,37 @@ int32_t ttsamd_loudness_measure(const float* wave, int64_t wave_stride, const in
 int32_t ttsamd_wave_level(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
                           const float* target, float ceiling, const double* loudness, const float* peak, float* gain_out, void* stream);
 
+/* ---- look-ahead limiter (csrc/limiter.hip): a row gain and a gain-reduction curve, so that a LUFS target is reached where the cap of
+ * ttsamd_wave_level stops short of it, and so that a fixed gain can be applied inside a stream.  wave [batch][wave_stride] fp32, in
+ * place; nsamples: device int64 [batch], clamped to [0, wave_stride]; nothing at or past nsamples[b] is read or written and nothing is
+ * read back to the host.  The curve is computed in Q30 integers (Q = 2^30): minimum and integer sum are exact and order-free, so a
+ * row alone, a row of a ragged batch and a row cut into windows that carry the reach below leave with the same bits.
+ * Per row, with n samples x, the row gain g (fp32), the ceiling c, attack A and hold R in samples (0 <= A <= R, A <= 1024, R <= 4096):
+ *   u[i] = fl32(x[i] g);  d[i] = |u[i]|;  q[i] = Q if not d[i] > c, else floor((double)c / (double)d[i] 2^30) (a float64 division);
+ *   m[i] = min q[j] over j in [i - R, i + A] within [0, n);
+ *   s[i] = floor(sum over k = -A .. A of m[clamp(i + k, 0, n - 1)] / (2A + 1)) in int64;
+ *   y[i] = (float)((double)u[i] (double)s[i] 2^-30)  (the product rounded to float64, then to fp32).
+ * Every m term of s[i] has a window that contains i (A <= R), so s[i] <= q[i] and |y[i]| <= c holds exactly.  Where no sample within
+ * reach exceeds the ceiling, y[i] = u[i] bit for bit.  One sample over the ceiling at j lowers the gain on [j - 2A, j + R + A], fully on
+ * [j, j + R - A], with linear ramps.  y[i] depends on x over [i - A - R, i + 2A] only: the limiter's reach.  A NaN passes through
+ * (q = Q), an infinity gives q = 0; memory-safe and unspecified beyond that.
+ * Two launches: the q plane to the workspace, then blocks that own tiles of 2048 samples stage q for the tile plus reach in LDS, take the
+ * sliding minimum by doubling and the box sum in int64, and write y. */
+/* bytes of workspace ttsamd_wave_limit needs; -1: refused (batch < 1, a negative stride or one of 2^40 and more) */
+int64_t ttsamd_wave_limit_workspace_bytes(int32_t batch, int64_t wave_stride);
+/* mode: device int32 [batch], target: device fp32 [batch].  mode 0: the row is not written, gain 1.  mode 2 (target in LUFS):
+ * g = fl32(min(10^((target - L) / 20), max_gain)) in float64 with L = loudness[b] (device float64 [batch], what
+ * ttsamd_loudness_measure wrote) and NO cap from the peak; L not finite, or loudness NULL: not written, gain 1.  mode 3 (target is a gain
+ * in dB, the stream's mode): g = fl32(min(10^(target / 20), max_gain)).  Any other device value is treated as mode 0 (the callers
+ * check the modes on the host before the upload).  max_gain is linear, finite and > 0.  gain_out: device fp32 [batch];
+ * reduction_out: device int32 [batch] = min over i of s[i]: Q where nothing was limited, and for a row that is empty or not written.
+ * TTSAMD_EINVAL (nothing launched): a NULL pointer other than loudness, batch outside 1 .. 65535, a ceiling that is not in (0, 1], a
+ * max_gain that is not finite and > 0, attack / hold outside the limits above, a workspace smaller than
+ * ttsamd_wave_limit_workspace_bytes. */
+int32_t ttsamd_wave_limit(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
+                          const float* target, float ceiling, float max_gain, int32_t attack, int32_t hold, const double* loudness,
+                          float* gain_out, int32_t* reduction_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- wave-against-wave scores (csrc/wavescore.hip): STOI / ESTOI at 10 kHz, SI-SDR / SNR and a log-spectral distance between the rows
  * of two ragged mono batches that are sample-aligned (copy synthesis, a precision mode against fp32, a delivery format against the float
  * wave; free-running synthesis is NOT aligned with a recording and has no meaningful score here).  Both waves are [batch][wave_stride]

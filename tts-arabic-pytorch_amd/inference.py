@@ -43,7 +43,8 @@ def infer(args):
     with open(os.path.join(args.out_dir, 'index.tsv'), 'w', encoding='utf-8') as index:
         for k in range(0, len(lines), args.batch_size):
             batch = lines[k:k + args.batch_size]
-            wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, normalize=args.normalize)
+            wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, normalize=args.normalize,
+                             **({'limiter': True} if args.limiter else {}))
             for line, wav in zip(batch, wavs):
                 if rate != 22_050:                      # the finished wave through the device resampler, then the matching file format
                     wav = resample(wav.reshape(1, -1).to('cuda'), 22_050, rate)[0]
@@ -70,7 +71,12 @@ def main(argv=None):
     p.add_argument('--encoding', type=str, default='pcm16', choices=sorted(WAV_ENCODINGS))
     # ... and the level of every wave, set on the device: peak (x / max|x| * 0.99), lufs (-23 LUFS, ITU-R BS.1770-4) or a target in LUFS
     p.add_argument('--normalize', type=normalize_option, default=None, metavar='peak|lufs|<LUFS>')
-    infer(p.parse_args(argv))
+    # ... with the look-ahead limiter in place of the cap on the gain, so that a LUFS target is reached (needs --normalize lufs or a target)
+    p.add_argument('--limiter', action='store_true')
+    args = p.parse_args(argv)
+    if args.limiter and args.normalize in (None, 'peak'):
+        p.error("--limiter needs --normalize lufs or a target in LUFS")
+    infer(args)
 
 
 if __name__ == '__main__':

@@ -23,7 +23,7 @@ from ttsamd.engine import average_pitch as _average_pitch
 from ttsamd.engine import binarization_loss as _binarization_loss
 from ttsamd.engine import forward_sum_loss as _forward_sum_loss
 from ttsamd.engine import mas as _mas
-from ttsamd.engine import check_finite, check_normalize, check_speakers, level_waves, per_row, row_values
+from ttsamd.engine import check_finite, check_limiter, check_normalize, check_speakers, level_waves, limiter_spec, per_row, row_values
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
@@ -51,6 +51,14 @@ def _take(value, idx):
 
 def _at(value, i):
     return value[i] if per_row(value) else value
+
+
+def _lim(limiter, normalize):
+    """the `limiter` keyword for a call that gets `normalize` (one option or a list): only where a limiter is asked for and a line of
+    that call asks for a level -- every other call gets exactly the arguments it got before"""
+    if not limiter or not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
+        return {}
+    return {'limiter': limiter}
 
 
 def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1., pitch_add=0., denoise=0., normalize=None):
@@ -398,25 +406,28 @@ class FastPitch2Wave(nn.Module):
 
     @torch.inference_mode()
     def tts_single(self, text_buckw: str, speed: float = 1, speaker_id: int = 0, denoise: float = 0,
-                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None):
+                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None,
+                   limiter=False):
         check_normalize(normalize, 1)
+        limiter = check_limiter(limiter, normalize)
         mel_spec = self.model.ttmel_single(text_buckw, speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
                                            pitch_add=pitch_add)
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
         if normalize is not None:
-            wave = level_waves(wave, None, normalize, self.sample_rate)
+            wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize))
         if return_mel:
             return wave[0].cpu(), mel_spec
         return wave[0].cpu()
 
-    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize=None):
+    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize=None, limiter=False):
         """What tts_batch and tts_batch_device share: (wave [B, n_max], n_samples int64 [B], reverse_ids), rows in the collate order (longest
         first).  Every control is a scalar or one value per line of `batch`; a per-line denoise strength goes through the same sort as
         the lines, and a line whose strength is not > 0 keeps its vocoder output bit for bit.  `normalize` takes the same sort; the
         rows are levelled on the device after the denoiser (ttsamd.engine.level_waves)."""
         check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise, normalize=normalize)
+        limiter = check_limiter(limiter, normalize)
         mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
                                                                     pitch_add)
         wave = self.vocoder.engine().forward(mel, dec_lens)             # one ragged batched launch sequence
@@ -425,23 +436,24 @@ class FastPitch2Wave(nn.Module):
         if any(d > 0 for d in denoise) if per_row(denoise) else denoise > 0:
             wave = self.denoiser.forward_batch(wave, n, denoise)
         if normalize is not None:
-            wave = level_waves(wave, n, _take(normalize, reverse_ids.argsort().tolist()), self.sample_rate)
+            wave = level_waves(wave, n, _take(normalize, reverse_ids.argsort().tolist()), self.sample_rate, **_lim(limiter, normalize))
         return wave, n, reverse_ids
 
     @torch.inference_mode()
     def tts_batch_device(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0,
-                         vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None):
+                         vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None,
+                         limiter=False):
         """`tts_batch` without the device->host copy: (wave [B, n_max] float32, n_samples int64 [B]), both in HBM,
         rows in the order of `batch` (zeros past n_samples[b]).  What the data-parallel gather (ttsamd.dp) and
         any GPU-side consumer take; `tts_batch` is this plus one D2H."""
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize)
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter)
         rev = reverse_ids.to(wave.device)
         return wave.index_select(0, rev), n.index_select(0, rev)
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0, vowelizer=None,
-                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None):
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize)
+                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None, limiter=False):
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter)
         n = n.tolist()
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:347-350); so do we
@@ -449,7 +461,7 @@ class FastPitch2Wave(nn.Module):
 
     def tts(self, text_input: Union[str, List[str]], speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
             batch_size: int = 2, vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.,
-            return_mel: bool = False, normalize=None) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None, limiter=False) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:352-435): str -> Tensor[n_samples] (CPU);
         list -> list of tensors, chunked by `batch_size`.
         Mixed requests (not in the reference): for a list of lines, speed, denoise, speaker_id, pitch_mul and pitch_add each take a scalar
@@ -462,31 +474,37 @@ class FastPitch2Wave(nn.Module):
         the device after the denoiser and before the copy to the host -- None (as it comes from the vocoder), 'peak' (x / max|x| * 0.99:
         the bits of utils.audio.peak_normalise on that wave), 'lufs' (ITU-R BS.1770-4 integrated loudness -23 LUFS) or a target in LUFS
         (one gain per wave, capped so that the peak stays <= 0.99), or for a list of lines one such value per line.  It changes
-        nothing in front of it: a wave is its un-normalised wave, levelled."""
+        nothing in front of it: a wave is its un-normalised wave, levelled.
+        limiter (False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db; needs a normalize): the lines with 'lufs' or
+        a target get the full gain towards it (at most max_gain_db) and the look-ahead limiter holds their peaks at the ceiling
+        (utils.audio.limit; include/ttsamd.h states the arithmetic), so the target is reached where the cap would have stopped short of
+        it; 'peak' and None lines keep their path.  One setting for the call, not per line."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, pitch_mul=pitch_mul, pitch_add=pitch_add)
         if normalize is not None and not (per_row(normalize) and all(v is None for v in normalize)):
             kw['normalize'] = normalize         # (None, or only None: the calls below get exactly the arguments they got before)
         if isinstance(text_input, str):
-            return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw)
+            return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw, **({'limiter': limiter} if limiter else {}))
         assert isinstance(text_input, list)
         check_line_controls(len(text_input), self.model.net_config['n_speakers'], **dict(kw, normalize=normalize))
+        limiter = check_limiter(limiter, normalize)
         if (len(text_input) > batch_size and not return_mel and self.device.type == 'cuda'
                 and os.environ.get('TTSAMD_TTS_PIPELINE', '1') != '0'):
-            return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw)
+            return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw, **_lim(limiter, normalize))
         if batch_size == 1:
-            return [self.tts_single(sample, vowelizer=vowelizer, return_mel=return_mel, **{k: _at(v, i) for k, v in kw.items()})
+            return [self.tts_single(sample, vowelizer=vowelizer, return_mel=return_mel, **{k: _at(v, i) for k, v in kw.items()},
+                                    **_lim(limiter, _at(normalize, i)))
                     for i, sample in enumerate(text_input)]
         wav_list = []
         for k in range(0, len(text_input), batch_size):
             idx = range(k, min(k + batch_size, len(text_input)))
             wav_list += self.tts_batch(text_input[k:k + batch_size], vowelizer=vowelizer, return_mel=return_mel,
-                                       **{n: _take(v, idx) for n, v in kw.items()})
+                                       **{n: _take(v, idx) for n, v in kw.items()}, **_lim(limiter, _take(normalize, idx)))
         return wav_list
 
     # the options of one request of tts_requests and what a request that leaves one out gets: tts()'s own defaults
     REQUEST_DEFAULTS = dict(speed=1., denoise=0.005, speaker_id=0, pitch_mul=1., pitch_add=0.)
 
-    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None):
+    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None, limiter=False):
         """A server's queue in one go: `requests` is a list of dicts with `text` and any of speed, denoise, speaker_id, pitch_mul, pitch_add, normalize
         (the per-request options of the reference's app); returns one wave per request, in request order, from ONE `tts` call with the
         options as per-line lists -- requests with different options share batches instead of one call per distinct option tuple."""
@@ -501,18 +519,20 @@ class FastPitch2Wave(nn.Module):
         lists = {k: [r.get(k, d) for r in requests] for k, d in self.REQUEST_DEFAULTS.items()}
         if any(r.get('normalize') is not None for r in requests):
             lists['normalize'] = [r.get('normalize') for r in requests]
+        if limiter:                               # one setting for the call (a request has no limiter of its own); tts checks it
+            lists['limiter'] = limiter
         return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
     # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
-    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None):
+    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None, limiter=None):
         """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
         from ttsamd.stream import StreamingVocoder
         key = (str(self.device), int(chunk_frames), int(first_chunk_frames), bool(pcm16), int(max_streams), int(max_frames),
-               None if sample_rate is None else int(sample_rate), encoding)
+               None if sample_rate is None else int(sample_rate), encoding, None if limiter is None else tuple(sorted(limiter.items())))
         if getattr(self, '_stream_key', None) != key:
             self._stream_voc = StreamingVocoder(self.vocoder, self.denoiser, max_streams=max_streams, max_frames=max_frames,
                                                 chunk_frames=chunk_frames, first_chunk_frames=first_chunk_frames, pcm16=pcm16,
-                                                sample_rate=sample_rate, encoding=encoding)
+                                                sample_rate=sample_rate, encoding=encoding, limiter=limiter)
             self._stream_key = key
         for sid in self._stream_voc.open_streams:           # a generator that was abandoned half-way
             self._stream_voc.close(sid)
@@ -520,7 +540,8 @@ class FastPitch2Wave(nn.Module):
 
     def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
                    max_streams: int = 32, max_frames: int = 4096, speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
-                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., sample_rate=None, encoding=None):
+                   vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., sample_rate=None, encoding=None, gain_db=0.0,
+                   limiter=False):
         """`tts` that hands out audio while it is being made (a generator; one at a time per model).  FastPitch is not autoregressive, so
         the whole mel exists at once; the vocoder then runs over windows of it (ttsamd.stream.StreamingVocoder), the first of
         first_chunk_frames frames, the following of chunk_frames.
@@ -533,19 +554,30 @@ class FastPitch2Wave(nn.Module):
         `last` once.  No peak normalisation: that needs the whole wave.
         sample_rate / encoding ('float32' | 'pcm16' | 'mulaw' | 'alaw'): the chunks leave at that rate and in that encoding (8 000 Hz
         'mulaw' is telephony's G.711: uint8 chunks); put together they are utils.audio.resample of the line's 22 050 Hz samples,
-        encoded, bit for bit -- no seam at a chunk border."""
+        encoded, bit for bit -- no seam at a chunk border.
+        limiter (False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db) and gain_db (a scalar, or one value per
+        line): levelling inside the stream.  A stream cannot measure its loudness, so it is levelled the way a live chain is: a fixed
+        gain, then the look-ahead limiter, at 22 050 Hz in front of the resampler.  The chunks put together are utils.audio.limit of
+        the stream's samples in front of the limiter (StreamingVocoder.bypass), bit for bit; against the stream without a limiter
+        those differ within fp32 summation order, as its windows are narrower.  gain_db other than 0 without a limiter is a ValueError."""
         kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
+        limiter = limiter_spec(limiter)
+        n_lines = 1 if isinstance(text_input, str) else len(text_input)
+        gains = row_values(gain_db, n_lines, 'gain_db') if per_row(gain_db) else [gain_db]
+        check_finite(gains, 'gain_db')
+        if limiter is None and any(float(g) != 0.0 for g in gains):
+            raise ValueError('tts_stream: gain_db needs limiter=True (or its settings): a gain alone could clip')
         if isinstance(text_input, str):
             mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw)
-            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding)
-            sv.open(mel, denoise)
+            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter)
+            sv.open(mel, denoise, float(gains[0]))
             while sv.open_streams:
                 for _, chunk, _ in sv.step():
                     yield chunk.cpu()
             return
         lines = list(text_input)
         check_line_controls(len(lines), self.model.net_config['n_speakers'], denoise=denoise, **kw)
-        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding)
+        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter)
         # FastPitch over the lines in input order, in ragged calls of up to _ALONE_GROUP rows computed as if alone; a group is made when
         # a slot is free and no mel is waiting
         groups, fill, longest = [], [], 0
@@ -566,7 +598,7 @@ class FastPitch2Wave(nn.Module):
                                                                  pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos))
                     waiting = [(p, mel_b[b, :, :t]) for b, (p, t) in enumerate(zip(pos, lens_d.cpu().tolist()))]
                 p, mel = waiting.pop(0)
-                line_of[sv.open(mel, _at(denoise, p))] = p
+                line_of[sv.open(mel, _at(denoise, p), float(_at(gain_db, p)))] = p
             if not line_of:
                 return
             for sid, chunk, last in sv.step():
@@ -663,7 +695,7 @@ class FastPitch2Wave(nn.Module):
 
     @torch.inference_mode()
     def _tts_list_pipelined(self, text_input, batch_size, speed, denoise, speaker_id, vowelizer, pitch_mul, pitch_add,
-                            return_mel=False, normalize=None):
+                            return_mel=False, normalize=None, limiter=False):
         """The list path of `tts` over several chunks, as a three-stage pipeline on three HIP streams: tokenisation + FastPitch
         of the next chunks (host work and ~150 short launches that leave most CUs idle) run under the vocoder + denoiser of the
         previous ones, whose audio is copied to the host on a third stream.  FastPitch sees exactly the chunks of the one-stream
@@ -764,7 +796,7 @@ class FastPitch2Wave(nn.Module):
                 elif dn > 0:
                     wave = self.denoiser.forward_batch(wave, lens_d * hop, dn, nsamples_min=min(n_host))
                 if normalize is not None:
-                    wave = level_waves(wave, lens_d * hop, _take(normalize, pos), self.sample_rate)
+                    wave = level_waves(wave, lens_d * hop, _take(normalize, pos), self.sample_rate, **_lim(limiter, _take(normalize, pos)))
                 done = torch.cuda.Event()
                 done.record(s_hg)
             if pending is not None:

@@ -1578,6 +1578,7 @@ class LoudnessEngine:
         L.check(self.lib.ttsamd_loudness_coefficients(self.sample_rate, coef), 'loudness_coefficients')
         self.coefficients = np.array(coef)      # b1[0..2], a1[1..2], b2[0..2], a2[1..2]
         self.ws = _Workspace()
+        self.limit_ws = _Workspace()
 
     def _wave(self, wave, lens):
         wave = _dev_f32(wave, 2, 'LoudnessEngine: wave')
@@ -1627,8 +1628,115 @@ class LoudnessEngine:
                                                    float(ceiling), _ptr(loud), _ptr(peak), _ptr(gain), _stream()), 'wave_level')
         return wave, gain
 
+    def limit_samples(self, wave, lens, mode, target, ceiling, max_gain, attack, hold, loudness=None):
+        """ttsamd_wave_limit as it is: attack and hold in samples, max_gain linear, mode int32 [B] and target fp32 [B] ON THE DEVICE
+        (already checked), loudness float64 [B] on the device or None (no mode 2 row) -> (wave, gain fp32 [B], reduction int32 [B])."""
+        B, n_max = wave.shape
+        gain = torch.ones(B, dtype=torch.float32, device=wave.device)
+        red = torch.full((B,), LIMITER_Q, dtype=torch.int32, device=wave.device)
+        if B:
+            nbytes = int(self.lib.ttsamd_wave_limit_workspace_bytes(B, n_max))
+            if nbytes < 0:
+                raise L.TtsAmdError(f'limit: a batch of {B} rows of {n_max} samples is refused')
+            ws = self.limit_ws.get(max(nbytes, 1), wave.device)
+            with torch.cuda.device(wave.device):
+                L.check(self.lib.ttsamd_wave_limit(_ptr(wave), n_max, _ptr(lens), B, _ptr(mode), _ptr(target), float(ceiling), float(max_gain),
+                                                   int(attack), int(hold), _ptr(loudness), _ptr(gain), _ptr(red), _ptr(ws), nbytes,
+                                                   _stream()), 'wave_limit')
+        return wave, gain, red
 
-STOI_BANDS, STOI_SEGMENT = 15, 30                               # third-octave bands, frames per segment (include/ttsamd.h)
+    def limit(self, wave, lens, mode, target, ceiling=0.99, max_gain_db=30.0, attack_ms=1.5, hold_ms=15.0):
+        """The look-ahead limiter (csrc/limiter.hip; include/ttsamd.h states its arithmetic): wave [B, n_max] fp32 contiguous on the
+        device, IN PLACE up to lens[b]: row b times its gain, then a gain-reduction curve that keeps |y| <= ceiling exactly and leaves a
+        row that stays under the ceiling as fl32(x g).  mode: 0 / 'off', 2 / 'lufs' (towards `target` LUFS, measured here, with no cap
+        from the peak), 3 / 'gain' (`target` is a gain in dB); mode and target are scalars or one value per row, checked here on the host.
+        The gain is at most max_gain_db.  attack_ms: the look-ahead and the length of both ramps, hold_ms: how long the reduction stays
+        after a peak; A = round(attack_ms fs / 1000) <= 1024 samples, R = max(round(hold_ms fs / 1000), A) <= 4096.
+        -> (wave, gain fp32 [B], reduction int32 [B] = the smallest curve value in Q30, LIMITER_Q where nothing was limited)."""
+        if not isinstance(wave, torch.Tensor) or wave.device.type != 'cuda' or wave.dtype != torch.float32 or not wave.is_contiguous() \
+                or wave.dim() != 2:
+            raise L.TtsAmdError('LoudnessEngine.limit: expected a contiguous float32 tensor [B, n] on the ROCm device (it is limited in place)')
+        B, n_max = wave.shape
+        lens = _dev_lens(lens, B, n_max, wave.device)
+        modes = row_values(mode, B, 'limit mode') if per_row(mode) else [mode] * B
+        modes = [LIMIT_MODES.get(m, m) if isinstance(m, str) else m for m in modes]
+        for m in modes:
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or int(m) not in (0, 2, 3):
+                raise L.TtsAmdError(f"limit: mode {m!r}: one of 0 / 'off', 2 / 'lufs', 3 / 'gain'")
+        targets = row_values(target, B, 'limit target') if per_row(target) else [target] * B
+        check_finite(targets, 'limit target')
+        if not 0.0 < float(ceiling) <= 1.0:
+            raise L.TtsAmdError(f'limit: ceiling {ceiling!r} is not in (0, 1]')
+        check_finite([max_gain_db], 'limit max_gain_db')
+        attack, hold = limiter_samples(attack_ms, hold_ms, self.sample_rate)
+        if not B:
+            return wave, torch.ones(0, dtype=torch.float32, device=wave.device), torch.zeros(0, dtype=torch.int32, device=wave.device)
+        loud = self.measure(wave, lens)[0] if any(int(m) == 2 for m in modes) else None
+        mode_d = torch.tensor([int(m) for m in modes], dtype=torch.int32).to(wave.device)
+        return self.limit_samples(wave, lens, mode_d, _rows_f32(targets, wave.device), ceiling, 10.0 ** (float(max_gain_db) / 20.0), attack,
+                                  hold, loud)
+
+
+LIMIT_MODES = {'off': 0, 'lufs': 2, 'gain': 3}
+LIMITER_TILE = 2048                     # samples per block of the limiter's second launch (csrc/limiter.hip: LM_T)
+LIMITER_Q = 1 << 30                     # the gain-reduction curve's one: reduction == LIMITER_Q means nothing was limited
+LIMITER_MAX_ATTACK, LIMITER_MAX_HOLD = 1024, 4096
+LIMITER_NO_MAX_GAIN = 3.0e38            # a max_gain that clamps no fp32 gain (utils.audio.limit: the gain is the caller's own)
+LIMITER_DEFAULTS = dict(ceiling=0.99, attack_ms=1.5, hold_ms=15.0, max_gain_db=30.0)
+
+
+def limiter_samples(attack_ms, hold_ms, sample_rate):
+    """(attack, hold) in samples: A = round(attack_ms fs / 1000), R = max(round(hold_ms fs / 1000), A); ValueError outside the kernel's
+    limits (A <= 1024, R <= 4096) or for a negative or non-finite time"""
+    for name, v in (('attack_ms', attack_ms), ('hold_ms', hold_ms)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)) or float(v) < 0:
+            raise ValueError(f'limiter: {name} {v!r}: a finite time in milliseconds, 0 or more')
+    A = int(round(float(attack_ms) * sample_rate / 1000.0))
+    R = max(int(round(float(hold_ms) * sample_rate / 1000.0)), A)
+    if A > LIMITER_MAX_ATTACK or R > LIMITER_MAX_HOLD:
+        raise ValueError(f'limiter: attack of {A} and hold of {R} samples at {sample_rate} Hz: at most {LIMITER_MAX_ATTACK} and {LIMITER_MAX_HOLD}')
+    return A, R
+
+
+def limiter_reach(attack, hold):
+    """samples of input before and after a sample that its limited value depends on: (A + R, 2A)"""
+    return attack + hold, 2 * attack
+
+
+def limiter_spec(limiter):
+    """The `limiter` option of the tts wrappers and the streams -> None (off: None or False) or a dict(ceiling, attack_ms, hold_ms,
+    max_gain_db) with the defaults filled in (True: all defaults).  ValueError for anything else, an unknown key or a bad value."""
+    if limiter is None or limiter is False:
+        return None
+    if limiter is True:
+        return dict(LIMITER_DEFAULTS)
+    if not isinstance(limiter, dict):
+        raise ValueError(f'limiter: {limiter!r}: False, True or a dict with {sorted(LIMITER_DEFAULTS)}')
+    unknown = sorted(set(limiter) - set(LIMITER_DEFAULTS))
+    if unknown:
+        raise ValueError(f'limiter: unknown keys {unknown}: {sorted(LIMITER_DEFAULTS)}')
+    spec = dict(LIMITER_DEFAULTS, **limiter)
+    for name, v in spec.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(float(v)):
+            raise ValueError(f'limiter: {name} {v!r} is not a finite number')
+        spec[name] = float(v)
+    if not 0.0 < spec['ceiling'] <= 1.0:
+        raise ValueError(f"limiter: ceiling {spec['ceiling']!r} is not in (0, 1]")
+    if spec['attack_ms'] < 0 or spec['hold_ms'] < 0:
+        raise ValueError('limiter: attack_ms and hold_ms are 0 or more')
+    return spec
+
+
+def check_limiter(limiter, normalize):
+    """Host-side validation of `limiter` next to `normalize` (already checked): the spec of limiter_spec, or None.  A limiter with no
+    line that asks for a level is a ValueError: it has nothing to work on."""
+    spec = limiter_spec(limiter)
+    if spec is not None and not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
+        raise ValueError("limiter: needs normalize ('lufs' or a target in LUFS on the lines it is to work on)")
+    return spec
+
+
+STOI_BANDS, STOI_SEGMENT = 15, 30                              # third-octave bands, frames per segment (include/ttsamd.h)
 _wavescore_ws = _Workspace()
 
 
@@ -1786,16 +1894,29 @@ def check_normalize(normalize, n_lines):
         level_spec(normalize)
 
 
-def level_waves(wave, nsamples, normalize, sample_rate=22050, ceiling=0.99):
+def level_waves(wave, nsamples, normalize, sample_rate=22050, ceiling=0.99, limiter=None):
     """The levelling step of the tts wrappers, after the denoiser and before the copy to the host: wave [B, n_max] on the device, row b
-    levelled by its option (`normalize`: one option or one per row) over its nsamples[b] samples.  Only None: the wave as it is."""
+    levelled by its option (`normalize`: one option or one per row) over its nsamples[b] samples.  Only None: the wave as it is.
+    limiter (None / False, True or a dict: limiter_spec): the rows with 'lufs' or a target go through the look-ahead limiter
+    (LoudnessEngine.limit in mode 2: the full gain towards the target, the peaks held at the limiter's ceiling) instead of the capped
+    gain; 'peak' and None rows keep their path."""
     rows = list(normalize) if per_row(normalize) else [normalize] * wave.shape[0]
     specs = [level_spec(v) for v in rows]
+    lim = limiter_spec(limiter)
     if not any(s is not None for s in specs):
+        if lim is not None:
+            raise ValueError("limiter: needs normalize ('lufs' or a target in LUFS on the rows it is to work on)")
         return wave
     if len(specs) != wave.shape[0]:
         raise ValueError(f'normalize: {len(specs)} values for {wave.shape[0]} rows')
     shape = wave.shape
     wave = wave.to(torch.float32).reshape(-1, shape[-1]).contiguous()
-    leveller(sample_rate, wave.device).level(wave, nsamples, [s[0] if s else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling)
+    eng = leveller(sample_rate, wave.device)
+    if lim is None:
+        eng.level(wave, nsamples, [s[0] if s else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling)
+        return wave.reshape(shape)
+    if any(s and s[0] == 1 for s in specs):
+        eng.level(wave, nsamples, [1 if s and s[0] == 1 else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling)
+    if any(s and s[0] == 2 for s in specs):
+        eng.limit(wave, nsamples, [2 if s and s[0] == 2 else 0 for s in specs], [s[1] if s else 0.0 for s in specs], **lim)
     return wave.reshape(shape)

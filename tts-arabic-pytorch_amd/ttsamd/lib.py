@@ -160,6 +160,9 @@ SYMBOLS = {
     'ttsamd_loudness_workspace_bytes': (_I64, [_I32, _I64, _I32]),
     'ttsamd_loudness_measure': (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _I64, _P]),
     'ttsamd_wave_level': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _P, _P, _P, _P]),
+    # look-ahead limiter (csrc/limiter.hip): gain fp32 [B] and reduction int32 [B] (Q30) on the device
+    'ttsamd_wave_limit_workspace_bytes': (_I64, [_I32, _I64]),
+    'ttsamd_wave_limit': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _F, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     # wave-against-wave scores (csrc/wavescore.hip): float64 results, lengths int64 on the device
     'ttsamd_stoi_workspace_bytes': (_I64, [_I32, _I64]),
     'ttsamd_stoi': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I64, _P]),

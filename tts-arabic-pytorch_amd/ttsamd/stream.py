@@ -10,7 +10,12 @@ lengths share one chip-filling vocoder call, and audio leaves while the rest is 
 Vocos (MelVocos '22k' / '24k') goes the same way with its own receptive field (`vocos_halo_frames`): its backbone is zero-padded
 convolutions with a per-frame LayerNorm, its head an ISTFT whose frames overlap by three hops.  A step is gather ->
 ttsamd_vocos_forward_windows -> emit; the bias denoise is a per-frame spectral subtraction inside that call (no Denoiser, no halo of its
-own).  The "center" framing of '24k' gives an utterance of T frames 256 (T - 1) samples: `plan_chunks_center` cuts those."""
+own).  The "center" framing of '24k' gives an utterance of T frames 256 (T - 1) samples: `plan_chunks_center` cuts those.
+
+Levelling inside a stream: with `limiter=` a step runs vocoder -> denoise -> ttsamd_wave_limit (mode 3: the stream's fixed gain in dB and
+the look-ahead limiter, in place on the window rows) -> emit.  A limited sample depends on the input over [i - A - R, i + 2A] only, so
+the windows widen by that reach in frames (`limiter_halo_frames`), as they widen by the resampler's, and the curve is integer
+arithmetic: the chunks put together are the bits of utils.audio.limit on the whole wave."""
 import ctypes as C
 
 import numpy as np
@@ -72,6 +77,11 @@ def resample_reach(o, width):
 def resample_halo_frames(o, n, width, hop):
     """resample_reach in frames of hop samples, rounded up: 2 for 22 050 -> 8 000, 16 000 or 32 000 Hz, 1 for 11 025, 24 000, 44 100, 48 000"""
     return -(-resample_reach(o, width) // int(hop))
+
+
+def limiter_halo_frames(attack, hold, hop):
+    """the limiter's reach (A + R samples back, 2A ahead: include/ttsamd.h) in frames of hop samples, rounded up"""
+    return -(-max(int(attack) + int(hold), 2 * int(attack)) // int(hop))
 
 
 def chunk_outputs(core_start, core_end, o, n):
@@ -138,10 +148,11 @@ def max_core_frames(first_chunk_frames, chunk_frames):
 
 
 class _Open:
-    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise', 'frames')
+    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise', 'frames', 'gain_db', 'lim_end')
 
-    def __init__(self, sid, slot, plan, denoise, frames):
-        self.sid, self.slot, self.plan, self.next, self.denoise, self.frames = sid, slot, plan, 0, denoise, frames
+    def __init__(self, sid, slot, plan, denoise, frames, gain_db=0.0):
+        self.sid, self.slot, self.plan, self.next, self.denoise, self.frames, self.gain_db = sid, slot, plan, 0, denoise, frames, gain_db
+        self.lim_end = 0                # samples of the utterance whose value in front of the limiter is settled (see _carry)
 
 
 class StreamingVocoder:
@@ -158,12 +169,20 @@ class StreamingVocoder:
     resampler of utils.audio.resample with lowpass_filter_width and rolloff; encoding: 'float32' (default) | 'pcm16' | 'mulaw' |
     'alaw' (G.711, one byte per sample); pcm16=True means encoding='pcm16'.  Put together, the chunks of a stream are the bits of
     utils.audio.resample on the samples the stream has at the vocoder's rate, encoded.  The vocoder's rate as float32 or PCM16 is the
-    path without a resampler, ttsamd_stream_emit."""
+    path without a resampler, ttsamd_stream_emit.
+
+    limiter (None / False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db: ttsamd.engine.limiter_spec): every
+    window goes through the look-ahead limiter at the vocoder's rate, after the denoiser and before the resampler, with the gain
+    open(gain_db=) gave its utterance (at most max_gain_db); the chunks of a stream are then the bits of utils.audio.limit on the
+    stream's unlimited samples (resampled and encoded as above).  `reduction` holds the last step's smallest curve value per row.
+    `bypass = True` skips the limiter's launch (and with it the gain) and leaves everything else as it is: the same windows, the same
+    vocoder launches, the same samples carried from step to step (`_carry`), so these are, bit for bit, the samples the limiter works
+    on -- for an A / B comparison."""
 
     def __init__(self, vocoder, denoiser=None, max_streams=32, max_frames=4096, chunk_frames=64, first_chunk_frames=32, pcm16=False,
-                 sample_rate=None, encoding=None, lowpass_filter_width=6, rolloff=0.99):
+                 sample_rate=None, encoding=None, lowpass_filter_width=6, rolloff=0.99, limiter=None):
         import torch
-        from .engine import DenoiserEngine
+        from .engine import DenoiserEngine, _Workspace, limiter_samples, limiter_spec
         if min(int(max_streams), int(max_frames), int(chunk_frames), int(first_chunk_frames)) < 1:
             raise ValueError('StreamingVocoder: max_streams, max_frames, chunk_frames and first_chunk_frames must be >= 1')
         source_rate = int(getattr(vocoder, 'sampling_rate', None) or (getattr(vocoder, 'h', None) or {}).get('sampling_rate') or 22050)
@@ -206,6 +225,16 @@ class StreamingVocoder:
             self._rs_eng = _resampler(source_rate, self._sample_rate, lowpass_filter_width, rolloff, 'sinc_interp_hann', dev)
             assert (self._rs_eng.o, self._rs_eng.n, self._rs_eng.width) == self._rs
             self._rs_halo = resample_halo_frames(*self._rs, self.hop)
+        # the limiter (ttsamd_wave_limit, mode 3) between the denoiser and the emit: its reach widens the windows as the resampler's does
+        self._lim = limiter_spec(limiter)
+        self._lim_halo = 0
+        self.bypass = False
+        self.reduction = None           # int32 [rows] on the device after a step with a limiter: min of the curve per window (Q30)
+        if self._lim is not None:
+            self._lim_ar = limiter_samples(self._lim['attack_ms'], self._lim['hold_ms'], source_rate)
+            self._lim_halo = limiter_halo_frames(*self._lim_ar, self.hop)
+            self._lim_ws = _Workspace()
+        self._rs_halo += self._lim_halo         # everything below plans with the sum: the emit reads limited samples
         self._core_cap = max_core_frames(first_chunk_frames, chunk_frames)
         self._w_cap = (self._core_cap + left.value + right.value + 2 * dn_halo + 2 * self._rs_halo + 3) & ~3
         self._rows = min(MAX_WINDOWS, self.max_streams)
@@ -217,6 +246,14 @@ class StreamingVocoder:
         o, n = self._rs[:2] if self._rs else (1, 1)
         self._c_cap = self.hop * self._core_cap if not self._resampled else -(-n * self.hop * self._core_cap // o) + 1
         self._out = [torch.empty(self._rows * self._c_cap, dtype=out_dtype, device=dev) for _ in range(2)]
+        if self._lim is not None:
+            self._lim_gain = torch.empty(self._rows, dtype=torch.float32, device=dev)
+            self._lim_red = [torch.empty(self._rows, dtype=torch.int32, device=dev) for _ in range(2)]
+            self._lim_mode = torch.full((self._rows,), 3, dtype=torch.int32, device=dev)
+            # samples behind / ahead of a core that its chunk depends on through the limiter (and the resampler behind it)
+            rs_reach = resample_reach(self._rs[0], self._rs[2]) if self._rs else 0
+            self._lim_lb, self._lim_la = rs_reach + sum(self._lim_ar), rs_reach + 2 * self._lim_ar[0]
+            self._hist = torch.zeros(self.max_streams, max(self._lim_lb + self._lim_la, 1), dtype=torch.float32, device=dev)
         self._flip = 0
         self._free = list(range(self.max_streams))
         self._open = {}                 # sid -> _Open, in opening order (oldest first)
@@ -245,10 +282,11 @@ class StreamingVocoder:
     def open_streams(self):
         return list(self._open)
 
-    def open(self, mel, denoise=0.0):
+    def open(self, mel, denoise=0.0, gain_db=0.0):
         """mel [num_mels, T] (a device tensor: copied device to device) -> sid.  ValueError: T > max_frames, no free slot, a denoise
         strength that is not finite, denoise > 0 without a denoiser or on an utterance of at most 512 samples (as the one-shot Denoiser).
-        A Vocos vocoder takes any denoise >= 0 on any length; '24k' refuses one frame, as MelVocos.forward does."""
+        A Vocos vocoder takes any denoise >= 0 on any length; '24k' refuses one frame, as MelVocos.forward does.
+        gain_db: the utterance's fixed gain in front of the limiter; a value other than 0 without a limiter is a ValueError."""
         import torch
         mel = torch.as_tensor(mel)
         if mel.dim() != 2 or mel.shape[0] != self.num_mels or mel.shape[1] < 1:
@@ -257,6 +295,11 @@ class StreamingVocoder:
         denoise = float(denoise)
         if not np.isfinite(denoise):
             raise ValueError(f'StreamingVocoder.open: denoise {denoise!r} is not finite')
+        gain_db = float(gain_db)
+        if not np.isfinite(gain_db):
+            raise ValueError(f'StreamingVocoder.open: gain_db {gain_db!r} is not finite')
+        if gain_db != 0.0 and self._lim is None:
+            raise ValueError('StreamingVocoder.open: gain_db needs the limiter (StreamingVocoder(..., limiter=True)): a gain alone could clip')
         if T > self.max_frames:
             raise ValueError(f'StreamingVocoder.open: {T} frames, the pool holds utterances of up to max_frames = {self.max_frames}')
         if self._vocos:
@@ -279,8 +322,41 @@ class StreamingVocoder:
         self._pool[slot, :, :T].copy_(mel.to(dtype=torch.float32), non_blocking=True)
         sid = self._next_sid
         self._next_sid += 1
-        self._open[sid] = _Open(sid, slot, plan, denoise, T - 1 if self._center else T)        # frames of hop samples
+        self._open[sid] = _Open(sid, slot, plan, denoise, T - 1 if self._center else T, gain_db)        # frames of hop samples
         return sid
+
+    def _carry(self, rows, chunks, w_max):
+        """The vocoder's fp32 sums for one sample differ in their last bits from window to window, and the limiter's curve at a chunk's
+        edge depends on samples of the neighbouring cores.  So that the chunks are the limiter's bits on ONE wave, a sample's value in
+        front of the limiter is settled by the first window that has to provide it: step k settles [end of step k - 1, core end + la)
+        from its window and takes what lies before from the utterance's history (the last lb + la settled samples, kept per slot),
+        copied over the window row; then the history moves on.  Two index copies per step; the cores read behind this (with `bypass`,
+        as they are) are that one wave."""
+        import torch
+        H, hop = self._lim_lb + self._lim_la, self.hop
+        if H == 0:
+            return
+        stride = hop * w_max
+        put_w, put_h, get_w, get_h = [], [], [], []
+        for w, (st, c) in enumerate(zip(rows, chunks)):
+            w0, end, prev = hop * c[2], min(hop * (c[0] + c[1]) + self._lim_la, hop * st.frames), st.lim_end
+            lo = max(prev - H, w0, 0)
+            if prev > lo:                   # history -> window row
+                pos = np.arange(lo, prev, dtype=np.int64)
+                put_w.append(w * stride + pos - w0)
+                put_h.append(st.slot * H + pos - (prev - H))
+            lo = max(end - H, w0, 0)
+            if end > lo:                    # window row -> history, right-aligned at `end`
+                pos = np.arange(lo, end, dtype=np.int64)
+                get_w.append(w * stride + pos - w0)
+                get_h.append(st.slot * H + pos - (end - H))
+            st.lim_end = end
+        up = lambda parts: torch.from_numpy(np.concatenate(parts)).pin_memory().to(self.device, non_blocking=True)      # noqa: E731
+        hist = self._hist.view(-1)
+        if put_w:
+            self._wave[up(put_w)] = hist[up(put_h)]
+        if get_w:
+            hist[up(get_h)] = self._wave[up(get_w)]
 
     def close(self, sid):
         """Drop an open utterance (its remaining chunks are not made) and free its slot.  KeyError for a sid that is not open."""
@@ -342,6 +418,22 @@ class StreamingVocoder:
                     dws = self._dn_eng.ws.get(nb, self.device)
                     L.check(lib.ttsamd_denoise_rows(self._dn_eng.handle, _ptr(self._wave), n_max, _ptr(nsamples), W, n_max, _ptr(self._bias),
                                                     _ptr(strength), _ptr(dws), nb, _stream()), 'denoise_rows')
+            if self._lim is not None:
+                self._carry(rows, chunks, w_max)
+            if self._lim is not None and not self.bypass:
+                # mode 3 in place on the window rows, over the samples the vocoder made: a HiFi-GAN window whole, a Vocos window up to
+                # the end of what its head ran on (what lies in front of that range is outside the reach of every sample the emit reads)
+                ends = [self.hop * (nd[1] if self._vocos else c[3]) for nd, c in zip(need if self._vocos else chunks, chunks)]
+                ends_d = torch.tensor(ends, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+                gains_d = torch.tensor([st.gain_db for st in rows], dtype=torch.float32).pin_memory().to(self.device, non_blocking=True)
+                n_max = self.hop * w_max
+                nb = lib.ttsamd_wave_limit_workspace_bytes(W, n_max)
+                lws = self._lim_ws.get(max(nb, 1), self.device)
+                self.reduction = self._lim_red[self._flip][:W]
+                L.check(lib.ttsamd_wave_limit(_ptr(self._wave), n_max, _ptr(ends_d), W, _ptr(self._lim_mode), _ptr(gains_d),
+                                              float(self._lim['ceiling']), 10.0 ** (self._lim['max_gain_db'] / 20.0), self._lim_ar[0],
+                                              self._lim_ar[1], None, _ptr(self._lim_gain), _ptr(self.reduction), _ptr(lws), nb, _stream()),
+                        'wave_limit')
             if self._resampled:
                 hop = self.hop
                 L.check(lib.ttsamd_stream_emit_resampled(self._rs_eng.handle if self._rs_eng else None, _ptr(self._wave), W, w_max, hop,

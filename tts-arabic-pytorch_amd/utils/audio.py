@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from ttsamd import melfb
 from ttsamd.engine import MelSpecEngine, ResampleEngine, TrimEngine
+from ttsamd.engine import LIMITER_NO_MAX_GAIN, LIMITER_Q, check_finite, limiter_samples, limiter_spec, per_row, row_values
 from ttsamd.engine import leveller as _leveller
 from ttsamd.lib import TtsAmdError
 
@@ -262,11 +263,47 @@ def _level(wave, lens, sample_rate, mode, target, ceiling, what):
 
 
 @torch.inference_mode()
-def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None):
+def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None, limiter=False):
     """Every row of wave [..., n] scaled by ONE gain to target_lufs (a float or one per row); where that would lift the row's peak
     above peak_ceiling, the gain is ceiling / peak instead (a cap on the gain, no limiter).  A silent row is returned as it is.  A new
-    tensor on the device; the samples behind lens[row] are copied unchanged."""
-    return _level(wave, lens, sample_rate, 2, target_lufs, peak_ceiling, 'normalize_loudness')
+    tensor on the device; the samples behind lens[row] are copied unchanged.
+    limiter (True, or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db): the full gain towards the target instead, and the
+    look-ahead limiter (`limit`) holds the peaks at the ceiling (peak_ceiling unless the dict names one), so the target is reached."""
+    spec = limiter_spec(limiter)
+    if spec is None:
+        return _level(wave, lens, sample_rate, 2, target_lufs, peak_ceiling, 'normalize_loudness')
+    if not (isinstance(limiter, dict) and 'ceiling' in limiter):
+        spec['ceiling'] = peak_ceiling
+    x, lens = _level_rows(wave, lens, 'normalize_loudness')
+    if x.data_ptr() == wave.data_ptr():
+        x = x.clone()
+    out, _, _ = _leveller(sample_rate, x.device).limit(x, lens, 2, target_lufs, **spec)
+    return out.reshape(wave.shape)
+
+
+@torch.inference_mode()
+def limit(wave, gain_db=0.0, ceiling=0.99, attack_ms=1.5, hold_ms=15.0, sample_rate=22050, lens=None):
+    """A fixed gain and the look-ahead limiter (include/ttsamd.h states the arithmetic): every row of wave [..., n] times 10^(gain_db /
+    20) (a float or one per row), then a gain-reduction curve in Q30 integers that looks attack_ms ahead, holds hold_ms and keeps
+    |y| <= ceiling exactly; samples that no peak reaches are fl32(x g) bit for bit.  -> (a new tensor on the device, reduction_db
+    float64 [rows] on the device: the deepest gain reduction in dB, 0 where nothing was limited).  The samples behind lens[row] are copied
+    unchanged.  This is what a stream with `limiter=` applies to its windows: the concatenated chunks have the bits of this call on the
+    whole wave."""
+    x, lens = _level_rows(wave, lens, 'limit')
+    if x.data_ptr() == wave.data_ptr():
+        x = x.clone()
+    if not 0.0 < float(ceiling) <= 1.0:
+        raise ValueError(f'limit: ceiling {ceiling!r} is not in (0, 1]')
+    B = x.shape[0]
+    gains = row_values(gain_db, B, 'limit gain_db') if per_row(gain_db) else [gain_db] * B
+    check_finite(gains, 'limit gain_db')
+    attack, hold = limiter_samples(attack_ms, hold_ms, sample_rate)
+    eng = _leveller(sample_rate, x.device)
+    lens_d = torch.full((B,), x.shape[1], dtype=torch.int64, device=x.device) if lens is None else lens
+    mode = torch.full((B,), 3, dtype=torch.int32, device=x.device)
+    target = torch.tensor([float(v) for v in gains], dtype=torch.float32).to(x.device)
+    out, _, red = eng.limit_samples(x, lens_d, mode, target, ceiling, LIMITER_NO_MAX_GAIN, attack, hold)
+    return out.reshape(wave.shape), 20.0 * torch.log10(red.to(torch.float64) / float(LIMITER_Q))
 
 
 @torch.inference_mode()
