@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from recurrent_ref import _gate_for_stops
+
 pytestmark = pytest.mark.gpu
 
 MEL_TOL = 1e-3
@@ -78,29 +80,6 @@ def test_tacotron2_single_speaker_model(dev):
     mel_ref, _, al_ref = T.tacotron2_infer(sd, cfg, tok, None, lens, max_step=10, seed=-1)
     mel, _, al = Tacotron2Engine(sd, cfg, device=dev).infer(tok, None, lens, max_step=10, dropout_seed=-1)
     assert maxabs(mel, mel_ref) < MEL_TOL and maxabs(al, al_ref) < ALIGN_TOL
-
-
-def _gate_for_stops(cfg, sd, tok, sids, lens, stops, max_step, seed):
-    """Synthetic gates barely move in time, so fit (ridge, dual form) a gate layer whose logit is -2 before
-    utterance b's chosen stop step and +2 from it on.  The trajectory before a stop does not depend on the
-    gate, so a traced never-stopping run provides the layer's inputs; with the prenet dropout on they differ
-    enough from step to step that the fit needs only O(1) weights (margin 2 vs ~1e-3 of fp32 noise)."""
-    import taco_oracle as T
-    tr = {}
-    T.tacotron2_infer(sd, cfg, tok, sids, lens, max_step=max_step, seed=seed, trace=tr)
-    hc = torch.stack(tr['hc']).double()                                   # [T, B, D+M]
-    rows, tgt = [], []
-    for b, stop in enumerate(stops):
-        for t in range(max_step):
-            rows.append(hc[t, b])
-            tgt.append(2.0 if t >= stop - 1 else -2.0)
-    H, y = torch.stack(rows), torch.tensor(tgt, dtype=torch.float64)
-    w = H.T @ torch.linalg.solve(H @ H.T + 1e-6 * torch.eye(len(y), dtype=torch.float64), y)
-    assert float(((H @ w) * y).min()) > 1.0 and float(w.abs().sum()) < 5e3
-    out = dict(sd)
-    out['decoder.gate_layer.weight'] = w[None].float().numpy().copy()
-    out['decoder.gate_layer.bias'] = np.zeros(1, np.float32)
-    return out
 
 
 def test_tacotron2_stop_token(dev):

@@ -164,6 +164,10 @@ struct ConvParams {
     unsigned long long* timing;   // unused (nullptr); kept so the kernel argument layout is unchanged
     const float* w_wino44; // k = 7 / 11: the same conv as SEVEN-point groups [Cin/8][wino44_groups(k)][2][CoutP][4] (conv_wino4.hip, TTSAMD_WINO4 bits 5 / 6;
                            // nullptr = none: the launch stays on w_wino4).  Both forms travel with a launch, the switch picks one per launch
+    int32_t res_late;      // direct kernels: 1 = add the residual behind the finished sum, never preload it into the accumulators.  A preloaded
+                           // residual makes every rounding of the Cin * K sum as large as the residual's: fine where conv and residual are of
+                           // one size (ResBlocks, FFT blocks), ten times the fp32 noise where the residual is the output and the conv a small
+                           // correction to it (Tacotron2 postnet: mel + postnet(mel), 2560 terms)
 };
 constexpr int64_t kSplitKFloats = 4 << 20;   // 16 MB covers every case the launchers pick (direct kernel: < 320 blocks, ~640 blocks wanted; conv_wino4.hip: four C-in slices of a 1 x 256 x 3584 launch = 3.7 M floats)
 constexpr int64_t kSplitKFloatsFp = 8 << 20; // FastPitch: 32 MB, the deep conv-FF conv (1536 -> 384) splits K at batch 4..13 too

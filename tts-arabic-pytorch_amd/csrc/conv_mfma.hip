@@ -595,7 +595,7 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     TTS_REQUIRE(p.relu_out < 2 || K == 1 || K == 5, "conv: GELU / tanh epilogues are built for kernel sizes 1 and 5 only (K=%d)", K);
     // the residual rides in through the accumulators (EPI 3) unless a per-channel scale sits between conv and residual
     // (Vocos gamma) or the kernel was built without it
-    const bool pre_ok = p.res != nullptr && p.scale == nullptr && p.relu_out < 2 &&
+    const bool pre_ok = p.res != nullptr && !p.res_late && p.scale == nullptr && p.relu_out < 2 &&
                         (int64_t)p.Cout * std::max(p.r_cs, p.y_cs) * 4 < ((int64_t)1 << 31);
     const int epi = !vec_ok ? 2 : (p.relu_out >= 2 ? 1 : (pre_ok ? 3 : 0));
     int32_t rc;

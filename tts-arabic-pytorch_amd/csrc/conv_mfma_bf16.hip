@@ -458,7 +458,7 @@ static int32_t launch_cfg_bf16(const ConvParams& p_in, hipStream_t stream) {
                         ((uintptr_t)p.y & 15) == 0 &&
                         (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0));
     const bool act = HAS_ACT && p.relu_out >= 2;
-    const bool pre_ok = p.res != nullptr && p.scale == nullptr && p.relu_out < 2 &&
+    const bool pre_ok = p.res != nullptr && !p.res_late && p.scale == nullptr && p.relu_out < 2 &&
                         (int64_t)p.Cout * std::max(p.r_cs, p.y_cs) * 4 < ((int64_t)1 << 31);
     if (vec_ok) {
         if (act) return launch_act_bf16<K, MT, NTL, WM, WN, NPL, 0, HAS_ACT>(p, grid, lds, stream);

@@ -338,9 +338,14 @@ __global__ __launch_bounds__(128) void taco_pm_kernel(const float* __restrict__ 
                                                       int L, int M, float* __restrict__ pm) {
     const int b = blockIdx.y, t = blockIdx.x, hh = threadIdx.x;
     const float* mr = memory + ((int64_t)b * L + t) * M;
-    float acc = 0.f;
-    for (int m = 0; m < M; ++m) acc = fmaf(mr[m], wmT[(int64_t)m * 128 + hh], acc);
-    pm[((int64_t)b * L + t) * 128 + hh] = acc;
+    // eight partial sums (M = 512 / 640), added pairwise: one chain of M fmas rounds the whole sum M times, and pm feeds every step's energies
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int m = 0; m + 8 <= M; m += 8) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(mr[m + i], wmT[(int64_t)(m + i) * 128 + hh], acc[i]);
+    }
+    for (int m = M & ~7; m < M; ++m) acc[0] = fmaf(mr[m], wmT[(int64_t)m * 128 + hh], acc[0]);
+    pm[((int64_t)b * L + t) * 128 + hh] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
 }
 
 __device__ __forceinline__ float taco_keep(unsigned seed, unsigned layer, unsigned step, unsigned b, unsigned j) {
@@ -1823,8 +1828,14 @@ int64_t tacotron2_workspace_bytes(const Taco2* h, int32_t B, int32_t L, int32_t 
     return a.off;
 }
 
+// `slices` > 1 (fp32 only): the Cin range goes through in that many launches, each adding its partial sum to y (mode 1; the bias rides with
+// the first).  The direct kernel keeps ONE fp32 accumulator over all Cin * K terms (conv_mfma.hip: acc = mfma(a, b, acc)), so the rounding
+// error of a 2560-term sum grows like sqrt(1280) roundings of the whole sum; in slices of 32 channels it is sqrt(80) roundings of a
+// sixteenth of it plus sixteen of the whole.  The encoder output feeds every decoder step, and the attention of a short row beside long ones
+// amplifies its error step by step (profiles/r32/NOTES.md: 14 times the float32 reference's own error after 20 steps, 4 to 5 with slices).
+// A sliced conv cannot apply an activation: its consumer does, on load (in_slope 0 = ReLU).
 static int32_t tconv(const Taco2* h, const TConv& c, const float* x, int64_t x_bs, int x_cs, float* y, int64_t y_bs,
-                     int y_cs, const float* res, int B, int T, int act, hipStream_t s) {
+                     int y_cs, const float* res, int B, int T, int act, hipStream_t s, float in_slope = 1.f, int slices = 1) {
     ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.x = x; p.x_bs = x_bs; p.x_cs = x_cs;
@@ -1832,11 +1843,24 @@ static int32_t tconv(const Taco2* h, const TConv& c, const float* x, int64_t x_b
     p.w_bf16 = h->dev16 + c.w16_off; p.precision = default_precision();
     p.y = y; p.y_bs = y_bs; p.y_cs = y_cs; p.y_ts = 1;
     p.res = res; p.r_bs = y_bs; p.r_cs = y_cs;
+    p.res_late = 1;                                             // postnet: mel + a small correction (ConvParams::res_late)
     p.len_in_mul = 1; p.len_out_mul = 1; p.Lin = T; p.Nout = T;
     p.Cin = c.cin; p.Cout = c.cout; p.CoutP = cout_padded(c.cout); p.K = c.k;
-    p.dil = 1; p.pad = c.k / 2; p.n_phase = 1; p.in_slope = 1.f; p.relu_out = act; p.mode = 0; p.div = 1.f; p.batch = B;
+    p.dil = 1; p.pad = c.k / 2; p.n_phase = 1; p.in_slope = in_slope; p.relu_out = act; p.mode = 0; p.div = 1.f; p.batch = B;
+    if (p.precision != 0) slices = 1;                           // the bf16 planes are addressed through the whole Cin
+    TTS_REQUIRE(slices == 1 || (act == 0 && res == nullptr && c.cin % (8 * slices) == 0), "tacotron2: conv %d -> %d cannot go in %d slices",
+                c.cin, c.cout, slices);
+    const int cs = c.cin / slices;
     prof_begin(s, 2.0 * c.cout * c.cin * c.k);
-    const int32_t rc = launch_conv(p, s);
+    int32_t rc = 0;
+    for (int i = 0; i < slices && rc == 0; ++i) {
+        ConvParams q = p;
+        q.x = x + (int64_t)i * cs * x_cs;
+        q.w = p.w + (int64_t)i * (cs / 8) * c.k * 2 * p.CoutP * 4;          // packed [Cin / 8][K][2][CoutP][4]
+        q.Cin = cs;
+        if (i > 0) { q.bias = nullptr; q.mode = 1; }
+        rc = launch_conv(q, s);
+    }
     prof_end(s);
     return rc;
 }
@@ -1883,11 +1907,14 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
     hipLaunchKernelGGL(taco_embed_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, tokens, W + h->emb, h->cfg.n_symbol, E, L, w.x0);
     TTS_CHECK_HIP(hipGetLastError());
     float *cur = w.x0, *nxt = w.x1;
+    // conv + BatchNorm (folded) in slices of 32 input channels (tconv); the ReLU behind each is applied by its consumer on load
+    float enc_slope = 1.f;
     for (const TConv& cv : h->enc_convs) {
-        TTS_TRY(tconv(h, cv, cur, (int64_t)E * L, L, nxt, (int64_t)E * L, L, nullptr, B, L, 1, s));
+        TTS_TRY(tconv(h, cv, cur, (int64_t)E * L, L, nxt, (int64_t)E * L, L, nullptr, B, L, 0, s, enc_slope, cv.cin / 32));
         std::swap(cur, nxt);
+        enc_slope = 0.f;
     }
-    TTS_TRY(tconv(h, h->enc_xproj, cur, (int64_t)E * L, L, w.xproj, (int64_t)4 * E * L, L, nullptr, B, L, 0, s));
+    TTS_TRY(tconv(h, h->enc_xproj, cur, (int64_t)E * L, L, w.xproj, (int64_t)4 * E * L, L, nullptr, B, L, 0, s, enc_slope, E / 32));
     TTS_CHECK_HIP(hipMemsetAsync(w.memory, 0, (size_t)B * L * M * sizeof(float), s));
     hipLaunchKernelGGL(taco_bilstm_kernel, dim3(B, 2), dim3(256), 0, s, w.xproj, W + h->enc_whhT[0], W + h->enc_whhT[1],
                        lengths, L, M, w.memory);

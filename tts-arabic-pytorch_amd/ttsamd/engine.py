@@ -588,9 +588,10 @@ class Tacotron2Engine:
             self.lib.ttsamd_tacotron2_destroy(self.handle)
             self.handle = None
 
-    def infer(self, tokens, speaker_ids=None, lengths=None, max_step=None, dropout_seed=-1):
+    def infer(self, tokens, speaker_ids=None, lengths=None, max_step=None, dropout_seed=-1, return_raw=False):
         """tokens int64 [B,L] -> (mel_postnet [B,80,T], mel_lens int32 [B], alignments [B,T,L]);
-        dropout_seed None draws a fresh seed per call (the reference's always-on prenet dropout)."""
+        dropout_seed None draws a fresh seed per call (the reference's always-on prenet dropout);
+        return_raw=True appends the decoder's frames before the postnet, mel_raw [B,80,T]."""
         _check_ids(tokens, self.config['n_symbol'], 'Tacotron2 tokens')
         if speaker_ids is not None and self.config['num_speakers'] > 1:
             _check_ids(speaker_ids, self.config['num_speakers'], 'Tacotron2 speaker_ids')
@@ -621,6 +622,8 @@ class Tacotron2Engine:
                                                     _ptr(align), _ptr(mel_raw), C.byref(n_steps), _ptr(ws), nb,
                                                     _stream()), 'tacotron2_infer')
         T = n_steps.value
+        if return_raw:
+            return mel_post[:, :, :T], mel_lens, align[:, :T], mel_raw[:, :, :T]
         return mel_post[:, :, :T], mel_lens, align[:, :T]
 
 
