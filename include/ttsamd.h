@@ -650,7 +650,8 @@ int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, 
                              void* stream);
 /* What the calling thread's last fp32 conv launch decided (ttsamd_conv1d*, ttsamd_conv_transpose1d, or the last conv of a model forward
  * on this thread): *route = 0 direct kernel, 1 / 2 the two Winograd F(2,3) kernels, 3 / 4 Winograd F(4,3) on six- / seven-point groups,
- * 5 the all-phase transposed conv, 6 the transposed conv as a two-tap conv on Winograd F(4,2); *ksplit = its input-channel slices (1 = not split).  -1 / 0 before the first launch.  Host state of
+ * 5 the all-phase transposed conv, 6 the transposed conv as a two-tap conv on Winograd F(4,2), 7 / 8 Winograd F(4,3) on six- / seven-point
+ * groups in the packed strip form (dilation 3 / 5, one C-in slice, no residual, mode 0; TTSAMD_WINO4 bit 7); *ksplit = its input-channel slices (1 = not split).  -1 / 0 before the first launch.  Host state of
  * the thread only: nothing is read from the device.  The bf16 engines and the fused ResBlock launches do not record. */
 int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit);
 /* One HiFi-GAN upsampler (vocoder/hifigan/models.py:96-99, 114-115) as the generator runs it: y = conv_transpose1d(lrelu_slope(x), w,

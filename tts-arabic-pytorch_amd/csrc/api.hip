@@ -265,8 +265,9 @@ bool opt_valid(const OptDesc& d, const char* v) {
     const long long x = std::strtoll(v, &end, d.kind == 1 ? 16 : 10);
     if (!(errno == 0 && end != v && *end == '\0' && x >= d.lo && x <= d.hi)) return false;
     // TTSAMD_WINO4 bits 5 / 6 say HOW the F(4,3) kernel runs k = 7 / 11 (seven-point groups): without bit 1 / 2 it does not run that k at
-    // all and the mask contradicts itself -- an error like any malformed value, not a bit that is quietly ignored
-    if (&d == &kOpts[OPT_WINO4] && (((x & 32) && !(x & 2)) || ((x & 64) && !(x & 4)))) return false;
+    // all and the mask contradicts itself -- an error like any malformed value, not a bit that is quietly ignored.  Bit 7 says how it runs
+    // the dilated launches (packed tiles, register epilogue): the same without bit 3
+    if (&d == &kOpts[OPT_WINO4] && (((x & 32) && !(x & 2)) || ((x & 64) && !(x & 4)) || ((x & 128) && !(x & 8)))) return false;
     return true;
 }
 void opt_init() {

@@ -63,7 +63,7 @@ inline hipError_t lds_opt_in(const void* fn, int bytes, std::atomic<uint64_t>& d
     X(HIFIGAN_STREAMS, 0, 0, 1)   /* ResBlock branches of a HiFi-GAN stage on one / three streams (default: by size) */ \
     X(WINO, 0, 0, 1)              /* fp32 engine: 0 = direct kernels only */                                \
     X(WINO2, 0, 0, 31)            /* F(2,3) decomposition kernel: bit 0 / 1 / 2 = k 3 / 7 / 11, 3 = dilated, 4 = Cout 64 */ \
-    X(WINO4, 0, 0, 127)           /* F(4,3) decomposition kernel: bit 0 / 1 / 2 = k 3 / 7 / 11, 3 = dilated, 4 = k 1, 5 / 6 = k 7 / 11 on seven-point groups */ \
+    X(WINO4, 0, 0, 255)           /* F(4,3) decomposition kernel: bit 0 / 1 / 2 = k 3 / 7 / 11, 3 = dilated, 4 = k 1, 5 / 6 = k 7 / 11 on seven-point groups, 7 = packed tiles + register epilogue of the dilated launches */ \
     X(FUSED_PAIR, 0, 0, 1)        /* fp32 fused c1 -> c2 pairs: 0 = every pair as two launches */           \
     X(FUSED2, 0, 0, 1)            /* second-generation fused pair off / on */                               \
     X(FUSED2_MASK, 1, 0, 0x1ff)   /* which (C, k) pairs it takes: bit 3 ci + ki (default 00f) */            \
@@ -181,7 +181,8 @@ int32_t launch_conv(const ConvParams& p, hipStream_t stream);
 // What the calling thread's last fp32 conv launch decided (ttsamd_conv_last_launch; conv_mfma.hip): two thread_local ints, written by
 // the launcher that takes the decision.  route 0: direct kernel, 1 / 2: the F(2,3) kernels (conv_wino.hip / conv_wino2.hip), 3 / 4: F(4,3)
 // on six- / seven-point groups, 5: the all-phase transposed conv (convt_mfma.hip), 6: the transposed conv as a two-tap conv on F(4,2)
-// (launch_convt_wino, conv_wino4.hip).  Host only, no atomics.
+// (launch_convt_wino, conv_wino4.hip), 7 / 8: F(4,3) on six- / seven-point groups in the PACKED strip form (dilation 3 / 5, packed tiles and
+// the register epilogue: conv_wino4.hip EPI 7, TTSAMD_WINO4 bit 7).  Host only, no atomics.
 void note_conv_launch(int32_t route, int32_t ksplit);
 void last_conv_launch(int32_t* route, int32_t* ksplit);
 // ConvTranspose1d with all output phases per wave (convt_mfma.hip): takes the polyphase ConvParams of the generic engine
@@ -250,9 +251,20 @@ void pack_wino2_weight(const float* w, int cout, int cin, int k, float* out);   
 // ... and the F(4,3) decomposition (conv_wino4.hip: 6 / 16 / 23 products per output QUAD at k = 3 / 7 / 11): 64 rows x 64 quads per block
 int wino4_groups(int k);                         // groups per octet in the packed weights: 6 / 16 / 24 (k = 11: 23 + one zero group)
 int wino44_groups(int k);                        // ... of the seven-point form: 13 / 20 at k = 7 / 11 (0: no such form)
-constexpr int kWino4Default = 127;               // TTSAMD_WINO4 when unset
+constexpr int kWino4Default = 255;               // TTSAMD_WINO4 when unset
 bool wino44_wanted(const ConvParams& p);         // the launch goes to the seven-point groups (has them, and its k's bit is set)
 int wino4_block_outputs(int dil);
+// PACKED tiles of the dilated F(4,3) launches (conv_wino4.hip, EPI 7).  A row of n outputs at dilation d is cut into G = ceil(n / 4d)
+// groups of 4 d columns = T = d G tuples; tuple t holds the columns (t / d) 4d + t % d + j d, j = 0..3, and tile i the tuples
+// [64 i, 64 i + 64): every tuple slot of every tile but a row's last is live (the plain tile -- the largest multiple of 4 d columns in
+// 256 -- leaves 1 of 64 slots idle at d = 3 and 4 at d = 5).  A tile then starts at residue r0 = 64 i % d inside its first group, which
+// begins at column q0 = (64 i / d) 4d, and slot pe of the tile sits at q0 + wino4_pk_col(r0 + pe, d).  The launcher (grid), the kernel
+// (block -> tile) and live_tile below all count tiles with these; at d = 1 the map is the plain one.
+__host__ __device__ constexpr int wino4_pk_tuples(int n, int d) { return d * ((n + 4 * d - 1) / (4 * d)); }
+__host__ __device__ constexpr int wino4_pk_tiles(int n, int d) { return (wino4_pk_tuples(n, d) + 63) / 64; }
+__host__ __device__ constexpr int wino4_pk_col(int t, int d) { return (t / d) * 4 * d + t % d; }      // first column of tuple t
+__host__ __device__ constexpr int wino4_pk_q0(int tile, int d) { return (64 * tile / d) * 4 * d; }
+__host__ __device__ constexpr int wino4_pk_r0(int tile, int d) { return 64 * tile % d; }
 int wino4_ksplit(const ConvParams& p);           // C-in slices the launcher will use for this launch (1 = none)
 int32_t launch_splitk_reduce(const ConvParams& q, hipStream_t stream);   // conv_mfma.hip: y = epilogue(sum of the ksplit partial tensors)
 int32_t launch_wino4(const ConvParams& p, hipStream_t stream);
@@ -282,9 +294,10 @@ int32_t default_precision();
 // (A persistent variant -- as many blocks as the chip holds, tiles handed out by a device counter -- measured 1-3 %
 // BELOW this on the ragged launches and 3-4 % below the plain grid on uniform ones; not kept.)
 // EXTRA = 1 (the transposed conv on the F(4,2) kernel, conv_wino4.hip): a row of length len > 0 has len + 1 positions, one of length 0 none.
-template <int EXTRA = 0>
+// PK_DIL > 0 at run time (PACKED only: the packed tiles above at that dilation): a row has wino4_pk_tiles(len, PK_DIL) tiles; tile_w is unused.
+template <int EXTRA = 0, bool PACKED = false>
 __device__ __forceinline__ bool live_tile(const int64_t* __restrict__ lens, const int mul, const int n_max, const int tile_w,
-                                          const int batch, const unsigned lin, int& b, int& tile) {
+                                          const int batch, const unsigned lin, int& b, int& tile, const int pk_dil = 0) {
     const int lane = threadIdx.x & 63;
     unsigned base = 0;
     for (int u0 = 0; u0 < batch; u0 += 64) {
@@ -294,6 +307,8 @@ __device__ __forceinline__ bool live_tile(const int64_t* __restrict__ lens, cons
                 const int len = (int)lens[u0 + lane] * mul;
                 n = (max(min(n_max, len > 0 ? len + EXTRA : 0), 0) + tile_w - 1) / tile_w;
             }
+        } else if constexpr (PACKED) {
+            if (u0 + lane < batch) n = wino4_pk_tiles(max(min(n_max, (int)lens[u0 + lane] * mul), 0), pk_dil);
         } else {
             if (u0 + lane < batch) n = (max(min(n_max, (int)lens[u0 + lane] * mul), 0) + tile_w - 1) / tile_w;
         }

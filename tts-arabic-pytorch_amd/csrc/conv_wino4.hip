@@ -36,7 +36,7 @@
 // fragment per octet (the direct engine's packed weights as they are) feeds 16 MFMAs, the epilogue also knows GELU / tanh / the per-row
 // factor of the direct kernel.  Same products in the same order as conv1d_mfma_f32<1>; 251 / 217 vs 263 / 233 us on Vocos' two GEMMs
 // (512 <-> 1536 rows x 15 872 frames: matrix pipe 65 / 75 % busy against 61 / 70 %), Vocos at batch 32 4.99 -> 4.67 ms.
-// EPILOGUES.  EPI 0 (strip kernels, C-in slices, k = 1): the output transform goes through the dead ring (64 KB + the bias, two barriers)
+// EPILOGUES.  EPI 0 (C-in slices, k = 1, the strip kernels where EPI 7 below does not apply): the output transform goes through the dead ring (64 KB + the bias, two barriers)
 // and leaves as whole rows -- the row epilogue of conv_mfma.hip.  EPI 3 / 4 (every other dilation-1 launch, with / without a residual):
 // the REGISTER epilogue.  After the output transform a lane holds y0..y3 of one quad for 16 rows, and for a fixed accumulator row a wave
 // covers two rows x 32 adjacent quads = two runs of 512 bytes, so the rows are stored straight from registers: no barrier and no LDS
@@ -49,6 +49,20 @@
 // at a time (four with eight planes), in front of those rows' transform.  (Before round 23 the residual was PRELOADED into planes that
 // reach one output each, two of them extra: 16-32 loads per lane in front of the weight queue and the first window, in a queue that
 // returns in order, with no MFMA beside them -- 798 against 733 us on the k = 7 launches at C = 128 / 64; profiles/r23/NOTES.md.)
+// EPI 7 (round 33; TTSAMD_WINO4 bit 7, default on): the PACKED STRIP FORM of the dilated launches with one C-in slice, no residual and
+// mode 0 -- HiFi-GAN's c1 convs, bias and ReLU only.  (a) Packed tiles.  The plain strip tile is the largest multiple of 4 d columns in
+// 256: 63 / 60 of the block's 64 quad slots at d = 3 / 5, the idle ones repeat the last tuple -- MFMAs issued, never stored (1.6 / 6.25 %
+// of all products, and as many blocks more).  Packed: a row of n outputs is T = d ceil(n / 4d) tuples, tile i = tuples [64 i, 64 i + 64),
+// which start at residue r0 = 64 i % d of the group at column q0 = (64 i / d) 4d; slot pe at q0 + ((r0 + pe) / d) 4d + (r0 + pe) % d
+// (common.hpp: wino4_pk_*, one constexpr map for the grid, the block -> tile map and live_tile; static_assert'ed below to cover every
+// column once).  A tile's slots reach at most column 262 of its first group (d = 5), so the strip is 332 positions at k = 11 and 320
+// otherwise (Wino4Geo::strip_need).  (b) The register epilogue with the peeled last step of EPI 4: the bias arrives under the peeled
+// step's MFMAs, the lane's y0..y3 of a row go to the columns q, q + d, q + 2 d, q + 3 d as four dword stores checked against the row's
+// length -- the d lanes of a group fill 4 d consecutive floats between them --, no barrier and no LDS behind the loop: ring + strip set
+// the LDS size.  Same products in the same order, same output transform and bias / ReLU order: the bits of EPI 0
+// (tests/test_gpu_wino4_strip_packed.py).  C-in slices, a residual and the accumulate modes keep EPI 0.  The strip's activation-and-store
+// job (8 VALU + one 16-byte LDS write per gap, four per step) is NOT cut in two: one more gap per job leaves 17 gaps for the 20 write
+// jobs of k = 7 and 11 for the 12 of k = 3 (wst() = 0); only k = 11 would fit.  Measurements: profiles/r33/NOTES.md.
 #include <cstdlib>
 #include <cstring>
 
@@ -103,8 +117,10 @@ typedef float w4_f32x2 __attribute__((ext_vector_type(2)));
 // CT_ = u (8 / 2): the TRANSPOSED conv of stride u, kernel 2u, padding u/2 as a two-tap Conv1d with u Cout rows (the note in front of
 // launch_convt_wino below): k = 3 with g2 = 0, so U5 = 0 is never multiplied (NG = 5 of the NGQ = 6 packed groups) and x5 is never read
 // (a window of five positions = two 16-byte vectors per lane).
-template <int K, int NOCT_, int NSTAGE_, int PT_ = 6, int LP_ = 1, int CT_ = 0>
+// PK_ = 1 (EPI 7): the PACKED strip form -- packed tiles (common.hpp: wino4_pk_*), whose tuples reach further right in the strip.
+template <int K, int NOCT_, int NSTAGE_, int PT_ = 6, int LP_ = 1, int CT_ = 0, int PK_ = 0>
 struct Wino4Geo {
+    static_assert(PK_ == 0 || LP_ == 2, "packed tiles: the strip kernels");
     static constexpr bool PT7 = PT_ == 7;
     static_assert(PT_ == 6 || (PT7 && (K == 7 || K == 11)), "seven-point groups: k = 7 / 11");
     static_assert(CT_ == 0 || (K == 3 && PT_ == 6 && LP_ == 1), "transposed conv: the k = 3 six-point form at dilation 1");
@@ -193,7 +209,15 @@ struct Wino4Geo {
     // 16-byte vectors per row = 320 positions >= 240 + 13 x 5 + 3), activates them, parks them in a private LDS strip and reads its
     // tuples' positions back at stride d (4-byte LDS reads instead of one 64-lane dword load per position through the L1: the dilated
     // launches sat at 63-76 % matrix-pipe busy against 77-82 % of the dilation-1 ones).  Same wave writes and reads: no block barrier.
-    static constexpr int RAWW = 320;                                  // positions per row of the strip
+    // Packed tiles (PK_): slot pe of a tile sits at column wino4_pk_col(r0 + pe, d) of the tile's first group, r0 <= d - 1, and the strip
+    // starts up to three positions left of the window of column 0 (16-byte alignment): strip_need(d) positions.  d = 5: the last slot at
+    // column 262, so k = 11 needs 3 + 262 + 13 x 5 + 1 = 331 (k = 7: 311, k = 3: 291; d = 3: 297 / 285 / 273) -- only k = 11 outgrows 320.
+    __host__ __device__ static constexpr int strip_need(int d) {
+        return 3 + (PK_ ? wino4_pk_col(d - 1 + 63, d) : wino4_pk_col(4 * 64 / (4 * d) * d - 1, d)) + (NPOS - 1) * d + 1;
+    }
+    static constexpr int RAWW = (PK_ && K == 11) ? 332 : 320;        // positions per row of the strip
+    static_assert(RAWW % 4 == 0 && RAWW >= 256 && RAWW <= 512 && strip_need(3) <= RAWW && strip_need(5) <= RAWW, "the strip holds every tuple's window");
+    static constexpr int NV2 = (RAWW - 256) / 4;                      // lanes of the second vector set (the first: all 64)
     static constexpr int NROW = 2 * NOCT;                             // channel rows a wave stages per chunk
     static constexpr int RAW_BYTES = 4 * (NROW * RAWW * 4 + 16);      // four waves x (their rows + a dump slot for the idle lanes of the second load)
     static constexpr int DAT = K == 7 ? 16 : (K == 11 ? 12 : 8);      // gaps between the row loads and their activation
@@ -218,12 +242,47 @@ struct Wino4Geo {
 // outputs per tile at dilation d: the largest multiple of 4 d in 4 * ntup
 __device__ __host__ constexpr int wino4_tile(int d, int ntup) { return (4 * ntup / (4 * d)) * (4 * d); }
 
+// strip lengths of the packed form (tests/test_wino4_tiles_cpu.py restates the map against the same numbers)
+static_assert(Wino4Geo<3, 2, 2, 6, 2, 0, 1>::RAWW == 320 && Wino4Geo<7, 1, 2, 7, 2, 0, 1>::RAWW == 320 && Wino4Geo<7, 1, 2, 6, 2, 0, 1>::RAWW == 320 &&
+              Wino4Geo<11, 1, 2, 7, 2, 0, 1>::RAWW == 332 && Wino4Geo<11, 1, 2, 6, 2, 0, 1>::RAWW == 332, "strip lengths of the packed form");
+
+// the packed map (common.hpp: wino4_pk_*) covers every column of a row of n outputs exactly once: column c lies in group c / 4d as output
+// j = (c % 4d) / d of tuple t = (c / 4d) d + c % d; that tuple exists (t < T), and slot t % 64 of tile t / 64 maps back to c through the
+// tile's (q0, r0) as the kernel computes it.  (t, j) -> column is one-to-one, so no column has a second tuple; the tile count is ceil(T / 64)
+__host__ __device__ constexpr bool wino4_pk_covers(int n, int d) {
+    const int T = wino4_pk_tuples(n, d);
+    if (4 * T < n || wino4_pk_tiles(n, d) != (T + 63) / 64 || (d == 1 && wino4_pk_tiles(n, 1) != (n + 255) / 256)) return false;
+    for (int c = 0; c < n; ++c) {
+        const int t = (c / (4 * d)) * d + c % d, j = (c % (4 * d)) / d;
+        const int tile = t / 64, pe = t % 64;
+        if (t >= T || tile >= wino4_pk_tiles(n, d)) return false;
+        if (wino4_pk_q0(tile, d) + wino4_pk_col(wino4_pk_r0(tile, d) + pe, d) + j * d != c) return false;
+        if (wino4_pk_col(t, d) + j * d != c) return false;
+    }
+    return true;
+}
+__host__ __device__ constexpr bool wino4_pk_covers_range(int d, int n_lo, int n_hi, int step) {
+    for (int n = n_lo; n <= n_hi; n += step)
+        if (!wino4_pk_covers(n, d)) return false;
+    return true;
+}
+// (one assertion per range: a constant expression has a step limit)
+static_assert(wino4_pk_covers_range(1, 1, 130, 1) && wino4_pk_covers_range(1, 131, 700, 13), "packed tiles, d = 1: rows of 1 .. 700 outputs");
+static_assert(wino4_pk_covers_range(3, 1, 130, 1) && wino4_pk_covers_range(3, 131, 700, 13), "packed tiles, d = 3: rows of 1 .. 700 outputs");
+static_assert(wino4_pk_covers_range(5, 1, 130, 1) && wino4_pk_covers_range(5, 131, 700, 13), "packed tiles, d = 5: rows of 1 .. 700 outputs");
+static_assert(wino4_pk_covers_range(3, 1020, 1030, 1) && wino4_pk_covers_range(5, 1020, 1030, 1), "packed tiles: around 1028");
+static_assert(wino4_pk_covers(1357, 3) && wino4_pk_covers(1357, 5) && wino4_pk_covers(2048, 3) && wino4_pk_covers(2048, 5), "packed tiles: long rows");
+static_assert(wino4_pk_covers(28672, 3), "packed tiles, d = 3: a row of 28672");
+static_assert(wino4_pk_covers(28672, 5), "packed tiles, d = 5: a row of 28672");
+static_assert(wino4_pk_tiles(1028, 5) == 5 && wino4_pk_tuples(1028, 5) == 260 && wino4_pk_tuples(1028, 3) == 258, "packed tiles of a row of 1028");
+
 template <int K, int NOCT_, int NSTAGE_, int EPI, int LP, int PT = 6>
 __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float4 smem4[];
     constexpr int CTU = EPI == 5 ? 8 : (EPI == 6 ? 2 : 0);     // EPI 5 / 6: transposed conv of stride 8 / 2 (launch_convt_wino)
     constexpr bool CT = CTU != 0;
-    using G = Wino4Geo<K, NOCT_, NSTAGE_, PT, LP, CTU>;
+    constexpr bool PK = EPI == 7;                              // EPI 7: the packed strip form (packed tiles, register epilogue)
+    using G = Wino4Geo<K, NOCT_, NSTAGE_, PT, LP, CTU, PK ? 1 : 0>;
     constexpr bool PT7 = G::PT7;
     constexpr int WN = G::WN, NSF = G::NSF, NOCT = G::NOCT, NSTAGE = G::NSTAGE, NPL = G::NPL, NGPM = G::NGPM;
     constexpr int CO_BLK = G::CO_BLK, NTUP = G::NTUP, NT_BLK = G::NT_BLK, PF = G::PF;
@@ -241,16 +300,24 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     const unsigned sidx = blockIdx.x, xcd = sidx & 7u, u = sidx >> 3;
     const int yk = (int)(u % (unsigned)per_tile);
     const unsigned gt = (u / (unsigned)per_tile) * 8u + xcd;            // global time-tile index (utterance-major)
-    const int n_tiles_x = (p.Nout + nt_eff - 1) / nt_eff;
+    // PK: packed tiles (common.hpp: wino4_pk_*) -- tile i of a row = its tuples [64 i, 64 i + 64), which start at residue r0 of the group
+    // at column q0; a tile past the row's last has q0 >= 4 d G >= n_out like a plain one
+    const int n_tiles_x = PK ? wino4_pk_tiles(p.Nout, dil) : (p.Nout + nt_eff - 1) / nt_eff;
+    const int tile_w = PK ? 1 : nt_eff;                                // PK: q0 is the tile INDEX down to the map below
     int b = (int)(gt / (unsigned)n_tiles_x);
-    int q0 = (int)(gt % (unsigned)n_tiles_x) * nt_eff;
+    int q0 = (int)(gt % (unsigned)n_tiles_x) * tile_w;
     if (p.compact) {   // dead blocks last (live_tile, common.hpp)
         int tile = 0;
-        if (!live_tile<CT ? 1 : 0>(p.lens_out, p.len_out_mul, p.Nout, nt_eff, p.batch, gt, b, tile)) return;
+        if (!live_tile<CT ? 1 : 0, PK>(p.lens_out, p.len_out_mul, p.Nout, nt_eff, p.batch, gt, b, tile, dil)) return;
         b = __builtin_amdgcn_readfirstlane(b);
-        q0 = __builtin_amdgcn_readfirstlane(tile) * nt_eff;
+        q0 = __builtin_amdgcn_readfirstlane(tile) * tile_w;
     } else if (b >= p.batch) {
         return;                                                        // the grid is rounded up to whole groups of 8 tiles
+    }
+    int r0 = 0;                                                        // residue of the tile's first tuple in its group (packed tiles)
+    if constexpr (PK) {
+        r0 = wino4_pk_r0(q0, dil);
+        q0 = wino4_pk_q0(q0, dil);
     }
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wm = wid / WN, wn = wid % WN;
@@ -282,8 +349,11 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     // stages nothing and fetches in its gaps what the epilogue adds (EPI 3: the residual quads; the bias), the rows go from the output
     // transform straight to memory.  EPI 0: the row epilogue through LDS.
     constexpr bool REG = EPI >= 3, RES = EPI == 3;
-    static_assert(!REG || (LP == 1 && K != 1), "register epilogue: dilation 1, k = 3 / 7 / 11");
-    static_assert(EPI <= 6 && (!CT || K == 3), "epilogues 0, 3, 4 and the transposed conv's 5 / 6 (k = 3 form)");
+    // EPI 7 (dilation 3 / 5, one C-in slice, no residual, mode 0: HiFi-GAN's c1 convs -- the launcher's choice): packed tiles, and the same
+    // peeled last step in front of a register epilogue that stores the quad's four columns q, q + d, q + 2 d, q + 3 d as dwords.
+    static_assert(!REG || ((LP == 1 || PK) && K != 1), "register epilogue: dilation 1 or the packed strip form, k = 3 / 7 / 11");
+    static_assert(!PK || LP == 2, "packed tiles: the strip kernels");
+    static_assert(EPI <= 7 && (!CT || K == 3), "epilogues 0, 3, 4, 7 and the transposed conv's 5 / 6 (k = 3 form)");
     float ep_bias = 0.f;
     if constexpr (!REG) {
         if (tid < CO_BLK && p.bias) ep_bias = p.bias[min(co_blk0 + tid, p.Cout - 1)];
@@ -291,7 +361,8 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
 
     const int kk = lane >> 5, l31 = lane & 31;
     const int pe = wn * 32 + l31;                                           // the tuple this lane holds in the accumulators
-    const int col_e = dil == 1 ? 4 * pe : (pe / dil) * 4 * dil + pe % dil;  // ... its first column in the tile (then + dil, 2 dil, 3 dil)
+    // ... its first column in the tile (then + dil, 2 dil, 3 dil); packed tiles: slot pe is tuple r0 + pe of the tile's first group
+    const int col_e = PK ? wino4_pk_col(r0 + pe, dil) : (dil == 1 ? 4 * pe : (pe / dil) * 4 * dil + pe % dil);
     f32x16 acc[NPL];
 #pragma unroll
     for (int g = 0; g < NPL; ++g)
@@ -345,7 +416,9 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     w4_f32x4 sv[D1 ? NOCT : 1][2][D1 ? G::NVP : 1];          // D1: [octet][pp][vector]
     w4_f32x2 ta[NOCT], tb[NOCT];                             // partial sums shared by two consecutive plane jobs
     w4_f32x2 tf[PT7 ? 5 : 1], te[PT7 ? 4 : 1], td[PT7 ? 3 : 1], th[PT7 ? 2 : 1];    // seven-point groups: f(0..4), e(0..3), d(1..3), h(1, 2) of the sub-filter in work
-    const int spe = min(lane, ntup_eff - 1);                 // idle tuple slots (d > 1) repeat the last tuple: never stored
+    // idle tuple slots (d > 1) repeat the last tuple: never stored.  Packed tiles have none inside a row: slot `lane` is tuple r0 + lane of the
+    // first group, and the slots past a row's last tuple read strip positions the strip has (Wino4Geo::strip_need) and are never stored
+    const int spe = PK ? r0 + lane : min(lane, ntup_eff - 1);
     const int xw0 = (q0 + 4 * lane) * 4;                      // D1: byte offset of the lane's vector 0 in its row
     constexpr int pad_c = (K - 1) / 2;
     const int ch_off = (4 * sh + skk) * x_cs;                 // channel 2 (2 h) + kks; pp adds 2 rows, the octet 8
@@ -372,7 +445,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
             sv[ol_][pp_][vi_].w = bfo_lrelu(sv[ol_][pp_][vi_].w, in_slope);                          \
         }                                                                                            \
     }
-    // LP = 2: row job J -> (pp, vector set): lane l fetches vector l (set 0) or 64 + l (set 1: lanes 0..15) of row pp; positions A + 4 v .. + 3,
+    // LP = 2: row job J -> (pp, vector set): lane l fetches vector l (set 0) or 64 + l (set 1: lanes 0..NV2 - 1) of row pp; positions A + 4 v .. + 3,
     // A = the window start rounded down to a multiple of 4 (a vector is then entirely left of position 0 or not at all)
     float* const strip = reinterpret_cast<float*>(smem4 + NSTAGE * G::BUF4) + wid * (G::NROW * G::RAWW + 4);
     const int tr_a = (q0 - pad_c * dil) & ~3;                 // position of strip column 0
@@ -383,7 +456,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
         const int pp_ = (J) / 2, vs_ = (J) % 2;                                                      \
         const bfo_i4 xrs_ = bfo_rsrc(xb + ((XSO) + ch_off + (8 * (pp_ / 2) + 2 * (pp_ % 2)) * x_cs), (unsigned)in_len * 4u); \
         const int v_ = lane + 64 * vs_;                                                              \
-        rv[pp_][vs_] = __builtin_bit_cast(w4_f32x4, bfo_ld16(xrs_, (vs_ == 1 && lane >= 16) ? BFO_OOB : (tr_a + 4 * v_) * 4, 0, 0)); \
+        rv[pp_][vs_] = __builtin_bit_cast(w4_f32x4, bfo_ld16(xrs_, (vs_ == 1 && lane >= G::NV2) ? BFO_OOB : (tr_a + 4 * v_) * 4, 0, 0)); \
     }
     // ... activation + the 16-byte strip write (idle lanes of set 1 write the dump slot behind the rows)
 #define TTS_TSTORE_JOB(J)                                                                            \
@@ -393,7 +466,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
         a_.x = bfo_lrelu(a_.x, in_slope); a_.y = bfo_lrelu(a_.y, in_slope);                          \
         a_.z = bfo_lrelu(a_.z, in_slope); a_.w = bfo_lrelu(a_.w, in_slope);                          \
         const int v_ = lane + 64 * vs_;                                                              \
-        float* dst_ = (vs_ == 1 && lane >= 16) ? strip + G::NROW * G::RAWW : strip + pp_ * G::RAWW + 4 * v_;    \
+        float* dst_ = (vs_ == 1 && lane >= G::NV2) ? strip + G::NROW * G::RAWW : strip + pp_ * G::RAWW + 4 * v_;    \
         *reinterpret_cast<w4_f32x4*>(dst_) = a_;                                                     \
     }
     // ... read job J of phase PH -> (pp, positions 2 jp, 2 jp + 1 of the phase's window) into the staged values
@@ -697,6 +770,29 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
     // row, one 16-byte store per lane and row -- for fixed r a wave writes two rows x 32 adjacent quads = two runs of 512 bytes.  No barrier,
     // no LDS.  mode != 0 (one c2 conv in three): the running sum's quads do not fit beside the residual's under the last step, so they are
     // fetched here, eight rows at a time, in front of those rows' transform.
+    // Packed strip form (EPI 7: mode 0, no residual): the lane's quad of a row is the four columns q, q + d, q + 2 d, q + 3 d, stored as
+    // dwords, each checked against the row's length.  For a fixed row the d lanes of a group write 4 d consecutive floats between their
+    // four stores, so every touched 128-byte line is filled by the wave's four instructions of that row.  Bias and ReLU in the row
+    // epilogue's order.
+    if constexpr (PK) {
+        const int q = q0 + col_e, y_cs = p.y_cs;
+        if (q >= n_out) return;
+        const float lo = relu_out == 1 ? 0.f : -__builtin_inff();
+        const bool in1 = q + dil < n_out, in2 = q + 2 * dil < n_out, in3 = q + 3 * dil < n_out;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int co = ep_rrow + (r & 3) + 8 * (r >> 2);
+            TTS_OUT_QUAD(r)
+            const float bsv = bsq[REG ? r >> 2 : 0][r & 3];
+            if (co >= Cout) continue;                                   // padded rows of the last row block
+            float* yp = yb + (int64_t)co * y_cs + q;
+            yp[0] = fmaxf(y0 + bsv, lo);
+            if (in1) yp[dil] = fmaxf(y1 + bsv, lo);
+            if (in2) yp[2 * dil] = fmaxf(y2 + bsv, lo);
+            if (in3) yp[3 * dil] = fmaxf(y3 + bsv, lo);
+        }
+        return;
+    }
     if constexpr (REG) {
         const int q = q0 + col_e, y_cs = p.y_cs;
         if (q >= n_out) return;
@@ -803,23 +899,24 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
 
 template <int K, int NOCT, int NSTAGE, int EPI, int LP, int PT = 6>
 static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
-    using G = Wino4Geo<K, NOCT, NSTAGE, PT, LP>;
+    constexpr bool PK = EPI == 7;                            // packed strip form: packed tiles, ring + strip only
+    using G = Wino4Geo<K, NOCT, NSTAGE, PT, LP, 0, PK ? 1 : 0>;
     constexpr size_t ring = (size_t)G::NSTAGE * G::BUF4 * sizeof(float4);
     constexpr size_t epi = ((size_t)G::CO_BLK * G::NT_BLK + G::CO_BLK) * sizeof(float);
     constexpr size_t strip = LP == 2 ? (size_t)G::RAW_BYTES : 0;
-    // the register epilogue (EPI 3 / 4) touches no LDS: such a launch allocates the ring alone
+    // the register epilogue (EPI 3 / 4 / 7) touches no LDS: such a launch allocates the ring (and the strip) alone
     constexpr size_t lds = (EPI >= 3 || ring + strip > epi) ? ring + strip : epi;
     static_assert(lds <= 80 * 1024, "two blocks per CU");
-    static_assert(EPI < 3 || lds == ring, "register epilogue: the ring sets the LDS size");
+    static_assert(EPI < 3 || lds == ring + strip, "register epilogue: the ring (and the strip) set the LDS size");
     static std::atomic<uint64_t> lds_done{0};
     const auto kern = conv1d_wino4_f32<K, NOCT, NSTAGE, EPI, LP, PT>;
     TTS_CHECK_HIP(lds_opt_in((const void*)kern, (int)lds, lds_done));
     const int nt = wino4_tile(p.dil, G::NTUP);
     ConvParams q = p;
     q.ksplit = EPI == 0 ? wino4_ksplit(p) : 1;
-    note_conv_launch(PT == 7 ? 4 : 3, q.ksplit);
+    note_conv_launch(PK ? (PT == 7 ? 8 : 7) : (PT == 7 ? 4 : 3), q.ksplit);
     // 1-D grid: (time tiles of the whole batch, rounded up to groups of 8) x row blocks x C-in slices; the kernel maps it XCD-aware
-    const int64_t n_tiles = (int64_t)((p.Nout + nt - 1) / nt) * p.batch;
+    const int64_t n_tiles = (int64_t)(PK ? wino4_pk_tiles(p.Nout, p.dil) : (p.Nout + nt - 1) / nt) * p.batch;
     const int64_t n_blocks = ((n_tiles + 7) / 8) * 8 * (p.CoutP / G::CO_BLK) * q.ksplit;
     TTS_REQUIRE(n_blocks < ((int64_t)1 << 31), "wino4: %lld blocks", (long long)n_blocks);
     dim3 grid((unsigned)n_blocks, 1, 1);
@@ -828,6 +925,12 @@ static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
     TTS_CHECK_HIP(hipGetLastError());
     if (q.ksplit > 1) return launch_splitk_reduce(q, stream);
     return 0;
+}
+
+// TTSAMD_WINO4 bit 7: a dilated launch with one C-in slice, no residual and mode 0 (HiFi-GAN's c1 convs: bias and ReLU only) runs in the
+// packed strip form (EPI 7); C-in slices, a residual and the accumulate modes keep the row epilogue (EPI 0)
+static bool wino4_packed_wanted(const ConvParams& p) {
+    return ((int)opt_int(OPT_WINO4, kWino4Default) & 128) != 0 && p.dil != 1 && p.res == nullptr && p.mode == 0 && wino4_ksplit(p) == 1;
 }
 
 template <int K, int NOCT, int NSTAGE>
@@ -840,7 +943,8 @@ static int32_t launch_wino4_cfg(const ConvParams& p, hipStream_t stream) {
         if (p.res != nullptr) return launch_wino4_epi<K, NOCT, NSTAGE, 3, 1>(p, stream);
         return launch_wino4_epi<K, NOCT, NSTAGE, 4, 1>(p, stream);
     }
-    // dilation 3 / 5: the window through the per-wave LDS strip (two stages: the strip takes 10 / 20 KB)
+    // dilation 3 / 5: the window through the per-wave LDS strip (two stages: the strip takes 10 / 20 KB); the packed form where it applies
+    if (wino4_packed_wanted(p)) return launch_wino4_epi<K, NOCT, 2, 7, 2>(p, stream);
     return launch_wino4_epi<K, NOCT, 2, 0, 2>(p, stream);
 }
 
@@ -853,6 +957,7 @@ static int32_t launch_wino44_cfg(const ConvParams& p, hipStream_t stream) {
         if (p.res != nullptr) return launch_wino4_epi<K, 1, 2, 3, 1, 7>(p, stream);
         return launch_wino4_epi<K, 1, 2, 4, 1, 7>(p, stream);
     }
+    if (wino4_packed_wanted(p)) return launch_wino4_epi<K, 1, 2, 7, 2, 7>(p, stream);
     return launch_wino4_epi<K, 1, 2, 0, 2, 7>(p, stream);
 }
 

@@ -704,7 +704,9 @@ def conv1d(x, w, bias=None, lens=None, dilation=1, in_slope=1.0, relu_out=False,
 
 def last_conv_launch():
     """(route, ksplit) of this thread's last fp32 conv launch (ttsamd_conv_last_launch): route 0 direct kernel, 1 / 2 Winograd F(2,3),
-    3 / 4 Winograd F(4,3) on six- / seven-point groups, 5 the all-phase transposed conv, 6 the transposed conv on Winograd F(4,2); ksplit = input-channel slices (1: not split)."""
+    3 / 4 Winograd F(4,3) on six- / seven-point groups, 5 the all-phase transposed conv, 6 the transposed conv on Winograd F(4,2),
+    7 / 8 Winograd F(4,3) on six- / seven-point groups in the packed strip form (dilation 3 / 5; TTSAMD_WINO4 bit 7);
+    ksplit = input-channel slices (1: not split)."""
     route, ksplit = C.c_int32(-1), C.c_int32(0)
     L.check(L.load().ttsamd_conv_last_launch(C.byref(route), C.byref(ksplit)), 'conv_last_launch')
     return route.value, ksplit.value
