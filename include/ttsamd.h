@@ -1005,6 +1005,50 @@ int32_t ttsamd_wave_limit(float* wave, int64_t wave_stride, const int64_t* nsamp
                           const float* target, float ceiling, float max_gain, int32_t attack, int32_t hold, const double* loudness,
                           float* gain_out, int32_t* reduction_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- true peak (csrc/true_peak.hpp, csrc/loudness.hip, csrc/limiter.hip): the peak of the 4x oversampled row, and the levelling and
+ * the limiter against it.  New symbols only, added WITHOUT a bump.  Specified by the arithmetic below (the interpolator is the
+ * project's own resampler table, not the FIR of ITU-R BS.1770-4 Annex 2; the EBU Tech 3341 true-peak signals read within that
+ * document's +0.2 / -0.4 dB); parity with libebur128 / pyloudnorm is not pinned.
+ * Interpolator: the resampler's formula above with o = 1, n = 4, lowpass_filter_width = 12, rolloff = 1.0: W = width = 12, J = 25 and,
+ * in float64, t = clamp((j - 12) - p / 4, -12, 12), h[p][j] = sinc(t) cos^2(t pi / 24), rounded once to fp32 (in ttsamd/resample.py's
+ * order of operations: the table is ttsamd.resample.resample_taps(1, 4, 12, 1.0)).  Only the phases p = 1, 2, 3 are used: phase 0 is
+ * the sample itself, not a filtered copy.  The library builds the table on the host (ttsamd_true_peak_taps returns it) and hands it to
+ * its kernels as an argument.  For a row x of n samples, xz = the row, zero outside [0, n):
+ *   v[i][p] = sum over j = 0 .. 24 ascending of (double)h[p][j] (double)xz[i + j - 12], 0 <= i < n, a float64 accumulator from +0.0.
+ * The product of two fp32 values is exact in float64, so fma and multiply-then-add give the same bits, and a numpy loop over j
+ * reproduces the kernel bit for bit (an fp32 chain would not).
+ * True peak: TP = max(max_i |x[i]|, max_{i, p} |v[i][p]|) in float64: the 4n positions i + p / 4 of a 4x resample, the tail behind the
+ * last sample included, nothing before sample 0.  Returned as fp32 rounded UPWARD (the smallest fp32 >= TP), so that a ceiling
+ * computed from it is never too lax; an empty row gives 0.  A maximum is order-free: row b of a batch has the bits the row has alone.
+ * Level with a true-peak cap: ttsamd_wave_level with the true-peak array as its `peak`.  With H = max_p sum_j |h[p][j]| (from the
+ * table), the levelled row y = fl32(x g) of mode 2 has TP(y) <= ceiling (1 + H 2^-24) up to the rounding of the gain itself: each
+ * y[i] is within 2^-24 |x[i] g| of x[i] g, and the interpolator passes these errors with a gain of at most H.  (Strictly:
+ * fl32(TP g) <= ceiling leaves TP g up to 2^-24 ceiling above the ceiling, so the proven bound is ceiling (1 + (H + 1) 2^-24
+ * (1 + 2^-24)); mode 1 rounds twice, fl32(fl32(x / TP) target), and has target (1 + 2 H 2^-24 (1 + 2^-24)).  Both worst cases need
+ * every rounding error under the 25 taps at its limit and with the taps' signs; the tests hold real rows to the first bound.)
+ * Limiter with a true-peak detector: ttsamd_wave_limit's arithmetic literally (u, q, m, s, y, Q30) except for the detector d, which is
+ * float64: with v computed from u as above (u zero outside the row),
+ *   d[i] = max(|u[i]|, max_p |v[i][p]|, max_p |v[i - 1][p]|), the last term omitted for i = 0;
+ *   q[i] = Q if not d[i] > (double)c, else floor((double)c / d[i] 2^30).
+ * An inter-sample point between i and i + 1 pulls the gain down at both neighbours.  d[i] >= |u[i]|, so |y[i]| <= c still holds
+ * exactly.  The reach grows by W + 1 = 13 on each side: y[i] depends on x over [i - A - R - 13, i + 2A + 13] only.  The true peak of y
+ * is NOT bounded exactly by c: the gain curve varies across the 25 taps.  The overshoot is a measured number, not
+ * a guarantee.
+ * ttsamd_true_peak: two launches whatever the lengths (the result is zeroed, then blocks that own tiles of 2048 samples stage the tile
+ * and 12 samples to either side in LDS, run the 3 chains per sample in registers and end in one unsigned integer atomic max per block:
+ * non-negative IEEE floats order as their bit patterns).  The 4x signal is never written to memory. */
+/* HOST out[3][25] float64: h[p][j] for p = 1, 2, 3 (each the widened fp32 value).  TTSAMD_EINVAL for NULL.  Needs no GPU. */
+int32_t ttsamd_true_peak_taps(double* out);
+/* true_peak: device fp32 [batch].  Nothing at or past nsamples[b] is read; nothing is read back to the host.
+ * TTSAMD_EINVAL (nothing launched): a NULL pointer, batch outside 1 .. 65535, a negative stride or one of 2^40 and more. */
+int32_t ttsamd_true_peak(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, float* true_peak, void* stream);
+/* ttsamd_wave_limit with the detector above: the same arguments, modes, outputs, limits, TTSAMD_EINVAL rules and workspace
+ * (ttsamd_wave_limit_workspace_bytes); two launches, the second is ttsamd_wave_limit's own. */
+int32_t ttsamd_wave_limit_true_peak(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
+                                    const float* target, float ceiling, float max_gain, int32_t attack, int32_t hold,
+                                    const double* loudness, float* gain_out, int32_t* reduction_out, void* workspace,
+                                    int64_t workspace_bytes, void* stream);
+
 /* ---- wave-against-wave scores (csrc/wavescore.hip): STOI / ESTOI at 10 kHz, SI-SDR / SNR and a log-spectral distance between the rows
  * of two ragged mono batches that are sample-aligned (copy synthesis, a precision mode against fp32, a delivery format against the float
  * wave; free-running synthesis is NOT aligned with a recording and has no meaningful score here).  Both waves are [batch][wave_stride]

@@ -9,9 +9,12 @@
 //      [i - R, i + A] from two overlapping windows of 2^k, adds m over [i - A, i + A] (int64; sums of eight first, then a sliding sum over a
 //      thread's eight samples) and writes y = fl32(u s 2^-30) over its own tile.
 // Two launches: the call works in place, and a tile's halo covers samples that another tile writes.
+// ttsamd_wave_limit_true_peak: launch 1 is limit_q_tp_kernel, whose d is the larger of |u| and the 4x interpolator's values to either side
+// of the sample (true_peak.hpp); launch 2 is the same kernel.
 #include <cmath>
 
 #include "common.hpp"
+#include "true_peak.hpp"
 
 namespace ttsamd {
 
@@ -75,6 +78,48 @@ __global__ __launch_bounds__(LM_NT) void limit_q_kernel(const float* __restrict_
     for (int j = 0; j < LM_T / LM_NT; ++j) {
         const int64_t i = t0 + j * LM_NT + threadIdx.x;
         if (i < n) qb[i] = limit_q(__fmul_rn(wb[i], g), ceiling);
+    }
+}
+
+// limit_q_kernel with the true-peak detector (ttsamd_wave_limit_true_peak): the block stages u for its tile and LM_TPH samples to either
+// side (13 are needed: 12 taps and the sample in front; 16 keeps the 16-byte loads), every thread runs the interpolator's chains for
+// the sample in front of its eight and for the eight, and d[i] = max(|u[i]|, max_p |v[i][p]|, max_p |v[i - 1][p]|) in float64.
+constexpr int LM_TPH = 16;
+constexpr int LM_UN = LM_T + 2 * LM_TPH;
+static_assert(LM_TPH >= TP_W + 1 && LM_TPH % 4 == 0, "true-peak halo of the limiter");
+
+__global__ __launch_bounds__(LM_NT) void limit_q_tp_kernel(const float* __restrict__ wave, int64_t stride, const int64_t* __restrict__ ns,
+                                                           const int32_t* __restrict__ mode, const float* __restrict__ target, float ceiling,
+                                                           float max_gain, const double* __restrict__ loudness, const TpTaps taps,
+                                                           float* __restrict__ gain_out, int32_t* __restrict__ reduction_out,
+                                                           int32_t* __restrict__ live_out, int32_t* __restrict__ qp) {
+    __shared__ __align__(16) float us[LM_UN];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int64_t n = limit_len(ns, b, stride);
+    float g;
+    const bool live = limit_gain(mode[b], target[b], max_gain, loudness, b, g);
+    if (blockIdx.x == 0 && tid == 0) {
+        gain_out[b] = g;
+        reduction_out[b] = LM_Q;
+        live_out[b] = live ? 1 : 0;
+    }
+    const int64_t t0 = (int64_t)blockIdx.x * LM_T;
+    if (!live || t0 >= n) return;                              // the whole block
+    tp_stage<true>(wave + (int64_t)b * stride, t0 - LM_TPH, LM_UN, n, g, us);
+    __syncthreads();
+    const int64_t i0 = t0 + 8 * tid;
+    if (i0 >= n) return;
+    double vm[9];                                              // samples i0 - 1 .. i0 + 7; us[8 tid + LM_TPH] is u[i0]
+    tp_chains<9>(us + 8 * tid + LM_TPH - 1 - TP_W, taps, vm);
+    int32_t* qb = qp + (int64_t)b * stride;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int64_t i = i0 + e;
+        if (i < n) {
+            double d = fmax(fabs((double)us[8 * tid + LM_TPH + e]), vm[e + 1]);
+            if (i > 0) d = fmax(d, vm[e]);
+            qb[i] = d > (double)ceiling ? (int32_t)floor((double)ceiling / d * 1073741824.0) : LM_Q;
+        }
     }
 }
 
@@ -177,7 +222,7 @@ static void limit_carve(void* base, int64_t B, int64_t stride, LimitWs& w) {
 
 static int32_t wave_limit(float* wave, int64_t stride, const int64_t* nsamples, int32_t B, const int32_t* mode, const float* target,
                           float ceiling, float max_gain, int32_t A, int32_t R, const double* loudness, float* gain_out,
-                          int32_t* reduction_out, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+                          int32_t* reduction_out, void* workspace, int64_t workspace_bytes, bool true_peak, hipStream_t s) {
     TTS_REQUIRE(nsamples && mode && target && gain_out && reduction_out && workspace && (wave || stride == 0), "wave_limit: null argument");
     TTS_REQUIRE(B >= 1 && B <= 65535 && stride >= 0 && stride < ((int64_t)1 << 40), "wave_limit: bad batch %d / stride", B);
     TTS_REQUIRE(ceiling > 0.f && ceiling <= 1.f, "wave_limit: ceiling %g is not in (0, 1]", (double)ceiling);
@@ -194,8 +239,12 @@ static int32_t wave_limit(float* wave, int64_t stride, const int64_t* nsamples, 
     int K2 = 1;
     while (2 * K2 <= R + A + 1) K2 *= 2;
     const dim3 grid((unsigned)nt, B);
-    hipLaunchKernelGGL(limit_q_kernel, grid, dim3(LM_NT), 0, s, wave, stride, nsamples, mode, target, ceiling, max_gain, loudness, gain_out,
-                       reduction_out, w.live, w.q);
+    if (true_peak)
+        hipLaunchKernelGGL(limit_q_tp_kernel, grid, dim3(LM_NT), 0, s, wave, stride, nsamples, mode, target, ceiling, max_gain, loudness,
+                           tp_taps(), gain_out, reduction_out, w.live, w.q);
+    else
+        hipLaunchKernelGGL(limit_q_kernel, grid, dim3(LM_NT), 0, s, wave, stride, nsamples, mode, target, ceiling, max_gain, loudness, gain_out,
+                           reduction_out, w.live, w.q);
     TTS_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(limit_apply_kernel, grid, dim3(LM_NT), 0, s, wave, stride, nsamples, (int)A, (int)R, K2, gain_out, w.live, w.q,
                        reduction_out);
@@ -220,7 +269,14 @@ int32_t ttsamd_wave_limit(float* wave, int64_t wave_stride, const int64_t* nsamp
                           float ceiling, float max_gain, int32_t attack, int32_t hold, const double* loudness, float* gain_out,
                           int32_t* reduction_out, void* workspace, int64_t workspace_bytes, void* stream) {
     return wave_limit(wave, wave_stride, nsamples, batch, mode, target, ceiling, max_gain, attack, hold, loudness, gain_out, reduction_out,
-                      workspace, workspace_bytes, (hipStream_t)stream);
+                      workspace, workspace_bytes, false, (hipStream_t)stream);
+}
+
+int32_t ttsamd_wave_limit_true_peak(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
+                                    const float* target, float ceiling, float max_gain, int32_t attack, int32_t hold, const double* loudness,
+                                    float* gain_out, int32_t* reduction_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    return wave_limit(wave, wave_stride, nsamples, batch, mode, target, ceiling, max_gain, attack, hold, loudness, gain_out, reduction_out,
+                      workspace, workspace_bytes, true, (hipStream_t)stream);
 }
 
 }  // extern "C"

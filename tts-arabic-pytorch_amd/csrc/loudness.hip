@@ -15,9 +15,12 @@
 // order, a block's segments in order, strided partial sums and an LDS tree over the blocks), so row b of a batch has the bits it has alone.
 // wave_level_kernel: every block works its row's gain out again from L, peak, mode and target (a few float64 operations) and scales
 // its share of the row in place.
+// true_peak_kernel (ttsamd_true_peak): the peak of the 4x interpolated row from the chains of true_peak.hpp; its result can stand in for
+// `peak` in wave_level_kernel, which makes the ceiling a true-peak ceiling.
 #include <cmath>
 
 #include "common.hpp"
+#include "true_peak.hpp"
 
 namespace ttsamd {
 
@@ -358,6 +361,56 @@ static int32_t loudness_measure(const float* wave, int64_t stride, const int64_t
     return 0;
 }
 
+// True peak (include/ttsamd.h): a block owns a tile of TPK_T samples of one row, stages the tile and 12 samples to either side in LDS,
+// and every thread runs the three float64 chains of its eight samples.  max |x|, |v| over the block in float64, rounded UPWARD to fp32;
+// non-negative IEEE floats order as their bit patterns, so one unsigned atomic max per block on the (zeroed) result is exact and
+// order-free.  The 4x signal lives in registers only.
+constexpr int TPK_T = 2048, TPK_NT = 256;
+constexpr int TPK_XN = TPK_T + 2 * TP_W;
+static_assert(TPK_T == 8 * TPK_NT && TPK_XN % 4 == 0 && TP_W % 4 == 0, "true-peak tiling");
+
+__global__ __launch_bounds__(TPK_NT) void true_peak_kernel(const float* __restrict__ wave, int64_t stride, const int64_t* __restrict__ ns,
+                                                           const TpTaps taps, float* __restrict__ out) {
+    __shared__ __align__(16) float xs[TPK_XN];
+    __shared__ float red[TPK_NT / 64];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int64_t n = loud_len(ns, b, stride), t0 = (int64_t)blockIdx.x * TPK_T;
+    if (t0 >= n) return;                                       // the whole block: an empty row keeps its zero
+    tp_stage<false>(wave + (int64_t)b * stride, t0 - TP_W, TPK_XN, n, 1.f, xs);
+    __syncthreads();
+    const int64_t i0 = t0 + 8 * tid;
+    double m = 0.0;
+    if (i0 < n) {
+        double vm[8];
+        tp_chains<8>(xs + 8 * tid, taps, vm);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (i0 + e < n) m = fmax(m, fmax(fabs((double)xs[8 * tid + TP_W + e]), vm[e]));
+    }
+    float f = (float)m;
+    if ((double)f < m) f = nextafterf(f, INFINITY);            // the smallest fp32 >= m
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) f = fmaxf(f, __shfl_xor(f, d, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = f;
+    __syncthreads();
+    if (tid == 0) {
+        f = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        if (f > 0.f) atomicMax((unsigned int*)out + b, __float_as_uint(f));
+    }
+}
+
+static int32_t true_peak(const float* wave, int64_t stride, const int64_t* nsamples, int32_t B, float* out, hipStream_t s) {
+    TTS_REQUIRE(nsamples && out && (wave || stride == 0), "true_peak: null argument");
+    TTS_REQUIRE(B >= 1 && B <= 65535 && stride >= 0 && stride < ((int64_t)1 << 40), "true_peak: bad batch %d / stride", B);
+    int64_t nt = (stride + TPK_T - 1) / TPK_T;
+    nt = nt < 1 ? 1 : nt;
+    TTS_REQUIRE(nt <= 0x7fffffff, "true_peak: stride too large");
+    TTS_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)B * sizeof(float), s));
+    hipLaunchKernelGGL(true_peak_kernel, dim3((unsigned)nt, B), dim3(TPK_NT), 0, s, wave, stride, nsamples, tp_taps(), out);
+    TTS_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void wave_level_kernel(float* __restrict__ wave, int64_t stride, const int64_t* __restrict__ ns,
                                                          const int32_t* __restrict__ mode, const float* __restrict__ target, float ceiling,
                                                          const double* __restrict__ loudness, const float* __restrict__ peak,
@@ -436,6 +489,18 @@ int32_t ttsamd_loudness_measure(const float* wave, int64_t wave_stride, const in
 int32_t ttsamd_wave_level(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,
                           const float* target, float ceiling, const double* loudness, const float* peak, float* gain_out, void* stream) {
     return wave_level(wave, wave_stride, nsamples, batch, mode, target, ceiling, loudness, peak, gain_out, (hipStream_t)stream);
+}
+
+int32_t ttsamd_true_peak_taps(double* out) {
+    TTS_REQUIRE(out, "true_peak_taps: out is null");
+    const TpTaps& t = tp_taps();
+    for (int p = 0; p < TP_P; ++p)
+        for (int j = 0; j < TP_J; ++j) out[p * TP_J + j] = t.h[p][j];
+    return 0;
+}
+
+int32_t ttsamd_true_peak(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, float* true_peak_out, void* stream) {
+    return true_peak(wave, wave_stride, nsamples, batch, true_peak_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -44,7 +44,7 @@ def infer(args):
         for k in range(0, len(lines), args.batch_size):
             batch = lines[k:k + args.batch_size]
             wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, normalize=args.normalize,
-                             **({'limiter': True} if args.limiter else {}))
+                             **({'limiter': True} if args.limiter else {}), **({'true_peak': True} if args.true_peak else {}))
             for line, wav in zip(batch, wavs):
                 if rate != 22_050:                      # the finished wave through the device resampler, then the matching file format
                     wav = resample(wav.reshape(1, -1).to('cuda'), 22_050, rate)[0]
@@ -73,9 +73,13 @@ def main(argv=None):
     p.add_argument('--normalize', type=normalize_option, default=None, metavar='peak|lufs|<LUFS>')
     # ... with the look-ahead limiter in place of the cap on the gain, so that a LUFS target is reached (needs --normalize lufs or a target)
     p.add_argument('--limiter', action='store_true')
+    # ... and with 0.99 as a true-peak ceiling (4x oversampled) instead of a sample peak, so that the resampled files do not clip
+    p.add_argument('--true_peak', action='store_true')
     args = p.parse_args(argv)
     if args.limiter and args.normalize in (None, 'peak'):
         p.error("--limiter needs --normalize lufs or a target in LUFS")
+    if args.true_peak and args.normalize is None:
+        p.error("--true_peak needs --normalize")
     infer(args)
 
 

@@ -23,7 +23,8 @@ from ttsamd.engine import average_pitch as _average_pitch
 from ttsamd.engine import binarization_loss as _binarization_loss
 from ttsamd.engine import forward_sum_loss as _forward_sum_loss
 from ttsamd.engine import mas as _mas
-from ttsamd.engine import check_finite, check_limiter, check_normalize, check_speakers, level_waves, limiter_spec, per_row, row_values
+from ttsamd.engine import check_finite, check_limiter, check_normalize, check_speakers, check_true_peak, level_waves, limiter_spec, per_row, \
+    row_values
 from ttsamd.lib import TtsAmdError
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
@@ -53,20 +54,23 @@ def _at(value, i):
     return value[i] if per_row(value) else value
 
 
-def _lim(limiter, normalize):
-    """the `limiter` keyword for a call that gets `normalize` (one option or a list): only where a limiter is asked for and a line of
-    that call asks for a level -- every other call gets exactly the arguments it got before"""
-    if not limiter or not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
+def _lim(limiter, normalize, true_peak=False):
+    """the `limiter` and `true_peak` keywords for a call that gets `normalize` (one option or a list): only where they are asked for and
+    a line of that call asks for a level -- every other call gets exactly the arguments it got before"""
+    if not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
         return {}
-    return {'limiter': limiter}
+    return dict({'limiter': limiter} if limiter else {}, **({'true_peak': True} if true_peak else {}))
 
 
-def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1., pitch_add=0., denoise=0., normalize=None):
+def check_line_controls(n_lines, n_speakers, speed=1., speaker_id=0, pitch_mul=1., pitch_add=0., denoise=0., normalize=None, true_peak=False):
     """Host-side validation of per-line controls before any work: a list must have one value per line (ValueError), speakers lie in
     [0, n_speakers) (IndexError), speeds are finite and > 0, pitch values and denoise strengths finite (ValueError).  Scalars pass
     through to the checks of the calls that take them.  `normalize` (the level of the wave: None, 'peak', 'lufs' or a finite target in
-    LUFS, one for all lines or one per line) is checked in both forms: nothing below looks at it before the vocoder has run."""
+    LUFS, one for all lines or one per line) is checked in both forms: nothing below looks at it before the vocoder has run.
+    `true_peak` (False or True: the peaks of `normalize` and of its limiter are true peaks) with no line that asks for a level is a
+    ValueError."""
     check_normalize(normalize, n_lines)
+    check_true_peak(true_peak, normalize, None)
     for what, v in (('speed', speed), ('speaker_id', speaker_id), ('pitch_mul', pitch_mul), ('pitch_add', pitch_add), ('denoise', denoise)):
         if not per_row(v):
             continue
@@ -407,26 +411,28 @@ class FastPitch2Wave(nn.Module):
     @torch.inference_mode()
     def tts_single(self, text_buckw: str, speed: float = 1, speaker_id: int = 0, denoise: float = 0,
                    vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None,
-                   limiter=False):
+                   limiter=False, true_peak=False):
         check_normalize(normalize, 1)
         limiter = check_limiter(limiter, normalize)
+        check_true_peak(true_peak, normalize, limiter)
         mel_spec = self.model.ttmel_single(text_buckw, speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
                                            pitch_add=pitch_add)
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
         if normalize is not None:
-            wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize))
+            wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize, true_peak))
         if return_mel:
             return wave[0].cpu(), mel_spec
         return wave[0].cpu()
 
-    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize=None, limiter=False):
+    def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize=None, limiter=False,
+                          true_peak=False):
         """What tts_batch and tts_batch_device share: (wave [B, n_max], n_samples int64 [B], reverse_ids), rows in the collate order (longest
         first).  Every control is a scalar or one value per line of `batch`; a per-line denoise strength goes through the same sort as
         the lines, and a line whose strength is not > 0 keeps its vocoder output bit for bit.  `normalize` takes the same sort; the
         rows are levelled on the device after the denoiser (ttsamd.engine.level_waves)."""
-        check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise, normalize=normalize)
+        check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise, normalize=normalize, true_peak=true_peak)
         limiter = check_limiter(limiter, normalize)
         mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
                                                                     pitch_add)
@@ -436,24 +442,27 @@ class FastPitch2Wave(nn.Module):
         if any(d > 0 for d in denoise) if per_row(denoise) else denoise > 0:
             wave = self.denoiser.forward_batch(wave, n, denoise)
         if normalize is not None:
-            wave = level_waves(wave, n, _take(normalize, reverse_ids.argsort().tolist()), self.sample_rate, **_lim(limiter, normalize))
+            wave = level_waves(wave, n, _take(normalize, reverse_ids.argsort().tolist()), self.sample_rate,
+                               **_lim(limiter, normalize, true_peak))
         return wave, n, reverse_ids
 
     @torch.inference_mode()
     def tts_batch_device(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0,
                          vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None,
-                         limiter=False):
+                         limiter=False, true_peak=False):
         """`tts_batch` without the device->host copy: (wave [B, n_max] float32, n_samples int64 [B]), both in HBM,
         rows in the order of `batch` (zeros past n_samples[b]).  What the data-parallel gather (ttsamd.dp) and
         any GPU-side consumer take; `tts_batch` is this plus one D2H."""
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter)
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter,
+                                                      true_peak)
         rev = reverse_ids.to(wave.device)
         return wave.index_select(0, rev), n.index_select(0, rev)
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0, vowelizer=None,
-                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None, limiter=False):
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter)
+                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None, limiter=False, true_peak=False):
+        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter,
+                                                      true_peak)
         n = n.tolist()
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:347-350); so do we
@@ -461,7 +470,7 @@ class FastPitch2Wave(nn.Module):
 
     def tts(self, text_input: Union[str, List[str]], speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
             batch_size: int = 2, vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.,
-            return_mel: bool = False, normalize=None, limiter=False) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None, limiter=False, true_peak=False) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:352-435): str -> Tensor[n_samples] (CPU);
         list -> list of tensors, chunked by `batch_size`.
         Mixed requests (not in the reference): for a list of lines, speed, denoise, speaker_id, pitch_mul and pitch_add each take a scalar
@@ -478,33 +487,37 @@ class FastPitch2Wave(nn.Module):
         limiter (False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db; needs a normalize): the lines with 'lufs' or
         a target get the full gain towards it (at most max_gain_db) and the look-ahead limiter holds their peaks at the ceiling
         (utils.audio.limit; include/ttsamd.h states the arithmetic), so the target is reached where the cap would have stopped short of
-        it; 'peak' and None lines keep their path.  One setting for the call, not per line."""
+        it; 'peak' and None lines keep their path.  One setting for the call, not per line.
+        true_peak (False or True; needs a normalize): every peak above is the true peak (utils.audio.true_peak: 4x oversampled), so
+        0.99 and the limiter's ceiling are true-peak ceilings; one setting for the call.  With no line to level it is a ValueError."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, pitch_mul=pitch_mul, pitch_add=pitch_add)
         if normalize is not None and not (per_row(normalize) and all(v is None for v in normalize)):
             kw['normalize'] = normalize         # (None, or only None: the calls below get exactly the arguments they got before)
         if isinstance(text_input, str):
-            return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw, **({'limiter': limiter} if limiter else {}))
+            return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw, **({'limiter': limiter} if limiter else {}),
+                                   **({'true_peak': true_peak} if true_peak else {}))
         assert isinstance(text_input, list)
-        check_line_controls(len(text_input), self.model.net_config['n_speakers'], **dict(kw, normalize=normalize))
+        check_line_controls(len(text_input), self.model.net_config['n_speakers'], **dict(kw, normalize=normalize, true_peak=true_peak))
         limiter = check_limiter(limiter, normalize)
         if (len(text_input) > batch_size and not return_mel and self.device.type == 'cuda'
                 and os.environ.get('TTSAMD_TTS_PIPELINE', '1') != '0'):
-            return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw, **_lim(limiter, normalize))
+            return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw,
+                                            **_lim(limiter, normalize, true_peak))
         if batch_size == 1:
             return [self.tts_single(sample, vowelizer=vowelizer, return_mel=return_mel, **{k: _at(v, i) for k, v in kw.items()},
-                                    **_lim(limiter, _at(normalize, i)))
+                                    **_lim(limiter, _at(normalize, i), true_peak))
                     for i, sample in enumerate(text_input)]
         wav_list = []
         for k in range(0, len(text_input), batch_size):
             idx = range(k, min(k + batch_size, len(text_input)))
             wav_list += self.tts_batch(text_input[k:k + batch_size], vowelizer=vowelizer, return_mel=return_mel,
-                                       **{n: _take(v, idx) for n, v in kw.items()}, **_lim(limiter, _take(normalize, idx)))
+                                       **{n: _take(v, idx) for n, v in kw.items()}, **_lim(limiter, _take(normalize, idx), true_peak))
         return wav_list
 
     # the options of one request of tts_requests and what a request that leaves one out gets: tts()'s own defaults
     REQUEST_DEFAULTS = dict(speed=1., denoise=0.005, speaker_id=0, pitch_mul=1., pitch_add=0.)
 
-    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None, limiter=False):
+    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None, limiter=False, true_peak=False):
         """A server's queue in one go: `requests` is a list of dicts with `text` and any of speed, denoise, speaker_id, pitch_mul, pitch_add, normalize
         (the per-request options of the reference's app); returns one wave per request, in request order, from ONE `tts` call with the
         options as per-line lists -- requests with different options share batches instead of one call per distinct option tuple."""
@@ -521,18 +534,23 @@ class FastPitch2Wave(nn.Module):
             lists['normalize'] = [r.get('normalize') for r in requests]
         if limiter:                               # one setting for the call (a request has no limiter of its own); tts checks it
             lists['limiter'] = limiter
+        if true_peak:                             # likewise one setting for the call
+            lists['true_peak'] = true_peak
         return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
     # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
-    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None, limiter=None):
+    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None, limiter=None,
+                  true_peak=False):
         """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
         from ttsamd.stream import StreamingVocoder
         key = (str(self.device), int(chunk_frames), int(first_chunk_frames), bool(pcm16), int(max_streams), int(max_frames),
-               None if sample_rate is None else int(sample_rate), encoding, None if limiter is None else tuple(sorted(limiter.items())))
+               None if sample_rate is None else int(sample_rate), encoding, None if limiter is None else tuple(sorted(limiter.items())),
+               bool(true_peak))
         if getattr(self, '_stream_key', None) != key:
             self._stream_voc = StreamingVocoder(self.vocoder, self.denoiser, max_streams=max_streams, max_frames=max_frames,
                                                 chunk_frames=chunk_frames, first_chunk_frames=first_chunk_frames, pcm16=pcm16,
-                                                sample_rate=sample_rate, encoding=encoding, limiter=limiter)
+                                                sample_rate=sample_rate, encoding=encoding, limiter=limiter,
+                                                **({'true_peak': True} if true_peak else {}))
             self._stream_key = key
         for sid in self._stream_voc.open_streams:           # a generator that was abandoned half-way
             self._stream_voc.close(sid)
@@ -541,7 +559,7 @@ class FastPitch2Wave(nn.Module):
     def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
                    max_streams: int = 32, max_frames: int = 4096, speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
                    vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., sample_rate=None, encoding=None, gain_db=0.0,
-                   limiter=False):
+                   limiter=False, true_peak=False):
         """`tts` that hands out audio while it is being made (a generator; one at a time per model).  FastPitch is not autoregressive, so
         the whole mel exists at once; the vocoder then runs over windows of it (ttsamd.stream.StreamingVocoder), the first of
         first_chunk_frames frames, the following of chunk_frames.
@@ -559,9 +577,12 @@ class FastPitch2Wave(nn.Module):
         line): levelling inside the stream.  A stream cannot measure its loudness, so it is levelled the way a live chain is: a fixed
         gain, then the look-ahead limiter, at 22 050 Hz in front of the resampler.  The chunks put together are utils.audio.limit of
         the stream's samples in front of the limiter (StreamingVocoder.bypass), bit for bit; against the stream without a limiter
-        those differ within fp32 summation order, as its windows are narrower.  gain_db other than 0 without a limiter is a ValueError."""
+        those differ within fp32 summation order, as its windows are narrower.  gain_db other than 0 without a limiter is a ValueError.
+        true_peak (needs a limiter; ValueError without one): the limiter's detector is the true-peak one, and the chunks are the bits
+        of utils.audio.limit(true_peak=True)."""
         kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
         limiter = limiter_spec(limiter)
+        check_true_peak(true_peak, None, limiter)
         n_lines = 1 if isinstance(text_input, str) else len(text_input)
         gains = row_values(gain_db, n_lines, 'gain_db') if per_row(gain_db) else [gain_db]
         check_finite(gains, 'gain_db')
@@ -569,7 +590,7 @@ class FastPitch2Wave(nn.Module):
             raise ValueError('tts_stream: gain_db needs limiter=True (or its settings): a gain alone could clip')
         if isinstance(text_input, str):
             mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw)
-            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter)
+            sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak)
             sv.open(mel, denoise, float(gains[0]))
             while sv.open_streams:
                 for _, chunk, _ in sv.step():
@@ -577,7 +598,7 @@ class FastPitch2Wave(nn.Module):
             return
         lines = list(text_input)
         check_line_controls(len(lines), self.model.net_config['n_speakers'], denoise=denoise, **kw)
-        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter)
+        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak)
         # FastPitch over the lines in input order, in ragged calls of up to _ALONE_GROUP rows computed as if alone; a group is made when
         # a slot is free and no mel is waiting
         groups, fill, longest = [], [], 0
@@ -695,7 +716,7 @@ class FastPitch2Wave(nn.Module):
 
     @torch.inference_mode()
     def _tts_list_pipelined(self, text_input, batch_size, speed, denoise, speaker_id, vowelizer, pitch_mul, pitch_add,
-                            return_mel=False, normalize=None, limiter=False):
+                            return_mel=False, normalize=None, limiter=False, true_peak=False):
         """The list path of `tts` over several chunks, as a three-stage pipeline on three HIP streams: tokenisation + FastPitch
         of the next chunks (host work and ~150 short launches that leave most CUs idle) run under the vocoder + denoiser of the
         previous ones, whose audio is copied to the host on a third stream.  FastPitch sees exactly the chunks of the one-stream
@@ -796,7 +817,8 @@ class FastPitch2Wave(nn.Module):
                 elif dn > 0:
                     wave = self.denoiser.forward_batch(wave, lens_d * hop, dn, nsamples_min=min(n_host))
                 if normalize is not None:
-                    wave = level_waves(wave, lens_d * hop, _take(normalize, pos), self.sample_rate, **_lim(limiter, _take(normalize, pos)))
+                    wave = level_waves(wave, lens_d * hop, _take(normalize, pos), self.sample_rate,
+                                       **_lim(limiter, _take(normalize, pos), true_peak))
                 done = torch.cuda.Event()
                 done.record(s_hg)
             if pending is not None:

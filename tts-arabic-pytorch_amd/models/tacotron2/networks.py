@@ -19,7 +19,7 @@ from text.symbols import EOS_TOKENS, SEPARATOR_TOKEN
 from utils import get_basic_config
 from models.diacritizers import load_vowelizer
 from vocoder import load_hifigan
-from ttsamd.engine import check_limiter, check_normalize, level_waves, per_row
+from ttsamd.engine import check_limiter, check_normalize, check_true_peak, level_waves, per_row
 from vocoder.hifigan.denoiser import Denoiser
 
 from .tacotron2_ms import Tacotron2MS
@@ -155,11 +155,12 @@ class Tacotron2(Tacotron2MS):
         return mel_list
 
 
-def _lim(limiter, normalize):
-    """the `limiter` keyword for a call that gets `normalize`: only where a limiter is asked for and a line of that call asks for a level"""
-    if not limiter or not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
+def _lim(limiter, normalize, true_peak=False):
+    """the `limiter` and `true_peak` keywords for a call that gets `normalize`: only where they are asked for and a line of that call asks
+    for a level"""
+    if not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
         return {}
-    return {'limiter': limiter}
+    return dict({'limiter': limiter} if limiter else {}, **({'true_peak': True} if true_peak else {}))
 
 
 class Tacotron2Wave(nn.Module):
@@ -186,15 +187,16 @@ class Tacotron2Wave(nn.Module):
     @torch.inference_mode()
     def tts_single(self, text_input: str, speed: Union[int, float, None] = None, speaker_id: int = 0,
                    denoise: float = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False, normalize=None,
-                   limiter=False):
+                   limiter=False, true_peak=False):
         check_normalize(normalize, 1)
         limiter = check_limiter(limiter, normalize)
+        check_true_peak(true_peak, normalize, limiter)
         mel_spec = self.model.ttmel_single(text_input, speaker_id, speed, vowelizer, postprocess_mel)
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
         if normalize is not None:
-            wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize))
+            wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize, true_peak))
         if return_mel:
             return wave[0].cpu(), mel_spec
         return wave[0].cpu()
@@ -202,9 +204,10 @@ class Tacotron2Wave(nn.Module):
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: Union[int, float, None] = None, denoise: float = 0,
                   speaker_id: int = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False, normalize=None,
-                  limiter=False):
+                  limiter=False, true_peak=False):
         check_normalize(normalize, len(batch))
         limiter = check_limiter(limiter, normalize)
+        check_true_peak(true_peak, normalize, limiter)
         mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel)
         eng = self.vocoder.engine()
         lens_host = [m.shape[-1] for m in mel_list]
@@ -217,34 +220,37 @@ class Tacotron2Wave(nn.Module):
         if denoise > 0:
             wave = self.denoiser.forward_batch(wave, lens * eng.hop, denoise, nsamples_min=min(n))
         if normalize is not None:
-            wave = level_waves(wave, lens * eng.hop, normalize, self.sample_rate, **_lim(limiter, normalize))       # on the device, after the denoiser
+            wave = level_waves(wave, lens * eng.hop, normalize, self.sample_rate, **_lim(limiter, normalize, true_peak))    # on the device, after the denoiser
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:348-351); so do we
         return [wave[i, :n[i]].cpu() for i in range(len(mel_list))]
 
     def tts(self, text_buckw: Union[str, List[str]], speed: Union[int, float, None] = None, denoise: float = 0.005,
             speaker_id: int = 0, batch_size: int = 8, vowelizer=None, postprocess_mel: bool = True,
-            return_mel: bool = False, normalize=None, limiter=False) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None, limiter=False, true_peak=False) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:353-426): str -> Tensor[n_samples] (CPU); list -> list of
         tensors, chunked by `batch_size`.
         normalize (not in the reference): the level of every wave, set on the device after the denoiser -- None, 'peak' (x / max|x| *
         0.99), 'lufs' (-23 LUFS, ITU-R BS.1770-4) or a target in LUFS, or for a list of lines one such value per line (as
         FastPitch2Wave.tts takes it).
         limiter (False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db; needs a normalize): the lines with 'lufs' or
-        a target get the full gain towards it and the look-ahead limiter holds their peaks at the ceiling (as FastPitch2Wave.tts)."""
+        a target get the full gain towards it and the look-ahead limiter holds their peaks at the ceiling (as FastPitch2Wave.tts).
+        true_peak (False or True; needs a normalize): the peaks of both are true peaks (utils.audio.true_peak), as FastPitch2Wave.tts."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, vowelizer=vowelizer,
                   postprocess_mel=postprocess_mel, return_mel=return_mel)
         if isinstance(text_buckw, str):
-            return self.tts_single(text_buckw, normalize=normalize, **kw, **({'limiter': limiter} if limiter else {}))
+            return self.tts_single(text_buckw, normalize=normalize, **kw, **({'limiter': limiter} if limiter else {}),
+                                   **({'true_peak': true_peak} if true_peak else {}))
         assert isinstance(text_buckw, list)
         check_normalize(normalize, len(text_buckw))
         limiter = check_limiter(limiter, normalize)
+        check_true_peak(true_peak, normalize, limiter)
         at = (lambda i: normalize[i]) if per_row(normalize) else (lambda i: normalize)
         if batch_size == 1:
-            return [self.tts_single(sample, normalize=at(i), **kw, **_lim(limiter, at(i))) for i, sample in enumerate(text_buckw)]
+            return [self.tts_single(sample, normalize=at(i), **kw, **_lim(limiter, at(i), true_peak)) for i, sample in enumerate(text_buckw)]
         wav_list = []
         for k in range(0, len(text_buckw), batch_size):
             idx = range(k, min(k + batch_size, len(text_buckw)))
             chunk_norm = [at(i) for i in idx] if per_row(normalize) else normalize
-            wav_list += self.tts_batch(text_buckw[k:k + batch_size], normalize=chunk_norm, **kw, **_lim(limiter, chunk_norm))
+            wav_list += self.tts_batch(text_buckw[k:k + batch_size], normalize=chunk_norm, **kw, **_lim(limiter, chunk_norm, true_peak))
         return wav_list

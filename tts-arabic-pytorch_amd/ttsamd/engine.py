@@ -1606,10 +1606,22 @@ class LoudnessEngine:
                                                          _ptr(ws), nbytes, _stream()), 'loudness_measure')
         return loud, peak
 
-    def level(self, wave, lens, mode, target, ceiling=0.99):
+    def true_peak(self, wave, lens=None):
+        """wave [B, n_max], lens int64 [B] or None -> fp32 [B] on the device: the peak of the 4x oversampled row (ttsamd_true_peak;
+        include/ttsamd.h states the interpolator), rounded upward to fp32; 0 for an empty row.  Two launches, no workspace."""
+        wave, lens = self._wave(wave, lens)
+        B, n_max = wave.shape
+        tp = torch.zeros(B, dtype=torch.float32, device=wave.device)
+        if B:
+            with torch.cuda.device(wave.device):
+                L.check(self.lib.ttsamd_true_peak(_ptr(wave), n_max, _ptr(lens), B, _ptr(tp), _stream()), 'true_peak')
+        return tp
+
+    def level(self, wave, lens, mode, target, ceiling=0.99, true_peak=False):
         """wave [B, n_max] fp32 contiguous on the device, scaled IN PLACE up to lens[b] and returned with the gains fp32 [B].
         mode: 0 / 'off', 1 / 'peak' (x / max|x| * target), 2 / 'lufs' (towards `target` LUFS, the gain capped so that the peak stays
-        <= ceiling); mode and target are scalars or one value per row, checked here on the host before they go to the device."""
+        <= ceiling); mode and target are scalars or one value per row, checked here on the host before they go to the device.
+        true_peak: the peak of both modes is the row's true peak (`true_peak`) instead of max |x|."""
         if not isinstance(wave, torch.Tensor) or wave.device.type != 'cuda' or wave.dtype != torch.float32 or not wave.is_contiguous() \
                 or wave.dim() != 2:
             raise L.TtsAmdError('LoudnessEngine.level: expected a contiguous float32 tensor [B, n] on the ROCm device (it is scaled in place)')
@@ -1627,15 +1639,19 @@ class LoudnessEngine:
         gain = torch.ones(B, dtype=torch.float32, device=wave.device)
         if B:
             loud, peak = self.measure(wave, lens)
+            if true_peak:
+                peak = self.true_peak(wave, lens)
             mode_d = torch.tensor([int(m) for m in modes], dtype=torch.int32).to(wave.device)
             with torch.cuda.device(wave.device):
                 L.check(self.lib.ttsamd_wave_level(_ptr(wave), n_max, _ptr(lens), B, _ptr(mode_d), _ptr(_rows_f32(targets, wave.device)),
                                                    float(ceiling), _ptr(loud), _ptr(peak), _ptr(gain), _stream()), 'wave_level')
         return wave, gain
 
-    def limit_samples(self, wave, lens, mode, target, ceiling, max_gain, attack, hold, loudness=None):
+    def limit_samples(self, wave, lens, mode, target, ceiling, max_gain, attack, hold, loudness=None, true_peak=False):
         """ttsamd_wave_limit as it is: attack and hold in samples, max_gain linear, mode int32 [B] and target fp32 [B] ON THE DEVICE
-        (already checked), loudness float64 [B] on the device or None (no mode 2 row) -> (wave, gain fp32 [B], reduction int32 [B])."""
+        (already checked), loudness float64 [B] on the device or None (no mode 2 row) -> (wave, gain fp32 [B], reduction int32 [B]).
+        true_peak: ttsamd_wave_limit_true_peak, the same call with the true-peak detector."""
+        call, what = (self.lib.ttsamd_wave_limit_true_peak, 'wave_limit_true_peak') if true_peak else (self.lib.ttsamd_wave_limit, 'wave_limit')
         B, n_max = wave.shape
         gain = torch.ones(B, dtype=torch.float32, device=wave.device)
         red = torch.full((B,), LIMITER_Q, dtype=torch.int32, device=wave.device)
@@ -1645,18 +1661,19 @@ class LoudnessEngine:
                 raise L.TtsAmdError(f'limit: a batch of {B} rows of {n_max} samples is refused')
             ws = self.limit_ws.get(max(nbytes, 1), wave.device)
             with torch.cuda.device(wave.device):
-                L.check(self.lib.ttsamd_wave_limit(_ptr(wave), n_max, _ptr(lens), B, _ptr(mode), _ptr(target), float(ceiling), float(max_gain),
-                                                   int(attack), int(hold), _ptr(loudness), _ptr(gain), _ptr(red), _ptr(ws), nbytes,
-                                                   _stream()), 'wave_limit')
+                L.check(call(_ptr(wave), n_max, _ptr(lens), B, _ptr(mode), _ptr(target), float(ceiling), float(max_gain), int(attack), int(hold),
+                             _ptr(loudness), _ptr(gain), _ptr(red), _ptr(ws), nbytes, _stream()), what)
         return wave, gain, red
 
-    def limit(self, wave, lens, mode, target, ceiling=0.99, max_gain_db=30.0, attack_ms=1.5, hold_ms=15.0):
+    def limit(self, wave, lens, mode, target, ceiling=0.99, max_gain_db=30.0, attack_ms=1.5, hold_ms=15.0, true_peak=False):
         """The look-ahead limiter (csrc/limiter.hip; include/ttsamd.h states its arithmetic): wave [B, n_max] fp32 contiguous on the
         device, IN PLACE up to lens[b]: row b times its gain, then a gain-reduction curve that keeps |y| <= ceiling exactly and leaves a
         row that stays under the ceiling as fl32(x g).  mode: 0 / 'off', 2 / 'lufs' (towards `target` LUFS, measured here, with no cap
         from the peak), 3 / 'gain' (`target` is a gain in dB); mode and target are scalars or one value per row, checked here on the host.
         The gain is at most max_gain_db.  attack_ms: the look-ahead and the length of both ramps, hold_ms: how long the reduction stays
         after a peak; A = round(attack_ms fs / 1000) <= 1024 samples, R = max(round(hold_ms fs / 1000), A) <= 4096.
+        true_peak: the detector also sees the 4x interpolator's values to either side of a sample (ttsamd_wave_limit_true_peak): the
+        sample peak still stays <= ceiling exactly, the true peak close to it (no exact bound: include/ttsamd.h).
         -> (wave, gain fp32 [B], reduction int32 [B] = the smallest curve value in Q30, LIMITER_Q where nothing was limited)."""
         if not isinstance(wave, torch.Tensor) or wave.device.type != 'cuda' or wave.dtype != torch.float32 or not wave.is_contiguous() \
                 or wave.dim() != 2:
@@ -1679,7 +1696,7 @@ class LoudnessEngine:
         loud = self.measure(wave, lens)[0] if any(int(m) == 2 for m in modes) else None
         mode_d = torch.tensor([int(m) for m in modes], dtype=torch.int32).to(wave.device)
         return self.limit_samples(wave, lens, mode_d, _rows_f32(targets, wave.device), ceiling, 10.0 ** (float(max_gain_db) / 20.0), attack,
-                                  hold, loud)
+                                  hold, loud, true_peak=bool(true_peak))
 
 
 LIMIT_MODES = {'off': 0, 'lufs': 2, 'gain': 3}
@@ -1703,9 +1720,31 @@ def limiter_samples(attack_ms, hold_ms, sample_rate):
     return A, R
 
 
-def limiter_reach(attack, hold):
-    """samples of input before and after a sample that its limited value depends on: (A + R, 2A)"""
-    return attack + hold, 2 * attack
+TRUE_PEAK_REACH = 13                    # the true-peak detector widens the limiter's reach by W + 1 samples on each side (include/ttsamd.h)
+
+
+def limiter_reach(attack, hold, true_peak=False):
+    """samples of input before and after a sample that its limited value depends on: (A + R, 2A), each 13 more with the true-peak
+    detector"""
+    extra = TRUE_PEAK_REACH if true_peak else 0
+    return attack + hold + extra, 2 * attack + extra
+
+
+def true_peak_taps():
+    """-> float64 [3, 25]: the interpolator's phases 1 .. 3 as the kernels take them (ttsamd_true_peak_taps; needs no GPU)"""
+    out = (C.c_double * 75)()
+    L.check(L.load().ttsamd_true_peak_taps(out), 'true_peak_taps')
+    return np.array(out).reshape(3, 25)
+
+
+def check_true_peak(true_peak, normalize, limiter):
+    """Host-side validation of `true_peak` next to `normalize` and `limiter` (both already checked): it has effect only where one of
+    them is set, so True with neither is a ValueError."""
+    if not isinstance(true_peak, (bool, np.bool_)):
+        raise ValueError(f'true_peak: {true_peak!r}: False or True')
+    if true_peak and limiter_spec(limiter) is None and not any(v is not None for v in (normalize if per_row(normalize) else [normalize])):
+        raise ValueError('true_peak: needs normalize or a limiter to work in')
+    return bool(true_peak)
 
 
 def limiter_spec(limiter):
@@ -1899,29 +1938,33 @@ def check_normalize(normalize, n_lines):
         level_spec(normalize)
 
 
-def level_waves(wave, nsamples, normalize, sample_rate=22050, ceiling=0.99, limiter=None):
+def level_waves(wave, nsamples, normalize, sample_rate=22050, ceiling=0.99, limiter=None, true_peak=False):
     """The levelling step of the tts wrappers, after the denoiser and before the copy to the host: wave [B, n_max] on the device, row b
     levelled by its option (`normalize`: one option or one per row) over its nsamples[b] samples.  Only None: the wave as it is.
     limiter (None / False, True or a dict: limiter_spec): the rows with 'lufs' or a target go through the look-ahead limiter
     (LoudnessEngine.limit in mode 2: the full gain towards the target, the peaks held at the limiter's ceiling) instead of the capped
-    gain; 'peak' and None rows keep their path."""
+    gain; 'peak' and None rows keep their path.  true_peak: every peak above is the true peak (LoudnessEngine.level / limit with
+    true_peak=True); with no row to level it is a ValueError, as a limiter is."""
     rows = list(normalize) if per_row(normalize) else [normalize] * wave.shape[0]
     specs = [level_spec(v) for v in rows]
     lim = limiter_spec(limiter)
     if not any(s is not None for s in specs):
         if lim is not None:
             raise ValueError("limiter: needs normalize ('lufs' or a target in LUFS on the rows it is to work on)")
+        if true_peak:
+            raise ValueError('true_peak: needs normalize or a limiter to work in')
         return wave
     if len(specs) != wave.shape[0]:
         raise ValueError(f'normalize: {len(specs)} values for {wave.shape[0]} rows')
     shape = wave.shape
     wave = wave.to(torch.float32).reshape(-1, shape[-1]).contiguous()
     eng = leveller(sample_rate, wave.device)
+    tp = dict(true_peak=True) if true_peak else {}         # without it: the calls as they were
     if lim is None:
-        eng.level(wave, nsamples, [s[0] if s else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling)
+        eng.level(wave, nsamples, [s[0] if s else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling, **tp)
         return wave.reshape(shape)
     if any(s and s[0] == 1 for s in specs):
-        eng.level(wave, nsamples, [1 if s and s[0] == 1 else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling)
+        eng.level(wave, nsamples, [1 if s and s[0] == 1 else 0 for s in specs], [s[1] if s else 0.0 for s in specs], ceiling, **tp)
     if any(s and s[0] == 2 for s in specs):
-        eng.limit(wave, nsamples, [2 if s and s[0] == 2 else 0 for s in specs], [s[1] if s else 0.0 for s in specs], **lim)
+        eng.limit(wave, nsamples, [2 if s and s[0] == 2 else 0 for s in specs], [s[1] if s else 0.0 for s in specs], **lim, **tp)
     return wave.reshape(shape)

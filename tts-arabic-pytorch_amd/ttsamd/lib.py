@@ -163,6 +163,10 @@ SYMBOLS = {
     # look-ahead limiter (csrc/limiter.hip): gain fp32 [B] and reduction int32 [B] (Q30) on the device
     'ttsamd_wave_limit_workspace_bytes': (_I64, [_I32, _I64]),
     'ttsamd_wave_limit': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _F, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    # true peak (csrc/true_peak.hpp): the taps go to a HOST float64 [3][25] and need no GPU; true_peak fp32 [B] on the device
+    'ttsamd_true_peak_taps': (_I32, [C.POINTER(C.c_double)]),
+    'ttsamd_true_peak': (_I32, [_P, _I64, _P, _I32, _P, _P]),
+    'ttsamd_wave_limit_true_peak': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _F, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     # wave-against-wave scores (csrc/wavescore.hip): float64 results, lengths int64 on the device
     'ttsamd_stoi_workspace_bytes': (_I64, [_I32, _I64]),
     'ttsamd_stoi': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I64, _P]),

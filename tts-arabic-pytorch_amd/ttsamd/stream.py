@@ -15,7 +15,9 @@ own).  The "center" framing of '24k' gives an utterance of T frames 256 (T - 1) 
 Levelling inside a stream: with `limiter=` a step runs vocoder -> denoise -> ttsamd_wave_limit (mode 3: the stream's fixed gain in dB and
 the look-ahead limiter, in place on the window rows) -> emit.  A limited sample depends on the input over [i - A - R, i + 2A] only, so
 the windows widen by that reach in frames (`limiter_halo_frames`), as they widen by the resampler's, and the curve is integer
-arithmetic: the chunks put together are the bits of utils.audio.limit on the whole wave."""
+arithmetic: the chunks put together are the bits of utils.audio.limit on the whole wave.  With `true_peak=True` the call is
+ttsamd_wave_limit_true_peak, whose detector reads 13 more samples on each side: the reach, the windows and the carried history grow by
+that, and the chunks are the bits of utils.audio.limit(true_peak=True)."""
 import ctypes as C
 
 import numpy as np
@@ -79,9 +81,11 @@ def resample_halo_frames(o, n, width, hop):
     return -(-resample_reach(o, width) // int(hop))
 
 
-def limiter_halo_frames(attack, hold, hop):
-    """the limiter's reach (A + R samples back, 2A ahead: include/ttsamd.h) in frames of hop samples, rounded up"""
-    return -(-max(int(attack) + int(hold), 2 * int(attack)) // int(hop))
+def limiter_halo_frames(attack, hold, hop, true_peak=False):
+    """the limiter's reach (A + R samples back, 2A ahead, each 13 more with the true-peak detector: include/ttsamd.h) in frames of hop
+    samples, rounded up"""
+    extra = 13 if true_peak else 0
+    return -(-(max(int(attack) + int(hold), 2 * int(attack)) + extra) // int(hop))
 
 
 def chunk_outputs(core_start, core_end, o, n):
@@ -177,12 +181,14 @@ class StreamingVocoder:
     stream's unlimited samples (resampled and encoded as above).  `reduction` holds the last step's smallest curve value per row.
     `bypass = True` skips the limiter's launch (and with it the gain) and leaves everything else as it is: the same windows, the same
     vocoder launches, the same samples carried from step to step (`_carry`), so these are, bit for bit, the samples the limiter works
-    on -- for an A / B comparison."""
+    on -- for an A / B comparison.
+    true_peak (needs a limiter; ValueError without one): the limiter's detector is the true-peak one (ttsamd_wave_limit_true_peak),
+    and the chunks are the bits of utils.audio.limit(true_peak=True)."""
 
     def __init__(self, vocoder, denoiser=None, max_streams=32, max_frames=4096, chunk_frames=64, first_chunk_frames=32, pcm16=False,
-                 sample_rate=None, encoding=None, lowpass_filter_width=6, rolloff=0.99, limiter=None):
+                 sample_rate=None, encoding=None, lowpass_filter_width=6, rolloff=0.99, limiter=None, true_peak=False):
         import torch
-        from .engine import DenoiserEngine, _Workspace, limiter_samples, limiter_spec
+        from .engine import DenoiserEngine, _Workspace, limiter_reach, limiter_samples, limiter_spec
         if min(int(max_streams), int(max_frames), int(chunk_frames), int(first_chunk_frames)) < 1:
             raise ValueError('StreamingVocoder: max_streams, max_frames, chunk_frames and first_chunk_frames must be >= 1')
         source_rate = int(getattr(vocoder, 'sampling_rate', None) or (getattr(vocoder, 'h', None) or {}).get('sampling_rate') or 22050)
@@ -227,12 +233,15 @@ class StreamingVocoder:
             self._rs_halo = resample_halo_frames(*self._rs, self.hop)
         # the limiter (ttsamd_wave_limit, mode 3) between the denoiser and the emit: its reach widens the windows as the resampler's does
         self._lim = limiter_spec(limiter)
+        self._lim_tp = bool(true_peak)
+        if self._lim_tp and self._lim is None:
+            raise ValueError('StreamingVocoder: true_peak needs the limiter (StreamingVocoder(..., limiter=True))')
         self._lim_halo = 0
         self.bypass = False
         self.reduction = None           # int32 [rows] on the device after a step with a limiter: min of the curve per window (Q30)
         if self._lim is not None:
             self._lim_ar = limiter_samples(self._lim['attack_ms'], self._lim['hold_ms'], source_rate)
-            self._lim_halo = limiter_halo_frames(*self._lim_ar, self.hop)
+            self._lim_halo = limiter_halo_frames(*self._lim_ar, self.hop, self._lim_tp)
             self._lim_ws = _Workspace()
         self._rs_halo += self._lim_halo         # everything below plans with the sum: the emit reads limited samples
         self._core_cap = max_core_frames(first_chunk_frames, chunk_frames)
@@ -252,7 +261,8 @@ class StreamingVocoder:
             self._lim_mode = torch.full((self._rows,), 3, dtype=torch.int32, device=dev)
             # samples behind / ahead of a core that its chunk depends on through the limiter (and the resampler behind it)
             rs_reach = resample_reach(self._rs[0], self._rs[2]) if self._rs else 0
-            self._lim_lb, self._lim_la = rs_reach + sum(self._lim_ar), rs_reach + 2 * self._lim_ar[0]
+            back, ahead = limiter_reach(*self._lim_ar, true_peak=self._lim_tp)
+            self._lim_lb, self._lim_la = rs_reach + back, rs_reach + ahead
             self._hist = torch.zeros(self.max_streams, max(self._lim_lb + self._lim_la, 1), dtype=torch.float32, device=dev)
         self._flip = 0
         self._free = list(range(self.max_streams))
@@ -430,10 +440,10 @@ class StreamingVocoder:
                 nb = lib.ttsamd_wave_limit_workspace_bytes(W, n_max)
                 lws = self._lim_ws.get(max(nb, 1), self.device)
                 self.reduction = self._lim_red[self._flip][:W]
-                L.check(lib.ttsamd_wave_limit(_ptr(self._wave), n_max, _ptr(ends_d), W, _ptr(self._lim_mode), _ptr(gains_d),
-                                              float(self._lim['ceiling']), 10.0 ** (self._lim['max_gain_db'] / 20.0), self._lim_ar[0],
-                                              self._lim_ar[1], None, _ptr(self._lim_gain), _ptr(self.reduction), _ptr(lws), nb, _stream()),
-                        'wave_limit')
+                call, what = (lib.ttsamd_wave_limit_true_peak, 'wave_limit_true_peak') if self._lim_tp else (lib.ttsamd_wave_limit, 'wave_limit')
+                L.check(call(_ptr(self._wave), n_max, _ptr(ends_d), W, _ptr(self._lim_mode), _ptr(gains_d), float(self._lim['ceiling']),
+                             10.0 ** (self._lim['max_gain_db'] / 20.0), self._lim_ar[0], self._lim_ar[1], None, _ptr(self._lim_gain),
+                             _ptr(self.reduction), _ptr(lws), nb, _stream()), what)
             if self._resampled:
                 hop = self.hop
                 L.check(lib.ttsamd_stream_emit_resampled(self._rs_eng.handle if self._rs_eng else None, _ptr(self._wave), W, w_max, hop,

@@ -254,41 +254,64 @@ def loudness(wave, sample_rate=22050, lens=None):
     return _leveller(sample_rate, x.device).measure(x, lens)[0]
 
 
-def _level(wave, lens, sample_rate, mode, target, ceiling, what):
+@torch.inference_mode()
+def true_peak(wave, lens=None):
+    """True peak of every row of wave [..., n] -> fp32 tensor [rows] on the device, linear: the largest magnitude among the samples and
+    the three points between each sample and the next (and behind the last) of a 4x interpolation with a 25-tap Hann-windowed sinc
+    (include/ttsamd.h states the arithmetic), in float64, rounded upward to fp32; 0 for an empty row.  The interpolator needs no rate.
+    Specified by its arithmetic; parity with libebur128 / pyloudnorm is not pinned.  lens (int64 [rows]): samples per row of a ragged
+    batch; nothing behind a row's length is read.  No host synchronisation."""
+    x, lens = _level_rows(wave, lens, 'true_peak')
+    return _leveller(22050, x.device).true_peak(x, lens)
+
+
+@torch.inference_mode()
+def true_peak_db(wave, lens=None):
+    """`true_peak` in dBTP: 20 log10 of it as float64 [rows] on the device, -inf for a row of zeros or an empty row"""
+    return 20.0 * torch.log10(true_peak(wave, lens).to(torch.float64))
+
+
+def _level(wave, lens, sample_rate, mode, target, ceiling, what, true_peak=False):
     x, lens = _level_rows(wave, lens, what)
     if x.data_ptr() == wave.data_ptr():
         x = x.clone()                           # the caller's tensor stays as it is
-    out, _ = _leveller(sample_rate, x.device).level(x, lens, mode, target, ceiling)
+    out, _ = _leveller(sample_rate, x.device).level(x, lens, mode, target, ceiling, **(dict(true_peak=True) if true_peak else {}))
     return out.reshape(wave.shape)
 
 
 @torch.inference_mode()
-def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None, limiter=False):
+def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None, limiter=False, true_peak=False):
     """Every row of wave [..., n] scaled by ONE gain to target_lufs (a float or one per row); where that would lift the row's peak
     above peak_ceiling, the gain is ceiling / peak instead (a cap on the gain, no limiter).  A silent row is returned as it is.  A new
     tensor on the device; the samples behind lens[row] are copied unchanged.
     limiter (True, or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db): the full gain towards the target instead, and the
-    look-ahead limiter (`limit`) holds the peaks at the ceiling (peak_ceiling unless the dict names one), so the target is reached."""
+    look-ahead limiter (`limit`) holds the peaks at the ceiling (peak_ceiling unless the dict names one), so the target is reached.
+    true_peak: the ceiling is a true-peak ceiling (dBTP as a linear value): the cap uses `true_peak` of the row, and the levelled row's
+    true peak stays within peak_ceiling (1 + H 2^-24), H = 2.31 (the fp32 rounding of the output: include/ttsamd.h); with a limiter, its detector is the true-peak one (no exact bound: see `limit`)."""
     spec = limiter_spec(limiter)
     if spec is None:
-        return _level(wave, lens, sample_rate, 2, target_lufs, peak_ceiling, 'normalize_loudness')
+        return _level(wave, lens, sample_rate, 2, target_lufs, peak_ceiling, 'normalize_loudness', true_peak)
     if not (isinstance(limiter, dict) and 'ceiling' in limiter):
         spec['ceiling'] = peak_ceiling
     x, lens = _level_rows(wave, lens, 'normalize_loudness')
     if x.data_ptr() == wave.data_ptr():
         x = x.clone()
-    out, _, _ = _leveller(sample_rate, x.device).limit(x, lens, 2, target_lufs, **spec)
+    out, _, _ = _leveller(sample_rate, x.device).limit(x, lens, 2, target_lufs, **spec, **(dict(true_peak=True) if true_peak else {}))
     return out.reshape(wave.shape)
 
 
 @torch.inference_mode()
-def limit(wave, gain_db=0.0, ceiling=0.99, attack_ms=1.5, hold_ms=15.0, sample_rate=22050, lens=None):
+def limit(wave, gain_db=0.0, ceiling=0.99, attack_ms=1.5, hold_ms=15.0, sample_rate=22050, lens=None, true_peak=False):
     """A fixed gain and the look-ahead limiter (include/ttsamd.h states the arithmetic): every row of wave [..., n] times 10^(gain_db /
     20) (a float or one per row), then a gain-reduction curve in Q30 integers that looks attack_ms ahead, holds hold_ms and keeps
     |y| <= ceiling exactly; samples that no peak reaches are fl32(x g) bit for bit.  -> (a new tensor on the device, reduction_db
     float64 [rows] on the device: the deepest gain reduction in dB, 0 where nothing was limited).  The samples behind lens[row] are copied
     unchanged.  This is what a stream with `limiter=` applies to its windows: the concatenated chunks have the bits of this call on the
-    whole wave."""
+    whole wave.
+    true_peak: the detector is max(|u[i]|, the 4x interpolator's values between i - 1 and i + 1) instead of |u[i]|, so a peak between
+    two samples pulls the gain down as one on a sample does.  |y| <= ceiling still holds exactly; the true peak of y lands close to the
+    ceiling but has no exact bound (the gain curve varies under the interpolator's 25 taps: DESIGN.md section 4 has the measured
+    overshoot)."""
     x, lens = _level_rows(wave, lens, 'limit')
     if x.data_ptr() == wave.data_ptr():
         x = x.clone()
@@ -302,15 +325,17 @@ def limit(wave, gain_db=0.0, ceiling=0.99, attack_ms=1.5, hold_ms=15.0, sample_r
     lens_d = torch.full((B,), x.shape[1], dtype=torch.int64, device=x.device) if lens is None else lens
     mode = torch.full((B,), 3, dtype=torch.int32, device=x.device)
     target = torch.tensor([float(v) for v in gains], dtype=torch.float32).to(x.device)
-    out, _, red = eng.limit_samples(x, lens_d, mode, target, ceiling, LIMITER_NO_MAX_GAIN, attack, hold)
+    out, _, red = eng.limit_samples(x, lens_d, mode, target, ceiling, LIMITER_NO_MAX_GAIN, attack, hold,
+                                    **(dict(true_peak=True) if true_peak else {}))
     return out.reshape(wave.shape), 20.0 * torch.log10(red.to(torch.float64) / float(LIMITER_Q))
 
 
 @torch.inference_mode()
-def peak_normalize(wave, peak=0.99, lens=None):
+def peak_normalize(wave, peak=0.99, lens=None, true_peak=False):
     """`peak_normalise` for a batch on the device: every row of wave [..., n] becomes x / max|x| * peak over its own samples (the bits
-    of peak_normalise on that row); an all-zero row is returned as it is.  A new tensor on the device."""
-    return _level(wave, lens, 22050, 1, peak, 0.99, 'peak_normalize')
+    of peak_normalise on that row); an all-zero row is returned as it is.  A new tensor on the device.
+    true_peak: x / TP * peak with TP = `true_peak` of the row, so `peak` is where the true peak lands."""
+    return _level(wave, lens, 22050, 1, peak, 0.99, 'peak_normalize', true_peak)
 
 
 def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99, resampling_method='sinc_interp_hann', beta=None,
