@@ -1049,6 +1049,70 @@ int32_t ttsamd_wave_limit_true_peak(float* wave, int64_t wave_stride, const int6
                                     const double* loudness, float* gain_out, int32_t* reduction_out, void* workspace,
                                     int64_t workspace_bytes, void* stream);
 
+/* ---- loudness meter (csrc/loudness.hip): EBU R 128 / Tech 3341 / 3342 momentary and short-term loudness, their maxima and the
+ * loudness range, per row of a ragged mono batch and inside a stream.  New symbols only, added WITHOUT a bump.  Specified by the
+ * arithmetic below; parity with libebur128 is left unpinned: libebur128 takes its short-term blocks for the range at another hop
+ * (one block per second, here one per step of 100 ms), so the two populations of blocks, and with them the percentiles, differ.
+ * Everything is float64.  With y, step, block, S (the segment) and Q = step / S of the output levelling above, for a row of n samples:
+ *   step energies   u[i] = the sum of the Q segment sums of y^2 of step i, ascending, 0 <= i < U = n / step;
+ *   momentary       z[j] = (((u[j] + u[j+1]) + u[j+2]) + u[j+3]) / block, 0 <= j < J: exactly the block energies of
+ *                   ttsamd_loudness_measure, the short-row rule included (0 < n < block: J = 1, z[0] = mean of y^2 over the n samples;
+ *                   n = 0: J = 0); M[j] = -0.691 + 10 log10 z[j];
+ *   integrated loudness and peak: those of ttsamd_loudness_measure, bit for bit;
+ *   short-term      JS = U - 29 values when U >= 30, else none; s[j] = (u[j] + .. + u[j+29]) / (30 step), summed ascending from 0;
+ *                   S[j] = -0.691 + 10 log10 s[j].  The hop is one step, the overlap 2.9 s (Tech 3342 asks for at least 2 s);
+ *   maxima          max_momentary = max_j M[j], max_short_term = max_j S[j]; -inf when there is no value;
+ *   loudness range  keep the S[j] > -70; Gamma = -0.691 + 10 log10(mean of their s[j]) - 20; keep the S[j] > Gamma; with the k
+ *                   survivors sorted ascending as v, LRA = v[((k - 1) 95 + 50) / 100] - v[((k - 1) 10 + 50) / 100] (integer
+ *                   divisions: round((k - 1) p)); 0 when k = 0.
+ * The three filter launches of ttsamd_loudness_measure, then ONE launch with a block per row: four launches whatever the lengths.
+ * The percentiles are taken by rank counting (the rank of a survivor is the number of survivors below it, ties by index; the keys go
+ * through LDS in tiles), so there is no cap on the length of a row.  Every sum has a fixed order that depends on the row's own length
+ * only (the mean for Gamma: strided partial sums and an LDS tree, as the gates of the integrated loudness): row b of a batch has
+ * the bits it has alone.  No atomics. */
+/* bytes of workspace ttsamd_loudness_meter needs; -1: refused as ttsamd_loudness_workspace_bytes refuses */
+int64_t ttsamd_loudness_meter_workspace_bytes(int32_t batch, int64_t wave_stride, int32_t sample_rate);
+/* wave, nsamples, batch, sample_rate as ttsamd_loudness_measure.  Device outputs: loudness float64 [batch], peak fp32 [batch],
+ * loudness_range, max_momentary, max_short_term float64 [batch], counts int64 [batch][2] = (J, JS).  momentary
+ * [batch][momentary_stride] and short_term [batch][short_term_stride] float64 may be NULL; a stride is at least the J / JS of a row of
+ * wave_stride samples, and entries at and past a row's own count are not written.  Nothing is read back to the host.
+ * TTSAMD_EINVAL (nothing launched): a NULL pointer other than the two series, batch outside 1 .. 65535, a rate out of range, a series
+ * stride too small, a workspace smaller than ttsamd_loudness_meter_workspace_bytes. */
+int32_t ttsamd_loudness_meter(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t sample_rate,
+                              double* loudness, float* peak, double* loudness_range, double* max_momentary, double* max_short_term,
+                              int64_t* counts, double* momentary, int64_t momentary_stride, double* short_term, int64_t short_term_stride,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+/* Stream meter: a device-resident state of `slots` slots, each a stream of at most max_samples samples at sample_rate; every call on a
+ * state names the same three numbers.  A slot holds the four filter state doubles behind its last whole segment, the samples of the
+ * unfinished segment (fewer than S), the sum of the finished segments of the unfinished step, the step energies u so far, the running
+ * peak and a status word.  `slot`: device int32 [rows], one slot per row, no slot twice in a call; a row whose slot does not exist is
+ * left out (push: its three readings are -inf; result: status 2).
+ * push: chunks [rows][chunk_stride] fp32, nsamples device int64 [rows] clamped to [0, chunk_stride], any length.  Four launches: the
+ * three filter launches run the row "unfinished segment, then the chunk" from the slot's filter state (the segments of a stream lie
+ * on the stream's own grid whatever the chunking), the fourth takes the whole segments in: segment sums are added to the unfinished
+ * step in order, a finished step goes to u.  Then per row: momentary = M of the last four steps and short_term = S of the last
+ * thirty (-inf before there are four / thirty), integrated = both gates over all blocks so far (-inf before the first block: the
+ * short-row rule is applied by result only).  A push that would take a slot beyond max_samples takes nothing in and sets bit 0 of
+ * the slot's status; the readings are those of the samples so far.  A stream's values depend on its own samples and chunking only,
+ * not on which other slots share the call.  Against the whole-wave entry the sums have the same order, but the filter state in front
+ * of a segment comes through scans that start anew at every push: the results agree within 1e-9 LU, not bit for bit; the peak exactly.
+ * result: loudness, loudness_range, max_momentary, max_short_term (float64 [rows]), peak (fp32 [rows]), counts (int64 [rows][2]) as
+ * the whole-wave entry defines them over the samples so far (the short-row rule included), status int32 [rows].  One launch; the slot
+ * is not changed.  reset: the slots named start again at zero samples (a new state is reset before its first push).
+ * TTSAMD_EINVAL (nothing launched): a NULL pointer, slots or rows outside 1 .. 65535, max_samples outside 1 .. 2^40 - 1, a rate out
+ * of range, a state smaller than ttsamd_meter_state_bytes, a workspace smaller than ttsamd_meter_push_workspace_bytes.
+ * Nothing is read back to the host. */
+int64_t ttsamd_meter_state_bytes(int32_t slots, int64_t max_samples, int32_t sample_rate);               /* -1: refused */
+int64_t ttsamd_meter_push_workspace_bytes(int32_t rows, int64_t chunk_stride, int32_t sample_rate);      /* -1: refused */
+int32_t ttsamd_meter_reset(void* state, int64_t state_bytes, int32_t slots, int64_t max_samples, int32_t sample_rate, const int32_t* slot,
+                           int32_t rows, void* stream);
+int32_t ttsamd_meter_push(void* state, int64_t state_bytes, int32_t slots, int64_t max_samples, int32_t sample_rate, const float* chunks,
+                          int64_t chunk_stride, const int64_t* nsamples, const int32_t* slot, int32_t rows, double* momentary,
+                          double* short_term, double* integrated, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t ttsamd_meter_result(void* state, int64_t state_bytes, int32_t slots, int64_t max_samples, int32_t sample_rate, const int32_t* slot,
+                            int32_t rows, double* loudness, double* loudness_range, double* max_momentary, double* max_short_term, float* peak,
+                            int64_t* counts, int32_t* status, void* stream);
+
 /* ---- wave-against-wave scores (csrc/wavescore.hip): STOI / ESTOI at 10 kHz, SI-SDR / SNR and a log-spectral distance between the rows
  * of two ragged mono batches that are sample-aligned (copy synthesis, a precision mode against fp32, a delivery format against the float
  * wave; free-running synthesis is NOT aligned with a recording and has no meaningful score here).  Both waves are [batch][wave_stride]

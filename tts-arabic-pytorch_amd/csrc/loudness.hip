@@ -13,6 +13,10 @@
 //   4. loud_gate_kernel: one block per row adds the segment sums to block energies, applies the two gates and writes L and the peak.
 // Four launches whatever the lengths.  Every sum has a fixed order that depends on the row's own length only (a thread's samples in
 // order, a block's segments in order, strided partial sums and an LDS tree over the blocks), so row b of a batch has the bits it has alone.
+// The meter (ttsamd_loudness_meter): launches 1 - 3, then loud_meter_kernel, one block per row: step energies, momentary and short-term
+// series with their maxima, the integrated loudness by the gates loud_gate_kernel uses (the same bits), the loudness range by rank
+// counting.  The stream meter (ttsamd_meter_*) keeps a slot per stream (MeterHead and its planes); a push runs launches 1 - 3 as their
+// <true> instantiations over "the slot's unfinished segment, then the chunk" from the slot's filter state, then meter_push_kernel.
 // wave_level_kernel: every block works its row's gain out again from L, peak, mode and target (a few float64 operations) and scales
 // its share of the row in place.
 // true_peak_kernel (ttsamd_true_peak): the peak of the 4x interpolated row from the chains of true_peak.hpp; its result can stand in for
@@ -116,29 +120,86 @@ __device__ __forceinline__ int64_t loud_len(const int64_t* __restrict__ ns, cons
     return max((int64_t)0, min(ns[b], stride));
 }
 
+// Stream meter (ttsamd_meter_*): what a slot carries from push to push.  The three filter kernels below run a push as the row
+// "pending samples, then the chunk" from the carried filter state (their <true> instantiations); <false> is the whole-wave path.
+struct MeterHead {
+    double fst[4];                    // the filter state behind the last whole segment
+    double upart;                     // the finished segments of the unfinished step, added in order
+    int64_t n;                        // samples so far: n / S whole segments, (n / S) / Q whole steps in u
+    float peak;
+    int32_t status;                   // bit 0: a push beyond max_samples was dropped
+    float pend[LD_SMAX];              // the n % S samples of the unfinished segment
+};
+struct MeterStream {
+    char* state;                      // [nslots][slot_bytes]: a MeterHead, then u, z / s scratch and key scratch, [ucap] doubles each
+    const int32_t* slots;             // device [rows]
+    int64_t slot_bytes, max_samples, ucap;
+    int32_t nslots;
+};
+constexpr int64_t METER_HEAD_BYTES = 512;
+static_assert(sizeof(MeterHead) <= METER_HEAD_BYTES, "meter head");
+
+__device__ __forceinline__ MeterHead* meter_head(const MeterStream& ms, const int b) {
+    const int32_t sl = ms.slots[b];
+    return sl >= 0 && sl < ms.nslots ? (MeterHead*)(ms.state + (int64_t)sl * ms.slot_bytes) : nullptr;
+}
+__device__ __forceinline__ double* meter_plane(MeterHead* h, const MeterStream& ms, const int i) {
+    return (double*)((char*)h + METER_HEAD_BYTES) + (int64_t)i * ms.ucap;
+}
+// the row a push filters: r pending samples and c new ones; a bad slot or a push beyond max_samples takes nothing in (c = 0)
+__device__ __forceinline__ MeterHead* meter_row(const MeterStream& ms, const int64_t* __restrict__ ns, const int b, const int64_t stride,
+                                                const int S, int& r, int64_t& c) {
+    MeterHead* h = meter_head(ms, b);
+    r = 0;
+    c = 0;
+    if (!h) return h;
+    c = loud_len(ns, b, stride);
+    if (h->n + c > ms.max_samples) c = 0;
+    r = (int)(h->n % S);
+    return h;
+}
+
 // the block's tile (LD_T segments of S samples from sample `base`) into LDS, zeros at and past n; returns the thread's max |x|
+// (a push: the first r samples of the row are the slot's pending ones)
+template <bool ST>
 __device__ __forceinline__ float loud_load_tile(const float* __restrict__ wb, const int64_t base, const int64_t n, const int S,
-                                                float* __restrict__ xs) {
+                                                float* __restrict__ xs, const float* pend = nullptr, const int r = 0) {
     float m = 0.f;
     for (int idx = threadIdx.x; idx < LD_T * S; idx += LD_T) {
         const int sg = idx / S, j = idx - sg * S;
         const int64_t g = base + idx;
-        const float v = g < n ? wb[g] : 0.f;
+        float v;
+        if constexpr (ST)
+            v = g < n ? (g < r ? pend[g] : wb[g - r]) : 0.f;
+        else
+            v = g < n ? wb[g] : 0.f;
         m = fmaxf(m, fabsf(v));
         xs[sg * LD_SP + j] = v;
     }
     return m;
 }
 
+template <bool ST>
 __global__ __launch_bounds__(LD_T) void loud_zero_state_kernel(const float* __restrict__ wave, int64_t stride, const int64_t* __restrict__ ns,
                                                                LoudPlan p, int64_t K, int64_t NB, double* __restrict__ st,
-                                                               float* __restrict__ pk) {
+                                                               float* __restrict__ pk, MeterStream ms) {
     __shared__ float xs[LD_T * LD_SP];
     __shared__ float red[LD_T / 64];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int64_t n = loud_len(ns, b, stride), base = (int64_t)blockIdx.x * LD_T * p.S;
+    int64_t n;
+    int r = 0;
+    const float* pend = nullptr;
+    if constexpr (ST) {
+        int64_t c;
+        const MeterHead* h = meter_row(ms, ns, b, stride, p.S, r, c);
+        n = r + c;
+        if (h) pend = h->pend;
+    } else {
+        n = loud_len(ns, b, stride);
+    }
+    const int64_t base = (int64_t)blockIdx.x * LD_T * p.S;
     if (base >= n) return;                                     // the whole block: nothing of the row is here
-    float m = loud_load_tile(wave + (int64_t)b * stride, base, n, p.S, xs);
+    float m = loud_load_tile<ST>(wave + (int64_t)b * stride, base, n, p.S, xs, pend, r);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
     if ((tid & 63) == 0) red[tid >> 6] = m;
@@ -154,12 +215,27 @@ __global__ __launch_bounds__(LD_T) void loud_zero_state_kernel(const float* __re
     for (int i = 0; i < 4; ++i) o[i] = s[i];
 }
 
+template <bool ST>
 __global__ __launch_bounds__(64) void loud_scan_kernel(const int64_t* __restrict__ ns, int64_t stride, LoudPlan p, int64_t K,
-                                                       double* __restrict__ st) {
+                                                       double* __restrict__ st, MeterStream ms) {
     __shared__ double P[6][16];                                // M^(2^d)
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int64_t n = loud_len(ns, b, stride), Kr = (n + p.S - 1) / p.S;
-    if (Kr < 2) return;                                        // one segment: nothing to carry
+    int64_t n;
+    double carry[4] = {0.0, 0.0, 0.0, 0.0};                    // the state in front of this run of 64 segments
+    if constexpr (ST) {
+        int r;
+        int64_t c;
+        const MeterHead* h = meter_row(ms, ns, b, stride, p.S, r, c);
+        n = r + c;
+        if (h) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) carry[i] = h->fst[i];
+        }
+    } else {
+        n = loud_len(ns, b, stride);
+    }
+    const int64_t Kr = (n + p.S - 1) / p.S;
+    if (Kr < (ST ? 1 : 2)) return;                             // one segment from a zero state: nothing to carry
     if (lane < 16) P[0][lane] = p.M[lane];
     __syncthreads();
     for (int d = 1; d < 6; ++d) {
@@ -173,7 +249,6 @@ __global__ __launch_bounds__(64) void loud_scan_kernel(const int64_t* __restrict
         __syncthreads();
     }
     double* sb = st + (int64_t)b * K * 4;
-    double carry[4] = {0.0, 0.0, 0.0, 0.0};                    // the state in front of this run of 64 segments
     for (int64_t k0 = 0; k0 < Kr; k0 += 64) {
         const int64_t k = k0 + lane;
         double v[4] = {0.0, 0.0, 0.0, 0.0};
@@ -216,13 +291,25 @@ __global__ __launch_bounds__(64) void loud_scan_kernel(const int64_t* __restrict
     }
 }
 
+template <bool ST>
 __global__ __launch_bounds__(LD_T) void loud_energy_kernel(const float* __restrict__ wave, int64_t stride, const int64_t* __restrict__ ns,
-                                                           LoudPlan p, int64_t K, const double* __restrict__ st, double* __restrict__ seg) {
+                                                           LoudPlan p, int64_t K, const double* __restrict__ st, double* __restrict__ seg,
+                                                           MeterStream ms) {
     __shared__ float xs[LD_T * LD_SP];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int64_t n = loud_len(ns, b, stride), base = (int64_t)blockIdx.x * LD_T * p.S;
+    int64_t n;
+    int r = 0;
+    const MeterHead* h = nullptr;
+    if constexpr (ST) {
+        int64_t c;
+        h = meter_row(ms, ns, b, stride, p.S, r, c);
+        n = r + c;
+    } else {
+        n = loud_len(ns, b, stride);
+    }
+    const int64_t base = (int64_t)blockIdx.x * LD_T * p.S;
     if (base >= n) return;
-    loud_load_tile(wave + (int64_t)b * stride, base, n, p.S, xs);
+    loud_load_tile<ST>(wave + (int64_t)b * stride, base, n, p.S, xs, h ? h->pend : nullptr, r);
     __syncthreads();
     const int64_t k = (int64_t)blockIdx.x * LD_T + tid;
     if (k * p.S >= n) return;
@@ -231,6 +318,9 @@ __global__ __launch_bounds__(LD_T) void loud_energy_kernel(const float* __restri
         const double* i0 = st + ((int64_t)b * K + k - 1) * 4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[i] = i0[i];
+    } else if constexpr (ST) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] = h->fst[i];          // n > 0 here, so the slot is a good one
     }
     const int m = (int)min((int64_t)p.S, n - k * p.S);         // the last segment of the row may be short
     const float* xr = xs + tid * LD_SP;
@@ -260,6 +350,59 @@ __device__ __forceinline__ void loud_block_sum(double& v, int& c, double* rs, in
     c = rc[0];
 }
 
+// both gates over the block energies z[0 .. Jr) (written by this block, a barrier behind them): the integrated loudness, in every thread
+__device__ __forceinline__ double loud_gates(const double* z, const int64_t Jr, double* rs, int* rc) {
+    const int tid = threadIdx.x;
+    double sa = 0.0;
+    int ca = 0;
+    for (int64_t j = tid; j < Jr; j += LD_GT) {
+        const double zj = z[j];
+        if (-0.691 + 10.0 * log10(zj) > -70.0) {
+            sa += zj;
+            ++ca;
+        }
+    }
+    loud_block_sum(sa, ca, rs, rc);
+    if (ca == 0) return -INFINITY;
+    const double gamma = -0.691 + 10.0 * log10(sa / (double)ca) - 10.0;
+    double sr = 0.0;
+    int cr = 0;
+    for (int64_t j = tid; j < Jr; j += LD_GT) {
+        const double zj = z[j], l = -0.691 + 10.0 * log10(zj);
+        if (l > -70.0 && l > gamma) {
+            sr += zj;
+            ++cr;
+        }
+    }
+    loud_block_sum(sr, cr, rs, rc);
+    return cr > 0 ? -0.691 + 10.0 * log10(sr / (double)cr) : -INFINITY;
+}
+
+// the largest of the threads' values, in every thread
+__device__ __forceinline__ double loud_block_max(const double v, double* rs) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    rs[tid] = v;
+    __syncthreads();
+    for (int d = LD_GT / 2; d >= 1; d >>= 1) {
+        if (tid < d) rs[tid] = fmax(rs[tid], rs[tid + d]);
+        __syncthreads();
+    }
+    return rs[0];
+}
+
+// the block's partial peaks of a row of Kr segments -> max |x|, in thread 0
+__device__ __forceinline__ float loud_row_peak(const float* __restrict__ pkb, const int64_t Kr, float* rm) {
+    const int tid = threadIdx.x;
+    float m = 0.f;
+    for (int64_t i = tid; i < (Kr + LD_T - 1) / LD_T; i += LD_GT) m = fmaxf(m, pkb[i]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
+    if ((tid & 63) == 0) rm[tid >> 6] = m;
+    __syncthreads();
+    return fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+}
+
 __global__ __launch_bounds__(LD_GT) void loud_gate_kernel(const int64_t* __restrict__ ns, int64_t stride, int step, int S, int Q, int64_t K,
                                                           int64_t NB, int64_t J, const double* __restrict__ seg, const float* __restrict__ pk,
                                                           double* __restrict__ zb, double* __restrict__ loudness, float* __restrict__ peak) {
@@ -270,13 +413,8 @@ __global__ __launch_bounds__(LD_GT) void loud_gate_kernel(const int64_t* __restr
     const int64_t n = loud_len(ns, b, stride), Kr = (n + S - 1) / S, block = 4 * (int64_t)step;
     const double* sg = seg + (int64_t)b * K;
     double* z = zb + (int64_t)b * J;
-    float m = 0.f;
-    for (int64_t i = tid; i < (Kr + LD_T - 1) / LD_T; i += LD_GT) m = fmaxf(m, pk[(int64_t)b * NB + i]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = fmaxf(m, __shfl_xor(m, d, 64));
-    if ((tid & 63) == 0) rm[tid >> 6] = m;
-    __syncthreads();
-    if (tid == 0) peak[b] = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+    const float m = loud_row_peak(pk + (int64_t)b * NB, Kr, rm);
+    if (tid == 0) peak[b] = m;
     if (n == 0) {
         if (tid == 0) loudness[b] = -INFINITY;
         return;
@@ -302,36 +440,275 @@ __global__ __launch_bounds__(LD_GT) void loud_gate_kernel(const int64_t* __restr
         }
     }
     __syncthreads();                                           // z[0] of a short row is read by every thread (a block's own writes)
+    const double L = loud_gates(z, Jr, rs, rc);
+    if (tid == 0) loudness[b] = L;
+}
+
+// ---- the meter (include/ttsamd.h, "loudness meter"): what comes after the step energies ----
+constexpr int MT_TILE = 1024;                                  // keys per LDS tile of the rank count
+struct MeterLds {
+    double rs[LD_GT], tile[MT_TILE], lohi[2];
+    int rc[LD_GT];
+    float rm[LD_GT / 64];
+};
+struct MeterOut {
+    double L, lra, maxm, maxs;
+    int64_t J, JS;
+};
+
+// One block, from the step energies u[0 .. U) of a row of n samples: momentary blocks z (z[0] of a short row is there already), both
+// gates, the short-term series, its two gates and the two percentiles by rank counting.  z is scratch of max(J, JS) doubles (the
+// short-term energies take the blocks' place once those are used up), key of JS.  Mrow / Srow may be null.  The results are in every thread.
+__device__ __forceinline__ MeterOut meter_windows(const double* u, const int64_t U, const int64_t n, const int step, double* z, double* key,
+                                                  double* Mrow, double* Srow, MeterLds& l) {
+    const int tid = threadIdx.x;
+    const int64_t block = 4 * (int64_t)step;
+    MeterOut o;
+    o.J = n == 0 ? 0 : (n < block ? 1 : U - 3);
+    o.JS = U >= 30 ? U - 29 : 0;
+    if (n >= block)
+        for (int64_t j = tid; j < o.J; j += LD_GT) z[j] = (((u[j] + u[j + 1]) + u[j + 2]) + u[j + 3]) / (double)block;
+    __syncthreads();
+    o.L = loud_gates(z, o.J, l.rs, l.rc);
+    double mx = -INFINITY;
+    for (int64_t j = tid; j < o.J; j += LD_GT) {
+        const double m = -0.691 + 10.0 * log10(z[j]);
+        if (Mrow) Mrow[j] = m;
+        mx = fmax(mx, m);
+    }
+    o.maxm = loud_block_max(mx, l.rs);                         // (its barriers: z is free from here)
+    double* se = z;
     double sa = 0.0;
     int ca = 0;
-    for (int64_t j = tid; j < Jr; j += LD_GT) {
-        const double zj = z[j];
-        if (-0.691 + 10.0 * log10(zj) > -70.0) {
-            sa += zj;
+    mx = -INFINITY;
+    for (int64_t j = tid; j < o.JS; j += LD_GT) {
+        double e = 0.0;
+        for (int q = 0; q < 30; ++q) e += u[j + q];
+        e /= 30.0 * (double)step;
+        const double s = -0.691 + 10.0 * log10(e);
+        se[j] = e;
+        key[j] = s;
+        if (Srow) Srow[j] = s;
+        mx = fmax(mx, s);
+        if (s > -70.0) {
+            sa += e;
             ++ca;
         }
     }
-    loud_block_sum(sa, ca, rs, rc);
-    if (ca == 0) {
-        if (tid == 0) loudness[b] = -INFINITY;
-        return;
+    o.maxs = loud_block_max(mx, l.rs);
+    loud_block_sum(sa, ca, l.rs, l.rc);
+    o.lra = 0.0;
+    if (ca == 0) return o;
+    const double gamma = -0.691 + 10.0 * log10(sa / (double)ca) - 20.0;
+    double unused = 0.0;
+    int k = 0;
+    for (int64_t j = tid; j < o.JS; j += LD_GT) {              // a thread's own entries: the key is the value, +inf for a gated one
+        const double s = key[j];
+        const bool keep = s > -70.0 && s > gamma;
+        key[j] = keep ? s : INFINITY;
+        k += keep;
     }
-    const double gamma = -0.691 + 10.0 * log10(sa / (double)ca) - 10.0;
-    double sr = 0.0;
-    int cr = 0;
-    for (int64_t j = tid; j < Jr; j += LD_GT) {
-        const double zj = z[j], l = -0.691 + 10.0 * log10(zj);
-        if (l > -70.0 && l > gamma) {
-            sr += zj;
-            ++cr;
+    loud_block_sum(unused, k, l.rs, l.rc);
+    if (k == 0) return o;
+    const int64_t ilo = ((int64_t)(k - 1) * 10 + 50) / 100, ihi = ((int64_t)(k - 1) * 95 + 50) / 100;
+    for (int64_t j0 = 0; j0 < o.JS; j0 += LD_GT) {             // rank of key[j] = the keys below it, ties by index: unique ranks 0 .. k - 1
+        const int64_t j = j0 + tid;
+        const double kj = j < o.JS ? key[j] : INFINITY;
+        int64_t rank = 0;
+        for (int64_t t0 = 0; t0 < o.JS; t0 += MT_TILE) {
+            const int cnt = (int)min((int64_t)MT_TILE, o.JS - t0);
+            __syncthreads();
+            for (int i = tid; i < cnt; i += LD_GT) l.tile[i] = key[t0 + i];
+            __syncthreads();
+            for (int i = 0; i < cnt; ++i) {
+                const double ki = l.tile[i];
+                rank += (ki < kj || (ki == kj && t0 + i < j)) ? 1 : 0;
+            }
+        }
+        if (kj < INFINITY) {
+            if (rank == ilo) l.lohi[0] = kj;
+            if (rank == ihi) l.lohi[1] = kj;
         }
     }
-    loud_block_sum(sr, cr, rs, rc);
-    if (tid == 0) loudness[b] = cr > 0 ? -0.691 + 10.0 * log10(sr / (double)cr) : -INFINITY;
+    __syncthreads();
+    o.lra = l.lohi[1] - l.lohi[0];
+    return o;
+}
+
+__device__ __forceinline__ void meter_write(const MeterOut& o, const int b, double* loudness, double* range, double* maxm, double* maxs,
+                                            int64_t* counts) {
+    loudness[b] = o.L;
+    range[b] = o.lra;
+    maxm[b] = o.maxm;
+    maxs[b] = o.maxs;
+    counts[2 * b] = o.J;
+    counts[2 * b + 1] = o.JS;
+}
+
+__global__ __launch_bounds__(LD_GT) void loud_meter_kernel(const int64_t* __restrict__ ns, int64_t stride, int step, int S, int Q, int64_t K,
+                                                           int64_t NB, int64_t J, int64_t UM, const double* __restrict__ seg,
+                                                           const float* __restrict__ pk, double* __restrict__ zb, double* __restrict__ ub,
+                                                           double* __restrict__ kb, double* __restrict__ loudness, float* __restrict__ peak,
+                                                           double* __restrict__ range, double* __restrict__ maxm, double* __restrict__ maxs,
+                                                           int64_t* __restrict__ counts, double* __restrict__ Mout, int64_t mstride,
+                                                           double* __restrict__ Sout, int64_t sstride) {
+    __shared__ MeterLds l;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t n = loud_len(ns, b, stride), Kr = (n + S - 1) / S, U = n / step;
+    const double* sg = seg + (int64_t)b * K;
+    double *z = zb + (int64_t)b * J, *u = ub + (int64_t)b * UM;
+    const float m = loud_row_peak(pk + (int64_t)b * NB, Kr, l.rm);
+    if (tid == 0) peak[b] = m;
+    for (int64_t i = tid; i < U; i += LD_GT) {                 // a step: its Q segments in order
+        double t = 0.0;
+        const double* s0 = sg + i * Q;
+        for (int q = 0; q < Q; ++q) t += s0[q];
+        u[i] = t;
+    }
+    if (n > 0 && n < 4 * (int64_t)step) {                      // a short row, as loud_gate_kernel takes it
+        double e = 0.0;
+        int c = 0;
+        for (int64_t k = tid; k < Kr; k += LD_GT) e += sg[k];
+        loud_block_sum(e, c, l.rs, l.rc);
+        if (tid == 0) z[0] = e / (double)n;
+    }
+    __syncthreads();
+    const MeterOut o = meter_windows(u, U, n, step, z, kb + (int64_t)b * max(UM - 29, (int64_t)0), Mout ? Mout + (int64_t)b * mstride : nullptr,
+                                     Sout ? Sout + (int64_t)b * sstride : nullptr, l);
+    if (tid == 0) meter_write(o, b, loudness, range, maxm, maxs, counts);
+}
+
+__global__ void meter_reset_kernel(MeterStream ms, int rows) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= rows) return;
+    MeterHead* h = meter_head(ms, b);
+    if (!h) return;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h->fst[i] = 0.0;
+    h->upart = 0.0;
+    h->n = 0;
+    h->peak = 0.f;
+    h->status = 0;
+}
+
+// The last launch of a push: one block per row takes the whole segments of "pending, then the chunk" into the slot (steps that end in
+// them, the partial step, the filter state behind them, the samples behind them, the peak) and reads the meter.
+__global__ __launch_bounds__(LD_GT) void meter_push_kernel(const float* __restrict__ chunks, int64_t stride, const int64_t* __restrict__ ns,
+                                                           MeterStream ms, int step, int S, int Q, int64_t K, int64_t NB,
+                                                           const double* __restrict__ st, const double* __restrict__ seg,
+                                                           const float* __restrict__ pk, double* __restrict__ momentary,
+                                                           double* __restrict__ short_term, double* __restrict__ integrated) {
+    __shared__ MeterLds l;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int r;
+    int64_t c;
+    MeterHead* h = meter_row(ms, ns, b, stride, S, r, c);
+    if (!h) {                                                  // a slot that does not exist: the row is left out
+        if (tid == 0) momentary[b] = short_term[b] = integrated[b] = -INFINITY;
+        return;
+    }
+    const int64_t n0 = h->n, nv = r + c, Kw = nv / S, Kr = (nv + S - 1) / S, nseg0 = n0 / S, U0 = nseg0 / Q;
+    const int q0 = (int)(nseg0 % Q);
+    const bool dropped = n0 + loud_len(ns, b, stride) > ms.max_samples;
+    const double up0 = h->upart;
+    const int64_t nU = (q0 + Kw) / Q, U1 = U0 + nU;
+    const float m = loud_row_peak(pk + (int64_t)b * NB, Kr, l.rm);      // (its barrier: every thread has read the head)
+    const double* sg = seg + (int64_t)b * K;
+    double *u = meter_plane(h, ms, 0), *z = meter_plane(h, ms, 1);
+    for (int64_t i = tid; i < nU; i += LD_GT) {                // the steps that end in this push, each its Q segments in order
+        double t = i == 0 ? up0 : 0.0;
+        const int64_t k0 = i == 0 ? 0 : i * Q - q0, k1 = (i + 1) * Q - q0;
+        for (int64_t k = k0; k < k1; ++k) t += sg[k];
+        u[U0 + i] = t;
+    }
+    const float* cb = chunks + (int64_t)b * stride;
+    for (int64_t g = Kw * S + tid; g < nv; g += LD_GT) {       // the samples behind the last whole segment (fewer than S)
+        const float v = g < r ? h->pend[g] : cb[g - r];        // g < r only with Kw = 0: the entry it is written to
+        h->pend[g - Kw * S] = v;
+    }
+    if (tid == 0) {
+        double t = nU == 0 ? up0 : 0.0;
+        for (int64_t k = nU == 0 ? 0 : nU * Q - q0; k < Kw; ++k) t += sg[k];
+        h->upart = t;
+        if (Kw > 0) {
+            const double* s1 = st + ((int64_t)b * K + Kw - 1) * 4;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) h->fst[i] = s1[i];
+        }
+        h->n = n0 + c;
+        h->peak = fmaxf(h->peak, m);
+        if (dropped) h->status |= 1;
+    }
+    __syncthreads();
+    const int64_t Jr = U1 >= 4 ? U1 - 3 : 0;
+    for (int64_t j = tid; j < Jr; j += LD_GT) z[j] = (((u[j] + u[j + 1]) + u[j + 2]) + u[j + 3]) / (double)(4 * (int64_t)step);
+    __syncthreads();
+    const double L = loud_gates(z, Jr, l.rs, l.rc);
+    if (tid == 0) {
+        integrated[b] = L;
+        momentary[b] = Jr > 0 ? -0.691 + 10.0 * log10(z[Jr - 1]) : -INFINITY;
+        double e = 0.0;
+        if (U1 >= 30)
+            for (int q = 0; q < 30; ++q) e += u[U1 - 30 + q];
+        short_term[b] = U1 >= 30 ? -0.691 + 10.0 * log10(e / (30.0 * (double)step)) : -INFINITY;
+    }
+}
+
+__global__ __launch_bounds__(LD_GT) void meter_result_kernel(MeterStream ms, LoudPlan p, double* __restrict__ loudness,
+                                                             double* __restrict__ range, double* __restrict__ maxm, double* __restrict__ maxs,
+                                                             float* __restrict__ peak, int64_t* __restrict__ counts,
+                                                             int32_t* __restrict__ status) {
+    __shared__ MeterLds l;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    MeterHead* h = meter_head(ms, b);
+    if (!h) {
+        if (tid == 0) {
+            MeterOut o = {-INFINITY, 0.0, -INFINITY, -INFINITY, 0, 0};
+            meter_write(o, b, loudness, range, maxm, maxs, counts);
+            peak[b] = 0.f;
+            status[b] = 2;                                     // no such slot
+        }
+        return;
+    }
+    const int64_t n = h->n, U = (n / p.S) / p.Q;
+    double *u = meter_plane(h, ms, 0), *z = meter_plane(h, ms, 1);
+    if (tid == 0 && n > 0 && n < 4 * (int64_t)p.step) {        // a short stream: one block over its n samples, the unfinished segment included
+        double e = 0.0, s[4];
+        for (int64_t i = 0; i < U; ++i) e += u[i];
+        e += h->upart;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s[i] = h->fst[i];
+        for (int j = 0; j < (int)(n % p.S); ++j) {
+            const double y = loud_sample(p.c, (double)h->pend[j], s);
+            e += y * y;
+        }
+        z[0] = e / (double)n;
+    }
+    __syncthreads();
+    const MeterOut o = meter_windows(u, U, n, p.step, z, meter_plane(h, ms, 2), nullptr, nullptr, l);
+    if (tid == 0) {
+        meter_write(o, b, loudness, range, maxm, maxs, counts);
+        peak[b] = h->peak;
+        status[b] = h->status;
+    }
 }
 
 static int32_t loud_check_rate(int32_t fs, const char* what) {
     TTS_REQUIRE(fs >= LD_FS_MIN && fs <= LD_FS_MAX, "%s: sample rate %d outside [%d, %d]", what, fs, LD_FS_MIN, LD_FS_MAX);
+    return 0;
+}
+
+// the three filter launches: the K-weighted energy of every segment to w.seg, the states behind the segments to w.st, peaks to w.pk
+template <bool ST>
+static int32_t loud_filter(const float* wave, int64_t stride, const int64_t* nsamples, int32_t B, const LoudPlan& p, const LoudWs& w,
+                           const MeterStream& ms, hipStream_t s) {
+    const dim3 grid((unsigned)w.NB, B);
+    hipLaunchKernelGGL(loud_zero_state_kernel<ST>, grid, dim3(LD_T), 0, s, wave, stride, nsamples, p, w.K, w.NB, w.st, w.pk, ms);
+    TTS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(loud_scan_kernel<ST>, dim3(B), dim3(64), 0, s, nsamples, stride, p, w.K, w.st, ms);
+    TTS_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(loud_energy_kernel<ST>, grid, dim3(LD_T), 0, s, wave, stride, nsamples, p, w.K, w.st, w.seg, ms);
+    TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
@@ -348,15 +725,94 @@ static int32_t loudness_measure(const float* wave, int64_t stride, const int64_t
                 (long long)w.bytes);
     TTS_REQUIRE(w.NB <= 0x7fffffff, "loudness_measure: stride too large");
     loud_carve(workspace, B, stride, p, w);
-    const dim3 grid((unsigned)w.NB, B);
-    hipLaunchKernelGGL(loud_zero_state_kernel, grid, dim3(LD_T), 0, s, wave, stride, nsamples, p, w.K, w.NB, w.st, w.pk);
-    TTS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(loud_scan_kernel, dim3(B), dim3(64), 0, s, nsamples, stride, p, w.K, w.st);
-    TTS_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(loud_energy_kernel, grid, dim3(LD_T), 0, s, wave, stride, nsamples, p, w.K, w.st, w.seg);
-    TTS_CHECK_HIP(hipGetLastError());
+    TTS_TRY(loud_filter<false>(wave, stride, nsamples, B, p, w, MeterStream{}, s));
     hipLaunchKernelGGL(loud_gate_kernel, dim3(B), dim3(LD_GT), 0, s, nsamples, stride, p.step, p.S, p.Q, w.K, w.NB, w.J, w.seg, w.pk, w.zb,
                        loudness, peak);
+    TTS_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+struct MeterWs {
+    LoudWs w;
+    int64_t UM, JSM;                  // per row of the stride: whole steps, short-term values
+    double *ub, *kb;                  // [B][UM] step energies, [B][JSM] keys of the rank count
+    int64_t bytes;
+};
+
+static void meter_carve(void* base, int64_t B, int64_t stride, const LoudPlan& p, MeterWs& m) {
+    loud_carve(base, B, stride, p, m.w);
+    m.UM = stride / p.step;
+    m.JSM = m.UM >= 30 ? m.UM - 29 : 0;
+    Arena a(base ? (char*)base + m.w.bytes : nullptr, (int64_t)1 << 62);
+    m.ub = a.take<double>(B * m.UM);
+    m.kb = a.take<double>(B * m.JSM);
+    m.bytes = m.w.bytes + a.off;
+}
+
+static int32_t loudness_meter(const float* wave, int64_t stride, const int64_t* nsamples, int32_t B, int32_t fs, double* loudness, float* peak,
+                              double* range, double* maxm, double* maxs, int64_t* counts, double* Mout, int64_t mstride, double* Sout,
+                              int64_t sstride, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    TTS_REQUIRE(nsamples && loudness && peak && range && maxm && maxs && counts && workspace && (wave || stride == 0),
+                "loudness_meter: null argument");
+    TTS_REQUIRE(B >= 1 && B <= 65535 && stride >= 0 && stride < ((int64_t)1 << 40), "loudness_meter: bad batch %d / stride", B);
+    TTS_TRY(loud_check_rate(fs, "loudness_meter"));
+    LoudPlan p;
+    loud_plan(fs, p);
+    MeterWs m;
+    meter_carve(nullptr, B, stride, p, m);
+    TTS_REQUIRE(workspace_bytes >= m.bytes, "loudness_meter: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)m.bytes);
+    TTS_REQUIRE(m.w.NB <= 0x7fffffff, "loudness_meter: stride too large");
+    TTS_REQUIRE((!Mout || mstride >= m.w.J) && (!Sout || sstride >= m.JSM), "loudness_meter: series strides %lld / %lld, %lld / %lld needed",
+                (long long)mstride, (long long)sstride, (long long)m.w.J, (long long)m.JSM);
+    meter_carve(workspace, B, stride, p, m);
+    TTS_TRY(loud_filter<false>(wave, stride, nsamples, B, p, m.w, MeterStream{}, s));
+    hipLaunchKernelGGL(loud_meter_kernel, dim3(B), dim3(LD_GT), 0, s, nsamples, stride, p.step, p.S, p.Q, m.w.K, m.w.NB, m.w.J, m.UM, m.w.seg,
+                       m.w.pk, m.w.zb, m.ub, m.kb, loudness, peak, range, maxm, maxs, counts, Mout, mstride, Sout, sstride);
+    TTS_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- stream meter: the host side.  A state is [nslots] slots of meter_slot_bytes each.
+static int64_t meter_ucap(int64_t max_samples, const LoudPlan& p) { return max_samples / p.step + 1; }
+static int64_t meter_slot_bytes(int64_t max_samples, const LoudPlan& p) {
+    return METER_HEAD_BYTES + align_up(3 * meter_ucap(max_samples, p) * (int64_t)sizeof(double), 256);
+}
+
+static int32_t meter_stream(void* state, int64_t state_bytes, int32_t nslots, int64_t max_samples, int32_t fs, const int32_t* slots,
+                            int32_t rows, const char* what, LoudPlan& p, MeterStream& ms) {
+    TTS_REQUIRE(state && slots, "%s: null argument", what);
+    TTS_REQUIRE(nslots >= 1 && nslots <= 65535 && rows >= 1 && rows <= 65535 && max_samples >= 1 && max_samples < ((int64_t)1 << 40),
+                "%s: %d slots, %d rows, max_samples %lld", what, nslots, rows, (long long)max_samples);
+    TTS_TRY(loud_check_rate(fs, what));
+    loud_plan(fs, p);
+    ms.state = (char*)state;
+    ms.slots = slots;
+    ms.slot_bytes = meter_slot_bytes(max_samples, p);
+    ms.max_samples = max_samples;
+    ms.ucap = meter_ucap(max_samples, p);
+    ms.nslots = nslots;
+    TTS_REQUIRE(state_bytes >= nslots * ms.slot_bytes, "%s: state of %lld bytes, %lld needed", what, (long long)state_bytes,
+                (long long)(nslots * ms.slot_bytes));
+    return 0;
+}
+
+static int32_t meter_push(void* state, int64_t state_bytes, int32_t nslots, int64_t max_samples, int32_t fs, const float* chunks, int64_t stride,
+                          const int64_t* nsamples, const int32_t* slots, int32_t rows, double* momentary, double* short_term,
+                          double* integrated, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+    LoudPlan p;
+    MeterStream ms;
+    TTS_TRY(meter_stream(state, state_bytes, nslots, max_samples, fs, slots, rows, "meter_push", p, ms));
+    TTS_REQUIRE(nsamples && momentary && short_term && integrated && workspace && (chunks || stride == 0), "meter_push: null argument");
+    TTS_REQUIRE(stride >= 0 && stride < ((int64_t)1 << 40), "meter_push: bad stride");
+    LoudWs w;
+    loud_carve(nullptr, rows, stride + LD_SMAX, p, w);         // the row a push filters: up to S - 1 pending samples, then the chunk
+    TTS_REQUIRE(workspace_bytes >= w.bytes, "meter_push: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)w.bytes);
+    TTS_REQUIRE(w.NB <= 0x7fffffff, "meter_push: stride too large");
+    loud_carve(workspace, rows, stride + LD_SMAX, p, w);
+    TTS_TRY(loud_filter<true>(chunks, stride, nsamples, rows, p, w, ms, s));
+    hipLaunchKernelGGL(meter_push_kernel, dim3(rows), dim3(LD_GT), 0, s, chunks, stride, nsamples, ms, p.step, p.S, p.Q, w.K, w.NB, w.st, w.seg,
+                       w.pk, momentary, short_term, integrated);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -484,6 +940,66 @@ int64_t ttsamd_loudness_workspace_bytes(int32_t batch, int64_t wave_stride, int3
 int32_t ttsamd_loudness_measure(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t sample_rate,
                                 double* loudness, float* peak, void* workspace, int64_t workspace_bytes, void* stream) {
     return loudness_measure(wave, wave_stride, nsamples, batch, sample_rate, loudness, peak, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int64_t ttsamd_loudness_meter_workspace_bytes(int32_t batch, int64_t wave_stride, int32_t sample_rate) {
+    if (batch < 1 || wave_stride < 0 || wave_stride >= ((int64_t)1 << 40) || sample_rate < LD_FS_MIN || sample_rate > LD_FS_MAX) return -1;
+    LoudPlan p;
+    loud_plan(sample_rate, p);
+    MeterWs m;
+    meter_carve(nullptr, batch, wave_stride, p, m);
+    return m.bytes;
+}
+
+int32_t ttsamd_loudness_meter(const float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, int32_t sample_rate,
+                              double* loudness, float* peak, double* loudness_range, double* max_momentary, double* max_short_term,
+                              int64_t* counts, double* momentary, int64_t momentary_stride, double* short_term, int64_t short_term_stride,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    return loudness_meter(wave, wave_stride, nsamples, batch, sample_rate, loudness, peak, loudness_range, max_momentary, max_short_term, counts,
+                          momentary, momentary_stride, short_term, short_term_stride, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int64_t ttsamd_meter_state_bytes(int32_t slots, int64_t max_samples, int32_t sample_rate) {
+    if (slots < 1 || slots > 65535 || max_samples < 1 || max_samples >= ((int64_t)1 << 40) || sample_rate < LD_FS_MIN || sample_rate > LD_FS_MAX)
+        return -1;
+    LoudPlan p;
+    loud_plan(sample_rate, p);
+    return slots * meter_slot_bytes(max_samples, p);
+}
+
+int32_t ttsamd_meter_reset(void* state, int64_t state_bytes, int32_t slots, int64_t max_samples, int32_t sample_rate, const int32_t* slot,
+                           int32_t rows, void* stream) {
+    LoudPlan p;
+    MeterStream ms;
+    TTS_TRY(meter_stream(state, state_bytes, slots, max_samples, sample_rate, slot, rows, "meter_reset", p, ms));
+    hipLaunchKernelGGL(meter_reset_kernel, dim3((rows + 63) / 64), dim3(64), 0, (hipStream_t)stream, ms, rows);
+    TTS_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int64_t ttsamd_meter_push_workspace_bytes(int32_t rows, int64_t chunk_stride, int32_t sample_rate) {
+    if (chunk_stride < 0 || chunk_stride >= ((int64_t)1 << 40)) return -1;
+    return ttsamd_loudness_workspace_bytes(rows, chunk_stride + LD_SMAX, sample_rate);
+}
+
+int32_t ttsamd_meter_push(void* state, int64_t state_bytes, int32_t slots, int64_t max_samples, int32_t sample_rate, const float* chunks,
+                          int64_t chunk_stride, const int64_t* nsamples, const int32_t* slot, int32_t rows, double* momentary,
+                          double* short_term, double* integrated, void* workspace, int64_t workspace_bytes, void* stream) {
+    return meter_push(state, state_bytes, slots, max_samples, sample_rate, chunks, chunk_stride, nsamples, slot, rows, momentary, short_term,
+                      integrated, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int32_t ttsamd_meter_result(void* state, int64_t state_bytes, int32_t slots, int64_t max_samples, int32_t sample_rate, const int32_t* slot,
+                            int32_t rows, double* loudness, double* loudness_range, double* max_momentary, double* max_short_term, float* peak,
+                            int64_t* counts, int32_t* status, void* stream) {
+    LoudPlan p;
+    MeterStream ms;
+    TTS_TRY(meter_stream(state, state_bytes, slots, max_samples, sample_rate, slot, rows, "meter_result", p, ms));
+    TTS_REQUIRE(loudness && loudness_range && max_momentary && max_short_term && peak && counts && status, "meter_result: null argument");
+    hipLaunchKernelGGL(meter_result_kernel, dim3(rows), dim3(LD_GT), 0, (hipStream_t)stream, ms, p, loudness, loudness_range, max_momentary,
+                       max_short_term, peak, counts, status);
+    TTS_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 int32_t ttsamd_wave_level(float* wave, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* mode,

@@ -559,7 +559,7 @@ class FastPitch2Wave(nn.Module):
     def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
                    max_streams: int = 32, max_frames: int = 4096, speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
                    vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., sample_rate=None, encoding=None, gain_db=0.0,
-                   limiter=False, true_peak=False):
+                   limiter=False, true_peak=False, meter=False):
         """`tts` that hands out audio while it is being made (a generator; one at a time per model).  FastPitch is not autoregressive, so
         the whole mel exists at once; the vocoder then runs over windows of it (ttsamd.stream.StreamingVocoder), the first of
         first_chunk_frames frames, the following of chunk_frames.
@@ -574,15 +574,22 @@ class FastPitch2Wave(nn.Module):
         'mulaw' is telephony's G.711: uint8 chunks); put together they are utils.audio.resample of the line's 22 050 Hz samples,
         encoded, bit for bit -- no seam at a chunk border.
         limiter (False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db) and gain_db (a scalar, or one value per
-        line): levelling inside the stream.  A stream cannot measure its loudness, so it is levelled the way a live chain is: a fixed
+        line): levelling inside the stream.  A stream has no whole-utterance loudness to level by, so it is levelled the way a live chain is: a fixed
         gain, then the look-ahead limiter, at 22 050 Hz in front of the resampler.  The chunks put together are utils.audio.limit of
         the stream's samples in front of the limiter (StreamingVocoder.bypass), bit for bit; against the stream without a limiter
         those differ within fp32 summation order, as its windows are narrower.  gain_db other than 0 without a limiter is a ValueError.
         true_peak (needs a limiter; ValueError without one): the limiter's detector is the true-peak one, and the chunks are the bits
-        of utils.audio.limit(true_peak=True)."""
+        of utils.audio.limit(true_peak=True).
+        meter=True: every chunk that leaves the stream is pushed into a utils.audio.LoudnessMeter at the stream's output rate, on the
+        device, so the meter measures what is delivered; the generator then yields (chunk, reading) for a str and (i, chunk, last,
+        reading) for a list.  reading: a dict of Python floats, momentary, short_term (-inf before the first 400 ms / 3 s) and
+        integrated (of the line so far); on a line's last chunk also loudness_range, max_momentary and max_short_term.  Float chunks
+        only: with pcm16 or an encoding other than None / 'float32' it is a ValueError."""
         kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
         limiter = limiter_spec(limiter)
         check_true_peak(true_peak, None, limiter)
+        if meter and (pcm16 or encoding not in (None, 'float32')):
+            raise ValueError('tts_stream: meter=True measures float chunks: not with pcm16 or an encoding')
         n_lines = 1 if isinstance(text_input, str) else len(text_input)
         gains = row_values(gain_db, n_lines, 'gain_db') if per_row(gain_db) else [gain_db]
         check_finite(gains, 'gain_db')
@@ -592,9 +599,10 @@ class FastPitch2Wave(nn.Module):
             mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw)
             sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak)
             sv.open(mel, denoise, float(gains[0]))
+            lm = self._stream_meter(sv, max_streams) if meter else None
             while sv.open_streams:
-                for _, chunk, _ in sv.step():
-                    yield chunk.cpu()
+                for sid, chunk, last in sv.step():
+                    yield (chunk.cpu(), self._meter_reading(lm, sid, chunk, last)) if meter else chunk.cpu()
             return
         lines = list(text_input)
         check_line_controls(len(lines), self.model.net_config['n_speakers'], denoise=denoise, **kw)
@@ -611,6 +619,7 @@ class FastPitch2Wave(nn.Module):
         if fill:
             groups.append(fill)
         waiting, line_of = [], {}
+        lm = self._stream_meter(sv, max_streams) if meter else None
         while True:
             while sv.free_slots and (waiting or groups):
                 if not waiting:
@@ -623,7 +632,32 @@ class FastPitch2Wave(nn.Module):
             if not line_of:
                 return
             for sid, chunk, last in sv.step():
-                yield (line_of.pop(sid) if last else line_of[sid]), chunk.cpu(), last
+                i = line_of.pop(sid) if last else line_of[sid]
+                yield (i, chunk.cpu(), last, self._meter_reading(lm, sid, chunk, last)) if meter else (i, chunk.cpu(), last)
+
+    def _stream_meter(self, sv, max_streams):
+        """the LoudnessMeter of this model's streams at the stream's output rate (made once per rate and pool size), every slot reset"""
+        from utils.audio import LoudnessMeter
+        key = (str(self.device), int(sv.sample_rate), int(max_streams))
+        if getattr(self, '_meter_key', None) != key:
+            self._meter = LoudnessMeter(sv.sample_rate, max_streams=max_streams, device=self.device)
+            self._meter_key = key
+        self._meter.reset(range(max_streams))
+        self._meter_free, self._meter_slot = list(range(max_streams)), {}
+        return self._meter
+
+    def _meter_reading(self, lm, sid, chunk, last):
+        """push the chunk of stream `sid` into its slot of the meter -> the reading as Python floats; behind `last` the slot is free again"""
+        if sid not in self._meter_slot:
+            self._meter_slot[sid] = self._meter_free.pop(0)
+        slot = self._meter_slot[sid]
+        reading = {k: float(v[0]) for k, v in lm.push(chunk, slots=[slot]).items()}
+        if last:
+            res = lm.result([slot])
+            reading.update({k: float(res[k][0]) for k in ('integrated', 'loudness_range', 'max_momentary', 'max_short_term')})
+            lm.reset([slot])
+            self._meter_free.append(self._meter_slot.pop(sid))
+        return reading
 
     # ---- objective evaluation against recordings (not in the reference; ttsamd.engine.ObjectiveEngine, csrc/objective.hip) ----
     @staticmethod

@@ -1606,6 +1606,37 @@ class LoudnessEngine:
                                                          _ptr(ws), nbytes, _stream()), 'loudness_measure')
         return loud, peak
 
+    def meter(self, wave, lens=None, series=False):
+        """The whole-wave loudness meter (ttsamd_loudness_meter; include/ttsamd.h states the arithmetic): wave [B, n_max], lens int64
+        [B] or None -> dict of device tensors [B]: integrated (float64 LUFS; the bits of `measure`), peak (fp32), loudness_range
+        (float64 LU), max_momentary, max_short_term (float64, -inf when there is no value), counts (int64 [B, 2]: momentary and
+        short-term values).  series: also momentary [B, J] and short_term [B, JS] (float64), NaN at and past a row's own count."""
+        wave, lens = self._wave(wave, lens)
+        B, n_max = wave.shape
+        dev = wave.device
+        step = (self.sample_rate + 5) // 10
+        J = (n_max - 4 * step) // step + 1 if n_max >= 4 * step else 1
+        JS = max(n_max // step - 29, 0)
+        out = dict(integrated=torch.full((B,), float('-inf'), dtype=torch.float64, device=dev),
+                   peak=torch.zeros(B, dtype=torch.float32, device=dev), loudness_range=torch.zeros(B, dtype=torch.float64, device=dev),
+                   max_momentary=torch.full((B,), float('-inf'), dtype=torch.float64, device=dev),
+                   max_short_term=torch.full((B,), float('-inf'), dtype=torch.float64, device=dev),
+                   counts=torch.zeros(B, 2, dtype=torch.int64, device=dev))
+        if series:
+            out['momentary'] = torch.full((B, J), float('nan'), dtype=torch.float64, device=dev)
+            out['short_term'] = torch.full((B, JS), float('nan'), dtype=torch.float64, device=dev)
+        if B:
+            nbytes = int(self.lib.ttsamd_loudness_meter_workspace_bytes(B, n_max, self.sample_rate))
+            if nbytes < 0:
+                raise L.TtsAmdError(f'loudness meter: a batch of {B} rows of {n_max} samples at {self.sample_rate} Hz is refused')
+            ws = self.ws.get(max(nbytes, 1), dev)
+            with torch.cuda.device(dev):
+                L.check(self.lib.ttsamd_loudness_meter(_ptr(wave), n_max, _ptr(lens), B, self.sample_rate, _ptr(out['integrated']),
+                                                       _ptr(out['peak']), _ptr(out['loudness_range']), _ptr(out['max_momentary']),
+                                                       _ptr(out['max_short_term']), _ptr(out['counts']), _ptr(out.get('momentary')), J,
+                                                       _ptr(out.get('short_term')), JS, _ptr(ws), nbytes, _stream()), 'loudness_meter')
+        return out
+
     def true_peak(self, wave, lens=None):
         """wave [B, n_max], lens int64 [B] or None -> fp32 [B] on the device: the peak of the 4x oversampled row (ttsamd_true_peak;
         include/ttsamd.h states the interpolator), rounded upward to fp32; 0 for an empty row.  Two launches, no workspace."""
@@ -1697,6 +1728,74 @@ class LoudnessEngine:
         mode_d = torch.tensor([int(m) for m in modes], dtype=torch.int32).to(wave.device)
         return self.limit_samples(wave, lens, mode_d, _rows_f32(targets, wave.device), ceiling, 10.0 ** (float(max_gain_db) / 20.0), attack,
                                   hold, loud, true_peak=bool(true_peak))
+
+
+class LoudnessMeter:
+    """The stream meter (ttsamd_meter_*; include/ttsamd.h states the arithmetic): `max_streams` slots on the device, each a stream of at
+    most `max_seconds` at `sample_rate` that is measured while it arrives, in chunks of any length.  Nothing is read back to the host.
+    METER_DROPPED in a result's status: a push went beyond max_seconds and was left out."""
+    METER_DROPPED = 1
+
+    def __init__(self, sample_rate=22050, max_streams=32, max_seconds=600.0, device='cuda'):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        self.sample_rate, self.max_streams = int(sample_rate), int(max_streams)
+        self.max_samples = int(float(max_seconds) * self.sample_rate)
+        nbytes = int(self.lib.ttsamd_meter_state_bytes(self.max_streams, self.max_samples, self.sample_rate))
+        if nbytes < 0:
+            raise L.TtsAmdError(f'LoudnessMeter: {max_streams} streams of {max_seconds} s at {sample_rate} Hz are refused')
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.ws = _Workspace()
+        self.reset(range(self.max_streams))
+
+    def _slots(self, slots, rows=None):
+        slots = [int(s) for s in slots]
+        if len(set(slots)) != len(slots) or any(not 0 <= s < self.max_streams for s in slots) or (rows is not None and len(slots) != rows):
+            raise ValueError(f'LoudnessMeter: slots {slots}: one slot of 0 .. {self.max_streams - 1} per row, none twice')
+        return torch.tensor(slots, dtype=torch.int32).to(self.device)
+
+    def _call(self, fn, what, *args):
+        with torch.cuda.device(self.device):
+            L.check(fn(_ptr(self.state), self.state.numel(), self.max_streams, self.max_samples, self.sample_rate, *args, _stream()), what)
+
+    def reset(self, slots):
+        """the slots start again at zero samples"""
+        slots_d = self._slots(slots)
+        if slots_d.numel():
+            self._call(self.lib.ttsamd_meter_reset, 'meter_reset', _ptr(slots_d), slots_d.numel())
+
+    def push(self, chunks, lens=None, slots=None):
+        """chunks [rows, n_max] fp32 on the device (or one chunk [n]), lens int64 [rows] or None, slots: one slot per row (default
+        0 .. rows - 1) -> dict of float64 device tensors [rows]: momentary and short_term (the latest value, -inf before the first)
+        and integrated (both gates over the blocks so far)."""
+        chunks = _dev_f32(chunks if chunks.dim() != 1 else chunks[None], 2, 'LoudnessMeter.push: chunks')
+        rows, n_max = chunks.shape
+        lens = _dev_lens(lens, rows, n_max, chunks.device)
+        slots_d = self._slots(range(rows) if slots is None else slots, rows)
+        out = {k: torch.full((rows,), float('-inf'), dtype=torch.float64, device=self.device) for k in ('momentary', 'short_term', 'integrated')}
+        if rows:
+            nbytes = int(self.lib.ttsamd_meter_push_workspace_bytes(rows, n_max, self.sample_rate))
+            if nbytes < 0:
+                raise L.TtsAmdError(f'LoudnessMeter.push: {rows} rows of {n_max} samples are refused')
+            ws = self.ws.get(max(nbytes, 1), self.device)
+            self._call(self.lib.ttsamd_meter_push, 'meter_push', _ptr(chunks), n_max, _ptr(lens), _ptr(slots_d), rows,
+                       _ptr(out['momentary']), _ptr(out['short_term']), _ptr(out['integrated']), _ptr(ws), nbytes)
+        return out
+
+    def result(self, slots):
+        """-> dict of device tensors [rows] over each slot's samples so far: integrated, loudness_range, max_momentary, max_short_term
+        (float64), peak (fp32), counts (int64 [rows, 2]: momentary and short-term values), status (int32; METER_DROPPED)"""
+        slots_d = self._slots(slots)
+        rows = slots_d.numel()
+        f64 = lambda: torch.zeros(rows, dtype=torch.float64, device=self.device)
+        out = dict(integrated=f64(), loudness_range=f64(), max_momentary=f64(), max_short_term=f64(),
+                   peak=torch.zeros(rows, dtype=torch.float32, device=self.device),
+                   counts=torch.zeros(rows, 2, dtype=torch.int64, device=self.device),
+                   status=torch.zeros(rows, dtype=torch.int32, device=self.device))
+        if rows:
+            self._call(self.lib.ttsamd_meter_result, 'meter_result', _ptr(slots_d), rows, *(_ptr(out[k]) for k in (
+                'integrated', 'loudness_range', 'max_momentary', 'max_short_term', 'peak', 'counts', 'status')))
+        return out
 
 
 LIMIT_MODES = {'off': 0, 'lufs': 2, 'gain': 3}

@@ -167,6 +167,14 @@ SYMBOLS = {
     'ttsamd_true_peak_taps': (_I32, [C.POINTER(C.c_double)]),
     'ttsamd_true_peak': (_I32, [_P, _I64, _P, _I32, _P, _P]),
     'ttsamd_wave_limit_true_peak': (_I32, [_P, _I64, _P, _I32, _P, _P, _F, _F, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    # loudness meter (csrc/loudness.hip): float64 results and series, counts int64 [B][2] on the device; the stream meter's state
+    'ttsamd_loudness_meter_workspace_bytes': (_I64, [_I32, _I64, _I32]),
+    'ttsamd_loudness_meter': (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _P]),
+    'ttsamd_meter_state_bytes': (_I64, [_I32, _I64, _I32]),
+    'ttsamd_meter_push_workspace_bytes': (_I64, [_I32, _I64, _I32]),
+    'ttsamd_meter_reset': (_I32, [_P, _I64, _I32, _I64, _I32, _P, _I32, _P]),
+    'ttsamd_meter_push': (_I32, [_P, _I64, _I32, _I64, _I32, _P, _I64, _P, _P, _I32, _P, _P, _P, _P, _I64, _P]),
+    'ttsamd_meter_result': (_I32, [_P, _I64, _I32, _I64, _I32, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     # wave-against-wave scores (csrc/wavescore.hip): float64 results, lengths int64 on the device
     'ttsamd_stoi_workspace_bytes': (_I64, [_I32, _I64]),
     'ttsamd_stoi': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I64, _P]),

@@ -279,20 +279,140 @@ def _level(wave, lens, sample_rate, mode, target, ceiling, what, true_peak=False
     return out.reshape(wave.shape)
 
 
+def _meter_rows(wave, lens, what, device=None):
+    """`_level_rows`, and a list of 1-D waves (what `tts` returns) zero-padded to one batch as FastPitch2Wave._pad_waves pads"""
+    if not isinstance(wave, (list, tuple)):
+        return _level_rows(wave, lens, what)
+    if lens is not None:
+        raise ValueError(f'{what}: a list of waves carries its own lengths')
+    rows = [torch.as_tensor(np.asarray(w) if not isinstance(w, torch.Tensor) else w).reshape(-1).float() for w in wave]
+    if device is None:
+        device = next((r.device for r in rows if r.device.type == 'cuda'), torch.device('cuda:0'))
+    n = [int(r.numel()) for r in rows]
+    out = torch.zeros(len(rows), max(n, default=0), dtype=torch.float32, device=device)
+    for b, r in enumerate(rows):
+        out[b, :n[b]] = r.to(device)
+    return out, torch.tensor(n, dtype=torch.int64).to(device)
+
+
 @torch.inference_mode()
-def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None, limiter=False, true_peak=False):
+def loudness_stats(wave, sample_rate=22050, lens=None):
+    """The EBU R 128 figures of every row of wave [..., n] (or of a list of waves) -> dict of device tensors [rows]: integrated (LUFS,
+    the bits of `loudness`), loudness_range (LU, EBU Tech 3342 on short-term values every 100 ms), max_momentary (400 ms windows),
+    max_short_term (3 s windows; both -inf for a row too short to have one), peak (max |x|, fp32).  include/ttsamd.h states the
+    arithmetic; it is specified by its arithmetic, parity with libebur128 unpinned (libebur128 takes its short-term blocks for the
+    range at another hop).  lens as in `loudness`.  No host synchronisation."""
+    x, lens = _meter_rows(wave, lens, 'loudness_stats')
+    m = _leveller(sample_rate, x.device).meter(x, lens)
+    return {k: m[k] for k in ('integrated', 'loudness_range', 'max_momentary', 'max_short_term', 'peak')}
+
+
+@torch.inference_mode()
+def momentary_loudness(wave, sample_rate=22050, lens=None):
+    """Momentary loudness M (400 ms windows every 100 ms; one window over a row shorter than 400 ms) -> (values float64 [rows, J] on the
+    device, NaN behind a row's own count; counts int64 [rows])"""
+    x, lens = _meter_rows(wave, lens, 'momentary_loudness')
+    m = _leveller(sample_rate, x.device).meter(x, lens, series=True)
+    return m['momentary'], m['counts'][:, 0]
+
+
+@torch.inference_mode()
+def short_term_loudness(wave, sample_rate=22050, lens=None):
+    """Short-term loudness S (3 s windows every 100 ms; none for a row shorter than 3 s) -> (values float64 [rows, JS] on the device,
+    NaN behind a row's own count; counts int64 [rows])"""
+    x, lens = _meter_rows(wave, lens, 'short_term_loudness')
+    m = _leveller(sample_rate, x.device).meter(x, lens, series=True)
+    return m['short_term'], m['counts'][:, 1]
+
+
+def loudness_range(wave, sample_rate=22050, lens=None):
+    """Loudness range (LRA, EBU Tech 3342) of every row -> float64 [rows] in LU on the device: `loudness_stats`'s loudness_range"""
+    return loudness_stats(wave, sample_rate, lens)['loudness_range']
+
+
+class LoudnessMeter:
+    """Loudness of streams while they arrive: `max_streams` slots on the device, each measuring one stream of at most `max_seconds`.
+    push(chunks [rows, n] or one chunk [n], lens, slots) -> dict(momentary, short_term, integrated) of float64 device tensors [rows]: the
+    latest 400 ms and 3 s values (-inf before the first) and the integrated loudness of the stream so far; result(slots) -> dict(integrated,
+    loudness_range, max_momentary, max_short_term, peak, counts, status) over the stream so far; reset(slots) starts a slot again.
+    A stream's figures do not depend on which other slots share a push.  Against `loudness_stats` on the whole wave they agree within
+    1e-9 LU (the peak exactly) for any chunking.  A push that would pass max_seconds is left out and flagged in status (bit 0)."""
+
+    def __init__(self, sample_rate=22050, max_streams=32, max_seconds=600.0, device='cuda'):
+        from ttsamd.engine import LoudnessMeter as _Meter
+        self._m = _Meter(sample_rate, max_streams, max_seconds, device=device)
+        self.sample_rate, self.max_streams, self.max_seconds = self._m.sample_rate, self._m.max_streams, float(max_seconds)
+
+    @torch.inference_mode()
+    def push(self, chunks, lens=None, slots=None):
+        return self._m.push(_device_wave(chunks, 'LoudnessMeter.push'), lens, slots)
+
+    @torch.inference_mode()
+    def result(self, slots):
+        return self._m.result(slots)
+
+    @torch.inference_mode()
+    def reset(self, slots):
+        self._m.reset(slots)
+
+
+def _level_capped(wave, lens, sample_rate, target_lufs, peak_ceiling, max_short_term, spec, true_peak):
+    """normalize_loudness with the short-term cap of EBU R 128 s1: the row's target becomes min(target, L + max_short_term - maxS),
+    worked out on the device from the meter's figures, and goes to ttsamd_wave_level / ttsamd_wave_limit as their per-row target"""
+    import ctypes as C
+    from ttsamd import lib as L
+    check_finite([max_short_term], 'normalize_loudness max_short_term')
+    x, lens = _level_rows(wave, lens, 'normalize_loudness')
+    if x.data_ptr() == wave.data_ptr():
+        x = x.clone()
+    B, n_max = x.shape
+    if not B:
+        return x.reshape(wave.shape)
+    targets = row_values(target_lufs, B, 'normalize_loudness target_lufs') if per_row(target_lufs) else [target_lufs] * B
+    check_finite(targets, 'normalize_loudness target_lufs')
+    eng = _leveller(sample_rate, x.device)
+    lens_d = torch.full((B,), n_max, dtype=torch.int64, device=x.device) if lens is None else lens
+    m = eng.meter(x, lens_d)
+    target = torch.tensor([float(t) for t in targets], dtype=torch.float64).to(x.device)
+    cap = m['integrated'] + (float(max_short_term) - m['max_short_term'])
+    target = torch.where(torch.isfinite(cap), torch.minimum(target, cap), target).to(torch.float32)
+    mode = torch.full((B,), 2, dtype=torch.int32, device=x.device)
+    if spec is not None:
+        attack, hold = limiter_samples(spec['attack_ms'], spec['hold_ms'], sample_rate)
+        eng.limit_samples(x, lens_d, mode, target, spec['ceiling'], 10.0 ** (float(spec['max_gain_db']) / 20.0), attack, hold, m['integrated'],
+                          **(dict(true_peak=True) if true_peak else {}))
+        return x.reshape(wave.shape)
+    if not 0.0 < float(peak_ceiling) <= 1.0:
+        raise TtsAmdError(f'level: ceiling {peak_ceiling!r} is not in (0, 1]')
+    peak = eng.true_peak(x, lens_d) if true_peak else m['peak']
+    gain = torch.ones(B, dtype=torch.float32, device=x.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(x.device):
+        L.check(L.load().ttsamd_wave_level(p(x), n_max, p(lens_d), B, p(mode), p(target), float(peak_ceiling), p(m['integrated']), p(peak),
+                                           p(gain), C.c_void_p(torch.cuda.current_stream().cuda_stream)), 'wave_level')
+    return x.reshape(wave.shape)
+
+
+@torch.inference_mode()
+def normalize_loudness(wave, sample_rate=22050, target_lufs=-23.0, peak_ceiling=0.99, lens=None, limiter=False, true_peak=False,
+                       max_short_term=None):
     """Every row of wave [..., n] scaled by ONE gain to target_lufs (a float or one per row); where that would lift the row's peak
     above peak_ceiling, the gain is ceiling / peak instead (a cap on the gain, no limiter).  A silent row is returned as it is.  A new
     tensor on the device; the samples behind lens[row] are copied unchanged.
     limiter (True, or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db): the full gain towards the target instead, and the
     look-ahead limiter (`limit`) holds the peaks at the ceiling (peak_ceiling unless the dict names one), so the target is reached.
     true_peak: the ceiling is a true-peak ceiling (dBTP as a linear value): the cap uses `true_peak` of the row, and the levelled row's
-    true peak stays within peak_ceiling (1 + H 2^-24), H = 2.31 (the fp32 rounding of the output: include/ttsamd.h); with a limiter, its detector is the true-peak one (no exact bound: see `limit`)."""
+    true peak stays within peak_ceiling (1 + H 2^-24), H = 2.31 (the fp32 rounding of the output: include/ttsamd.h); with a limiter, its detector is the true-peak one (no exact bound: see `limit`).
+    max_short_term (LUFS, e.g. -18.0: EBU R 128 s1 for short-form content): a row whose maximum short-term loudness would end above it
+    is levelled to min(target, L + max_short_term - maxS) instead, worked out on the device with no synchronisation; None: the call as
+    it was, bit for bit."""
     spec = limiter_spec(limiter)
+    if spec is not None and not (isinstance(limiter, dict) and 'ceiling' in limiter):
+        spec['ceiling'] = peak_ceiling
+    if max_short_term is not None:
+        return _level_capped(wave, lens, sample_rate, target_lufs, peak_ceiling, max_short_term, spec, true_peak)
     if spec is None:
         return _level(wave, lens, sample_rate, 2, target_lufs, peak_ceiling, 'normalize_loudness', true_peak)
-    if not (isinstance(limiter, dict) and 'ceiling' in limiter):
-        spec['ceiling'] = peak_ceiling
     x, lens = _level_rows(wave, lens, 'normalize_loudness')
     if x.data_ptr() == wave.data_ptr():
         x = x.clone()
