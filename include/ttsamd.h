@@ -654,6 +654,12 @@ int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, 
  * groups in the packed strip form (dilation 3 / 5, one C-in slice, no residual, mode 0; TTSAMD_WINO4 bit 7); *ksplit = its input-channel slices (1 = not split).  -1 / 0 before the first launch.  Host state of
  * the thread only: nothing is read from the device.  The bf16 engines and the fused ResBlock launches do not record. */
 int32_t ttsamd_conv_last_launch(int32_t* route, int32_t* ksplit);
+/* Asks without launching (new symbol, added WITHOUT a bump; host only, needs no GPU): the (*route, *ksplit) that ttsamd_conv_last_launch
+ * would report after ttsamd_conv1d_splitk with these arguments under the current options, for 16-byte aligned x / y / res (has_res != 0:
+ * a residual is passed) and a workspace of splitk_floats floats (0: none).  TTSAMD_EINVAL where that call would be rejected, and under the
+ * bf16 precisions, whose launchers keep their own choices. */
+int32_t ttsamd_conv1d_route(int32_t batch, int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
+                            int32_t relu_out, int32_t has_res, int32_t mode, int64_t splitk_floats, int32_t* route, int32_t* ksplit);
 /* One HiFi-GAN upsampler (vocoder/hifigan/models.py:96-99, 114-115) as the generator runs it: y = conv_transpose1d(lrelu_slope(x), w,
  * stride u, padding u / 2) + b with the kernel size 2 u (u even), the only form the engine packs.  x [B][Cin][lin] (Cin a multiple of
  * 8), w [Cin][Cout][2u] (torch layout, DEVICE), y [B][Cout][lin * u], bias [Cout] or NULL, lens int64 [B] or NULL: row b reads lens[b]

@@ -351,7 +351,7 @@ DEC_CASES = {
     'W576': (_dec_cfg(576, dec_filter=1152), 2, 100, (100, 37)),     # layernorm_cf_kernel: two passes
     'A5': (_dec_cfg(layers=6), 3, 200, (200, 129, 65)),              # the product's depth
     # rows of 256 frames and 192 blocks per launch: the first size at which the conv-FF pair leaves the direct kernel for the Winograd
-    # F(4,3) route (csrc/conv_wino.hip: wino_route), so that the TTSAMD_WINO=0 run of this case differs from its default run
+    # F(4,3) route (csrc/conv_route.hip: conv_route), so that the TTSAMD_WINO=0 run of this case differs from its default run
     'A6': (_dec_cfg(), 8, 256, (256, 255, 200, 131, 129, 64, 17, 1)),
 }
 # the smallest shapes hold fewer than 64 keys: the largest probability is at least 1 / len whatever the weights are, so the conditions

@@ -151,7 +151,7 @@ BACKBONE_CASES = {
     'B7-256': ('W256', 2, 36, (36, 33), False),
     'B7-384': ('W384', 2, 36, (36, 33), False),
     'B7-640': ('W640', 2, 36, (36, 33), False),
-    # The routes of the benchmark-size call (32 x 496 frames; csrc/conv_wino.hip: wino_route, csrc/conv_mfma.hip: launch_k): the three
+    # The routes of the benchmark-size call (32 x 496 frames; csrc/conv_route.hip: conv_route): the three
     # k = 1 convs on the GEMM route of the F(4,3) kernel (from 512 blocks of 64 rows x 256 frames and t_max >= 256: pwconv2 needs
     # 32 x 257), the embed conv on the direct kernel's 128 x 64 tile (from 768 such tiles: 32 x 321).  32 x 324 is the smallest batch
     # of 32 with all four; at 32 x 256 pwconv2 stays on the direct kernel (its 128 x 128 tile, as the embed conv) next to pwconv1 and

@@ -62,13 +62,17 @@ def _case(cin, cout, k, d, L, B, lens, res, mode, relu):
 
 def _run(dev, case, d, mode, relu, splitk_floats=None, repeat=1):
     """One call on the case's data (the batch `repeat` times over) -> (y on the host, (route, ksplit))."""
-    from ttsamd.engine import conv1d, last_conv_launch
+    from ttsamd.engine import conv1d, conv_route, last_conv_launch
     x, w, b, r, y0, ln, _ = case
     rep = (lambda t: None if t is None else t.repeat(repeat, *([1] * (t.dim() - 1))).to(dev))
     y = rep(y0)
     conv1d(rep(x), w.to(dev), b.to(dev), lens=rep(ln), dilation=d, in_slope=0.1, relu_out=relu, res=rep(r), mode=mode or 0, div=3.0, y=y,
            splitk_floats=splitk_floats)
     rec = last_conv_launch()
+    # ... and it is what the routing function answers for this launch without launching (ttsamd_conv1d_route)
+    asked = conv_route(x.shape[0] * repeat, x.shape[1], w.shape[0], w.shape[2], x.shape[2], dilation=d, in_slope=0.1, relu_out=relu,
+                       has_res=r is not None, mode=mode or 0, splitk_floats=splitk_floats)
+    assert rec == asked, f'launched {rec}, conv_route says {asked}'
     return y.cpu(), rec
 
 
@@ -183,5 +187,5 @@ def test_wino4_splitk_k7_k11(dev, mask, route, shape, lens, res, mode, relu, ksp
 ])
 def test_wino4_splitk_k3(dev, shape, lens, res, mode, relu, ksplit, ttsopt):
     """k = 3 (16-channel chunks, six-point groups only): HiFi-GAN's C = 256 stage and FastPitch's conv-FF pair; slice counts as
-    wino4_ksplit (csrc/conv_wino4.hip) gives them: ~224 blocks wanted, at least 8 chunks per slice."""
+    wino4_ksplit (csrc/conv_route.hip) gives them: ~224 blocks wanted, at least 8 chunks per slice."""
     _wino4_case(dev, ttsopt, '127', 3, shape, lens, res, mode, relu, ksplit)

@@ -183,7 +183,7 @@ def test_wino_decomposition_k3_k7_k11(dev, monkeypatch, k, d, cin, cout, L, B, m
 
 
 @pytest.mark.parametrize('cin,cout,L,B,act,mode', [
-    # (every case is >= 512 blocks of 64 rows x 256 outputs: what wino_route asks of a k = 1 launch)
+    # (every case is >= 512 blocks of 64 rows x 256 outputs: what conv_route (csrc/conv_route.hip) asks of a k = 1 launch)
     (512, 1536, 496, 12, 2, None),       # Vocos pwconv1 + GELU
     (1536, 512, 500, 32, 0, 0),          # pwconv2 + residual
     (384, 192, 1030, 36, 0, None),       # FastPitch's qkv projection: three 64-row blocks

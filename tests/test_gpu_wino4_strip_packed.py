@@ -77,7 +77,7 @@ def _case(cin, cout, k, d, L, B, lens, res, mode, relu):
 
 def _run_mask(dev, ttsopt, mask, case, d, mode, relu, splitk_floats=None):
     """two calls under one mask -> (y on the host, (route, ksplit), max-abs against float64); tails and repeatability asserted"""
-    from ttsamd.engine import conv1d, last_conv_launch
+    from ttsamd.engine import conv1d, conv_route, last_conv_launch
     x, w, b, r, y0, ln, refs = case
     ttsopt.set('TTSAMD_WINO', '1')
     ttsopt.set('TTSAMD_WINO2', '31')
@@ -90,6 +90,9 @@ def _run_mask(dev, ttsopt, mask, case, d, mode, relu, splitk_floats=None):
         conv1d(xd, wd, bd, lens=ld, dilation=d, in_slope=0.1, relu_out=relu, res=rd, mode=mode or 0, div=3.0, y=y, splitk_floats=splitk_floats)
         return y.cpu(), last_conv_launch()
     out, rec = run()
+    asked = conv_route(x.shape[0], x.shape[1], w.shape[0], w.shape[2], x.shape[2], dilation=d, in_slope=0.1, relu_out=relu, has_res=r is not None,
+                       mode=mode or 0, splitk_floats=splitk_floats)
+    assert rec == asked, f'mask {mask}: launched {rec}, conv_route (ttsamd_conv1d_route) says {asked}'
     again, _ = run()
     worst = 0.0
     for i, ref in enumerate(refs):

@@ -847,51 +847,25 @@ int32_t ttsamd_conv1d_ex(const float* x, const float* w, const float* bias, cons
                                 0, stream);
 }
 
-int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, const float* res, const int64_t* lens, int32_t batch,
-                             int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
-                             int32_t relu_out, int32_t mode, float div, float* y, float* packed, float* splitk_ws, int64_t splitk_floats,
-                             void* stream) {
-    TTS_REQUIRE(x && w && y && packed, "conv1d: null argument");
-    TTS_REQUIRE(splitk_floats >= 0 && (splitk_ws != nullptr || splitk_floats == 0), "conv1d: %lld split-K floats without a workspace",
-                (long long)splitk_floats);
+// The ConvParams of a ttsamd_conv1d_splitk call, shared with ttsamd_conv1d_route so that both route the same launch.  The forms a launch
+// carries sit in `packed` one behind the other (ttsamd_conv1d_packed_floats): direct | bf16 planes | F(2,3) | F(4,3) | seven-point groups.
+static int32_t conv1d_params(ConvParams& p, const float* x, const float* bias, const float* res, const int64_t* lens, int32_t batch,
+                             int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope, int32_t relu_out,
+                             int32_t mode, float div, float* y, float* packed, float* splitk_ws, int64_t splitk_floats) {
     TTS_REQUIRE(mode >= 0 && mode <= 2 && (mode != 2 || div != 0.f), "conv1d: bad mode / div");
     // the residual-preload epilogues apply the activation to y_prev + res + conv + b: only mode 0 has the documented meaning with relu_out
     TTS_REQUIRE(relu_out == 0 || mode == 0, "conv1d: relu_out with an accumulate mode (mode %d) is not defined", mode);
-    hipStream_t s = (hipStream_t)stream;
     const int cp = cout_padded(cout);
     const int64_t n = (int64_t)cin * k * cp;
-    hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, cout, cin, k,
-                       cp, packed);
-    TTS_CHECK_HIP(hipGetLastError());
-    ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.x = x; p.x_bs = (int64_t)cin * lin; p.x_cs = lin;
     p.w = packed; p.bias = bias;
     p.precision = default_precision();
-    if (p.precision != 0) {
-        unsigned short* planes = reinterpret_cast<unsigned short*>(packed + n);
-        hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, packed, n, planes);
-        TTS_CHECK_HIP(hipGetLastError());
-        p.w_bf16 = planes;
-    }
+    if (p.precision != 0) p.w_bf16 = packed + n;
     if ((k == 3 || k == 7 || k == 11) && p.precision == 0 && cin % 8 == 0) {
-        float* wino = packed + 2 * n;
-        const int64_t nw = (int64_t)cin * wino2_groups(k) * cp;
-        hipLaunchKernelGGL(pack_wino2_weight_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, cout, cin, k, cp, wino);
-        TTS_CHECK_HIP(hipGetLastError());
-        p.w_wino = wino;
-        float* wino4 = wino + nw;
-        const int64_t nw4 = (int64_t)cin * wino4_groups(k) * cp;
-        hipLaunchKernelGGL(pack_wino4_weight_kernel, dim3((unsigned)((nw4 + 255) / 256)), dim3(256), 0, s, w, cout, cin, k, cp, wino4);
-        TTS_CHECK_HIP(hipGetLastError());
-        p.w_wino4 = wino4;
-        if (wino44_groups(k) != 0) {
-            float* wino44 = wino4 + nw4;
-            const int64_t nw44 = (int64_t)cin * wino44_groups(k) * cp;
-            hipLaunchKernelGGL(pack_wino44_weight_kernel, dim3((unsigned)((nw44 + 255) / 256)), dim3(256), 0, s, w, cout, cin, k, cp, wino44);
-            TTS_CHECK_HIP(hipGetLastError());
-            p.w_wino44 = wino44;
-        }
+        p.w_wino = packed + 2 * n;
+        p.w_wino4 = p.w_wino + (int64_t)cin * wino2_groups(k) * cp;
+        if (wino44_groups(k) != 0) p.w_wino44 = p.w_wino4 + (int64_t)cin * wino4_groups(k) * cp;
     }
     p.y = y; p.y_bs = (int64_t)cout * lin; p.y_cs = lin; p.y_ts = 1;
     p.lens_in = lens; p.lens_out = lens; p.len_in_mul = 1; p.len_out_mul = 1;
@@ -900,10 +874,63 @@ int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, 
     p.res = res; p.r_bs = (int64_t)cout * lin; p.r_cs = lin;
     p.n_phase = 1; p.in_slope = in_slope; p.relu_out = relu_out; p.mode = mode; p.div = div; p.batch = batch;
     if (splitk_ws != nullptr && splitk_floats > 0) { p.splitk_ws = splitk_ws; p.splitk_floats = splitk_floats; }
+    return 0;
+}
+
+int32_t ttsamd_conv1d_splitk(const float* x, const float* w, const float* bias, const float* res, const int64_t* lens, int32_t batch,
+                             int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
+                             int32_t relu_out, int32_t mode, float div, float* y, float* packed, float* splitk_ws, int64_t splitk_floats,
+                             void* stream) {
+    TTS_REQUIRE(x && w && y && packed, "conv1d: null argument");
+    TTS_REQUIRE(splitk_floats >= 0 && (splitk_ws != nullptr || splitk_floats == 0), "conv1d: %lld split-K floats without a workspace",
+                (long long)splitk_floats);
+    ConvParams p;
+    TTS_TRY(conv1d_params(p, x, bias, res, lens, batch, cin, cout, k, dilation, lin, in_slope, relu_out, mode, div, y, packed, splitk_ws,
+                          splitk_floats));
+    hipStream_t s = (hipStream_t)stream;
+    const int cp = p.CoutP;
+    const int64_t n = (int64_t)cin * k * cp;
+    const auto blocks = [](int64_t floats) { return dim3((unsigned)((floats + 255) / 256)); };
+    hipLaunchKernelGGL(pack_conv_weight_kernel, blocks(n), dim3(256), 0, s, w, cout, cin, k, cp, packed);
+    TTS_CHECK_HIP(hipGetLastError());
+    if (p.w_bf16 != nullptr) {
+        hipLaunchKernelGGL(split_bf16_kernel, blocks(n), dim3(256), 0, s, packed, n, reinterpret_cast<unsigned short*>(packed + n));
+        TTS_CHECK_HIP(hipGetLastError());
+    }
+    if (p.w_wino != nullptr) {
+        hipLaunchKernelGGL(pack_wino2_weight_kernel, blocks((int64_t)cin * wino2_groups(k) * cp), dim3(256), 0, s, w, cout, cin, k, cp,
+                           const_cast<float*>(p.w_wino));
+        TTS_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(pack_wino4_weight_kernel, blocks((int64_t)cin * wino4_groups(k) * cp), dim3(256), 0, s, w, cout, cin, k, cp,
+                           const_cast<float*>(p.w_wino4));
+        TTS_CHECK_HIP(hipGetLastError());
+    }
+    if (p.w_wino44 != nullptr) {
+        hipLaunchKernelGGL(pack_wino44_weight_kernel, blocks((int64_t)cin * wino44_groups(k) * cp), dim3(256), 0, s, w, cout, cin, k, cp,
+                           const_cast<float*>(p.w_wino44));
+        TTS_CHECK_HIP(hipGetLastError());
+    }
     prof_begin(s, 2.0 * cout * cin * k);
     const int32_t rc = launch_conv(p, s);
     prof_end(s);
     return rc;
+}
+
+int32_t ttsamd_conv1d_route(int32_t batch, int32_t cin, int32_t cout, int32_t k, int32_t dilation, int32_t lin, float in_slope,
+                            int32_t relu_out, int32_t has_res, int32_t mode, int64_t splitk_floats, int32_t* route, int32_t* ksplit) {
+    TTS_REQUIRE(route && ksplit, "conv1d_route: null argument");
+    TTS_REQUIRE(batch >= 1 && cin >= 1 && cout >= 1 && k >= 1 && lin >= 1 && dilation >= 1 && dilation <= 5 && splitk_floats >= 0,
+                "conv1d_route: bad shape");
+    float* const any = reinterpret_cast<float*>((uintptr_t)256);   // stands for every buffer: 16-byte aligned, never followed
+    ConvParams p;
+    TTS_TRY(conv1d_params(p, any, any, has_res ? any : nullptr, nullptr, batch, cin, cout, k, dilation, lin, in_slope, relu_out, mode, 1.f, any,
+                          any, any, splitk_floats));
+    TTS_REQUIRE(p.precision == 0, "conv1d_route: the bf16 launchers keep their own choices (precision %d)", p.precision);
+    const ConvRoute r = conv_route(p, conv_route_opts());
+    TTS_REQUIRE(r.id >= 0 && (relu_out < 2 || k == 1 || k == 5), "conv1d_route: no fp32 kernel takes k = %d, Cin = %d, relu_out = %d", k, cin, relu_out);
+    *route = r.id;
+    *ksplit = r.ksplit;
+    return 0;
 }
 
 int32_t ttsamd_conv1d(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t batch,

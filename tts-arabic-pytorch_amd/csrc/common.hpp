@@ -121,7 +121,7 @@ struct ConvParams {
     int32_t x_cs;
     const float* w;      // packed fp32 weights [n_phase][Cin/8][K][2][CoutP][4]
     const void* w_bf16;  // same element order as bf16: plane hi then plane lo (nullptr if not packed)
-    const float* w_wino; // k = 3 only: the Winograd F(2,3) filters as a 4-tap conv [Cin/8][4][2][CoutP][4] (conv_wino.hip; nullptr = none)
+    const float* w_wino; // k = 3 / 7 / 11: the Winograd F(2,3) group filters [Cin/8][wino2_groups(k)][2][CoutP][4] (pack_wino2_weight, conv_wino2.hip; k = 3: four taps, also conv_wino.hip's; nullptr = none)
     const float* w_wino4; // k = 3 / 7 / 11: the Winograd F(4,3) group filters [Cin/8][wino4_groups(k)][2][CoutP][4] (conv_wino4.hip; nullptr = none)
     int32_t precision;   // 0 fp32 MFMA, 1 bf16 MFMA, 2 split bf16 (3 MFMAs per product)
     const float* bias;   // [>=Cout] or nullptr
@@ -146,8 +146,9 @@ struct ConvParams {
     float div;
     int32_t batch;
     // split-K for problems that cannot fill the chip (batch 1, encoder-side S = 64): when splitk_ws is set and
-    // the tile grid has < 192 blocks, the Cin range is cut into `ksplit` slices (extra grid.y factor) that write
-    // raw partial sums to splitk_ws[ks][b][Cout][Nout]; a second kernel sums them and applies the epilogue.
+    // the tile grid is small (conv_route.hip: direct engine < 320 blocks, aiming at 640; F(4,3) < 192, aiming at 224), the Cin range is
+    // cut into `ksplit` slices (extra grid factor) that write raw partial sums to splitk_ws[ks][b][Cout][Nout]; a second kernel sums
+    // them and applies the epilogue.
     float* splitk_ws;         // >= splitk_floats floats of scratch, or nullptr (never split)
     int64_t splitk_floats;
     int32_t ksplit;           // set by the launcher
@@ -178,8 +179,30 @@ void conv_log(const char* kind, int K, int cin, int cout, int nout, int batch, i
 bool compact_order(const void* lens, int batch);
 // Launches the kernel; returns 0 or a negative code.
 int32_t launch_conv(const ConvParams& p, hipStream_t stream);
+// Routing of an exact-fp32 launch_conv (conv_route.hip): decided once per launch, by a function that launches nothing.
+struct ConvRouteOpts { int wino, wino2, wino4, deep_splitk; };   // the options a route depends on, snapshotted once per launch
+struct ConvRoute {
+    int id;       // what note_conv_launch records: 0 direct, 1 / 2 F(2,3), 3 / 4 F(4,3) six- / seven-point, 7 / 8 their packed strip form;
+                  // -1: no kernel takes it (kernel size not built, C-in no multiple of the tile's chunk) -- the direct launcher reports it
+    int ksplit;   // C-in slices (1 = none), direct and F(4,3) alike
+    int epi;      // F(4,3): the epilogue kind of conv1d_wino4_f32, 0 / 3 / 4 / 7
+    int co_blk, nt_blk;   // direct engine: rows x columns of the tile
+};
+ConvRouteOpts conv_route_opts();                                   // the only place the fp32 conv path calls opt_int for these four
+ConvRoute conv_route(const ConvParams& p, const ConvRouteOpts& o);  // pure: no opt_int, no globals, no HIP call, no allocation
+// rows of y (and of the residual) are 16-byte aligned: what every float4 row epilogue asks
+inline bool conv_rows_aligned(const ConvParams& p) {
+    return (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
+           (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0));
+}
+// input channels per chunk of the direct engine's co_blk x nt_blk tile (conv_mfma.hip: Geo::KC).  k = 3 on the 128 x 128 tile takes two
+// octets: a one-octet chunk is 48 MFMAs per wave (1.3 us) between barriers; two halve the barriers and still leave two blocks per CU
+// (FastPitch's 384 -> 1536 conv 121 -> 128 TFLOP/s, HiFi-GAN C = 128 k = 3 106 -> 108; the smaller k = 3 tiles lose 2-3 % with it)
+constexpr int conv_chunk_channels(int k, int nt_blk, int co_blk) {
+    return (k == 3 && nt_blk == 128 && co_blk == 128) ? 16 : (k == 1 ? 32 : (k == 2 ? 16 : 8));
+}
 // What the calling thread's last fp32 conv launch decided (ttsamd_conv_last_launch; conv_mfma.hip): two thread_local ints, written by
-// the launcher that takes the decision.  route 0: direct kernel, 1 / 2: the F(2,3) kernels (conv_wino.hip / conv_wino2.hip), 3 / 4: F(4,3)
+// launch_conv with its ConvRoute and by the transposed-conv launchers.  route 0: direct kernel, 1 / 2: the F(2,3) kernels (conv_wino.hip / conv_wino2.hip), 3 / 4: F(4,3)
 // on six- / seven-point groups, 5: the all-phase transposed conv (convt_mfma.hip), 6: the transposed conv as a two-tap conv on F(4,2)
 // (launch_convt_wino, conv_wino4.hip), 7 / 8: F(4,3) on six- / seven-point groups in the PACKED strip form (dilation 3 / 5, packed tiles and
 // the register epilogue: conv_wino4.hip EPI 7, TTSAMD_WINO4 bit 7).  Host only, no atomics.
@@ -238,22 +261,22 @@ bool resblock2_pair_supported(int32_t channels, int32_t k, int32_t d1, int32_t d
 int32_t launch_resblock2_pair(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
                               const float* b2, int32_t k, int32_t d1, int32_t d2, const int64_t* lens, int32_t len_mul, int32_t L,
                               int32_t batch, int32_t mode, float div, float slope, hipStream_t stream);
-// Winograd F(2,3) path of the k = 3, dilation-1 convs (conv_wino.hip): routing test, launcher, host-side filter transform + packing
-int wino_route(const ConvParams& p);       // 0: direct kernel, 1: conv1d_wino_f32, 2: conv1d_wino2_f32, 3: conv1d_wino4_f32 (conv_wino.hip)
+// Winograd F(2,3) path of the k = 3, dilation-1 convs (conv_wino.hip): launcher, host-side filter transform + packing
 int32_t launch_wino(const ConvParams& p, hipStream_t stream);
 void pack_wino_weight(const float* w, int cout, int cin, float* out);   // out: cin * 4 * cout_padded(cout) floats
 // ... and its generalisation to k = 7 / 11 as sums of F(2,3) sub-filters + single taps (conv_wino2.hip): NG = wino2_groups(k) operand
 // groups per octet, weights [Cin/8][NG][2][CoutP][4] (k = 3: identical to pack_wino_weight)
 int wino2_groups(int k);
-int wino2_block_outputs(int coutp, int dil);     // outputs per block of the kernel launch_wino2 picks
+// outputs per tile at dilation d (see the kernel): the largest multiple of 2 d and of 4 in 2 * npair
+__device__ __host__ constexpr int wino2_tile(int d, int npair) { return (2 * npair / ((d & 1) ? 4 * d : 2 * d)) * ((d & 1) ? 4 * d : 2 * d); }
 int32_t launch_wino2(const ConvParams& p, hipStream_t stream);
 void pack_wino2_weight(const float* w, int cout, int cin, int k, float* out);   // out: cin * wino2_groups(k) * cout_padded(cout) floats
 // ... and the F(4,3) decomposition (conv_wino4.hip: 6 / 16 / 23 products per output QUAD at k = 3 / 7 / 11): 64 rows x 64 quads per block
 int wino4_groups(int k);                         // groups per octet in the packed weights: 6 / 16 / 24 (k = 11: 23 + one zero group)
 int wino44_groups(int k);                        // ... of the seven-point form: 13 / 20 at k = 7 / 11 (0: no such form)
 constexpr int kWino4Default = 255;               // TTSAMD_WINO4 when unset
-bool wino44_wanted(const ConvParams& p);         // the launch goes to the seven-point groups (has them, and its k's bit is set)
-int wino4_block_outputs(int dil);
+// outputs per tile at dilation d: the largest multiple of 4 d in 4 * ntup
+__device__ __host__ constexpr int wino4_tile(int d, int ntup) { return (4 * ntup / (4 * d)) * (4 * d); }
 // PACKED tiles of the dilated F(4,3) launches (conv_wino4.hip, EPI 7).  A row of n outputs at dilation d is cut into G = ceil(n / 4d)
 // groups of 4 d columns = T = d G tuples; tuple t holds the columns (t / d) 4d + t % d + j d, j = 0..3, and tile i the tuples
 // [64 i, 64 i + 64): every tuple slot of every tile but a row's last is live (the plain tile -- the largest multiple of 4 d columns in
@@ -265,9 +288,8 @@ __host__ __device__ constexpr int wino4_pk_tiles(int n, int d) { return (wino4_p
 __host__ __device__ constexpr int wino4_pk_col(int t, int d) { return (t / d) * 4 * d + t % d; }      // first column of tuple t
 __host__ __device__ constexpr int wino4_pk_q0(int tile, int d) { return (64 * tile / d) * 4 * d; }
 __host__ __device__ constexpr int wino4_pk_r0(int tile, int d) { return 64 * tile % d; }
-int wino4_ksplit(const ConvParams& p);           // C-in slices the launcher will use for this launch (1 = none)
 int32_t launch_splitk_reduce(const ConvParams& q, hipStream_t stream);   // conv_mfma.hip: y = epilogue(sum of the ksplit partial tensors)
-int32_t launch_wino4(const ConvParams& p, hipStream_t stream);
+int32_t launch_wino4(const ConvParams& p, const ConvRoute& r, hipStream_t stream);   // r.id 3 / 4 / 7 / 8
 void wino4_filter_groups(const float* g, int k, float* o);                      // one (co, ci) filter -> its wino4_groups(k) group filters
 void pack_wino4_weight(const float* w, int cout, int cin, int k, float* out);   // out: cin * wino4_groups(k) * cout_padded(cout) floats
 void wino44_filter_groups(const float* g, int k, float* o);                     // k = 7 / 11: one filter -> its wino44_groups(k) seven-point group filters

@@ -41,16 +41,10 @@
 
 namespace ttsamd {
 
-// octets (8 input channels) staged per chunk
-
-
 template <int K, int NT_BLK, int CO_BLK>
 struct Geo {
-    // octets (8 input channels) per chunk.  k = 3 on the 128 x 128 tile takes two: a one-octet chunk is 48 MFMAs per wave (1.3 us)
-    // between barriers; two halve the barriers and still leave two blocks per CU (FastPitch's 384 -> 1536 conv 121 -> 128 TFLOP/s,
-    // HiFi-GAN C = 128 k = 3 106 -> 108; the smaller k = 3 tiles lose 2-3 % with it)
-    static constexpr int NOCT = (K == 3 && NT_BLK == 128 && CO_BLK == 128) ? 2 : OctsOf<K>::NOCT;
-    static constexpr int KC = 8 * NOCT;                       // input channels per chunk
+    static constexpr int KC = conv_chunk_channels(K, NT_BLK, CO_BLK);   // input channels per chunk (common.hpp: the routing counts chunks too)
+    static constexpr int NOCT = KC / 8;                       // octets (8 input channels) per chunk
     static constexpr int WS = NT_BLK + (K - 1) * DMAX;        // staged columns (one float4 each)
     static constexpr int XI = 2 * NOCT * WS;                  // X float4s per stage
     static constexpr int NXI = (XI + 255) / 256;              // ... per thread
@@ -547,14 +541,14 @@ bool compact_order(const void* lens, int batch) { return lens != nullptr && batc
 constexpr int kXcdWeightKB = 3000;
 
 template <int K, int MT, int NTL, int WM, int WN>
-static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
+static int32_t launch_cfg(const ConvParams& p, int ksplit, hipStream_t stream) {
     constexpr int CO_BLK = WM * MT * 32, NT_BLK = WN * NTL * 32;
     using G = Geo<K, NT_BLK, CO_BLK>;
     TTS_REQUIRE(p.Cin % G::KC == 0, "conv: Cin=%d must be a multiple of %d for K=%d", p.Cin, G::KC, K);
     const size_t lds = (size_t)G::NSTAGE * G::BUF4 * sizeof(float4);
     dim3 grid((p.Nout + NT_BLK - 1) / NT_BLK, (p.CoutP / CO_BLK) * p.n_phase, p.batch);
     ConvParams q = p;
-    q.ksplit = 1;
+    q.ksplit = ksplit;
     q.tile_major = 0;
     q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
     {
@@ -575,22 +569,11 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
                 q.xcd_w = (int)g2 | 0x100 | (q.xcd_w << 16);   // (bits 16..: the plain choice, for a split-K launch)
         }
     }
-    const int64_t nblk = (int64_t)grid.x * grid.y * grid.z, per = (int64_t)p.batch * p.Cout * p.Nout;
-    const int n_chunks = p.Cin / G::KC;
-    constexpr int sk_blocks = 320, sk_target = 640, sk_chunks = 8;
-    if (p.splitk_ws && p.n_phase == 1 && p.y_ts == 1 && nblk < sk_blocks && n_chunks >= sk_chunks) {
-        int64_t ks = std::min<int64_t>((sk_target + nblk - 1) / nblk, n_chunks / 4);
-        ks = std::min<int64_t>(ks, p.splitk_floats / per);
-        if (ks >= 2) q.ksplit = (int)ks;
-        if (ks >= 2 && (q.xcd_w & 0x100)) q.xcd_w >>= 16;
-    }
+    if (q.ksplit > 1 && (q.xcd_w & 0x100)) q.xcd_w >>= 16;   // C-in slices (conv_route.hip): the plain map
     if (q.xcd_w & 0x100) q.xcd_w &= 0x1ff;
     grid.y *= q.ksplit;
-    note_conv_launch(0, q.ksplit);
     // epilogue kind (see the kernel): the float4 row epilogue needs 16-byte aligned rows of y (and of the residual)
-    const bool vec_ok = q.ksplit == 1 && p.y_ts == 1 && p.n_phase == 1 && (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 &&
-                        ((uintptr_t)p.y & 15) == 0 &&
-                        (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0));
+    const bool vec_ok = q.ksplit == 1 && p.y_ts == 1 && p.n_phase == 1 && conv_rows_aligned(p);
     // GELU (Vocos pwconv1, k = 1) and tanh (Tacotron2 postnet, k = 5) are compiled into those kernel sizes only
     TTS_REQUIRE(p.relu_out < 2 || K == 1 || K == 5, "conv: GELU / tanh epilogues are built for kernel sizes 1 and 5 only (K=%d)", K);
     // the residual rides in through the accumulators (EPI 3) unless a per-channel scale sits between conv and residual
@@ -608,44 +591,16 @@ static int32_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     return 0;
 }
 
-// Tile choice: the largest tile that still gives the chip >= 3 blocks per CU (768); small
-// problems (batch 1, encoder-side S = 64) fall back to smaller tiles to fill the 256 CUs.
+// the tile conv_route chose (conv_route.hip: route_direct)
 template <int K>
-static int32_t launch_k(const ConvParams& p, hipStream_t stream) {
-    auto blocks = [&](int co_blk, int nt_blk) -> int64_t {
-        return (int64_t)((p.Nout + nt_blk - 1) / nt_blk) * (p.CoutP / co_blk) * p.n_phase * p.batch;
-    };
-    // blocks a launch should have: 3 per CU -- unless the whole problem is about one round of the smallest tiles (batch 1: 914 tiles
-    // of 64 x 64 for a stage-2 conv): then one block per CU of a LARGE tile (64 x 256: 230 blocks at 0.85 of the matrix peak) beats
-    // four of the small one (0.62): batch 1 5.04 -> 4.86 ms per call (200 vs 768 blocks wanted)
-    const int64_t want = blocks(64, 64) <= 1024 ? (int64_t)200 : (int64_t)768;
-    const bool tiny = p.Nout <= 96;
-    // (measured and not kept, round 4: a 96 co x 128 t tile for FastPitch's second conv-FF conv -- 1536 -> 384, exactly two blocks per CU
-    // instead of 2.6-2.8 of the 128 x 64 tile -- runs the step in 77.83 vs 77.82 ms)
-    if (p.CoutP % 128 == 0) {
-        // deep-K layers on short sequences (HiFi-GAN stage 1: C = 256, 8 positions per frame) have few, long blocks;
-        // a launch is then 2-4 rounds of blocks and its tail costs 15-19 %: finer tiles pay there
-        const bool few_long = p.Cin >= 256 && p.CoutP <= p.Cin && !tiny && blocks(128, 128) < 4 * want;
-        if (few_long && K == 3 && blocks(128, 64) >= want) return launch_cfg<K, 1, 2, 4, 1>(p, stream);  // 128 co x 64 t
-        if (few_long && K >= 7 && blocks(64, 128) >= want) return launch_cfg<K, 1, 2, 2, 2>(p, stream);  //  64 co x 128 t
-        if (K < 11 && !tiny && blocks(128, 128) >= want && (K != 3 || p.Cin % 16 == 0))                 // (k = 3: 16-channel chunks)
-            return launch_cfg<K, 2, 2, 2, 2>(p, stream);                                                // 128 co x 128 t
-        if (K == 11 && !tiny && blocks(64, 256) >= want) return launch_cfg<K, 2, 2, 1, 4>(p, stream);   //  64 co x 256 t
-        // deep K, a few hundred tiles (FastPitch's second conv-FF conv, 1536 -> 384, at batch 7..13): 128 x 64 tiles with K split
-        // (launch_cfg: < 320 tiles -> 2..4 slices) instead of twice as many 64 x 64 tiles that each walk all 96 chunks
-        if (p.splitk_ws && p.Cin >= 1024 && !tiny && blocks(128, 64) >= 160 && blocks(128, 64) < 320 &&
-            (int64_t)2 * p.batch * p.Cout * p.Nout <= p.splitk_floats) {
-            if (opt_int(OPT_DEEP_SPLITK, 1) != 0) return launch_cfg<K, 1, 2, 4, 1>(p, stream);   // read per launch of this (rare) shape: the tests flip it
-        }
-        if (blocks(128, 64) >= want || (tiny && blocks(64, 64) < 2 * want)) return launch_cfg<K, 1, 2, 4, 1>(p, stream);   // 128 co x 64 t
-        return launch_cfg<K, 1, 1, 2, 2>(p, stream);                                                    //  64 co x  64 t
-    }
-    if (p.CoutP % 64 == 0) {
-        if (!tiny && blocks(64, 256) >= want) return launch_cfg<K, 2, 2, 1, 4>(p, stream);              //  64 co x 256 t
-        return launch_cfg<K, 1, 1, 2, 2>(p, stream);                                                    //  64 co x  64 t
-    }
-    if (!tiny && blocks(32, 256) >= want) return launch_cfg<K, 1, 2, 1, 4>(p, stream);                  //  32 co x 256 t
-    return launch_cfg<K, 1, 1, 1, 4>(p, stream);                                                        //  32 co x 128 t
+static int32_t launch_k(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    if (r.co_blk == 128 && r.nt_blk == 64) return launch_cfg<K, 1, 2, 4, 1>(p, r.ksplit, stream);    // 128 co x 64 t
+    if (r.co_blk == 64 && r.nt_blk == 128) return launch_cfg<K, 1, 2, 2, 2>(p, r.ksplit, stream);    //  64 co x 128 t
+    if (r.co_blk == 128 && r.nt_blk == 128) return launch_cfg<K, 2, 2, 2, 2>(p, r.ksplit, stream);   // 128 co x 128 t
+    if (r.co_blk == 64 && r.nt_blk == 256) return launch_cfg<K, 2, 2, 1, 4>(p, r.ksplit, stream);    //  64 co x 256 t
+    if (r.co_blk == 64 && r.nt_blk == 64) return launch_cfg<K, 1, 1, 2, 2>(p, r.ksplit, stream);     //  64 co x  64 t
+    if (r.co_blk == 32 && r.nt_blk == 256) return launch_cfg<K, 1, 2, 1, 4>(p, r.ksplit, stream);    //  32 co x 256 t
+    return launch_cfg<K, 1, 1, 1, 4>(p, r.ksplit, stream);                                           //  32 co x 128 t
 }
 
 // TTSAMD_CONV_LOG=<file>: one CSV line per conv launch, in launch order (= rocprofv3 dispatch order), so that
@@ -663,19 +618,21 @@ int32_t launch_conv(const ConvParams& p, hipStream_t stream) {
     TTS_REQUIRE(p.n_phase >= 1 && p.batch >= 1, "conv: bad n_phase/batch");
     TTS_REQUIRE(p.dil >= -DMAX && p.dil <= DMAX && p.dil != 0, "conv: dilation %d outside [-%d,%d]", p.dil, DMAX, DMAX);
     if (p.Nout <= 0) return 0;
-    const int wino = wino_route(p);
-    conv_log(p.precision == 0 ? (wino == 3 ? "f32_wino4" : (wino ? "f32_wino" : "f32")) : "bf16", p.K, p.Cin, p.Cout, p.Nout, p.batch, p.res != nullptr, p.mode, p.len_out_mul,
+    // the route: decided here, once, from one snapshot of the switches (conv_route.hip); the launchers below execute it
+    const ConvRoute r = p.precision == 0 ? conv_route(p, conv_route_opts()) : ConvRoute{0, 1, 0, 0, 0};
+    conv_log(p.precision == 0 ? (r.id >= 3 ? "f32_wino4" : (r.id > 0 ? "f32_wino" : "f32")) : "bf16", p.K, p.Cin, p.Cout, p.Nout, p.batch, p.res != nullptr, p.mode, p.len_out_mul,
              p.lens_out != nullptr, p.n_phase);
     if (p.precision != 0) return launch_conv_bf16_any(p, stream);
     TTS_REQUIRE(!p.x_packed && !p.y_packed, "conv: packed bf16 activations exist only in the bf16 mode");
-    if (wino) return wino == 3 ? launch_wino4(p, stream) : (wino == 2 ? launch_wino2(p, stream) : launch_wino(p, stream));
+    if (r.id >= 0) note_conv_launch(r.id, r.ksplit);   // (-1: the direct launcher below says why)
+    if (r.id > 0) return r.id >= 3 ? launch_wino4(p, r, stream) : (r.id == 2 ? launch_wino2(p, stream) : launch_wino(p, stream));
     switch (p.K) {
-        case 1: return launch_k<1>(p, stream);
-        case 2: return launch_k<2>(p, stream);
-        case 3: return launch_k<3>(p, stream);
-        case 5: return launch_k<5>(p, stream);
-        case 7: return launch_k<7>(p, stream);
-        case 11: return launch_k<11>(p, stream);
+        case 1: return launch_k<1>(p, r, stream);
+        case 2: return launch_k<2>(p, r, stream);
+        case 3: return launch_k<3>(p, r, stream);
+        case 5: return launch_k<5>(p, r, stream);
+        case 7: return launch_k<7>(p, r, stream);
+        case 11: return launch_k<11>(p, r, stream);
         default:
             set_error("conv: kernel size %d not instantiated (1,2,3,5,7,11)", p.K);
             return TTSAMD_EINVAL;

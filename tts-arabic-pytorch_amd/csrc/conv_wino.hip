@@ -21,9 +21,6 @@
 //     residual preload (EPI 3) puts res[2j] into M0 and -res[2j + 1] into M3.
 #include <cstdlib>
 #include <cstring>
-
-#include <algorithm>
-
 #include <vector>
 
 #include "conv_mfma_common.hpp"
@@ -309,98 +306,17 @@ static int32_t launch_wino_epi(const ConvParams& q, dim3 grid, hipStream_t strea
     return 0;
 }
 
-// What the row epilogue and the residual preload of the three Winograd kernels ask of a launch: rows of y (and of the residual) are
-// 16-byte aligned, and a row block addresses within 2^31 bytes (32-bit buffer offsets)
-static bool rows_vec_ok(const ConvParams& p) {
-    return (p.y_cs & 3) == 0 && (p.y_bs & 3) == 0 && ((uintptr_t)p.y & 15) == 0 &&
-           (!p.res || ((p.r_cs & 3) == 0 && (p.r_bs & 3) == 0 && ((uintptr_t)p.res & 15) == 0)) &&
-           (int64_t)p.Cout * std::max(std::max(p.r_cs, p.y_cs), 1) * 4 < ((int64_t)1 << 31);
-}
-
-// Routing of an exact-fp32 conv launch: 0 = the direct kernel, 1 = conv1d_wino_f32 (this file: k = 3, dilation 1, 128-row tiles),
-// 2 = conv1d_wino2_f32 (conv_wino2.hip: k = 3 / 7 / 11, dilation 1 / 3 / 5, 128- or 64-row tiles).  Wanted when the Winograd weights
-// are there, the padding is 'same', rows are float4-aligned (row epilogue, residual preload) and the launch has at least 192 blocks.
-// The two switches are read ONCE per launch (A/B runs and the parity tests of all three kernels flip them between calls):
-//   TTSAMD_WINO=0        everything on the direct kernel
-//   TTSAMD_WINO2=<mask>  what the decomposition kernel takes: bit 0 / 1 / 2 = k 3 / 7 / 11, bit 3 = their dilated (3 / 5) convs, bit 4
-//                        = Cout = 64.  Default 31 (same-box A/B of the bench step, tools/ab_env.sh: 74.2 ms with none, 73.1 with k = 3,
-//                        68.5 with k = 7 + 11, 67.5 with the three, 65.6 with dilations, 64.6-65.1 with Cout = 64)
-int wino_route(const ConvParams& p) {
-    if (p.precision != 0) return 0;
-    if (opt_int(OPT_WINO, 1) == 0) return 0;
-    if (p.K == 1) {
-        // k = 1 (Vocos' pointwise convs and head, FastPitch's qkv / o_net projections) on the F(4,3) kernel's skeleton with nothing to transform
-        // (conv_wino4.hip, Wino4Geo::WSHARE): the direct engine's packed weights as they are; TTSAMD_WINO4 bit 4.  Same tile as the F(4,3) launches.
-        const int mask4 = (int)opt_int(OPT_WINO4, kWino4Default);
-        const bool ok1 = (mask4 & 16) && p.w != nullptr && p.dil == 1 && p.pad == 0 && p.n_phase == 1 && p.y_ts == 1 && p.CoutP % 64 == 0 &&
-                         p.Cin % 32 == 0 && p.in_slope >= 0.f && p.in_slope <= 1.f && !p.x_packed && !p.y_packed &&
-                         rows_vec_ok(p);
-        if (!ok1) return 0;
-        // (k = 1 never splits K here: wino4_ksplit answers > 1 only under 192 blocks and then aims at 224, so blocks1 stays under the 512
-        // this route asks for -- the two rules exclude each other, and the factor below is always 1 on a launch that passes)
-        const int64_t blocks1 = (int64_t)((p.Nout + 255) / 256) * (p.CoutP / 64) * p.batch * wino4_ksplit(p);
-        // one full round of the chip's 512 block slots or more: Vocos' GEMMs (512 ... 1536 blocks); FastPitch's qkv / o_net at batch 32 (192 / 384
-        // blocks) stay on the direct kernel's smaller tiles -- same-box A/B of the step: 52.43 ms with them here, 52.33 without
-        return (blocks1 >= 512 && p.Nout >= 256) ? 3 : 0;
-    }
-    if ((p.w_wino == nullptr && p.w_wino4 == nullptr) || (p.K != 3 && p.K != 7 && p.K != 11)) return 0;
-    if (p.w_wino4 != nullptr) {
-        // F(4,3) decomposition (conv_wino4.hip): TTSAMD_WINO4=<mask>, bit 0 / 1 / 2 = k 3 / 7 / 11, bit 3 = their dilated convs, bit 4 = k 1
-        // (above), bit 5 / 6 = what it takes of k = 7 / 11 runs on seven-point groups (13 / 20 products per quad instead of 16 / 23:
-        // launch_wino4 picks the kernel, same tile, same conditions); default 127.
-        // (k = 3 -- 6 instead of 8 products per quad -- did not pay with the kernel's first staging path: 414 / 330 vs 392 / 315 us on
-        // FastPitch's conv-FF pair; with the aligned 16-byte window loads it does: same-box A/B of the step 55.46 (mask 14) vs 54.68 ms.)
-        // 64 rows x 64 quads per block, float4-aligned rows, at least 192 blocks (below: the F(2,3) / direct routing that follows)
-        const int mask4 = (int)opt_int(OPT_WINO4, kWino4Default);
-        const int kbit4 = p.K == 3 ? 1 : (p.K == 7 ? 2 : 4);
-        const bool ok4 = (mask4 & kbit4) && (p.dil == 1 || (mask4 & 8)) && (p.K != 3 || p.Cin % 16 == 0) &&
-                         (p.dil == 1 || p.dil == 3 || p.dil == 5) && p.pad == p.dil * (p.K - 1) / 2 && p.n_phase == 1 && p.y_ts == 1 &&
-                         p.CoutP % 64 == 0 && p.Cin % 8 == 0 && p.scale == nullptr && p.relu_out < 2 && p.in_slope >= 0.f && p.in_slope <= 1.f &&
-                         rows_vec_ok(p);
-        if (ok4) {
-            const int bo4 = wino4_block_outputs(p.dil);
-            const int64_t blocks4 = (int64_t)((p.Nout + bo4 - 1) / bo4) * (p.CoutP / 64) * p.batch * wino4_ksplit(p);
-            if (blocks4 >= 192 && p.Nout >= 256) return 3;
-        }
-        if (p.w_wino == nullptr) return 0;
-    }
-    const int mask = (int)opt_int(OPT_WINO2, 31);
-    const int kbit = p.K == 3 ? 1 : (p.K == 7 ? 2 : 4);
-    const bool rows64 = p.CoutP % 128 != 0;
-    // what the decomposition kernel can take of this launch (its k = 3 chunks are 16 channels)
-    const bool w2 = (mask & kbit) && (p.dil == 1 || (mask & 8)) && (!rows64 || (mask & 16)) && (p.K != 3 || p.Cin % 16 == 0);
-    const bool w1 = p.K == 3 && p.dil == 1 && !rows64;
-    if (!w2 && !w1) return 0;
-    if ((p.dil != 1 && p.dil != 3 && p.dil != 5) || p.pad != p.dil * (p.K - 1) / 2 || p.n_phase != 1 || p.y_ts != 1) return 0;
-    if (p.CoutP % 64 != 0 || p.Cin % 8 != 0 || p.scale != nullptr || p.relu_out >= 2) return 0;
-    if (!(p.in_slope >= 0.f && p.in_slope <= 1.f)) return 0;         // conv_wino2.hip activates with max(x, slope x)
-    if (!rows_vec_ok(p)) return 0;
-    const int bo = wino2_block_outputs(p.CoutP, p.dil);
-    const int64_t blocks = (int64_t)((p.Nout + bo - 1) / bo) * (p.CoutP / (rows64 ? 64 : 128)) * p.batch;
-    // under ~3/4 of a block per CU the direct kernel's 64 x 64 tiles with split K fill the chip better (batch 1: 3.68 ms per step with
-    // the limit at 200, 3.74 at 100, 3.9-4.0 at 50 / 1 and with the Winograd kernels off; batch 4: 10.0 vs 10.5-11.0: tools/ab_small.sh);
-    // short sequences (FastPitch's 64-token encoder) would leave half of a 128-output tile empty
-    if (blocks < 192 || p.Nout < 256) return 0;
-    return w2 ? 2 : 1;
-}
-
-template <int MT, int WM, int WN>
-static int32_t launch_wino_cfg(const ConvParams& p, hipStream_t stream) {
-    using G = WinoGeo<MT, WM, WN>;
-    dim3 grid((p.Nout + G::NT_BLK - 1) / G::NT_BLK, p.CoutP / G::CO_BLK, p.batch);
-    ConvParams q = p;
-    q.ksplit = 1;
-    note_conv_launch(1, 1);
-    q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
-    if (p.res != nullptr) return launch_wino_epi<MT, WM, WN, 3>(q, grid, stream);
-    return launch_wino_epi<MT, WM, WN, 0>(q, grid, stream);
-}
-
 int32_t launch_wino(const ConvParams& p, hipStream_t stream) {
     // 128 co x 128 outputs (64 pairs).  (A 128 co x 64 outputs tile for launches under two blocks per CU -- FastPitch's 1536 -> 384 conv
     // at batch 32 is 384 blocks -- measured slower: 75.04 vs 74.45 ms per step; everything on it: 76.67.  A 64 co x 128 outputs tile,
     // three blocks per CU: 74.61 vs 74.22-74.35; everything on it: 75.44.)
-    return launch_wino_cfg<2, 2, 2>(p, stream);
+    using G = WinoGeo<2, 2, 2>;
+    dim3 grid((p.Nout + G::NT_BLK - 1) / G::NT_BLK, p.CoutP / G::CO_BLK, p.batch);
+    ConvParams q = p;
+    q.ksplit = 1;
+    q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
+    if (p.res != nullptr) return launch_wino_epi<2, 2, 2, 3>(q, grid, stream);
+    return launch_wino_epi<2, 2, 2, 0>(q, grid, stream);
 }
 
 // host: torch Conv1d weight [Cout][Cin][3] -> the four transformed filters as a 4-tap conv in the engine's packed layout

@@ -6,7 +6,7 @@
 //     P_i += U_{s,i} V_{s,i}   (sub-filter s, i = 0..3),      P_0 += g_t x[q + (t - pad) d],  P_3 += (-g_t) x[q + d + (t - pad) d]   (single tap t)
 //     y[q] = P_0 + P_1 + P_2,   y[q + d] = P_1 - P_2 - P_3          (dilation d: the output pair is (q, q + d))
 // Serves every ResBlock conv of HiFi-GAN's stages with 128 / 256 channels and the un-fused ones with 64 (vocoder/hifigan/models.py:
-// 30-53) and FastPitch's conv-FF convs (transformer.py:59-65); routing: wino_route (conv_wino.hip).  tests/test_wino_decomposition_cpu.py
+// 30-53) and FastPitch's conv-FF convs (transformer.py:59-65); routing: conv_route (conv_route.hip).  tests/test_wino_decomposition_cpu.py
 // states the arithmetic in numpy, tests/test_gpu_wino.py checks the kernel against float64.
 //
 // Anatomy (what differs from the round's first Winograd kernel, conv_wino.hip):
@@ -76,9 +76,6 @@ template <int K>
 __device__ __host__ constexpr int wino2_plane(int g) {
     return g < 4 * (K / 3) ? (g & 3) : (((g - 4 * (K / 3)) & 1) ? 3 : 0);
 }
-
-// outputs per tile at dilation d (see the kernel): the largest multiple of 2 d and of 4 in 2 * npair
-__device__ __host__ constexpr int wino2_tile(int d, int npair) { return (2 * npair / ((d & 1) ? 4 * d : 2 * d)) * ((d & 1) ? 4 * d : 2 * d); }
 
 template <int K, int NOCT_, int NSTAGE_, int WM_, int NPH_, int EPI>
 __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino2_f32(const ConvParams p) {
@@ -369,7 +366,6 @@ static int32_t launch_wino2_cfg(const ConvParams& p, hipStream_t stream) {
     dim3 grid((p.Nout + nt - 1) / nt, p.CoutP / G::CO_BLK, p.batch);
     ConvParams q = p;
     q.ksplit = 1;
-    note_conv_launch(2, 1);
     q.compact = compact_order(p.lens_out, p.batch) ? 1 : 0;
     if (p.res != nullptr) return launch_wino2_epi<K, NOCT, NSTAGE, WM, NPH, 3>(q, grid, stream);
     return launch_wino2_epi<K, NOCT, NSTAGE, WM, NPH, 0>(q, grid, stream);
@@ -389,9 +385,6 @@ int32_t launch_wino2(const ConvParams& p, hipStream_t stream) {
     set_error("wino2: kernel size %d not built (3, 7, 11)", p.K);
     return TTSAMD_EINVAL;
 }
-
-// outputs per block of the kernel launch_wino2 picks (the routing's block count)
-int wino2_block_outputs(int coutp, int dil) { return wino2_tile(dil, coutp % 128 == 0 ? 64 : 128); }
 
 int wino2_groups(int k) { return 4 * (k / 3) + 2 * (k - 3 * (k / 3)); }
 

@@ -239,9 +239,6 @@ struct Wino4Geo {
     static_assert(NPH == 1 || NOCT == 1, "phases split an octet's groups");
 };
 
-// outputs per tile at dilation d: the largest multiple of 4 d in 4 * ntup
-__device__ __host__ constexpr int wino4_tile(int d, int ntup) { return (4 * ntup / (4 * d)) * (4 * d); }
-
 // strip lengths of the packed form (tests/test_wino4_tiles_cpu.py restates the map against the same numbers)
 static_assert(Wino4Geo<3, 2, 2, 6, 2, 0, 1>::RAWW == 320 && Wino4Geo<7, 1, 2, 7, 2, 0, 1>::RAWW == 320 && Wino4Geo<7, 1, 2, 6, 2, 0, 1>::RAWW == 320 &&
               Wino4Geo<11, 1, 2, 7, 2, 0, 1>::RAWW == 332 && Wino4Geo<11, 1, 2, 6, 2, 0, 1>::RAWW == 332, "strip lengths of the packed form");
@@ -898,7 +895,7 @@ __global__ __launch_bounds__(256, kConvMinWaves) void conv1d_wino4_f32(const Con
 }
 
 template <int K, int NOCT, int NSTAGE, int EPI, int LP, int PT = 6>
-static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
+static int32_t launch_wino4_epi(const ConvParams& p, int ksplit, hipStream_t stream) {
     constexpr bool PK = EPI == 7;                            // packed strip form: packed tiles, ring + strip only
     using G = Wino4Geo<K, NOCT, NSTAGE, PT, LP, 0, PK ? 1 : 0>;
     constexpr size_t ring = (size_t)G::NSTAGE * G::BUF4 * sizeof(float4);
@@ -913,8 +910,7 @@ static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
     TTS_CHECK_HIP(lds_opt_in((const void*)kern, (int)lds, lds_done));
     const int nt = wino4_tile(p.dil, G::NTUP);
     ConvParams q = p;
-    q.ksplit = EPI == 0 ? wino4_ksplit(p) : 1;
-    note_conv_launch(PK ? (PT == 7 ? 8 : 7) : (PT == 7 ? 4 : 3), q.ksplit);
+    q.ksplit = ksplit;                                       // (> 1 with the row epilogue, EPI 0, only: conv_route.hip)
     // 1-D grid: (time tiles of the whole batch, rounded up to groups of 8) x row blocks x C-in slices; the kernel maps it XCD-aware
     const int64_t n_tiles = (int64_t)(PK ? wino4_pk_tiles(p.Nout, p.dil) : (p.Nout + nt - 1) / nt) * p.batch;
     const int64_t n_blocks = ((n_tiles + 7) / 8) * 8 * (p.CoutP / G::CO_BLK) * q.ksplit;
@@ -927,57 +923,30 @@ static int32_t launch_wino4_epi(const ConvParams& p, hipStream_t stream) {
     return 0;
 }
 
-// TTSAMD_WINO4 bit 7: a dilated launch with one C-in slice, no residual and mode 0 (HiFi-GAN's c1 convs: bias and ReLU only) runs in the
-// packed strip form (EPI 7); C-in slices, a residual and the accumulate modes keep the row epilogue (EPI 0)
-static bool wino4_packed_wanted(const ConvParams& p) {
-    return ((int)opt_int(OPT_WINO4, kWino4Default) & 128) != 0 && p.dil != 1 && p.res == nullptr && p.mode == 0 && wino4_ksplit(p) == 1;
-}
-
-template <int K, int NOCT, int NSTAGE>
-static int32_t launch_wino4_cfg(const ConvParams& p, hipStream_t stream) {
-    // dilation 1: the window as aligned 16-byte vectors (D1).  One C-in slice: the register epilogue, with the residual's quads fetched
-    // under the last step (EPI 3: every c2 conv of a ResBlock, the second conv-FF conv) or without a residual (EPI 4: conv_pre, c1 at
-    // d = 1, the first conv-FF conv).  C-in slices write raw partial sums through the row epilogue (EPI 0)
+// The form conv_route chose (conv_route.hip: r.epi).  Dilation 1 takes the window as aligned 16-byte vectors, dilation 3 / 5 through the
+// per-wave LDS strip (two stages: the strip takes 10 / 20 KB).  Seven-point groups (PT = 7, Wino4Geo PT_): k = 7 in one phase of 13 groups,
+// two stages (52 KB ring); k = 11 at dilation 1 in one phase of 20 groups, two stages (80 KB ring), with the strip in two phases of
+// 8 + 12 groups (48 KB ring + the strip)
+template <int K, int NOCT, int NSTAGE, int PT = 6>
+static int32_t launch_wino4_cfg(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
     if (p.dil == 1) {
-        if (wino4_ksplit(p) != 1) return launch_wino4_epi<K, NOCT, NSTAGE, 0, 1>(p, stream);
-        if (p.res != nullptr) return launch_wino4_epi<K, NOCT, NSTAGE, 3, 1>(p, stream);
-        return launch_wino4_epi<K, NOCT, NSTAGE, 4, 1>(p, stream);
+        if (r.epi == 0) return launch_wino4_epi<K, NOCT, NSTAGE, 0, 1, PT>(p, r.ksplit, stream);
+        if (r.epi == 3) return launch_wino4_epi<K, NOCT, NSTAGE, 3, 1, PT>(p, r.ksplit, stream);
+        return launch_wino4_epi<K, NOCT, NSTAGE, 4, 1, PT>(p, r.ksplit, stream);
     }
-    // dilation 3 / 5: the window through the per-wave LDS strip (two stages: the strip takes 10 / 20 KB); the packed form where it applies
-    if (wino4_packed_wanted(p)) return launch_wino4_epi<K, NOCT, 2, 7, 2>(p, stream);
-    return launch_wino4_epi<K, NOCT, 2, 0, 2>(p, stream);
+    if (r.epi == 7) return launch_wino4_epi<K, NOCT, 2, 7, 2, PT>(p, r.ksplit, stream);
+    return launch_wino4_epi<K, NOCT, 2, 0, 2, PT>(p, r.ksplit, stream);
 }
 
-// seven-point groups (Wino4Geo PT_ = 7): k = 7 in one phase of 13 groups, two stages (52 KB ring); k = 11 at dilation 1 in one phase of
-// 20 groups, two stages (80 KB ring), with the strip in two phases of 8 + 12 groups (48 KB ring + the strip)
-template <int K>
-static int32_t launch_wino44_cfg(const ConvParams& p, hipStream_t stream) {
-    if (p.dil == 1) {
-        if (wino4_ksplit(p) != 1) return launch_wino4_epi<K, 1, 2, 0, 1, 7>(p, stream);
-        if (p.res != nullptr) return launch_wino4_epi<K, 1, 2, 3, 1, 7>(p, stream);
-        return launch_wino4_epi<K, 1, 2, 4, 1, 7>(p, stream);
-    }
-    if (wino4_packed_wanted(p)) return launch_wino4_epi<K, 1, 2, 7, 2, 7>(p, stream);
-    return launch_wino4_epi<K, 1, 2, 0, 2, 7>(p, stream);
-}
-
-// TTSAMD_WINO4 bit 5 / 6: k = 7 / 11 on seven-point groups (when the launch carries them: ConvParams::w_wino44)
-bool wino44_wanted(const ConvParams& p) {
-    if (p.w_wino44 == nullptr || (p.K != 7 && p.K != 11)) return false;
-    return ((int)opt_int(OPT_WINO4, kWino4Default) & (p.K == 7 ? 32 : 64)) != 0;
-}
-
-int32_t launch_wino4(const ConvParams& p, hipStream_t stream) {
-    if (wino44_wanted(p)) return p.K == 7 ? launch_wino44_cfg<7>(p, stream) : launch_wino44_cfg<11>(p, stream);
-    if (p.K == 1) return launch_wino4_epi<1, 4, 2, 0, 1>(p, stream);   // 32-channel chunks: 64 MFMAs per wave between barriers, 64 KB ring
-    if (p.K == 3) return launch_wino4_cfg<3, 2, 3>(p, stream);       // 16-channel chunks: 48 MFMAs per wave between barriers, 72 KB ring
-    if (p.K == 7) return launch_wino4_cfg<7, 1, 2>(p, stream);       // 64 MFMAs, 64 KB ring
-    if (p.K == 11) return launch_wino4_cfg<11, 1, 3>(p, stream);     // two phases of 12 / 11 groups: 48 / 44 MFMAs, 72 KB ring
+int32_t launch_wino4(const ConvParams& p, const ConvRoute& r, hipStream_t stream) {
+    if (r.id == 4 || r.id == 8) return p.K == 7 ? launch_wino4_cfg<7, 1, 2, 7>(p, r, stream) : launch_wino4_cfg<11, 1, 2, 7>(p, r, stream);
+    if (p.K == 1) return launch_wino4_epi<1, 4, 2, 0, 1>(p, r.ksplit, stream);   // 32-channel chunks: 64 MFMAs per wave between barriers, 64 KB ring
+    if (p.K == 3) return launch_wino4_cfg<3, 2, 3>(p, r, stream);    // 16-channel chunks: 48 MFMAs per wave between barriers, 72 KB ring
+    if (p.K == 7) return launch_wino4_cfg<7, 1, 2>(p, r, stream);    // 64 MFMAs, 64 KB ring
+    if (p.K == 11) return launch_wino4_cfg<11, 1, 3>(p, r, stream);  // two phases of 12 / 11 groups: 48 / 44 MFMAs, 72 KB ring
     set_error("wino4: kernel size %d not built (1, 3, 7, 11)", p.K);
     return TTSAMD_EINVAL;
 }
-
-int wino4_block_outputs(int dil) { return wino4_tile(dil, 64); }
 
 // ---- ConvTranspose1d(stride u, kernel 2u, padding u/2) + leaky-relu on load (HiFi-GAN's upsamplers) on this kernel.  With the phase index
 // shifted by u/2 every phase takes the same two input positions,
@@ -1047,23 +1016,6 @@ void pack_convt_wino_weight(const float* w, const float* bias, int cin, int cout
             }
     pack_wino4_weight(t.data(), rows, cin, 3, out_w);        // U5 = g2 = 0: the zero group
     for (int r = 0; r < rows; ++r) out_bias[r] = bias ? bias[r / u] : 0.f;
-}
-
-// C-in slices of a launch that cannot fill the chip by its tiles alone (batch 1: HiFi-GAN's C = 256 stage is 56 blocks): enough for
-// ~224 blocks, at least eight chunks per slice, partial sums within the caller's split-K workspace.  1 = no split.
-int wino4_ksplit(const ConvParams& p) {
-    const int bo = wino4_block_outputs(p.dil);
-    const int64_t blocks = (int64_t)((p.Nout + bo - 1) / bo) * (p.CoutP / 64) * p.batch;
-    // (more slices / a higher block threshold were measured: no change at batch 1, 2.34-2.40 ms at every setting -- profiles/r6/NOTES.md)
-    constexpr int sk_blocks = 192, sk_target = 224;
-    if (blocks >= sk_blocks || p.splitk_ws == nullptr) return 1;
-    const int n_chunks = p.Cin / (p.K == 1 ? 32 : (p.K == 3 ? 16 : 8));
-    const int64_t per = (int64_t)p.batch * p.Cout * p.Nout;
-    // at least 8 chunks per slice: a block of 4-5 chunks is mostly prologue and output transform (FastPitch's conv-FF at batch 1 -- 48 / 12
-    // blocks x 24 / 96 chunks -- ran 30 % slower on 5 / 19 slices than on the direct kernel's split-K tiles)
-    int64_t ks = std::min<int64_t>((sk_target + blocks - 1) / blocks, n_chunks / 8);
-    ks = std::min<int64_t>(ks, p.splitk_floats / std::max<int64_t>(per, 1));
-    return ks >= 2 ? (int)ks : 1;
 }
 
 // groups per octet in the packed weights (k = 11: 23 multiplied + one zero group)

@@ -712,6 +712,15 @@ def last_conv_launch():
     return route.value, ksplit.value
 
 
+def conv_route(batch, cin, cout, k, lin, dilation=1, in_slope=1.0, relu_out=False, has_res=False, mode=0, splitk_floats=None):
+    """(route, ksplit) that last_conv_launch() would report after conv1d() with these shapes and arguments under the current options
+    (ttsamd_conv1d_route): asked on the host, nothing is launched and no GPU is needed."""
+    route, ksplit = C.c_int32(-1), C.c_int32(0)
+    L.check(L.load().ttsamd_conv1d_route(batch, cin, cout, k, dilation, lin, float(in_slope), int(relu_out), int(bool(has_res)), mode,
+                                         int(splitk_floats or 0), C.byref(route), C.byref(ksplit)), 'conv1d_route')
+    return route.value, ksplit.value
+
+
 def conv_transpose1d(x, w, bias=None, lens=None, in_slope=1.0, y=None):
     """Kernel-level entry (parity tests): one HiFi-GAN upsampler as the generator launches it (ttsamd_conv_transpose1d),
     y = conv_transpose1d(lrelu(x), w, stride=u, padding=u // 2) + b for w [Cin][Cout][2u] (torch layout); x [B][Cin][L] -> y [B][Cout][L * u];

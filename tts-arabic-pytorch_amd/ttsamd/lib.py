@@ -194,6 +194,7 @@ SYMBOLS = {
     'ttsamd_conv1d_ex': (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _I32, _F, _P, _P, _P]),
     'ttsamd_conv1d_splitk': (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
     'ttsamd_conv_last_launch': (_I32, [C.POINTER(_I32), C.POINTER(_I32)]),
+    'ttsamd_conv1d_route': (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _I32, _I32, _I64, C.POINTER(_I32), C.POINTER(_I32)]),
     'ttsamd_convt_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_conv_transpose1d': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P]),
     'ttsamd_convt_wino_packed_floats': (_I64, [_I32, _I32, _I32]),
