@@ -606,6 +606,47 @@ int32_t ttsamd_tacotron2_infer(void* handle, const int64_t* tokens, const int64_
                                float* mel_raw, int32_t* n_steps, void* workspace, int64_t workspace_bytes,
                                void* stream);
 
+/* ---- Tacotron2 as a stream: the same decode in advances of a few steps, so that audio can leave while the decoder is still running
+ *      (no reference counterpart; ttsamd/engine.py Tacotron2Engine.stream, models/tacotron2/networks.py Tacotron2Wave.tts_stream).
+ *      New entries at ABI revision 8; the handle is not changed by a session.  Device state lives in the caller's `workspace`
+ *      (ttsamd_tacotron2_stream_bytes: the exchange arena is sized by max_chunk_steps, not by max_step, and there are no postnet
+ *      buffers in it) and in the caller's output buffers, all of which must stay alive and untouched until ttsamd_tacotron2_stream_end;
+ *      the small host side (the decoder path, the step position, the captured step graph of the graph path) is *session. ----------- */
+int64_t ttsamd_tacotron2_stream_bytes(void* handle, int32_t batch, int32_t n_tokens, int32_t max_step, int32_t max_chunk_steps);
+/* The head of ttsamd_tacotron2_infer (encoder, speaker concat, processed memory, the zero decoder state) and the choice of the decoder
+ * path, made once by infer's own rule (persistent where it fits, TTSAMD_TACO_PERSISTENT as there).  tokens / lengths / speaker_ids /
+ * mel_raw / mel_lens / alignments: as ttsamd_tacotron2_infer (device; row strides max_step).  max_chunk_steps: the longest advance, a
+ * positive multiple of 8.  cut_columns int32 [B] (device, copied; may be NULL = no row has one): per row the token column whose
+ * attention weights define the wrapper's end-of-utterance cut (truncate_mel), < 0 = none.  rows_to_batch_end != 0: a row ends with the
+ * batch and is as long as the batch (Tacotron2.ttmel_single's rule); 0: a row ends at its own mel_lens (ttmel_batch's). */
+int32_t ttsamd_tacotron2_stream_begin(void* handle, const int64_t* tokens, const int64_t* lengths, const int64_t* speaker_ids, int32_t batch,
+                                      int32_t n_tokens, int32_t max_step, int32_t max_chunk_steps, int64_t dropout_seed,
+                                      const int32_t* cut_columns, int32_t rows_to_batch_end, float* mel_raw, int32_t* mel_lens,
+                                      float* alignments, void* workspace, int64_t workspace_bytes, void** session, void* stream);
+/* Steps [s, s + n_steps) of the same loop, clipped to max_step: one cooperative launch on the persistent path, n_steps / 8 replays of a
+ * graph captured once per session on the graph path; the frames and alignments written are ttsamd_tacotron2_infer's bit for bit.
+ * n_steps: a positive multiple of 8, at most max_chunk_steps.  HOST outputs (the call waits for the steps): *ended = every row's gate has
+ * fired (with decoder_early_stopping) or max_step is reached; *steps_done = the steps ttsamd_tacotron2_infer would report so far;
+ * rows int32 [B][4] (may be NULL) = per row { final_frames, row_ended, n_end, row_length }:
+ *   n_end        the cut bound c_s = the first t < s with ps[t] >= 0.8f * max(ps[:s]) over the row's cut column (never decreases, never
+ *                exceeds truncate_mel's cut, and is that cut once row_ended); the row length for a row without a column
+ *   final_frames min(n_end, frames whose postnet output is settled: t + halo < steps computed, or all of them once ended)
+ *   row_ended    the row's length is known (a gate that fires on the very last step of an advance shows one advance later, or with *ended)
+ * A hand-off time-out of a persistent segment (as in ttsamd_tacotron2_infer) replays steps [0, s + n_steps) on the graph path and the
+ * session stays there; under an explicit TTSAMD_TACO_PERSISTENT=1 / 2 it is an error.  After *ended a further call is TTSAMD_EINVAL. */
+int32_t ttsamd_tacotron2_stream_advance(void* session, int32_t n_steps, int32_t* steps_done, int32_t* ended, int32_t* rows, void* stream);
+int32_t ttsamd_tacotron2_stream_end(void* session);
+/* The postnet over windows.  *halo = postnet_n_convolution * (postnet_kernel_size - 1) / 2 frames (10): what an output frame reads on
+ * each side.  ttsamd_tacotron2_postnet_window writes mel_post[:, :, t0:t1) from the raw frames [t0 - halo, t1 + halo) clipped to
+ * [0, t_known): zero padding falls where the one-shot postnet has it -- at frame 0, and at t_known when `ended` is set (t_known is then the
+ * step count of the decode) -- and nowhere else: t1 + halo > t_known with ended == 0 is TTSAMD_EINVAL.  A row that finished early reads
+ * the frames decoded after its gate fired, as the one-shot postnet on the padded batch does.  mel_raw / mel_post [B][n_mels][t_cap];
+ * workspace: ttsamd_tacotron2_postnet_window_bytes(handle, batch, t1 - t0). */
+int32_t ttsamd_tacotron2_postnet_halo_frames(void* handle, int32_t* halo);
+int64_t ttsamd_tacotron2_postnet_window_bytes(void* handle, int32_t batch, int32_t n_frames);
+int32_t ttsamd_tacotron2_postnet_window(void* handle, const float* mel_raw, float* mel_post, int32_t batch, int32_t t_cap, int32_t t_known,
+                                        int32_t t0, int32_t t1, int32_t ended, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- diacritizer taggers: replaces Shakkelha.forward / Shakkala.forward
  *      (models/diacritizers/shakkelha/network.py:29-42, shakkala/network.py:31-43).  Weight names are
  *      canonical: emb.weight, lstm<i>.{weight,bias}_{ih,hh}_l0[_reverse], bn0.{weight,bias,running_mean,

@@ -136,6 +136,16 @@ void tacotron2_destroy(Taco2*);
 int64_t tacotron2_workspace_bytes(const Taco2*, int32_t, int32_t, int32_t);
 int32_t tacotron2_infer(const Taco2*, const int64_t*, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, int64_t,
                         float*, int32_t*, float*, float*, int32_t*, void*, int64_t, hipStream_t);
+struct TacoStream;
+int64_t tacotron2_stream_bytes(const Taco2*, int32_t, int32_t, int32_t, int32_t);
+int32_t tacotron2_stream_begin(const Taco2*, const int64_t*, const int64_t*, const int64_t*, int32_t, int32_t, int32_t, int32_t, int64_t,
+                               const int32_t*, int32_t, float*, int32_t*, float*, void*, int64_t, TacoStream**, hipStream_t);
+int32_t tacotron2_stream_advance(TacoStream*, int32_t, int32_t*, int32_t*, int32_t*, hipStream_t);
+void tacotron2_stream_end(TacoStream*);
+int32_t tacotron2_postnet_halo(const Taco2*);
+int64_t tacotron2_postnet_window_bytes(const Taco2*, int32_t, int32_t);
+int32_t tacotron2_postnet_window(const Taco2*, const float*, float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, void*, int64_t,
+                                 hipStream_t);
 struct Tagger;
 int32_t tagger_create(const ttsamd_tensor*, int32_t, const ttsamd_tagger_cfg*, Tagger**);
 void tagger_destroy(Tagger*);
@@ -728,6 +738,43 @@ int32_t ttsamd_tacotron2_infer(void* handle, const int64_t* tokens, const int64_
                                int64_t workspace_bytes, void* stream) {
     return tacotron2_infer((Taco2*)handle, tokens, lengths, speaker_ids, batch, n_tokens, max_step, dropout_seed, mel_post,
                            mel_lens, alignments, mel_raw, n_steps, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int64_t ttsamd_tacotron2_stream_bytes(void* handle, int32_t batch, int32_t n_tokens, int32_t max_step, int32_t max_chunk_steps) {
+    if (!handle || batch < 1 || n_tokens < 1 || max_step < 1 || max_chunk_steps < 8 || max_chunk_steps % 8 != 0) return 0;
+    return tacotron2_stream_bytes((Taco2*)handle, batch, n_tokens, max_step, max_chunk_steps);
+}
+int32_t ttsamd_tacotron2_stream_begin(void* handle, const int64_t* tokens, const int64_t* lengths, const int64_t* speaker_ids, int32_t batch,
+                                      int32_t n_tokens, int32_t max_step, int32_t max_chunk_steps, int64_t dropout_seed,
+                                      const int32_t* cut_columns, int32_t rows_to_batch_end, float* mel_raw, int32_t* mel_lens,
+                                      float* alignments, void* workspace, int64_t workspace_bytes, void** session, void* stream) {
+    TTS_REQUIRE(session, "tacotron2_stream_begin: null session");
+    TacoStream* st = nullptr;
+    const int32_t rc = tacotron2_stream_begin((Taco2*)handle, tokens, lengths, speaker_ids, batch, n_tokens, max_step, max_chunk_steps,
+                                              dropout_seed, cut_columns, rows_to_batch_end, mel_raw, mel_lens, alignments, workspace,
+                                              workspace_bytes, &st, (hipStream_t)stream);
+    if (rc == 0) *session = st;
+    return rc;
+}
+int32_t ttsamd_tacotron2_stream_advance(void* session, int32_t n_steps, int32_t* steps_done, int32_t* ended, int32_t* rows, void* stream) {
+    return tacotron2_stream_advance((TacoStream*)session, n_steps, steps_done, ended, rows, (hipStream_t)stream);
+}
+int32_t ttsamd_tacotron2_stream_end(void* session) {
+    tacotron2_stream_end((TacoStream*)session);
+    return 0;
+}
+int32_t ttsamd_tacotron2_postnet_halo_frames(void* handle, int32_t* halo) {
+    TTS_REQUIRE(handle && halo, "tacotron2_postnet_halo_frames: null argument");
+    *halo = tacotron2_postnet_halo((Taco2*)handle);
+    return 0;
+}
+int64_t ttsamd_tacotron2_postnet_window_bytes(void* handle, int32_t batch, int32_t n_frames) {
+    if (!handle || batch < 1 || n_frames < 1) return 0;
+    return tacotron2_postnet_window_bytes((Taco2*)handle, batch, n_frames);
+}
+int32_t ttsamd_tacotron2_postnet_window(void* handle, const float* mel_raw, float* mel_post, int32_t batch, int32_t t_cap, int32_t t_known,
+                                        int32_t t0, int32_t t1, int32_t ended, void* workspace, int64_t workspace_bytes, void* stream) {
+    return tacotron2_postnet_window((Taco2*)handle, mel_raw, mel_post, batch, t_cap, t_known, t0, t1, ended, workspace, workspace_bytes,
+                                    (hipStream_t)stream);
 }
 
 int32_t ttsamd_tagger_create(const ttsamd_tensor* weights, int32_t n, const ttsamd_tagger_cfg* cfg, void** handle) {

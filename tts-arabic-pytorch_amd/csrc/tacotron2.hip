@@ -1787,7 +1787,9 @@ struct TWs {
 // given ("workspace of N bytes needed"), never written past.
 static int taco_segment_steps() { return (int)std::max<int64_t>(8, opt_int(OPT_TACO_SEG, 512)); }
 
-static void tcarve(const Taco2* h, Arena& a, int B, int L, int Tcap, TWs& w) {
+// `seg_cap`: the steps of the longest persistent launch (regions of the exchange arena - 1); `post_T`: the frames the two postnet buffers
+// hold (0: none, a streaming session runs its postnet over windows with buffers of their own)
+static void tcarve(const Taco2* h, Arena& a, int B, int L, int seg_cap, int post_T, TWs& w) {
     const ttsamd_tacotron2_cfg& c = h->cfg;
     const int E = c.encoder_embedding_dim, M = h->mem_dim;
     w.x0 = a.take<float>((int64_t)B * E * L);
@@ -1811,20 +1813,20 @@ static void tcarve(const Taco2* h, Arena& a, int B, int L, int Tcap, TWs& w) {
     w.PTp = (int)align_up(((int64_t)std::min(B, 8) * L + 15) / 16, 32);
     w.step_floats = taco_region_floats(w.Lp, w.PTp);
     const bool persist_geo = taco_persistent_wanted() && B <= 8 && L <= 256;   // (taco_decoder_persistent's residency plan; else no arena)
-    w.seg = std::min(Tcap, taco_segment_steps());
+    w.seg = seg_cap;
     w.tail_o = persist_geo ? (int64_t)(w.seg + 1) * w.step_floats : 0;
     w.xch_floats = w.tail_o + 384;
     w.xch = a.take<float>(w.xch_floats);
     w.pstate = a.take<float>(persist_geo ? (int64_t)256 * 256 * 8 : 0);
-    w.post0 = a.take<float>((int64_t)B * c.postnet_embedding_dim * Tcap);
-    w.post1 = a.take<float>((int64_t)B * c.postnet_embedding_dim * Tcap);
+    w.post0 = a.take<float>((int64_t)B * c.postnet_embedding_dim * post_T);
+    w.post1 = a.take<float>((int64_t)B * c.postnet_embedding_dim * post_T);
     w.step = a.take<int32_t>(1);
 }
 
 int64_t tacotron2_workspace_bytes(const Taco2* h, int32_t B, int32_t L, int32_t Tcap) {
     Arena a(nullptr, 0);
     TWs w;
-    tcarve(h, a, B, L, Tcap, w);
+    tcarve(h, a, B, L, std::min(Tcap, taco_segment_steps()), Tcap, w);
     return a.off;
 }
 
@@ -1835,14 +1837,15 @@ int64_t tacotron2_workspace_bytes(const Taco2* h, int32_t B, int32_t L, int32_t 
 // amplifies its error step by step (profiles/r32/NOTES.md: 14 times the float32 reference's own error after 20 steps, 4 to 5 with slices).
 // A sliced conv cannot apply an activation: its consumer does, on load (in_slope 0 = ReLU).
 static int32_t tconv(const Taco2* h, const TConv& c, const float* x, int64_t x_bs, int x_cs, float* y, int64_t y_bs,
-                     int y_cs, const float* res, int B, int T, int act, hipStream_t s, float in_slope = 1.f, int slices = 1) {
+                     int y_cs, const float* res, int B, int T, int act, hipStream_t s, float in_slope = 1.f, int slices = 1,
+                     int64_t r_bs = -1, int r_cs = -1) {           // the residual's strides where they are not the output's
     ConvParams p;
     std::memset(&p, 0, sizeof(p));
     p.x = x; p.x_bs = x_bs; p.x_cs = x_cs;
     p.w = h->dev + c.w_off; p.bias = h->dev + c.b_off;
     p.w_bf16 = h->dev16 + c.w16_off; p.precision = default_precision();
     p.y = y; p.y_bs = y_bs; p.y_cs = y_cs; p.y_ts = 1;
-    p.res = res; p.r_bs = y_bs; p.r_cs = y_cs;
+    p.res = res; p.r_bs = r_bs < 0 ? y_bs : r_bs; p.r_cs = r_cs < 0 ? y_cs : r_cs;
     p.res_late = 1;                                             // postnet: mel + a small correction (ConvParams::res_late)
     p.len_in_mul = 1; p.len_out_mul = 1; p.Lin = T; p.Nout = T;
     p.Cin = c.cin; p.Cout = c.cout; p.CoutP = cout_padded(c.cout); p.K = c.k;
@@ -1884,24 +1887,12 @@ static int32_t launch_lstm(const float* x1, int n1, const float* x2, int n2, con
     return 0;
 }
 
-int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* lengths, const int64_t* speaker_ids,
-                        int32_t B, int32_t L, int32_t max_step, int64_t dropout_seed, float* mel_post,
-                        int32_t* mel_lens, float* alignments, float* mel_raw, int32_t* n_steps_out, void* ws,
-                        int64_t ws_bytes, hipStream_t s) {
-    TTS_REQUIRE(h && tokens && lengths && mel_post && mel_lens && alignments && mel_raw && n_steps_out,
-                "tacotron2_infer: null argument");
-    TTS_REQUIRE(B >= 1 && L >= 1 && L <= TACO_LMAX && max_step >= 1, "tacotron2_infer: bad batch/length/max_step");
+// The head of a decode, shared by tacotron2_infer and a streaming session's begin: encoder, speaker concat, processed memory, and the
+// zero decoder state of both decoder paths (the persistent one zeroes region 0 of its arena itself, at its first segment).
+static int32_t taco_head(const Taco2* h, const int64_t* tokens, const int64_t* lengths, const int64_t* speaker_ids, int B, int L,
+                         const TWs& w, int32_t* mel_lens, hipStream_t s) {
     const ttsamd_tacotron2_cfg& c = h->cfg;
-    TTS_REQUIRE(c.num_speakers <= 1 || speaker_ids, "tacotron2_infer: speaker_ids is null");
-    Arena a(ws, ws_bytes);
-    TWs w;
-    const int Tcap = max_step;
-    tcarve(h, a, B, L, Tcap, w);
-    if (!ws || !a.ok) {
-        set_error("tacotron2_infer: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
-        return TTSAMD_ENOMEM;
-    }
-    const int E = c.encoder_embedding_dim, M = h->mem_dim, A = c.attention_rnn_dim, D = c.decoder_rnn_dim, P = c.prenet_dim;
+    const int E = c.encoder_embedding_dim, M = h->mem_dim, A = c.attention_rnn_dim, D = c.decoder_rnn_dim;
     const float* W = h->dev;
     // ---- encoder
     hipLaunchKernelGGL(taco_embed_kernel, dim3((L + 63) / 64, B), dim3(256), 0, s, tokens, W + h->emb, h->cfg.n_symbol, E, L, w.x0);
@@ -1935,144 +1926,150 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
     TTS_CHECK_HIP(hipMemsetAsync(w.dec_in, 0, (size_t)B * c.n_mels * sizeof(float), s));
     TTS_CHECK_HIP(hipMemsetAsync(mel_lens, 0, (size_t)B * sizeof(int32_t), s));
     TTS_CHECK_HIP(hipMemsetAsync(w.step, 0, sizeof(int32_t), s));
-    int steps = 0;
-    bool done = false;
-    // ---- the persistent decoder (one cooperative launch for the whole loop) when the geometry fits its residency plan
-    {
-        const bool want = taco_persistent_wanted();
-        const int KS = c.attention_location_kernel_size, half = (KS - 1) / 2, PT = (B * L + 15) / 16;
-        const int MC = M / 32, NS = MC ? 256 / MC : 0, K4A = (P + M + A) / 4;
-        const size_t lds = (size_t)16 * K4A * 16 +
-                           sizeof(float) * ((size_t)L * MC + (size_t)PT * 8 + 16 * KS + 2 * (PT + 2 * half) + 256 + 128 + 64 + 256 + NS * MC + 16 + 1024);
-        int dev_id = 0, n_cu = 0, coop = 0, lds_max = 0;
-        (void)hipGetDevice(&dev_id);
-        (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id);
-        (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev_id);
-        (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id);
-        const int req = (int)opt_int(OPT_TACO_PERSISTENT, 0);
-        const bool explicit_req = req != 0;                                     // an explicit request must run the persistent kernel or fail
-        bool fits = want && B <= 8 && L <= 256 && (M == 512 || M == 640) && A == 1024 && D == 1024 && P == 256 && KS % 2 == 1 &&
-                    (B * L + 15) / 16 + KS - 1 <= 256 &&      /* the alignment window of an energy tile: one word per thread */
-                    lds <= (size_t)std::max(lds_max, 64 * 1024) && n_cu >= 256 && coop && w.tail_o > 0;
-        if (explicit_req && !fits) {
-            set_error("tacotron2_infer: TTSAMD_TACO_PERSISTENT=%d but the persistent decoder does not fit (B=%d <= 8, L=%d <= 256, memory dim %d in "
-                      "{512, 640}, %zu B of LDS <= %d, %d CUs >= 256, cooperative launch %d)", req, B, L, M, lds, lds_max, n_cu, coop);
-            return TTSAMD_EINVAL;
-        }
-        if (fits && !explicit_req) {
-            std::lock_guard<std::mutex> lock(h->mu);
-            if (h->persist_skip > 0) { --h->persist_skip; fits = false; }        // a recent time-out: do not pay the spin again
-        }
-        if (fits) {
-            TacoPersist q;
-            q.pre1 = W + h->pre1;
-            q.att_wih = W + h->att_wih; q.att_whh = W + h->att_whh; q.att_b = W + h->att_b;
-            q.dec_wih = W + h->dec_wih; q.dec_whh = W + h->dec_whh; q.dec_b = W + h->dec_b;
-            q.wq = W + h->wq; q.loc_fold = W + h->loc_fold; q.v = W + h->v;
-            q.pm = w.pm; q.memory = w.memory;
-            q.projx_w = W + h->projx_w; q.projx_b = W + h->projx_b;
-            q.lens = lengths;
-            q.xch = w.xch; q.tail_o = w.tail_o; q.step_floats = w.step_floats; q.Lp = w.Lp; q.PTp = w.PTp;
-            q.mel_out = mel_raw; q.align_out = alignments; q.mel_lens = mel_lens;
-            q.B = B; q.L = L; q.KS = KS; q.Tcap = Tcap; q.max_step = max_step; q.n_mels = c.n_mels;
-            q.thr = c.gate_threshold; q.seed = (long long)dropout_seed; q.early_stop = c.decoder_early_stopping != 0;
-            const bool flow = taco_persistent_mode() == 2;
-            const void* fn = flow ? (M == 512 ? (const void*)taco_decoder_persistent<512, true> : (const void*)taco_decoder_persistent<640, true>)
-                                  : (M == 512 ? (const void*)taco_decoder_persistent<512, false> : (const void*)taco_decoder_persistent<640, false>);
-            std::lock_guard<std::mutex> lock(h->mu);
-            q.state = w.pstate;
-            void* args[] = {&q};
-            int32_t tail[2] = {0, 0};                                   // err_o and steps_o are 64 floats apart: two copies
-            // one cooperative launch per segment of at most w.seg steps (TacoPersist: why); a whole bench-size decode (448 steps) is one
-            for (int s0 = 0; s0 < max_step; s0 += w.seg) {
-                q.s0 = s0;
-                q.s1 = std::min(max_step, s0 + w.seg);
-                if (s0 > 0)    // region 0 of this segment = what the last step of the previous one produced
-                    TTS_CHECK_HIP(hipMemcpyAsync(w.xch, w.xch + (int64_t)w.seg * w.step_floats, (size_t)w.step_floats * sizeof(float),
-                                                 hipMemcpyDeviceToDevice, s));
-                if (flow)    // every word a consumer may poll starts as the sentinel 0xFFFFFFFF (regions 1 ... of this segment)
-                    TTS_CHECK_HIP(hipMemsetAsync(w.xch + w.step_floats, 0xFF, (size_t)(w.tail_o - w.step_floats) * sizeof(float), s));
-                if (s0 == 0) TTS_CHECK_HIP(hipMemsetAsync(w.xch, 0, (size_t)w.step_floats * sizeof(float), s));    // region 0: the zero initial state
-                TTS_CHECK_HIP(hipMemsetAsync(w.xch + w.tail_o, 0, 384 * sizeof(float), s));                        // barrier slots, error flag, step count
-                // LDS opt-in or cooperative launch rejected (another partitioning / device, hipErrorCooperativeLaunchTooLarge): the
-                // graph path below still works, so only an explicit request turns this into an error
-                hipError_t le = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (le == hipSuccess) le = hipLaunchCooperativeKernel(fn, dim3(256), dim3(256), args, (unsigned)lds, s);
-                if (le != hipSuccess) {
-                    (void)hipGetLastError();
-                    if (explicit_req) {
-                        set_error("tacotron2_infer: launching the persistent decoder failed: %s", hipGetErrorString(le));
-                        return TTSAMD_EHIP;
-                    }
-                    // hipErrorCooperativeLaunchTooLarge can be transient (another stream held CUs at that moment): same bounded back-off
-                    // as a hand-off time-out; anything else (LDS opt-in rejected, no cooperative launch on this partitioning) is permanent
-                    if (le == hipErrorCooperativeLaunchTooLarge) {
-                        h->persist_backoff = std::min(256, std::max(8, 2 * h->persist_backoff));
-                        h->persist_skip = h->persist_backoff;
-                    } else {
-                        h->persist_skip = 1 << 30;
-                    }
-                    ++h->persist_launch_failures;
-                    fprintf(stderr, "ttsamd: tacotron2 persistent decoder could not be launched (%s), using the graph path%s\n", hipGetErrorString(le),
-                            le == hipErrorCooperativeLaunchTooLarge ? " (retrying after a back-off)" : " for the life of this handle");
-                    tail[0] = -1;
-                    break;
-                }
-                TTS_CHECK_HIP(hipMemcpyAsync(&tail[0], w.xch + w.tail_o + 256, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                TTS_CHECK_HIP(hipMemcpyAsync(&tail[1], w.xch + w.tail_o + 320, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                TTS_CHECK_HIP(hipStreamSynchronize(s));
-                // a time-out, or every utterance's gate fired inside this segment -- also on its LAST step (the kernel then reports exactly s1;
-                // an unfinished segment reports max_step): no extra segment (a region copy, an 82 MB memset and a cooperative launch for nothing)
-                if (tail[0] != 0 || (int64_t)tail[1] <= (int64_t)q.s1) break;
-            }
-            if (tail[0] != 0) {
-                // a block waited > 80 ms for another one: the 256 blocks were not all resident (CUs held by other streams).  The
-                // graph path below recomputes the whole loop from the same state; only an explicit request is an error.
-                if (explicit_req) {
-                    set_error("tacotron2_infer: the persistent decoder timed out waiting for another block (are 256 CUs free for it?)");
-                    return TTSAMD_EHIP;
-                }
-                if (tail[0] > 0) {
-                    h->persist_backoff = std::min(256, std::max(8, 2 * h->persist_backoff));
-                    h->persist_skip = h->persist_backoff;
-                    fprintf(stderr, "ttsamd: tacotron2 persistent decoder timed out, using the graph path (and for the next %d calls)\n",
-                            h->persist_skip);
-                }
-                TTS_CHECK_HIP(hipMemsetAsync(mel_lens, 0, (size_t)B * sizeof(int32_t), s));     // (the kernel had started counting)
-            } else {
-                steps = tail[1];
-                done = true;
-                h->persist_backoff = 0;
-            }
-        }
+    return 0;
+}
+
+// Whether the persistent decoder takes a decode: its residency plan, decided once per decode (tacotron2_infer) or per session (begin).
+struct TacoPlan {
+    bool fits = false;
+    bool explicit_req = false;  // TTSAMD_TACO_PERSISTENT=1 / 2: the persistent kernel must run, or the call fails
+    size_t lds = 0;
+};
+static int32_t taco_persist_plan(const Taco2* h, int B, int L, const TWs& w, const char* who, TacoPlan& pl) {
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    const int M = h->mem_dim, A = c.attention_rnn_dim, D = c.decoder_rnn_dim, P = c.prenet_dim;
+    const bool want = taco_persistent_wanted();
+    const int KS = c.attention_location_kernel_size, half = (KS - 1) / 2, PT = (B * L + 15) / 16;
+    const int MC = M / 32, NS = MC ? 256 / MC : 0, K4A = (P + M + A) / 4;
+    const size_t lds = (size_t)16 * K4A * 16 +
+                       sizeof(float) * ((size_t)L * MC + (size_t)PT * 8 + 16 * KS + 2 * (PT + 2 * half) + 256 + 128 + 64 + 256 + NS * MC + 16 + 1024);
+    int dev_id = 0, n_cu = 0, coop = 0, lds_max = 0;
+    (void)hipGetDevice(&dev_id);
+    (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev_id);
+    (void)hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev_id);
+    (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id);
+    const int req = (int)opt_int(OPT_TACO_PERSISTENT, 0);
+    const bool explicit_req = req != 0;                                     // an explicit request must run the persistent kernel or fail
+    bool fits = want && B <= 8 && L <= 256 && (M == 512 || M == 640) && A == 1024 && D == 1024 && P == 256 && KS % 2 == 1 &&
+                (B * L + 15) / 16 + KS - 1 <= 256 &&      /* the alignment window of an energy tile: one word per thread */
+                lds <= (size_t)std::max(lds_max, 64 * 1024) && n_cu >= 256 && coop && w.tail_o > 0;
+    if (explicit_req && !fits) {
+        set_error("%s: TTSAMD_TACO_PERSISTENT=%d but the persistent decoder does not fit (B=%d <= 8, L=%d <= 256, memory dim %d in "
+                  "{512, 640}, %zu B of LDS <= %d, %d CUs >= 256, cooperative launch %d)", who, req, B, L, M, lds, lds_max, n_cu, coop);
+        return TTSAMD_EINVAL;
     }
-    if (!done) {
-    // The loop is launch-bound when issued kernel by kernel (7 dependent launches of 4-14 us per step), so
-    // 8 steps are captured once into a hipGraph (the step index lives in device memory and is advanced by the
-    // graph's last node) and replayed.  The stop flags come back through pinned memory two replays late, so
-    // the host never drains the queue; frames computed past the stop are sliced off (the reference breaks
-    // as soon as every utterance has finished, tacotron2_ms.py:327 -> torchaudio _Decoder.infer).
-    constexpr int GSTEPS = 8, RING = 4;
-    std::lock_guard<std::mutex> lock(h->mu);
-    if (h->pinned_cap < B) {
-        if (h->pinned) TTS_CHECK_HIP(hipHostFree(h->pinned));
-        h->pinned = nullptr;
-        TTS_CHECK_HIP(hipHostMalloc((void**)&h->pinned, (size_t)RING * B * sizeof(int32_t), hipHostMallocDefault));
-        h->pinned_cap = B;
+    if (fits && !explicit_req) {
+        std::lock_guard<std::mutex> lock(h->mu);
+        if (h->persist_skip > 0) { --h->persist_skip; fits = false; }        // a recent time-out: do not pay the spin again
     }
-    for (auto& e : h->ev)
-        if (!e) TTS_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!h->ev_in) TTS_CHECK_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-    if (!h->loop_stream) TTS_CHECK_HIP(hipStreamCreateWithFlags(&h->loop_stream, hipStreamNonBlocking));
-    hipStream_t caller = s;
-    TTS_CHECK_HIP(hipEventRecord(h->ev_in, caller));          // encoder + state resets were queued on the caller's stream
-    s = h->loop_stream;
-    TTS_CHECK_HIP(hipStreamWaitEvent(s, h->ev_in, 0));
+    pl.fits = fits;
+    pl.explicit_req = explicit_req;
+    pl.lds = lds;
+    return 0;
+}
+
+// The persistent kernel's arguments for a decode (s0 / s1 are set per segment) -> the instantiation that runs it
+static const void* taco_persist_params(const Taco2* h, const TWs& w, const int64_t* lengths, int B, int L, int Tcap, int max_step,
+                                       int64_t dropout_seed, float* mel_raw, float* alignments, int32_t* mel_lens, TacoPersist& q) {
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    const float* W = h->dev;
+    const int M = h->mem_dim;
+    q.pre1 = W + h->pre1;
+    q.att_wih = W + h->att_wih; q.att_whh = W + h->att_whh; q.att_b = W + h->att_b;
+    q.dec_wih = W + h->dec_wih; q.dec_whh = W + h->dec_whh; q.dec_b = W + h->dec_b;
+    q.wq = W + h->wq; q.loc_fold = W + h->loc_fold; q.v = W + h->v;
+    q.pm = w.pm; q.memory = w.memory;
+    q.projx_w = W + h->projx_w; q.projx_b = W + h->projx_b;
+    q.lens = lengths;
+    q.xch = w.xch; q.tail_o = w.tail_o; q.step_floats = w.step_floats; q.Lp = w.Lp; q.PTp = w.PTp;
+    q.mel_out = mel_raw; q.align_out = alignments; q.mel_lens = mel_lens;
+    q.B = B; q.L = L; q.KS = c.attention_location_kernel_size; q.Tcap = Tcap; q.max_step = max_step; q.n_mels = c.n_mels;
+    q.thr = c.gate_threshold; q.seed = (long long)dropout_seed; q.early_stop = c.decoder_early_stopping != 0;
+    q.s0 = q.s1 = 0;
+    q.state = w.pstate;
+    const bool flow = taco_persistent_mode() == 2;
+    return flow ? (M == 512 ? (const void*)taco_decoder_persistent<512, true> : (const void*)taco_decoder_persistent<640, true>)
+                : (M == 512 ? (const void*)taco_decoder_persistent<512, false> : (const void*)taco_decoder_persistent<640, false>);
+}
+
+// One segment of the persistent decoder: steps [s0, s1) as one cooperative launch (TacoPersist: why), s1 - s0 <= w.seg.  `prev_steps` is
+// the length of the segment before it, whose last region becomes region 0.  Queues only; the caller reads the tail (error flag at
+// tail_o + 256, step count at tail_o + 320) behind it.  *launched = false: the launch was refused and the graph path takes over (the
+// back-off is recorded; with an explicit request that is an error instead).  The caller holds h->mu.
+static int32_t taco_persist_segment(const Taco2* h, const TWs& w, TacoPersist& q, const void* fn, const TacoPlan& pl, int s0, int s1,
+                                    int prev_steps, const char* who, bool* launched, hipStream_t s) {
+    const bool flow = fn == (const void*)taco_decoder_persistent<512, true> || fn == (const void*)taco_decoder_persistent<640, true>;
+    void* args[] = {&q};
+    *launched = false;
+    q.s0 = s0;
+    q.s1 = s1;
+    if (s0 > 0)    // region 0 of this segment = what the last step of the previous one produced
+        TTS_CHECK_HIP(hipMemcpyAsync(w.xch, w.xch + (int64_t)prev_steps * w.step_floats, (size_t)w.step_floats * sizeof(float),
+                                     hipMemcpyDeviceToDevice, s));
+    if (flow)    // every word a consumer may poll starts as the sentinel 0xFFFFFFFF (regions 1 ... of this segment)
+        TTS_CHECK_HIP(hipMemsetAsync(w.xch + w.step_floats, 0xFF, (size_t)(w.tail_o - w.step_floats) * sizeof(float), s));
+    if (s0 == 0) TTS_CHECK_HIP(hipMemsetAsync(w.xch, 0, (size_t)w.step_floats * sizeof(float), s));    // region 0: the zero initial state
+    TTS_CHECK_HIP(hipMemsetAsync(w.xch + w.tail_o, 0, 384 * sizeof(float), s));                        // barrier slots, error flag, step count
+    // LDS opt-in or cooperative launch rejected (another partitioning / device, hipErrorCooperativeLaunchTooLarge): the
+    // graph path still works, so only an explicit request turns this into an error
+    hipError_t le = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+    if (le == hipSuccess) le = hipLaunchCooperativeKernel(fn, dim3(256), dim3(256), args, (unsigned)pl.lds, s);
+    if (le != hipSuccess) {
+        (void)hipGetLastError();
+        if (pl.explicit_req) {
+            set_error("%s: launching the persistent decoder failed: %s", who, hipGetErrorString(le));
+            return TTSAMD_EHIP;
+        }
+        // hipErrorCooperativeLaunchTooLarge can be transient (another stream held CUs at that moment): same bounded back-off
+        // as a hand-off time-out; anything else (LDS opt-in rejected, no cooperative launch on this partitioning) is permanent
+        if (le == hipErrorCooperativeLaunchTooLarge) {
+            h->persist_backoff = std::min(256, std::max(8, 2 * h->persist_backoff));
+            h->persist_skip = h->persist_backoff;
+        } else {
+            h->persist_skip = 1 << 30;
+        }
+        ++h->persist_launch_failures;
+        fprintf(stderr, "ttsamd: tacotron2 persistent decoder could not be launched (%s), using the graph path%s\n", hipGetErrorString(le),
+                le == hipErrorCooperativeLaunchTooLarge ? " (retrying after a back-off)" : " for the life of this handle");
+        return 0;
+    }
+    *launched = true;
+    return 0;
+}
+
+// A segment's error flag came back set (err > 0: a block waited > 80 ms for another one, the 256 blocks were not all resident -- CUs held
+// by other streams; err < 0: the launch was refused).  The graph path recomputes the loop from the same state -- the persistent kernel keeps
+// its own in the arena, the graph path's buffers are still the zero state of taco_head --; only an explicit request is an error.  The
+// caller holds h->mu.
+static int32_t taco_persist_gave_up(const Taco2* h, const TacoPlan& pl, int err, const char* who, int32_t* mel_lens, int B, hipStream_t s) {
+    if (pl.explicit_req) {
+        set_error("%s: the persistent decoder timed out waiting for another block (are 256 CUs free for it?)", who);
+        return TTSAMD_EHIP;
+    }
+    if (err > 0) {
+        h->persist_backoff = std::min(256, std::max(8, 2 * h->persist_backoff));
+        h->persist_skip = h->persist_backoff;
+        fprintf(stderr, "ttsamd: tacotron2 persistent decoder timed out, using the graph path (and for the next %d calls)\n",
+                h->persist_skip);
+    }
+    TTS_CHECK_HIP(hipMemsetAsync(mel_lens, 0, (size_t)B * sizeof(int32_t), s));     // (the kernel had started counting)
+    return 0;
+}
+
+// Eight decoder steps captured on `s` (not the legacy default stream) into an executable graph: the step index lives in device memory
+// (w.step) and is advanced by the graph's last node, so one graph serves every replay of a decode.
+constexpr int TACO_GSTEPS = 8;
+static int32_t taco_graph_capture(const Taco2* h, const TWs& w, const int64_t* lengths, int B, int L, int Tcap, int64_t dropout_seed,
+                                  float* mel_raw, float* alignments, int32_t* mel_lens, const char* who, hipGraphExec_t* exec_out,
+                                  hipStream_t s) {
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    const int M = h->mem_dim, A = c.attention_rnn_dim, D = c.decoder_rnn_dim, P = c.prenet_dim;
+    const float* W = h->dev;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     TTS_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
     int32_t cap_rc = 0;
-    for (int i = 0; i < GSTEPS && cap_rc == 0; ++i) {
+    for (int i = 0; i < TACO_GSTEPS && cap_rc == 0; ++i) {
         const int pi = i & 1, po = pi ^ 1;
         hipLaunchKernelGGL(taco_prenet_kernel, dim3(B, 8), dim3(1024), 0, s, w.dec_in, W + h->pre0, W + h->pre1, c.n_mels,
                            (long long)dropout_seed, w.step, i, w.pre);
@@ -2090,15 +2087,121 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
                            W + h->proj_b, c.n_mels, c.gate_threshold, w.step, i, Tcap, B, mel_raw, w.dec_in, mel_lens,
                            w.finished);
     }
-    hipLaunchKernelGGL(taco_advance_kernel, dim3(1), dim3(1), 0, s, w.step, GSTEPS);
+    hipLaunchKernelGGL(taco_advance_kernel, dim3(1), dim3(1), 0, s, w.step, TACO_GSTEPS);
     hipError_t cap_err = hipStreamEndCapture(s, &graph);
     if (cap_err == hipSuccess && cap_rc == 0) cap_err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     if (graph) (void)hipGraphDestroy(graph);
-    if (cap_rc != 0) return cap_rc;
+    if (cap_rc != 0) {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        return cap_rc;
+    }
     if (cap_err != hipSuccess) {
-        set_error("tacotron2_infer: capturing the decoder step graph failed: %s", hipGetErrorString(cap_err));
+        set_error("%s: capturing the decoder step graph failed: %s", who, hipGetErrorString(cap_err));
         return TTSAMD_EHIP;
     }
+    *exec_out = exec;
+    return 0;
+}
+
+// The postnet on T frames: x [B][80][T] with row stride x_cs (the raw mel, or a window of it through an offset pointer) -> y with strides
+// y_bs / y_cs; the residual fused into the last conv is x itself.  b0 / b1: [B][postnet_embedding_dim][T] each.
+static int32_t taco_postnet(const Taco2* h, const float* x, int x_cs, float* y_out, int64_t yo_bs, int yo_cs, float* b0, float* b1, int B,
+                            int T, hipStream_t s) {
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    const float* px = x;
+    int64_t px_bs = (int64_t)c.n_mels * x_cs;
+    int px_cs = x_cs;
+    float* bufs[2] = {b0, b1};
+    const int np_ = (int)h->post_convs.size();
+    for (int i = 0; i < np_; ++i) {
+        const TConv& cv = h->post_convs[i];
+        const bool last = i == np_ - 1;
+        float* y = last ? y_out : bufs[i & 1];
+        const int64_t y_bs = last ? yo_bs : (int64_t)cv.cout * T;
+        const int y_cs = last ? yo_cs : T;
+        TTS_TRY(tconv(h, cv, px, px_bs, px_cs, y, y_bs, y_cs, last ? x : nullptr, B, T, last ? 0 : 3, s, 1.f, 1, (int64_t)c.n_mels * x_cs, x_cs));
+        px = y; px_bs = y_bs; px_cs = y_cs;
+    }
+    return 0;
+}
+
+int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* lengths, const int64_t* speaker_ids,
+                        int32_t B, int32_t L, int32_t max_step, int64_t dropout_seed, float* mel_post,
+                        int32_t* mel_lens, float* alignments, float* mel_raw, int32_t* n_steps_out, void* ws,
+                        int64_t ws_bytes, hipStream_t s) {
+    TTS_REQUIRE(h && tokens && lengths && mel_post && mel_lens && alignments && mel_raw && n_steps_out,
+                "tacotron2_infer: null argument");
+    TTS_REQUIRE(B >= 1 && L >= 1 && L <= TACO_LMAX && max_step >= 1, "tacotron2_infer: bad batch/length/max_step");
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    TTS_REQUIRE(c.num_speakers <= 1 || speaker_ids, "tacotron2_infer: speaker_ids is null");
+    Arena a(ws, ws_bytes);
+    TWs w;
+    const int Tcap = max_step;
+    tcarve(h, a, B, L, std::min(Tcap, taco_segment_steps()), Tcap, w);
+    if (!ws || !a.ok) {
+        set_error("tacotron2_infer: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
+        return TTSAMD_ENOMEM;
+    }
+    TTS_TRY(taco_head(h, tokens, lengths, speaker_ids, B, L, w, mel_lens, s));
+    int steps = 0;
+    bool done = false;
+    // ---- the persistent decoder (one cooperative launch for the whole loop) when the geometry fits its residency plan
+    {
+        TacoPlan pl;
+        TTS_TRY(taco_persist_plan(h, B, L, w, "tacotron2_infer", pl));
+        if (pl.fits) {
+            TacoPersist q;
+            const void* fn = taco_persist_params(h, w, lengths, B, L, Tcap, max_step, dropout_seed, mel_raw, alignments, mel_lens, q);
+            std::lock_guard<std::mutex> lock(h->mu);
+            int32_t tail[2] = {0, 0};                                   // err_o and steps_o are 64 floats apart: two copies
+            // one cooperative launch per segment of at most w.seg steps (TacoPersist: why); a whole bench-size decode (448 steps) is one
+            for (int s0 = 0; s0 < max_step; s0 += w.seg) {
+                bool launched = false;
+                TTS_TRY(taco_persist_segment(h, w, q, fn, pl, s0, std::min(max_step, s0 + w.seg), w.seg, "tacotron2_infer", &launched, s));
+                if (!launched) {
+                    tail[0] = -1;
+                    break;
+                }
+                TTS_CHECK_HIP(hipMemcpyAsync(&tail[0], w.xch + w.tail_o + 256, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                TTS_CHECK_HIP(hipMemcpyAsync(&tail[1], w.xch + w.tail_o + 320, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                TTS_CHECK_HIP(hipStreamSynchronize(s));
+                // a time-out, or every utterance's gate fired inside this segment -- also on its LAST step (the kernel then reports exactly s1;
+                // an unfinished segment reports max_step): no extra segment (a region copy, an 82 MB memset and a cooperative launch for nothing)
+                if (tail[0] != 0 || (int64_t)tail[1] <= (int64_t)q.s1) break;
+            }
+            if (tail[0] != 0) {
+                TTS_TRY(taco_persist_gave_up(h, pl, tail[0], "tacotron2_infer", mel_lens, B, s));
+            } else {
+                steps = tail[1];
+                done = true;
+                h->persist_backoff = 0;
+            }
+        }
+    }
+    if (!done) {
+    // The loop is launch-bound when issued kernel by kernel (7 dependent launches of 4-14 us per step), so
+    // 8 steps are captured once into a hipGraph (the step index lives in device memory and is advanced by the
+    // graph's last node) and replayed.  The stop flags come back through pinned memory two replays late, so
+    // the host never drains the queue; frames computed past the stop are sliced off (the reference breaks
+    // as soon as every utterance has finished, tacotron2_ms.py:327 -> torchaudio _Decoder.infer).
+    constexpr int GSTEPS = TACO_GSTEPS, RING = 4;
+    std::lock_guard<std::mutex> lock(h->mu);
+    if (h->pinned_cap < B) {
+        if (h->pinned) TTS_CHECK_HIP(hipHostFree(h->pinned));
+        h->pinned = nullptr;
+        TTS_CHECK_HIP(hipHostMalloc((void**)&h->pinned, (size_t)RING * B * sizeof(int32_t), hipHostMallocDefault));
+        h->pinned_cap = B;
+    }
+    for (auto& e : h->ev)
+        if (!e) TTS_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (!h->ev_in) TTS_CHECK_HIP(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+    if (!h->loop_stream) TTS_CHECK_HIP(hipStreamCreateWithFlags(&h->loop_stream, hipStreamNonBlocking));
+    hipStream_t caller = s;
+    TTS_CHECK_HIP(hipEventRecord(h->ev_in, caller));          // encoder + state resets were queued on the caller's stream
+    s = h->loop_stream;
+    TTS_CHECK_HIP(hipStreamWaitEvent(s, h->ev_in, 0));
+    hipGraphExec_t exec = nullptr;
+    TTS_TRY(taco_graph_capture(h, w, lengths, B, L, Tcap, dropout_seed, mel_raw, alignments, mel_lens, "tacotron2_infer", &exec, s));
     hipError_t run_err = hipSuccess;
     for (int g = 0; steps < max_step && run_err == hipSuccess; ++g) {
         run_err = hipGraphLaunch(exec, s);
@@ -2132,20 +2235,287 @@ int32_t tacotron2_infer(const Taco2* h, const int64_t* tokens, const int64_t* le
     T = c.decoder_early_stopping != 0 ? std::min(T, steps) : steps;   // without early stopping the reference returns every step it ran
     *n_steps_out = T;
     // ---- postnet on [B][80][T] (row stride Tcap), residual fused into the last conv
-    const float* px = mel_raw;
-    int64_t px_bs = (int64_t)c.n_mels * Tcap;
-    int px_cs = Tcap;
-    float* bufs[2] = {w.post0, w.post1};
-    const int np_ = (int)h->post_convs.size();
-    for (int i = 0; i < np_; ++i) {
-        const TConv& cv = h->post_convs[i];
-        const bool last = i == np_ - 1;
-        float* y = last ? mel_post : bufs[i & 1];
-        const int64_t y_bs = last ? (int64_t)c.n_mels * Tcap : (int64_t)cv.cout * T;
-        const int y_cs = last ? Tcap : T;
-        TTS_TRY(tconv(h, cv, px, px_bs, px_cs, y, y_bs, y_cs, last ? mel_raw : nullptr, B, T, last ? 0 : 3, s));
-        px = y; px_bs = y_bs; px_cs = y_cs;
+    return taco_postnet(h, mel_raw, Tcap, mel_post, (int64_t)c.n_mels * Tcap, Tcap, w.post0, w.post1, B, T, s);
+}
+
+// ---- streaming session: the same decode in caller-sized advances ---------------------------------------------------------------------
+// Host side of a session (ttsamd_tacotron2_stream_begin ... _end).  Everything on the device lives in the caller's workspace and output
+// buffers; the handle is not changed (its mutex serialises cooperative launches and guards the back-off counters, as in tacotron2_infer).
+struct TacoStream {
+    const Taco2* h = nullptr;
+    TWs w;
+    TacoPlan pl;
+    TacoPersist q;
+    const void* fn = nullptr;
+    bool persistent = false;    // the path, decided once at begin; a hand-off time-out moves the session to the graph path for good
+    int B = 0, L = 0, max_step = 0, max_chunk = 0;
+    int64_t seed = -1;
+    const int64_t* lengths = nullptr;
+    float *mel_raw = nullptr, *alignments = nullptr;
+    int32_t* mel_lens = nullptr;
+    int steps_run = 0;          // decoder steps computed so far
+    int prev_steps = 0;         // length of the last persistent segment
+    int steps_done = 0, ended = 0;
+    // cut bound (taco_cut_kernel): per row the separator column (< 0: none), the running maximum, the bound, the frames scanned
+    int32_t *cut_col = nullptr, *cut_c = nullptr, *cut_seen = nullptr, *cut_out = nullptr;
+    float* cut_max = nullptr;
+    int rows_to_batch_end = 0;
+    int halo = 0;
+    hipStream_t loop = nullptr;        // graph path: capture is not allowed on the legacy default stream
+    hipEvent_t ev = nullptr;
+    hipGraphExec_t exec = nullptr;
+};
+
+constexpr int TACO_CUT_HEAD = 4, TACO_CUT_ROW = 4;      // int32 words of taco_cut_kernel's report: head, then per row
+
+// One thread per row, behind every advance.  Head: [0] the persistent segment's error flag (non-zero: nothing else is valid and no state
+// was touched), [1] ended, [2] steps_done (what tacotron2_infer would report: min(longest row, steps run) with early stopping),
+// [3] steps run.  Row b: [0] final_frames, [1] row_ended, [2] n_end (the cut bound c_s; the cut itself once row_ended), [3] row length.
+//   ended      persistent path: the kernel's step word <= s1 (every gate fired inside the segment) or s1 == max_step;
+//              graph path (tail == nullptr): every `finished` flag set and early stopping on, or s1 == max_step
+//   row_ended  ended, or the row's frame count stands still below the steps run (a row whose gate fires on the very last step of an
+//              advance is reported one advance later); with rows_to_end a row ends with the batch and runs to steps_done (tts_single's rule)
+//   c_s        first t < s with ps[t] >= 0.8f * max(ps[:s]), ps = alignments[b, :, col_b]: never decreases, <= n_end, = n_end at the row's end
+//   final      frames whose postnet output cannot change any more, t + halo < steps run (all of them once ended), below the cut bound
+__global__ void taco_cut_kernel(const float* __restrict__ tail, const int32_t* __restrict__ finished, const int32_t* __restrict__ mel_lens,
+                                const float* __restrict__ align, const int32_t* __restrict__ cols, int B, int L, int Tcap, int s1, int max_step,
+                                int early_stop, int halo, int rows_to_end, float* __restrict__ run_max, int32_t* __restrict__ cut_c,
+                                int32_t* __restrict__ seen, int32_t* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    int err = 0, steps_run = s1, ended = s1 >= max_step;
+    if (tail != nullptr) {
+        err = *reinterpret_cast<const int32_t*>(tail + 256);
+        const int st = *reinterpret_cast<const int32_t*>(tail + 320);
+        if (st <= s1) { steps_run = st; ended = 1; }
+    } else if (early_stop) {
+        int all = 1;
+        for (int i = 0; i < B; ++i) all &= finished[i] != 0;
+        ended |= all;
     }
+    if (err != 0) {
+        if (b == 0) out[0] = err;
+        return;
+    }
+    int longest = 0;
+    for (int i = 0; i < B; ++i) longest = max(longest, mel_lens[i]);
+    const int t_now = (ended && early_stop) ? min(longest, steps_run) : steps_run;
+    if (b == 0) {
+        out[0] = 0; out[1] = ended; out[2] = t_now; out[3] = steps_run;
+    }
+    if (b >= B) return;
+    const int len_b = min(mel_lens[b], t_now);
+    const int row_ended = rows_to_end ? ended : (ended || len_b < steps_run);
+    const int row_len = rows_to_end ? t_now : (row_ended ? len_b : t_now);
+    int c = row_len;
+    const int col = cols ? cols[b] : -1;
+    if (col >= 0 && col < L) {
+        float m = run_max[b];
+        c = cut_c[b];
+        const float* ps = align + (int64_t)b * Tcap * L + col;
+        for (int t = seen[b]; t < row_len; ++t) m = fmaxf(m, ps[(int64_t)t * L]);
+        const float thr = 0.8f * m;
+        while (c < row_len && !(ps[(int64_t)c * L] >= thr)) ++c;
+        run_max[b] = m;
+        cut_c[b] = c;
+        seen[b] = max(seen[b], row_len);
+    }
+    const int settled = ended ? row_len : max(0, min(row_len, steps_run - halo));
+    int32_t* o = out + TACO_CUT_HEAD + TACO_CUT_ROW * b;
+    o[0] = min(settled, c);
+    o[1] = row_ended;
+    o[2] = c;
+    o[3] = row_len;
+}
+
+static void tcarve_stream(const Taco2* h, Arena& a, int B, int L, int max_chunk, TacoStream& st) {
+    tcarve(h, a, B, L, max_chunk, 0, st.w);
+    st.cut_col = a.take<int32_t>(B);
+    st.cut_c = a.take<int32_t>(B);
+    st.cut_seen = a.take<int32_t>(B);
+    st.cut_max = a.take<float>(B);
+    st.cut_out = a.take<int32_t>(TACO_CUT_HEAD + (int64_t)TACO_CUT_ROW * B);
+}
+
+int64_t tacotron2_stream_bytes(const Taco2* h, int32_t B, int32_t L, int32_t max_step, int32_t max_chunk) {
+    (void)max_step;             // the arena is sized by the longest advance; the frames themselves are in the caller's output buffers
+    Arena a(nullptr, 0);
+    TacoStream st;
+    tcarve_stream(h, a, B, L, max_chunk, st);
+    return a.off;
+}
+
+int32_t tacotron2_postnet_halo(const Taco2* h) {
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    return c.postnet_n_convolution * (c.postnet_kernel_size - 1) / 2;
+}
+
+void tacotron2_stream_end(TacoStream* st) {
+    if (!st) return;
+    if (st->exec) (void)hipGraphExecDestroy(st->exec);
+    if (st->ev) (void)hipEventDestroy(st->ev);
+    if (st->loop) (void)hipStreamDestroy(st->loop);
+    delete st;
+}
+
+int32_t tacotron2_stream_begin(const Taco2* h, const int64_t* tokens, const int64_t* lengths, const int64_t* speaker_ids, int32_t B,
+                               int32_t L, int32_t max_step, int32_t max_chunk, int64_t dropout_seed, const int32_t* cut_cols,
+                               int32_t rows_to_batch_end, float* mel_raw, int32_t* mel_lens, float* alignments, void* ws, int64_t ws_bytes,
+                               TacoStream** out, hipStream_t s) {
+    TTS_REQUIRE(h && tokens && lengths && mel_raw && mel_lens && alignments && out, "tacotron2_stream_begin: null argument");
+    TTS_REQUIRE(B >= 1 && L >= 1 && L <= TACO_LMAX && max_step >= 1, "tacotron2_stream_begin: bad batch/length/max_step");
+    TTS_REQUIRE(max_chunk >= TACO_GSTEPS && max_chunk % TACO_GSTEPS == 0,
+                "tacotron2_stream_begin: max_chunk_steps %d must be a positive multiple of %d", max_chunk, TACO_GSTEPS);
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    TTS_REQUIRE(c.num_speakers <= 1 || speaker_ids, "tacotron2_stream_begin: speaker_ids is null");
+    TacoStream* st = new TacoStream();
+    Arena a(ws, ws_bytes);
+    tcarve_stream(h, a, B, L, max_chunk, *st);
+    if (!ws || !a.ok) {
+        set_error("tacotron2_stream_begin: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
+        delete st;
+        return TTSAMD_ENOMEM;
+    }
+    st->h = h; st->B = B; st->L = L; st->max_step = max_step; st->max_chunk = max_chunk; st->seed = dropout_seed;
+    st->lengths = lengths; st->mel_raw = mel_raw; st->alignments = alignments; st->mel_lens = mel_lens;
+    st->rows_to_batch_end = rows_to_batch_end != 0;
+    st->halo = tacotron2_postnet_halo(h);
+    int32_t rc = taco_head(h, tokens, lengths, speaker_ids, B, L, st->w, mel_lens, s);
+    if (rc == 0) rc = taco_persist_plan(h, B, L, st->w, "tacotron2_stream_begin", st->pl);
+    if (rc == 0) {
+        st->persistent = st->pl.fits;
+        if (st->persistent)
+            st->fn = taco_persist_params(h, st->w, lengths, B, L, max_step, max_step, dropout_seed, mel_raw, alignments, mel_lens, st->q);
+        hipError_t e = hipSuccess;
+        if (cut_cols) e = hipMemcpyAsync(st->cut_col, cut_cols, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+        else e = hipMemsetAsync(st->cut_col, 0xFF, (size_t)B * sizeof(int32_t), s);           // -1: no cut
+        if (e == hipSuccess) e = hipMemsetAsync(st->cut_c, 0, (size_t)B * sizeof(int32_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(st->cut_seen, 0, (size_t)B * sizeof(int32_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(st->cut_max, 0, (size_t)B * sizeof(float), s);      // attention weights are >= 0
+        if (e != hipSuccess) {
+            set_error("tacotron2_stream_begin: %s", hipGetErrorString(e));
+            rc = TTSAMD_EHIP;
+        }
+    }
+    if (rc != 0) {
+        tacotron2_stream_end(st);
+        return rc;
+    }
+    *out = st;
+    return 0;
+}
+
+// graph path of a session: `n` more steps as n / 8 replays of the session's graph (captured at the first use) on the session's own
+// stream, ordered behind the caller's by an event; the caller's stream waits for the replays in turn
+static int32_t taco_stream_replay(TacoStream* st, int n, hipStream_t s) {
+    const Taco2* h = st->h;
+    if (!st->loop) TTS_CHECK_HIP(hipStreamCreateWithFlags(&st->loop, hipStreamNonBlocking));
+    if (!st->ev) TTS_CHECK_HIP(hipEventCreateWithFlags(&st->ev, hipEventDisableTiming));
+    TTS_CHECK_HIP(hipEventRecord(st->ev, s));
+    TTS_CHECK_HIP(hipStreamWaitEvent(st->loop, st->ev, 0));
+    if (!st->exec)
+        TTS_TRY(taco_graph_capture(h, st->w, st->lengths, st->B, st->L, st->max_step, st->seed, st->mel_raw, st->alignments, st->mel_lens,
+                                   "tacotron2_stream_advance", &st->exec, st->loop));
+    for (int g = 0; g < (n + TACO_GSTEPS - 1) / TACO_GSTEPS; ++g) {
+        const hipError_t e = hipGraphLaunch(st->exec, st->loop);
+        if (e != hipSuccess) {
+            set_error("tacotron2_stream_advance: decoder loop failed: %s", hipGetErrorString(e));
+            return TTSAMD_EHIP;
+        }
+    }
+    TTS_CHECK_HIP(hipEventRecord(st->ev, st->loop));
+    TTS_CHECK_HIP(hipStreamWaitEvent(s, st->ev, 0));
+    return 0;
+}
+
+static int32_t taco_stream_report(TacoStream* st, bool from_tail, int s1, int32_t* host, hipStream_t s) {
+    const ttsamd_tacotron2_cfg& c = st->h->cfg;
+    const int B = st->B, words = TACO_CUT_HEAD + TACO_CUT_ROW * B;
+    hipLaunchKernelGGL(taco_cut_kernel, dim3((B + 63) / 64), dim3(64), 0, s, from_tail ? st->w.xch + st->w.tail_o : (const float*)nullptr,
+                       st->w.finished, st->mel_lens, st->alignments, st->cut_col, B, st->L, st->max_step, s1, st->max_step,
+                       (int)(c.decoder_early_stopping != 0), st->halo, st->rows_to_batch_end, st->cut_max, st->cut_c, st->cut_seen,
+                       st->cut_out);
+    TTS_CHECK_HIP(hipGetLastError());
+    TTS_CHECK_HIP(hipMemcpyAsync(host, st->cut_out, (size_t)words * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    TTS_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int32_t tacotron2_stream_advance(TacoStream* st, int32_t n_steps, int32_t* steps_done, int32_t* ended, int32_t* rows, hipStream_t s) {
+    TTS_REQUIRE(st && steps_done && ended, "tacotron2_stream_advance: null argument");
+    TTS_REQUIRE(n_steps >= TACO_GSTEPS && n_steps % TACO_GSTEPS == 0 && n_steps <= st->max_chunk,
+                "tacotron2_stream_advance: n_steps %d must be a positive multiple of %d and at most max_chunk_steps = %d", n_steps, TACO_GSTEPS,
+                st->max_chunk);
+    TTS_REQUIRE(!st->ended, "tacotron2_stream_advance: the session has ended (%d steps)", st->steps_done);
+    const Taco2* h = st->h;
+    const int B = st->B, s0 = st->steps_run, s1 = std::min(st->max_step, s0 + n_steps);
+    std::vector<int32_t> rep(TACO_CUT_HEAD + (size_t)TACO_CUT_ROW * B, 0);
+    bool on_graph = !st->persistent;
+    if (st->persistent) {
+        std::lock_guard<std::mutex> lock(h->mu);
+        bool launched = false;
+        TTS_TRY(taco_persist_segment(h, st->w, st->q, st->fn, st->pl, s0, s1, st->prev_steps, "tacotron2_stream_advance", &launched, s));
+        if (launched) TTS_TRY(taco_stream_report(st, true, s1, rep.data(), s));
+        else rep[0] = -1;
+        if (rep[0] != 0) {
+            // tacotron2_infer's fallback: the graph path recomputes steps [0, s1) from the encoder outputs the session kept, and the
+            // session stays there (frames the caller already passed on are its business: it does not take them again)
+            TTS_TRY(taco_persist_gave_up(h, st->pl, rep[0], "tacotron2_stream_advance", st->mel_lens, B, s));
+            st->persistent = false;
+            TTS_TRY(taco_stream_replay(st, s1, s));
+            on_graph = true;
+        } else {
+            h->persist_backoff = 0;
+            st->prev_steps = s1 - s0;
+        }
+    } else {
+        TTS_TRY(taco_stream_replay(st, s1 - s0, s));
+    }
+    if (on_graph) TTS_TRY(taco_stream_report(st, false, s1, rep.data(), s));
+    st->ended = rep[1];
+    st->steps_done = rep[2];
+    st->steps_run = on_graph ? s1 : rep[3];
+    *steps_done = st->steps_done;
+    *ended = st->ended;
+    if (rows) std::memcpy(rows, rep.data() + TACO_CUT_HEAD, (size_t)TACO_CUT_ROW * B * sizeof(int32_t));
+    return 0;
+}
+
+int64_t tacotron2_postnet_window_bytes(const Taco2* h, int32_t B, int32_t n_frames) {
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    Arena a(nullptr, 0);
+    const int64_t span = (int64_t)n_frames + 2 * tacotron2_postnet_halo(h);
+    a.take<float>((int64_t)B * c.postnet_embedding_dim * span);
+    a.take<float>((int64_t)B * c.postnet_embedding_dim * span);
+    a.take<float>((int64_t)B * c.n_mels * span);
+    return a.off;
+}
+
+// mel_post[:, :, t0:t1) from the raw frames [t0 - halo, t1 + halo) clipped to [0, t_known): the five convs run over that span with its own
+// zero padding, which is the one-shot postnet's only at frame 0 and -- once the decode has ended -- at t_known; what an edge inside
+// the utterance spoils reaches `halo` frames inwards and stays outside [t0, t1).  The last conv adds the raw mel and writes to a
+// scratch row block, of which the core is copied out (frames of the halo already delivered are not written again).
+int32_t tacotron2_postnet_window(const Taco2* h, const float* mel_raw, float* mel_post, int32_t B, int32_t t_cap, int32_t t_known,
+                                 int32_t t0, int32_t t1, int32_t ended, void* ws, int64_t ws_bytes, hipStream_t s) {
+    TTS_REQUIRE(h && mel_raw && mel_post, "tacotron2_postnet_window: null argument");
+    const ttsamd_tacotron2_cfg& c = h->cfg;
+    const int halo = tacotron2_postnet_halo(h);
+    TTS_REQUIRE(B >= 1 && t_cap >= 1 && t_known >= 0 && t_known <= t_cap && t0 >= 0 && t0 < t1 && t1 <= t_known,
+                "tacotron2_postnet_window: bad window [%d, %d) of %d known frames (capacity %d)", t0, t1, t_known, t_cap);
+    TTS_REQUIRE(ended != 0 || (int64_t)t1 + halo <= t_known,
+                "tacotron2_postnet_window: frames [%d, %d) are not final: %d + halo %d > %d known frames and the decode has not ended", t0, t1, t1,
+                halo, t_known);
+    const int a0 = std::max(0, t0 - halo), a1 = (int)std::min<int64_t>(t_known, (int64_t)t1 + halo), span = a1 - a0;
+    Arena a(ws, ws_bytes);
+    float* b0 = a.take<float>((int64_t)B * c.postnet_embedding_dim * span);
+    float* b1 = a.take<float>((int64_t)B * c.postnet_embedding_dim * span);
+    float* yo = a.take<float>((int64_t)B * c.n_mels * span);
+    if (!ws || !a.ok) {
+        set_error("tacotron2_postnet_window: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
+        return TTSAMD_ENOMEM;
+    }
+    TTS_TRY(taco_postnet(h, mel_raw + a0, t_cap, yo, (int64_t)c.n_mels * span, span, b0, b1, B, span, s));
+    TTS_CHECK_HIP(hipMemcpy2DAsync(mel_post + t0, (size_t)t_cap * sizeof(float), yo + (t0 - a0), (size_t)span * sizeof(float),
+                                   (size_t)(t1 - t0) * sizeof(float), (size_t)B * c.n_mels, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 

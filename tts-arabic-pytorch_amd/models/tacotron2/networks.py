@@ -8,6 +8,8 @@ return conventions, with the arithmetic routed to the HIP engines.
 Differences, host-side only: `tts_batch` vocodes the (truncated / resized, hence ragged) mels in ONE
 ragged HiFi-GAN call instead of a per-mel loop (:340-346) — identical results, every layer pads at the
 true utterance edge — `vowelizer=` runs the Shakkelha / Shakkala taggers of models/diacritizers on the HIP tagger engine.
+Not in the reference: `Tacotron2Wave.tts_stream` (audio in chunks while the decoder is still running) with `cut_bound`, truncate_mel's
+cut in causal form.
 """
 from typing import List, Optional, Union
 
@@ -50,6 +52,50 @@ def truncate_mel(mel_spec: torch.Tensor, ps_end):
     n_end = int(hit[0])
     mel_cut = mel_spec[:, :n_end]
     return torch.nn.functional.pad(mel_cut, (0, 3), mode='replicate')
+
+
+def cut_bound(ps_seen, state=None):
+    """truncate_mel's cut in causal form.  The cut n_end = first t with ps[t] >= 0.8 * max(ps) needs the whole column; with
+    m_s = max(ps[:s]) and c_s = the first t < s with ps[t] >= 0.8 * m_s: c_s never decreases (the threshold only rises, so a frame
+    that failed it keeps failing), c_s <= n_end (no frame before c_s reaches 0.8 * m_s, let alone 0.8 * max(ps)) and c_T = n_end.
+    Frames below c_s can therefore leave before the utterance is over.  ps_seen: the NEW values of the separator column
+    (1-D float32 tensor), state: what the previous call returned (None at the start) -> (c_s, state).  The device twin is
+    taco_cut_kernel (csrc/tacotron2.hip).  How far c_s runs behind s depends on the checkpoint: one tiny early value of the column
+    holds it at that frame until the attention reaches the separator, i.e. until the end.  On a trained checkpoint the lag has not
+    been measured; the synthetic test checkpoint shows both cases (profiles/r36/NOTES.md: one line's bound is final 8 steps behind its
+    cut, another's sits at frame 1 until the cut at frame 35 has been decoded)."""
+    ps_seen = torch.as_tensor(ps_seen, dtype=torch.float32).reshape(-1).cpu()
+    m, c, ps = state if state is not None else (None, 0, ps_seen[:0])
+    ps = torch.cat([ps, ps_seen])
+    if ps.numel() == 0:
+        return 0, (m, c, ps)
+    m = ps_seen.max() if m is None else (torch.maximum(m, ps_seen.max()) if ps_seen.numel() else m)
+    thr = 0.8 * m
+    while c < ps.numel() and not bool(ps[c] >= thr):
+        c += 1
+    return c, (m, c, ps)
+
+
+def stream_truncate_mel(mel_spec: torch.Tensor, ps_end, halo: int = 0, block: int = 8):
+    """Host model of what Tacotron2Wave.tts_stream puts into the vocoder stream for one row with a cut: the frames arrive in blocks of
+    `block`; after each, the frames below min(c_s, s - halo) are appended; at the end what remains up to n_end, then frame n_end - 1
+    three more times.  -> (the mel put together, [appended-so-far after each block]): the mel is truncate_mel's, frame for frame."""
+    T = int(mel_spec.shape[-1])
+    out, sent, state, trace = [], 0, None, []
+    for s0 in range(0, T, block):
+        s1 = min(s0 + block, T)
+        c, state = cut_bound(ps_end[s0:s1], state)
+        final = min(c, s1 if s1 == T else max(s1 - halo, 0))
+        if final > sent:
+            out.append(mel_spec[:, sent:final])
+            sent = final
+        trace.append(sent)
+    n_end = state[1] if state is not None else 0
+    assert sent == n_end, (sent, n_end)
+    if n_end == 0:
+        return truncate_mel(mel_spec, ps_end), trace            # (what the one-shot path does with an empty cut)
+    out += [mel_spec[:, n_end - 1:n_end]] * 3
+    return torch.cat(out, dim=-1), trace
 
 
 def resize_mel(mel: torch.Tensor, rate: Union[int, float] = 1.0, mode: str = 'bicubic'):
@@ -224,6 +270,128 @@ class Tacotron2Wave(nn.Module):
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:348-351); so do we
         return [wave[i, :n[i]].cpu() for i in range(len(mel_list))]
+
+    def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak):
+        """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
+        from ttsamd.stream import StreamingVocoder
+        key = (str(self.device), int(chunk_frames), int(first_chunk_frames), bool(pcm16), int(max_streams), int(max_frames),
+               None if sample_rate is None else int(sample_rate), encoding, None if limiter is None else tuple(sorted(limiter.items())),
+               bool(true_peak))
+        if getattr(self, '_stream_key', None) != key:
+            self._stream_voc = StreamingVocoder(self.vocoder, self.denoiser, max_streams=max_streams, max_frames=max_frames,
+                                                chunk_frames=chunk_frames, first_chunk_frames=first_chunk_frames, pcm16=pcm16,
+                                                sample_rate=sample_rate, encoding=encoding, limiter=limiter,
+                                                **({'true_peak': True} if true_peak else {}))
+            self._stream_key = key
+        for sid in self._stream_voc.open_streams:           # a generator that was abandoned half-way
+            self._stream_voc.close(sid)
+        return self._stream_voc
+
+    def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
+                   denoise: float = 0.005, speaker_id: int = 0, batch_size: int = 8, vowelizer=None, postprocess_mel: bool = True,
+                   sample_rate=None, encoding=None, gain_db=0.0, limiter=False, true_peak=False, max_frames: int = 4096,
+                   speed: Union[int, float, None] = None, meter=False):
+        """`tts` that hands out audio while the decoder is still running (a generator; one at a time per model).  Tacotron2 makes its
+        mel frame by frame: the decoder runs in advances (Tacotron2Engine.stream), the postnet over windows of the frames that are
+        final, and every row of the batch is a growing stream of the chunked vocoder (StreamingVocoder.open_growing).
+        str -> CPU chunks whose concatenation has tts_single's samples and equals them within fp32 summation order (the vocoder's
+        windows); list -> (i, chunk, last) as the steps produce them: the lines go through Tacotron2 in batches of batch_size, sorted
+        by text_collate_fn, line i's audio is tts(list, batch_size)[i]'s, its chunks arrive in order and `last` once; the rows of a
+        finished batch drain while the next batch decodes.  Each turn of the loop runs one advance, one postnet window, the appends and
+        finishes, and one vocoder step.  The first advance is first_chunk_frames + the look-ahead the chunk planner asks for
+        (max(chunk_frames // 2, the right halo of vocoder, denoiser, resampler and limiter)) + the postnet's halo, rounded up to 8
+        steps; later ones are chunk_frames rounded up to 8.  The cooperative decoder holds every CU while it runs, so decoder and
+        vocoder alternate; they do not overlap.
+        postprocess_mel: the end-of-utterance cut in causal form (cut_bound): frames below the bound -- and at least the postnet's
+        halo behind the decoder -- enter the vocoder while the row is still being decoded; at the row's end follow the rest up to the
+        cut and the three repeated frames, so the streamed mel is truncate_mel's frame for frame.  How early audio leaves a row with
+        a cut depends on how far the bound runs behind the decoder on the checkpoint (cut_bound).
+        pcm16, sample_rate, encoding, gain_db (a scalar, or one value per line), limiter, true_peak: as FastPitch2Wave.tts_stream.
+        speed other than None / 1 (resize_mel needs the total length) and meter are ValueErrors; there is no peak normalisation (it
+        needs the whole wave).  Tacotron2.dropout_seed applies per batch as in `infer`.  `stream_sessions` maps each line to the
+        decoder session of its batch (its steps_done / ended at the time of a yield)."""
+        from ttsamd.engine import check_finite, check_true_peak, limiter_spec, row_values
+        if speed is not None and float(speed) != 1.0:
+            raise ValueError('tts_stream: speed is not supported in the stream (resize_mel needs the total length): use tts')
+        if meter:
+            raise ValueError('tts_stream: meter is not supported for Tacotron2 streams')
+        limiter = limiter_spec(limiter)
+        check_true_peak(true_peak, None, limiter)
+        single = isinstance(text_input, str)
+        lines = [text_input] if single else list(text_input)
+        gains = row_values(gain_db, len(lines), 'gain_db') if per_row(gain_db) else [gain_db] * len(lines)
+        check_finite(gains, 'gain_db')
+        if limiter is None and any(float(g) != 0.0 for g in gains):
+            raise ValueError('tts_stream: gain_db needs limiter=True (or its settings): a gain alone could clip')
+        batch_size = max(int(batch_size), 1)
+        gen = self._tts_stream(lines, [float(g) for g in gains], single, int(chunk_frames), int(first_chunk_frames), pcm16, float(denoise),
+                               speaker_id, batch_size, vowelizer, postprocess_mel, sample_rate, encoding, limiter, true_peak, int(max_frames))
+        return gen
+
+    @torch.inference_mode()
+    def _tts_stream(self, lines, gains, single, chunk_frames, first_chunk_frames, pcm16, denoise, speaker_id, batch_size, vowelizer,
+                    postprocess_mel, sample_rate, encoding, limiter, true_peak, max_frames):
+        model = self.model
+        sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, 2 * batch_size, max_frames, sample_rate, encoding, limiter, true_peak)
+        eng = model.engine()
+        up8 = lambda n: -(-int(n) // 8) * 8                                                              # noqa: E731
+        first_steps = up8(sv.first_release_frames(denoise) + eng.postnet_halo)
+        later_steps = up8(chunk_frames)
+        whole_rows = single or batch_size == 1          # tts_single's rule: the row is as long as the decode
+        self.stream_sessions = {}
+        todo = list(range(len(lines)))
+        sess, rows, line_of = None, [], {}              # rows of the session: [line, batch row, sid, frames sent, cut?]
+        while True:
+            if sess is None and todo and sv.free_slots >= min(batch_size, len(todo)):
+                idx, todo = todo[:batch_size], todo[batch_size:]
+                prepared = [model._tokens_for(lines[i], vowelizer, postprocess_mel) for i in idx]
+                ids = [torch.LongTensor(text.tokens_to_ids(tokens, model.phon_to_id)) for tokens, _ in prepared]
+                ids_pad, lens_sorted, reverse_ids = text_collate_fn(ids)
+                in_lens = lens_sorted.tolist()
+                cols = [-1] * len(idx)
+                for k, j in enumerate(reverse_ids.tolist()):
+                    if prepared[k][1]:
+                        cols[j] = in_lens[j] - model.n_eos - 1
+                sess = eng.stream(ids_pad, lens_sorted * 0 + speaker_id, lens_sorted, max_step=model.decoder_max_step,
+                                  dropout_seed=model.dropout_seed, max_chunk_steps=max(first_steps, later_steps), cut_columns=cols,
+                                  rows_to_batch_end=whole_rows)
+                rows = []
+                for k, j in enumerate(reverse_ids.tolist()):
+                    sid = sv.open_growing(denoise, gains[idx[k]])
+                    line_of[sid] = idx[k]
+                    self.stream_sessions[idx[k]] = sess
+                    rows.append([idx[k], j, sid, 0, cols[j] >= 0])
+                post_pos = 0
+            if sess is not None:
+                sess.advance(first_steps if sess.n_advances == 0 else later_steps)
+                if sess.final_frames > post_pos:
+                    sess.postnet(post_pos, sess.final_frames)
+                    post_pos = sess.final_frames
+                mel_post = sess.mel_post
+                for row in rows:
+                    i, j, sid, sent, cut = row
+                    if sid is None:
+                        continue
+                    final, row_ended, n_end, row_len = sess.rows[j]
+                    if final > sent:
+                        sv.append(sid, mel_post[j, :, sent:final])
+                        row[3] = sent = final
+                    if row_ended and sent == n_end:             # (n_end is the row's length where it has no cut)
+                        if cut:
+                            if n_end == 0:                       # an empty cut: what tts_single does with it
+                                truncate_mel(mel_post[j, :, :row_len], sess.alignments[j, :row_len, int(sess._keep[3][j])])
+                            sv.append(sid, mel_post[j, :, n_end - 1:n_end].expand(-1, 3))
+                        sv.finish(sid)
+                        row[2] = None
+                if sess.ended:
+                    assert all(row[2] is None for row in rows)
+                    sess, rows = None, []
+            chunks = sv.step()
+            for sid, chunk, last in chunks:
+                i = line_of.pop(sid) if last else line_of[sid]
+                yield chunk.cpu() if single else (i, chunk.cpu(), last)
+            if sess is None and not todo and not line_of:
+                return
 
     def tts(self, text_buckw: Union[str, List[str]], speed: Union[int, float, None] = None, denoise: float = 0.005,
             speaker_id: int = 0, batch_size: int = 8, vowelizer=None, postprocess_mel: bool = True,

@@ -67,3 +67,22 @@ class Tacotron2MS(_HipModule):
         alignments [B, T, L]) with T = max(mel_lengths)   (tacotron2_ms.py:279-332)."""
         return self.engine().infer(tokens, speaker_ids, lengths, max_step=self.decoder_max_step,
                                    dropout_seed=self.dropout_seed)
+
+    @torch.inference_mode()
+    def infer_stream(self, tokens: Tensor, speaker_ids: Optional[Tensor] = None, lengths: Optional[Tensor] = None,
+                     chunk_steps: int = 64):
+        """`infer` as a generator (not in the reference): the decoder runs in advances of chunk_steps steps (rounded up to 8) and every
+        turn yields (t0, t1, mel_postnet[:, :, t0:t1], session) for the frames that became final -- the postnet reads 10 frames on each
+        side, so they trail the decoder by that until the end.  Put together, the frames are infer()'s mel_postnet (within fp32
+        summation order of the postnet's windows; the decoder's own frames, session.mel_raw, bit for bit); after the last yield
+        session.mel_lens and session.alignments are infer()'s other two results."""
+        n = -(-int(chunk_steps) // 8) * 8
+        sess = self.engine().stream(tokens, speaker_ids, lengths, max_step=self.decoder_max_step, dropout_seed=self.dropout_seed,
+                                    max_chunk_steps=n)
+        t0 = 0
+        while not sess.ended:
+            sess.advance(n)
+            t1 = sess.final_frames
+            if t1 > t0:
+                yield t0, t1, sess.postnet(t0, t1), sess
+                t0 = t1

@@ -626,6 +626,134 @@ class Tacotron2Engine:
             return mel_post[:, :, :T], mel_lens, align[:, :T], mel_raw[:, :, :T]
         return mel_post[:, :, :T], mel_lens, align[:, :T]
 
+    @property
+    def postnet_halo(self):
+        """frames an output frame of the postnet reads on each side: ttsamd_tacotron2_postnet_halo_frames (10)"""
+        halo = C.c_int32(0)
+        L.check(self.lib.ttsamd_tacotron2_postnet_halo_frames(self.handle, C.byref(halo)), 'tacotron2_postnet_halo_frames')
+        return halo.value
+
+    def stream(self, tokens, speaker_ids=None, lengths=None, max_step=None, dropout_seed=-1, max_chunk_steps=64, cut_columns=None,
+               rows_to_batch_end=False):
+        """The decode of infer() as a session of advances -> Tacotron2Stream (advance(n), postnet(t0, t1), mel_raw, alignments,
+        mel_lens, steps_done, ended).  Arguments as infer(); max_chunk_steps: the longest advance (a multiple of 8) -- the workspace
+        is sized by it, not by max_step; cut_columns (a list or tensor of B ints, < 0 = none): per row the token column of the
+        wrapper's end-of-utterance cut, whose causal bound every advance reports (Tacotron2Stream.rows); rows_to_batch_end: rows end
+        with the batch (ttmel_single's rule) instead of at their own mel_lens."""
+        return Tacotron2Stream(self, tokens, speaker_ids, lengths, max_step, dropout_seed, max_chunk_steps, cut_columns, rows_to_batch_end)
+
+
+class Tacotron2Stream:
+    """One streaming decode (ttsamd_tacotron2_stream_*): `advance(n)` runs n more decoder steps of the loop infer() runs -- the frames
+    in mel_raw[:, :, :steps_done], alignments[:, :steps_done] and mel_lens are infer()'s bit for bit --, `postnet(t0, t1)` the postnet
+    over a window of final frames.  After every advance: `steps_done`, `ended`, and `rows`, per row (final_frames, row_ended, n_end,
+    row_length) as include/ttsamd.h describes them.  The session owns its buffers; close() (or the garbage collector) ends it."""
+
+    def __init__(self, eng, tokens, speaker_ids, lengths, max_step, dropout_seed, max_chunk_steps, cut_columns, rows_to_batch_end):
+        _check_ids(tokens, eng.config['n_symbol'], 'Tacotron2 tokens')
+        if speaker_ids is not None and eng.config['num_speakers'] > 1:
+            _check_ids(speaker_ids, eng.config['num_speakers'], 'Tacotron2 speaker_ids')
+        self.eng, self.lib, dev = eng, eng.lib, eng.device
+        self._session = None
+        tokens = tokens.to(device=dev, dtype=torch.int64).contiguous()
+        B, Ltok = tokens.shape
+        if lengths is None:
+            lengths = torch.full((B,), Ltok, dtype=torch.int64)
+        lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+        if eng.config['num_speakers'] > 1:
+            if speaker_ids is None:
+                speaker_ids = torch.zeros(B, dtype=torch.int64)
+            speaker_ids = speaker_ids.to(device=dev, dtype=torch.int64).contiguous()
+        else:
+            speaker_ids = None
+        max_step = int(eng.max_decoder_steps if max_step is None else max_step)
+        max_chunk_steps = int(max_chunk_steps)
+        if max_chunk_steps < 8 or max_chunk_steps % 8:
+            raise ValueError(f'Tacotron2Engine.stream: max_chunk_steps {max_chunk_steps} must be a positive multiple of 8')
+        if dropout_seed is None:
+            dropout_seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        cols = None
+        if cut_columns is not None:
+            cols = torch.as_tensor(cut_columns).to(dtype=torch.int32).reshape(-1)
+            if cols.numel() != B:
+                raise ValueError(f'Tacotron2Engine.stream: cut_columns has {cols.numel()} entries for {B} rows')
+            if int(cols.max()) >= Ltok:
+                raise ValueError(f'Tacotron2Engine.stream: cut column {int(cols.max())} outside the {Ltok} tokens')
+            cols = cols.to(dev).contiguous()
+        self.B, self.n_tokens, self.max_step, self.max_chunk_steps = B, Ltok, max_step, max_chunk_steps
+        self.halo = eng.postnet_halo
+        self._keep = (tokens, lengths, speaker_ids, cols)        # the session reads `lengths` at every advance
+        self._mel_raw = torch.zeros(B, eng.n_mels, max_step, dtype=torch.float32, device=dev)
+        self._mel_post = torch.zeros(B, eng.n_mels, max_step, dtype=torch.float32, device=dev)
+        self.mel_lens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._align = torch.zeros(B, max_step, Ltok, dtype=torch.float32, device=dev)
+        self.steps_done, self.ended, self.n_advances = 0, False, 0
+        self.rows = [(0, 0, 0, 0)] * B
+        self._post_ws = _Workspace()
+        session = C.c_void_p()
+        with torch.cuda.device(dev):
+            nb = self.lib.ttsamd_tacotron2_stream_bytes(eng.handle, B, Ltok, max_step, max_chunk_steps)
+            self._ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)       # the session's own: it lives across calls
+            L.check(self.lib.ttsamd_tacotron2_stream_begin(eng.handle, _ptr(tokens), _ptr(lengths), _ptr(speaker_ids), B, Ltok, max_step,
+                                                           max_chunk_steps, int(dropout_seed), _ptr(cols), int(bool(rows_to_batch_end)),
+                                                           _ptr(self._mel_raw), _ptr(self.mel_lens), _ptr(self._align), _ptr(self._ws), nb,
+                                                           C.byref(session), _stream()), 'tacotron2_stream_begin')
+        self._session = session
+
+    def close(self):
+        if getattr(self, '_session', None):
+            self.lib.ttsamd_tacotron2_stream_end(self._session)
+            self._session = None
+
+    __del__ = close
+
+    @property
+    def mel_raw(self):
+        """[B, n_mels, steps_done]: the decoder's frames so far, before the postnet"""
+        return self._mel_raw[:, :, :self.steps_done]
+
+    @property
+    def alignments(self):
+        """[B, steps_done, n_tokens]"""
+        return self._align[:, :self.steps_done]
+
+    @property
+    def mel_post(self):
+        """[B, n_mels, steps_done]: valid where postnet() windows have written"""
+        return self._mel_post[:, :, :self.steps_done]
+
+    def advance(self, n_steps):
+        """n_steps more decoder steps (a multiple of 8, at most max_chunk_steps; clipped to max_step) -> (steps_done, ended).  The
+        call waits for them.  ValueError after the session has ended."""
+        if self._session is None or self.ended:
+            raise ValueError('Tacotron2Stream.advance: the session has ended')
+        done, ended = C.c_int32(0), C.c_int32(0)
+        rows = (C.c_int32 * (4 * self.B))()
+        with torch.cuda.device(self.eng.device):
+            L.check(self.lib.ttsamd_tacotron2_stream_advance(self._session, int(n_steps), C.byref(done), C.byref(ended), rows, _stream()),
+                    'tacotron2_stream_advance')
+        self.steps_done, self.ended = done.value, bool(ended.value)
+        self.n_advances += 1
+        self.rows = [tuple(rows[4 * b:4 * b + 4]) for b in range(self.B)]
+        return self.steps_done, self.ended
+
+    @property
+    def final_frames(self):
+        """frames [0, n) whose postnet output cannot change any more, for the whole batch: steps_done - halo, or steps_done once ended"""
+        return self.steps_done if self.ended else max(self.steps_done - self.halo, 0)
+
+    def postnet(self, t0, t1):
+        """mel_post[:, :, t0:t1] -> that view, from the raw frames [t0 - halo, t1 + halo) inside [0, steps_done); the frames must be
+        final (t1 <= final_frames), otherwise the library refuses the call."""
+        t0, t1 = int(t0), int(t1)
+        with torch.cuda.device(self.eng.device):
+            nb = self.lib.ttsamd_tacotron2_postnet_window_bytes(self.eng.handle, self.B, max(t1 - t0, 1))
+            ws = self._post_ws.get(nb, self.eng.device)
+            L.check(self.lib.ttsamd_tacotron2_postnet_window(self.eng.handle, _ptr(self._mel_raw), _ptr(self._mel_post), self.B, self.max_step,
+                                                             self.steps_done, t0, t1, int(self.ended), _ptr(ws), nb, _stream()),
+                    'tacotron2_postnet_window')
+        return self._mel_post[:, :, t0:t1]
+
 
 class TaggerEngine:
     """Handle over ttsamd_tagger_* (replaces Shakkelha.forward / Shakkala.forward of models/diacritizers)."""

@@ -185,6 +185,15 @@ SYMBOLS = {
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),
     'ttsamd_tacotron2_infer': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I64, _P, _P, _P, _P,
                                       C.POINTER(_I32), _P, _I64, _P]),
+    # the same decode as a session of advances (csrc/tacotron2.hip); steps_done, ended and the row report are HOST int32
+    'ttsamd_tacotron2_stream_bytes': (_I64, [_P, _I32, _I32, _I32, _I32]),
+    'ttsamd_tacotron2_stream_begin': (_I32, [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I64, _P, _I32, _P, _P, _P, _P, _I64,
+                                             C.POINTER(_P), _P]),
+    'ttsamd_tacotron2_stream_advance': (_I32, [_P, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _P]),
+    'ttsamd_tacotron2_stream_end': (_I32, [_P]),
+    'ttsamd_tacotron2_postnet_halo_frames': (_I32, [_P, C.POINTER(_I32)]),
+    'ttsamd_tacotron2_postnet_window_bytes': (_I64, [_P, _I32, _I32]),
+    'ttsamd_tacotron2_postnet_window': (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I64, _P]),
     'ttsamd_tagger_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(TaggerCfg), C.POINTER(_P)]),
     'ttsamd_tagger_destroy': (_I32, [_P]),
     'ttsamd_tagger_workspace_bytes': (_I64, [_P, _I32, _I32]),

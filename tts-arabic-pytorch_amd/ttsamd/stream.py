@@ -12,6 +12,10 @@ convolutions with a per-frame LayerNorm, its head an ISTFT whose frames overlap 
 ttsamd_vocos_forward_windows -> emit; the bias denoise is a per-frame spectral subtraction inside that call (no Denoiser, no halo of its
 own).  The "center" framing of '24k' gives an utterance of T frames 256 (T - 1) samples: `plan_chunks_center` cuts those.
 
+A stream may grow (Tacotron2 makes its mel frame by frame: `open_growing` / `append` / `finish`).  `next_growing_chunk` releases a core
+as soon as enough frames are known behind it that it is a core of `plan_chunks` of the final length with a complete window, so the
+chunks -- and with them the denoiser halo, the resampler, the limiter's carried samples -- are those of open() on the whole mel.
+
 Levelling inside a stream: with `limiter=` a step runs vocoder -> denoise -> ttsamd_wave_limit (mode 3: the stream's fixed gain in dB and
 the look-ahead limiter, in place on the window rows) -> emit.  A limited sample depends on the input over [i - A - R, i + 2A] only, so
 the windows widen by that reach in frames (`limiter_halo_frames`), as they widen by the resampler's, and the curve is integer
@@ -131,6 +135,38 @@ def plan_chunks(T, first_chunk_frames, chunk_frames, halo_left, halo_right):
     return plan
 
 
+def growing_lookahead(chunk_frames, halo_right):
+    """the frames a growing stream must know behind a core before it may release it while the end is unknown:
+    max(chunk_frames // 2, halo_right, 1).  The first term: the rest of the utterance is then at least chunk_frames // 2 frames, so
+    plan_chunks would not fold it into this core; the second: the core's window is complete and does not touch the utterance's end;
+    the 1 (it only matters with chunk_frames = 1 and no halo): the last core is never released before the end is known, so every
+    stream has a chunk left to carry `last`."""
+    return max(int(chunk_frames) // 2, int(halo_right), 1)
+
+
+def next_growing_chunk(pos, known_frames, ended, first_chunk_frames, chunk_frames, halo_left, halo_right):
+    """The planner of a stream whose length is not known when it opens: the next (core_start, core_len, win_start, win_len) of an
+    utterance whose released cores cover [0, pos), of which `known_frames` frames have arrived and whose end is known (`ended`: the
+    utterance has known_frames frames) or not -- or None while that chunk may not be released yet (and when nothing is left).
+    Whatever the arrival schedule, the chunks released are plan_chunks(T, ...) of the final T, in order: with the end known, the core
+    at `pos` of that plan; without, the nominal core [pos, pos + n) once known_frames >= pos + n + growing_lookahead(...)."""
+    pos, known, first, chunk, hl, hr = int(pos), int(known_frames), int(first_chunk_frames), int(chunk_frames), int(halo_left), int(halo_right)
+    if pos < 0 or known < pos or first < 1 or chunk < 1 or hl < 0 or hr < 0:
+        raise ValueError(f'next_growing_chunk: pos {pos}, known_frames {known}, first_chunk_frames {first}, chunk_frames {chunk}, halos {hl} / {hr}')
+    if ended:
+        if pos >= known:
+            return None
+        for c in plan_chunks(known, first, chunk, hl, hr):
+            if c[0] == pos:
+                return c
+        raise ValueError(f'next_growing_chunk: no core of plan_chunks({known}, ...) starts at {pos}')
+    n = first if pos == 0 else chunk
+    if known < pos + n + growing_lookahead(chunk, hr):
+        return None
+    ws = pos - min(hl, pos)
+    return (pos, n, ws, pos + n + hr - ws)
+
+
 def plan_chunks_center(T, first_chunk_frames, chunk_frames, halo_left, halo_right):
     """plan_chunks for the "center" framing (MelVocos '24k'), where an utterance of T >= 2 mel frames has hop * (T - 1) samples:
     [(core_start, core_len, win_start, win_len)] with the cores in frames of hop SAMPLES, partitioning [0, T - 1) by plan_chunks' rule
@@ -152,11 +188,13 @@ def max_core_frames(first_chunk_frames, chunk_frames):
 
 
 class _Open:
-    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise', 'frames', 'gain_db', 'lim_end')
+    __slots__ = ('sid', 'slot', 'plan', 'next', 'denoise', 'frames', 'gain_db', 'lim_end', 'growing', 'ended', 'pos', 'halos')
 
     def __init__(self, sid, slot, plan, denoise, frames, gain_db=0.0):
         self.sid, self.slot, self.plan, self.next, self.denoise, self.frames, self.gain_db = sid, slot, plan, 0, denoise, frames, gain_db
         self.lim_end = 0                # samples of the utterance whose value in front of the limiter is settled (see _carry)
+        # a growing stream (open_growing): `plan` is None, `frames` the frames that have arrived, `pos` the end of the released cores
+        self.growing, self.ended, self.pos, self.halos = False, True, 0, None
 
 
 class StreamingVocoder:
@@ -335,6 +373,77 @@ class StreamingVocoder:
         self._open[sid] = _Open(sid, slot, plan, denoise, T - 1 if self._center else T, gain_db)        # frames of hop samples
         return sid
 
+    def first_release_frames(self, denoise=0.0):
+        """the frames a growing stream opened with this denoise strength needs before step() releases its first chunk while its end is
+        unknown: first_chunk_frames + growing_lookahead over the right halo in total (vocoder, denoiser, resampler, limiter)"""
+        halo = (self._dn_halo if float(denoise) > 0 and not self._vocos else 0) + self._rs_halo
+        return self.first_chunk_frames + growing_lookahead(self.chunk_frames, self._halo[1] + halo)
+
+    def open_growing(self, denoise=0.0, gain_db=0.0):
+        """A stream whose length is not known when it opens -> sid: `append` its frames as they come, `finish` it at its end.  step()
+        returns its next chunk as soon as the planner may release it (`next_growing_chunk`) and skips it otherwise; the chunks are those
+        of open() on the whole mel, bit for bit, because the cores and windows are the same.  denoise / gain_db and their ValueErrors
+        as open(); the short-utterance check of the denoiser falls at finish(), where the length is known.  The centred framing
+        (MelVocos '24k') is refused: its last core reads one frame past its end."""
+        if self._center:
+            raise ValueError("StreamingVocoder.open_growing: the centred framing (MelVocos '24k') is not supported for growing streams")
+        denoise, gain_db = float(denoise), float(gain_db)
+        if not np.isfinite(denoise):
+            raise ValueError(f'StreamingVocoder.open_growing: denoise {denoise!r} is not finite')
+        if not np.isfinite(gain_db):
+            raise ValueError(f'StreamingVocoder.open_growing: gain_db {gain_db!r} is not finite')
+        if gain_db != 0.0 and self._lim is None:
+            raise ValueError('StreamingVocoder.open_growing: gain_db needs the limiter (StreamingVocoder(..., limiter=True)): a gain alone could clip')
+        if self._vocos and denoise < 0:
+            raise ValueError(f'StreamingVocoder.open_growing: denoise {denoise!r} is negative')
+        if not self._vocos and denoise > 0 and self._dn_eng is None:
+            raise ValueError('StreamingVocoder.open_growing: denoise > 0 needs the denoiser (StreamingVocoder(vocoder, denoiser=...))')
+        if not self._free:
+            raise ValueError(f'StreamingVocoder.open_growing: all {self.max_streams} slots are taken (max_streams)')
+        halo = (self._dn_halo if denoise > 0 and not self._vocos else 0) + self._rs_halo
+        sid = self._next_sid
+        self._next_sid += 1
+        st = _Open(sid, self._free.pop(0), None, denoise, 0, gain_db)
+        st.growing, st.ended, st.halos = True, False, (self._halo[0] + halo, self._halo[1] + halo)
+        self._open[sid] = st
+        return sid
+
+    def append(self, sid, frames):
+        """frames [num_mels, n] (a device tensor: copied device to device behind the stream's frames so far); n = 0 is allowed.
+        KeyError: sid is not open; ValueError: not a growing stream, already finished, a wrong shape, more than max_frames in all."""
+        import torch
+        st = self._open[sid]
+        if not st.growing or st.ended:
+            raise ValueError(f'StreamingVocoder.append: stream {sid} is not a growing stream that is still open for frames')
+        frames = torch.as_tensor(frames)
+        if frames.dim() != 2 or frames.shape[0] != self.num_mels:
+            raise ValueError(f'StreamingVocoder.append: frames must be [{self.num_mels}, n], got {tuple(frames.shape)}')
+        n = int(frames.shape[1])
+        if st.frames + n > self.max_frames:
+            raise ValueError(f'StreamingVocoder.append: {st.frames + n} frames, the pool holds utterances of up to max_frames = {self.max_frames}')
+        if n:
+            self._pool[st.slot, :, st.frames:st.frames + n].copy_(frames.to(dtype=torch.float32), non_blocking=True)
+            st.frames += n
+
+    def finish(self, sid):
+        """The stream has all its frames: its remaining chunks follow, the last one marked.  ValueError: no frame at all, or denoise > 0
+        on an utterance of at most 512 samples (as open() and the one-shot Denoiser)."""
+        st = self._open[sid]
+        if not st.growing or st.ended:
+            raise ValueError(f'StreamingVocoder.finish: stream {sid} is not a growing stream that is still open for frames')
+        if st.frames < 1:
+            raise ValueError(f'StreamingVocoder.finish: stream {sid} has no frames')
+        if not self._vocos and st.denoise > 0 and self.hop * st.frames <= 512:
+            raise ValueError('Denoiser: every utterance needs more than 512 samples (reflect padding of n_fft/2); '
+                             f'shortest has {self.hop * st.frames}')
+        st.ended = True
+
+    def _next_chunk(self, st):
+        """the chunk step() takes next from an open stream, or None (a growing stream that has to wait for frames)"""
+        if not st.growing:
+            return st.plan[st.next]
+        return next_growing_chunk(st.pos, st.frames, st.ended, self.first_chunk_frames, self.chunk_frames, *st.halos)
+
     def _carry(self, rows, chunks, w_max):
         """The vocoder's fp32 sums for one sample differ in their last bits from window to window, and the limiter's curve at a chunk's
         edge depends on samples of the neighbouring cores.  So that the chunks are the limiter's bits on ONE wave, a sample's value in
@@ -373,7 +482,8 @@ class StreamingVocoder:
         self._free.append(self._open.pop(sid).slot)
 
     def step(self):
-        """The next chunk of every open utterance, oldest first, at most 64 -> [(sid, chunk, last)]: chunk is a device tensor of
+        """The next chunk of every open utterance whose next window is ready (a growing stream that waits for frames is skipped and stays
+        open), oldest first, at most 64 -> [(sid, chunk, last)]: chunk is a device tensor of
         hop * core_len samples (float32, or int16 with pcm16) -- at another sample_rate, of the resampler's outputs that belong to the
         core (`chunk_outputs`: float32, int16, or uint8 for G.711) --, valid until the step after next; `last` marks an utterance's
         final chunk, after which it is closed.  One gather, one vocoder forward, one denoise (when a row asks for it) and one emit on
@@ -381,12 +491,12 @@ class StreamingVocoder:
         ttsamd_vocos_forward_windows (whose head runs only on the core, widened by the resampler's reach), one emit."""
         import torch
         from .engine import _ptr, _stream
-        rows = list(self._open.values())[:self._rows]
-        if not rows:
-            return []
+        ready = [(st, c) for st, c in ((st, self._next_chunk(st)) for st in self._open.values()) if c is not None][:self._rows]
+        if not ready:
+            return []               # nothing open, or only growing streams that wait for frames: they stay open
+        rows, chunks = [st for st, _ in ready], [c for _, c in ready]
         W = len(rows)
         i32 = C.c_int32 * W
-        chunks = [st.plan[st.next] for st in rows]
         w_max = (max(c[3] for c in chunks) + 3) & ~3
         if self._resampled:
             o, n = self._rs[:2] if self._rs else (1, 1)
@@ -458,7 +568,8 @@ class StreamingVocoder:
         res = []
         for w, (st, c) in enumerate(zip(rows, chunks)):
             st.next += 1
-            last = st.next == len(st.plan)
+            st.pos = c[0] + c[1]
+            last = st.ended and st.pos == st.frames if st.growing else st.next == len(st.plan)
             res.append((st.sid, view[w, :counts[w]], last))
             if last:
                 self.close(st.sid)
