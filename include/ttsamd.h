@@ -737,6 +737,14 @@ int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const fl
                              int32_t channels, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L,
                              int32_t batch, int32_t mode, float div, float slope, int32_t variant, float* packed, int64_t packed_floats,
                              void* stream);
+/* Asks without launching (new symbol, added WITHOUT a bump; host only, needs no GPU): what ttsamd_hifigan_forward launches under the
+ * current options and precision for the c1 -> c2 pair of a ResBlock1 with C channels, kernel size k and this dilation at a stage of L
+ * positions per row and `batch` rows, packed as ttsamd_hifigan_create packs it, on 16-byte aligned, distinct buffers.  *kernel: 0 two
+ * conv launches (ttsamd_conv1d_route says which), 1 first-generation fused pair, 2 second generation (*ntw = 2 / 1: 256- / 128-column
+ * blocks; *wino_phases = 0 / 1 / 2: none, conv 2, both convs on Winograd F(2,3)), 3 both convs on Winograd F(4,3) (*points = 6 / 7:
+ * six- / seven-point groups).  *name: the kind TTSAMD_CONV_LOG records for the launch ("" for kernel 0; a static string). */
+int32_t ttsamd_resblock_pair_route(int32_t batch, int32_t channels, int32_t k, int32_t dilation, int32_t L, int32_t* kernel, int32_t* ntw,
+                                   int32_t* wino_phases, int32_t* points, const char** name);
 
 /* One ResBlock2 (vocoder/hifigan/models.py:62-83) in exact fp32:
  *   x1 = x + conv1d(lrelu(x, slope), w1, dilation dil1) + b1;  v = x1 + conv1d(lrelu(x1, slope), w2, dilation dil2) + b2;

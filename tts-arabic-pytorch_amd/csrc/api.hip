@@ -1067,63 +1067,55 @@ int32_t ttsamd_resblock_pair(const float* x, float* y, const float* w1, const fl
                 "resblock_pair: `packed` holds %lld floats, variant %d at C = %d, k = %d needs %lld (ttsamd_resblock_pair_packed_floats)",
                 (long long)packed_floats, variant, channels, k, (long long)ttsamd_resblock_pair_packed_floats(channels, k, variant));
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n = (int64_t)channels * k * channels;
-    for (int i = 0; i < 2; ++i) {
-        hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, i == 0 ? w1 : w2, channels,
-                           channels, k, channels, packed + i * n);
-        TTS_CHECK_HIP(hipGetLastError());
-    }
-    const double fl = 2.0 * (2.0 * channels * channels * k);
-    int32_t rc;
-    prof_begin(s, fl);
-    if (variant == 1) {
-        rc = launch_fused_pair(channels, x, y, packed, b1, packed + n, b2, k, dil, lens, len_mul, L, batch, mode, div, slope, s);
-    } else if (variant >= 2 && variant <= 5) {
-        const float *w2w = nullptr, *w1w = nullptr;
-        if (variant >= 4) {       // 256-column blocks with phase B (4) or both phases (5) on Winograd F(2,3): the groups behind the direct packings
-            TTS_REQUIRE((k == 3 || k == 7 || k == 11) && (channels <= 64 || (variant == 5 && channels == 128)),
-                        "resblock_pair: variants 4 / 5 are built for C = 32 / 64 (5: and 128), k = 3 / 7 / 11");
-            const int64_t nw = (int64_t)channels * wino2_groups(k) * channels;
-            for (int i = 0; i < (variant == 5 ? 2 : 1); ++i) {
-                float* wino = packed + 2 * n + i * nw;
-                hipLaunchKernelGGL(pack_wino2_weight_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, i == 0 ? w2 : w1, channels,
-                                   channels, k, channels, wino);
-                TTS_CHECK_HIP(hipGetLastError());
-                (i == 0 ? w2w : w1w) = wino;
-            }
-        }
-        rc = launch_fused_pair2(channels, x, y, packed, b1, packed + n, b2, k, dil, lens, len_mul, L, batch, mode, div, slope,
-                                variant == 3 ? 1 : 2, s, w2w, w1w);
-    } else if (variant == 6) {
-        // C = 32, both convs on Winograd F(4,3) (resblock_pair4.hip): the group filters behind the direct packings
+    // every form the variant reads, re-laid out on the device into `packed` one behind the other: the two direct packings, then the
+    // variant's group filters; then its route through the dispatch hifigan_forward uses
+    PairConv c[2] = {{nullptr, b1, nullptr, nullptr, nullptr}, {nullptr, b2, nullptr, nullptr, nullptr}};
+    float* next = packed;
+    const auto pack = [&](void (*kernel)(const float*, int, int, int, int, float*), int groups, const float* w, const float*& form) {
+        const int64_t nw = (int64_t)channels * groups * channels;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w, channels, channels, k, channels, next);
+        form = next;
+        next += nw;
+        return hipGetLastError();
+    };
+    TTS_CHECK_HIP(pack(pack_conv_weight_kernel, k, w1, c[0].w));
+    TTS_CHECK_HIP(pack(pack_conv_weight_kernel, k, w2, c[1].w));
+    prof_begin(s, 2.0 * (2.0 * channels * channels * k));
+    int32_t rc = 0;
+    if (variant == 4 || variant == 5) {       // 256-column blocks with phase B (4) or both phases (5) on Winograd F(2,3): conv 2's groups, then conv 1's
+        TTS_REQUIRE((k == 3 || k == 7 || k == 11) && (channels <= 64 || (variant == 5 && channels == 128)),
+                    "resblock_pair: variants 4 / 5 are built for C = 32 / 64 (5: and 128), k = 3 / 7 / 11");
+        TTS_CHECK_HIP(pack(pack_wino2_weight_kernel, wino2_groups(k), w2, c[1].w_wino2));
+        if (variant == 5) TTS_CHECK_HIP(pack(pack_wino2_weight_kernel, wino2_groups(k), w1, c[0].w_wino2));
+    } else if (variant == 6) {                // C = 32, both convs on Winograd F(4,3) (resblock_pair4.hip)
         TTS_REQUIRE(channels == 32 && (k == 3 || k == 7 || k == 11), "resblock_pair: variant 6 is built for C = 32, k = 3 / 7 / 11");
-        const int64_t nw4 = (int64_t)channels * wino4_groups(k) * channels;
-        for (int i = 0; i < 2; ++i) {
-            hipLaunchKernelGGL(pack_wino4_weight_kernel, dim3((unsigned)((nw4 + 255) / 256)), dim3(256), 0, s, i == 0 ? w1 : w2, channels,
-                               channels, k, channels, packed + 2 * n + i * nw4);
-            TTS_CHECK_HIP(hipGetLastError());
-        }
-        rc = launch_fused_pair4(channels, x, y, packed + 2 * n, b1, packed + 2 * n + nw4, b2, k, dil, lens, len_mul, L, batch, mode, div,
-                                slope, s);
-    } else if (variant == 7) {
-        // ... both convs on seven-point groups (13 / 20 products per quad)
+        TTS_CHECK_HIP(pack(pack_wino4_weight_kernel, wino4_groups(k), w1, c[0].w_wino4));
+        TTS_CHECK_HIP(pack(pack_wino4_weight_kernel, wino4_groups(k), w2, c[1].w_wino4));
+    } else if (variant == 7) {                // ... both convs on seven-point groups (13 / 20 products per quad)
         TTS_REQUIRE(channels == 32 && (k == 7 || k == 11), "resblock_pair: variant 7 is built for C = 32, k = 7 / 11");
-        const int64_t nw44 = (int64_t)channels * wino44_groups(k) * channels;
-        for (int i = 0; i < 2; ++i) {
-            hipLaunchKernelGGL(pack_wino44_weight_kernel, dim3((unsigned)((nw44 + 255) / 256)), dim3(256), 0, s, i == 0 ? w1 : w2, channels,
-                               channels, k, channels, packed + 2 * n + i * nw44);
-            TTS_CHECK_HIP(hipGetLastError());
-        }
-        rc = launch_fused_pair4(channels, x, y, packed + 2 * n, b1, packed + 2 * n + nw44, b2, k, dil, lens, len_mul, L, batch, mode, div,
-                                slope, s, 7);
-    } else if (variant == -1) {
-        rc = 0;                                    // the two weight re-layout launches only (tools/fused_pair_bench.py subtracts them)
-    } else {
+        TTS_CHECK_HIP(pack(pack_wino44_weight_kernel, wino44_groups(k), w1, c[0].w_wino44));
+        TTS_CHECK_HIP(pack(pack_wino44_weight_kernel, wino44_groups(k), w2, c[1].w_wino44));
+    } else if (variant != -1 && (variant < 1 || variant > 3)) {
         set_error("resblock_pair: variant %d (1: first generation, 2 / 3: second generation with 256- / 128-column blocks, 4 / 5: 256 columns + Winograd phase B / both phases, 6: C = 32 with both phases on Winograd F(4,3), 7: ... on its seven-point groups, k = 7 / 11)", variant);
         rc = TTSAMD_EINVAL;
     }
+    // (variant -1: the two weight re-layout launches only -- tools/fused_pair_bench.py subtracts them)
+    if (rc == 0 && variant != -1)
+        rc = launch_pair(pair_route_of_variant(variant, channels, dil),
+                         PairArgs{channels, k, dil, x, y, c[0], c[1], lens, len_mul, L, batch, mode, div, slope}, s);
     prof_end(s);
     return rc;
+}
+
+int32_t ttsamd_resblock_pair_route(int32_t batch, int32_t channels, int32_t k, int32_t dilation, int32_t L, int32_t* kernel, int32_t* ntw,
+                                   int32_t* wino_phases, int32_t* points, const char** name) {
+    TTS_REQUIRE(kernel && ntw && wino_phases && points && name, "resblock_pair_route: null argument");
+    TTS_REQUIRE(batch >= 1 && channels >= 1 && k >= 1 && dilation >= 1 && L >= 1, "resblock_pair_route: bad shape");
+    float* const any = reinterpret_cast<float*>((uintptr_t)256);   // stand for the two buffers: 16-byte aligned, distinct, never followed
+    const PairRoute r = pair_route(PairShape{channels, k, dilation, L, batch, true, any, any + 64, hifigan_conv_forms(channels, channels, k),
+                                             default_precision()}, pair_route_opts());
+    *kernel = r.kernel; *ntw = r.ntw; *wino_phases = r.wm; *points = r.points; *name = r.name;
+    return 0;
 }
 
 int64_t ttsamd_resblock2_packed_floats(int32_t channels, int32_t k, int32_t variant) {

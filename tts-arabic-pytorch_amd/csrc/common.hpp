@@ -229,27 +229,42 @@ bool convt_wino_packable(int cin, int cout, int u);
 void pack_convt_wino_weight(const float* w, const float* bias, int cin, int cout, int u, float* out_w, float* out_bias);
 bool convt_wino_supported(const ConvParams& p, const float* w_wino, const float* bias_wino);
 int32_t launch_convt_wino(const ConvParams& p, const float* w_wino, const float* bias_wino, hipStream_t stream);
-// One launch for a c1 -> c2 pair of a C = 32 ResBlock1 with the intermediate in LDS (resblock_fused.hip); x != y.
+// Routing of an exact-fp32 c1 -> c2 pair of a ResBlock1 (conv_route.hip): which of the three fused kernels takes it as ONE launch with
+// the intermediate in LDS, and in which form -- decided once per pair, by a function that launches nothing.  launch_pair executes the
+// answer; hifigan_forward and ttsamd_resblock_pair both go through it, ttsamd_resblock_pair_route asks without launching.
+struct PairRouteOpts { int fused_pair, fused2, fused2_mask, fused2_mask_n1, fused2_wb, pair4; };   // fused2_mask < 0: not forced (the default mask)
+struct ConvForms { bool wino2, wino4, wino44; };   // the Winograd forms a conv carries: F(2,3) groups, F(4,3) six-point, seven-point
+// The pair: L positions per row (after the stage's upsampling), batch rows; square: c1 and c2 are both C -> C convs of the same k; x / y
+// for their alignment and distinctness only, never followed; forms: what BOTH convs carry
+struct PairShape { int32_t channels, k, dil, L, batch; bool square; const float *x, *y; ConvForms forms; int32_t precision; };
+enum PairKernel : int32_t { PAIR_NONE = 0, PAIR_GEN1 = 1, PAIR_GEN2 = 2, PAIR_F43 = 3 };   // two launch_conv calls / resblock_pair / resblock_pair2 / resblock_pair4
+// ntw, wm (resblock_pair2): 2 / 1 = 256- / 128-column blocks; phases on Winograd F(2,3), 0 none, 1 phase B (conv 2), 2 both.  points
+// (resblock_pair4): 6 / 7 = six- / seven-point groups.  name: what the launch is logged under (TTSAMD_CONV_LOG); "" for PAIR_NONE
+struct PairRoute { int32_t kernel, ntw, wm, points; const char* name; };
+PairRouteOpts pair_route_opts();                                   // the only place the pair path calls opt_int for these six
+PairRoute pair_route(const PairShape& s, const PairRouteOpts& o);  // pure: no opt_int, no globals, no HIP call, no allocation
+PairRoute pair_route_of_variant(int32_t variant, int32_t channels, int32_t dil);   // the forced routes of ttsamd_resblock_pair (variant 1..7)
+bool pair2_phases_built(int32_t channels, int32_t dil, int32_t ntw, int32_t wm);   // resblock_pair2<.., ntw, wm> exists for this pair
+ConvForms hifigan_conv_forms(int cin, int cout, int k);            // what hifigan_create packs for a conv besides the direct layout
+// one conv of a pair in every form it was packed in (nullptr = not packed); the route says which ones the launch reads
+struct PairConv { const float *w, *b, *w_wino2, *w_wino4, *w_wino44; };
+// one pair launch: v = x + conv(lrelu(conv(lrelu(x), c1, dil) + b1), c2) + b2;  y = v | y + v | (y + v) / div by mode 0 | 1 | 2.  x != y
+struct PairArgs { int32_t channels, k, dil; const float* x; float* y; PairConv c1, c2; const int64_t* lens; int32_t len_mul, L, batch, mode; float div, slope; };
+int32_t launch_pair(const PairRoute& r, const PairArgs& a, hipStream_t stream);
+// The three kernels: the geometry each is built for (pair_route and the launcher's own argument check ask), and the launcher.
+// First generation (resblock_fused.hip): C = 32, k = 3 / 7 / 11 and C = 64, k = 3.
 bool fused_pair_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
-int32_t launch_fused_pair(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
-                          const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                          int32_t mode, float div, float slope, hipStream_t stream);
-// Second generation of the fused pair (resblock_fused2.hip): weights from L2 into a register queue, raw window, 5 barriers per
-// block; C = 32 / 64 / 128 at k = 3 / 7 / 11; ntw = 2: 256-column blocks, 1: 128-column blocks.
+int32_t launch_fused_pair(const PairArgs& a, hipStream_t stream);
+// Second generation (resblock_fused2.hip): weights from L2 into a register queue, raw window, 5 barriers per block; C = 32 / 64 / 128
+// at k = 3 / 7 / 11.  r.ntw / r.wm pick the instantiation: conv 2 / conv 1 are read as Winograd F(2,3) groups (pack_wino2_weight)
+// where r.wm >= 1 / == 2.
 bool fused_pair2_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y, int32_t ntw);
-int32_t launch_fused_pair2(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
-                           const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                           int32_t mode, float div, float slope, int32_t ntw, hipStream_t stream, const float* w2_wino = nullptr,
-                           const float* w1_wino = nullptr);
-// (w2_wino: conv 2 as Winograd F(2,3) groups -- pack_wino2_weight; C = 32 / 64, ntw = 2: phase B of the pair runs on them; w1_wino:
-// conv 1 likewise -> phase A too)
+int32_t launch_fused_pair2(const PairArgs& a, const PairRoute& r, hipStream_t stream);
 // The C = 32 pair with both convs on Winograd F(4,3) (resblock_pair4.hip): k = 3 / 7 / 11, dilation 1 / 3 / 5; the weights are the
-// F(4,3) group filters of both convs (points = 6: pack_wino4_weight; points = 7, k = 7 / 11 only: the seven-point groups of
+// F(4,3) group filters of both convs (r.points = 6: pack_wino4_weight; 7, k = 7 / 11 only: the seven-point groups of
 // pack_wino44_weight at 32 x 32, [4][wino44_groups(k)][2][32][4])
 bool fused_pair4_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y);
-int32_t launch_fused_pair4(int32_t channels, const float* x, float* y, const float* w1_wino4, const float* b1, const float* w2_wino4,
-                           const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                           int32_t mode, float div, float slope, hipStream_t stream, int32_t points = 6);
+int32_t launch_fused_pair4(const PairArgs& a, const PairRoute& r, hipStream_t stream);
 // HiFi-GAN ResBlock2 (resblock2.hip), exact fp32: one conv y = x + conv(lrelu(x), w, dil) + b with the stage-sum epilogue (C = 32 / 64 /
 // 128, k = 3 / 5 / 7 / 11, dilation 1..16), and both convs of a ResBlock2 in one launch (C = 32 / 64).  Direct weight packing
 // (pack_conv_weight); x != y.

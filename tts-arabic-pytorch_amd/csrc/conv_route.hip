@@ -1,6 +1,9 @@
 // Routing of an exact-fp32 conv launch (launch_conv, conv_mfma.hip): which kernel, in which form, in how many C-in slices.  Host only, no
 // kernel here: conv_route decides from the launch and ONE snapshot of the switches and launches nothing; the launchers (conv_mfma.hip,
 // conv_wino.hip, conv_wino2.hip, conv_wino4.hip) execute what it returned, and ttsamd_conv1d_route (api.hip) asks without launching.
+// Below it, the same for a c1 -> c2 pair of a ResBlock1: pair_route decides which fused kernel takes the pair (resblock_fused.hip,
+// resblock_fused2.hip, resblock_pair4.hip) and in which form, launch_pair executes it for hifigan_forward and ttsamd_resblock_pair alike,
+// and ttsamd_resblock_pair_route asks without launching.
 //   TTSAMD_WINO=0        everything on the direct kernel
 //   TTSAMD_WINO2=<mask>  what the F(2,3) decomposition kernel takes: bit 0 / 1 / 2 = k 3 / 7 / 11, bit 3 = their dilated (3 / 5) convs, bit 4
 //                        = Cout = 64.  Default 31 (same-box A/B of the bench step, tools/ab_env.sh: 74.2 ms with none, 73.1 with k = 3,
@@ -152,6 +155,124 @@ static ConvRoute route_wino(const ConvParams& p, const ConvRouteOpts& o) {
 ConvRoute conv_route(const ConvParams& p, const ConvRouteOpts& o) {
     const ConvRoute r = route_wino(p, o);
     return r.id != 0 ? r : route_direct(p, o);
+}
+
+// ---- the c1 -> c2 pairs of a ResBlock1, exact fp32: one fused launch, or two launch_conv calls routed above ----
+//   TTSAMD_FUSED_PAIR=0      no fused pair at all
+//   TTSAMD_FUSED2=0          no second-generation kernel (resblock_fused2.hip) and none of its F(4,3) successor
+//   TTSAMD_FUSED2_MASK / _MASK_N1 (hex)  replace kFused2Mask / kFused2MaskN1 (A/B runs and the forced-kernel parity tests); a forced
+//                            MASK also lifts the small-problem rule
+//   TTSAMD_FUSED2_WB         phases of the second-generation pair on Winograd F(2,3): 2 (default) both, 1 phase B only, 0 both direct
+//   TTSAMD_PAIR4             1 (default) the routed C = 32 pairs on resblock_pair4.hip, seven-point groups at the k of kPair44Mask;
+//                            2 six-point groups at every k; 0 they stay on resblock_pair2
+// Bit 3 * ci + ki of the masks, ci = 0 / 1 / 2 for C = 32 / 64 / 128, ki = 0 / 1 / 2 for k = 3 / 7 / 11.
+// default routing of the second-generation fused pair, set from same-box A/B runs of the bench workload
+constexpr unsigned kFused2Mask = 0x00F;       // C = 32: k = 3 / 7 / 11; C = 64: k = 3.  Both convs of these pairs run on Winograd F(2,3) inside the launch
+                                              // (resblock_pair2<..., WM = 2>).  Round 6: every other pair runs un-fused on the F(4,3) kernel (conv_wino4.hip,
+                                              // 64-row blocks): same-box A/B of the bench step (tools/ab_env.sh) 56.72 (07f, k = 7 / 11 only on F(4,3)) / 56.15
+                                              // (06f) / 55.00 (05f) / 54.81 ms (04f); then with k = 3 on F(4,3) too: 54.68 (04f) / 55.11 (047: C = 64 k = 3
+                                              // un-fused) / 54.59 (007) / 54.10 ms (00f: C = 128 k = 3 un-fused).  Round 5 on F(2,3): C = 64 k = 11 fused 61.93 vs
+                                              // 62.45; C = 128 k = 3 fused 63.90 vs 64.06
+// Of those, the C = 32 k = 7 / 11 pairs run with both convs on Winograd F(4,3) (resblock_pair4.hip: 16 / 23 products per output quad
+// against 20 / 32 on F(2,3)) when the pair takes the 256-column kernel and TTSAMD_FUSED2_WB asks for both phases on Winograd.
+// Since round 28 the launch runs on SEVEN-point groups (13 / 20 products per quad, the arithmetic of the un-fused k = 7 / 11 convs) at
+// the k of kPair44Mask (bit 0: k = 7, bit 1: k = 11; both: 749 / 712 / 707 -> 665 / 629 / 630 us and 972 / 920 / 894 -> 905 / 869 / 842 us
+// per launch at batch 32, step 47.74 -> 47.15 ms, profiles/r28/NOTES.md).
+// One-stream kernel table at batch 32 (profiles/r7/NOTES.md): k = 11 3.61 -> 2.75 ms per step, k = 7 2.43 -> 2.12, but k = 3 1.22 -> 1.32
+// (memory-bound: 6 products per quad do not pay for the larger window and the extra LDS traffic), so k = 3 stays on resblock_pair2.
+// C = 64 k = 3 stays there too (resblock_pair4 is built for C = 32 only: MT = 1, one 32-row tile per wave).
+constexpr int kPair4MinK = 7;
+constexpr unsigned kPair44Mask = 0x3;
+constexpr unsigned kFused2MaskN1 = 0x000;     // 128-column blocks (the direct-arithmetic kernels only): none by default
+constexpr int64_t kFused2SmallColumns = 2 * 256 * 252;   // batch x positions under which a stage counts as a small problem
+
+PairRouteOpts pair_route_opts() {
+    return {(int)opt_int(OPT_FUSED_PAIR, 1), (int)opt_int(OPT_FUSED2, 1), (int)opt_int(OPT_FUSED2_MASK, -1),
+            (int)opt_int(OPT_FUSED2_MASK_N1, kFused2MaskN1), (int)opt_int(OPT_FUSED2_WB, 2), (int)opt_int(OPT_PAIR4, 1)};
+}
+
+// k = 3 / 7 / 11 convs carry their F(2,3) groups (Cout = 32: the fused pairs' Winograd phases); the un-fused ResBlock convs (Cout >= 64)
+// and the C = 32 pairs that resblock_pair4.hip takes carry the F(4,3) groups too, in both forms where k has a seven-point one: the
+// switches are read per launch (Cout >= 64) / per forward (the C = 32 pairs)
+ConvForms hifigan_conv_forms(int cin, int cout, int k) {
+    const bool wino2 = (k == 3 || k == 7 || k == 11) && cin % 8 == 0 && cout % 32 == 0;
+    const bool wino4 = wino2 && (cout >= 64 || (cout == 32 && cin == 32 && k >= kPair4MinK));
+    return {wino2, wino4, wino4 && wino44_groups(k) != 0};
+}
+
+// resblock_pair2<K, C, NTW, WM> is instantiated with Winograd phases for 256-column blocks only: phase B alone (WM 1) at C = 32 / 64,
+// both phases (WM 2) at dilation 1 / 3 / 5 (256 / 252 / 250 intermediate columns per block) -- so C = 128 (8 waves) only with both
+bool pair2_phases_built(int32_t channels, int32_t dil, int32_t ntw, int32_t wm) {
+    if (wm == 0) return true;
+    if (ntw != 2) return false;
+    return wm == 1 ? channels <= 64 : (wm == 2 && (dil == 1 || dil == 3 || dil == 5));
+}
+
+// the most phases on Winograd that the forms at hand (conv 2's groups: phase B, conv 1's too: phase A) and the instantiations allow
+static int pair2_phases(int32_t channels, int32_t dil, int32_t ntw, bool have_b, bool have_a) {
+    if (have_b && have_a && pair2_phases_built(channels, dil, ntw, 2)) return 2;
+    return (have_b && pair2_phases_built(channels, dil, ntw, 1)) ? 1 : 0;
+}
+
+static PairRoute make_pair_route(int32_t kernel, int32_t ntw, int32_t wm, int32_t points) {
+    if (kernel == PAIR_GEN1) return {PAIR_GEN1, 0, 0, 0, "fused_pair"};
+    if (kernel == PAIR_GEN2) return {PAIR_GEN2, ntw, wm, 0, wm == 2 ? "fused_pair2ww" : (wm == 1 ? "fused_pair2w" : (ntw == 2 ? "fused_pair2" : "fused_pair2n"))};
+    if (kernel == PAIR_F43) return {PAIR_F43, 0, 0, points, points == 7 ? "fused_pair44" : "fused_pair4"};
+    return {PAIR_NONE, 0, 0, 0, ""};
+}
+
+// The block width of the second-generation kernel for this pair: 2 = 256-column blocks, 1 = 128-column blocks, 0 = not this pair.
+static int fused2_width(const PairShape& s, const PairRouteOpts& o) {
+    if (o.fused2 == 0) return 0;
+    const int ci = s.channels == 32 ? 0 : (s.channels == 64 ? 1 : (s.channels == 128 ? 2 : -1));
+    const int ki = s.k == 3 ? 0 : (s.k == 7 ? 1 : (s.k == 11 ? 2 : -1));
+    if (ci < 0 || ki < 0) return 0;
+    const unsigned bit = 1u << (3 * ci + ki);
+    // small problems (batch 1 ... 4: under two rounds of 256-column blocks).  Measured: every pair as ONE launch of 128-column blocks of
+    // this kernel -- half the launches of the un-fused engine -- is SLOWER there (batch 1: 5.27 vs 5.04 ms per step, batch 4: 13.35 vs
+    // 12.88; batch 8 equal): the un-fused engine's 64 x 64 tiles with split K put 3-4x more blocks on the chip.  So this kernel leaves
+    // small problems alone (a forced TTSAMD_FUSED2_MASK overrides the rule: parity tests of the fused kernels on small inputs).  What
+    // it leaves falls through to the first-generation kernel where that one is built (pair_route below), else to two launches.
+    if ((int64_t)s.batch * s.L < kFused2SmallColumns && o.fused2_mask < 0) return 0;
+    if (!((o.fused2_mask < 0 ? kFused2Mask : (unsigned)o.fused2_mask) & bit)) return 0;
+    // the width the mask asks for; where the kernel's geometry refuses it, the other one
+    const int ntw = ((unsigned)o.fused2_mask_n1 & bit) ? 1 : 2;
+    const auto fits = [&](int n) { return fused_pair2_supported(s.channels, s.k, s.dil, s.L, s.x, s.y, n); };
+    return fits(ntw) ? ntw : (fits(3 - ntw) ? 3 - ntw : 0);
+}
+
+PairRoute pair_route(const PairShape& s, const PairRouteOpts& o) {
+    if (s.precision != 0 || o.fused_pair == 0 || !s.square) return make_pair_route(PAIR_NONE, 0, 0, 0);
+    const int ntw = fused2_width(s, o);
+    if (ntw == 0) {
+        // What the second-generation kernel does not take -- a small problem, TTSAMD_FUSED2=0, a pair outside the mask -- goes to the
+        // first-generation kernel wherever that is built (C = 32 at every k, C = 64 at k = 3): batch 1 runs those pairs on it by default
+        return make_pair_route(fused_pair_supported(s.channels, s.k, s.dil, s.L, s.x, s.y) ? PAIR_GEN1 : PAIR_NONE, 0, 0, 0);
+    }
+    // the 256-column pair with both phases asked on Winograd -> its F(4,3) successor where it is built (C = 32) and packed (k = 7 / 11)
+    if (ntw == 2 && o.pair4 != 0 && o.fused2_wb == 2 && s.k >= kPair4MinK && s.forms.wino4 &&
+        fused_pair4_supported(s.channels, s.k, s.dil, s.L, s.x, s.y)) {
+        const bool seven = o.pair4 == 1 && (kPair44Mask & (s.k == 7 ? 1u : (s.k == 11 ? 2u : 0u))) != 0 && s.forms.wino44;
+        return make_pair_route(PAIR_F43, 0, 0, seven ? 7 : 6);
+    }
+    return make_pair_route(PAIR_GEN2, ntw, pair2_phases(s.channels, s.dil, ntw, o.fused2_wb != 0 && s.forms.wino2, o.fused2_wb == 2 && s.forms.wino2), 0);
+}
+
+// ttsamd_resblock_pair's variants: 1 first generation; 2 / 3 second generation with 256- / 128-column blocks; 4 / 5: 256 columns with
+// phase B / both phases on Winograd where that is built; 6 / 7: F(4,3) on six- / seven-point groups
+PairRoute pair_route_of_variant(int32_t variant, int32_t channels, int32_t dil) {
+    if (variant == 2 || variant == 3) return make_pair_route(PAIR_GEN2, variant == 3 ? 1 : 2, 0, 0);
+    if (variant == 4 || variant == 5) return make_pair_route(PAIR_GEN2, 2, pair2_phases(channels, dil, 2, true, variant == 5), 0);
+    if (variant == 6 || variant == 7) return make_pair_route(PAIR_F43, 0, 0, variant);
+    return make_pair_route(variant == 1 ? PAIR_GEN1 : PAIR_NONE, 0, 0, 0);
+}
+
+int32_t launch_pair(const PairRoute& r, const PairArgs& a, hipStream_t stream) {
+    if (r.kernel == PAIR_GEN1) return launch_fused_pair(a, stream);
+    if (r.kernel == PAIR_GEN2) return launch_fused_pair2(a, r, stream);
+    if (r.kernel == PAIR_F43) return launch_fused_pair4(a, r, stream);
+    set_error("launch_pair: no fused kernel takes this pair (C = %d, k = %d, dilation %d)", a.channels, a.k, a.dil);
+    return TTSAMD_EINVAL;
 }
 
 }  // namespace ttsamd

@@ -16,26 +16,6 @@
 
 namespace ttsamd {
 
-// default routing of the second-generation fused pair (fused2_choice below), set from same-box A/B runs of the bench workload
-constexpr unsigned kFused2Mask = 0x00F;       // C = 32: k = 3 / 7 / 11; C = 64: k = 3.  Both convs of these pairs run on Winograd F(2,3) inside the launch
-                                              // (resblock_pair2<..., WM = 2>).  Round 6: every other pair runs un-fused on the F(4,3) kernel (conv_wino4.hip,
-                                              // 64-row blocks): same-box A/B of the bench step (tools/ab_env.sh) 56.72 (07f, k = 7 / 11 only on F(4,3)) / 56.15
-                                              // (06f) / 55.00 (05f) / 54.81 ms (04f); then with k = 3 on F(4,3) too: 54.68 (04f) / 55.11 (047: C = 64 k = 3
-                                              // un-fused) / 54.59 (007) / 54.10 ms (00f: C = 128 k = 3 un-fused).  Round 5 on F(2,3): C = 64 k = 11 fused 61.93 vs
-                                              // 62.45; C = 128 k = 3 fused 63.90 vs 64.06
-// Of those, the C = 32 k = 7 / 11 pairs run with both convs on Winograd F(4,3) (resblock_pair4.hip: 16 / 23 products per output quad
-// against 20 / 32 on F(2,3)) when the pair takes the 256-column kernel with both phases on Winograd; TTSAMD_PAIR4=0 keeps resblock_pair2.
-// Since round 28 the launch runs on SEVEN-point groups (13 / 20 products per quad, the arithmetic of the un-fused k = 7 / 11 convs) at
-// the k of kPair44Mask (bit 0: k = 7, bit 1: k = 11; both: 749 / 712 / 707 -> 665 / 629 / 630 us and 972 / 920 / 894 -> 905 / 869 / 842 us
-// per launch at batch 32, step 47.74 -> 47.15 ms, profiles/r28/NOTES.md); TTSAMD_PAIR4=2 keeps every pair on the six-point groups.
-// One-stream kernel table at batch 32 (profiles/r7/NOTES.md): k = 11 3.61 -> 2.75 ms per step, k = 7 2.43 -> 2.12, but k = 3 1.22 -> 1.32
-// (memory-bound: 6 products per quad do not pay for the larger window and the extra LDS traffic), so k = 3 stays on resblock_pair2.
-// C = 64 k = 3 stays there too (resblock_pair4 is built for C = 32 only: MT = 1, one 32-row tile per wave).
-constexpr int kPair4MinK = 7;
-constexpr unsigned kPair44Mask = 0x3;
-constexpr unsigned kFused2MaskN1 = 0x000;     // 128-column blocks (the direct-arithmetic kernels only): none by default
-constexpr int64_t kFused2SmallColumns = 2 * 256 * 252;   // batch x positions under which a stage counts as a small problem
-
 // ResBlock2 (V3) routing: which (C, k) go out as ONE resblock2_pair launch instead of two resblock2_conv launches.  Bit 3 ci + ki,
 // ci = 0 / 1 for C = 32 / 64, ki = 0 / 1 / 2 for k = 3 / 5 / 7; TTSAMD_RESBLOCK2_PAIR (hex) replaces the default, read per call.
 // Default none: same-run A/B of the V3 vocoder (tools/hifigan_v3_bench.py, profiles/r7/hifigan_v3_bench.jsonl) with every pair fused
@@ -103,57 +83,6 @@ static bool use_branch_streams(const HifiGan* h, int32_t B, int32_t T) {
         if (opt_int(OPT_BFO, 1) != 0) return (int64_t)B * T >= 8192;
     }
     return true;
-}
-
-// Which ResBlock pairs of the fp32 engine go out as ONE launch of the second-generation fused kernel (resblock_fused2.hip), and with
-// which block width: 0 = not this pair, 2 = 256-column blocks, 1 = 128-column blocks.  Bit 3 * ci + ki of the masks, ci = 0 / 1 / 2
-// for C = 32 / 64 / 128, ki = 0 / 1 / 2 for k = 3 / 7 / 11.  TTSAMD_FUSED2=0 turns the kernel off, TTSAMD_FUSED2_MASK / _MASK_N1 (hex)
-// replace the defaults (A/B runs and the forced-kernel parity tests); all read per call.
-// The routing switches are read ONCE per forward call (snapshot below) and handed down: a forward used to make several hundred
-// getenv calls, each a window for a concurrent setenv from another host thread (os.environ writes in Python do exactly that).
-struct Fused2Switches {
-    bool on = true, mask_forced = false;
-    bool wino_b = true, wino_a = true;   // phase B / phase A + B of the C = 32 / 64 pairs as Winograd F(2,3) (TTSAMD_FUSED2_WB=0: both direct, =1: phase B only)
-    bool pair4 = true;                   // ... the C = 32 ones with both phases on Winograd as F(4,3) instead (TTSAMD_PAIR4=0: resblock_pair2)
-    bool pair44 = true;                  // ... on seven-point groups at the k of kPair44Mask (TTSAMD_PAIR4=2: six-point groups at every k)
-    unsigned mask = kFused2Mask, mask_n1 = kFused2MaskN1;
-};
-static Fused2Switches read_fused2_switches() {
-    Fused2Switches sw;
-    sw.on = opt_int(OPT_FUSED2, 1) != 0;
-    const int64_t m = opt_int(OPT_FUSED2_MASK, -1);
-    sw.mask_forced = m >= 0;
-    if (sw.mask_forced) sw.mask = (unsigned)m;
-    sw.mask_n1 = (unsigned)opt_int(OPT_FUSED2_MASK_N1, kFused2MaskN1);
-    const int64_t wb = opt_int(OPT_FUSED2_WB, 2);
-    sw.wino_b = wb != 0;
-    sw.wino_a = wb == 2;
-    const int64_t p4 = opt_int(OPT_PAIR4, 1);
-    sw.pair4 = p4 != 0;
-    sw.pair44 = p4 == 1;
-    return sw;
-}
-
-static int fused2_choice(const Fused2Switches& sw, int32_t channels, int32_t k, int32_t dil, int32_t L, const float* x, const float* y,
-                         int64_t columns) {
-    if (!sw.on) return 0;
-    const int ci = channels == 32 ? 0 : (channels == 64 ? 1 : (channels == 128 ? 2 : -1));
-    const int ki = k == 3 ? 0 : (k == 7 ? 1 : (k == 11 ? 2 : -1));
-    if (ci < 0 || ki < 0) return 0;
-    const unsigned bit = 1u << (3 * ci + ki);
-    // small problems (batch 1 ... 4: under two rounds of 256-column blocks).  Measured: every pair as ONE launch of
-    // 128-column blocks -- half the launches of the un-fused engine -- is SLOWER there (batch 1: 5.27 vs 5.04 ms per step, batch 4: 13.35
-    // vs 12.88; batch 8 equal): the un-fused engine's 64 x 64 tiles with split K put 3-4x more blocks on the chip.  So small problems
-    // keep the un-fused engine (a forced TTSAMD_FUSED2_MASK overrides the rule: parity tests of the fused kernels on small inputs).
-    const bool small = columns < (int64_t)kFused2SmallColumns && !sw.mask_forced;
-    if (small) return 0;
-    if (!(sw.mask & bit)) return 0;
-    int ntw = (sw.mask_n1 & bit) ? 1 : 2;
-    if (!fused_pair2_supported(channels, k, dil, L, x, y, ntw)) {
-        ntw = 3 - ntw;
-        if (!fused_pair2_supported(channels, k, dil, L, x, y, ntw)) return 0;
-    }
-    return ntw;
 }
 
 using TensorMap = std::map<std::string, const ttsamd_tensor*>;
@@ -239,25 +168,17 @@ static int32_t add_conv(const TensorMap& tm, const std::string& base, int cin, i
         return get_bias(tm, base, cout, blob, cw.b_off);
     }
     add_bf16(blob, blob16, cw, (int64_t)cin * k * cout_padded(cout));
-    if ((k == 3 || k == 7 || k == 11) && cin % 8 == 0 && cout % 32 == 0) {      // (cout = 32: the fused pairs' Winograd phase B)
+    // the Winograd forms this conv carries (hifigan_conv_forms, conv_route.hip), one behind the other
+    const auto add_form = [&](int groups, void (*pack)(const float*, int, int, int, float*), int64_t& off) {
         blob.resize(align_up((int64_t)blob.size(), 64));
-        cw.ww_off = (int64_t)blob.size();
-        blob.resize(blob.size() + (size_t)cin * wino2_groups(k) * cout_padded(cout));
-        pack_wino2_weight(w.data(), cout, cin, k, blob.data() + cw.ww_off);
-        if (cout >= 64 || (cout == 32 && cin == 32 && k >= kPair4MinK)) {   // the un-fused ResBlock convs (Cout >= 64) and the routed C = 32 pairs: F(4,3)
-            blob.resize(align_up((int64_t)blob.size(), 64));
-            cw.ww4_off = (int64_t)blob.size();
-            blob.resize(blob.size() + (size_t)cin * wino4_groups(k) * cout_padded(cout));
-            pack_wino4_weight(w.data(), cout, cin, k, blob.data() + cw.ww4_off);
-        }
-        // both forms are kept: the routing switch is read per launch (Cout >= 64) / per forward (the routed C = 32 pairs)
-        if ((cout >= 64 || (cout == 32 && cin == 32 && k >= kPair4MinK)) && wino44_groups(k) != 0) {
-            blob.resize(align_up((int64_t)blob.size(), 64));
-            cw.ww44_off = (int64_t)blob.size();
-            blob.resize(blob.size() + (size_t)cin * wino44_groups(k) * cout_padded(cout));
-            pack_wino44_weight(w.data(), cout, cin, k, blob.data() + cw.ww44_off);
-        }
-    }
+        off = (int64_t)blob.size();
+        blob.resize(blob.size() + (size_t)cin * groups * cout_padded(cout));
+        pack(w.data(), cout, cin, k, blob.data() + off);
+    };
+    const ConvForms forms = hifigan_conv_forms(cin, cout, k);
+    if (forms.wino2) add_form(wino2_groups(k), pack_wino2_weight, cw.ww_off);
+    if (forms.wino4) add_form(wino4_groups(k), pack_wino4_weight, cw.ww4_off);
+    if (forms.wino44) add_form(wino44_groups(k), pack_wino44_weight, cw.ww44_off);
     if (cin % 8 == 0 && cout % 32 == 0) cw.wo = bfo_append_weights(w.data(), cout, cin, k, 1, blob16);
     blob.resize(align_up((int64_t)blob.size(), 64));
     return get_bias(tm, base, cout, blob, cw.b_off);
@@ -445,357 +366,373 @@ void hifigan_destroy(HifiGan* h) {
     delete h;
 }
 
+// The workspace of a forward, carved once for hifigan_workspace_bytes (null arena: it only counts) and hifigan_forward.  nb = branches
+// with buffers of their own (3 on three streams, else 1: the others alias branch 0's)
+struct HgWorkspace {
+    float *cur, *ups_out;             // the stage sum and the upsampler's output
+    float *Tb[3], *R[3], *splitk[3];  // per branch: the c1 -> c2 intermediate, the ResBlock's running output, split-K partial sums
+    uint16_t* mel_o;                  // octet engine: the mel in its layout (x3: 4 bytes per element)
+};
+static HgWorkspace hg_carve(Arena& a, const HifiGan* h, int32_t B, int32_t T, int nb) {
+    HgWorkspace w;
+    const int64_t n = (int64_t)B * h->max_cl * T;
+    w.cur = a.take<float>(n); w.ups_out = a.take<float>(n);
+    for (int i = 0; i < nb; ++i) { w.Tb[i] = a.take<float>(n); w.R[i] = a.take<float>(n); }
+    for (int i = 0; i < nb; ++i) w.splitk[i] = a.take<float>(kSplitKFloats);
+    for (int i = nb; i < 3; ++i) { w.Tb[i] = w.Tb[0]; w.R[i] = w.R[0]; w.splitk[i] = w.splitk[0]; }
+    w.mel_o = a.take<uint16_t>((int64_t)B * align_up(h->cfg.num_mels, 8) * T * 2);
+    return w;
+}
+
 int64_t hifigan_workspace_bytes(const HifiGan* h, int32_t B, int32_t T) {
     Arena a(nullptr, 0);
-    const int nb = use_branch_streams(h, B, T) ? 3 : 1;
-    for (int i = 0; i < 2 + 2 * nb; ++i) a.take<float>((int64_t)B * h->max_cl * T);
-    for (int i = 0; i < nb; ++i) a.take<float>(kSplitKFloats);
-    a.take<uint16_t>((int64_t)B * align_up(h->cfg.num_mels, 8) * T * 2);   // octet engine: the mel in its layout (x3: 4 bytes per element)
+    hg_carve(a, h, B, T, use_branch_streams(h, B, T) ? 3 : 1);
     return a.off;
+}
+
+// The accumulate mode of a launch that writes the stage sum: branch 0 stores (0), the middle branches add (1), the last one adds and
+// divides by n_kernels (2).  Every launch that is not its branch's last stores, and so does a lone branch.
+static int sum_mode(int j, int n_kernels, bool last) {
+    return (!last || n_kernels == 1 || j == 0) ? 0 : (j + 1 < n_kernels ? 1 : 2);
+}
+
+// The schedule of a stage's ResBlocks, for all three engines: the only place that records or waits for an event, and the one
+// profiling bracket.  A branch body asks for its stream (branch), says that its next launch accumulates into the stage sum
+// (before_sum: the sum is formed in the order j = 0 -> 1 -> 2) and that it is done (done).  One stream: all of it is a no-op.
+struct StageSchedule {
+    const HifiGan* h;
+    hipStream_t s;            // the caller's stream: branch 0 and everything outside the ResBlocks
+    bool multi;
+    hipStream_t bs[3];
+    bool in_section = false;  // inside fork..join: profiling brackets the section once, per-launch spans would overlap
+    bool failed = false;
+
+    // a failure must not leave the side streams running on a workspace the caller is about to recycle
+    ~StageSchedule() { if (multi && failed) { (void)hipStreamSynchronize(bs[1]); (void)hipStreamSynchronize(bs[2]); } }
+    int32_t fail(int32_t rc) { failed = failed || rc != 0; return rc; }
+
+    int32_t fork() {
+        if (!multi) return 0;
+        prof_section_begin(s);
+        in_section = true;
+        TTS_CHECK_HIP(hipEventRecord(h->ev_fork, s));
+        return 0;
+    }
+    int32_t branch(int j, hipStream_t* st) {
+        *st = bs[j % 3];
+        if (multi && j > 0) TTS_CHECK_HIP(hipStreamWaitEvent(*st, h->ev_fork, 0));
+        return 0;
+    }
+    int32_t before_sum(int j) {
+        if (multi && j > 0) TTS_CHECK_HIP(hipStreamWaitEvent(bs[j % 3], h->ev_done[j - 1], 0));
+        return 0;
+    }
+    int32_t done(int j) {
+        if (multi) TTS_CHECK_HIP(hipEventRecord(h->ev_done[j], bs[j % 3]));
+        return 0;
+    }
+    int32_t join(int n_kernels) {
+        if (!multi) return 0;
+        TTS_CHECK_HIP(hipStreamWaitEvent(s, h->ev_done[n_kernels - 1], 0));
+        in_section = false;
+        prof_section_end(s);
+        return 0;
+    }
+    template <class F>
+    int32_t timed(hipStream_t st, double flops, F&& launch) {
+        if (in_section) prof_add(flops);
+        else prof_begin(st, flops);
+        const int32_t rc = launch();
+        if (!in_section) prof_end(st);
+        return rc;
+    }
+};
+
+// what one forward hands to its branch bodies: read once, constant from there on
+struct HgCall {
+    const HifiGan* h;
+    const int64_t* lens;
+    int32_t B, prec;
+    HgWorkspace w;
+    StageSchedule& sch;
+    // the launch_conv engines (exact fp32; TTSAMD_BFO=0: the round-2 bf16 engine) only:
+    ConvParams base;        // what every launch_conv of the forward shares; each launch builds its own parameters from it
+    bool pack_t;            // plain bf16 mode: the c1 -> c2 intermediate of a ResBlock only feeds c2, so it crosses HBM as packed bf16
+                            // (ConvParams::y_packed / x_packed; same rounding point as the fp32 buffer + round-on-load, bit-identical)
+    PairRouteOpts pair_opts;
+    unsigned rb2_mask;
+};
+struct Stage { int i, L, mul; };   // upsampler index, positions per row and length multiplier behind it
+
+// ---- config 3: plain bf16 (precision 1) and split bf16 (precision 2) run on the octet engine (bfo.hpp / bfo3.hpp):
+// v_mfma_f32_32x32x16_bf16, activations in HBM as octet entries (bf16, or hi + lo) stored pre-activated for their consumer,
+// fused c1 -> c2 pairs for C <= 128.  TTSAMD_BFO=0 keeps the round-2 bf16 engine (fp32 activations in HBM).
+// One ResBlock1: a chained launch, or per dilation a pair launch or (C = 256) two conv launches.  `cp` is the forward's one conv
+// parameter block (octet_forward); next_slope: what reads the stage sum applies it
+static int32_t octet_branch(const HgCall& c, const BfoMode& M, BfoConvParams& cp, const Stage& g, int j, float next_slope) {
+    const HifiGan* h = c.h;
+    const ttsamd_hifigan_cfg& cfg = h->cfg;
+    const uint16_t* W16 = h->dev16;
+    const int L = g.L, mul = g.mul;
+    void *curo = c.w.cur, *Tb = c.w.Tb[j % 3], *R = c.w.R[j % 3];
+    hipStream_t st;
+    TTS_TRY(c.sch.branch(j, &st));
+    const void* src = c.w.ups_out;
+    const int li0 = (g.i * cfg.n_kernels + j) * cfg.n_dilations;
+    const float div = (float)cfg.n_kernels, sum_slope = j + 1 == cfg.n_kernels ? next_slope : 1.f;
+    // a ResBlock whose three pairs fit the chained kernel (k = 3; k = 7 at C <= 64) goes out as ONE launch (bfo_chain.hip; bit-identical)
+    int32_t dl[3] = {0, 0, 0};
+    for (int m = 0; m < cfg.n_dilations && m < 3; ++m) dl[m] = cfg.resblock_dilations[j][m];
+    // (TTSAMD_BFO_CHAIN=0: three pair launches per ResBlock; bit-identical, A/B and parity runs)
+    if (M.chain_wanted(h->c1[li0].cin, h->c1[li0].k, dl, cfg.n_dilations, L, c.B)) {
+        BfoChainParams cc;
+        std::memset(&cc, 0, sizeof(cc));
+        cc.x = src; cc.y = curo; cc.sum_in = curo;
+        for (int m = 0; m < 3; ++m) {
+            const ConvW &w1 = h->c1[li0 + m], &w2 = h->c2[li0 + m];
+            cc.w1[m] = W16 + w1.wo.of(M); cc.w2[m] = W16 + w2.wo.of(M); cc.b1[m] = h->dev + w1.b_off; cc.b2[m] = h->dev + w2.b_off;
+            cc.dil[m] = dl[m];
+        }
+        cc.lens = c.lens; cc.len_mul = mul; cc.L = L; cc.batch = c.B; cc.k = h->c1[li0].k;
+        cc.mode = sum_mode(j, cfg.n_kernels, true);
+        cc.div = div; cc.in_slope = 0.1f; cc.mid_slope = 0.1f; cc.out_slope = sum_slope;
+        TTS_TRY(c.sch.before_sum(j));
+        TTS_TRY(c.sch.timed(st, 3 * 2.0 * (2.0 * h->c1[li0].cin * h->c1[li0].cin * h->c1[li0].k) * mul,
+                            [&] { return M.chain(h->c1[li0].cin, cc, st); }));
+        return c.sch.done(j);
+    }
+    for (int m = 0; m < cfg.n_dilations; ++m) {
+        const int d = cfg.resblock_dilations[j][m];
+        const bool last = m + 1 == cfg.n_dilations;
+        const ConvW &w1 = h->c1[li0 + m], &w2 = h->c2[li0 + m];
+        void* dst = last ? curo : (src == R ? Tb : R);
+        // running ResBlock sum in `cur`: raw bf16 until the last branch stores it activated for its consumer
+        const int mode = sum_mode(j, cfg.n_kernels, last);
+        const float out_slope = !last ? 0.1f : sum_slope;
+        if (last) TTS_TRY(c.sch.before_sum(j));
+        const double fl = 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * mul;
+        if (M.pair_supported(w1.cin, w1.k, d, L)) {
+            BfoPairParams pp;
+            std::memset(&pp, 0, sizeof(pp));
+            pp.x = src; pp.y = dst; pp.sum_in = curo;
+            pp.w1 = W16 + w1.wo.of(M); pp.w2 = W16 + w2.wo.of(M); pp.b1 = h->dev + w1.b_off; pp.b2 = h->dev + w2.b_off;
+            pp.lens = c.lens; pp.len_mul = mul; pp.L = L; pp.dil = d; pp.batch = c.B;
+            pp.mode = mode; pp.div = div; pp.in_slope = 0.1f; pp.mid_slope = 0.1f; pp.out_slope = out_slope;
+            TTS_TRY(c.sch.timed(st, fl, [&] { return M.pair(w1.cin, w1.k, pp, st); }));
+        } else {
+            // C = 256 (stage 1): c1 and c2 as two launches, the intermediate stored activated for c2.  c2 reads its
+            // residual only at its own output positions, so it may run in place (dst == src == R)
+            if (!last) dst = R;
+            TTS_TRY(c.sch.timed(st, fl, [&] {
+                cp.x = src; cp.y = Tb; cp.w = W16 + w1.wo.of(M); cp.bias = h->dev + w1.b_off; cp.res = nullptr; cp.sum_in = nullptr;
+                cp.len_mul = mul; cp.Lin = L; cp.Cin = w1.cin; cp.Cout = w1.cout; cp.K = w1.k; cp.dil = d; cp.up = 1;
+                cp.mode = 0; cp.out_slope = 0.1f; cp.res_slope = 1.f;
+                cp.splitk_ws = c.w.splitk[j % 3]; cp.splitk_floats = kSplitKFloats;     // batch 1: 30 blocks per stage-1 conv
+                const int32_t rc = M.conv(cp, st);
+                if (rc != 0) return rc;
+                cp.x = Tb; cp.y = dst; cp.w = W16 + w2.wo.of(M); cp.bias = h->dev + w2.b_off; cp.res = src; cp.sum_in = curo;
+                cp.dil = 1; cp.mode = mode; cp.div = div; cp.out_slope = out_slope; cp.res_slope = 0.1f;
+                return M.conv(cp, st);
+            }));
+        }
+        if (last) TTS_TRY(c.sch.done(j));
+        src = dst;
+    }
+    return 0;
+}
+
+static int32_t octet_forward(const HgCall& c, const float* mel, int32_t T, float* wave) {
+    const HifiGan* h = c.h;
+    const ttsamd_hifigan_cfg& cfg = h->cfg;
+    const BfoMode& M = bfo_mode(c.prec);
+    const uint16_t* W16 = h->dev16;
+    hipStream_t s = c.sch.s;
+    void *curo = c.w.cur, *upso = c.w.ups_out;                 // the fp32-sized buffers hold bf16 / x3 tensors of the same element count
+    TTS_TRY(M.pack(mel, c.B, cfg.num_mels, T, 1.f, c.w.mel_o, s));
+    BfoConvParams cp;
+    std::memset(&cp, 0, sizeof(cp));
+    cp.batch = c.B; cp.lens = c.lens; cp.div = 1.f; cp.res_slope = 1.f;
+    // conv_pre (models.py:112); its consumer, the first upsampler, applies leaky_relu(0.1) (models.py:114)
+    cp.x = c.w.mel_o; cp.y = curo; cp.w = W16 + h->conv_pre.wo.of(M); cp.bias = h->dev + h->conv_pre.b_off;
+    cp.len_mul = 1; cp.Lin = T; cp.Cin = h->conv_pre.cin; cp.Cout = h->conv_pre.cout; cp.K = 7; cp.dil = 1; cp.up = 1;
+    cp.mode = 0; cp.out_slope = 0.1f;
+    TTS_TRY(c.sch.timed(s, 2.0 * cp.Cout * cp.Cin * 7, [&] { return M.conv(cp, s); }));
+    Stage g = {0, T, 1};
+    for (g.i = 0; g.i < cfg.n_ups; ++g.i) {
+        const int u = cfg.upsample_rates[g.i];
+        const ConvW& uw = h->ups[g.i];
+        // ConvTranspose1d on the activated stage input; the ResBlocks read its output through leaky_relu(0.1)
+        cp.x = curo; cp.y = upso; cp.w = W16 + uw.wo.of(M); cp.bias = h->dev + uw.b_off; cp.res = nullptr; cp.sum_in = nullptr;
+        cp.len_mul = g.mul; cp.Lin = g.L; cp.Cin = uw.cin; cp.Cout = uw.cout; cp.K = 2; cp.dil = 1; cp.up = u;
+        cp.mode = 0; cp.out_slope = 0.1f;
+        TTS_TRY(c.sch.timed(s, 2.0 * uw.cout * uw.cin * 2 * u * g.mul, [&] { return M.convt(cp, s); }));
+        g.L *= u; g.mul *= u;
+        // what reads the stage sum: the next upsampler through leaky_relu(0.1), conv_post through leaky_relu(0.01)
+        const float next_slope = g.i + 1 < cfg.n_ups ? 0.1f : 0.01f;
+        TTS_TRY(c.sch.fork());
+        for (int j = 0; j < cfg.n_kernels; ++j) TTS_TRY(octet_branch(c, M, cp, g, j, next_slope));
+        TTS_TRY(c.sch.join(cfg.n_kernels));
+    }
+    return M.conv_post(curo, h->dev + h->conv_post.w_off, h->dev + h->conv_post.b_off, c.lens, g.mul, c.B, h->conv_post.cin, g.L, wave,
+                       (int64_t)g.L, s);
+}
+
+// ---- exact fp32 (and TTSAMD_BFO=0: the round-2 bf16 engine) on launch_conv and the fused fp32 kernels
+// one launch_conv.  pack_io bit 0: x is packed, bit 1: write y packed
+static int32_t hg_conv(const HgCall& c, const ConvW& cw, const float* x, hipStream_t st, float* y, const float* res,
+                       const Stage& g, int dil, float slope, int mode, float div, float* splitk_ws, int pack_io) {
+    const HifiGan* h = c.h;
+    const int L = g.L;
+    ConvParams p = c.base;
+    p.x = x; p.x_bs = (int64_t)cw.cin * L; p.x_cs = L;
+    p.w = h->dev + cw.w_off; p.bias = h->dev + cw.b_off;
+    p.w_bf16 = h->dev16 + cw.w16_off; p.precision = c.prec;
+    p.w_wino = cw.ww_off >= 0 ? h->dev + cw.ww_off : nullptr;
+    p.w_wino4 = (cw.ww4_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww4_off : nullptr;   // (C = 32: the fused pair's filters only)
+    p.w_wino44 = (cw.ww44_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww44_off : nullptr;   // (likewise: 32 rows are no launch of the 64-row kernel)
+    p.y = y; p.y_bs = (int64_t)cw.cout * L; p.y_cs = L; p.y_ts = 1;
+    p.res = res; p.r_bs = (int64_t)cw.cout * L; p.r_cs = L;
+    p.len_in_mul = g.mul; p.len_out_mul = g.mul; p.Lin = L; p.Nout = L;
+    p.Cin = cw.cin; p.Cout = cw.cout; p.CoutP = cout_padded(cw.cout); p.K = cw.k;
+    p.dil = dil; p.pad = (cw.k * dil - dil) / 2;
+    p.in_slope = slope; p.mode = mode; p.div = div;
+    p.x_packed = (pack_io & 1) ? 1 : 0; p.y_packed = (pack_io & 2) ? 1 : 0;
+    p.splitk_ws = splitk_ws;
+    return c.sch.timed(st, 2.0 * cw.cout * cw.cin * cw.k * g.mul, [&] { return launch_conv(p, st); });
+}
+
+static PairConv pair_conv(const HifiGan* h, const ConvW& cw) {
+    const auto form = [&](int64_t off) { return off >= 0 ? h->dev + off : (const float*)nullptr; };
+    return {h->dev + cw.w_off, h->dev + cw.b_off, form(cw.ww_off), form(cw.ww4_off), form(cw.ww44_off)};
+}
+
+// One ResBlock1 (models.py:46-53): per dilation the c1 -> c2 pair as ONE fused launch where pair_route says so (x and y must differ
+// -- halo reads -- so the pair outputs alternate between R and the unused c1 buffer), else c1 into Tb and c2, with the residual, into R
+static int32_t resblock1_branch(const HgCall& c, const Stage& g, int j) {
+    const HifiGan* h = c.h;
+    const ttsamd_hifigan_cfg& cfg = h->cfg;
+    float *cur = c.w.cur, *Tb = c.w.Tb[j % 3], *R = c.w.R[j % 3], *splitk = c.w.splitk[j % 3];
+    hipStream_t st;
+    TTS_TRY(c.sch.branch(j, &st));
+    const float* src = c.w.ups_out;
+    for (int m = 0; m < cfg.n_dilations; ++m) {
+        const int li = (g.i * cfg.n_kernels + j) * cfg.n_dilations + m;
+        const int d = cfg.resblock_dilations[j][m];
+        const bool last = m + 1 == cfg.n_dilations;
+        const ConvW &w1 = h->c1[li], &w2 = h->c2[li];
+        const PairConv p1 = pair_conv(h, w1), p2 = pair_conv(h, w2);
+        const int mode = sum_mode(j, cfg.n_kernels, last);
+        float* dst = last ? cur : (src == R ? Tb : R);
+        const bool square = w1.cin == w1.cout && w2.cin == w1.cin && w2.cout == w1.cin && w1.k == w2.k;
+        const ConvForms forms = {p1.w_wino2 && p2.w_wino2, p1.w_wino4 && p2.w_wino4, p1.w_wino44 && p2.w_wino44};
+        const PairRoute r = pair_route(PairShape{w1.cin, w1.k, d, g.L, c.B, square, src, dst, forms, c.prec}, c.pair_opts);
+        if (r.kernel != PAIR_NONE) {
+            if (last) TTS_TRY(c.sch.before_sum(j));
+            const PairArgs a = {w1.cin, w1.k, d, src, dst, p1, p2, c.lens, g.mul, g.L, c.B, mode, (float)cfg.n_kernels, 0.1f};
+            TTS_TRY(c.sch.timed(st, 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * g.mul, [&] { return launch_pair(r, a, st); }));
+        } else {
+            dst = last ? cur : R;
+            TTS_TRY(hg_conv(c, w1, src, st, Tb, nullptr, g, d, 0.1f, 0, 1.f, splitk, c.pack_t ? 2 : 0));
+            if (last) TTS_TRY(c.sch.before_sum(j));
+            TTS_TRY(hg_conv(c, w2, Tb, st, dst, src, g, 1, 0.1f, mode, last ? (float)cfg.n_kernels : 1.f, splitk, c.pack_t ? 1 : 0));
+        }
+        if (last) TTS_TRY(c.sch.done(j));
+        src = dst;
+    }
+    return 0;
+}
+
+// One ResBlock2 (models.py:62-83): both convs as one resblock2_pair launch where routed, else two resblock2_conv launches through Tb
+// (x != y: halo reads).  The second writes the stage sum into `cur` (mode / div as for ResBlock1)
+static int32_t resblock2_branch(const HgCall& c, const Stage& g, int j) {
+    const HifiGan* h = c.h;
+    const ttsamd_hifigan_cfg& cfg = h->cfg;
+    const float* x = c.w.ups_out;
+    float *cur = c.w.cur, *Tb = c.w.Tb[j % 3];
+    hipStream_t st;
+    TTS_TRY(c.sch.branch(j, &st));
+    const ConvW &w1 = h->c1[g.i * cfg.n_kernels + j], &w2 = h->c2[g.i * cfg.n_kernels + j];
+    const float *W1 = h->dev + w1.w_off, *B1 = h->dev + w1.b_off, *W2 = h->dev + w2.w_off, *B2 = h->dev + w2.b_off;
+    const int d1 = cfg.resblock_dilations[j][0], d2 = cfg.resblock_dilations[j][1];
+    const int mode = sum_mode(j, cfg.n_kernels, true);
+    const float div = (float)cfg.n_kernels;
+    const double fl = 2.0 * w1.cout * w1.cin * w1.k * g.mul;      // per conv
+    if (resblock2_pair_choice(c.rb2_mask, w1.cin, w1.k, d1, d2, g.L, x, cur)) {
+        TTS_TRY(c.sch.before_sum(j));
+        TTS_TRY(c.sch.timed(st, 2 * fl, [&] {
+            return launch_resblock2_pair(w1.cin, x, cur, W1, B1, W2, B2, w1.k, d1, d2, c.lens, g.mul, g.L, c.B, mode, div, 0.1f, st);
+        }));
+    } else {
+        TTS_TRY(c.sch.timed(st, fl, [&] {
+            return launch_resblock2_conv(w1.cin, x, Tb, W1, B1, w1.k, d1, c.lens, g.mul, g.L, c.B, 0, 1.f, 0.1f, st);
+        }));
+        TTS_TRY(c.sch.before_sum(j));
+        TTS_TRY(c.sch.timed(st, fl, [&] {
+            return launch_resblock2_conv(w2.cin, Tb, cur, W2, B2, w2.k, d2, c.lens, g.mul, g.L, c.B, mode, div, 0.1f, st);
+        }));
+    }
+    return c.sch.done(j);
+}
+
+static int32_t f32_forward(const HgCall& c, const float* mel, int32_t T, float* wave) {
+    const HifiGan* h = c.h;
+    const ttsamd_hifigan_cfg& cfg = h->cfg;
+    hipStream_t s = c.sch.s;
+    float *cur = c.w.cur, *ups_out = c.w.ups_out;
+    const bool convt_ok = opt_int(OPT_CONVT, 1) != 0;   // all-phases-per-wave transposed conv (convt_mfma.hip)
+    // conv_pre (models.py:112)
+    Stage g = {0, T, 1};
+    TTS_TRY(hg_conv(c, h->conv_pre, mel, s, cur, nullptr, g, 1, 1.0f, 0, 1.f, c.w.splitk[0], 0));
+    for (g.i = 0; g.i < cfg.n_ups; ++g.i) {
+        const int u = cfg.upsample_rates[g.i], kt = cfg.upsample_kernel_sizes[g.i];
+        const ConvW& uw = h->ups[g.i];
+        // leaky_relu(0.1) + ConvTranspose1d as u polyphase 2-tap convs (models.py:114-115)
+        ConvParams pu = c.base;
+        pu.splitk_ws = c.w.splitk[0];
+        TTS_TRY(c.sch.timed(s, 2.0 * uw.cout * uw.cin * 2 * u * g.mul, [&] {
+            return launch_upsampler(pu, cur, h->dev + uw.w_off, h->dev16 + uw.w16_off, h->dev + uw.b_off, ups_out, uw.cin, uw.cout, u, kt, g.L,
+                                    g.mul, 0.1f, convt_ok, s, uw.wct_off >= 0 ? h->dev + uw.wct_off : nullptr,
+                                    uw.bct_off >= 0 ? h->dev + uw.bct_off : nullptr);
+        }));
+        g.L *= u; g.mul *= u;
+        // the ResBlocks on the same input, averaged (models.py:116-122)
+        TTS_TRY(c.sch.fork());
+        for (int j = 0; j < cfg.n_kernels; ++j) TTS_TRY(h->rb2 ? resblock2_branch(c, g, j) : resblock1_branch(c, g, j));
+        TTS_TRY(c.sch.join(cfg.n_kernels));
+    }
+    // leaky_relu (default slope 0.01) + conv_post + tanh (models.py:123-125)
+    return launch_conv_post(cur, (int64_t)h->conv_post.cin * g.L, g.L, h->dev + h->conv_post.w_off, h->dev + h->conv_post.b_off, c.lens, g.mul,
+                            c.B, h->conv_post.cin, g.L, 0.01f, wave, (int64_t)g.L, s);
 }
 
 int32_t hifigan_forward(const HifiGan* h, const float* mel, const int64_t* lens, int32_t B, int32_t T, float* wave,
                         void* ws, int64_t ws_bytes, hipStream_t s) {
     TTS_REQUIRE(h && mel && wave && B >= 1 && T >= 1, "hifigan_forward: bad argument");
-    TTS_REQUIRE(!h->rb2 || default_precision() == 0, "hifigan_forward: a ResBlock2 generator is built for f32 only (precision %d "
-                "requested; ttsamd_set_precision(0))", default_precision());
+    const int prec = default_precision();
+    TTS_REQUIRE(!h->rb2 || prec == 0, "hifigan_forward: a ResBlock2 generator is built for f32 only (precision %d "
+                "requested; ttsamd_set_precision(0))", prec);
     Arena a(ws, ws_bytes);
     const bool multi = use_branch_streams(h, B, T);
-    const int nb = multi ? 3 : 1;
-    float* cur = a.take<float>((int64_t)B * h->max_cl * T);
-    float* ups_out = a.take<float>((int64_t)B * h->max_cl * T);
-    float *Tbs[3], *Rs[3], *splitks[3];
-    for (int i = 0; i < nb; ++i) {
-        Tbs[i] = a.take<float>((int64_t)B * h->max_cl * T);
-        Rs[i] = a.take<float>((int64_t)B * h->max_cl * T);
-    }
-    for (int i = 0; i < nb; ++i) splitks[i] = a.take<float>(kSplitKFloats);
-    for (int i = nb; i < 3; ++i) { Tbs[i] = Tbs[0]; Rs[i] = Rs[0]; splitks[i] = splitks[0]; }
-    uint16_t* mel_o = a.take<uint16_t>((int64_t)B * align_up(h->cfg.num_mels, 8) * T * 2);
+    const HgWorkspace w = hg_carve(a, h, B, T, multi ? 3 : 1);
     if (!ws || !a.ok) {
         set_error("hifigan_forward: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
         return TTSAMD_ENOMEM;
     }
-    const ttsamd_hifigan_cfg& cfg = h->cfg;
     std::unique_lock<std::mutex> lk(h->mu, std::defer_lock);
-    hipStream_t bs[3] = {s, s, s};
     if (multi) {
         lk.lock();
         TTS_REQUIRE(h->ev_fork && h->side[0] && h->side[1], "hifigan_forward: the branch streams were not created (hifigan_create)");
-        bs[1] = h->side[0];
-        bs[2] = h->side[1];
     }
-
-    // any failure below must not leave the side streams running on a workspace the caller is about to recycle
-    struct Join {
-        bool on; hipStream_t a, b;
-        ~Join() { if (on) { (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); } }
-    } join{false, bs[1], bs[2]};
-    const auto fail = [&](int32_t rc) { join.on = multi && rc != 0; return rc; };
-
-    ConvParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.batch = B;
-    p.lens_in = lens; p.lens_out = lens;
-    p.n_phase = 1; p.div = 1.f;
-    p.splitk_ws = splitks[0]; p.splitk_floats = kSplitKFloats;     // batch 1: stage-1 launches have < 256 tiles
-    // plain bf16 mode: the c1 -> c2 intermediate of a ResBlock only feeds c2, so it crosses HBM as packed bf16
-    // (ConvParams::y_packed / x_packed; same rounding point as the fp32 buffer + round-on-load, bit-identical)
-    const bool pack_t = default_precision() == 1 && opt_int(OPT_BF16_PACKED_T, 1) != 0;
-    const Fused2Switches f2sw = read_fused2_switches();
-    const bool fused_ok = default_precision() == 0 && opt_int(OPT_FUSED_PAIR, 1) != 0;
-    const bool convt_ok = opt_int(OPT_CONVT, 1) != 0;   // all-phases-per-wave transposed conv (convt_mfma.hip)
-    const unsigned rb2_mask = (unsigned)opt_int(OPT_RESBLOCK2_PAIR, kResblock2PairMask);
-    bool in_section = false;   // inside a multi-stream fork..join section (profiling brackets the section)
-    int pack_io = 0;   // bit 0: x is packed, bit 1: write y packed (set around the c1 / c2 launches below)
-    auto conv = [&](const ConvW& cw, const float* x, hipStream_t st, float* y, const float* res, int L, int mul,
-                    int dil, float slope, int mode, float div) -> int32_t {
-        p.x = x; p.x_bs = (int64_t)cw.cin * L; p.x_cs = L;
-        p.w = h->dev + cw.w_off; p.bias = h->dev + cw.b_off;
-        p.w_bf16 = h->dev16 + cw.w16_off; p.precision = default_precision();
-        p.w_wino = cw.ww_off >= 0 ? h->dev + cw.ww_off : nullptr;
-        p.w_wino4 = (cw.ww4_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww4_off : nullptr;   // (C = 32: the fused pair's filters only)
-        p.w_wino44 = (cw.ww44_off >= 0 && cw.cout >= 64) ? h->dev + cw.ww44_off : nullptr;   // (likewise: 32 rows are no launch of the 64-row kernel)
-        p.y = y; p.y_bs = (int64_t)cw.cout * L; p.y_cs = L; p.y_ts = 1;
-        p.res = res; p.r_bs = (int64_t)cw.cout * L; p.r_cs = L;
-        p.len_in_mul = mul; p.len_out_mul = mul; p.Lin = L; p.Nout = L;
-        p.Cin = cw.cin; p.Cout = cw.cout; p.CoutP = cout_padded(cw.cout); p.K = cw.k;
-        p.dil = dil; p.pad = (cw.k * dil - dil) / 2;
-        p.n_phase = 1; p.phase_p = 0;
-        p.in_slope = slope; p.relu_out = 0; p.mode = mode; p.div = div;
-        p.x_packed = (pack_io & 1) ? 1 : 0; p.y_packed = (pack_io & 2) ? 1 : 0; p.pack_slope = 0.1f;
-        // in the three-stream schedule the whole fork..join section is bracketed once (below): per-launch spans overlap
-        if (in_section) prof_add(2.0 * cw.cout * cw.cin * cw.k * mul);
-        else prof_begin(st, 2.0 * cw.cout * cw.cin * cw.k * mul);
-        const int32_t rc = launch_conv(p, st);
-        if (!in_section) prof_end(st);
-        return rc;
-    };
-
-#define HG_TRY(expr) do { int32_t rc_ = (expr); if (rc_ != 0) return fail(rc_); } while (0)
-#define HG_CHECK_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return fail(TTSAMD_EHIP); } } while (0)
-    // ---- config 3: plain bf16 (precision 1) and split bf16 (precision 2) run on the octet engine (bfo.hpp / bfo3.hpp):
-    // v_mfma_f32_32x32x16_bf16, activations in HBM as octet entries (bf16, or hi + lo) stored pre-activated for their consumer,
-    // fused c1 -> c2 pairs for C <= 128.  TTSAMD_BFO=0 keeps the round-2 bf16 engine (fp32 activations in HBM).
-    const int prec = default_precision();
-    if ((prec == 1 || prec == 2) && h->bfo_ok && opt_int(OPT_BFO, 1) != 0) {
-        const BfoMode& M = bfo_mode(prec);
-        const uint16_t* W16 = h->dev16;
-        void *curo = cur, *upso = ups_out;                 // the fp32-sized buffers hold bf16 / x3 tensors of the same element count
-        HG_TRY(M.pack(mel, B, cfg.num_mels, T, 1.f, mel_o, s));
-        BfoConvParams cp;
-        std::memset(&cp, 0, sizeof(cp));
-        cp.batch = B; cp.lens = lens; cp.div = 1.f; cp.res_slope = 1.f;
-        // conv_pre (models.py:112); its consumer, the first upsampler, applies leaky_relu(0.1) (models.py:114)
-        cp.x = mel_o; cp.y = curo; cp.w = W16 + h->conv_pre.wo.of(M); cp.bias = h->dev + h->conv_pre.b_off;
-        cp.len_mul = 1; cp.Lin = T; cp.Cin = h->conv_pre.cin; cp.Cout = h->conv_pre.cout; cp.K = 7; cp.dil = 1; cp.up = 1;
-        cp.mode = 0; cp.out_slope = 0.1f;
-        prof_begin(s, 2.0 * cp.Cout * cp.Cin * 7);
-        int32_t rc = M.conv(cp, s);
-        prof_end(s);
-        HG_TRY(rc);
-        int L = T, mul = 1;
-        for (int i = 0; i < cfg.n_ups; ++i) {
-            const int u = cfg.upsample_rates[i];
-            const ConvW& uw = h->ups[i];
-            // ConvTranspose1d on the activated stage input; the ResBlocks read its output through leaky_relu(0.1)
-            cp.x = curo; cp.y = upso; cp.w = W16 + uw.wo.of(M); cp.bias = h->dev + uw.b_off; cp.res = nullptr; cp.sum_in = nullptr;
-            cp.len_mul = mul; cp.Lin = L; cp.Cin = uw.cin; cp.Cout = uw.cout; cp.K = 2; cp.dil = 1; cp.up = u;
-            cp.mode = 0; cp.out_slope = 0.1f;
-            prof_begin(s, 2.0 * uw.cout * uw.cin * 2 * u * mul);
-            rc = M.convt(cp, s);
-            prof_end(s);
-            HG_TRY(rc);
-            L *= u; mul *= u;
-            // what reads the stage sum: the next upsampler through leaky_relu(0.1), conv_post through leaky_relu(0.01)
-            const float next_slope = i + 1 < cfg.n_ups ? 0.1f : 0.01f;
-            if (multi) {
-                prof_section_begin(s);
-                in_section = true;
-                HG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
-            }
-            for (int j = 0; j < cfg.n_kernels; ++j) {
-                hipStream_t st = bs[j % 3];
-                void *Tb = Tbs[j % 3], *R = Rs[j % 3];
-                if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_fork, 0));
-                const void* src = upso;
-                {
-                    // a ResBlock whose three pairs fit the chained kernel (k = 3; k = 7 at C <= 64) goes out as ONE launch (bfo_chain.hip; bit-identical)
-                    const int li0 = (i * cfg.n_kernels + j) * cfg.n_dilations;
-                    int32_t dl[3] = {0, 0, 0};
-                    for (int m = 0; m < cfg.n_dilations && m < 3; ++m) dl[m] = cfg.resblock_dilations[j][m];
-                    // (TTSAMD_BFO_CHAIN=0: three pair launches per ResBlock; bit-identical, A/B and parity runs)
-                    if (M.chain_wanted(h->c1[li0].cin, h->c1[li0].k, dl, cfg.n_dilations, L, B)) {
-                        BfoChainParams cc;
-                        std::memset(&cc, 0, sizeof(cc));
-                        cc.x = src; cc.y = curo; cc.sum_in = curo;
-                        for (int m = 0; m < 3; ++m) {
-                            const ConvW &w1 = h->c1[li0 + m], &w2 = h->c2[li0 + m];
-                            cc.w1[m] = W16 + w1.wo.of(M); cc.w2[m] = W16 + w2.wo.of(M); cc.b1[m] = h->dev + w1.b_off; cc.b2[m] = h->dev + w2.b_off;
-                            cc.dil[m] = dl[m];
-                        }
-                        cc.lens = lens; cc.len_mul = mul; cc.L = L; cc.batch = B; cc.k = h->c1[li0].k;
-                        cc.mode = cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2));
-                        cc.div = (float)cfg.n_kernels; cc.in_slope = 0.1f; cc.mid_slope = 0.1f;
-                        cc.out_slope = j + 1 == cfg.n_kernels ? next_slope : 1.f;
-                        if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
-                        const double fl = 3 * 2.0 * (2.0 * h->c1[li0].cin * h->c1[li0].cin * h->c1[li0].k) * mul;
-                        if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        rc = M.chain(h->c1[li0].cin, cc, st);
-                        if (!in_section) prof_end(st);
-                        HG_TRY(rc);
-                        if (multi) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
-                        continue;
-                    }
-                }
-                for (int m = 0; m < cfg.n_dilations; ++m) {
-                    const int li = (i * cfg.n_kernels + j) * cfg.n_dilations + m;
-                    const int d = cfg.resblock_dilations[j][m];
-                    const bool last = m + 1 == cfg.n_dilations;
-                    const ConvW &w1 = h->c1[li], &w2 = h->c2[li];
-                    void* dst = last ? curo : (src == R ? Tb : R);
-                    // running ResBlock sum in `cur`: raw bf16 until the last branch stores it activated for its consumer
-                    const int mode = !last || cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2));
-                    const float out_slope = !last ? 0.1f : (j + 1 == cfg.n_kernels ? next_slope : 1.f);
-                    if (multi && last && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
-                    const double fl = 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * mul;
-                    if (M.pair_supported(w1.cin, w1.k, d, L)) {
-                        BfoPairParams pp;
-                        std::memset(&pp, 0, sizeof(pp));
-                        pp.x = src; pp.y = dst; pp.sum_in = curo;
-                        pp.w1 = W16 + w1.wo.of(M); pp.w2 = W16 + w2.wo.of(M); pp.b1 = h->dev + w1.b_off; pp.b2 = h->dev + w2.b_off;
-                        pp.lens = lens; pp.len_mul = mul; pp.L = L; pp.dil = d; pp.batch = B;
-                        pp.mode = mode; pp.div = (float)cfg.n_kernels; pp.in_slope = 0.1f; pp.mid_slope = 0.1f; pp.out_slope = out_slope;
-                        if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        rc = M.pair(w1.cin, w1.k, pp, st);
-                        if (!in_section) prof_end(st);
-                        HG_TRY(rc);
-                    } else {
-                        // C = 256 (stage 1): c1 and c2 as two launches, the intermediate stored activated for c2.  c2 reads its
-                        // residual only at its own output positions, so it may run in place (dst == src == R)
-                        void* t1 = Tb;
-                        if (!last) dst = R;
-                        cp.x = src; cp.y = t1; cp.w = W16 + w1.wo.of(M); cp.bias = h->dev + w1.b_off; cp.res = nullptr; cp.sum_in = nullptr;
-                        cp.len_mul = mul; cp.Lin = L; cp.Cin = w1.cin; cp.Cout = w1.cout; cp.K = w1.k; cp.dil = d; cp.up = 1;
-                        cp.mode = 0; cp.out_slope = 0.1f; cp.res_slope = 1.f;
-                        cp.splitk_ws = splitks[j % 3]; cp.splitk_floats = kSplitKFloats;     // batch 1: 30 blocks per stage-1 conv
-                        if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        rc = M.conv(cp, st);
-                        if (rc == 0) {
-                            cp.x = t1; cp.y = dst; cp.w = W16 + w2.wo.of(M); cp.bias = h->dev + w2.b_off; cp.res = src; cp.sum_in = curo;
-                            cp.dil = 1; cp.mode = mode; cp.div = (float)cfg.n_kernels; cp.out_slope = out_slope; cp.res_slope = 0.1f;
-                            rc = M.conv(cp, st);
-                        }
-                        if (!in_section) prof_end(st);
-                        HG_TRY(rc);
-                    }
-                    if (multi && last) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
-                    src = dst;
-                }
-            }
-            if (multi) {
-                HG_CHECK_HIP(hipStreamWaitEvent(s, h->ev_done[cfg.n_kernels - 1], 0));
-                in_section = false;
-                prof_section_end(s);
-            }
-        }
-        HG_TRY(M.conv_post(curo, h->dev + h->conv_post.w_off, h->dev + h->conv_post.b_off, lens, mul, B, h->conv_post.cin, L, wave, (int64_t)L, s));
-        return 0;
-    }
-
-    // conv_pre (models.py:112)
-    HG_TRY(conv(h->conv_pre, mel, s, cur, nullptr, T, 1, 1, 1.0f, 0, 1.f));
-    int L = T, mul = 1;
-    for (int i = 0; i < cfg.n_ups; ++i) {
-        const int u = cfg.upsample_rates[i], kt = cfg.upsample_kernel_sizes[i];
-        const ConvW& uw = h->ups[i];
-        // leaky_relu(0.1) + ConvTranspose1d as u polyphase 2-tap convs (models.py:114-115)
-        prof_begin(s, 2.0 * uw.cout * uw.cin * 2 * u * mul);
-        int32_t rc = launch_upsampler(p, cur, h->dev + uw.w_off, h->dev16 + uw.w16_off, h->dev + uw.b_off, ups_out, uw.cin, uw.cout, u, kt, L,
-                                      mul, 0.1f, convt_ok, s, uw.wct_off >= 0 ? h->dev + uw.wct_off : nullptr,
-                                      uw.bct_off >= 0 ? h->dev + uw.bct_off : nullptr);
-        prof_end(s);
-        HG_TRY(rc);
-        L *= u; mul *= u;
-        // 3 ResBlock1 on the same input, averaged (models.py:116-122, 46-53)
-        if (multi) {
-            prof_section_begin(s);
-            in_section = true;
-            HG_CHECK_HIP(hipEventRecord(h->ev_fork, s));
-        }
-        for (int j = 0; h->rb2 && j < cfg.n_kernels; ++j) {
-            // ResBlock2 (models.py:62-83): both convs as one resblock2_pair launch where routed, else two resblock2_conv launches
-            // through Tb (x != y: halo reads).  The second writes the stage sum into `cur` (mode / div as for ResBlock1)
-            hipStream_t st = bs[j % 3];
-            float* Tb = Tbs[j % 3];
-            if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_fork, 0));
-            const int r = i * cfg.n_kernels + j;
-            const ConvW &w1 = h->c1[r], &w2 = h->c2[r];
-            const int d1 = cfg.resblock_dilations[j][0], d2 = cfg.resblock_dilations[j][1];
-            const int mode = cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2));
-            const float div = (float)cfg.n_kernels;
-            const double fl = 2.0 * w1.cout * w1.cin * w1.k * mul;      // per conv
-            if (resblock2_pair_choice(rb2_mask, w1.cin, w1.k, d1, d2, L, ups_out, cur)) {
-                if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
-                if (in_section) prof_add(2 * fl); else prof_begin(st, 2 * fl);
-                const int32_t rc2 = launch_resblock2_pair(w1.cin, ups_out, cur, h->dev + w1.w_off, h->dev + w1.b_off, h->dev + w2.w_off,
-                                                          h->dev + w2.b_off, w1.k, d1, d2, lens, mul, L, B, mode, div, 0.1f, st);
-                if (!in_section) prof_end(st);
-                HG_TRY(rc2);
-            } else {
-                if (in_section) prof_add(fl); else prof_begin(st, fl);
-                int32_t rc2 = launch_resblock2_conv(w1.cin, ups_out, Tb, h->dev + w1.w_off, h->dev + w1.b_off, w1.k, d1, lens, mul, L, B,
-                                                    0, 1.f, 0.1f, st);
-                if (!in_section) prof_end(st);
-                HG_TRY(rc2);
-                if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
-                if (in_section) prof_add(fl); else prof_begin(st, fl);
-                rc2 = launch_resblock2_conv(w2.cin, Tb, cur, h->dev + w2.w_off, h->dev + w2.b_off, w2.k, d2, lens, mul, L, B, mode, div,
-                                            0.1f, st);
-                if (!in_section) prof_end(st);
-                HG_TRY(rc2);
-            }
-            if (multi) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
-        }
-        for (int j = 0; !h->rb2 && j < cfg.n_kernels; ++j) {
-            hipStream_t st = bs[j % 3];
-            float *Tb = Tbs[j % 3], *R = Rs[j % 3];
-            p.splitk_ws = splitks[j % 3];
-            if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_fork, 0));
-            const float* src = ups_out;
-            for (int m = 0; m < cfg.n_dilations; ++m) {
-                const int li = (i * cfg.n_kernels + j) * cfg.n_dilations + m;
-                const int d = cfg.resblock_dilations[j][m];
-                // C = 32 stage (and k = 3 of the C = 64 stage), fp32: the c1 -> c2 pair in one launch with the intermediate in LDS (resblock_fused.hip);
-                // x and y must differ (halo reads), so the pair outputs alternate between R and the unused c1 buffer
-                {
-                    const bool last = m + 1 == cfg.n_dilations;
-                    float* dst = last ? cur : (src == R ? Tb : R);
-                    const ConvW &w1 = h->c1[li], &w2 = h->c2[li];
-                    const bool square = w1.cin == w1.cout && w2.cin == w1.cin && w2.cout == w1.cin && w1.k == w2.k;
-                    const int ntw2 = (fused_ok && square) ? fused2_choice(f2sw, w1.cin, w1.k, d, L, src, dst, (int64_t)B * L) : 0;
-                    // the F(2,3) pair with both phases on Winograd -> its F(4,3) successor where it is built (C = 32)
-                    const bool f43 = ntw2 == 2 && f2sw.pair4 && f2sw.wino_a && w1.k >= kPair4MinK && w1.ww4_off >= 0 && w2.ww4_off >= 0 &&
-                                     fused_pair4_supported(w1.cin, w1.k, d, L, src, dst);
-                    const bool f44 = f43 && f2sw.pair44 && (kPair44Mask & (w1.k == 7 ? 1u : (w1.k == 11 ? 2u : 0u))) != 0 &&
-                                     w1.ww44_off >= 0 && w2.ww44_off >= 0;
-                    if (ntw2 != 0 || (fused_ok && square && fused_pair_supported(w1.cin, w1.k, d, L, src, dst))) {
-                        const int mode = !last ? 0 : (cfg.n_kernels == 1 ? 0 : (j == 0 ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2)));
-                        if (multi && last && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
-                        const double fl = 2.0 * (2.0 * w1.cin * w1.cin * w1.k) * mul;
-                        if (in_section) prof_add(fl); else prof_begin(st, fl);
-                        const int32_t frc = f44
-                            ? launch_fused_pair4(w1.cin, src, dst, h->dev + w1.ww44_off, h->dev + w1.b_off, h->dev + w2.ww44_off,
-                                                 h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, st, 7)
-                            : f43
-                            ? launch_fused_pair4(w1.cin, src, dst, h->dev + w1.ww4_off, h->dev + w1.b_off, h->dev + w2.ww4_off,
-                                                 h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, st)
-                            : ntw2 != 0
-                            ? launch_fused_pair2(w1.cin, src, dst, h->dev + w1.w_off, h->dev + w1.b_off, h->dev + w2.w_off,
-                                                 h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, ntw2, st,
-                                                 (f2sw.wino_b && w2.ww_off >= 0) ? h->dev + w2.ww_off : nullptr,
-                                                 (f2sw.wino_a && w1.ww_off >= 0) ? h->dev + w1.ww_off : nullptr)
-                            : launch_fused_pair(w1.cin, src, dst, h->dev + w1.w_off, h->dev + w1.b_off, h->dev + w2.w_off,
-                                                h->dev + w2.b_off, w1.k, d, lens, mul, L, B, mode, (float)cfg.n_kernels, 0.1f, st);
-                        if (!in_section) prof_end(st);
-                        HG_TRY(frc);
-                        if (multi && last) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
-                        src = dst;
-                        continue;
-                    }
-                }
-                pack_io = pack_t ? 2 : 0;
-                HG_TRY(conv(h->c1[li], src, st, Tb, nullptr, L, mul, d, 0.1f, 0, 1.f));
-                pack_io = pack_t ? 1 : 0;
-                if (m + 1 < cfg.n_dilations) {
-                    HG_TRY(conv(h->c2[li], Tb, st, R, src, L, mul, 1, 0.1f, 0, 1.f));
-                    pack_io = 0;
-                    src = R;
-                } else {
-                    const int mode = (j == 0) ? 0 : (j + 1 < cfg.n_kernels ? 1 : 2);
-                    const int md = cfg.n_kernels == 1 ? 0 : mode;
-                    // the accumulation into `cur` follows branch j-1's
-                    if (multi && j > 0) HG_CHECK_HIP(hipStreamWaitEvent(st, h->ev_done[j - 1], 0));
-                    HG_TRY(conv(h->c2[li], Tb, st, cur, src, L, mul, 1, 0.1f, md, (float)cfg.n_kernels));
-                    pack_io = 0;
-                    if (multi) HG_CHECK_HIP(hipEventRecord(h->ev_done[j], st));
-                }
-            }
-        }
-        p.splitk_ws = splitks[0];
-        if (multi) {
-            HG_CHECK_HIP(hipStreamWaitEvent(s, h->ev_done[cfg.n_kernels - 1], 0));
-            in_section = false;
-            prof_section_end(s);
-        }
-    }
-    // leaky_relu (default slope 0.01) + conv_post + tanh (models.py:123-125)
-    HG_TRY(launch_conv_post(cur, (int64_t)h->conv_post.cin * L, L, h->dev + h->conv_post.w_off,
-                             h->dev + h->conv_post.b_off, lens, mul, B, h->conv_post.cin, L, 0.01f, wave,
-                             (int64_t)L, s));
-#undef HG_TRY
-#undef HG_CHECK_HIP
-    return 0;
+    StageSchedule sch{h, s, multi, {s, multi ? h->side[0] : s, multi ? h->side[1] : s}};
+    HgCall c = {h, lens, B, prec, w, sch};     // (the rest zeroed)
+    c.base.batch = B; c.base.lens_in = lens; c.base.lens_out = lens;
+    c.base.n_phase = 1; c.base.div = 1.f; c.base.pack_slope = 0.1f;
+    c.base.splitk_floats = kSplitKFloats;     // batch 1: stage-1 launches have < 256 tiles
+    c.pack_t = prec == 1 && opt_int(OPT_BF16_PACKED_T, 1) != 0;
+    c.pair_opts = pair_route_opts();
+    c.rb2_mask = (unsigned)opt_int(OPT_RESBLOCK2_PAIR, kResblock2PairMask);
+    const bool octet = (prec == 1 || prec == 2) && h->bfo_ok && opt_int(OPT_BFO, 1) != 0;
+    return sch.fail(octet ? octet_forward(c, mel, T, wave) : f32_forward(c, mel, T, wave));
 }
 
 // the config a handle was created with (resblock already 1 / 2): what stream.hip derives the receptive field from

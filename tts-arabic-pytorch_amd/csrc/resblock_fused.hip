@@ -338,19 +338,18 @@ bool fused_pair_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, c
            (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && x != y && (int64_t)channels * L * 4 < ((int64_t)1 << 31);
 }
 
-int32_t launch_fused_pair(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
-                          const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                          int32_t mode, float div, float slope, hipStream_t stream) {
-    TTS_REQUIRE(fused_pair_supported(channels, k, dil, L, x, y), "fused ResBlock pair: unsupported geometry (C=%d, k=%d, dil=%d, L=%d)",
-                channels, k, dil, L);
-    conv_log("fused_pair", k, channels, channels, L, batch, 1, mode, len_mul, lens != nullptr, 1);
+int32_t launch_fused_pair(const PairArgs& a, hipStream_t stream) {
+    const int32_t channels = a.channels, k = a.k;
+    TTS_REQUIRE(fused_pair_supported(channels, k, a.dil, a.L, a.x, a.y), "fused ResBlock pair: unsupported geometry (C=%d, k=%d, dil=%d, L=%d)",
+                channels, k, a.dil, a.L);
+    conv_log("fused_pair", k, channels, channels, a.L, a.batch, 1, a.mode, a.len_mul, a.lens != nullptr, 1);
     FusedPairParams p;
     std::memset(&p, 0, sizeof(p));
-    p.x = x; p.y = y;
-    p.w1 = reinterpret_cast<const float4*>(w1); p.w2 = reinterpret_cast<const float4*>(w2);
-    p.b1 = b1; p.b2 = b2; p.lens = lens; p.len_mul = len_mul; p.L = L; p.dil = dil; p.batch = batch;
-    p.mode = mode; p.div = div; p.slope = slope;
-    p.compact = compact_order(lens, batch) ? 1 : 0;
+    p.x = a.x; p.y = a.y;
+    p.w1 = reinterpret_cast<const float4*>(a.c1.w); p.w2 = reinterpret_cast<const float4*>(a.c2.w);
+    p.b1 = a.c1.b; p.b2 = a.c2.b; p.lens = a.lens; p.len_mul = a.len_mul; p.L = a.L; p.dil = a.dil; p.batch = a.batch;
+    p.mode = a.mode; p.div = a.div; p.slope = a.slope;
+    p.compact = compact_order(a.lens, a.batch) ? 1 : 0;
     if (channels == 64) return launch_fused_k<3, 64>(p, stream);
     switch (k) {
         case 3: return launch_fused_k<3, 32>(p, stream);

@@ -628,43 +628,33 @@ bool fused_pair2_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, 
     return lds <= 160 * 1024;
 }
 
-int32_t launch_fused_pair2(int32_t channels, const float* x, float* y, const float* w1, const float* b1, const float* w2,
-                           const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                           int32_t mode, float div, float slope, int32_t ntw, hipStream_t stream, const float* w2_wino,
-                           const float* w1_wino) {
-    TTS_REQUIRE(fused_pair2_supported(channels, k, dil, L, x, y, ntw),
-                "fused ResBlock pair (direct weights): unsupported geometry (C=%d, k=%d, dil=%d, L=%d, ntw=%d)", channels, k, dil, L, ntw);
-    TTS_REQUIRE(slope > 0.f && slope <= 1.f, "fused ResBlock pair: leaky-relu slope %g outside (0, 1]", (double)slope);
-    // w2_wino (conv 2 as Winograd groups, pack_wino2_weight): phase B on F(2,3) -- 256-column blocks of C = 32 / 64 only
-    // ... + w1_wino: phase A too (dilations 1 / 3 / 5: 256 / 252 / 250 intermediate columns per block)
-    const bool wa = w2_wino != nullptr && w1_wino != nullptr && ntw == 2 && (dil == 1 || dil == 3 || dil == 5);   // C = 128: 8 waves
-    const bool wb = w2_wino != nullptr && ntw == 2 && (channels <= 64 || wa);
-    conv_log(wa ? "fused_pair2ww" : wb ? "fused_pair2w" : (ntw == 2 ? "fused_pair2" : "fused_pair2n"), k, channels, channels, L, batch, 1, mode, len_mul, lens != nullptr, 1);
+int32_t launch_fused_pair2(const PairArgs& a, const PairRoute& r, hipStream_t stream) {
+    const int32_t channels = a.channels, k = a.k, ntw = r.ntw;
+    TTS_REQUIRE(r.kernel == PAIR_GEN2 && fused_pair2_supported(channels, k, a.dil, a.L, a.x, a.y, ntw),
+                "fused ResBlock pair (direct weights): unsupported geometry (C=%d, k=%d, dil=%d, L=%d, ntw=%d)", channels, k, a.dil, a.L, ntw);
+    TTS_REQUIRE(a.slope > 0.f && a.slope <= 1.f, "fused ResBlock pair: leaky-relu slope %g outside (0, 1]", (double)a.slope);
+    const bool wa = r.wm == 2, wb = r.wm >= 1;   // the route's phases on Winograd F(2,3) groups: phase A (conv 1) / phase B (conv 2)
+    TTS_REQUIRE(r.wm >= 0 && r.wm <= 2 && pair2_phases_built(channels, a.dil, ntw, r.wm) && (!wb || a.c2.w_wino2) && (!wa || a.c1.w_wino2),
+                "fused ResBlock pair: %d Winograd phase(s) at C=%d, dil=%d, ntw=%d are not built, or their weights are missing", r.wm, channels,
+                a.dil, ntw);
+    conv_log(r.name, k, channels, channels, a.L, a.batch, 1, a.mode, a.len_mul, a.lens != nullptr, 1);
     FusedPair2Params p;
     std::memset(&p, 0, sizeof(p));
-    p.x = x; p.y = y;
-    p.w1 = reinterpret_cast<const float4*>(w1); p.w2 = reinterpret_cast<const float4*>(w2);
-    p.w2w = reinterpret_cast<const float4*>(w2_wino);
-    p.w1w = reinterpret_cast<const float4*>(w1_wino);
-    p.b1 = b1; p.b2 = b2; p.lens = lens; p.len_mul = len_mul; p.L = L; p.dil = dil; p.batch = batch;
-    p.mode = mode; p.div = div; p.slope = slope;
-    p.compact = compact_order(lens, batch) ? 1 : 0;
-#define TTS_F2W(KK, CC) if (wa && k == KK && channels == CC) return launch_fused2_k<KK, CC, 2, 2>(p, stream); \
-                        if (wb && k == KK && channels == CC) return launch_fused2_k<KK, CC, 2, 1>(p, stream);
-    TTS_F2W(3, 32) TTS_F2W(7, 32) TTS_F2W(11, 32) TTS_F2W(3, 64) TTS_F2W(7, 64) TTS_F2W(11, 64)
-#undef TTS_F2W
-    if (wa && channels == 128) {
-        if (k == 3) return launch_fused2_k<3, 128, 2, 2>(p, stream);
-        if (k == 7) return launch_fused2_k<7, 128, 2, 2>(p, stream);
-        if (k == 11) return launch_fused2_k<11, 128, 2, 2>(p, stream);
-    }
-#define TTS_F2(KK, CC, NN) if (k == KK && channels == CC && ntw == NN) return launch_fused2_k<KK, CC, NN, 0>(p, stream);
-    TTS_F2(3, 32, 2) TTS_F2(7, 32, 2) TTS_F2(11, 32, 2)
-    TTS_F2(3, 64, 2) TTS_F2(7, 64, 2) TTS_F2(11, 64, 2)
-    TTS_F2(3, 128, 2) TTS_F2(7, 128, 2) TTS_F2(11, 128, 2)
-    TTS_F2(3, 32, 1) TTS_F2(7, 32, 1) TTS_F2(11, 32, 1)
-    TTS_F2(3, 64, 1) TTS_F2(7, 64, 1) TTS_F2(11, 64, 1)
-    TTS_F2(3, 128, 1) TTS_F2(7, 128, 1) TTS_F2(11, 128, 1)
+    p.x = a.x; p.y = a.y;
+    p.w1 = reinterpret_cast<const float4*>(a.c1.w); p.w2 = reinterpret_cast<const float4*>(a.c2.w);
+    p.w2w = reinterpret_cast<const float4*>(wb ? a.c2.w_wino2 : nullptr);
+    p.w1w = reinterpret_cast<const float4*>(wa ? a.c1.w_wino2 : nullptr);
+    p.b1 = a.c1.b; p.b2 = a.c2.b; p.lens = a.lens; p.len_mul = a.len_mul; p.L = a.L; p.dil = a.dil; p.batch = a.batch;
+    p.mode = a.mode; p.div = a.div; p.slope = a.slope;
+    p.compact = compact_order(a.lens, a.batch) ? 1 : 0;
+    // every instantiation, by (k, C, block width, Winograd phases): the route names one of them
+#define TTS_F2(KK, CC, NN, WW) if (k == KK && channels == CC && ntw == NN && r.wm == WW) return launch_fused2_k<KK, CC, NN, WW>(p, stream);
+#define TTS_F2K(CC, NN, WW) TTS_F2(3, CC, NN, WW) TTS_F2(7, CC, NN, WW) TTS_F2(11, CC, NN, WW)
+    TTS_F2(3, 32, 2, 2) TTS_F2(3, 32, 2, 1) TTS_F2(7, 32, 2, 2) TTS_F2(7, 32, 2, 1) TTS_F2(11, 32, 2, 2) TTS_F2(11, 32, 2, 1)
+    TTS_F2(3, 64, 2, 2) TTS_F2(3, 64, 2, 1) TTS_F2(7, 64, 2, 2) TTS_F2(7, 64, 2, 1) TTS_F2(11, 64, 2, 2) TTS_F2(11, 64, 2, 1)
+    TTS_F2K(128, 2, 2)
+    TTS_F2K(32, 2, 0) TTS_F2K(64, 2, 0) TTS_F2K(128, 2, 0) TTS_F2K(32, 1, 0) TTS_F2K(64, 1, 0) TTS_F2K(128, 1, 0)
+#undef TTS_F2K
 #undef TTS_F2
     set_error("fused ResBlock pair (direct weights): no instantiation for C=%d, k=%d, ntw=%d", channels, k, ntw);
     return TTSAMD_EINVAL;

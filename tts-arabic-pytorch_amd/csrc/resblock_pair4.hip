@@ -32,7 +32,7 @@
 // / 11 -- they do not fit.  So phase B forms V0..V5 on the operand path, like phase A: six entry reads and ~13 packed VALU operations
 // per sub-filter, next to its 24 MFMAs (seven-point: seven / six reads and 42 / 36 packed operations next to 28 / 24 MFMAs).  The window is staged ACTIVATED (one leaky-relu per value, not per use), so the residual comes
 // from global memory in the epilogue (an L2 hit: the block read the same lines at its start), next to the running ResBlock sum.
-// Routing (hifigan.hip): k = 7 / 11 only, TTSAMD_PAIR4 = 1 (default): the seven-point form at the k of kPair44Mask, 2: the six-point
+// Routing (conv_route.hip: pair_route): k = 7 / 11 only, TTSAMD_PAIR4 = 1 (default): the seven-point form at the k of kPair44Mask, 2: the six-point
 // form (profiles/r28/NOTES.md).  k = 3 is built and tested (ttsamd_resblock_pair variant 6; variant 7 = the seven-point form) but
 // measured slower than resblock_pair2 (profiles/r7/NOTES.md).
 // Epilogue straight from the accumulators: phase B is dilation 1, so a lane's quad is 4 contiguous outputs of a row -- a 16-byte store,
@@ -413,24 +413,24 @@ bool fused_pair4_supported(int32_t channels, int32_t k, int32_t dil, int32_t L, 
     return (int64_t)channels * L * 4 < ((int64_t)1 << 31);
 }
 
-int32_t launch_fused_pair4(int32_t channels, const float* x, float* y, const float* w1_wino4, const float* b1, const float* w2_wino4,
-                           const float* b2, int32_t k, int32_t dil, const int64_t* lens, int32_t len_mul, int32_t L, int32_t batch,
-                           int32_t mode, float div, float slope, hipStream_t stream, int32_t points) {
-    TTS_REQUIRE(fused_pair4_supported(channels, k, dil, L, x, y),
-                "fused ResBlock pair (F(4,3)): unsupported geometry (C=%d, k=%d, dil=%d, L=%d)", channels, k, dil, L);
+int32_t launch_fused_pair4(const PairArgs& a, const PairRoute& r, hipStream_t stream) {
+    const int32_t channels = a.channels, k = a.k, points = r.points;
+    const float *w1 = points == 7 ? a.c1.w_wino44 : a.c1.w_wino4, *w2 = points == 7 ? a.c2.w_wino44 : a.c2.w_wino4;
+    TTS_REQUIRE(r.kernel == PAIR_F43 && fused_pair4_supported(channels, k, a.dil, a.L, a.x, a.y),
+                "fused ResBlock pair (F(4,3)): unsupported geometry (C=%d, k=%d, dil=%d, L=%d)", channels, k, a.dil, a.L);
     TTS_REQUIRE(points == 6 || (points == 7 && (k == 7 || k == 11)),
                 "fused ResBlock pair (F(4,3)): %d-point groups at k = %d (six-point: k = 3 / 7 / 11, seven-point: k = 7 / 11)", points, k);
-    TTS_REQUIRE(w1_wino4 && w2_wino4 && b1 && b2, "fused ResBlock pair (F(4,3)): null weights");
-    TTS_REQUIRE(slope > 0.f && slope <= 1.f, "fused ResBlock pair (F(4,3)): leaky-relu slope %g outside (0, 1]", (double)slope);
-    TTS_REQUIRE(mode >= 0 && mode <= 2 && (mode != 2 || div != 0.f), "fused ResBlock pair (F(4,3)): bad mode / div");
-    conv_log(points == 7 ? "fused_pair44" : "fused_pair4", k, channels, channels, L, batch, 1, mode, len_mul, lens != nullptr, 1);
+    TTS_REQUIRE(w1 && w2 && a.c1.b && a.c2.b, "fused ResBlock pair (F(4,3)): null weights");
+    TTS_REQUIRE(a.slope > 0.f && a.slope <= 1.f, "fused ResBlock pair (F(4,3)): leaky-relu slope %g outside (0, 1]", (double)a.slope);
+    TTS_REQUIRE(a.mode >= 0 && a.mode <= 2 && (a.mode != 2 || a.div != 0.f), "fused ResBlock pair (F(4,3)): bad mode / div");
+    conv_log(r.name, k, channels, channels, a.L, a.batch, 1, a.mode, a.len_mul, a.lens != nullptr, 1);
     FusedPair4Params p;
     std::memset(&p, 0, sizeof(p));
-    p.x = x; p.y = y;
-    p.w1 = reinterpret_cast<const float4*>(w1_wino4); p.w2 = reinterpret_cast<const float4*>(w2_wino4);
-    p.b1 = b1; p.b2 = b2; p.lens = lens; p.len_mul = len_mul; p.L = L; p.dil = dil; p.batch = batch;
-    p.mode = mode; p.div = div; p.slope = slope;
-    p.compact = compact_order(lens, batch) ? 1 : 0;
+    p.x = a.x; p.y = a.y;
+    p.w1 = reinterpret_cast<const float4*>(w1); p.w2 = reinterpret_cast<const float4*>(w2);
+    p.b1 = a.c1.b; p.b2 = a.c2.b; p.lens = a.lens; p.len_mul = a.len_mul; p.L = a.L; p.dil = a.dil; p.batch = a.batch;
+    p.mode = a.mode; p.div = a.div; p.slope = a.slope;
+    p.compact = compact_order(a.lens, a.batch) ? 1 : 0;
     if (points == 7) return k == 7 ? launch_pair4_k<7, 7>(p, stream) : launch_pair4_k<11, 7>(p, stream);
     if (k == 3) return launch_pair4_k<3>(p, stream);
     if (k == 7) return launch_pair4_k<7>(p, stream);

@@ -849,6 +849,16 @@ def conv_route(batch, cin, cout, k, lin, dilation=1, in_slope=1.0, relu_out=Fals
     return route.value, ksplit.value
 
 
+def pair_route(batch, channels, k, lin, dilation=1):
+    """What HifiGanEngine.forward launches for the c1 -> c2 pair of a ResBlock1 at a stage of `lin` positions per row under the current
+    options (ttsamd_resblock_pair_route; host only, no GPU): {'kernel': 0 two convs | 1 resblock_pair | 2 resblock_pair2 | 3 resblock_pair4,
+    'ntw', 'wino_phases' (kernel 2), 'points' (kernel 3), 'name': the TTSAMD_CONV_LOG kind}."""
+    kernel, ntw, wm, points, name = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_char_p()
+    L.check(L.load().ttsamd_resblock_pair_route(batch, channels, k, dilation, lin, C.byref(kernel), C.byref(ntw), C.byref(wm), C.byref(points),
+                                                C.byref(name)), 'resblock_pair_route')
+    return {'kernel': kernel.value, 'ntw': ntw.value, 'wino_phases': wm.value, 'points': points.value, 'name': name.value.decode()}
+
+
 def conv_transpose1d(x, w, bias=None, lens=None, in_slope=1.0, y=None):
     """Kernel-level entry (parity tests): one HiFi-GAN upsampler as the generator launches it (ttsamd_conv_transpose1d),
     y = conv_transpose1d(lrelu(x), w, stride=u, padding=u // 2) + b for w [Cin][Cout][2u] (torch layout); x [B][Cin][L] -> y [B][Cout][L * u];

@@ -210,6 +210,7 @@ SYMBOLS = {
     'ttsamd_convt_wino_pack_weight': (_I32, [_P, _P, _I32, _I32, _I32, _P]),
     'ttsamd_resblock_pair_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_resblock_pair': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
+    'ttsamd_resblock_pair_route': (_I32, [_I32, _I32, _I32, _I32, _I32] + [C.POINTER(_I32)] * 4 + [C.POINTER(C.c_char_p)]),
     'ttsamd_resblock2_packed_floats': (_I64, [_I32, _I32, _I32]),
     'ttsamd_resblock2': (_I32, [_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _F, _F, _I32, _P, _I64, _P]),
     'ttsamd_set_precision': (_I32, [_I32]),
