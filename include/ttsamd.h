@@ -1220,6 +1220,41 @@ int32_t ttsamd_wave_sdr(const float* ref, const float* est, int64_t wave_stride,
 int32_t ttsamd_log_spectral_distance(const float* ref, const float* est, int64_t wave_stride, const int64_t* nsamples, int32_t batch,
                                      double* out, void* stream);
 
+/* ---- multi-resolution STFT distance (csrc/mrstft.hip): the spectral convergence and the log-magnitude distance of Parallel WaveGAN's
+ * loss, per resolution, between the rows of two sample-aligned ragged mono batches, with the conventions of the block above: both waves
+ * [batch][wave_stride] fp32, nsamples device int64 [batch] clamped to [0, wave_stride], nothing at or past nsamples[b] read into a
+ * result, nothing read back to the host, float64 after the fp32 samples are loaded (window products, the transforms: the template of
+ * the block above at 512, 1024 and 2048 points, magnitudes, logarithms, every sum), no floating-point atomics and a fixed order in
+ * every reduction that depends on the row's own length only: row b of a batch has the bits of the call on row b alone, and two runs
+ * give the same bits.  1 <= batch <= 65535, 0 <= wave_stride < 2^31.
+ * Specified by the arithmetic below; the framing is torch.stft(center=True, pad_mode='reflect')'s, parity with auraloss or with
+ * Parallel WaveGAN's batch-wide sums is not pinned (there the sums run over a padded batch; here over the row's own frames only).
+ *
+ * n_res resolutions, 1 <= n_res <= 8, each (N = n_fft[r], H = hop[r], W = win[r]) with N in {512, 1024, 2048}, 1 <= W <= N, H >= 1
+ * (HOST arrays).  For row b with n = nsamples[b] samples, for ref and for est:
+ *  1. Window: w[i] = 0.5 - 0.5 cos(2 pi i / W) for i < W (periodic Hann), placed at offset (N - W) / 2 (rounded down) inside a frame of
+ *     N, zero elsewhere.
+ *  2. Reflect padding by P = N / 2 on both sides: padded index p maps to j = p - P, j < 0 -> -j, j >= n -> 2 (n - 1) - j.  This needs
+ *     n > P: for a row with n <= P this resolution gives NaN for both numbers and 0 frames.
+ *  3. F = 1 + n / H frames (rounded down); frame f is padded[f H : f H + N] * w, X[f][k] its N-point DFT for k = 0 .. N / 2.
+ *  4. S[f][k] = sqrt(max(re^2 + im^2, 1e-7)).
+ *  5. Spectral convergence: sc = sqrt(sum_{f,k} (S_ref - S_est)^2) / sqrt(sum_{f,k} S_ref^2).
+ *  6. Log-magnitude distance: mag = sum_{f,k} |ln S_ref - ln S_est| / (F (N / 2 + 1)).
+ * An identical pair gives exactly (0, 0): the two signals go through the same transform one after the other.
+ * out: device float64 [batch][n_res][2] = (sc, mag); frames: device int32 [batch][n_res] = F.
+ * n_res + 1 launches whatever the lengths: per resolution a block of N / 4 threads per 16 consecutive frames of a row writes its three
+ * partial sums to the workspace (a thread adds the terms of its bins frame after frame; the block sums its threads by a butterfly over
+ * the lanes of each wave, then the waves in ascending order); the last launch adds a row's partial sums in ascending order. */
+/* bytes of workspace ttsamd_mr_stft needs; -1: refused (batch outside 1 .. 65535, wave_stride negative or so long that a resolution has
+ * 2^31 frames or more, n_res outside 1 .. 8, a NULL array, a resolution outside the ranges above) */
+int64_t ttsamd_mr_stft_workspace_bytes(int32_t batch, int64_t wave_stride, const int32_t* n_fft, const int32_t* hop, const int32_t* win,
+                                       int32_t n_res);
+/* TTSAMD_EINVAL (nothing launched, out and frames untouched): a NULL pointer, anything ttsamd_mr_stft_workspace_bytes refuses, a
+ * workspace smaller than ttsamd_mr_stft_workspace_bytes. */
+int32_t ttsamd_mr_stft(const float* ref, const float* est, int64_t wave_stride, const int64_t* nsamples, int32_t batch, const int32_t* n_fft,
+                       const int32_t* hop, const int32_t* win, int32_t n_res, double* out, int32_t* frames, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* Timing hooks for bench.py (roofline of the dominant kernel): when enabled, hifigan
  * forward brackets its ResBlock conv launches with HIP events on the launch stream. */
 int32_t ttsamd_profile_enable(int32_t on);

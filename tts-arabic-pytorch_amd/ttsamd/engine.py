@@ -2094,6 +2094,39 @@ def log_spectral_distance(wave_ref, wave_est, lens=None):
     return out
 
 
+MR_STFT_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))   # (n_fft, hop, win_length): Parallel WaveGAN's three
+
+
+def mr_stft(wave_ref, wave_est, lens=None, resolutions=MR_STFT_RESOLUTIONS):
+    """wave_ref, wave_est [B, n] on the device, lens int64 [B] or None, resolutions: 1 .. 8 triples (n_fft in 512 / 1024 / 2048, hop,
+    win_length <= n_fft) -> (float64 [B, R, 2] = (spectral convergence, log-magnitude distance) per resolution, frames int32 [B, R]):
+    torch.stft's framing (periodic Hann centred in the frame, reflect padding by n_fft / 2, 1 + n // hop frames), S = sqrt(max(|X|^2,
+    1e-7)), sc = ||S_ref - S_est|| / ||S_ref||, mag = mean |ln S_ref - ln S_est| over the row's own frames.  NaN and 0 frames for a row
+    of n_fft / 2 samples or fewer.  R + 1 launches (ttsamd_mr_stft), float64 throughout; specified by the arithmetic in include/ttsamd.h."""
+    lib = _require_gpu()
+    ref, est, lens, B, W = _wave_pair(wave_ref, wave_est, lens, 'mr_stft')
+    try:
+        res = [tuple(int(v) for v in r) for r in resolutions]
+    except (TypeError, ValueError):
+        raise L.TtsAmdError(f'mr_stft: resolutions {resolutions!r} are not (n_fft, hop, win_length) triples') from None
+    if any(len(r) != 3 for r in res):
+        raise L.TtsAmdError(f'mr_stft: resolutions {resolutions!r} are not (n_fft, hop, win_length) triples')
+    R = len(res)
+    arr = [(C.c_int32 * max(R, 1))(*(r[q] for r in res)) for q in range(3)]
+    out = torch.empty(B, R, 2, dtype=torch.float64, device=ref.device)
+    frames = torch.zeros(B, R, dtype=torch.int32, device=ref.device)
+    if B:
+        nbytes = int(lib.ttsamd_mr_stft_workspace_bytes(B, W, arr[0], arr[1], arr[2], R))
+        if nbytes < 0:
+            raise L.TtsAmdError(f'mr_stft: a batch of {B} rows of {W} samples at the resolutions {res} is refused (1 .. 8 of n_fft 512 / '
+                                f'1024 / 2048, 1 <= win_length <= n_fft, hop >= 1)')
+        ws = _wavescore_ws.get(max(nbytes, 1), ref.device)
+        with torch.cuda.device(ref.device):
+            L.check(lib.ttsamd_mr_stft(_ptr(ref), _ptr(est), W, _ptr(lens), B, arr[0], arr[1], arr[2], R, _ptr(out), _ptr(frames), _ptr(ws),
+                                       nbytes, _stream()), 'mr_stft')
+    return out, frames
+
+
 class WaveScoreEngine:
     """Wave against wave at `sample_rate`, sample for sample (csrc/wavescore.hip): STOI / ESTOI (after the engine's own
     ResampleEngine(sample_rate, 10000, lowpass_filter_width=64, rolloff=0.99): the project's resampler, not pystoi's), SI-SDR / SNR and
@@ -2134,6 +2167,11 @@ class WaveScoreEngine:
         sdr = wave_sdr(ref, est, lens)
         lsd = log_spectral_distance(ref, est, lens)
         return dict(stoi=st, estoi=es, si_sdr=sdr[:, 0], snr=sdr[:, 1], lsd=lsd[:, 0], frames=fr[:, 0], frames_kept=fr[:, 1])
+
+    def mr_stft(self, wave_ref, wave_est, lens=None, resolutions=MR_STFT_RESOLUTIONS):
+        """-> (float64 [B, R, 2] = (spectral convergence, log-magnitude distance) per resolution, frames int32 [B, R]) of the
+        module-level mr_stft at the waves' own rate"""
+        return mr_stft(wave_ref, wave_est, lens, resolutions)
 
 
 _wave_scorers = {}

@@ -180,6 +180,9 @@ SYMBOLS = {
     'ttsamd_stoi': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _I64, _P]),
     'ttsamd_wave_sdr': (_I32, [_P, _P, _I64, _P, _I32, _I32, _P, _P]),
     'ttsamd_log_spectral_distance': (_I32, [_P, _P, _I64, _P, _I32, _P, _P]),
+    # multi-resolution STFT distance (csrc/mrstft.hip): the resolution arrays are HOST int32 [n_res]
+    'ttsamd_mr_stft_workspace_bytes': (_I64, [_I32, _I64, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32]),
+    'ttsamd_mr_stft': (_I32, [_P, _P, _I64, _P, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32, _P, _P, _P, _I64, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

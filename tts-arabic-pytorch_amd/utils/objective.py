@@ -109,9 +109,11 @@ def evaluate_waves(wave_pred, wave_ref, n_coef=13, align='dtw', window=None, len
 # not sample-aligned with a recording, so a wave-level score of it would be meaningless: evaluate_waves and FastPitch2Wave.evaluate stay
 # on the DTW-aligned feature scores above and do not call these.  Specified by their arithmetic (include/ttsamd.h, restated in float64
 # by tests/wavescore_ref.py); parity with a release of pystoi is not pinned, and the 10 kHz resampling is the project's own resampler
-# (lowpass_filter_width = 64), not pystoi's.  float64 throughout.  Out of scope: PESQ, multi-resolution STFT losses, VISQOL, use as
-# training losses, time alignment of unaligned waves.
+# (lowpass_filter_width = 64), not pystoi's.  float64 throughout.  The multi-resolution STFT distance (csrc/mrstft.hip, restated by
+# tests/mrstft_ref.py) is specified by its arithmetic; the framing is `torch.stft`'s, parity with `auraloss` or Parallel WaveGAN's
+# batch-wide sums unpinned.  Out of scope: PESQ, VISQOL, use as training losses, time alignment of unaligned waves.
 WAVE_KEYS = ('stoi', 'estoi', 'si_sdr', 'snr', 'lsd', 'frames', 'frames_kept')
+MR_STFT_KEYS = ('mr_stft', 'spectral_convergence', 'log_stft_magnitude', 'per_resolution', 'frames')
 
 
 def _wave_pair(wave_a, wave_b, lens, what):
@@ -157,19 +159,67 @@ def log_spectral_distance(wave_est, wave_ref, lens=None):
     return _out(E.log_spectral_distance(r, e, n)[:, 0], was_np, batched)
 
 
-def wave_metrics(wave_est, wave_ref, fs=22050, lens=None):
+def _resolutions(fft_sizes, hop_sizes, win_lengths, what):
+    try:
+        res = tuple(zip(*(tuple(int(v) for v in a) for a in (fft_sizes, hop_sizes, win_lengths)), strict=True))
+    except (TypeError, ValueError):
+        raise TtsAmdError(f'{what}: fft_sizes {fft_sizes!r}, hop_sizes {hop_sizes!r} and win_lengths {win_lengths!r} are not three '
+                          f'sequences of integers of one length') from None
+    return res
+
+
+def _mr_scores(per, frames):
+    """per [B, R, 2], frames [B, R] -> the MR_STFT_KEYS dict of device tensors; NaN where any resolution is NaN (the mean over them)"""
+    sc, mag = per[:, :, 0].mean(dim=1), per[:, :, 1].mean(dim=1)
+    return dict(mr_stft=sc + mag, spectral_convergence=sc, log_stft_magnitude=mag, per_resolution=per, frames=frames)
+
+
+def multi_resolution_stft(wave_est, wave_ref, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), lens=None):
+    """Multi-resolution STFT distance of wave_est [n] against the sample-aligned wave_ref [n] (Parallel WaveGAN's three resolutions by
+    default; n_fft in 512 / 1024 / 2048, up to eight).  Per resolution, on torch.stft's framing (center=True, reflect padding, periodic
+    Hann of win_length centred in the frame) with S = sqrt(max(|X|^2, 1e-7)): the spectral convergence ||S_ref - S_est|| / ||S_ref|| and
+    the log-magnitude distance mean |ln S_ref - ln S_est|, over the row's own frames.  -> {mr_stft, spectral_convergence,
+    log_stft_magnitude, per_resolution [R, 2], frames [R]}: the two means over the resolutions, their sum first; NaN where any resolution
+    is NaN (a row of n_fft / 2 samples or fewer).  The two waves share `lens`; rows of different padded width are compared over the min
+    of the two."""
+    res = _resolutions(fft_sizes, hop_sizes, win_lengths, 'multi_resolution_stft')
+    e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'multi_resolution_stft')
+    return _scores(_mr_scores(*E.mr_stft(r, e, n, res)), MR_STFT_KEYS, was_np, batched)
+
+
+def stft_distance(wave_est, wave_ref, n_fft=1024, hop_length=256, win_length=None, lens=None):
+    """-> (spectral convergence, log-magnitude distance) of wave_est [n] against wave_ref [n] at ONE resolution (win_length None: n_fft):
+    the bits of that resolution's row of multi_resolution_stft's per_resolution."""
+    res = _resolutions((n_fft,), (hop_length,), (n_fft if win_length is None else win_length,), 'stft_distance')
+    e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'stft_distance')
+    per, _ = E.mr_stft(r, e, n, res)
+    return _out(per[:, 0, 0], was_np, batched), _out(per[:, 0, 1], was_np, batched)
+
+
+def _wave_scores(ref, est, n, fs, mr_stft, was_np, batched):
+    score = E.wave_scorer(fs, ref.device).metrics(ref, est, n)
+    keys = WAVE_KEYS
+    if mr_stft:
+        score.update({k: v for k, v in _mr_scores(*E.mr_stft(ref, est, n)).items() if k in MR_STFT_KEYS[:3]})
+        keys = WAVE_KEYS + MR_STFT_KEYS[:3]
+    return _scores(score, keys, was_np, batched)
+
+
+def wave_metrics(wave_est, wave_ref, fs=22050, lens=None, mr_stft=False):
     """{stoi, estoi, si_sdr (zero-mean), snr, lsd, frames, frames_kept} of wave_est [n] against the sample-aligned wave_ref [n] at `fs`
-    Hz; frames / frames_kept are the STOI frames at 10 kHz before and after the silent-frame removal.  The two waves share `lens`; rows
+    Hz; frames / frames_kept are the STOI frames at 10 kHz before and after the silent-frame removal.  mr_stft: + {mr_stft,
+    spectral_convergence, log_stft_magnitude} of multi_resolution_stft at its default resolutions.  The two waves share `lens`; rows
     of different padded width are compared over the min of the two."""
     e, r, n, was_np, batched = _wave_pair(wave_est, wave_ref, lens, 'wave_metrics')
-    return _scores(E.wave_scorer(fs, r.device).metrics(r, e, n), WAVE_KEYS, was_np, batched)
+    return _wave_scores(r, e, n, fs, mr_stft, was_np, batched)
 
 
-def copy_synthesis(vocoder, wave, lens=None):
+def copy_synthesis(vocoder, wave, lens=None, mr_stft=False):
     """Copy synthesis, the standard way to judge a vocoder: `wave` [n] at 22 050 Hz is analysed with ObjectiveEngine's log-mel analysis,
     the HiFi-GAN `Generator` resynthesises it (vocoder.engine().forward(mel, frames)) under the current ttsamd.engine.set_precision
-    mode, and the result is scored against the input over 256 * frames samples.  -> (wave_metrics dict, the resynthesised wave
-    [256 * frames] on the device, or numpy for numpy input).  Vocos and Tacotron2 are out of scope for this helper."""
+    mode, and the result is scored against the input over 256 * frames samples.  -> (wave_metrics dict (mr_stft: with its three
+    multi-resolution STFT entries), the resynthesised wave [256 * frames] on the device, or numpy for numpy input).  Vocos and Tacotron2
+    are out of scope for this helper."""
     x, was_np, batched = _prep(wave, 1, 'copy_synthesis')
     n = _lens(lens, x, batched)
     if str(x.device) not in _engines:
@@ -180,5 +230,5 @@ def copy_synthesis(vocoder, wave, lens=None):
     mel, frames = _engines[str(x.device)].melspec.forward(x, n)
     out = vocoder.engine().forward(mel, frames)
     W = min(out.shape[1], x.shape[1])
-    score = E.wave_scorer(22050, x.device).metrics(x[:, :W].contiguous(), out[:, :W].contiguous(), 256 * frames)
-    return _scores(score, WAVE_KEYS, was_np, batched), _out(out, was_np, batched)
+    return (_wave_scores(x[:, :W].contiguous(), out[:, :W].contiguous(), 256 * frames, 22050, mr_stft, was_np, batched),
+            _out(out, was_np, batched))
