@@ -1255,6 +1255,52 @@ int32_t ttsamd_mr_stft(const float* ref, const float* est, int64_t wave_stride, 
                        const int32_t* hop, const int32_t* win, int32_t n_res, double* out, int32_t* frames, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/* ---- Griffin-Lim (csrc/griffinlim.hip): a linear magnitude -> wave without a vocoder, and the mel inversion in front of it.
+ * n_fft = win = 1024, hop 256, the periodic Hann window of the mel analysis; the two framings of ttsamd_melspec_create, so that the mel
+ * analysis of the result sees the frames that were given:
+ *   framing 0 (same):   reflect padding 384 per side, T frames <-> n = 256 T samples,        T >= 2
+ *   framing 1 (center): reflect padding 512 per side, T frames <-> n = 256 (T - 1) samples,  T >= 4   (torch.stft / istft, center=True)
+ * Specified by its arithmetic, which is torchaudio.functional.griffinlim's for a linear magnitude (power 1):
+ *   c = momentum / (1 + momentum);  angles = init;  tprev = 0
+ *   n_iter times:  inv = istft(mag * angles);  rebuilt = stft(inv);  a = rebuilt - c * tprev (momentum != 0);
+ *                  angles = a / (|a| + 1e-16);  tprev = rebuilt
+ *   wave = istft(mag * angles)
+ * istft: inverse real transform of each frame (the imaginary parts of bins 0 and 512 are dropped), times the window, overlap-add over
+ * 256 (T - 1) + 1024 padded samples, divided by the sum of the squared windows of the frames that exist at that sample, cropped by the
+ * padding.  stft: reflect padding at the row's own ends (j < 0 -> -j, j >= n -> 2 (n - 1) - j), frame t = padded[256 t : 256 t + 1024]
+ * times the window.  In the center framing frame 0 is even about its middle, so its spectrum is real: the imaginary part of its
+ * `rebuilt`, rounding noise only, is dropped.  The center framing is pinned against torch.stft / torch.istft; parity with a torchaudio release is not (the random
+ * initial phase is the hash below).
+ * mag: device fp32 [batch][513][t_max]; frames: device int32 [batch], clamped to [0, t_max]; a row below the framing's minimum is an empty
+ * row (device data cannot be refused): a wave of zeros, inconsistency NaN.  Nothing at or past a row's frame count is read.
+ * init 0: zero phase (angles = 1).  init 1: angle(t, k) = 2 pi (h >> 8) 2^-24 with
+ *   h = fmix32(fmix32(seed_lo + 0x9E3779B9 (513 t + k)) ^ seed_hi)   (uint32 arithmetic, fmix32 = murmur3's finaliser)
+ * under the row's 64-bit seed: seed_rows[b] (device uint64 [batch]) or, with seed_rows NULL, `seed` for every row -- a row's audio depends
+ * on neither its batch nor its position.  init 2: angles = phase (which must not be NULL), used as they are.
+ * phase: device complex64 [batch][t_max][513] or NULL; when not NULL it receives the final angles of the frames below the row's count
+ * (the rest is not written): 1 + 1 iterations through `phase` are 2 iterations when momentum is 0 (tprev is not carried).
+ * wave: device fp32 [batch][wave_stride], wave_stride >= the n of t_max; samples at or past the row's n are written as zero.
+ * inconsistency: device float64 [batch] or NULL: || |rebuilt| - mag || / || mag || over the row's frames and bins, from the last
+ * iteration's `rebuilt` (no extra transform; |rebuilt| - mag in fp32, the two sums in float64: per-block partial sums in a fixed order,
+ * then one fixed-order sum per row); NaN for n_iter = 0.
+ * fp32 arithmetic.  n_iter + 3 launches whatever the batch and the lengths; between two iterations the windowed inverse frames
+ * [batch][t_max][1024] cross HBM (a ping-pong pair in the workspace) and, with momentum != 0, tprev [batch][t_max][513] complex: no
+ * other spectrum matrix exists.  Row b of a batch has the bits of the call on row b alone; two runs give the same bits. */
+/* bytes of workspace ttsamd_griffinlim needs; -1: refused (batch outside 1 .. 65535, t_max outside 1 .. 2^22) */
+int64_t ttsamd_griffinlim_workspace_bytes(int32_t batch, int32_t t_max, float momentum);
+/* TTSAMD_EINVAL (nothing launched): a NULL mag / frames / wave / workspace, a framing other than 0 / 1, t_max below the framing's
+ * minimum (the message names it), n_iter < 0, momentum outside [0, 1), init outside 0 .. 2 or init 2 without phase, a wave_stride
+ * below the n of t_max or of 2^31 - 1024 and more, a workspace smaller than ttsamd_griffinlim_workspace_bytes. */
+int32_t ttsamd_griffinlim(const float* mag, const int32_t* frames, int32_t batch, int32_t t_max, int32_t framing, int32_t n_iter,
+                          float momentum, int32_t init, const uint64_t* seed_rows, uint64_t seed, void* phase, float* wave,
+                          int64_t wave_stride, double* inconsistency, void* workspace, int64_t workspace_bytes, void* stream);
+/* Mel inversion by the pseudo-inverse of the filterbank: mag[b][f][t] = max(sum_m pinv[f][m] e(mel[b][m][t]), floor) for t < frames[b],
+ * 0 from there on; e = exp when log_input != 0 (the natural log of a clamped mel, as the HiFi-GAN analysis writes it), the identity
+ * otherwise.  mel: device fp32 [batch][n_mels][t_max], 1 <= n_mels <= 128; pinv: device fp32 [513][n_mels] (computed once by the caller,
+ * in float64); mag: device fp32 [batch][513][t_max].  One launch, fp32, m ascending. */
+int32_t ttsamd_mel_to_linear(const float* mel, const int32_t* frames, int32_t batch, int32_t n_mels, int32_t t_max, const float* pinv,
+                             int32_t log_input, float floor, float* mag, void* stream);
+
 /* Timing hooks for bench.py (roofline of the dominant kernel): when enabled, hifigan
  * forward brackets its ResBlock conv launches with HIP events on the launch stream. */
 int32_t ttsamd_profile_enable(int32_t on);

@@ -389,9 +389,21 @@ class FastPitch(_HipModule):
 
 class FastPitch2Wave(nn.Module):
     def __init__(self, model_sd_path: str, vocoder_sd: Optional[str] = None, vocoder_config: Optional[str] = None,
-                 vowelizer: Optional[str] = None, arabic_in: bool = True):
+                 vowelizer: Optional[str] = None, arabic_in: bool = True, vocoder: Optional[str] = None):
+        """vocoder=None: the HiFi-GAN checkpoint (vocoder_sd / vocoder_config, or the basic config's).  vocoder='griffin_lim' (not in the
+        reference): no vocoder checkpoint is read; the mel goes through the pseudo-inverse of the filterbank and 32 Griffin-Lim
+        iterations on the device (vocoder.griffinlim.GriffinLimVocoder), and tts / tts_single / tts_batch / tts_requests return those
+        waves.  `denoise` is then taken as 0 -- the bias denoiser removes HiFi-GAN's own artefact, which these waves do not have --
+        while normalize= and limiter= act on the wave as they always do; tts_stream raises ValueError (streaming is out of scope)."""
         super().__init__()
         self.model = FastPitch(model_sd_path, arabic_in=arabic_in, vowelizer=vowelizer)
+        if vocoder is not None:
+            if vocoder != 'griffin_lim':
+                raise ValueError(f"FastPitch2Wave: vocoder={vocoder!r}: None (the HiFi-GAN checkpoint) or 'griffin_lim'")
+            from vocoder.griffinlim import NoDenoiser, GriffinLimVocoder
+            self.vocoder, self.denoiser = GriffinLimVocoder().eval(), NoDenoiser()
+            self.eval()
+            return
         if vocoder_sd is None or vocoder_config is None:
             config = get_basic_config()
             vocoder_sd, vocoder_config = config.vocoder_state_path, config.vocoder_config_path
@@ -585,6 +597,8 @@ class FastPitch2Wave(nn.Module):
         reading) for a list.  reading: a dict of Python floats, momentary, short_term (-inf before the first 400 ms / 3 s) and
         integrated (of the line so far); on a line's last chunk also loudness_range, max_momentary and max_short_term.  Float chunks
         only: with pcm16 or an encoding other than None / 'float32' it is a ValueError."""
+        if not hasattr(self.vocoder, 'h'):
+            raise ValueError("tts_stream: vocoder='griffin_lim' does not stream (every iteration needs the whole utterance)")
         kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
         limiter = limiter_spec(limiter)
         check_true_peak(true_peak, None, limiter)

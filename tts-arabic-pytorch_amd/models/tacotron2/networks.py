@@ -211,9 +211,20 @@ def _lim(limiter, normalize, true_peak=False):
 
 class Tacotron2Wave(nn.Module):
     def __init__(self, model_sd_path: str, vocoder_sd: Optional[str] = None, vocoder_config: Optional[str] = None,
-                 vowelizer: Optional[str] = None, arabic_in: bool = True, n_symbol: int = 40):
+                 vowelizer: Optional[str] = None, arabic_in: bool = True, n_symbol: int = 40, vocoder: Optional[str] = None):
+        """vocoder=None: the HiFi-GAN checkpoint.  vocoder='griffin_lim' (not in the reference): no vocoder checkpoint is read, the
+        waves of tts / tts_single / tts_batch come from vocoder.griffinlim.GriffinLimVocoder (pseudo-inverse of the filterbank, 32
+        Griffin-Lim iterations on the device); `denoise` is then taken as 0 (the bias denoiser removes HiFi-GAN's own artefact),
+        normalize= / limiter= act on the wave as always, and tts_stream raises ValueError (streaming is out of scope)."""
         super().__init__()
         self.model = Tacotron2(model_sd_path, n_symbol=n_symbol, arabic_in=arabic_in, vowelizer=vowelizer)
+        if vocoder is not None:
+            if vocoder != 'griffin_lim':
+                raise ValueError(f"Tacotron2Wave: vocoder={vocoder!r}: None (the HiFi-GAN checkpoint) or 'griffin_lim'")
+            from vocoder.griffinlim import NoDenoiser, GriffinLimVocoder
+            self.vocoder, self.denoiser = GriffinLimVocoder().eval(), NoDenoiser()
+            self.eval()
+            return
         if vocoder_sd is None or vocoder_config is None:
             config = get_basic_config()
             vocoder_sd, vocoder_config = config.vocoder_state_path, config.vocoder_config_path
@@ -311,6 +322,8 @@ class Tacotron2Wave(nn.Module):
         needs the whole wave).  Tacotron2.dropout_seed applies per batch as in `infer`.  `stream_sessions` maps each line to the
         decoder session of its batch (its steps_done / ended at the time of a yield)."""
         from ttsamd.engine import check_finite, check_true_peak, limiter_spec, row_values
+        if not hasattr(self.vocoder, 'h'):
+            raise ValueError("tts_stream: vocoder='griffin_lim' does not stream (every iteration needs the whole utterance)")
         if speed is not None and float(speed) != 1.0:
             raise ValueError('tts_stream: speed is not supported in the stream (resize_mel needs the total length): use tts')
         if meter:

@@ -441,6 +441,140 @@ class MelSpecEngine:
         return mel, frames
 
 
+class GriffinLimEngine:
+    """ttsamd_griffinlim / ttsamd_mel_to_linear (csrc/griffinlim.hip) with a workspace cache: a linear magnitude -> wave without a
+    vocoder.  Only n_fft = win = 1024, hop 256, periodic hann is built; framing 'same' (T frames <-> 256 T samples, T >= 2: the HiFi-GAN
+    mel's) or 'center' (T frames <-> 256 (T - 1) samples, T >= 4: torch.stft's).  Specified by its arithmetic (include/ttsamd.h); the
+    `center` framing is pinned against torch.stft / torch.istft, parity with a torchaudio release is not (own random init)."""
+
+    MIN_FRAMES = {'same': 2, 'center': 4}                      # the reflect padding (384 / 512 per side) needs more samples than it adds
+    INIT = {'zeros': 0, 'hash': 1, 'phase': 2}
+    FLOOR = 1e-10
+
+    def __init__(self, device='cuda'):
+        self.lib = _require_gpu()
+        self.device = torch.device(device if device != 'cuda' else 'cuda:0')
+        self.ws = _Workspace()
+        self._pinv = {}
+
+    @classmethod
+    def samples(cls, frames, framing):
+        return 256 * (frames - 1) if framing == 'center' else 256 * frames
+
+    def _frames(self, frames, B, T, framing, what):
+        """int32 [B] on the device; counts that still live on the host are checked there (a row below the minimum is refused by name),
+        device counts are only clamped by the kernel (such a row is an empty row)"""
+        if framing not in self.MIN_FRAMES:
+            raise L.TtsAmdError(f"{what}: framing {framing!r}: only 'same' and 'center' are built")
+        need = self.MIN_FRAMES[framing]
+        if T < need:
+            raise L.TtsAmdError(f'{what}: {T} frames, the {framing!r} framing needs at least {need} (reflect padding)')
+        if frames is None:
+            return torch.full((B,), T, dtype=torch.int32, device=self.device)
+        if not (isinstance(frames, torch.Tensor) and frames.device.type != 'cpu'):
+            host = np.asarray(frames.numpy() if isinstance(frames, torch.Tensor) else frames).reshape(-1)
+            if host.size != B:
+                raise L.TtsAmdError(f'{what}: {host.size} frame counts for {B} rows')
+            if host.size and (int(host.min()) < need or int(host.max()) > T):
+                raise L.TtsAmdError(f'{what}: frame counts {host.tolist()} outside [{need}, {T}]: the {framing!r} framing needs at '
+                                    f'least {need} frames (reflect padding)')
+            frames = torch.as_tensor(host.astype(np.int32))
+        if frames.numel() != B:
+            raise L.TtsAmdError(f'{what}: {frames.numel()} frame counts for {B} rows')
+        return frames.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def forward(self, mag, frames=None, n_iter=32, momentum=0.99, framing='same', init='hash', seed=0, phase=None, return_phase=False,
+                return_inconsistency=False):
+        """mag [B, 513, T] float32 (the project's channel-first layout), frames int [B] or None (every row T) -> wave [B, n(T)], zeros
+        at and past a row's own length; row b is the call on row b alone, bit for bit.  init 'zeros' | 'hash' | 'phase'; seed: one int
+        for every row or one per row (64 bits); phase: complex64 [B, T, 513], the initial angles of init='phase'.  return_phase: also
+        the final angles [B, T, 513] complex64 (rows / frames past a row's count are zero); return_inconsistency: also float64 [B],
+        || |rebuilt| - mag || / || mag || of the last iteration (NaN for n_iter = 0).  -> wave, or (wave[, phase][, inconsistency])."""
+        what = 'GriffinLimEngine.forward'
+        mag = _f32(mag, self.device)
+        if mag.dim() != 3 or mag.shape[1] != 513:
+            raise L.TtsAmdError(f'{what}: mag of shape {tuple(mag.shape)}, expected [B, 513, T] (only n_fft = 1024 is built)')
+        B, _, T = mag.shape
+        if init not in self.INIT:
+            raise L.TtsAmdError(f"{what}: init {init!r} ('zeros' | 'hash' | 'phase')")
+        if int(n_iter) != n_iter or n_iter < 0:
+            raise L.TtsAmdError(f'{what}: n_iter = {n_iter!r} is not an integer >= 0')
+        if not 0.0 <= float(momentum) < 1.0:
+            raise L.TtsAmdError(f'{what}: momentum = {momentum!r} outside [0, 1)')
+        frames = self._frames(frames, B, T, framing, what)
+        if (init == 'phase') != (phase is not None):
+            raise L.TtsAmdError(f"{what}: init='phase' and phase= go together (init {init!r}, phase {'given' if phase is not None else 'None'})")
+        ph = None
+        if phase is not None:
+            if tuple(phase.shape) != (B, T, 513) or not torch.is_complex(phase):
+                raise L.TtsAmdError(f'{what}: phase of shape {tuple(phase.shape)} / {phase.dtype}, expected complex [B, T, 513] = {(B, T, 513)}')
+            ph = torch.view_as_real(phase.to(device=self.device, dtype=torch.complex64)).contiguous().clone()
+        elif return_phase:
+            ph = torch.zeros(B, T, 513, 2, dtype=torch.float32, device=self.device)
+        seed_rows = None
+        if per_row(seed):
+            vals = [int(v) & 0xFFFFFFFFFFFFFFFF for v in row_values(seed, B, 'seed')]
+            seed_rows = torch.from_numpy(np.array(vals, dtype=np.uint64).view(np.int64)).to(self.device)
+            seed = 0
+        n = self.samples(T, framing)
+        wave = torch.empty(B, n, dtype=torch.float32, device=self.device)
+        inc = torch.empty(B, dtype=torch.float64, device=self.device) if return_inconsistency else None
+        if B:
+            with torch.cuda.device(self.device):
+                nbytes = int(self.lib.ttsamd_griffinlim_workspace_bytes(B, T, float(momentum)))
+                if nbytes < 0:
+                    raise L.TtsAmdError(f'{what}: a batch of {B} rows of {T} frames is refused (1 .. 65535 rows, 1 .. 2^22 frames)')
+                ws = self.ws.get(nbytes, self.device)
+                L.check(self.lib.ttsamd_griffinlim(_ptr(mag), _ptr(frames), B, T, int(framing == 'center'), int(n_iter), float(momentum),
+                                                   self.INIT[init], _ptr(seed_rows), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ph), _ptr(wave), n,
+                                                   _ptr(inc), _ptr(ws), nbytes, _stream()), 'griffinlim')
+        out = (wave,)
+        if return_phase:
+            out += (torch.view_as_complex(ph),)
+        if return_inconsistency:
+            out += (inc,)
+        return out[0] if len(out) == 1 else out
+
+    def pinv(self, fbank):
+        """The pseudo-inverse [513, n_mels] of a filterbank [n_mels, 513], float64 on the host, rounded once to fp32; cached per matrix"""
+        fb = fbank.detach().cpu().numpy() if hasattr(fbank, 'detach') else np.asarray(fbank)
+        if fb.ndim != 2 or fb.shape[1] != 513 or not 1 <= fb.shape[0] <= 128:
+            raise L.TtsAmdError(f'GriffinLimEngine: filterbank of shape {fb.shape}, expected [n_mels <= 128, 513]')
+        fb = np.ascontiguousarray(fb, dtype=np.float32)
+        key = fb.tobytes()
+        if key not in self._pinv:
+            self._pinv = {key: torch.from_numpy(np.linalg.pinv(fb.astype(np.float64)).astype(np.float32)).to(self.device).contiguous()}
+        return self._pinv[key]
+
+    def mel_to_linear(self, mel, frames=None, log=True, fbank=None):
+        """mel [B, n_mels, T] (log=True: the natural log of a clamped mel, as the HiFi-GAN analysis writes it) -> mag [B, 513, T] =
+        max(pinv(fbank) exp(mel), 1e-10), zero at and past a row's frame count.  fbank [n_mels, 513]: None = the 80-band mel of
+        utils.audio.MelSpectrogram (ttsamd.melfb).  The plain pseudo-inverse: no NNLS refinement."""
+        what = 'GriffinLimEngine.mel_to_linear'
+        mel = _f32(mel, self.device)
+        if mel.dim() != 3:
+            raise L.TtsAmdError(f'{what}: mel of shape {tuple(mel.shape)}, expected [B, n_mels, T]')
+        B, n_mels, T = mel.shape
+        if fbank is None:
+            from . import melfb
+            fbank = melfb.mel_filterbank(22050, 1024, 80, 0.0, 8000.0, 'slaney', 'slaney')
+        P = self.pinv(fbank)
+        if P.shape[1] != n_mels:
+            raise L.TtsAmdError(f'{what}: mel of {n_mels} bands, filterbank of {P.shape[1]}')
+        if frames is None:
+            frames = torch.full((B,), T, dtype=torch.int32, device=self.device)
+        frames = frames.to(device=self.device, dtype=torch.int32).contiguous() if isinstance(frames, torch.Tensor) else \
+            torch.as_tensor(np.asarray(frames, dtype=np.int32)).to(self.device)
+        if frames.numel() != B:
+            raise L.TtsAmdError(f'{what}: {frames.numel()} frame counts for {B} rows')
+        mag = torch.empty(B, 513, T, dtype=torch.float32, device=self.device)
+        if B and T:
+            with torch.cuda.device(self.device):
+                L.check(self.lib.ttsamd_mel_to_linear(_ptr(mel), _ptr(frames), B, n_mels, T, _ptr(P), int(bool(log)), self.FLOOR, _ptr(mag),
+                                                      _stream()), 'mel_to_linear')
+        return mag
+
+
 class VocosEngine:
     """Handle over ttsamd_vocos_* (replaces vocoder.vocos.pretrained.MelVocos: '22k' = "same" head, 80 bands; '24k' = "center" head, 100)."""
 

@@ -183,6 +183,11 @@ SYMBOLS = {
     # multi-resolution STFT distance (csrc/mrstft.hip): the resolution arrays are HOST int32 [n_res]
     'ttsamd_mr_stft_workspace_bytes': (_I64, [_I32, _I64, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32]),
     'ttsamd_mr_stft': (_I32, [_P, _P, _I64, _P, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _I32, _P, _P, _P, _I64, _P]),
+    # Griffin-Lim (csrc/griffinlim.hip): mag, frames (int32), B, t_max, framing, n_iter, momentum, init, seed_rows (uint64 [B] or NULL), seed,
+    # phase (complex64 or NULL), wave, wave_stride, inconsistency (float64 [B] or NULL), workspace, bytes, stream
+    'ttsamd_griffinlim_workspace_bytes': (_I64, [_I32, _I32, _F]),
+    'ttsamd_griffinlim': (_I32, [_P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, C.c_uint64, _P, _P, _I64, _P, _P, _I64, _P]),
+    'ttsamd_mel_to_linear': (_I32, [_P, _P, _I32, _I32, _I32, _P, _I32, _F, _P, _P]),
     'ttsamd_tacotron2_create': (_I32, [C.POINTER(Tensor), _I32, C.POINTER(Tacotron2Cfg), C.POINTER(_P)]),
     'ttsamd_tacotron2_destroy': (_I32, [_P]),
     'ttsamd_tacotron2_workspace_bytes': (_I64, [_P, _I32, _I32, _I32]),

@@ -3,6 +3,9 @@ The reference calls torchaudio.save(path, wave[None], 22050) (inference.py:61-63
 torchaudio is not a dependency here, so the RIFF container is written directly.
 Analysis side: `MelSpectrogram` (reference utils/audio.py:6-46), the 80-band mel the acoustic models and HiFi-GAN were trained on,
 as one HIP launch (csrc/melspec.hip).
+Synthesis without a vocoder: `GriffinLim` / `griffinlim` (torchaudio.transforms.GriffinLim's names) and `mel_to_linear`, on the device
+(csrc/griffinlim.hip): specified by its arithmetic; `center` framing pinned against `torch.stft` / `torch.istft`; parity with a
+torchaudio release unpinned (own random init).
 Input side: `resample` / `Resample` (torchaudio.functional.resample's name and defaults), `trim` (librosa.effects.trim's) and
 `prepare_recording` = the clean-up of the reference's scripts/preprocess_audio.py:33-47 (resample with lowpass_filter_width=1024,
 peak 0.999, trim at 23 dB, 768 zeros appended), on the device (csrc/resample.hip, csrc/trim.hip).
@@ -15,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from ttsamd import melfb
-from ttsamd.engine import MelSpecEngine, ResampleEngine, TrimEngine
+from ttsamd.engine import GriffinLimEngine, MelSpecEngine, ResampleEngine, TrimEngine
 from ttsamd.engine import LIMITER_NO_MAX_GAIN, LIMITER_Q, check_finite, limiter_samples, limiter_spec, per_row, row_values
 from ttsamd.engine import leveller as _leveller
 from ttsamd.lib import TtsAmdError
@@ -84,6 +87,113 @@ class MelSpectrogram(_MelModule):
     def forward(self, x, lens=None):
         mel, _ = self.extract(x, lens)
         return mel[0] if x.dim() == 1 else mel
+
+
+_gl_engines = {}
+
+
+def _gl_engine(device):
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise TtsAmdError(f'griffinlim: the input is on {device}: the MI355X path has no CPU fallback; move it with .to("cuda")')
+    key = str(device)
+    if key not in _gl_engines:
+        _gl_engines[key] = GriffinLimEngine(device=device)
+    return _gl_engines[key]
+
+
+def _gl_lens(lens, B, T, framing, what):
+    """frames per row from `lens` in samples (what the framing gives back: 256 T or 256 (T - 1)); host values are checked"""
+    if lens is None:
+        return None
+    if isinstance(lens, torch.Tensor) and lens.device.type != 'cpu':
+        return (lens // 256 + (framing == 'center')).to(torch.int32)
+    host = np.asarray(lens.numpy() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64).reshape(-1)
+    if host.size != B or (host % 256).any():
+        raise TtsAmdError(f'{what}: lens={host.tolist()}: one length per row ({B}), each a multiple of hop_length = 256 '
+                          f'(the {framing!r} framing gives {"256 (T - 1)" if framing == "center" else "256 T"} samples for T frames)')
+    return host // 256 + (framing == 'center')
+
+
+def griffinlim(specgram, window=None, n_fft=1024, hop_length=256, win_length=None, power=2.0, n_iter=32, momentum=0.99, length=None,
+               rand_init=True, framing='center', seed=0, lens=None):
+    """torchaudio.functional.griffinlim's names on the HIP path (csrc/griffinlim.hip): specgram [..., 513, T] on the device, a magnitude
+    to the power `power` (any positive float; the root is taken here with torch) -> wave [..., n], n = 256 (T - 1) for framing='center'
+    (torch.stft's center=True) or 256 T for 'same' (the HiFi-GAN mel's framing).  The project's additions: framing=, seed= (one int,
+    or one per row: the random initial phase is a hash of (seed, frame, bin), so a row's audio depends on neither its batch nor its
+    position) and lens= (samples per row of a ragged batch; what lies past a row's length is zero).  rand_init=False is zero phase.
+    Refused by name: n_fft other than 1024, hop_length other than 256, win_length other than 1024, a window other than the periodic
+    hann, a length other than the framing's n."""
+    what = 'griffinlim'
+    if n_fft != 1024:
+        raise TtsAmdError(f'{what}: n_fft={n_fft}: only n_fft = 1024 is built')
+    if hop_length not in (None, 256):
+        raise TtsAmdError(f'{what}: hop_length={hop_length}: only hop_length = 256 is built')
+    if win_length not in (None, 1024):
+        raise TtsAmdError(f'{what}: win_length={win_length}: only win_length = n_fft = 1024 is built')
+    if window is not None:
+        w = torch.as_tensor(window).detach().cpu().double()
+        if w.shape != (1024,) or float((w - torch.hann_window(1024, dtype=torch.float64)).abs().max()) > 1e-6:
+            raise TtsAmdError(f'{what}: window: only the periodic hann window of 1024 samples (torch.hann_window(1024)) is built')
+    if not (isinstance(power, (int, float)) and power > 0 and np.isfinite(power)):
+        raise TtsAmdError(f'{what}: power={power!r} is not a positive number')
+    if framing not in GriffinLimEngine.MIN_FRAMES:
+        raise TtsAmdError(f"{what}: framing={framing!r}: only 'same' and 'center' are built")
+    if not isinstance(specgram, torch.Tensor) or specgram.dim() < 2 or specgram.shape[-2] != 513:
+        raise TtsAmdError(f'{what}: specgram of shape {tuple(getattr(specgram, "shape", ()))}, expected [..., 513, T] (n_fft = 1024)')
+    T = specgram.shape[-1]
+    n = GriffinLimEngine.samples(T, framing)
+    if length is not None and length != n:
+        raise TtsAmdError(f'{what}: length={length}: {T} frames in the {framing!r} framing give {n} samples, no other length is built')
+    eng = _gl_engine(specgram.device)
+    lead = specgram.shape[:-2]
+    mag = specgram.reshape(-1, 513, T).float()
+    if power != 1:
+        mag = mag.pow(1.0 / power)
+    frames = _gl_lens(lens, mag.shape[0], T, framing, what)
+    wave = eng.forward(mag, frames, n_iter=n_iter, momentum=momentum, framing=framing, init='hash' if rand_init else 'zeros', seed=seed)
+    return wave.reshape(*lead, n)
+
+
+class GriffinLim(nn.Module):
+    """torchaudio.transforms.GriffinLim's names (n_fft, n_iter, win_length, hop_length, power, momentum, length, rand_init) over
+    `griffinlim` above; the project's additions are framing='center', seed=0 and, at the call, lens=.  No window_fn / wkwargs: the
+    window is the periodic hann."""
+
+    def __init__(self, n_fft: int = 1024, n_iter: int = 32, win_length=None, hop_length=None, power: float = 2.0, momentum: float = 0.99,
+                 length=None, rand_init: bool = True, framing: str = 'center', seed: int = 0):
+        super().__init__()
+        if n_fft != 1024:
+            raise TtsAmdError(f'GriffinLim: n_fft={n_fft}: only n_fft = 1024 is built')
+        if hop_length not in (None, 256):
+            raise TtsAmdError(f'GriffinLim: hop_length={hop_length}: only hop_length = 256 is built')
+        if win_length not in (None, 1024):
+            raise TtsAmdError(f'GriffinLim: win_length={win_length}: only win_length = n_fft = 1024 is built')
+        if framing not in GriffinLimEngine.MIN_FRAMES:
+            raise TtsAmdError(f"GriffinLim: framing={framing!r}: only 'same' and 'center' are built")
+        if not 0.0 <= momentum < 1.0:
+            raise TtsAmdError(f'GriffinLim: momentum={momentum!r} outside [0, 1)')
+        if not (isinstance(power, (int, float)) and power > 0):
+            raise TtsAmdError(f'GriffinLim: power={power!r} is not a positive number')
+        self.n_fft, self.n_iter, self.win_length, self.hop_length = n_fft, n_iter, 1024, 256
+        self.power, self.momentum, self.length, self.rand_init, self.framing, self.seed = power, momentum, length, rand_init, framing, seed
+
+    @torch.inference_mode()
+    def forward(self, specgram, lens=None, seed=None):
+        return griffinlim(specgram, None, self.n_fft, self.hop_length, self.win_length, self.power, self.n_iter, self.momentum,
+                          self.length, self.rand_init, self.framing, self.seed if seed is None else seed, lens)
+
+
+def mel_to_linear(mel, log=True, lens=None, fbank=None):
+    """mel [..., n_mels, T] on the device -> magnitude [..., 513, T] = max(pinv(fbank) exp(mel), 1e-10) (log=False: mel is linear);
+    fbank None = `MelSpectrogram`'s 80-band matrix, else [n_mels <= 128, 513] (a Vocos scale: pass its filterbank).  lens: FRAMES per
+    row; what lies at or past them is zero.  The plain pseudo-inverse (float64 on the host, once per matrix), no NNLS refinement."""
+    if not isinstance(mel, torch.Tensor) or mel.dim() < 2:
+        raise TtsAmdError(f'mel_to_linear: mel of shape {tuple(getattr(mel, "shape", ()))}, expected [..., n_mels, T]')
+    eng = _gl_engine(mel.device)
+    lead = mel.shape[:-2]
+    m3 = mel.reshape(-1, mel.shape[-2], mel.shape[-1])
+    return eng.mel_to_linear(m3, lens, log=log, fbank=fbank).reshape(*lead, 513, mel.shape[-1])
 
 
 def save_wav(path, wave, sample_rate=22_050, encoding='PCM_S', bits_per_sample=16):

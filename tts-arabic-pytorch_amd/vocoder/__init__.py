@@ -24,3 +24,10 @@ def load_hifigan(state_dict_path, config_file):
         hparams = AttrDict(json.load(fh))
     vocoder = Generator(hparams, state_dict=_read_generator_checkpoint(state_dict_path))
     return vocoder.eval()
+
+
+def load_griffinlim(n_iter=32, momentum=0.99, seed=0):
+    """The vocoder that needs no checkpoint (vocoder.griffinlim.GriffinLimVocoder): the HiFi-GAN analysis's log-mel -> wave by the
+    pseudo-inverse of the filterbank and `n_iter` Griffin-Lim iterations on the device."""
+    from vocoder.griffinlim import GriffinLimVocoder
+    return GriffinLimVocoder(n_iter=n_iter, momentum=momentum, seed=seed).eval()
