@@ -1,7 +1,7 @@
 """Reference, data, cases and checker for the spectral back end: Vocos' backbone (dwconv7_kernel, LayerNorm at eps 1e-6, the GELU and
 layer-scale epilogues of the conv engine, vocos_pad_channels_kernel) through ttsamd_vocos_features, its ISTFT head (vocos_spec_t_kernel,
 vocos_istft_kernel, vocos_bias_kernel, the frame-major overlap_add_kernel in both trims) through ttsamd_vocos_head, and the denoiser
-(denoise_fft_kernel, overlap_add_kernel, mag_frame0_kernel behind the DFT GEMM).  Plain module: tests/test_spectral_ref_cpu.py shows what
+(denoise_fft_kernel, overlap_add_kernel, bias_frame0_kernel).  Plain module: tests/test_spectral_ref_cpu.py shows what
 the checker rejects, tests/test_gpu_spectral.py holds the library to it.
 
 Reference = the oracle's own pieces (oracle/tts_oracle.py: _vocos_backbone, vocos_forward, vocos_bias_vec, denoise; tests/melspec_ref.py:
@@ -406,6 +406,7 @@ def clamping_strength(wave, ns, bias):
 
 
 BIAS_SPEC_N = 22528                                                           # the 88-frame call (denoiser.py:50-64)
+BIAS_SPEC_NS = (BIAS_SPEC_N, 513)                                             # ... and the smallest wave the call accepts
 
 
 def bias_spec_ref(audio, dtype=torch.float64):
@@ -424,6 +425,6 @@ R_BACKBONE_DIRECT = 6    # fp32, TTSAMD_WINO=0: every conv on the direct MFMA ke
 R_BACKBONE_X3 = 36       # split bf16, set_precision('bf16x3') (worst 17.57)
 R_HEAD = 3               # the head has no conv: one family (worst 1.12)
 R_DENOISE = 3            # denoise_fft_kernel + overlap-add (worst 1.23)
-# mag_frame0_kernel behind the DFT as a 1024-term fp32 GEMM (worst 34.49): the reference's float32 run is an FFT, ten stages deep; the
-# GEMM rounds its running sum 1024 times at the size of the bin (42 at the loudest), a random walk of 1024 steps of ulp(42) / sqrt(12)
-R_BIAS_SPEC = 69
+# bias_frame0_kernel: one radix-4 FFT of frame 0, the transform of denoise_fft_kernel (1.30 on the 22 528-sample wave and 1.30 on 513
+# samples, whose frame 0 holds the same 513 samples; profiles/r40/NOTES.md)
+R_BIAS_SPEC = 3

@@ -1,7 +1,7 @@
 """The spectral back end against float64 through the C ABI (pytest -m gpu): Vocos' backbone through ttsamd_vocos_features
 (dwconv7_kernel, LayerNorm at eps 1e-6, the GELU and layer-scale epilogues of the conv engine, vocos_pad_channels_kernel), its ISTFT head
 through ttsamd_vocos_head on crafted inputs (vocos_spec_t_kernel, vocos_istft_kernel, overlap_add_kernel frame-major in both trims,
-vocos_bias_kernel) and the denoiser (denoise_fft_kernel, overlap_add_kernel, mag_frame0_kernel behind the DFT GEMM).
+vocos_bias_kernel) and the denoiser (denoise_fft_kernel, overlap_add_kernel, bias_frame0_kernel).
 
 Reference, data, cases and checker: tests/spectral_ref.py -- every run is compared with the float64 reference (never with another run),
 over the valid positions, and must stay within R times the error of the same reference in float32 on the same data; every output must be
@@ -266,16 +266,19 @@ def test_denoise_clamping_strength_gives_exact_zeros(dev, name):
 
 
 @functools.lru_cache(maxsize=None)
-def _bias_spec_audio():
-    return torch.from_numpy(melspec_ref.voiced(S.BIAS_SPEC_N, 31))
+def _bias_spec_audio(n=S.BIAS_SPEC_N):
+    return torch.from_numpy(melspec_ref.voiced(n, 31))
 
 
-def test_bias_spec(dev):
-    """ttsamd_denoiser_bias_spec on a 22 528-sample wave (the 88-frame call): stft_frames_kernel, the DFT as a GEMM on the conv engine,
-    mag_frame0_kernel, against float64 |STFT| of frame 0."""
-    audio = _bias_spec_audio()
+@pytest.mark.parametrize('n', S.BIAS_SPEC_NS)
+def test_bias_spec(dev, n):
+    """ttsamd_denoiser_bias_spec (bias_frame0_kernel: frame 0 of the centred framing, windowed, one 1024-point FFT in LDS, |X| of bins
+    0 .. 512) against float64 |STFT| of frame 0, on a 22 528-sample wave (the 88-frame call) and on 513 samples, the smallest wave the
+    call accepts: frame 0 then reflects on the left and ends on the row's last sample."""
+    audio = _bias_spec_audio(n)
     got = _denoiser().bias_spec(audio.to(dev)).reshape(1, S.N_BIN)
-    S.check({'bias_spec': got}, S.bias_spec_ref(audio), S.bias_spec_ref(audio, torch.float32), (S.N_BIN,), S.R_BIAS_SPEC, 'bias_spec')
+    S.check({'bias_spec': got}, S.bias_spec_ref(audio), S.bias_spec_ref(audio, torch.float32), (S.N_BIN,), S.R_BIAS_SPEC,
+            f'bias_spec n = {n}')
 
 
 @pytest.mark.parametrize('strength', S.DENOISE_STRENGTHS)

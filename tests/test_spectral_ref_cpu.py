@@ -245,8 +245,9 @@ def test_denoise_rows_reference_skips_the_zero_row():
     ratios(r32, r64, r32, lens, 'denoise ragged rows fp32')
 
 
-def test_bias_spec_reference():
-    audio = melspec_ref.voiced(S.BIAS_SPEC_N, 31)
+@pytest.mark.parametrize('n', S.BIAS_SPEC_NS)
+def test_bias_spec_reference(n):
+    audio = melspec_ref.voiced(n, 31)
     r64, r32 = S.bias_spec_ref(audio), S.bias_spec_ref(audio, torch.float32)
-    ratios(r32, r64, r32, (S.N_BIN,), 'bias_spec fp32')
+    ratios(r32, r64, r32, (S.N_BIN,), f'bias_spec fp32 n = {n}')
     assert r64['bias_spec'].shape == (1, S.N_BIN) and float(r64['bias_spec'].min()) > 0

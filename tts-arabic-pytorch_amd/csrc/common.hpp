@@ -367,6 +367,29 @@ __device__ __forceinline__ bool live_tile(const int64_t* __restrict__ lens, cons
     }
     return false;
 }
+
+// K float64 sums over a block of NW waves in a fixed order, so that two runs agree bit for bit: a butterfly over the lanes of each
+// wave, then the waves in ascending order.  Every thread leaves with the K totals in v; red is the block's scratch in LDS.  Holds a
+// __syncthreads(): the whole block calls it.
+template <int NW, int K>
+__device__ __forceinline__ void block_sum_fixed(double (&v)[K], double (&red)[K][NW]) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) v[q] += __shfl_xor(v[q], d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) red[q][threadIdx.x >> 6] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        v[q] = red[q][0];
+#pragma unroll
+        for (int u = 1; u < NW; ++u) v[q] += red[q][u];
+    }
+}
 #endif
 
 }  // namespace ttsamd

@@ -36,11 +36,11 @@
 #include <cstring>
 
 #include "kernels.hpp"
-#include "fft1024.hpp"
+#include "stft1024.hpp"
 
 namespace ttsamd {
 
-constexpr int GL_N = 1024, GL_HOP = 256, GL_NBIN = GL_N / 2 + 1, GL_FPB = 2, GL_MAXMEL = 128;   // GL_FPB: frames per block, one pair
+constexpr int GL_FPB = 2, GL_MAXMEL = 128;                // GL_FPB: frames per block, one pair
 constexpr int GL_OLA = 1024;                              // samples per block of the overlap-add launch
 
 struct GlPlan {
@@ -52,21 +52,21 @@ static bool gl_plan(int32_t B, int32_t T, bool momentum, GlPlan& p) {
     if (B < 1 || B > 65535 || T < 1 || T > (1 << 22)) return false;
     Arena a(nullptr, 0);
     p.chunks = (T + GL_FPB - 1) / GL_FPB;
-    p.window = a.off;  a.take<float>(GL_N);
-    p.twiddle = a.off; a.take<float2>(GL_N);
+    p.window = a.off;  a.take<float>(STFT_N);
+    p.twiddle = a.off; a.take<float2>(STFT_N);
     p.part = a.off;    a.take<double>((int64_t)B * p.chunks * 2);
-    p.frames_a = a.off; a.take<float>((int64_t)B * T * GL_N);
-    p.frames_b = a.off; a.take<float>((int64_t)B * T * GL_N);
+    p.frames_a = a.off; a.take<float>((int64_t)B * T * STFT_N);
+    p.frames_b = a.off; a.take<float>((int64_t)B * T * STFT_N);
     p.tprev = a.off;
-    if (momentum) a.take<float2>((int64_t)B * T * GL_NBIN);
+    if (momentum) a.take<float2>((int64_t)B * T * STFT_NBIN);
     p.bytes = a.off;
     return true;
 }
 
 __global__ void gl_tables_kernel(float* __restrict__ win, float2* __restrict__ tw) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= GL_N) return;
-    const double x = (double)m / (GL_N / 2);               // exp(-2 pi i m / 1024) = (cos, -sin)(pi x)
+    if (m >= STFT_N) return;
+    const double x = (double)m / (STFT_N / 2);               // exp(-2 pi i m / 1024) = (cos, -sin)(pi x)
     win[m] = (float)(0.5 - 0.5 * cospi(x));
     tw[m] = make_float2((float)cospi(x), (float)(-sinpi(x)));
 }
@@ -78,7 +78,7 @@ __device__ __forceinline__ uint32_t gl_fmix32(uint32_t h) {   // murmur3's final
 
 // the hashed uniform phase of frame t, bin k under a row's 64-bit seed: (cos, sin) of 2 pi (h >> 8) 2^-24
 __device__ __forceinline__ float2 gl_hash_phase(const uint32_t seed_lo, const uint32_t seed_hi, const int t, const int k) {
-    const uint32_t h = gl_fmix32(gl_fmix32(seed_lo + 0x9E3779B9u * ((uint32_t)t * (uint32_t)GL_NBIN + (uint32_t)k)) ^ seed_hi);
+    const uint32_t h = gl_fmix32(gl_fmix32(seed_lo + 0x9E3779B9u * ((uint32_t)t * (uint32_t)STFT_NBIN + (uint32_t)k)) ^ seed_hi);
     float s, c;
     sincospif((float)(h >> 8) * (2.0f / 16777216.0f), &s, &c);   // the argument is exact in fp32
     return make_float2(c, s);
@@ -93,20 +93,20 @@ __device__ __forceinline__ int gl_row_frames(const int32_t* __restrict__ frames,
 // the signal of the padded axis at position p (0 <= p < 256 (fr - 1) + 1024): the frames that exist at p, added in ascending order,
 // over the sum of their squared windows.  fb: the row's windowed inverse frames [fr][1024]; win: the window in LDS.
 __device__ __forceinline__ float gl_sample(const float* __restrict__ fb, const float* win, const int p, const int fr) {
-    const int f_lo = p >= GL_N ? (p - (GL_N - GL_HOP)) >> 8 : 0, f_hi = min(p >> 8, fr - 1);
+    const int f_lo = p >= STFT_N ? (p - (STFT_N - STFT_HOP)) >> 8 : 0, f_hi = min(p >> 8, fr - 1);
     float v[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int f = f_lo + q;
-        v[q] = f <= f_hi ? fb[(int64_t)f * GL_N + (p - GL_HOP * f)] : 0.f;
+        v[q] = f <= f_hi ? fb[(int64_t)f * STFT_N + (p - STFT_HOP * f)] : 0.f;
     }
     float env = 1.5f;
-    if (p < GL_N - GL_HOP || p >= GL_HOP * fr) {           // within 768 samples of an end: fewer than four frames
+    if (p < STFT_N - STFT_HOP || p >= STFT_HOP * fr) {           // within 768 samples of an end: fewer than four frames
         env = 0.f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int f = f_lo + q;
-            const float w = win[min(max(p - GL_HOP * f, 0), GL_N - 1)];
+            const float w = win[min(max(p - STFT_HOP * f, 0), STFT_N - 1)];
             env += f <= f_hi ? w * w : 0.f;
         }
     }
@@ -132,27 +132,27 @@ struct GlArgs {
 
 template <bool FIRST>
 __global__ __launch_bounds__(256, 4) void gl_iter_kernel(const GlArgs a) {
-    __shared__ float2 buf[2][GL_N];
-    __shared__ float2 tw[GL_N];
-    __shared__ float wl[GL_N];
-    __shared__ double red[4][2];
+    __shared__ float2 buf[2][STFT_N];
+    __shared__ float2 tw[STFT_N];
+    __shared__ float wl[STFT_N];
+    __shared__ double red[2][4];
     const int b = blockIdx.y, t0 = blockIdx.x * GL_FPB, i = threadIdx.x;
     const int T_max = a.T_max;
     const int fr = gl_row_frames(a.frames, b, T_max, a.center);
     if (t0 >= fr) return;                                        // (block-uniform)
-    const int pad = a.center ? GL_N / 2 : (GL_N - GL_HOP) / 2;
-    const int n = a.center ? GL_HOP * (fr - 1) : GL_HOP * fr;
+    const int pad = stft1024_pad(a.center);
+    const int n = a.center ? STFT_HOP * (fr - 1) : STFT_HOP * fr;
+    stft1024_load_twiddles(tw, a.tw, i);
     float w[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        tw[i + 256 * r] = a.tw[i + 256 * r];
         w[r] = a.win[i + 256 * r];
         wl[i + 256 * r] = w[r];
     }
     __syncthreads();
-    const float* mg = a.mag + (int64_t)b * GL_NBIN * T_max;
+    const float* mg = a.mag + (int64_t)b * STFT_NBIN * T_max;
     const int64_t row = (int64_t)b * T_max;
-    const float* fprev = a.prev + row * GL_N;
+    const float* fprev = a.prev + row * STFT_N;
     uint32_t seed_lo = 0, seed_hi = 0;
     if (FIRST && a.init == 1) {
         const unsigned long long sd = a.seed_rows ? a.seed_rows[b] : a.seed;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256, 4) void gl_iter_kernel(const GlArgs a) {
         seed_hi = (uint32_t)(sd >> 32);
     }
     const bool with_tprev = !FIRST && a.tprev != nullptr;
-    double e_num = 0.0, e_den = 0.0;
+    double e[2] = {0.0, 0.0};                                    // (|rebuilt| - mag)^2, mag^2
     const int t = t0;                                            // the block's pair: frames t (even) and t + 1
     const bool two = t + 1 < fr;
     // bins of this thread: i, i + 256 and, for thread 0, 512
@@ -176,8 +176,8 @@ __global__ __launch_bounds__(256, 4) void gl_iter_kernel(const GlArgs a) {
             ma[r] = mg[(int64_t)k * T_max + t];
             if (two) mb[r] = mg[(int64_t)k * T_max + t + 1];
             if (with_tprev && a.tprev_valid) {
-                pa[r] = a.tprev[(row + t) * GL_NBIN + k];
-                if (two) pb[r] = a.tprev[(row + t + 1) * GL_NBIN + k];
+                pa[r] = a.tprev[(row + t) * STFT_NBIN + k];
+                if (two) pb[r] = a.tprev[(row + t + 1) * STFT_NBIN + k];
             }
         }
     }
@@ -186,13 +186,8 @@ __global__ __launch_bounds__(256, 4) void gl_iter_kernel(const GlArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = i + 256 * r;
-            int s0 = t * GL_HOP + j - pad, s1 = s0 + GL_HOP;
-            if (s0 < 0) s0 = -s0;
-            if (s0 >= n) s0 = 2 * (n - 1) - s0;
-            s0 = min(max(s0, 0), n - 1);
-            if (s1 < 0) s1 = -s1;
-            if (s1 >= n) s1 = 2 * (n - 1) - s1;
-            s1 = min(max(s1, 0), n - 1);
+            const int sp = t * STFT_HOP + j - pad;
+            const int s0 = stft1024_reflect(sp, n), s1 = stft1024_reflect(sp + STFT_HOP, n);
             const float xa = gl_sample(fprev, wl, s0 + pad, fr);
             const float xb = two ? gl_sample(fprev, wl, s1 + pad, fr) : 0.f;
             buf[0][j] = make_float2(xa * w[r], xb * w[r]);
@@ -211,77 +206,67 @@ __global__ __launch_bounds__(256, 4) void gl_iter_kernel(const GlArgs a) {
                     ga = gl_hash_phase(seed_lo, seed_hi, t, k);
                     gb = gl_hash_phase(seed_lo, seed_hi, t + 1, k);
                 } else if (a.init == 2) {
-                    ga = a.phase_in[(row + t) * GL_NBIN + k];
-                    gb = two ? a.phase_in[(row + t + 1) * GL_NBIN + k] : make_float2(0.f, 0.f);
+                    ga = a.phase_in[(row + t) * STFT_NBIN + k];
+                    gb = two ? a.phase_in[(row + t + 1) * STFT_NBIN + k] : make_float2(0.f, 0.f);
                 } else {
                     ga = gb = make_float2(1.f, 0.f);
                 }
             } else {
-                const float2 z = buf[1][k], cz = buf[1][(GL_N - k) & (GL_N - 1)];
-                float2 ra = make_float2(0.5f * (z.x + cz.x), 0.5f * (z.y - cz.y));           // rebuilt, frame t
+                const float2 z = buf[1][k], cz = buf[1][(STFT_N - k) & (STFT_N - 1)];
+                float2 ra, rb;                               // rebuilt, frames t and t + 1
+                stft1024_unpack_pair(z, cz, ra, rb);
                 // center framing, frame 0: reflected about sample 0 and windowed symmetrically, the frame is even about its middle,
                 // so its spectrum is real (times (-1)^k); what the transform leaves in the imaginary part is rounding noise only, and
                 // in a bin whose rebuilt magnitude is far below `mag` that noise would turn the angle (measured: 1e-5 of the frame's
                 // largest magnitude against 1e-6 in the other frames, profiles/r39/NOTES.md)
                 if (a.center && t == 0) ra.y = 0.f;
-                const float2 rb = make_float2(0.5f * (z.y + cz.y), 0.5f * (cz.x - z.x));     // rebuilt, frame t + 1
                 float2 aa = ra, ab = rb;
                 if (with_tprev) {
                     aa = make_float2(ra.x - a.coef * pa[r].x, ra.y - a.coef * pa[r].y);
                     ab = make_float2(rb.x - a.coef * pb[r].x, rb.y - a.coef * pb[r].y);
-                    a.tprev[(row + t) * GL_NBIN + k] = ra;
-                    if (two) a.tprev[(row + t + 1) * GL_NBIN + k] = rb;
+                    a.tprev[(row + t) * STFT_NBIN + k] = ra;
+                    if (two) a.tprev[(row + t + 1) * STFT_NBIN + k] = rb;
                 }
                 const float da = sqrtf(aa.x * aa.x + aa.y * aa.y) + 1e-16f, db = sqrtf(ab.x * ab.x + ab.y * ab.y) + 1e-16f;
                 ga = make_float2(aa.x / da, aa.y / da);
                 gb = make_float2(ab.x / db, ab.y / db);
                 if (a.part) {
                     const float ea = sqrtf(ra.x * ra.x + ra.y * ra.y) - ma[r];
-                    e_num += (double)ea * (double)ea;
-                    e_den += (double)ma[r] * (double)ma[r];
+                    e[0] += (double)ea * (double)ea;
+                    e[1] += (double)ma[r] * (double)ma[r];
                     if (two) {
                         const float eb = sqrtf(rb.x * rb.x + rb.y * rb.y) - mb[r];
-                        e_num += (double)eb * (double)eb;
-                        e_den += (double)mb[r] * (double)mb[r];
+                        e[0] += (double)eb * (double)eb;
+                        e[1] += (double)mb[r] * (double)mb[r];
                     }
                 }
             }
             if (a.phase_out) {
-                a.phase_out[(row + t) * GL_NBIN + k] = ga;
-                if (two) a.phase_out[(row + t + 1) * GL_NBIN + k] = gb;
+                a.phase_out[(row + t) * STFT_NBIN + k] = ga;
+                if (two) a.phase_out[(row + t + 1) * STFT_NBIN + k] = gb;
             }
             // (products rounded on their own, never contracted into the sums below: both instantiations of this kernel then give a
             // spectrum the same bits, which is what makes a run resumed through `phase` equal the uninterrupted one)
             float2 sa = make_float2(__fmul_rn(ma[r], ga.x), __fmul_rn(ma[r], ga.y));
             float2 sb = two ? make_float2(__fmul_rn(mb[r], gb.x), __fmul_rn(mb[r], gb.y)) : make_float2(0.f, 0.f);
-            if (k == 0 || k == GL_N / 2) sa.y = sb.y = 0.f;  // a real signal's bins 0 and 512 are real: c2r drops what is there
+            if (k == 0 || k == STFT_N / 2) sa.y = sb.y = 0.f;  // a real signal's bins 0 and 512 are real: c2r drops what is there
             buf[0][k] = make_float2(sa.x - sb.y, -(sa.y + sb.x));
-            if (k != 0 && k != GL_N / 2) buf[0][GL_N - k] = make_float2(sa.x + sb.y, sa.y - sb.x);
+            if (k != 0 && k != STFT_N / 2) buf[0][STFT_N - k] = make_float2(sa.x + sb.y, sa.y - sb.x);
         }
     }
     __syncthreads();
     fft1024_stockham(buf[0], buf[1], tw, i);                 // (1024 s_t, -1024 s_t+1) in buf[1]
-    float* fa = a.next + (row + t) * GL_N;
+    float* fa = a.next + (row + t) * STFT_N;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int j = i + 256 * r;
         const float2 y = buf[1][j];
-        fa[j] = w[r] * (y.x * (1.0f / GL_N));
-        if (two) fa[GL_N + j] = w[r] * (-y.y * (1.0f / GL_N));
+        fa[j] = stft1024_inverse_sample(y.x, w[r]);
+        if (two) fa[STFT_N + j] = stft1024_inverse_sample(-y.y, w[r]);
     }
     if (!FIRST && a.part) {
-        // the block's two sums: a butterfly over the lanes of each wave, then the waves in ascending order
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            e_num += __shfl_xor(e_num, d, 64);
-            e_den += __shfl_xor(e_den, d, 64);
-        }
-        if ((i & 63) == 0) {
-            red[i >> 6][0] = e_num;
-            red[i >> 6][1] = e_den;
-        }
-        __syncthreads();
-        if (i < 2) a.part[((int64_t)b * a.chunks + blockIdx.x) * 2 + i] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+        block_sum_fixed<4, 2>(e, red);                       // the block's two sums, in a fixed order
+        if (i < 2) a.part[((int64_t)b * a.chunks + blockIdx.x) * 2 + i] = i == 0 ? e[0] : e[1];
     }
 }
 
@@ -289,15 +274,15 @@ __global__ __launch_bounds__(256) void gl_ola_kernel(const float* __restrict__ f
                                                      const float* __restrict__ win, float* __restrict__ wave, int64_t wave_stride,
                                                      const double* __restrict__ part, int chunks, int have_part,
                                                      double* __restrict__ inconsistency) {
-    __shared__ float wl[GL_N];
+    __shared__ float wl[STFT_N];
     const int b = blockIdx.y, i = threadIdx.x;
     const int fr = gl_row_frames(frames, b, T_max, center);
-    const int pad = center ? GL_N / 2 : (GL_N - GL_HOP) / 2;
-    const int64_t n = fr == 0 ? 0 : (center ? (int64_t)GL_HOP * (fr - 1) : (int64_t)GL_HOP * fr);
+    const int pad = stft1024_pad(center);
+    const int64_t n = fr == 0 ? 0 : (center ? (int64_t)STFT_HOP * (fr - 1) : (int64_t)STFT_HOP * fr);
 #pragma unroll
     for (int r = 0; r < 4; ++r) wl[i + 256 * r] = win[i + 256 * r];
     __syncthreads();
-    const float* fb = fin + (int64_t)b * T_max * GL_N;
+    const float* fb = fin + (int64_t)b * T_max * STFT_N;
     float* wb = wave + (int64_t)b * wave_stride;
 #pragma unroll
     for (int r = 0; r < GL_OLA / 256; ++r) {
@@ -305,28 +290,15 @@ __global__ __launch_bounds__(256) void gl_ola_kernel(const float* __restrict__ f
         if (s < wave_stride) wb[s] = s < n ? gl_sample(fb, wl, (int)s + pad, fr) : 0.f;
     }
     if (inconsistency && blockIdx.x == 0) {                          // (block-uniform)
-        __shared__ double red[4][2];
-        double num = 0.0, den = 0.0;
+        __shared__ double red[2][4];
+        double e[2] = {0.0, 0.0};                                    // numerator, denominator
         const int C = (have_part && fr > 0) ? (fr + GL_FPB - 1) / GL_FPB : 0;
         for (int c = i; c < C; c += 256) {
-            num += part[((int64_t)b * chunks + c) * 2];
-            den += part[((int64_t)b * chunks + c) * 2 + 1];
+            e[0] += part[((int64_t)b * chunks + c) * 2];
+            e[1] += part[((int64_t)b * chunks + c) * 2 + 1];
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            num += __shfl_xor(num, d, 64);
-            den += __shfl_xor(den, d, 64);
-        }
-        if ((i & 63) == 0) {
-            red[i >> 6][0] = num;
-            red[i >> 6][1] = den;
-        }
-        __syncthreads();
-        if (i == 0) {
-            num = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-            den = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-            inconsistency[b] = C > 0 ? sqrt(num) / sqrt(den) : (double)NAN;     // NaN: no iteration, or an empty row: nothing was rebuilt
-        }
+        block_sum_fixed<4, 2>(e, red);
+        if (i == 0) inconsistency[b] = C > 0 ? sqrt(e[0]) / sqrt(e[1]) : (double)NAN;   // NaN: no iteration, or an empty row: nothing was rebuilt
     }
 }
 
@@ -343,15 +315,15 @@ static int32_t griffinlim(const float* mag, const int32_t* frames, int32_t B, in
     TTS_REQUIRE(init >= 0 && init <= 2 && (init != 2 || phase), "griffinlim: init = %d (0 zero phase, 1 hash, 2 the caller's phase, which needs `phase`)", init);
     GlPlan p;
     TTS_REQUIRE(gl_plan(B, T, momentum != 0.f, p), "griffinlim: bad batch %d / t_max %d (1 .. 65535 rows, 1 .. 2^22 frames)", B, T);
-    const int64_t n_max = framing ? (int64_t)GL_HOP * (T - 1) : (int64_t)GL_HOP * T;
-    TTS_REQUIRE(wave_stride >= n_max && wave_stride < ((int64_t)1 << 31) - GL_N, "griffinlim: wave_stride = %lld, %d frames give %lld samples",
+    const int64_t n_max = framing ? (int64_t)STFT_HOP * (T - 1) : (int64_t)STFT_HOP * T;
+    TTS_REQUIRE(wave_stride >= n_max && wave_stride < ((int64_t)1 << 31) - STFT_N, "griffinlim: wave_stride = %lld, %d frames give %lld samples",
                 (long long)wave_stride, T, (long long)n_max);
     TTS_REQUIRE(workspace_bytes >= p.bytes, "griffinlim: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)p.bytes);
     char* ws = (char*)workspace;
     float* win = (float*)(ws + p.window);
     float2* tw = (float2*)(ws + p.twiddle);
     float* fr_ab[2] = {(float*)(ws + p.frames_a), (float*)(ws + p.frames_b)};
-    hipLaunchKernelGGL(gl_tables_kernel, dim3(GL_N / 256), dim3(256), 0, s, win, tw);
+    hipLaunchKernelGGL(gl_tables_kernel, dim3(STFT_N / 256), dim3(256), 0, s, win, tw);
     TTS_CHECK_HIP(hipGetLastError());
     GlArgs a;
     memset(&a, 0, sizeof(a));
@@ -405,8 +377,8 @@ __global__ __launch_bounds__(256) void mel_to_linear_kernel(const float* __restr
     }
     __syncthreads();
     if (t >= T_max) return;
-    float* ob = mag + (int64_t)b * GL_NBIN * T_max;
-    for (int f = f0 + fy; f < min(f0 + ML_F, GL_NBIN); f += 4) {
+    float* ob = mag + (int64_t)b * STFT_NBIN * T_max;
+    for (int f = f0 + fy; f < min(f0 + ML_F, STFT_NBIN); f += 4) {
         float acc = 0.f;
         if (live) {
             const float* pr = pinv + (int64_t)f * n_mels;
@@ -422,7 +394,7 @@ static int32_t mel_to_linear(const float* mel, const int32_t* frames, int32_t B,
     TTS_REQUIRE(mel && frames && pinv && mag, "mel_to_linear: null argument");
     TTS_REQUIRE(n_mels >= 1 && n_mels <= GL_MAXMEL, "mel_to_linear: n_mels = %d outside [1, %d]", n_mels, GL_MAXMEL);
     TTS_REQUIRE(B >= 1 && B <= 65535 && T >= 1 && T <= (1 << 22), "mel_to_linear: bad batch %d / t_max %d (1 .. 65535 rows, 1 .. 2^22 frames)", B, T);
-    hipLaunchKernelGGL(mel_to_linear_kernel, dim3((T + ML_T - 1) / ML_T, (GL_NBIN + ML_F - 1) / ML_F, B), dim3(256), 0, s, mel, frames, pinv,
+    hipLaunchKernelGGL(mel_to_linear_kernel, dim3((T + ML_T - 1) / ML_T, (STFT_NBIN + ML_F - 1) / ML_F, B), dim3(256), 0, s, mel, frames, pinv,
                        n_mels, T, log_input, floor_v, mag);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;

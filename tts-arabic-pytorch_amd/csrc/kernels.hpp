@@ -72,11 +72,9 @@ int32_t launch_add_pos(float* x, const float* pos_table, int32_t pos_stride, con
 int32_t launch_dwconv7(const float* x, const float* w, const float* bias, const int64_t* lens, int32_t B, int32_t C,
                        int32_t S, float* y, hipStream_t s);
 
-// the window and the overlap-add shared by the denoiser and the Vocos ISTFT head
-void hann_window_1024(std::vector<float>& window);   // periodic hann, n = 1024 (denoiser.hip)
-int32_t launch_overlap_add(const float* Y, const float* win, const int64_t* frames, int32_t frames_mul, int32_t frames_add,
-                           int32_t pad, int32_t B, int32_t F, int32_t n_max, float* wave, int64_t wave_bs, hipStream_t s,
-                           int32_t frame_major = 0,    // Y as [b][k][F] (0) or [b][F][k] (1)
+// the overlap-add shared by the denoiser and the Vocos ISTFT head (denoiser.hip): Y [B][F][1024] frame-major, frames[b] of them live
+int32_t launch_overlap_add(const float* Y, const float* win, const int64_t* frames, int32_t pad, int32_t B, int32_t F, int32_t n_max,
+                           float* wave, int64_t wave_bs, hipStream_t s,
                            const float* keep_rows = nullptr);   // device [B]: a row whose value is not > 0 is not written (denoise_rows)
 
 // Recording preparation (resample.hip, trim.hip; include/ttsamd.h states the arithmetic)

@@ -4,7 +4,7 @@
 //   same   (pad 384 per side, stft(center=False)):  frames = n / 256      (n >= 385)
 //   center (pad 512 per side, stft(center=True)):   frames = n / 256 + 1  (n >= 513)
 // A block of 256 threads owns MS_FPB = 16 consecutive frames of one utterance.  Two real frames share one complex 1024-point FFT in LDS
-// (fft1024.hpp: frame t in .x, frame t + 1 in .y, t even; X_t[k] = (Z[k] + conj Z[1024 - k]) / 2, X_t+1[k] = (Z[k] - conj Z[1024 - k]) / 2i),
+// (fft1024.hpp: frame t in .x, frame t + 1 in .y, t even; the two spectra unpacked by bin k and 1024 - k, stft1024.hpp),
 // the magnitudes of bins 0..512 go to an LDS strip, thread (j, m) sums band m of frame t + j over the band's non-zero bin range
 // [lo, hi) (found at create from the matrix itself: a dense matrix has the range [0, 513) and is summed in full), its weights read once
 // per block from the filterbank stored TRANSPOSED ([513][128]: the lanes of a wave read consecutive floats) when the band has at most 32
@@ -20,16 +20,16 @@
 #include <vector>
 
 #include "kernels.hpp"
-#include "fft1024.hpp"
+#include "stft1024.hpp"
 
 namespace ttsamd {
 
-constexpr int MS_NFFT = 1024, MS_HOP = 256, MS_NBIN = MS_NFFT / 2 + 1, MS_MAXMEL = 128, MS_FPB = 16, MS_WREG = 32;
+constexpr int MS_MAXMEL = 128, MS_FPB = 16, MS_WREG = 32;
 
 struct MelSpec {
     float* dev = nullptr;     // fbT [513][128] | window [1024] | twiddles [1024] x (cos, -sin)
     int2* range = nullptr;    // [128] (lo, hi): bins of band m outside [lo, hi) are zero
-    int64_t window = 0, twiddle = 0;
+    Stft1024Tables stft = {0, 0};
     int n_mels = 0, center = 0, mag_mode = 0;
     float log_clip = 0.f;
 };
@@ -37,16 +37,16 @@ struct MelSpec {
 int32_t melspec_create(const float* fbank, int32_t n_mels, int32_t n_fft, int32_t hop, int32_t framing, int32_t mag_mode,
                        float log_clip, MelSpec** out) {
     TTS_REQUIRE(fbank && out, "melspec_create: null argument");
-    TTS_REQUIRE(n_fft == MS_NFFT && hop == MS_HOP, "melspec_create: only n_fft = win = %d, hop = %d is built (got %d / %d)", MS_NFFT,
-                MS_HOP, n_fft, hop);
+    TTS_REQUIRE(n_fft == STFT_N && hop == STFT_HOP, "melspec_create: only n_fft = win = %d, hop = %d is built (got %d / %d)", STFT_N,
+                STFT_HOP, n_fft, hop);
     TTS_REQUIRE(n_mels >= 1 && n_mels <= MS_MAXMEL, "melspec_create: n_mels = %d outside [1, %d]", n_mels, MS_MAXMEL);
     TTS_REQUIRE((framing == 0 || framing == 1) && (mag_mode == 0 || mag_mode == 1), "melspec_create: framing / mag_mode must be 0 or 1");
-    std::vector<float> blob((size_t)MS_NBIN * MS_MAXMEL, 0.f);
+    std::vector<float> blob((size_t)STFT_NBIN * MS_MAXMEL, 0.f);
     std::vector<int2> range(MS_MAXMEL, make_int2(0, 0));
     for (int m = 0; m < n_mels; ++m) {
-        int lo = MS_NBIN, hi = 0;
-        for (int f = 0; f < MS_NBIN; ++f) {
-            const float v = fbank[(size_t)m * MS_NBIN + f];
+        int lo = STFT_NBIN, hi = 0;
+        for (int f = 0; f < STFT_NBIN; ++f) {
+            const float v = fbank[(size_t)m * STFT_NBIN + f];
             blob[(size_t)f * MS_MAXMEL + m] = v;
             if (v != 0.f) {                                     // (NaN != 0 too: a poisoned matrix poisons its band, as a matmul would)
                 lo = f < lo ? f : lo;
@@ -57,11 +57,7 @@ int32_t melspec_create(const float* fbank, int32_t n_mels, int32_t n_fft, int32_
     }
     auto* h = new MelSpec();
     h->n_mels = n_mels; h->center = framing; h->mag_mode = mag_mode; h->log_clip = log_clip;
-    std::vector<float> wnd;
-    hann_window_1024(wnd);
-    h->window = (int64_t)blob.size();
-    blob.insert(blob.end(), wnd.begin(), wnd.end());
-    h->twiddle = fft1024_append_twiddles(blob);
+    h->stft = stft1024_append_tables(blob);
     hipError_t e = hipMalloc((void**)&h->dev, blob.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc((void**)&h->range, range.size() * sizeof(int2));
@@ -89,13 +85,13 @@ __global__ __launch_bounds__(256, 4) void melspec_kernel(const float* __restrict
                                                       const float* __restrict__ win, const float2* __restrict__ tw_g, int n_mels,
                                                       int center, int mag_mode, float log_clip, int T_max, float* __restrict__ mel,
                                                       int64_t* __restrict__ frames_out) {
-    __shared__ float2 buf[2][MS_NFFT];
-    __shared__ float2 tw[MS_NFFT];
-    __shared__ float mag[2][MS_NBIN + 3];
+    __shared__ float2 buf[2][STFT_N];
+    __shared__ float2 tw[STFT_N];
+    __shared__ float mag[2][STFT_NBIN + 3];
     __shared__ float tile[MS_MAXMEL][MS_FPB + 1];
     const int b = blockIdx.y, t0 = blockIdx.x * MS_FPB, i = threadIdx.x;
     const int n = (int)max((int64_t)0, min(ns[b], wave_bs));     // indices stay inside the row whatever the caller's lengths say
-    const int fr = min(n / MS_HOP + center, T_max);
+    const int fr = min(n / STFT_HOP + center, T_max);
     if (blockIdx.x == 0 && i == 0 && frames_out) frames_out[b] = fr;
     float* mb = mel + (int64_t)b * n_mels * T_max;
     if (t0 >= fr || n == 0) {                                    // past the utterance: zeros, coalesced along t
@@ -106,13 +102,11 @@ __global__ __launch_bounds__(256, 4) void melspec_kernel(const float* __restrict
         return;
     }
     const float* wb = wave + (int64_t)b * wave_bs;
-    const int pad = center ? MS_NFFT / 2 : (MS_NFFT - MS_HOP) / 2;
+    const int pad = stft1024_pad(center);
+    stft1024_load_twiddles(tw, tw_g, i);
     float w[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        tw[i + 256 * r] = tw_g[i + 256 * r];
-        w[r] = win[i + 256 * r];
-    }
+    for (int r = 0; r < 4; ++r) w[r] = win[i + 256 * r];
     const int j = i >> 7, m = i & 127;                           // filterbank: thread = (frame of the pair, band)
     const int2 rg = m < n_mels ? range[m] : make_int2(0, 0);
     // a band of at most MS_WREG bins (every triangle of the built configurations: <= 31) keeps its weights in registers for the
@@ -126,13 +120,8 @@ __global__ __launch_bounds__(256, 4) void melspec_kernel(const float* __restrict
     auto load_pair = [&](const int t) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            int s0 = t * MS_HOP + i + 256 * r - pad, s1 = s0 + MS_HOP;   // reflect padding at the utterance's own ends
-            if (s0 < 0) s0 = -s0;
-            if (s0 >= n) s0 = 2 * (n - 1) - s0;
-            s0 = min(max(s0, 0), n - 1);                         // shorter than the padding: torch raises, the wrappers too; here only in-row
-            if (s1 < 0) s1 = -s1;
-            if (s1 >= n) s1 = 2 * (n - 1) - s1;
-            s1 = min(max(s1, 0), n - 1);
+            const int s = t * STFT_HOP + i + 256 * r - pad;        // reflect padding at the utterance's own ends (n > 0 here)
+            const int s0 = stft1024_reflect(s, n), s1 = stft1024_reflect(s + STFT_HOP, n);
             xa[r] = t < fr ? wb[s0] : 0.f;
             xb[r] = t + 1 < fr ? wb[s1] : 0.f;
         }
@@ -153,10 +142,10 @@ __global__ __launch_bounds__(256, 4) void melspec_kernel(const float* __restrict
         for (int r = 0; r < 3; ++r) {
             const int k = i + 256 * r;                           // bins 0..511, and 512 by thread 0
             if (r == 2 && i != 0) break;
-            const float2 z = buf[1][k], c = buf[1][(MS_NFFT - k) & (MS_NFFT - 1)];
-            const float ar = 0.5f * (z.x + c.x), ai = 0.5f * (z.y - c.y);      // X_t[k]
-            const float br = 0.5f * (z.y + c.y), bi = 0.5f * (c.x - z.x);      // X_t+1[k]
-            float pa = ar * ar + ai * ai, pb = br * br + bi * bi;
+            const float2 z = buf[1][k], c = buf[1][(STFT_N - k) & (STFT_N - 1)];
+            float2 xt, xu;                                       // X_t[k], X_t+1[k]
+            stft1024_unpack_pair(z, c, xt, xu);
+            float pa = xt.x * xt.x + xt.y * xt.y, pb = xu.x * xu.x + xu.y * xu.y;
             if (mag_mode) { pa += 1e-9f; pb += 1e-9f; }
             mag[0][k] = sqrtf(pa);
             mag[1][k] = sqrtf(pb);
@@ -174,7 +163,7 @@ __global__ __launch_bounds__(256, 4) void melspec_kernel(const float* __restrict
                             for (int q = c; q < c + 8; ++q) {
                                 // the select must stay on v, not on the product: past the band's end v is another bin's magnitude, which
                                 // may be Inf / NaN for such an input, and 0 * v would poison a band the reference leaves finite
-                                const float v = mg[min(rg.x + q, MS_NBIN - 1)];
+                                const float v = mg[min(rg.x + q, STFT_NBIN - 1)];
                                 acc += wr[q] * (q < cnt ? v : 0.f);
                             }
                         }
@@ -200,7 +189,7 @@ int32_t melspec_forward(const MelSpec* h, const float* wave, int64_t wave_stride
     TTS_REQUIRE(B >= 1 && B <= 65535 && T_max >= 0 && wave_stride >= 0, "melspec_forward: bad batch %d / t_max %d / stride", B, T_max);
     const int nblk = T_max > 0 ? (T_max + MS_FPB - 1) / MS_FPB : 1;     // t_max = 0: the frame counts only
     hipLaunchKernelGGL(melspec_kernel, dim3(nblk, B), dim3(256), 0, s, wave, wave_stride, nsamples, h->dev, h->range,
-                       h->dev + h->window, reinterpret_cast<const float2*>(h->dev + h->twiddle), h->n_mels, h->center, h->mag_mode,
+                       h->dev + h->stft.window, reinterpret_cast<const float2*>(h->dev + h->stft.twiddle), h->n_mels, h->center, h->mag_mode,
                        h->log_clip, T_max, mel, frames_out);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;

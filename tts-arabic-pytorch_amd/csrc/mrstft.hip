@@ -98,7 +98,7 @@ __global__ __launch_bounds__(N / 4) void mr_stft_kernel(const float* __restrict_
     mr_load<N>(xr, n, f0, H, i, w, cur);
     __syncthreads();                                           // the twiddles
     double sref[3] = {0.0, 0.0, 0.0}, lref[3] = {0.0, 0.0, 0.0};
-    double a_d = 0.0, a_r = 0.0, a_l = 0.0;
+    double acc[3] = {0.0, 0.0, 0.0};                            // dS^2, S_ref^2, |d ln S|
     for (int fi = 0; fi < nf; ++fi) {
         for (int sig = 0; sig < 2; ++sig) {
             double *ar = buf, *ai = buf + N, *br = buf + 2 * N, *bi = buf + 3 * N;
@@ -123,9 +123,9 @@ __global__ __launch_bounds__(N / 4) void mr_stft_kernel(const float* __restrict_
                         lref[q] = l;
                     } else {
                         const double d = sref[q] - S;
-                        a_d += d * d;
-                        a_r += sref[q] * sref[q];
-                        a_l += fabs(lref[q] - l);
+                        acc[0] += d * d;
+                        acc[1] += sref[q] * sref[q];
+                        acc[2] += fabs(lref[q] - l);
                     }
                 }
             }
@@ -134,24 +134,8 @@ __global__ __launch_bounds__(N / 4) void mr_stft_kernel(const float* __restrict_
             for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        a_d += __shfl_xor(a_d, d, 64);
-        a_r += __shfl_xor(a_r, d, 64);
-        a_l += __shfl_xor(a_l, d, 64);
-    }
-    if ((i & 63) == 0) {
-        red[0][i >> 6] = a_d;
-        red[1][i >> 6] = a_r;
-        red[2][i >> 6] = a_l;
-    }
-    __syncthreads();
-    if (i < 3) {
-        double s = red[i][0];
-#pragma unroll
-        for (int v = 1; v < NW; ++v) s += red[i][v];
-        part[((int64_t)b * Cm + blockIdx.x) * 3 + i] = s;
-    }
+    block_sum_fixed<NW, 3>(acc, red);
+    if (i < 3) part[((int64_t)b * Cm + blockIdx.x) * 3 + i] = i == 0 ? acc[0] : i == 1 ? acc[1] : acc[2];
 }
 
 __global__ __launch_bounds__(64) void mr_stft_finish_kernel(MrPlan p, int64_t stride, const int64_t* __restrict__ ns,

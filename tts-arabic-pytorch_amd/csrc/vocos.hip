@@ -14,11 +14,11 @@
 #include <vector>
 
 #include "kernels.hpp"
-#include "fft1024.hpp"
+#include "stft1024.hpp"
 
 namespace ttsamd {
 
-constexpr int V_NFFT = 1024, V_HOP = 256, V_NBIN = 513, V_SPEC_CP = 1152;
+constexpr int V_SPEC_CP = 1152;   // head.out rows: 2 x 513 padded to 9 x 128 (co tiles)
 
 struct VConv {
     int64_t w_off = 0, b_off = -1, w16_off = 0;
@@ -34,7 +34,8 @@ struct Vocos {
     int in_ch = 80, in_chp = 80, dim = 512, inter = 1536;     // in_chp: in_ch rounded up to the conv engine's 8-channel chunks (100 -> 104)
     int center = 0;                                           // ISTFT trimming: 0 "same" (pad 384, 256 T samples), 1 "center" (pad 512, 256 (T - 1))
     VConv embed, head;
-    int64_t n0_g, n0_b, fl_g, fl_b, window, twiddle;
+    int64_t n0_g, n0_b, fl_g, fl_b;
+    Stft1024Tables stft;                                       // vocos_istft_kernel, the overlap-add
     std::vector<VBlock> blocks;
 };
 
@@ -128,14 +129,10 @@ int32_t vocos_create(const ttsamd_tensor* weights, int32_t n, int32_t in_ch, int
     h->fl_g = b.raw("backbone.final_layer_norm.weight", dim);
     h->fl_b = b.raw("backbone.final_layer_norm.bias", dim);
     // head.out: Linear(dim -> n_fft + 2), rows padded to V_SPEC_CP so the spectrum buffer is [re | im | 0]
-    h->head = b.conv("head.out", dim, V_NFFT + 2, 1, V_SPEC_CP);
+    h->head = b.conv("head.out", dim, STFT_N + 2, 1, V_SPEC_CP);
     int32_t rc = b.rc;
     if (rc == 0) {
-        std::vector<float> wnd;
-        hann_window_1024(wnd);
-        h->window = (int64_t)b.blob.size();
-        b.blob.insert(b.blob.end(), wnd.begin(), wnd.end());
-        h->twiddle = fft1024_append_twiddles(b.blob);            // vocos_istft_kernel
+        h->stft = stft1024_append_tables(b.blob);
         hipError_t e = hipMalloc((void**)&h->dev, b.blob.size() * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(h->dev, b.blob.data(), b.blob.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMalloc((void**)&h->dev16, b.blob16.size() * sizeof(uint16_t));
@@ -185,8 +182,8 @@ __device__ __forceinline__ void vocos_spec_tile(const float* __restrict__ O, int
     for (int r = 0; r < 4; ++r) {
         const int f = f0 + ty + 8 * r, t = t0 + tx;
         float2 v = make_float2(0.f, 0.f);
-        if (f < V_NBIN && t >= t_lo && t < t_hi) {
-            const float lm = ob[(int64_t)f * T + t], ph = ob[(int64_t)(V_NBIN + f) * T + t];
+        if (f < STFT_NBIN && t >= t_lo && t < t_hi) {
+            const float lm = ob[(int64_t)f * T + t], ph = ob[(int64_t)(STFT_NBIN + f) * T + t];
             float mag = expf(lm);
             if (sub) mag -= dn * bias[f];
             mag = fminf(fmaxf(mag, 0.f), 100.f);
@@ -198,7 +195,7 @@ __device__ __forceinline__ void vocos_spec_tile(const float* __restrict__ O, int
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int t = t0 + ty + 8 * r, f = f0 + tx;
-        if (t >= t_lo && t < t_hi && f < V_NBIN) S[((int64_t)b * T + t) * V_NBIN + f] = tile[tx][ty + 8 * r];
+        if (t >= t_lo && t < t_hi && f < STFT_NBIN) S[((int64_t)b * T + t) * STFT_NBIN + f] = tile[tx][ty + 8 * r];
     }
 }
 
@@ -214,27 +211,22 @@ __global__ __launch_bounds__(256) void vocos_spec_t_kernel(const float* __restri
 // frame t of row b: its 513 bins -> 1024 windowed samples, by the block's 256 threads
 __device__ __forceinline__ void vocos_istft_frame(const float2* __restrict__ S, const float* __restrict__ win, const float2* __restrict__ tw_g,
                                                   int b, int t, int T, float* __restrict__ Y) {
-    __shared__ float2 buf[2][V_NFFT];
-    __shared__ float2 tw[V_NFFT];
+    __shared__ float2 buf[2][STFT_N];
+    __shared__ float2 tw[STFT_N];
     const int i = threadIdx.x;
-    const float2* sb = S + ((int64_t)b * T + t) * V_NBIN;
+    const float2* sb = S + ((int64_t)b * T + t) * STFT_NBIN;
+    stft1024_load_twiddles(tw, tw_g, i);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int k = i + 256 * r;
-        tw[k] = tw_g[k];
-        float2 x = sb[k <= V_NFFT / 2 ? k : V_NFFT - k];         // conj(X)[k]: conj S[k] below Nyquist, S[1024 - k] above
-        if (k <= V_NFFT / 2) x.y = -x.y;
-        if (k == 0 || k == V_NFFT / 2) x.y = 0.f;
+        float2 x = sb[k <= STFT_N / 2 ? k : STFT_N - k];         // conj(X)[k]: conj S[k] below Nyquist, S[1024 - k] above
+        if (k <= STFT_N / 2) x.y = -x.y;
+        if (k == 0 || k == STFT_N / 2) x.y = 0.f;
         buf[0][k] = x;
     }
     __syncthreads();
     fft1024_stockham(buf[0], buf[1], tw, i);
-    float* yb = Y + ((int64_t)b * T + t) * V_NFFT;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int k = i + 256 * r;
-        yb[k] = buf[1][k].x * (1.0f / V_NFFT) * win[k];
-    }
+    stft1024_store_inverse_frame(buf[1], win, Y + ((int64_t)b * T + t) * STFT_N, i);
 }
 
 __global__ __launch_bounds__(256) void vocos_istft_kernel(const float2* __restrict__ S, const int64_t* __restrict__ lens,
@@ -280,34 +272,23 @@ __global__ __launch_bounds__(256) void vocos_istft_windows_kernel(const float2* 
     vocos_istft_frame(S, win, tw_g, w, t, T, Y);
 }
 
-// overlap_add_kernel (denoiser.hip) on frame-major Y for the samples of frame start[w] + blockIdx.x alone: the same terms over t
-// ascending, the same envelope, so the same bits
+// overlap_add_kernel (denoiser.hip) for the samples of frame start[w] + blockIdx.x alone: the same stft1024_ola_sample, so the same bits
 __global__ __launch_bounds__(256) void vocos_overlap_add_windows_kernel(const float* __restrict__ Y, const float* __restrict__ win,
                                                                         const int64_t* __restrict__ lens, const VocosWinTable tab, int pad,
                                                                         int T, float* __restrict__ wave) {
     const int w = blockIdx.y;
     if ((int)blockIdx.x >= tab.len[w]) return;
     const int fr = min((int)lens[w], T);
-    const int m = (tab.start[w] + blockIdx.x) * V_HOP + threadIdx.x;
-    const int n_out = (fr - 1) * V_HOP + V_NFFT - 2 * pad;
+    const int m = (tab.start[w] + blockIdx.x) * STFT_HOP + threadIdx.x;
+    const int n_out = (fr - 1) * STFT_HOP + STFT_N - 2 * pad;
     if (m >= n_out) return;
-    const int mp = m + pad;
-    const int t_hi = min(fr - 1, mp / V_HOP);
-    const int t_lo = mp >= V_NFFT ? (mp - V_NFFT) / V_HOP + 1 : 0;
-    float acc = 0.f, env = 0.f;
-    for (int t = t_lo; t <= t_hi; ++t) {
-        const int k = mp - t * V_HOP;
-        if (k < 0 || k >= V_NFFT) continue;
-        acc += Y[(int64_t)w * V_NFFT * T + (int64_t)k + (int64_t)t * V_NFFT];
-        env += win[k] * win[k];
-    }
-    wave[(int64_t)w * V_HOP * T + m] = acc / env;
+    wave[(int64_t)w * STFT_HOP * T + m] = stft1024_ola_sample(Y + (int64_t)w * STFT_N * T, win, m + pad, fr);
 }
 
 // bias_vec[f] = min(exp(O[f][0]), 100)   (pretrained.py:65-69)
 __global__ void vocos_bias_kernel(const float* __restrict__ O, int T, float* __restrict__ out) {
     const int f = blockIdx.x * 64 + threadIdx.x;
-    if (f < V_NBIN) out[f] = fminf(expf(O[(int64_t)f * T]), 100.f);
+    if (f < STFT_NBIN) out[f] = fminf(expf(O[(int64_t)f * T]), 100.f);
 }
 
 // mel [B][in_ch][T] -> [B][in_chp][T], the added channel rows zero (in_ch = 100: the embed conv reads 8-channel chunks)
@@ -328,7 +309,7 @@ static void vcarve(const Vocos* h, Arena& a, int B, int T, VWs& w) {
     w.d = a.take<float>((int64_t)B * h->dim * T);
     w.h = a.take<float>((int64_t)B * h->inter * T);
     w.o = a.take<float>((int64_t)B * V_SPEC_CP * T);
-    w.y = a.take<float>((int64_t)B * V_NFFT * T);
+    w.y = a.take<float>((int64_t)B * STFT_N * T);
 }
 int64_t vocos_workspace_bytes(const Vocos* h, int32_t B, int32_t T) {
     Arena a(nullptr, 0);
@@ -385,7 +366,7 @@ int32_t vocos_bias_vec(const Vocos* h, float* out513, void* ws, int64_t ws_bytes
     }
     TTS_CHECK_HIP(hipMemsetAsync(zero_mel, 0, (size_t)h->in_chp * T * sizeof(float), s));
     TTS_TRY(vocos_features(h, zero_mel, nullptr, 1, T, w, s));
-    hipLaunchKernelGGL(vocos_bias_kernel, dim3((V_NBIN + 63) / 64), dim3(64), 0, s, w.o, T, out513);
+    hipLaunchKernelGGL(vocos_bias_kernel, dim3((STFT_NBIN + 63) / 64), dim3(64), 0, s, w.o, T, out513);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -413,18 +394,16 @@ static int32_t vocos_padded_features(const Vocos* h, const float* mel, const int
 static int32_t vocos_head_run(const Vocos* h, const float* O, int64_t o_bs, const int64_t* lens, int B, int T, float denoise,
                               const float* denoise_rows, const float* bias_vec, float* wave, const VWs& w, hipStream_t s) {
     float2* S = reinterpret_cast<float2*>(w.h);
-    hipLaunchKernelGGL(vocos_spec_t_kernel, dim3((T + 31) / 32, (V_NBIN + 31) / 32, B), dim3(256), 0, s, O, o_bs,
+    hipLaunchKernelGGL(vocos_spec_t_kernel, dim3((T + 31) / 32, (STFT_NBIN + 31) / 32, B), dim3(256), 0, s, O, o_bs,
                        (denoise != 0.f || denoise_rows) ? bias_vec : nullptr, denoise, denoise_rows, lens, T, S);
-    hipLaunchKernelGGL(vocos_istft_kernel, dim3(T, B), dim3(256), 0, s, S, lens, h->dev + h->window,
-                       reinterpret_cast<const float2*>(h->dev + h->twiddle), T, w.y);
+    hipLaunchKernelGGL(vocos_istft_kernel, dim3(T, B), dim3(256), 0, s, S, lens, h->dev + h->stft.window,
+                       reinterpret_cast<const float2*>(h->dev + h->stft.twiddle), T, w.y);
     TTS_CHECK_HIP(hipGetLastError());
     // "center" (24k): torch.istft(center=True) trimming, pad = n_fft / 2, n_out = hop * (frames - 1) per utterance; rows keep the stride hop * T
     if (h->center)
-        return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, V_NFFT / 2, B, T, V_HOP * (T - 1), wave, (int64_t)V_HOP * T, s,
-                                  /*frame_major=*/1);
+        return launch_overlap_add(w.y, h->dev + h->stft.window, lens, stft1024_pad(1), B, T, STFT_HOP * (T - 1), wave, (int64_t)STFT_HOP * T, s);
     // overlap-add with "same" trimming (pad = (n_fft - hop) / 2, n_out = hop * frames) over the frame-major time-domain frames
-    return launch_overlap_add(w.y, h->dev + h->window, lens, 1, 0, (V_NFFT - V_HOP) / 2, B, T, V_HOP * T, wave,
-                              (int64_t)V_HOP * T, s, /*frame_major=*/1);
+    return launch_overlap_add(w.y, h->dev + h->stft.window, lens, stft1024_pad(0), B, T, STFT_HOP * T, wave, (int64_t)STFT_HOP * T, s);
 }
 
 // denoise_rows: device [B] in place of the scalar (ttsamd_vocos_forward_rows), nullptr: the scalar (ttsamd_vocos_forward)
@@ -441,7 +420,7 @@ int32_t vocos_forward(const Vocos* h, const float* mel, const int64_t* lens, int
         return TTSAMD_ENOMEM;
     }
     // complex spectrum frame-major into the (dead) hidden buffer of the backbone: 513 float2 per frame <= inter floats
-    TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_forward: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
+    TTS_REQUIRE(2 * STFT_NBIN <= h->inter, "vocos_forward: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
     TTS_TRY(vocos_padded_features(h, mel, lens, B, T, w, s));
     return vocos_head_run(h, w.o, (int64_t)V_SPEC_CP * T, lens, B, T, denoise, denoise_rows, bias_vec, wave, w, s);
 }
@@ -451,7 +430,7 @@ __global__ __launch_bounds__(256) void vocos_copy_features_kernel(const float* _
                                                                   float* __restrict__ out) {
     const int b = blockIdx.y;
     const int len = min((int)lens[b], T);
-    const int64_t n = (int64_t)(V_NFFT + 2) * T;
+    const int64_t n = (int64_t)(STFT_N + 2) * T;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256)
         out[b * n + e] = (int)(e % T) < len ? O[(int64_t)b * V_SPEC_CP * T + e] : 0.f;
 }
@@ -468,7 +447,7 @@ int32_t vocos_features_out(const Vocos* h, const float* mel, const int64_t* lens
         return TTSAMD_ENOMEM;
     }
     TTS_TRY(vocos_padded_features(h, mel, lens, B, T, w, s));
-    hipLaunchKernelGGL(vocos_copy_features_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)(V_NFFT + 2) * T + 255) / 256, 1024), B),
+    hipLaunchKernelGGL(vocos_copy_features_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)(STFT_N + 2) * T + 255) / 256, 1024), B),
                        dim3(256), 0, s, w.o, lens, T, out);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
@@ -487,8 +466,8 @@ int32_t vocos_head(const Vocos* h, const float* feats, const int64_t* lens, int3
         set_error("vocos_head: workspace of %lld bytes needed, %lld given", (long long)a.off, (long long)ws_bytes);
         return TTSAMD_ENOMEM;
     }
-    TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_head: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
-    return vocos_head_run(h, feats, (int64_t)(V_NFFT + 2) * T, lens, B, T, 0.f, denoise_rows, bias_vec, wave, w, s);
+    TTS_REQUIRE(2 * STFT_NBIN <= h->inter, "vocos_head: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
+    return vocos_head_run(h, feats, (int64_t)(STFT_N + 2) * T, lens, B, T, 0.f, denoise_rows, bias_vec, wave, w, s);
 }
 
 // 3 (embed, k = 7) + 3 per ConvNeXt block (depthwise k = 7; LayerNorm, the pointwise convs and head.out are per frame), then the ISTFT's
@@ -506,9 +485,9 @@ int32_t vocos_forward_windows(const Vocos* h, const float* mel, const int64_t* l
                               int64_t ws_bytes, hipStream_t s) {
     TTS_REQUIRE(h && mel && lens && wave && need_start && need_len, "vocos_forward_windows: null argument");
     TTS_REQUIRE(W >= 1 && W <= TTSAMD_STREAM_MAX_WINDOWS, "vocos_forward_windows: %d windows (1 .. %d)", W, TTSAMD_STREAM_MAX_WINDOWS);
-    TTS_REQUIRE(T >= 1 && (int64_t)V_NFFT * T * W < (1ll << 31), "vocos_forward_windows: bad w_max %d", T);
+    TTS_REQUIRE(T >= 1 && (int64_t)STFT_N * T * W < (1ll << 31), "vocos_forward_windows: bad w_max %d", T);
     TTS_REQUIRE(!denoise_rows || bias_vec, "vocos_forward_windows: denoise_rows needs bias_vec");
-    TTS_REQUIRE(2 * V_NBIN <= h->inter, "vocos_forward_windows: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
+    TTS_REQUIRE(2 * STFT_NBIN <= h->inter, "vocos_forward_windows: the spectrum does not fit the hidden buffer (inter %d)", h->inter);
     VocosWinTable tab = {};
     int max_len = 0;
     for (int w = 0; w < W; ++w) {
@@ -530,12 +509,12 @@ int32_t vocos_forward_windows(const Vocos* h, const float* mel, const int64_t* l
     float2* S = reinterpret_cast<float2*>(v.h);
     const int r_l = h->center ? 1 : 2, n_frames = std::min(max_len + r_l + 2, (int)T);
     // the tiles start at the 32-frame boundary at or below a window's first frame
-    hipLaunchKernelGGL(vocos_spec_t_windows_kernel, dim3((n_frames + 31 + 31) / 32, (V_NBIN + 31) / 32, W), dim3(256), 0, s, v.o,
+    hipLaunchKernelGGL(vocos_spec_t_windows_kernel, dim3((n_frames + 31 + 31) / 32, (STFT_NBIN + 31) / 32, W), dim3(256), 0, s, v.o,
                        denoise_rows ? bias_vec : nullptr, denoise_rows, lens, tab, r_l, T, S);
-    hipLaunchKernelGGL(vocos_istft_windows_kernel, dim3(n_frames, W), dim3(256), 0, s, S, lens, tab, r_l, h->dev + h->window,
-                       reinterpret_cast<const float2*>(h->dev + h->twiddle), T, v.y);
-    hipLaunchKernelGGL(vocos_overlap_add_windows_kernel, dim3(max_len, W), dim3(256), 0, s, v.y, h->dev + h->window, lens, tab,
-                       h->center ? V_NFFT / 2 : (V_NFFT - V_HOP) / 2, T, wave);
+    hipLaunchKernelGGL(vocos_istft_windows_kernel, dim3(n_frames, W), dim3(256), 0, s, S, lens, tab, r_l, h->dev + h->stft.window,
+                       reinterpret_cast<const float2*>(h->dev + h->stft.twiddle), T, v.y);
+    hipLaunchKernelGGL(vocos_overlap_add_windows_kernel, dim3(max_len, W), dim3(256), 0, s, v.y, h->dev + h->stft.window, lens, tab,
+                       stft1024_pad(h->center), T, wave);
     TTS_CHECK_HIP(hipGetLastError());
     return 0;
 }
