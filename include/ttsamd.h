@@ -585,6 +585,33 @@ int32_t ttsamd_frames_compact(const float* mel, const float* extra, const int64_
                               int32_t n_extra, int32_t t_max, float thresh, float* mel_out, float* extra_out, int64_t* lens_out,
                               void* stream);
 
+/* ---- Paragraph join (csrc/join.hip): the rows of a ragged batch of waves become ONE row -- each cut to its speech bounds, faded at
+ * both edges, followed by an exact pause or overlap-added onto the next row -- before anything leaves the device.
+ * All pointers are DEVICE pointers: wave fp32 [batch][wave_stride]; nsamples int64 [batch]; bounds int64 [batch][2] (what
+ * ttsamd_trim_bounds writes) or NULL = whole rows; gap int64 [batch]: samples of silence behind row b (the last entry: the trailing
+ * silence), negative = that many samples of overlap with the next row asked for (a gap above 2^40 is taken as 2^40); fade fp32
+ * [n_fade]: a rising table, n_fade = 0 (fade may be NULL): no fades.  keep: samples kept outside the bounds on each side; lead: zeros in
+ * front of the first row.  Specified by its arithmetic, matched bit for bit:
+ *   1. source range: n_b = clamp(nsamples[b], 0, wave_stride); (s, e) = bounds[b] clamped to 0 <= s <= e <= n_b, (0, n_b) without
+ *      bounds; if e > s: s = max(0, s - keep), e = min(n_b, e + keep); m_b = e - s.  A row with m_b = 0 gives no samples; its gap counts.
+ *   2. effective gap: g_b = gap[b] where that is >= 0, else g_b = -min(-gap[b], n_fade, m_b / 2, m_{b+1} / 2) (integer halves); a
+ *      negative gap of the last row is 0.  The halves leave at most two rows over any output sample.
+ *   3. positions: p_0 = lead, p_{b+1} = p_b + m_b + g_b; total = p_{B-1} + m_{B-1} + g_{B-1}.
+ *   4. fades: y_b[i] = fl32(fl32(x_b[i] fin(i)) fout(m_b - 1 - i)), x_b[i] = wave[b][s + i], fin(i) = fout(i) = fade[i] for i < n_fade,
+ *      else 1; both act on rows shorter than 2 n_fade, and the first row fades in and the last fades out like every other.
+ *   5. out[j] = y_b[j - p_b] of the one row with p_b <= j < p_b + m_b, fl32 of the sum of the two where two rows cover j (a two-term fp32
+ *      sum does not depend on the order), 0 where none does; everything from `total` to out_stride is written as zero; samples at or
+ *      past out_stride are dropped, and `total` and `segs` are reported unclamped so that the caller can tell (the resampler's convention).
+ * out fp32 [out_stride]; segs int64 [batch][4] = (p_b, p_b + m_b, s, e): where row b lies in `out` and which of its samples went there;
+ * total int64 [1].  Two launches whatever the batch (one block scans the rows; one gather over the output: plain dword loads, 16-byte
+ * stores where out + j is aligned), no atomics, no host read-back; every source sample is read once and every output sample written
+ * once; two runs give the same bits.
+ * TTSAMD_EINVAL (nothing launched): batch outside 1 .. 4096, n_fade outside 0 .. 4096, a NULL wave / nsamples / gap / out / segs / total,
+ * a NULL fade with n_fade > 0, a negative stride, keep or lead (or one of 2^40 and more). */
+int32_t ttsamd_wave_join(const float* wave, int64_t wave_stride, const int64_t* nsamples, const int64_t* bounds, const int64_t* gap,
+                         int32_t batch, const float* fade, int32_t n_fade, int64_t keep, int64_t lead, float* out, int64_t out_stride,
+                         int64_t* segs, int64_t* total, void* stream);
+
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of
  *      Tacotron2MS.state_dict() (embedding.weight, speaker_embedding.weight, encoder.*, decoder.*,

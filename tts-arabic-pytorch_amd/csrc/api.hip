@@ -712,6 +712,12 @@ int32_t ttsamd_frames_compact(const float* mel, const float* extra, const int64_
                               void* stream) {
     return frames_compact(mel, extra, lens, batch, n_channels, n_extra, t_max, thresh, mel_out, extra_out, lens_out, (hipStream_t)stream);
 }
+int32_t ttsamd_wave_join(const float* wave, int64_t wave_stride, const int64_t* nsamples, const int64_t* bounds, const int64_t* gap,
+                         int32_t batch, const float* fade, int32_t n_fade, int64_t keep, int64_t lead, float* out, int64_t out_stride,
+                         int64_t* segs, int64_t* total, void* stream) {
+    return wave_join(wave, wave_stride, nsamples, bounds, gap, batch, fade, n_fade, keep, lead, out, out_stride, segs, total,
+                     (hipStream_t)stream);
+}
 int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
                              float* out, void* stream) {
     return average_pitch(pitch, dur, batch, n_formants, n_frames, n_tokens, out, (hipStream_t)stream);

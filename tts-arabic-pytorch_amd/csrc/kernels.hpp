@@ -93,6 +93,10 @@ int32_t trim_apply(const float* wave, int64_t wave_stride, const int64_t* bounds
                    float* out, int64_t out_stride, int64_t* lens_out, hipStream_t s);
 int32_t frames_compact(const float* mel, const float* extra, const int64_t* lens, int32_t B, int32_t C, int32_t C2, int32_t t_max,
                        float thresh, float* mel_out, float* extra_out, int64_t* lens_out, hipStream_t s);
+// Paragraph join (join.hip): the rows of a ragged batch -> one row with trimmed seams, exact pauses, faded edges and overlap-added seams
+int32_t wave_join(const float* wave, int64_t wave_stride, const int64_t* nsamples, const int64_t* bounds, const int64_t* gap, int32_t B,
+                  const float* fade, int32_t F, int64_t keep, int64_t lead, float* out, int64_t out_stride, int64_t* segs, int64_t* total,
+                  hipStream_t s);
 
 // Profiling of conv launches (bench roofline)
 void prof_begin(hipStream_t s, double flops);

@@ -43,8 +43,11 @@ def infer(args):
     with open(os.path.join(args.out_dir, 'index.tsv'), 'w', encoding='utf-8') as index:
         for k in range(0, len(lines), args.batch_size):
             batch = lines[k:k + args.batch_size]
-            wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, normalize=args.normalize,
-                             **({'limiter': True} if args.limiter else {}), **({'true_peak': True} if args.true_peak else {}))
+            level = dict(normalize=args.normalize, **({'limiter': True} if args.limiter else {}), **({'true_peak': True} if args.true_peak else {}))
+            if args.long:                           # every line is a paragraph: split, synthesised and joined on the device (tts_long)
+                wavs = [model.tts_long(line, denoise=args.denoise, speed=args.speed, **level) for line in batch]
+            else:
+                wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, **level)
             for line, wav in zip(batch, wavs):
                 if rate != 22_050:                      # the finished wave through the device resampler, then the matching file format
                     wav = resample(wav.reshape(1, -1).to('cuda'), 22_050, rate)[0]
@@ -75,6 +78,8 @@ def main(argv=None):
     p.add_argument('--limiter', action='store_true')
     # ... and with 0.99 as a true-peak ceiling (4x oversampled) instead of a sample peak, so that the resampled files do not clip
     p.add_argument('--true_peak', action='store_true')
+    # ... every line of --list as a paragraph: cut into sentences, synthesised in batches and joined on the device with pauses (tts_long)
+    p.add_argument('--long', action='store_true')
     args = p.parse_args(argv)
     if args.limiter and args.normalize in (None, 'peak'):
         p.error("--limiter needs --normalize lufs or a target in LUFS")

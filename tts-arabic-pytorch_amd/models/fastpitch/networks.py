@@ -550,6 +550,47 @@ class FastPitch2Wave(nn.Module):
             lists['true_peak'] = true_peak
         return self.tts([r['text'] for r in requests], batch_size=batch_size, vowelizer=vowelizer, **lists)
 
+    # ---- paragraph synthesis (not in the reference; text.split_text, ttsamd.join, csrc/join.hip) ----
+    @torch.inference_mode()
+    def tts_long(self, text_input: Union[str, List[str]], speed: float = 1., denoise: float = 0.005, speaker_id: int = 0, batch_size: int = 32,
+                 vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., pauses=None, max_chars: int = 200, trim_db=40.0,
+                 keep_ms: float = 10.0, fade_ms: float = 5.0, normalize=None, limiter=False, true_peak=False, return_segments: bool = False):
+        """A paragraph -> ONE wave (CPU tensor [n_samples]).  text_input: a string, or a list of strings taken as paragraphs.  The text is
+        cut into segments by text.split_text (sentences; pieces longer than max_chars at clause marks, commas, and last at a space);
+        the segments go through FastPitch, the vocoder and the denoiser in groups of batch_size, every row computed as if alone
+        (FastPitch.infer(alone=True)), so that a sentence's audio is `tts(sentence)`'s within fp32 summation order whichever others
+        shared its group.  A segment is said without the marks that close it (text.spoken_text: a free-standing . , ? ! is a token the
+        symbol table does not hold, and `tts` raises KeyError on it as the reference does).  On the device each row is then cut to its speech bounds (librosa.effects.trim's at trim_db, frame 1024 /
+        hop 256, widened by keep_ms; trim_db=None: not cut), faded over fade_ms at both edges and joined with the pause of its
+        boundary: `pauses`, a dict in ms over the defaults paragraph 700, sentence 350, clause 250, comma 150, forced -fade_ms (an
+        overlap-added seam), end 0 -- choices, not measurements.  normalize / limiter / true_peak (as `tts` takes them, one option)
+        act on the JOINED wave as one row: one gain for the paragraph.  One copy to the host at the end.  speed, speaker_id,
+        pitch_mul, pitch_add, denoise: one value for the whole text.  return_segments: also a list of dicts, one per segment: text,
+        boundary, start, end (samples in the returned wave), src_start, src_end (samples in the segment's own wave).  Empty text: ValueError."""
+        from ttsamd.join import join_paragraph, paragraph_pieces, pause_table
+        from utils.audio import _trimmer
+        pieces, lines = paragraph_pieces(text_input, max_chars)
+        table = pause_table(pauses, fade_ms)
+        if any(per_row(v) for v in (speed, denoise, speaker_id, pitch_mul, pitch_add, normalize)):
+            raise ValueError('tts_long: speed, denoise, speaker_id, pitch_mul, pitch_add and normalize take one value for the whole text')
+        check_line_controls(1, self.model.net_config['n_speakers'], [speed], [speaker_id], [pitch_mul], [pitch_add], [denoise], normalize, true_peak)
+        limiter = check_limiter(limiter, normalize)
+        dev = self.device
+        if dev.type != 'cuda':
+            raise TtsAmdError(f'FastPitch2Wave is on {dev}: the MI355X path has no CPU fallback; move the module with .to("cuda")')
+        eng, groups = self.vocoder.engine(), []
+        batch_size = max(int(batch_size), 1)
+        for k in range(0, len(lines), batch_size):
+            mel, dec_lens = self.model.ttmel_lines_alone(lines[k:k + batch_size], speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
+                                                         pitch_add=pitch_add)
+            wave, n = eng.forward(mel, dec_lens), dec_lens * eng.hop
+            if denoise > 0:
+                wave = self.denoiser.forward_batch(wave, n, denoise)
+            groups.append((wave, n))
+        wave, rows = join_paragraph(groups, pieces, table, trim_db, keep_ms, fade_ms, self.sample_rate, _trimmer(dev), normalize, limiter,
+                                    true_peak)
+        return (wave, rows) if return_segments else wave
+
     # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
     def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None, limiter=None,
                   true_peak=False):

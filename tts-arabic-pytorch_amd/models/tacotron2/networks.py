@@ -282,6 +282,48 @@ class Tacotron2Wave(nn.Module):
         # NB the reference silently ignores return_mel here (:348-351); so do we
         return [wave[i, :n[i]].cpu() for i in range(len(mel_list))]
 
+    def _tts_batch_device(self, batch, speed, denoise, speaker_id, vowelizer, postprocess_mel):
+        """tts_batch up to the denoiser, without the copies to the host: (wave [B, n_max] fp32, samples int64 [B]), both on the device,
+        rows in the order of `batch`.  What tts_long joins."""
+        mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel)
+        eng = self.vocoder.engine()
+        lens_host = [m.shape[-1] for m in mel_list]
+        lens = torch.tensor(lens_host, dtype=torch.int64, device=mel_list[0].device)
+        mel = torch.zeros(len(mel_list), mel_list[0].shape[0], max(lens_host), device=lens.device)
+        for i, m in enumerate(mel_list):
+            mel[i, :, :m.shape[-1]] = m
+        wave = eng.forward(mel, lens)
+        if denoise > 0:
+            wave = self.denoiser.forward_batch(wave, lens * eng.hop, denoise, nsamples_min=min(lens_host) * eng.hop)
+        return wave, lens * eng.hop
+
+    @torch.inference_mode()
+    def tts_long(self, text_input: Union[str, List[str]], speed: Union[int, float, None] = None, denoise: float = 0.005, speaker_id: int = 0,
+                 batch_size: int = 32, vowelizer=None, postprocess_mel: bool = True, pauses=None, max_chars: int = 200, trim_db=40.0,
+                 keep_ms: float = 10.0, fade_ms: float = 5.0, normalize=None, limiter=False, true_peak=False, return_segments: bool = False):
+        """A paragraph -> ONE wave (CPU tensor [n_samples]), as FastPitch2Wave.tts_long: the text (a string, or a list of strings taken as
+        paragraphs) is cut by text.split_text, the segments -- each said without the marks that close it, text.spoken_text -- go through
+        the batch path in groups of batch_size (the rows of a group are decoded together, as tts_batch decodes them), and on the device every row is cut to its speech bounds (trim_db, keep_ms),
+        faded over fade_ms and joined with the pause of its boundary (`pauses` in ms over paragraph 700, sentence 350, clause 250,
+        comma 150, forced -fade_ms, end 0).  speed: tts's own (None, or the rate resize_mel stretches every mel by).  normalize /
+        limiter / true_peak act on the JOINED wave as one row; one copy to the host.  return_segments: also one dict per segment
+        (text, boundary, start, end, src_start, src_end).  Empty text: ValueError."""
+        from ttsamd.join import join_paragraph, paragraph_pieces, pause_table
+        from utils.audio import _trimmer
+        pieces, lines = paragraph_pieces(text_input, max_chars)
+        table = pause_table(pauses, fade_ms)
+        if per_row(normalize):
+            raise ValueError('tts_long: normalize takes one option for the whole text')
+        check_normalize(normalize, 1)
+        limiter = check_limiter(limiter, normalize)
+        check_true_peak(true_peak, normalize, limiter)
+        batch_size = max(int(batch_size), 1)
+        groups = [self._tts_batch_device(lines[k:k + batch_size], speed, denoise, speaker_id, vowelizer, postprocess_mel)
+                  for k in range(0, len(lines), batch_size)]
+        wave, rows = join_paragraph(groups, pieces, table, trim_db, keep_ms, fade_ms, self.sample_rate, _trimmer(groups[0][0].device), normalize,
+                                    limiter, true_peak)
+        return (wave, rows) if return_segments else wave
+
     def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak):
         """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
         from ttsamd.stream import StreamingVocoder

@@ -4,6 +4,7 @@ phoneme string -> model tokens -> ids.  Function names follow the reference
 """
 from text.symbols import symbols, DOUBLING_TOKEN, EOS_TOKEN, SEPARATOR_TOKEN
 from text.phonetise import arabic_to_buckwalter, buckwalter_to_arabic, process_utterance
+from text.segment import split_text, spoken_text        # noqa: F401  (not in the reference: paragraph -> sentences for tts_long)
 
 # phonetiser vowel variants (stress / emphasis / length marks) -> the six vowels the models know.
 # Order matters for simplify_phonemes(): long vowels are replaced before their short prefixes.

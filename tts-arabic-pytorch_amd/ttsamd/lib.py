@@ -155,6 +155,9 @@ SYMBOLS = {
     'ttsamd_trim_bounds': (_I32, [_P, _I64, _P, _I32, _F, _I32, _I32, _F, _P, _P, _P, _I64, _P]),
     'ttsamd_trim_apply': (_I32, [_P, _I64, _P, _P, _F, _I64, _I32, _P, _I64, _P, _P]),
     'ttsamd_frames_compact': (_I32, [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    # paragraph join (csrc/join.hip): wave, wave_stride, nsamples, bounds (or NULL), gap, B, fade, F, keep, lead, out, out_stride, segs
+    # (int64 [B][4]), total (int64 [1]), stream
+    'ttsamd_wave_join': (_I32, [_P, _I64, _P, _P, _P, _I32, _P, _I32, _I64, _I64, _P, _I64, _P, _P, _P]),
     # output levelling (csrc/loudness.hip): the coefficients go to a HOST float64 [10] and need no GPU
     'ttsamd_loudness_coefficients': (_I32, [_I32, C.POINTER(C.c_double)]),
     'ttsamd_loudness_workspace_bytes': (_I64, [_I32, _I64, _I32]),

@@ -10,7 +10,9 @@ Input side: `resample` / `Resample` (torchaudio.functional.resample's name and d
 `prepare_recording` = the clean-up of the reference's scripts/preprocess_audio.py:33-47 (resample with lowpass_filter_width=1024,
 peak 0.999, trim at 23 dB, 768 zeros appended), on the device (csrc/resample.hip, csrc/trim.hip).
 Level: `loudness` (ITU-R BS.1770-4 integrated loudness per row), `normalize_loudness` and `peak_normalize`, on the device and per row
-of a ragged batch (csrc/loudness.hip); `peak_normalise` is the host helper for one wave."""
+of a ragged batch (csrc/loudness.hip); `peak_normalise` is the host helper for one wave.
+Joining: `join_waves`, several waves -> one with trimmed seams, faded edges and exact pauses, on the device (csrc/join.hip): what
+`tts_long` of the models runs behind the vocoder."""
 import struct
 
 import numpy as np
@@ -613,6 +615,44 @@ def trim(y, top_db=60, frame_length=2048, hop_length=512, lens=None):
         return y[start:end], (start, end)
     bounds, _ = eng.bounds(y, lens, top_db, frame_length, hop_length)
     return bounds
+
+
+@torch.inference_mode()
+def join_waves(waves, lens=None, pause_ms=350.0, trim_db=40.0, keep_ms=10.0, fade_ms=5.0, sample_rate=22050):
+    """Several waves -> one, on the device (csrc/join.hip; include/ttsamd.h states the arithmetic): every wave is cut to its speech
+    bounds (librosa.effects.trim's at trim_db with frame 1024 / hop 256, widened by keep_ms on each side; trim_db=None: the waves whole),
+    faded in and out over fade_ms by a raised cosine, and followed by its pause.  waves: a list of 1-D tensors / arrays (host or
+    device, any lengths) or a tensor [B, n] with lens int64 [B].  pause_ms: one value = the pause BETWEEN two waves (none behind the
+    last), or one value per wave (the last: trailing silence); a negative pause asks for that much overlap with the next wave, which
+    is overlap-added over at most the fade's length and half of either wave.  -> (wave [N] float32 on the device, segs int64 [B, 4] on
+    the host = (out_start, out_end, src_start, src_end) per wave).  One read-back: the total length and the segment table."""
+    from ttsamd.join import fade_table, join_rows, ms_to_samples
+    if isinstance(waves, (list, tuple)):
+        if lens is not None:
+            raise ValueError('join_waves: lens goes with a [B, n] tensor; a list of waves carries its own lengths')
+        if not waves:
+            raise ValueError('join_waves: no waves')
+        rows = [(w if isinstance(w, torch.Tensor) else torch.as_tensor(np.asarray(w))).reshape(-1) for w in waves]
+        dev = next((r.device for r in rows if r.device.type == 'cuda'), torch.device('cuda:0'))
+        n = [int(r.numel()) for r in rows]
+        x = torch.zeros(len(rows), max(max(n), 1), dtype=torch.float32, device=dev)
+        for b, r in enumerate(rows):
+            x[b, :n[b]] = r.to(device=dev, dtype=torch.float32)
+        lens = torch.tensor(n, dtype=torch.int64).to(dev)
+    else:
+        x = _device_wave(waves, 'join_waves')
+        if x.dim() != 2:
+            raise ValueError(f'join_waves: a list of waves or a tensor [B, n] (+ lens), got shape {tuple(x.shape)}')
+        x = x.to(torch.float32).contiguous()
+    B = x.shape[0]
+    pauses = row_values(pause_ms, B, 'pause_ms') if per_row(pause_ms) else [pause_ms] * (B - 1) + [0.0]
+    check_finite(pauses, 'pause_ms')
+    gaps = [ms_to_samples(p, sample_rate) for p in pauses]
+    bounds = None
+    if trim_db is not None:
+        bounds, _ = _trimmer(x.device).bounds(x, lens, float(trim_db), 1024, 256, gain=0.0)
+    out, segs = join_rows(x, lens, gaps, bounds, keep=ms_to_samples(keep_ms, sample_rate), fade=fade_table(ms_to_samples(fade_ms, sample_rate)))
+    return out[0], segs
 
 
 @torch.inference_mode()
