@@ -612,6 +612,32 @@ int32_t ttsamd_wave_join(const float* wave, int64_t wave_stride, const int64_t* 
                          int32_t batch, const float* fade, int32_t n_fade, int64_t keep, int64_t lead, float* out, int64_t out_stride,
                          int64_t* segs, int64_t* total, void* stream);
 
+/* ---- Token and word spans (csrc/timing.hip): per-token repeat counts -> where every token and every group of tokens (a word) lies in
+ * the audio that is delivered.  A new symbol only, added WITHOUT a bump: TTSAMD_ABI_VERSION stays 8.
+ * All pointers are DEVICE pointers: reps int64 [batch][reps_stride] (FastPitch's reps, MAS durations as integers; reps_stride >=
+ * max_tokens); n_tokens int64 [batch] or NULL = max_tokens in every row, clamped to [0, max_tokens]; groups int32 [batch][max_groups][2]:
+ * half-open token ranges (t0, t1), or NULL = no groups; n_groups int32 [batch] or NULL = max_groups in every row, clamped to
+ * [0, max_groups]; hop: samples per repeat; map int64 [batch][5] = (lo, hi, off, num, den) per row, or NULL = (0, INT64_MAX, 0, 1, 1).
+ * Specified by its arithmetic, in exact int64, matched bit for bit (n = the row's token count):
+ *   1. c[0] = 0, c[i + 1] = c[i] + max(reps[i], 0) for i < n.
+ *   2. m(p) = off + ceil((min(max(p hop, lo), hi) - lo) num / den): the position p hop of the row's own audio, cut to the part [lo, hi]
+ *      that is kept, counted at num / den of the rate and moved to off.  The ceiling is the first delivered sample at or after the
+ *      instant, the rule of the stream's chunk borders.  (p hop saturates at INT64_MAX; the result is exact where it fits int64.)
+ *   3. tok[i] = (m(c[i]), m(c[i + 1])) for i < n, (m(c[n]), m(c[n])) for n <= i < max_tokens.
+ *   4. grp[g] = (m(c[t0']), m(c[t1'])), t0' = clamp(t0, 0, n), t1' = max(clamp(t1, 0, n), t0') for g < n_groups[b]: an empty range is an
+ *      empty span at its place; (m(c[n]), m(c[n])) for n_groups[b] <= g < max_groups.
+ *   5. a row whose map has num or den outside [1, 2^20] or hi < lo gets -1 in all of its tok and grp entries; the other rows do not
+ *      depend on it, and nothing faults.
+ * tok int64 [batch][max_tokens][2]; grp int64 [batch][max_groups][2] (with groups, else NULL), both 16-byte aligned.  One launch, one
+ * block per row (a wave64 shuffle scan per 64 tokens, carries through LDS and a register; c stays in LDS for the group pass), plain
+ * vector stores, no atomics, no host read-back; two runs give the same bits.
+ * TTSAMD_EINVAL (nothing launched, nothing written): batch < 1, max_tokens outside 1 .. 8192, reps_stride < max_tokens, max_groups < 0,
+ * hop < 1 (or 2^31 and more), a NULL reps / tok, groups without grp or grp without groups, a tok / grp that is not 16-byte aligned. */
+#define TTSAMD_SPANS_MAX_TOKENS 8192
+int32_t ttsamd_token_spans(const int64_t* reps, int64_t reps_stride, const int64_t* n_tokens, int32_t batch, int32_t max_tokens,
+                           const int32_t* groups, const int32_t* n_groups, int32_t max_groups, int64_t hop, const int64_t* map,
+                           int64_t* tok, int64_t* grp, void* stream);
+
 /* ---- Tacotron2MS.infer: replaces models/tacotron2/tacotron2_ms.py:279-332 (encoder, speaker
  *      concat, autoregressive _Decoder.infer, postnet).  Weight names are the keys of
  *      Tacotron2MS.state_dict() (embedding.weight, speaker_embedding.weight, encoder.*, decoder.*,

@@ -718,6 +718,12 @@ int32_t ttsamd_wave_join(const float* wave, int64_t wave_stride, const int64_t* 
     return wave_join(wave, wave_stride, nsamples, bounds, gap, batch, fade, n_fade, keep, lead, out, out_stride, segs, total,
                      (hipStream_t)stream);
 }
+int32_t ttsamd_token_spans(const int64_t* reps, int64_t reps_stride, const int64_t* n_tokens, int32_t batch, int32_t max_tokens,
+                           const int32_t* groups, const int32_t* n_groups, int32_t max_groups, int64_t hop, const int64_t* map,
+                           int64_t* tok, int64_t* grp, void* stream) {
+    return token_spans(reps, reps_stride, n_tokens, batch, max_tokens, groups, n_groups, max_groups, hop, map, tok, grp,
+                       (hipStream_t)stream);
+}
 int32_t ttsamd_average_pitch(const float* pitch, const float* dur, int32_t batch, int32_t n_formants, int32_t n_frames, int32_t n_tokens,
                              float* out, void* stream) {
     return average_pitch(pitch, dur, batch, n_formants, n_frames, n_tokens, out, (hipStream_t)stream);

@@ -97,6 +97,9 @@ int32_t frames_compact(const float* mel, const float* extra, const int64_t* lens
 int32_t wave_join(const float* wave, int64_t wave_stride, const int64_t* nsamples, const int64_t* bounds, const int64_t* gap, int32_t B,
                   const float* fade, int32_t F, int64_t keep, int64_t lead, float* out, int64_t out_stride, int64_t* segs, int64_t* total,
                   hipStream_t s);
+// Token and word spans (timing.hip): repeat counts -> positions in the delivered audio, one block per row
+int32_t token_spans(const int64_t* reps, int64_t reps_stride, const int64_t* n_tokens, int32_t B, int32_t L, const int32_t* groups,
+                    const int32_t* n_groups, int32_t G, int64_t hop, const int64_t* map, int64_t* tok, int64_t* grp, hipStream_t s);
 
 // Profiling of conv launches (bench roofline)
 void prof_begin(hipStream_t s, double flops);

@@ -44,13 +44,22 @@ def infer(args):
         for k in range(0, len(lines), args.batch_size):
             batch = lines[k:k + args.batch_size]
             level = dict(normalize=args.normalize, **({'limiter': True} if args.limiter else {}), **({'true_peak': True} if args.true_peak else {}))
+            stamps = {'return_timestamps': True} if args.timestamps else {}
             if args.long:                           # every line is a paragraph: split, synthesised and joined on the device (tts_long)
-                wavs = [model.tts_long(line, denoise=args.denoise, speed=args.speed, **level) for line in batch]
+                wavs = [model.tts_long(line, denoise=args.denoise, speed=args.speed, **level, **stamps) for line in batch]
+                wavs, timings = (zip(*wavs) if stamps else (wavs, [None] * len(batch)))
             else:
-                wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, **level)
-            for line, wav in zip(batch, wavs):
+                wavs = model.tts(batch, batch_size=args.batch_size, denoise=args.denoise, speed=args.speed, **level, **stamps)
+                wavs, timings = wavs if stamps else (wavs, [None] * len(batch))
+            for line, wav, timing in zip(batch, wavs, timings):
                 if rate != 22_050:                      # the finished wave through the device resampler, then the matching file format
                     wav = resample(wav.reshape(1, -1).to('cuda'), 22_050, rate)[0]
+                if timing is not None:                  # static<i>.json | srt | vtt next to the wave, the marks at the rate of the file
+                    from ttsamd.timing import delivered_timing
+                    from utils import timing as T
+                    write = {'json': T.to_json, 'srt': T.to_srt, 'vtt': T.to_vtt}[args.timestamps]
+                    with open(os.path.join(args.out_dir, 'wavs', f'static{idx}.{args.timestamps}'), 'w', encoding='utf-8') as f:
+                        f.write(write(delivered_timing(timing, rate)))
                 save_wav(os.path.join(args.out_dir, 'wavs', f'static{idx}.wav'), wav, rate, encoding=enc, bits_per_sample=bits)
                 index.write(f'wavs/static{idx}.wav\t{wav.numel()}\t{line}\n')
                 idx += 1
@@ -80,6 +89,8 @@ def main(argv=None):
     p.add_argument('--true_peak', action='store_true')
     # ... every line of --list as a paragraph: cut into sentences, synthesised in batches and joined on the device with pauses (tts_long)
     p.add_argument('--long', action='store_true')
+    # ... where every word lies in the wave: static<i>.json (words and tokens, in samples and seconds), .srt or .vtt cues next to static<i>.wav
+    p.add_argument('--timestamps', type=str, default=None, choices=['json', 'srt', 'vtt'])
     args = p.parse_args(argv)
     if args.limiter and args.normalize in (None, 'peak'):
         p.error("--limiter needs --normalize lufs or a target in LUFS")

@@ -194,6 +194,31 @@ class FastPitch(_HipModule):
         return Alignment(dur, pitch_tgt, energy_tgt, soft, hard, logprob)
 
     @torch.inference_mode()
+    def timestamps(self, ids_or_text, mel, mel_lens=None, attn_prior=None):
+        """Word and token timings of a RECORDING from the checkpoint's own aligner: align()'s durations (whole frames per token) through
+        the kernel the synthesis timestamps use (ttsamd.timing), at 256 samples a frame.  ids_or_text and mel as align() takes them ->
+        one timing dict per row (one dict for a single string): positions in samples of the recording the mel was made of.  Given ids
+        instead of text, a word is named by its tokens."""
+        single = isinstance(ids_or_text, str)
+        if single:
+            ids_or_text = [ids_or_text]
+        if isinstance(ids_or_text, (list, tuple)) and len(ids_or_text) and isinstance(ids_or_text[0], str):
+            toks = [self._tokenize_words(line) for line in ids_or_text]
+            token_rows, word_rows = [t for t, _ in toks], [w for _, w in toks]
+            rows = [text.tokens_to_ids(t, self.phon_to_id) for t in token_rows]
+            ids = torch.full((len(rows), max(len(r) for r in rows)), self.net_config['padding_idx'], dtype=torch.int64)
+            for b, r in enumerate(rows):
+                ids[b, :len(r)] = torch.as_tensor(r, dtype=torch.int64)
+        else:
+            ids = torch.as_tensor(ids_or_text).long().cpu()
+            names = {i: p for p, i in self.phon_to_id.items()} if self.phon_to_id else dict(enumerate(text.symbols))
+            token_rows = [[names[int(i)] for i in row[:n]] for row, n in zip(ids.tolist(), self._ends_padded(ids).tolist())]
+            word_rows = [[' '.join(t[t0:t1]) for t0, t1 in text.word_ranges(t)] for t in token_rows]
+        dur = self.align(ids, mel, mel_lens, attn_prior=attn_prior).dur_tgt
+        res = self._pending_timings(token_rows, word_rows, dur.round().to(torch.int64)).resolve()
+        return res[0] if single else res
+
+    @torch.inference_mode()
     def alignment_score(self, ids_or_text, mel, mel_lens=None, attn_prior='interpolated'):
         """How far a forced alignment can be trusted: align() as above (the prior defaults to the one the checkpoint was trained with), then
         the reference's two alignment losses, forward only (csrc/attn_loss.hip).  -> AlignmentScore(forward_sum [B] float64: the
@@ -238,8 +263,9 @@ class FastPitch(_HipModule):
     # ---- FastPitch.infer (models/fastpitch/fastpitch/model.py:351-353) -------------------
     @torch.inference_mode()
     def infer(self, inputs, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_transform=None,
-              max_duration=75, speaker=0, alone=False, pitch_mul=None, pitch_add=None):
-        """`alone=True` (not in the reference): every row of the batch as if it were the only utterance of the call, i.e. row b ==
+              max_duration=75, speaker=0, alone=False, pitch_mul=None, pitch_add=None, return_reps=False):
+        """`return_reps` (not in the reference): the tuple ends with reps int64 [B, L] on the device, the frames every token got.
+        `alone=True` (not in the reference): every row of the batch as if it were the only utterance of the call, i.e. row b ==
         infer(inputs[b:b+1, :len_b]) within fp32 summation order (FastPitchEngine.infer) -- the batch_size = 1 loop as one ragged call.
         Mixed requests (not in the reference): `pace` and `speaker` take a scalar or one value per row; `pitch_mul` / `pitch_add` (scalars
         or per row) are pitch_trf's two numbers given directly -- together with a `pitch_transform` they are refused, since a callable
@@ -265,10 +291,12 @@ class FastPitch(_HipModule):
                 mean, std = (218.14, 67.24) if self.pitch_std == 0.0 else (self.pitch_mean, self.pitch_std)
                 pp = pitch_transform(pp, lens.to(pp.device), mean, std)
                 out = eng.infer(ids, pace=pace, dur_tgt=dur_tgt, pitch_tgt=pp if pitch_tgt is None else pitch_tgt,
-                                energy_tgt=energy_tgt, max_duration=max_duration, speaker=speaker, alone=alone)
-                return out[0], out[1], out[2], pp, out[4]
+                                energy_tgt=energy_tgt, max_duration=max_duration, speaker=speaker, alone=alone,
+                                **({'return_reps': True} if return_reps else {}))
+                return (out[0], out[1], out[2], pp, out[4]) + tuple(out[5:])
         return eng.infer(ids, pace=pace, dur_tgt=dur_tgt, pitch_tgt=pitch_tgt, energy_tgt=energy_tgt,
-                         pitch_mul=mul, pitch_add=add, max_duration=max_duration, speaker=speaker, alone=alone)
+                         pitch_mul=mul, pitch_add=add, max_duration=max_duration, speaker=speaker, alone=alone,
+                         **({'return_reps': True} if return_reps else {}))
 
     def _ends_padded(self, ids):
         """token counts per row; ValueError unless every row is zero-padded at its end"""
@@ -291,11 +319,24 @@ class FastPitch(_HipModule):
             tagger.to(self.device)
         return tagger.predict(text.buckwalter_to_arabic(utterance))
 
+    def _tokenize_words(self, utterance: str, vowelizer=None):
+        """(the line's tokens, its words as text.line_words groups them -- of the line the tokeniser saw, behind the vowelizer)"""
+        utterance = self._vowelize(utterance, vowelizer)
+        return text.tokens_and_words(utterance, self.arabic_in, append_space=False)          # one pass of the phonetiser for both
+
     def _tokenize(self, utterance: str, vowelizer=None):
         utterance = self._vowelize(utterance, vowelizer)
         if self.arabic_in:
             return text.arabic_to_tokens(utterance, append_space=False)
         return text.buckwalter_to_tokens(utterance, append_space=False)
+
+    sample_rate, hop = 22050, 256           # of the mel: one frame is `hop` samples of the vocoder's wave
+
+    def _pending_timings(self, token_rows, word_rows, reps, launch=True):
+        """the spans of the rows of one infer call, launched behind it (ttsamd.timing.PendingTimings: resolve() is the one copy);
+        launch=False: held back until the rows' maps are known (tts_long: the join table)"""
+        from ttsamd.timing import PendingTimings
+        return PendingTimings(token_rows, word_rows, reps, self.hop, self.sample_rate, launch=launch)
 
     @staticmethod
     def _ptrf(pitch_mul, pitch_add, pitch_transform):
@@ -316,47 +357,62 @@ class FastPitch(_HipModule):
     @torch.inference_mode()
     def ttmel_single(self, utterance: str, speed: float = 1, speaker_id: int = 0, vowelizer=None,
                      pitch_mul: float = 1., pitch_add: float = 0., dur_tgt=None, pitch_tgt=None,
-                     energy_tgt=None, pitch_transform=None, max_duration=75):
-        tokens = self._tokenize(utterance, vowelizer=vowelizer)
+                     energy_tgt=None, pitch_transform=None, max_duration=75, return_timestamps=False):
+        """return_timestamps (not in the reference): -> (mel, PendingTimings of the one row)"""
+        if return_timestamps:
+            tokens, words = self._tokenize_words(utterance, vowelizer=vowelizer)
+        else:
+            tokens = self._tokenize(utterance, vowelizer=vowelizer)
         ids = torch.LongTensor(text.tokens_to_ids(tokens, self.phon_to_id)).unsqueeze(0)
-        mel, *_ = self.infer(ids, pace=speed, speaker=speaker_id, dur_tgt=dur_tgt, pitch_tgt=pitch_tgt,
-                             energy_tgt=energy_tgt, pitch_transform=self._ptrf(pitch_mul, pitch_add, pitch_transform),
-                             max_duration=max_duration)
+        mel, *rest = self.infer(ids, pace=speed, speaker=speaker_id, dur_tgt=dur_tgt, pitch_tgt=pitch_tgt,
+                                energy_tgt=energy_tgt, pitch_transform=self._ptrf(pitch_mul, pitch_add, pitch_transform),
+                                max_duration=max_duration, **({'return_reps': True} if return_timestamps else {}))
+        if return_timestamps:
+            return mel[0], self._pending_timings([tokens], [words], rest[-1])
         return mel[0]                                                   # [80, T]
 
     @torch.inference_mode()
     def _ttmel_batch_padded(self, batch, speed, speaker_id, vowelizer, pitch_mul, pitch_add, dur_tgt=None,
-                            pitch_tgt=None, energy_tgt=None, pitch_transform=None, max_duration=75, alone=None):
+                            pitch_tgt=None, energy_tgt=None, pitch_transform=None, max_duration=75, alone=None,
+                            return_timestamps=False):
         """alone None: rows as if alone exactly when a control is given per line -- mixed requests are independent requests, and one's
         mel must not depend on which others shared its batch (it equals ttmel_single with its options within fp32 summation order); all
-        scalars: the reference's padded-batch arithmetic, as before."""
-        batch_ids = [torch.LongTensor(text.tokens_to_ids(self._tokenize(line, vowelizer), self.phon_to_id))
-                     for line in batch]
+        scalars: the reference's padded-batch arithmetic, as before.  return_timestamps: a fourth result, the PendingTimings of the rows
+        in the order of the padded batch (row i is line sort_ids[i])."""
+        toks = [self._tokenize_words(line, vowelizer) if return_timestamps else (self._tokenize(line, vowelizer), None) for line in batch]
+        batch_ids = [torch.LongTensor(text.tokens_to_ids(t, self.phon_to_id)) for t, _ in toks]
         check_line_controls(len(batch), self.net_config['n_speakers'], speed, speaker_id, pitch_mul, pitch_add)
         ids_pad, lens_sorted, reverse_ids = text_collate_fn(batch_ids)
         # row i of the padded batch is line sort_ids[i]: per-line controls go through the same sort (a scalar stays a scalar)
         sort_ids = reverse_ids.argsort().tolist()
         if alone is None:
             alone = any(per_row(v) for v in (speed, speaker_id, pitch_mul, pitch_add))
-        mel, dec_lens, *_ = self.infer(ids_pad, alone=alone, pace=_take(speed, sort_ids), speaker=_take(speaker_id, sort_ids), dur_tgt=dur_tgt,
-                                       pitch_tgt=pitch_tgt, energy_tgt=energy_tgt, max_duration=max_duration,
-                                       **self._pitch_kw(_take(pitch_mul, sort_ids), _take(pitch_add, sort_ids), pitch_transform))
+        mel, dec_lens, *rest = self.infer(ids_pad, alone=alone, pace=_take(speed, sort_ids), speaker=_take(speaker_id, sort_ids), dur_tgt=dur_tgt,
+                                          pitch_tgt=pitch_tgt, energy_tgt=energy_tgt, max_duration=max_duration,
+                                          **self._pitch_kw(_take(pitch_mul, sort_ids), _take(pitch_add, sort_ids), pitch_transform),
+                                          **({'return_reps': True} if return_timestamps else {}))
+        if return_timestamps:
+            return mel, dec_lens, reverse_ids, self._pending_timings([toks[j][0] for j in sort_ids], [toks[j][1] for j in sort_ids], rest[-1])
         return mel, dec_lens, reverse_ids
 
     @torch.inference_mode()
     def ttmel_lines_alone(self, lines: List[str], speed: float = 1, speaker_id: int = 0, vowelizer=None,
-                          pitch_mul: float = 1., pitch_add: float = 0., max_duration=75):
+                          pitch_mul: float = 1., pitch_add: float = 0., max_duration=75, return_timestamps=False, _launch_spans=True):
         """`[ttmel_single(l) for l in lines]` as ONE ragged FastPitch call (infer(..., alone=True)): (mel [B, 80, T_max], dec_lens int64
         [B]) in HBM, rows in the order of `lines`; mel[b, :, :dec_lens[b]] equals ttmel_single(lines[b]) within fp32 summation order
         (frames past dec_lens[b] are undefined).  What `FastPitch2Wave.tts(list, batch_size=1)` runs per group of lines.  speed,
-        speaker_id, pitch_mul and pitch_add: scalars or one value per line (the rows keep the order of `lines`)."""
+        speaker_id, pitch_mul and pitch_add: scalars or one value per line (the rows keep the order of `lines`).  return_timestamps: a
+        third result, the PendingTimings of the rows (_launch_spans=False: not launched yet, for tts_long, whose maps come with the join)."""
         check_line_controls(len(lines), self.net_config['n_speakers'], speed, speaker_id, pitch_mul, pitch_add)
-        batch_ids = [text.tokens_to_ids(self._tokenize(line, vowelizer), self.phon_to_id) for line in lines]
+        toks = [self._tokenize_words(line, vowelizer) if return_timestamps else (self._tokenize(line, vowelizer), None) for line in lines]
+        batch_ids = [text.tokens_to_ids(t, self.phon_to_id) for t, _ in toks]
         ids = torch.zeros(len(batch_ids), max(len(i) for i in batch_ids), dtype=torch.int64)
         for b, i in enumerate(batch_ids):
             ids[b, :len(i)] = torch.as_tensor(i, dtype=torch.int64)
-        mel, dec_lens, *_ = self.infer(ids, pace=speed, speaker=speaker_id, max_duration=max_duration, alone=True,
-                                       **self._pitch_kw(pitch_mul, pitch_add, None))
+        mel, dec_lens, *rest = self.infer(ids, pace=speed, speaker=speaker_id, max_duration=max_duration, alone=True,
+                                          **self._pitch_kw(pitch_mul, pitch_add, None), **({'return_reps': True} if return_timestamps else {}))
+        if return_timestamps:
+            return mel, dec_lens, self._pending_timings([t for t, _ in toks], [w for _, w in toks], rest[-1], launch=_launch_spans)
         return mel, dec_lens
 
     @torch.inference_mode()
@@ -423,31 +479,36 @@ class FastPitch2Wave(nn.Module):
     @torch.inference_mode()
     def tts_single(self, text_buckw: str, speed: float = 1, speaker_id: int = 0, denoise: float = 0,
                    vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None,
-                   limiter=False, true_peak=False):
+                   limiter=False, true_peak=False, return_timestamps=False):
+        """return_timestamps (not in the reference): the result ends with the line's timing (ttsamd.timing: words and tokens in samples of
+        the returned wave) -- (wave, timing), or (wave, mel, timing) with return_mel."""
         check_normalize(normalize, 1)
         limiter = check_limiter(limiter, normalize)
         check_true_peak(true_peak, normalize, limiter)
         mel_spec = self.model.ttmel_single(text_buckw, speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
-                                           pitch_add=pitch_add)
+                                           pitch_add=pitch_add, **({'return_timestamps': True} if return_timestamps else {}))
+        if return_timestamps:
+            mel_spec, spans = mel_spec
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
         if normalize is not None:
             wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize, true_peak))
-        if return_mel:
-            return wave[0].cpu(), mel_spec
-        return wave[0].cpu()
+        out = (wave[0].cpu(), mel_spec) if return_mel else (wave[0].cpu(),)
+        if return_timestamps:
+            out += (spans.resolve()[0],)              # the one small copy, behind the wave's own
+        return out[0] if len(out) == 1 else out
 
     def _tts_batch_sorted(self, batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize=None, limiter=False,
-                          true_peak=False):
+                          true_peak=False, return_timestamps=False):
         """What tts_batch and tts_batch_device share: (wave [B, n_max], n_samples int64 [B], reverse_ids), rows in the collate order (longest
-        first).  Every control is a scalar or one value per line of `batch`; a per-line denoise strength goes through the same sort as
+        first; with return_timestamps a fourth result, the PendingTimings of those rows).  Every control is a scalar or one value per line of `batch`; a per-line denoise strength goes through the same sort as
         the lines, and a line whose strength is not > 0 keeps its vocoder output bit for bit.  `normalize` takes the same sort; the
         rows are levelled on the device after the denoiser (ttsamd.engine.level_waves)."""
         check_line_controls(len(batch), self.model.net_config['n_speakers'], denoise=denoise, normalize=normalize, true_peak=true_peak)
         limiter = check_limiter(limiter, normalize)
-        mel, dec_lens, reverse_ids = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul,
-                                                                    pitch_add)
+        mel, dec_lens, reverse_ids, *spans = self.model._ttmel_batch_padded(batch, speed, speaker_id, vowelizer, pitch_mul, pitch_add,
+                                                                            **({'return_timestamps': True} if return_timestamps else {}))
         wave = self.vocoder.engine().forward(mel, dec_lens)             # one ragged batched launch sequence
         n = (dec_lens * self.vocoder.engine().hop)
         denoise = _take(denoise, reverse_ids.argsort().tolist())
@@ -456,7 +517,7 @@ class FastPitch2Wave(nn.Module):
         if normalize is not None:
             wave = level_waves(wave, n, _take(normalize, reverse_ids.argsort().tolist()), self.sample_rate,
                                **_lim(limiter, normalize, true_peak))
-        return wave, n, reverse_ids
+        return (wave, n, reverse_ids, *spans)
 
     @torch.inference_mode()
     def tts_batch_device(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0,
@@ -472,17 +533,24 @@ class FastPitch2Wave(nn.Module):
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: float = 1, speaker_id: int = 0, denoise: float = 0, vowelizer=None,
-                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None, limiter=False, true_peak=False):
-        wave, n, reverse_ids = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize, limiter,
-                                                      true_peak)
+                  pitch_mul: float = 1., pitch_add: float = 0., return_mel: bool = False, normalize=None, limiter=False, true_peak=False,
+                  return_timestamps=False):
+        """return_timestamps (not in the reference): -> (waves, timings), timing i of line i (one more small copy for the batch)"""
+        wave, n, reverse_ids, *spans = self._tts_batch_sorted(batch, speed, speaker_id, denoise, vowelizer, pitch_mul, pitch_add, normalize,
+                                                              limiter, true_peak, **({'return_timestamps': True} if return_timestamps else {}))
         n = n.tolist()
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:347-350); so do we
-        return [wave[j, :n[j]].cpu() for j in reverse_ids.tolist()]
+        waves = [wave[j, :n[j]].cpu() for j in reverse_ids.tolist()]
+        if return_timestamps:
+            rows = spans[0].resolve()
+            return waves, [rows[j] for j in reverse_ids.tolist()]
+        return waves
 
     def tts(self, text_input: Union[str, List[str]], speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
             batch_size: int = 2, vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0.,
-            return_mel: bool = False, normalize=None, limiter=False, true_peak=False) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None, limiter=False, true_peak=False,
+            return_timestamps: bool = False) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:352-435): str -> Tensor[n_samples] (CPU);
         list -> list of tensors, chunked by `batch_size`.
         Mixed requests (not in the reference): for a list of lines, speed, denoise, speaker_id, pitch_mul and pitch_add each take a scalar
@@ -501,35 +569,49 @@ class FastPitch2Wave(nn.Module):
         (utils.audio.limit; include/ttsamd.h states the arithmetic), so the target is reached where the cap would have stopped short of
         it; 'peak' and None lines keep their path.  One setting for the call, not per line.
         true_peak (False or True; needs a normalize): every peak above is the true peak (utils.audio.true_peak: 4x oversampled), so
-        0.99 and the limiter's ceiling are true-peak ceilings; one setting for the call.  With no line to level it is a ValueError."""
+        0.99 and the limiter's ceiling are true-peak ceilings; one setting for the call.  With no line to level it is a ValueError.
+        return_timestamps (not in the reference): where every word and token lies in the wave -- (wave, timing) for a string, (waves,
+        timings) for a list, timing i of line i whatever the chunking and sorting did (ttsamd.timing: a dict of sample_rate, words =
+        dicts of word, start, end in samples of the returned wave, t0, t1 in seconds, tokens = the word's token range, and tokens =
+        dicts of token, start, end; the last token ends where the wave does).  The spans are made on the device from the frames every
+        token got (csrc/timing.hip) and cost one small copy per FastPitch call; the denoiser and the level move no sample, so no mark.
+        For a string with return_mel: (wave, mel, timing)."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, pitch_mul=pitch_mul, pitch_add=pitch_add)
         if normalize is not None and not (per_row(normalize) and all(v is None for v in normalize)):
             kw['normalize'] = normalize         # (None, or only None: the calls below get exactly the arguments they got before)
+        ts = {'return_timestamps': True} if return_timestamps else {}
         if isinstance(text_input, str):
             return self.tts_single(text_input, vowelizer=vowelizer, return_mel=return_mel, **kw, **({'limiter': limiter} if limiter else {}),
-                                   **({'true_peak': true_peak} if true_peak else {}))
+                                   **({'true_peak': true_peak} if true_peak else {}), **ts)
         assert isinstance(text_input, list)
         check_line_controls(len(text_input), self.model.net_config['n_speakers'], **dict(kw, normalize=normalize, true_peak=true_peak))
         limiter = check_limiter(limiter, normalize)
         if (len(text_input) > batch_size and not return_mel and self.device.type == 'cuda'
                 and os.environ.get('TTSAMD_TTS_PIPELINE', '1') != '0'):
             return self._tts_list_pipelined(text_input, batch_size, vowelizer=vowelizer, return_mel=return_mel, **kw,
-                                            **_lim(limiter, normalize, true_peak))
+                                            **_lim(limiter, normalize, true_peak), **ts)
         if batch_size == 1:
-            return [self.tts_single(sample, vowelizer=vowelizer, return_mel=return_mel, **{k: _at(v, i) for k, v in kw.items()},
-                                    **_lim(limiter, _at(normalize, i), true_peak))
-                    for i, sample in enumerate(text_input)]
-        wav_list = []
+            res = [self.tts_single(sample, vowelizer=vowelizer, return_mel=return_mel, **{k: _at(v, i) for k, v in kw.items()},
+                                   **_lim(limiter, _at(normalize, i), true_peak), **ts)
+                   for i, sample in enumerate(text_input)]
+            if return_timestamps:                   # (wave, [mel,] timing) per line -> (the list as without the flag, the timings)
+                return [r[0] if len(r) == 2 else r[:-1] for r in res], [r[-1] for r in res]
+            return res
+        wav_list, timings = [], []
         for k in range(0, len(text_input), batch_size):
             idx = range(k, min(k + batch_size, len(text_input)))
-            wav_list += self.tts_batch(text_input[k:k + batch_size], vowelizer=vowelizer, return_mel=return_mel,
-                                       **{n: _take(v, idx) for n, v in kw.items()}, **_lim(limiter, _take(normalize, idx), true_peak))
-        return wav_list
+            got = self.tts_batch(text_input[k:k + batch_size], vowelizer=vowelizer, return_mel=return_mel,
+                                 **{n: _take(v, idx) for n, v in kw.items()}, **_lim(limiter, _take(normalize, idx), true_peak), **ts)
+            if return_timestamps:
+                got, more = got
+                timings += more
+            wav_list += got
+        return (wav_list, timings) if return_timestamps else wav_list
 
     # the options of one request of tts_requests and what a request that leaves one out gets: tts()'s own defaults
     REQUEST_DEFAULTS = dict(speed=1., denoise=0.005, speaker_id=0, pitch_mul=1., pitch_add=0.)
 
-    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None, limiter=False, true_peak=False):
+    def tts_requests(self, requests, batch_size: int = 32, vowelizer=None, limiter=False, true_peak=False, return_timestamps=False):
         """A server's queue in one go: `requests` is a list of dicts with `text` and any of speed, denoise, speaker_id, pitch_mul, pitch_add, normalize
         (the per-request options of the reference's app); returns one wave per request, in request order, from ONE `tts` call with the
         options as per-line lists -- requests with different options share batches instead of one call per distinct option tuple."""
@@ -540,8 +622,10 @@ class FastPitch2Wave(nn.Module):
                 raise ValueError(f'request {i}: needs a `text` string and takes {sorted(self.REQUEST_DEFAULTS) + ["normalize"]}'
                                  + (f' (got {sorted(extra)})' if extra else ''))
         if not requests:
-            return []
+            return ([], []) if return_timestamps else []
         lists = {k: [r.get(k, d) for r in requests] for k, d in self.REQUEST_DEFAULTS.items()}
+        if return_timestamps:                     # -> (waves, timings), as tts does for a list
+            lists['return_timestamps'] = True
         if any(r.get('normalize') is not None for r in requests):
             lists['normalize'] = [r.get('normalize') for r in requests]
         if limiter:                               # one setting for the call (a request has no limiter of its own); tts checks it
@@ -554,7 +638,8 @@ class FastPitch2Wave(nn.Module):
     @torch.inference_mode()
     def tts_long(self, text_input: Union[str, List[str]], speed: float = 1., denoise: float = 0.005, speaker_id: int = 0, batch_size: int = 32,
                  vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., pauses=None, max_chars: int = 200, trim_db=40.0,
-                 keep_ms: float = 10.0, fade_ms: float = 5.0, normalize=None, limiter=False, true_peak=False, return_segments: bool = False):
+                 keep_ms: float = 10.0, fade_ms: float = 5.0, normalize=None, limiter=False, true_peak=False, return_segments: bool = False,
+                 return_timestamps: bool = False):
         """A paragraph -> ONE wave (CPU tensor [n_samples]).  text_input: a string, or a list of strings taken as paragraphs.  The text is
         cut into segments by text.split_text (sentences; pieces longer than max_chars at clause marks, commas, and last at a space);
         the segments go through FastPitch, the vocoder and the denoiser in groups of batch_size, every row computed as if alone
@@ -566,7 +651,11 @@ class FastPitch2Wave(nn.Module):
         overlap-added seam), end 0 -- choices, not measurements.  normalize / limiter / true_peak (as `tts` takes them, one option)
         act on the JOINED wave as one row: one gain for the paragraph.  One copy to the host at the end.  speed, speaker_id,
         pitch_mul, pitch_add, denoise: one value for the whole text.  return_segments: also a list of dicts, one per segment: text,
-        boundary, start, end (samples in the returned wave), src_start, src_end (samples in the segment's own wave).  Empty text: ValueError."""
+        boundary, start, end (samples in the returned wave), src_start, src_end (samples in the segment's own wave).  Empty text: ValueError.
+        return_timestamps: the result ends with the paragraph's timing (as `tts` describes it), positions in the JOINED wave: every
+        segment's tokens are clamped to what the trim kept of it and moved to the segment's place, on the device beside the join
+        table, so a token the trim cut away is an empty span at the segment's edge; words carry segment=k, and the pauses are the
+        gaps between the segments.  -> (wave, timing), or (wave, segments, timing) with return_segments."""
         from ttsamd.join import join_paragraph, paragraph_pieces, pause_table
         from utils.audio import _trimmer
         pieces, lines = paragraph_pieces(text_input, max_chars)
@@ -578,18 +667,20 @@ class FastPitch2Wave(nn.Module):
         dev = self.device
         if dev.type != 'cuda':
             raise TtsAmdError(f'FastPitch2Wave is on {dev}: the MI355X path has no CPU fallback; move the module with .to("cuda")')
-        eng, groups = self.vocoder.engine(), []
+        eng, groups, spans = self.vocoder.engine(), [], []
         batch_size = max(int(batch_size), 1)
         for k in range(0, len(lines), batch_size):
-            mel, dec_lens = self.model.ttmel_lines_alone(lines[k:k + batch_size], speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
-                                                         pitch_add=pitch_add)
+            mel, dec_lens, *sp = self.model.ttmel_lines_alone(lines[k:k + batch_size], speed, speaker_id, vowelizer, pitch_mul=pitch_mul,
+                                                              pitch_add=pitch_add, **({'return_timestamps': True, '_launch_spans': False} if return_timestamps else {}))
+            spans += sp
             wave, n = eng.forward(mel, dec_lens), dec_lens * eng.hop
             if denoise > 0:
                 wave = self.denoiser.forward_batch(wave, n, denoise)
             groups.append((wave, n))
-        wave, rows = join_paragraph(groups, pieces, table, trim_db, keep_ms, fade_ms, self.sample_rate, _trimmer(dev), normalize, limiter,
-                                    true_peak)
-        return (wave, rows) if return_segments else wave
+        wave, rows, *timing = join_paragraph(groups, pieces, table, trim_db, keep_ms, fade_ms, self.sample_rate, _trimmer(dev), normalize, limiter,
+                                             true_peak, **({'spans': spans} if return_timestamps else {}))
+        out = ((wave, rows) if return_segments else (wave,)) + tuple(timing)
+        return out[0] if len(out) == 1 else out
 
     # ---- streaming synthesis (not in the reference; ttsamd.stream, csrc/stream.hip) ----
     def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate=None, encoding=None, limiter=None,
@@ -612,7 +703,7 @@ class FastPitch2Wave(nn.Module):
     def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
                    max_streams: int = 32, max_frames: int = 4096, speed: float = 1., denoise: float = 0.005, speaker_id: int = 0,
                    vowelizer=None, pitch_mul: float = 1., pitch_add: float = 0., sample_rate=None, encoding=None, gain_db=0.0,
-                   limiter=False, true_peak=False, meter=False):
+                   limiter=False, true_peak=False, meter=False, marks=False):
         """`tts` that hands out audio while it is being made (a generator; one at a time per model).  FastPitch is not autoregressive, so
         the whole mel exists at once; the vocoder then runs over windows of it (ttsamd.stream.StreamingVocoder), the first of
         first_chunk_frames frames, the following of chunk_frames.
@@ -637,7 +728,12 @@ class FastPitch2Wave(nn.Module):
         device, so the meter measures what is delivered; the generator then yields (chunk, reading) for a str and (i, chunk, last,
         reading) for a list.  reading: a dict of Python floats, momentary, short_term (-inf before the first 400 ms / 3 s) and
         integrated (of the line so far); on a line's last chunk also loudness_range, max_momentary and max_short_term.  Float chunks
-        only: with pcm16 or an encoding other than None / 'float32' it is a ValueError."""
+        only: with pcm16 or an encoding other than None / 'float32' it is a ValueError.
+        marks=True: every item gets one more element at its end, the list of the word marks (the word dicts of `tts(...,
+        return_timestamps=True)`, at the DELIVERED rate: a position s of the 22 050 Hz wave is ceil(n s / o) of the resampler's ratio,
+        the rule of the chunk borders) whose start lies in the delivered range of that chunk; a mark at the very end goes with the
+        last chunk.  Put together they are the line's timing at that rate.  The spans are made once, when the line's mel is opened;
+        nothing runs per chunk on the device.  Works with every encoding, the meter and the limiter."""
         if not hasattr(self.vocoder, 'h'):
             raise ValueError("tts_stream: vocoder='griffin_lim' does not stream (every iteration needs the whole utterance)")
         kw = dict(speed=speed, speaker_id=speaker_id, pitch_mul=pitch_mul, pitch_add=pitch_add)
@@ -650,14 +746,22 @@ class FastPitch2Wave(nn.Module):
         check_finite(gains, 'gain_db')
         if limiter is None and any(float(g) != 0.0 for g in gains):
             raise ValueError('tts_stream: gain_db needs limiter=True (or its settings): a gain alone could clip')
+        ts = {'return_timestamps': True} if marks else {}
+        if marks:
+            from ttsamd.timing import MarkFeeder, delivered_timing
         if isinstance(text_input, str):
-            mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw)
+            mel = self.model.ttmel_single(text_input, vowelizer=vowelizer, **kw, **ts)
             sv = self._streamer(chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak)
+            if marks:                               # the spans once, when the mel is opened; from here on the marks are host work
+                mel, sp = mel
+                feed = MarkFeeder(delivered_timing(sp.resolve()[0], sv.sample_rate, self.sample_rate))
             sv.open(mel, denoise, float(gains[0]))
             lm = self._stream_meter(sv, max_streams) if meter else None
             while sv.open_streams:
                 for sid, chunk, last in sv.step():
-                    yield (chunk.cpu(), self._meter_reading(lm, sid, chunk, last)) if meter else chunk.cpu()
+                    item = (chunk.cpu(),) + ((self._meter_reading(lm, sid, chunk, last),) if meter else ())
+                    item += (feed.take(chunk.numel(), last),) if marks else ()
+                    yield item[0] if len(item) == 1 else item
             return
         lines = list(text_input)
         check_line_controls(len(lines), self.model.net_config['n_speakers'], denoise=denoise, **kw)
@@ -673,22 +777,26 @@ class FastPitch2Wave(nn.Module):
             longest = max(longest, len(line))
         if fill:
             groups.append(fill)
-        waiting, line_of = [], {}
+        waiting, line_of, feeds = [], {}, {}
         lm = self._stream_meter(sv, max_streams) if meter else None
         while True:
             while sv.free_slots and (waiting or groups):
                 if not waiting:
                     pos = groups.pop(0)
-                    mel_b, lens_d = self.model.ttmel_lines_alone([lines[p] for p in pos], _take(speed, pos), _take(speaker_id, pos), vowelizer,
-                                                                 pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos))
+                    mel_b, lens_d, *sp = self.model.ttmel_lines_alone([lines[p] for p in pos], _take(speed, pos), _take(speaker_id, pos),
+                                                                      vowelizer, pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos),
+                                                                      **ts)
                     waiting = [(p, mel_b[b, :, :t]) for b, (p, t) in enumerate(zip(pos, lens_d.cpu().tolist()))]
+                    if marks:                       # this FastPitch call's spans in one copy, beside the lengths'
+                        feeds.update({p: MarkFeeder(delivered_timing(t, sv.sample_rate, self.sample_rate)) for p, t in zip(pos, sp[0].resolve())})
                 p, mel = waiting.pop(0)
                 line_of[sv.open(mel, _at(denoise, p), float(_at(gain_db, p)))] = p
             if not line_of:
                 return
             for sid, chunk, last in sv.step():
                 i = line_of.pop(sid) if last else line_of[sid]
-                yield (i, chunk.cpu(), last, self._meter_reading(lm, sid, chunk, last)) if meter else (i, chunk.cpu(), last)
+                item = (i, chunk.cpu(), last) + ((self._meter_reading(lm, sid, chunk, last),) if meter else ())
+                yield item + ((feeds.pop(i) if last else feeds[i]).take(chunk.numel(), last),) if marks else item
 
     def _stream_meter(self, sv, max_streams):
         """the LoudnessMeter of this model's streams at the stream's output rate (made once per rate and pool size), every slot reset"""
@@ -805,7 +913,7 @@ class FastPitch2Wave(nn.Module):
 
     @torch.inference_mode()
     def _tts_list_pipelined(self, text_input, batch_size, speed, denoise, speaker_id, vowelizer, pitch_mul, pitch_add,
-                            return_mel=False, normalize=None, limiter=False, true_peak=False):
+                            return_mel=False, normalize=None, limiter=False, true_peak=False, return_timestamps=False):
         """The list path of `tts` over several chunks, as a three-stage pipeline on three HIP streams: tokenisation + FastPitch
         of the next chunks (host work and ~150 short launches that leave most CUs idle) run under the vocoder + denoiser of the
         previous ones, whose audio is copied to the host on a third stream.  FastPitch sees exactly the chunks of the one-stream
@@ -819,7 +927,9 @@ class FastPitch2Wave(nn.Module):
         of the engine computes every row of a ragged batch as if it were alone (ttsamd_fastpitch_set_batch_mode; tests/test_gpu_alone.py) --
         so the lines are sorted by length and go through FastPitch AND the vocoder in balanced groups of up to _ALONE_GROUP similar
         lengths (little padding), waves handed back in input order: 100 launch-bound batch-1 calls of ~1.7 ms become 4 chip-filling ones
-        (C1, 100 lines: 500 -> see DESIGN.md); each wave equals its line-by-line result within fp32 summation order, lengths exactly."""
+        (C1, 100 lines: 500 -> see DESIGN.md); each wave equals its line-by-line result within fp32 summation order, lengths exactly.
+        return_timestamps: every FastPitch call also launches its spans on the FastPitch stream (ttsamd.timing.PendingTimings, kept with
+        the positions of its rows); they are copied to the host behind the last group's audio -> (waves, timings)."""
         dev = self.device
         if getattr(self, '_pipe_streams', None) is None or self._pipe_streams[0].device != dev:
             self._pipe_streams = tuple(torch.cuda.Stream(dev) for _ in range(3))
@@ -830,6 +940,7 @@ class FastPitch2Wave(nn.Module):
         eng = self.vocoder.engine()
         hop = eng.hop
         out, pending = [], None
+        ts, spans = ({'return_timestamps': True} if return_timestamps else {}), []      # spans: (PendingTimings, the positions of its rows)
         group = max(1, self._VOCODER_GROUP // batch_size)           # chunks per vocoder call
         n_in = len(text_input)
         order = list(range(n_in))
@@ -865,19 +976,25 @@ class FastPitch2Wave(nn.Module):
                 if alone:
                     # the batch_size = 1 loop of this group's lines as ONE ragged FastPitch call whose rows are computed as if alone
                     # (ttsamd_fastpitch_set_batch_mode 1); the mel batch and its lengths go to the vocoder as they are
-                    mel_b, lens_d = self.model.ttmel_lines_alone([text_input[p] for p in pos], _take(speed, pos), _take(speaker_id, pos),
-                                                                 vowelizer, pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos))
+                    mel_b, lens_d, *sp = self.model.ttmel_lines_alone([text_input[p] for p in pos], _take(speed, pos), _take(speaker_id, pos),
+                                                                      vowelizer, pitch_mul=_take(pitch_mul, pos), pitch_add=_take(pitch_add, pos),
+                                                                      **ts)
+                    spans += [(sp[0], pos)] if sp else []
                     lens = lens_d.cpu().tolist()
                 for ch in ([] if alone else grp):
                     chunk = [text_input[p] for p in ch]
                     if batch_size == 1:
                         mel = self.model.ttmel_single(chunk[0], _at(speed, ch[0]), _at(speaker_id, ch[0]), vowelizer,
-                                                      pitch_mul=_at(pitch_mul, ch[0]), pitch_add=_at(pitch_add, ch[0]))
+                                                      pitch_mul=_at(pitch_mul, ch[0]), pitch_add=_at(pitch_add, ch[0]), **ts)
+                        if return_timestamps:
+                            mel, sp = mel
+                            spans.append((sp, [ch[0]]))
                         mels.append(mel)
                         lens.append(int(mel.shape[-1]))
                     else:
-                        mel, dec_lens, rev = self.model._ttmel_batch_padded(chunk, _take(speed, ch), _take(speaker_id, ch), vowelizer,
-                                                                            _take(pitch_mul, ch), _take(pitch_add, ch), alone=mixed)
+                        mel, dec_lens, rev, *sp = self.model._ttmel_batch_padded(chunk, _take(speed, ch), _take(speaker_id, ch), vowelizer,
+                                                                                 _take(pitch_mul, ch), _take(pitch_add, ch), alone=mixed, **ts)
+                        spans += [(sp[0], [ch[j] for j in rev.argsort().tolist()])] if sp else []      # row i of the padded batch is line sort_ids[i]
                         dl = dec_lens.cpu().tolist()                # (FastPitch has synchronised on these lengths already)
                         for j in rev.tolist():
                             mels.append(mel[j, :, :dl[j]])
@@ -917,9 +1034,13 @@ class FastPitch2Wave(nn.Module):
             flush(pending)
         cur.wait_stream(s_hg)
         cur.wait_stream(s_cp)
+        timings = [None] * n_in
+        for sp, rows in spans:                                      # s_hg has waited for every FastPitch call, and `cur` for s_hg
+            for p, t in zip(rows, sp.resolve()):
+                timings[order[p]] = t
         if alone_ok:                                                # back to the order of the input
             res = [None] * n_in
             for pos, w in enumerate(out):
                 res[order[pos]] = w
-            return res
-        return out
+            out = res
+        return (out, timings) if return_timestamps else out

@@ -145,46 +145,94 @@ class Tacotron2(Tacotron2MS):
             return text.arabic_to_tokens(utterance)
         return text.buckwalter_to_tokens(utterance)
 
-    def _tokens_for(self, utterance, vowelizer, postprocess_mel):
-        """tokens (+ the extra separator before the EOS tokens when the ending needs the cut)"""
-        tokens = self._tokenize(utterance, vowelizer=vowelizer)
+    def _tokens_for(self, utterance, vowelizer, postprocess_mel, with_words=False):
+        """tokens (+ the extra separator before the EOS tokens when the ending needs the cut); with_words: a third result, the line's
+        words as text.line_words groups them (of the line the tokeniser saw)"""
+        if with_words:                                                   # _tokenize's two steps, one pass of the phonetiser for tokens and words
+            tokens, words = text.tokens_and_words(self._vowelize(utterance, vowelizer), self.arabic_in)
+        else:
+            tokens = self._tokenize(utterance, vowelizer=vowelizer)
         process_mel = False
         if postprocess_mel and needs_postprocessing(tokens[-self.n_eos - 1]):
             tokens.insert(-self.n_eos, SEPARATOR_TOKEN)
             process_mel = True
-        return tokens, process_mel
+        return (tokens, process_mel, words) if with_words else (tokens, process_mel)
+
+    # ---- timestamps (not in the reference; ttsamd.timing, csrc/timing.hip) ----
+    sample_rate, hop = 22050, 256           # of the mel: one frame is `hop` samples of the vocoder's wave
+
+    @staticmethod
+    def attention_durations(alignments, in_lens, out_lens):
+        """The frames every token got: the monotonic path through the decoder's attention, ttsamd.engine.mas on log(max(alignments, tiny))
+        -- the clamp and the log taken on the device, so that an exact zero puts no -inf into the search.  alignments [B, T, L] on the
+        device -> (dur fp32 [B, L], the log-attention tensor the search ran on)."""
+        from ttsamd.engine import mas
+        log_attn = torch.log(torch.clamp(alignments.float(), min=torch.finfo(torch.float32).tiny)).contiguous()
+        dur, _ = mas(log_attn, in_lens, out_lens, is_log=True, return_hard=False)
+        return dur, log_attn
+
+    def _pending_timings(self, token_rows, word_rows, alignments, in_lens, out_lens, shapes, launch=True):
+        """the spans of the rows of one infer call (ttsamd.timing.PendingTimings: resolve() is the one copy).  shapes: per row (n_end or
+        None, n_t, n_t_new): where truncate_mel cut the mel, and the frame counts in front of and behind resize_mel.  A position is
+        clamped to n_end hop (the three replicated closing frames belong to no token) and counted at n_t_new / n_t of the rate: the
+        sampling grid of the resize, without bicubic's half-pixel offset -- a choice."""
+        from ttsamd.timing import PendingTimings
+        dev = alignments.device
+        dur, _ = self.attention_durations(alignments, torch.as_tensor(in_lens), torch.as_tensor(out_lens))
+        maps = torch.tensor([(0, (1 << 63) - 1 if n_end is None else n_end * self.hop, 0, max(n_new, 1), max(n_t, 1))
+                             for n_end, n_t, n_new in shapes], dtype=torch.int64).to(dev)
+        # launch=False (tts_long): held back until the join's map is known; it then comes on top of these in a second launch
+        return PendingTimings(token_rows, word_rows, dur.round().to(torch.int64), self.hop, self.sample_rate, row_maps=maps, launch=launch)
 
     @torch.inference_mode()
     def ttmel_single(self, utterance: str, speaker_id: int = 0, speed: Union[int, float, None] = None,
-                     vowelizer=None, postprocess_mel: bool = True):
-        tokens, process_mel = self._tokens_for(utterance, vowelizer, postprocess_mel)
+                     vowelizer=None, postprocess_mel: bool = True, return_timestamps=False):
+        """return_timestamps (not in the reference): -> (mel, PendingTimings of the one row)"""
+        tokens, process_mel, *words = self._tokens_for(utterance, vowelizer, postprocess_mel, **({'with_words': True} if return_timestamps else {}))
         ids_batch = torch.LongTensor(text.tokens_to_ids(tokens, self.phon_to_id)).unsqueeze(0)
         sid = torch.LongTensor([speaker_id])
         mel_spec, _, alignments = self.infer(ids_batch, sid)
         mel_spec = mel_spec[0]
+        n_end = None
         if process_mel:
             mel_spec = truncate_mel(mel_spec, alignments[0, :, -self.n_eos - 1])
+            n_end = int(mel_spec.shape[-1]) - 3
+        n_t = int(mel_spec.shape[-1])
         if speed is not None:
             mel_spec = resize_mel(mel_spec, rate=speed)
+        if return_timestamps:
+            return mel_spec, self._pending_timings([tokens], words, alignments, [len(tokens)], [alignments.shape[1]],
+                                                   [(n_end, n_t, int(mel_spec.shape[-1]))])
         return mel_spec                                                  # [80, T]
 
     @torch.inference_mode()
     def ttmel_batch(self, batch: List[str], speaker_id: int = 0, speed: Union[int, float, None] = None,
-                    vowelizer=None, postprocess_mel: bool = True):
-        prepared = [self._tokens_for(line, vowelizer, postprocess_mel) for line in batch]
-        batch_ids = [torch.LongTensor(text.tokens_to_ids(tokens, self.phon_to_id)) for tokens, _ in prepared]
+                    vowelizer=None, postprocess_mel: bool = True, return_timestamps=False, _launch_spans=True):
+        """return_timestamps (not in the reference): -> (mels, PendingTimings of the rows in the order of `batch`; _launch_spans=False: not
+        launched yet, for tts_long, whose maps come with the join)"""
+        prepared = [self._tokens_for(line, vowelizer, postprocess_mel, **({'with_words': True} if return_timestamps else {})) for line in batch]
+        batch_ids = [torch.LongTensor(text.tokens_to_ids(p[0], self.phon_to_id)) for p in prepared]
         ids_pad, lens_sorted, reverse_ids = text_collate_fn(batch_ids)
         sids = lens_sorted * 0 + speaker_id
         mel_post, mel_lens, alignments = self.infer(ids_pad, sids, lens_sorted)
         mel_lens, in_lens = mel_lens.tolist(), lens_sorted.tolist()
-        mel_list = []
+        mel_list, shapes = [], []
         for i, j in enumerate(reverse_ids.tolist()):
             mel = mel_post[j, :, :mel_lens[j]]
+            n_end = None
             if prepared[i][1]:
                 mel = truncate_mel(mel, alignments[j, :mel_lens[j], in_lens[j] - self.n_eos - 1])
+                n_end = int(mel.shape[-1]) - 3
+            n_t = int(mel.shape[-1])
             if speed is not None:
                 mel = resize_mel(mel, rate=speed)
+            shapes.append((n_end, n_t, int(mel.shape[-1])))
             mel_list.append(mel)
+        if return_timestamps:
+            rows = reverse_ids.tolist()                                  # line i is row rows[i] of the padded batch
+            return mel_list, self._pending_timings([p[0] for p in prepared], [p[2] for p in prepared], alignments.index_select(
+                0, reverse_ids.to(alignments.device)), [in_lens[j] for j in rows], [mel_lens[j] for j in rows], shapes,
+                launch=_launch_spans)
         return mel_list
 
     def ttmel(self, text_input: Union[str, List[str]], speaker_id: int = 0, speed: Union[int, float, None] = None,
@@ -244,28 +292,39 @@ class Tacotron2Wave(nn.Module):
     @torch.inference_mode()
     def tts_single(self, text_input: str, speed: Union[int, float, None] = None, speaker_id: int = 0,
                    denoise: float = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False, normalize=None,
-                   limiter=False, true_peak=False):
+                   limiter=False, true_peak=False, return_timestamps=False):
+        """return_timestamps (not in the reference): the result ends with the line's timing (ttsamd.timing), as FastPitch2Wave.tts
+        describes it; the durations are the monotonic path through the decoder's attention (Tacotron2.attention_durations), cut where
+        truncate_mel cut and scaled where resize_mel stretched."""
         check_normalize(normalize, 1)
         limiter = check_limiter(limiter, normalize)
         check_true_peak(true_peak, normalize, limiter)
-        mel_spec = self.model.ttmel_single(text_input, speaker_id, speed, vowelizer, postprocess_mel)
+        mel_spec = self.model.ttmel_single(text_input, speaker_id, speed, vowelizer, postprocess_mel,
+                                           **({'return_timestamps': True} if return_timestamps else {}))
+        if return_timestamps:
+            mel_spec, spans = mel_spec
         wave = self.vocoder(mel_spec)
         if denoise > 0:
             wave = self.denoiser(wave, denoise)
         if normalize is not None:
             wave = level_waves(wave, None, normalize, self.sample_rate, **_lim(limiter, normalize, true_peak))
-        if return_mel:
-            return wave[0].cpu(), mel_spec
-        return wave[0].cpu()
+        out = (wave[0].cpu(), mel_spec) if return_mel else (wave[0].cpu(),)
+        if return_timestamps:
+            out += (spans.resolve()[0],)              # the one small copy, behind the wave's own
+        return out[0] if len(out) == 1 else out
 
     @torch.inference_mode()
     def tts_batch(self, batch: List[str], speed: Union[int, float, None] = None, denoise: float = 0,
                   speaker_id: int = 0, vowelizer=None, postprocess_mel: bool = True, return_mel: bool = False, normalize=None,
-                  limiter=False, true_peak=False):
+                  limiter=False, true_peak=False, return_timestamps=False):
+        """return_timestamps (not in the reference): -> (waves, timings), timing i of line i (one more small copy for the batch)"""
         check_normalize(normalize, len(batch))
         limiter = check_limiter(limiter, normalize)
         check_true_peak(true_peak, normalize, limiter)
-        mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel)
+        mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel,
+                                          **({'return_timestamps': True} if return_timestamps else {}))
+        if return_timestamps:
+            mel_list, spans = mel_list
         eng = self.vocoder.engine()
         lens_host = [m.shape[-1] for m in mel_list]
         lens = torch.tensor(lens_host, dtype=torch.int64, device=mel_list[0].device)
@@ -280,12 +339,17 @@ class Tacotron2Wave(nn.Module):
             wave = level_waves(wave, lens * eng.hop, normalize, self.sample_rate, **_lim(limiter, normalize, true_peak))    # on the device, after the denoiser
         # one exact-size D2H per utterance (a padded [B, n_max] copy + per-row clones touches every host page twice)
         # NB the reference silently ignores return_mel here (:348-351); so do we
-        return [wave[i, :n[i]].cpu() for i in range(len(mel_list))]
+        waves = [wave[i, :n[i]].cpu() for i in range(len(mel_list))]
+        return (waves, spans.resolve()) if return_timestamps else waves
 
-    def _tts_batch_device(self, batch, speed, denoise, speaker_id, vowelizer, postprocess_mel):
+    def _tts_batch_device(self, batch, speed, denoise, speaker_id, vowelizer, postprocess_mel, spans=None):
         """tts_batch up to the denoiser, without the copies to the host: (wave [B, n_max] fp32, samples int64 [B]), both on the device,
-        rows in the order of `batch`.  What tts_long joins."""
-        mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel)
+        rows in the order of `batch`.  What tts_long joins.  spans: a list that gets the rows' PendingTimings, not launched yet."""
+        mel_list = self.model.ttmel_batch(batch, speaker_id, speed, vowelizer, postprocess_mel,
+                                          **({'return_timestamps': True, '_launch_spans': False} if spans is not None else {}))
+        if spans is not None:
+            mel_list, sp = mel_list
+            spans.append(sp)
         eng = self.vocoder.engine()
         lens_host = [m.shape[-1] for m in mel_list]
         lens = torch.tensor(lens_host, dtype=torch.int64, device=mel_list[0].device)
@@ -300,8 +364,12 @@ class Tacotron2Wave(nn.Module):
     @torch.inference_mode()
     def tts_long(self, text_input: Union[str, List[str]], speed: Union[int, float, None] = None, denoise: float = 0.005, speaker_id: int = 0,
                  batch_size: int = 32, vowelizer=None, postprocess_mel: bool = True, pauses=None, max_chars: int = 200, trim_db=40.0,
-                 keep_ms: float = 10.0, fade_ms: float = 5.0, normalize=None, limiter=False, true_peak=False, return_segments: bool = False):
-        """A paragraph -> ONE wave (CPU tensor [n_samples]), as FastPitch2Wave.tts_long: the text (a string, or a list of strings taken as
+                 keep_ms: float = 10.0, fade_ms: float = 5.0, normalize=None, limiter=False, true_peak=False, return_segments: bool = False,
+                 return_timestamps: bool = False):
+        """return_timestamps: the result ends with the paragraph's timing, positions in the JOINED wave, as FastPitch2Wave.tts_long hands
+        it out: a segment's marks are first put into its own wave (the end-of-utterance cut, the ratio of a `speed`), then clamped to
+        what the trim kept and moved to its place -- two launches per group, because the two maps do not compose into one.
+        A paragraph -> ONE wave (CPU tensor [n_samples]), as FastPitch2Wave.tts_long: the text (a string, or a list of strings taken as
         paragraphs) is cut by text.split_text, the segments -- each said without the marks that close it, text.spoken_text -- go through
         the batch path in groups of batch_size (the rows of a group are decoded together, as tts_batch decodes them), and on the device every row is cut to its speech bounds (trim_db, keep_ms),
         faded over fade_ms and joined with the pause of its boundary (`pauses` in ms over paragraph 700, sentence 350, clause 250,
@@ -318,11 +386,14 @@ class Tacotron2Wave(nn.Module):
         limiter = check_limiter(limiter, normalize)
         check_true_peak(true_peak, normalize, limiter)
         batch_size = max(int(batch_size), 1)
-        groups = [self._tts_batch_device(lines[k:k + batch_size], speed, denoise, speaker_id, vowelizer, postprocess_mel)
+        spans = [] if return_timestamps else None
+        groups = [self._tts_batch_device(lines[k:k + batch_size], speed, denoise, speaker_id, vowelizer, postprocess_mel,
+                                         **({'spans': spans} if return_timestamps else {}))
                   for k in range(0, len(lines), batch_size)]
-        wave, rows = join_paragraph(groups, pieces, table, trim_db, keep_ms, fade_ms, self.sample_rate, _trimmer(groups[0][0].device), normalize,
-                                    limiter, true_peak)
-        return (wave, rows) if return_segments else wave
+        wave, rows, *timing = join_paragraph(groups, pieces, table, trim_db, keep_ms, fade_ms, self.sample_rate, _trimmer(groups[0][0].device),
+                                             normalize, limiter, true_peak, **({'spans': spans} if return_timestamps else {}))
+        out = ((wave, rows) if return_segments else (wave,)) + tuple(timing)
+        return out[0] if len(out) == 1 else out
 
     def _streamer(self, chunk_frames, first_chunk_frames, pcm16, max_streams, max_frames, sample_rate, encoding, limiter, true_peak):
         """the StreamingVocoder of this model for these settings (its pool and buffers are allocated once and kept)"""
@@ -343,7 +414,7 @@ class Tacotron2Wave(nn.Module):
     def tts_stream(self, text_input: Union[str, List[str]], chunk_frames: int = 64, first_chunk_frames: int = 32, pcm16: bool = False,
                    denoise: float = 0.005, speaker_id: int = 0, batch_size: int = 8, vowelizer=None, postprocess_mel: bool = True,
                    sample_rate=None, encoding=None, gain_db=0.0, limiter=False, true_peak=False, max_frames: int = 4096,
-                   speed: Union[int, float, None] = None, meter=False):
+                   speed: Union[int, float, None] = None, meter=False, marks=False):
         """`tts` that hands out audio while the decoder is still running (a generator; one at a time per model).  Tacotron2 makes its
         mel frame by frame: the decoder runs in advances (Tacotron2Engine.stream), the postnet over windows of the frames that are
         final, and every row of the batch is a growing stream of the chunked vocoder (StreamingVocoder.open_growing).
@@ -360,7 +431,7 @@ class Tacotron2Wave(nn.Module):
         cut and the three repeated frames, so the streamed mel is truncate_mel's frame for frame.  How early audio leaves a row with
         a cut depends on how far the bound runs behind the decoder on the checkpoint (cut_bound).
         pcm16, sample_rate, encoding, gain_db (a scalar, or one value per line), limiter, true_peak: as FastPitch2Wave.tts_stream.
-        speed other than None / 1 (resize_mel needs the total length) and meter are ValueErrors; there is no peak normalisation (it
+        speed other than None / 1 (resize_mel needs the total length), meter and marks are ValueErrors; there is no peak normalisation (it
         needs the whole wave).  Tacotron2.dropout_seed applies per batch as in `infer`.  `stream_sessions` maps each line to the
         decoder session of its batch (its steps_done / ended at the time of a yield)."""
         from ttsamd.engine import check_finite, check_true_peak, limiter_spec, row_values
@@ -370,6 +441,9 @@ class Tacotron2Wave(nn.Module):
             raise ValueError('tts_stream: speed is not supported in the stream (resize_mel needs the total length): use tts')
         if meter:
             raise ValueError('tts_stream: meter is not supported for Tacotron2 streams')
+        if marks:
+            raise ValueError('tts_stream: marks are not supported for Tacotron2 streams (the attention path is known only at the end '
+                             'of the utterance): use tts(..., return_timestamps=True)')
         limiter = limiter_spec(limiter)
         check_true_peak(true_peak, None, limiter)
         single = isinstance(text_input, str)
@@ -450,7 +524,8 @@ class Tacotron2Wave(nn.Module):
 
     def tts(self, text_buckw: Union[str, List[str]], speed: Union[int, float, None] = None, denoise: float = 0.005,
             speaker_id: int = 0, batch_size: int = 8, vowelizer=None, postprocess_mel: bool = True,
-            return_mel: bool = False, normalize=None, limiter=False, true_peak=False) -> Union[torch.Tensor, List[torch.Tensor]]:
+            return_mel: bool = False, normalize=None, limiter=False, true_peak=False,
+            return_timestamps: bool = False) -> Union[torch.Tensor, List[torch.Tensor]]:
         """Same contract as the reference (:353-426): str -> Tensor[n_samples] (CPU); list -> list of
         tensors, chunked by `batch_size`.
         normalize (not in the reference): the level of every wave, set on the device after the denoiser -- None, 'peak' (x / max|x| *
@@ -458,9 +533,11 @@ class Tacotron2Wave(nn.Module):
         FastPitch2Wave.tts takes it).
         limiter (False, True or a dict with any of ceiling, attack_ms, hold_ms, max_gain_db; needs a normalize): the lines with 'lufs' or
         a target get the full gain towards it and the look-ahead limiter holds their peaks at the ceiling (as FastPitch2Wave.tts).
-        true_peak (False or True; needs a normalize): the peaks of both are true peaks (utils.audio.true_peak), as FastPitch2Wave.tts."""
+        true_peak (False or True; needs a normalize): the peaks of both are true peaks (utils.audio.true_peak), as FastPitch2Wave.tts.
+        return_timestamps (not in the reference): (wave, timing) for a string, (waves, timings) for a list, as FastPitch2Wave.tts
+        hands them out; Tacotron2 has no durations of its own, so they are the monotonic path through its attention (tts_single)."""
         kw = dict(speaker_id=speaker_id, speed=speed, denoise=denoise, vowelizer=vowelizer,
-                  postprocess_mel=postprocess_mel, return_mel=return_mel)
+                  postprocess_mel=postprocess_mel, return_mel=return_mel, **({'return_timestamps': True} if return_timestamps else {}))
         if isinstance(text_buckw, str):
             return self.tts_single(text_buckw, normalize=normalize, **kw, **({'limiter': limiter} if limiter else {}),
                                    **({'true_peak': true_peak} if true_peak else {}))
@@ -470,10 +547,17 @@ class Tacotron2Wave(nn.Module):
         check_true_peak(true_peak, normalize, limiter)
         at = (lambda i: normalize[i]) if per_row(normalize) else (lambda i: normalize)
         if batch_size == 1:
-            return [self.tts_single(sample, normalize=at(i), **kw, **_lim(limiter, at(i), true_peak)) for i, sample in enumerate(text_buckw)]
-        wav_list = []
+            res = [self.tts_single(sample, normalize=at(i), **kw, **_lim(limiter, at(i), true_peak)) for i, sample in enumerate(text_buckw)]
+            if return_timestamps:                   # (wave, [mel,] timing) per line -> (the list as without the flag, the timings)
+                return [r[0] if len(r) == 2 else r[:-1] for r in res], [r[-1] for r in res]
+            return res
+        wav_list, timings = [], []
         for k in range(0, len(text_buckw), batch_size):
             idx = range(k, min(k + batch_size, len(text_buckw)))
             chunk_norm = [at(i) for i in idx] if per_row(normalize) else normalize
-            wav_list += self.tts_batch(text_buckw[k:k + batch_size], normalize=chunk_norm, **kw, **_lim(limiter, chunk_norm, true_peak))
-        return wav_list
+            got = self.tts_batch(text_buckw[k:k + batch_size], normalize=chunk_norm, **kw, **_lim(limiter, chunk_norm, true_peak))
+            if return_timestamps:
+                got, more = got
+                timings += more
+            wav_list += got
+        return (wav_list, timings) if return_timestamps else wav_list

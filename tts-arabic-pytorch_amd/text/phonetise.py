@@ -193,6 +193,58 @@ def phonetise_word(word):
     return _tidy([p for p in (_first(e) for e in entries) if p != ''])
 
 
+def word_groups(line, to_buckwalter=True):
+    """The words of a line as process_utterance groups them, in the line's own spelling: [(text, phones)], one entry per group that
+    process_utterance joins with ' + ', in order; phones: the group's phones as process_utterance has them ([] for `-` / `sil` and for a
+    piece the phonetiser gets nothing from), so ' + '.join(' '.join(phones)) over the groups is process_utterance's string up to the
+    `sil` it writes for a pause, which phonemes_to_tokens drops.  It walks the tokeniser's own steps: the rewrites of _normalise (all but the last keep
+    every space, so the pieces between single spaces stay aligned with the line's), the last rewrite's cut in front of a . , ? ! that
+    follows a character, the split at spaces, then process_utterance's loop -- `-` and `sil` open a group without phones, a piece that is
+    exactly one mark joins the group in front of it (or opens one when there is none), anything else opens a group, with or without
+    phones.  The rewrites neither add nor drop a mark, so the n-th mark of a rewritten piece is the n-th mark of the typed piece, which
+    is where the typed piece is cut.  Pieces of one typed piece are joined as typed, pieces of different ones with a space.
+    to_buckwalter: the line goes through arabic_to_buckwalter first, as arabic_to_tokens does."""
+    norm = arabic_to_buckwalter(line) if to_buckwalter else line
+    for pat, rep in _REWRITES[:-1]:
+        norm = norm.replace(pat, rep) if isinstance(pat, str) else pat.sub(rep, norm)
+    raw, pieces = line.split(' '), norm.split(' ')
+    assert len(raw) == len(pieces), (line, norm)
+    cut_pat, cut_rep = _REWRITES[-1]
+    groups = []                                        # [[(typed piece index, text), ...], phones]
+    for k, (typed, piece) in enumerate(zip(raw, pieces)):
+        if piece not in ('-', 'sil') and not any(mark in piece for mark in _PUNCT):        # the common case: a plain word, nothing to cut
+            groups.append([[(k, typed)], list(phonetise_word(piece))])
+            continue
+        cuts = {sum(ch in _PUNCT for ch in piece[:m.start(2)]) for m in cut_pat.finditer(piece)}     # which marks get a space in front
+        parts, start, seen = [], 0, 0
+        for i, ch in enumerate(typed):
+            if ch in _PUNCT:
+                if seen in cuts:
+                    parts.append(typed[start:i])
+                    start = i
+                seen += 1
+        parts.append(typed[start:])
+        subs = cut_pat.sub(cut_rep, piece).split(' ')
+        assert len(parts) == len(subs), (typed, piece)
+        for part, sub in zip(parts, subs):
+            if sub in ('-', 'sil'):
+                groups.append([[(k, part)], []])
+                continue
+            ph = phonetise_word(sub)
+            if isinstance(ph, str) and groups:
+                groups[-1][0].append((k, part))
+                groups[-1][1] = groups[-1][1] + [ph]
+            else:
+                groups.append([[(k, part)], list(ph)])
+    out = []
+    for parts, phones in groups:
+        text = ''
+        for j, (k, part) in enumerate(parts):
+            text += (' ' if j and parts[j - 1][0] != k else '') + part
+        out.append((text, phones))
+    return out
+
+
 def process_utterance(utterance):
     words = []
     for word in _normalise(utterance):

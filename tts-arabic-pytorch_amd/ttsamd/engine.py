@@ -288,7 +288,7 @@ class FastPitchEngine:
         return mel
 
     def infer(self, ids, pace=1.0, dur_tgt=None, pitch_tgt=None, energy_tgt=None, pitch_mul=1.0, pitch_add=0.0,
-              max_duration=75, speaker=0, return_idx=False, lens_hook=None, alone=False):
+              max_duration=75, speaker=0, return_idx=False, lens_hook=None, alone=False, return_reps=False):
         """Same contract as FastPitch.infer (model.py:351-353) with pitch_transform restricted to
         the affine pitch_trf the reference wrappers install (networks.py:38-42,121-122).
         ids int64 [B,L] zero-padded at the end.  Returns (mel [B,80,T_max], dec_lens int64 [B],
@@ -301,7 +301,8 @@ class FastPitchEngine:
         on the host (length B, speaker in range, pace finite and > 0: ValueError / IndexError) before they are uploaded.  With any
         per-row control the call runs ttsamd_fastpitch_encode_rows / _decode_rows -- row b's bits are those of the scalar call with row
         b's values -- and `alone` goes down as the per-call flag: the handle's mode is left alone.  All scalars: the route above.
-        The two phases are `encode` and `decode`; between them the one host read and the length regulator."""
+        The two phases are `encode` and `decode`; between them the one host read and the length regulator.
+        `return_reps`: the tuple ends with reps int64 [B, L] in HBM, the frames every token got (no launch, no copy more)."""
         dev = self.device
         ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int64).contiguous()
         B, Lt = ids.shape
@@ -333,7 +334,8 @@ class FastPitchEngine:
             mel = mel[:, :, :t_max0]
             idx = None if idx is None else idx[:, :t_max0]
         out = (mel, dec_lens, dur_pred, pitch_pred, energy_pred)
-        return out + (idx,) if return_idx else out
+        out = out + (idx,) if return_idx else out
+        return out + (reps,) if return_reps else out        # reps int64 [B, L]: what ttsamd.timing turns into timestamps; last in the tuple
 
 
 class DenoiserEngine:

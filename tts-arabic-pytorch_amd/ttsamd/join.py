@@ -47,12 +47,13 @@ def pause_table(pauses, fade_ms):
     return table
 
 
-def join_rows(wave, lens, gaps, bounds=None, keep=0, lead=0, fade=None):
+def join_rows(wave, lens, gaps, bounds=None, keep=0, lead=0, fade=None, return_device_table=False):
     """wave [B, n_max] fp32 on the device, lens int64 [B] (None: whole rows), gaps: B host integers (samples behind each row; negative:
     overlap with the next row), bounds int64 [B, 2] on the device (TrimEngine.bounds) or None, keep / lead in samples, fade: a rising
     table (numpy / tensor, at most 4096 entries) or None -> (out [1, N] fp32 on the device, segs int64 [B, 4] on the host =
     (out_start, out_end, src_start, src_end) per row).  `out` is cut from a buffer sized by a host-side upper bound (lead + B n_max +
-    the positive gaps); the only read-back is total and segs, 8 (4 B + 1) bytes in one copy."""
+    the positive gaps); the only read-back is total and segs, 8 (4 B + 1) bytes in one copy.  return_device_table: a third result, segs
+    as int64 [B, 4] still on the device (the table the read-back copies), for work that goes on there: tts_long's timestamps."""
     lib = _require_gpu()
     wave = _dev_f32(wave, 2, 'join_rows: wave')
     B, n_max = wave.shape
@@ -83,10 +84,20 @@ def join_rows(wave, lens, gaps, bounds=None, keep=0, lead=0, fade=None):
     with torch.cuda.device(dev):
         L.check(lib.ttsamd_wave_join(_ptr(wave), n_max, _ptr(lens), _ptr(bounds), _ptr(gap_d), B, _ptr(fade), F, keep, lead, _ptr(out),
                                      width, _ptr(table), _ptr(table[4 * B:]), _stream()), 'wave_join')
-    table = table.cpu()
+    table_d, table = table, table.cpu()
     total = int(table[4 * B])
     assert 0 <= total <= width, (total, width)
+    if return_device_table:
+        return out[:, :total], table[:4 * B].reshape(B, 4), table_d[:4 * B].view(B, 4)
     return out[:, :total], table[:4 * B].reshape(B, 4)
+
+
+def span_maps(table):
+    """join_rows' device table int64 [B, 4] = (out_start, out_end, src_start, src_end) -> token_spans' maps int64 [B, 5] on the device:
+    (lo, hi, off, num, den) = (src_start, src_end, out_start, 1, 1): a position of the row's own wave, clamped to what the trim kept
+    and moved to its place in the joined wave"""
+    one = torch.ones_like(table[:, 0])
+    return torch.stack([table[:, 2], table[:, 3], table[:, 0], one, one], dim=1).contiguous()
 
 
 def paragraph_pieces(text_input, max_chars):
@@ -107,10 +118,14 @@ def paragraph_pieces(text_input, max_chars):
     return pieces, lines
 
 
-def join_paragraph(groups, pieces, pauses, trim_db, keep_ms, fade_ms, sample_rate, trimmer, normalize=None, limiter=None, true_peak=False):
+def join_paragraph(groups, pieces, pauses, trim_db, keep_ms, fade_ms, sample_rate, trimmer, normalize=None, limiter=None, true_peak=False,
+                   spans=None):
     """What the two `tts_long` share behind the vocoder: groups = [(wave [b, w] on the device, samples int64 [b] on the device), ...] in
     the order of `pieces` -> the rows in one padded buffer, their trim bounds (trim_db None: whole rows), the join, the level of the
-    JOINED wave as one row (level_waves: one gain for the paragraph), one copy to the host.  -> (wave [N] on the host, segment dicts)."""
+    JOINED wave as one row (level_waves: one gain for the paragraph), one copy to the host.  -> (wave [N] on the host, segment dicts).
+    spans: one ttsamd.timing.PendingTimings per group, not launched yet: each is launched behind the join with its rows of the join
+    table as maps (span_maps: clamped to what the trim kept, moved to the segment's place) and copied behind the wave -> a third result,
+    the timing of the paragraph (positions in the joined wave; every word carries the index of its segment)."""
     from .engine import level_waves
     dev = groups[0][0].device
     width = max(int(w.shape[1]) for w, _ in groups)
@@ -125,10 +140,19 @@ def join_paragraph(groups, pieces, pauses, trim_db, keep_ms, fade_ms, sample_rat
     if trim_db is not None:
         bounds, _ = trimmer.bounds(buf, lens, float(trim_db), 1024, 256, gain=0.0)
     gaps = gaps_for([b for _, b in pieces], pauses, sample_rate)
-    out, segs = join_rows(buf, lens, gaps, bounds, keep=ms_to_samples(keep_ms, sample_rate), fade=fade_table(ms_to_samples(fade_ms, sample_rate)))
+    out, segs, *table = join_rows(buf, lens, gaps, bounds, keep=ms_to_samples(keep_ms, sample_rate),
+                                  fade=fade_table(ms_to_samples(fade_ms, sample_rate)), **({'return_device_table': True} if spans else {}))
+    k = 0
+    for sp in spans or []:
+        b = len(sp.token_rows)
+        sp.launch(span_maps(table[0][k:k + b]), segments=list(range(k, k + b)))
+        k += b
     if normalize is not None and out.shape[1]:
         out = level_waves(out, None, normalize, sample_rate, **({'limiter': limiter} if limiter else {}),
                           **({'true_peak': True} if true_peak else {}))
+    if spans:
+        from .timing import merge_timings
+        return out[0].cpu(), segment_rows(pieces, segs), merge_timings([t for sp in spans for t in sp.resolve()])
     return out[0].cpu(), segment_rows(pieces, segs)
 
 

@@ -158,6 +158,9 @@ SYMBOLS = {
     # paragraph join (csrc/join.hip): wave, wave_stride, nsamples, bounds (or NULL), gap, B, fade, F, keep, lead, out, out_stride, segs
     # (int64 [B][4]), total (int64 [1]), stream
     'ttsamd_wave_join': (_I32, [_P, _I64, _P, _P, _P, _I32, _P, _I32, _I64, _I64, _P, _I64, _P, _P, _P]),
+    # token and word spans (csrc/timing.hip): reps, reps_stride, n_tokens (or NULL), B, L, groups (int32 [B][G][2] or NULL), n_groups (or
+    # NULL), G, hop, map (int64 [B][5] or NULL), tok (int64 [B][L][2]), grp (int64 [B][G][2] or NULL), stream
+    'ttsamd_token_spans': (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _I32, _I64, _P, _P, _P, _P]),
     # output levelling (csrc/loudness.hip): the coefficients go to a HOST float64 [10] and need no GPU
     'ttsamd_loudness_coefficients': (_I32, [_I32, C.POINTER(C.c_double)]),
     'ttsamd_loudness_workspace_bytes': (_I64, [_I32, _I64, _I32]),
